@@ -4,6 +4,7 @@
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the rows of the last timed step as DIR/*.npy
 
 One "step" = one pass of the hot path over one batch: 1024 single-term BM25 queries (BASELINE.json configs[1],
 SURVEY.md §8(d)) PLANNED (term ids -> term states, BM25 weights: the native batch planner behind the C ABI) and evaluated
@@ -234,6 +235,31 @@ def final_line(full, detail_path="bench_detail.json"):
     return text
 
 
+DUMP_MAX_BYTES = 64 << 20
+SEED_DUMP_SAMPLE = 0x527563656E65 ^ 0xD0  # "Rucene" ^ purpose tag
+
+
+def dump_outputs(out_dir, hits, totals):
+    """--dump-outputs: what a caller of the timed path receives, so that two builds can be compared output for output —
+    hits (n_queries x k rgpu_hit {i32 doc, f32 score}, best first, unused slots {-1, 0}) and totals (n_queries exact hit counts).
+    Written as doc.npy (float64: every i32 exactly), score.npy (float32: the bits the kernel wrote), total_hits.npy (float64) and
+    query.npy (float64: the batch row each written row is). At most DUMP_MAX_BYTES in all: a larger batch is cut to a fixed,
+    seeded sample of its rows, in batch order. Returns {name: shape}."""
+    hits = np.asarray(hits).view(np.dtype([("doc", "<i4"), ("score", "<f4")])).reshape(len(totals), -1)
+    totals = np.asarray(totals, dtype=np.int64)
+    n, k = hits.shape
+    row_bytes = 8 * k + 4 * k + 8 + 8
+    rows = np.arange(n)
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(SEED_DUMP_SAMPLE).choice(n, DUMP_MAX_BYTES // row_bytes, replace=False))
+    arrays = {"doc": hits["doc"][rows].astype(np.float64), "score": hits["score"][rows].astype(np.float32),
+              "total_hits": totals[rows].astype(np.float64), "query": rows.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: a.shape for name, a in arrays.items()}
+
+
 def _jsonable(o):
     if isinstance(o, dict):
         return {str(k): _jsonable(v) for k, v in o.items() if not str(k).startswith("_")}
@@ -265,7 +291,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--force-dist", action="store_true",
                     help="developer check: take the N > 1 code path (RCCL all-gather + device merge) with a world of one")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the rows the headline's timed path returned in its last step as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.regions < 1:
+        ap.error("--steps and --regions must be >= 1, --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -444,20 +474,25 @@ def main():
             torch.cuda.synchronize()
             fused_same = bool(torch.equal(a.hits, b.hits)) and bool(torch.equal(a.totals, b.totals))
         res["fused_same_rows_as_two_calls"] = fused_same
-        res["regions"] = {"ms_planned_two_streams": timed(2, "fused"), "ms_planned_one_stream": timed(1, "fused")}
+        # the rows of the last timed step behind each planned figure (timed_region ends in a synchronize): --dump-outputs writes
+        # those of the figure the headline reports
+        res["regions"], res["timed_rows"] = {}, {}
+        for name, n_lanes in (("ms_planned_two_streams", 2), ("ms_planned_one_stream", 1)):
+            res["regions"][name] = timed(n_lanes, "fused")
+            res["timed_rows"][name] = (merged["hits"].clone(), merged["totals"].clone())
         if full:
             res["regions"]["ms_two_calls_two_streams"] = timed(2, "array")
             res["regions"]["ms_two_calls_one_stream"] = timed(1, "array")
             res["regions"]["ms_resident_plan_two_streams"] = timed(2, False)
             res["regions"]["ms_resident_plan_one_stream"] = timed(1, False)
-            res["regions"]["ms_object_planner_one_stream"] = timed(1, "objects", max(3, steps // 4), 3)
+            res["regions"]["ms_object_planner_one_stream"] = timed(1, "objects", steps, 3)
         for name, reg in res["regions"].items():
             res[name] = reg["median"]
         if full and not dist_mode:
-            # ... and the same step for about 2.5 s on end (the regions above are 0.5 ms long each: a GPU-busy sampler never sees them, and
-            # clocks / thermals have no time to settle): the sustained rate next to the median region. One process, so the number of
-            # steps may follow this box's step time.
-            n_sus = int(min(400_000, max(1000, 2500.0 / res["ms_planned_two_streams"])))
+            # ... and the same step back to back in ONE region of `steps` steps, without warm-up or median: the sustained rate next to
+            # the median region. `--steps` sets its length, as it does every timed region's (seconds on end take --steps 100000 or so:
+            # the regions above are 0.5 ms long each at --steps 20, and clocks / thermals have no time to settle in them).
+            n_sus = steps
             gc.collect()
             gc.disable()
             torch.cuda.synchronize()
@@ -728,7 +763,8 @@ def main():
         dom = DOMINANT[kind]
         c = r["counters"]
         kms = r["kernels_ms"].get(dom, 0.0)
-        reg = r["regions"]["ms_planned_two_streams" if two_wins else "ms_planned_one_stream"]
+        reported = "ms_planned_two_streams" if two_wins else "ms_planned_one_stream"
+        reg = r["regions"][reported]
         out = {"workload": WORKLOAD_TEXT[kind], "k": k, "steps": steps, "ms_per_step": ms,
                "ms_per_step_min_median_max": [reg["min"], reg["median"], reg["max"]], "timed_regions": reg["regions"],
                "queries_per_sec": nq / (ms * 1e-3),
@@ -790,6 +826,7 @@ def main():
             out["parity_vs_oracle"] = bool(ok and (info["queries_checked"] == info["queries_in_batch"] or info.get("sampled") is True))
             out["parity"] = info
         out["_res"] = r
+        out["_timed_rows"] = r["timed_rows"][reported]
         return out
 
     def decode_bench(shard, reps, tag):
@@ -1060,6 +1097,7 @@ def main():
 
     def strip(c):
         c.pop("_res", None)
+        c.pop("_timed_rows", None)
         return c
 
     # ---- headline: BASELINE configs[1] (or --workload), one 10M-doc shard per rank -----------------------------------------
@@ -1067,6 +1105,10 @@ def main():
     head = search_config(shard, args.workload, args.steps, args.warmup, True, "%s_%s" % (ROUND, args.workload), 8.0, nq, nq)
     res = head["_res"]
     ms_per_step = head["ms_per_step"]
+    if args.dump_outputs and rank == 0:
+        hits, totals = head["_timed_rows"]
+        shapes = dump_outputs(args.dump_outputs, hits.cpu().numpy(), totals.cpu().numpy())
+        print("dumped the headline's last timed step to %s: %s" % (args.dump_outputs, shapes), file=sys.stderr)
     out = {
         "metric": "queries/sec + postings decoded/sec, BM25 10M-doc synthetic",
         "value": world * nq / (ms_per_step * 1e-3),

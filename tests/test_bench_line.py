@@ -83,3 +83,40 @@ def test_jsonable_drops_private_keys_and_numpy_types():
     import numpy as np
     tree = {"a": np.float32(1.5), "b": np.arange(3), "_rows": np.zeros(4), "c": {"_x": 1, "y": float("inf")}, 7: (np.int64(2),)}
     assert bench._jsonable(tree) == {"a": 1.5, "b": [0, 1, 2], "c": {"y": None}, "7": [2]}
+
+
+def test_dump_outputs_writes_what_the_caller_received(tmp_path):
+    import numpy as np
+    rng = np.random.default_rng(1)
+    hits = np.zeros((6, 4), dtype=[("doc", "<i4"), ("score", "<f4")])
+    hits["doc"] = rng.integers(0, 2**31 - 1, hits.shape)
+    hits["score"] = rng.random(hits.shape, dtype=np.float32)
+    hits[5, 2:] = (-1, 0.0)                                   # unused slots as the kernels leave them
+    totals = np.array([7, 2**40 + 1, 0, 3, 9, 2], np.int64)
+    shapes = bench.dump_outputs(str(tmp_path / "d"), hits.view(np.int64), totals)
+    assert shapes == {"doc": (6, 4), "score": (6, 4), "total_hits": (6,), "query": (6,)}
+    got = {n: np.load(str(tmp_path / "d" / (n + ".npy"))) for n in shapes}
+    assert got["doc"].dtype == np.float64 and (got["doc"].astype(np.int64) == hits["doc"]).all()
+    assert got["score"].dtype == np.float32 and (got["score"].view(np.int32) == hits["score"].view(np.int32)).all()
+    assert got["total_hits"].dtype == np.float64 and (got["total_hits"].astype(np.int64) == totals).all()
+    assert (got["query"] == np.arange(6)).all()
+
+
+def test_dump_outputs_samples_a_large_batch_the_same_way_every_time(tmp_path, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1000)
+    hits = np.zeros((100, 10), dtype=[("doc", "<i4"), ("score", "<f4")])
+    hits["doc"] = np.arange(1000).reshape(100, 10)
+    totals = np.arange(100, dtype=np.int64)
+    a = bench.dump_outputs(str(tmp_path / "a"), hits, totals)
+    bench.dump_outputs(str(tmp_path / "b"), hits, totals)
+    assert a["doc"] == (7, 10) and sum(os.path.getsize(str(tmp_path / "a" / (n + ".npy"))) - 128 for n in a) <= 1000
+    q = np.load(str(tmp_path / "a" / "query.npy"))
+    assert (np.diff(q) > 0).all() and (q == np.load(str(tmp_path / "b" / "query.npy"))).all()
+    assert (np.load(str(tmp_path / "a" / "doc.npy")) == hits["doc"][q.astype(np.int64)]).all()
+
+
+def test_steps_below_one_is_refused():
+    import subprocess
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert p.returncode == 2 and "--steps" in p.stderr
