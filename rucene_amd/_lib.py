@@ -427,8 +427,13 @@ class Context:
         _check(lib().rgpu_merge_records_device(self._h, records_ptr, n_ranks, n_queries, k, out_hits_ptr, out_totals_ptr, stream or None))
 
     def kernel_stats(self):
-        arr = (_KernelStat * 32)()
-        n = _check(lib().rgpu_kernel_stats(self._h, arr, 32))
+        cap = 64
+        while True:  # rgpu_kernel_stats returns at most `cap` entries: grow until every stat fits
+            arr = (_KernelStat * cap)()
+            n = _check(lib().rgpu_kernel_stats(self._h, arr, cap))
+            if n < cap:
+                break
+            cap *= 2
         return {arr[i].name.decode(): {"launches": arr[i].launches, "total_ms": arr[i].total_ms, "postings": arr[i].postings,
                                        "timed_launches": arr[i].timed_launches, "min_ms": arr[i].min_ms, "median_ms": arr[i].median_ms,
                                        "max_ms": arr[i].max_ms}

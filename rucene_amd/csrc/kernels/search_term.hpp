@@ -232,34 +232,51 @@ __device__ __forceinline__ void term_blocks_fast(const SegView& seg, const DevTe
   // kernel's 0.097 ms — and seven chunks in ten (more on longer lists) hold no block that can enter. Those are now never
   // requested at all: not their frontier words, not their directory rows. The chunks that remain are visited in index order, each
   // requested while the one in front of it is worked on, and the set is re-filtered with the threshold of the moment on the way.
-  const int n_chunks = (b1 - b0 + 63) >> 6;
-  uint64_t cand = n_chunks >= 64 ? ~0ull : ((1ull << n_chunks) - 1ull);
-  const bool summed = RGPU_TERM_CHUNK_SUMS && prune && seg.dir_sum != nullptr && n_chunks >= 2 && n_chunks <= 64 && (b0 & 63) == 0;
+  // The candidate chunks are one bit each of a 64-bit mask, so an item of more than 64 chunks (4096 blocks: a caller's blocks_per_item,
+  // or the launch's size doubled on a batch of many items) is walked in WINDOWS of at most 64 chunks from w0 on, one mask each; a
+  // window's start stays chunk-aligned when the item's is. (One window only, the mask used to drop every block past b0 + 4096.)
+  int w0 = b0;
+  uint64_t cand = 0ull;
   uint32_t cbest = 0xffffffffu;
-  if (summed) {
-    const int cj = (b0 >> 6) + lane;  // the chunk's index within the term; only whole chunks have a word
-    const bool whole = lane < n_chunks && 64 * cj + 64 <= T.nblocks;
-    cbest = bound_of(whole ? seg.dir_sum[((T.dir_base + 63u) >> 6) + (uint32_t)cj] : 15ull);
-    touched += 8u * (uint32_t)n_chunks;  // (what this item reads of the directory is counted where it is requested)
-  }
+  auto open_window = [&]() {
+    const int n_chunks = (min(b1, w0 + 64 * 64) - w0 + 63) >> 6;
+    cand = n_chunks >= 64 ? ~0ull : ((1ull << n_chunks) - 1ull);
+    const bool summed = RGPU_TERM_CHUNK_SUMS && prune && seg.dir_sum != nullptr && n_chunks >= 2 && (w0 & 63) == 0;
+    cbest = 0xffffffffu;
+    if (summed) {
+      const int cj = (w0 >> 6) + lane;  // the chunk's index within the term; only whole chunks have a word
+      const bool whole = lane < n_chunks && 64 * cj + 64 <= T.nblocks;
+      cbest = bound_of(whole ? seg.dir_sum[((T.dir_base + 63u) >> 6) + (uint32_t)cj] : 15ull);
+      touched += 8u * (uint32_t)n_chunks;  // (what this item reads of the directory is counted where it is requested)
+    }
+  };
   auto still = [&](uint64_t t) {  // the non-strict test: thr_of(t, lo) is `bits` or `bits + 1` (cbest is all ones without a word)
     const uint32_t thi = (uint32_t)(t >> 32);
     if (thi & 0x80000000u) cand &= __ballot(cbest >= (thi & 0x7fffffffu));
   };
+  auto next_window = [&]() {  // past windows none of whose chunks can still enter (wave-uniform: w0, b1, cand)
+    while (cand == 0ull && w0 + 64 * 64 < b1) {
+      w0 += 64 * 64;
+      open_window();
+      still(tau);
+    }
+  };
   count += 128 * (b1 - b0);
+  open_window();
   still(tau);
+  next_window();
   Chunk next{};
-  if (cand) next = load_chunk(b0 + 64 * (int)__builtin_ctzll(cand), 0);
+  if (cand) next = load_chunk(w0 + 64 * (int)__builtin_ctzll(cand), 0);
   TERM_PH_ADD(0, ph_enter);
   for (int visited = 0; cand != 0ull; ++visited) {
     TERM_PH_NOW(ph_chunk);
-    const int c0 = b0 + 64 * (int)__builtin_ctzll(cand);
+    const int c0 = w0 + 64 * (int)__builtin_ctzll(cand);
     cand &= cand - 1ull;
     const int nb = min(64, b1 - c0);
     const Chunk cur = next;
     touched += 18u * (uint32_t)nb;  // frontier word, store row, header, the doc in front: the directory entries of a visited chunk
     still(tau);  // (what the chunk before this one achieved)
-    if (cand) next = load_chunk(b0 + 64 * (int)__builtin_ctzll(cand), visited + 1);
+    if (cand) next = load_chunk(w0 + 64 * (int)__builtin_ctzll(cand), visited + 1);
     const DirChunk& dir = cur.dir;
     {
       uint64_t t0 = 0;
@@ -405,6 +422,11 @@ __device__ __forceinline__ void term_blocks_fast(const SegView& seg, const DevTe
       // that — RGPU_TERM_WAIT in k_search_term)
       const bool first_of_head = RGPU_TERM_WAIT && head && c0 == b0;
       if (first_of_head || (exchange && (RGPU_TERM_EXCHANGE == 1 || (RGPU_TERM_EXCHANGE == 2 && (ci & (ci - 1)) == 0)))) shared.publish_key(group_kth<WIDE>(group, k), lane);
+    }
+    if (cand == 0ull && w0 + 64 * 64 < b1) {  // this window is done: the item's next one, its first chunk requested now
+      tau = fresh_tau();
+      next_window();
+      if (cand) next = load_chunk(w0 + 64 * (int)__builtin_ctzll(cand), visited + 1);
     }
   }
   TERM_PH_ADD(6, ph_enter);

@@ -1144,6 +1144,9 @@ extern "C" int32_t rgpu_init(int32_t device_ordinal, const rgpu_config* cfg, rgp
   HIP_TRY(hipGetDeviceProperties(&prop, device_ordinal));
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(RGPU_ERR_RUNTIME, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
+  // blocks_per_item: 0 (auto) .. 1 << 17, the ceiling of the item-count loops that double it on batches of many items
+  if (cfg && (cfg->blocks_per_item < 0 || cfg->blocks_per_item > (1 << 17)))
+    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "blocks_per_item must be 0 (auto) or 1 .. 131072");
   rgpu_ctx* c = new rgpu_ctx();
   c->device = device_ordinal;
   if (cfg) c->cfg = *cfg;

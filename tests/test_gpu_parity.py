@@ -2712,6 +2712,11 @@ def test_single_term_lists_around_every_chunk_and_item_boundary(oracle):
         freqs[rng.integers(0, df, size=5)] = 9
         lists.append((docs, freqs))
     norms = rng.choice(np.array([100, 110, 124], dtype=np.uint8), size=max_doc)
+    # one unique winner in the last 104 blocks of the 4200-block list (block 4150: past the first 64 chunks of an 8192-block item),
+    # above every freq-9 posting: an item walk that stops after 4096 blocks loses it
+    planted = 128 * 4150 + 3
+    lists[-1][1][planted] = 10
+    norms[lists[-1][0][planted]] = 124
     seg = indexgen.build_explicit(max_doc, lists, norms=norms)
     oseg = oracle.Segment(seg.doc_bytes, seg.norms, max_doc, seg.terms, sum_total_term_freq=30 * max_doc)
     osearcher = oracle.Searcher([oseg])
@@ -2719,6 +2724,8 @@ def test_single_term_lists_around_every_chunk_and_item_boundary(oracle):
     want = {}
     for k in (10, 100):
         want[k] = [osearcher.search(oracle.OP_TERM, [int(t)], k, tie_mode=oracle.TIE_CANONICAL) for t in ids[:, 0]]
+        d = want[k][-1][0]
+        assert d[0] == lists[-1][0][planted] and lists[-1][0][planted] not in d[1:]  # (the fixture: the plant is the 4200-block list's top hit)
 
     def check(rows, totals, k, picked, what):
         for j, t in enumerate(picked):
@@ -2775,7 +2782,7 @@ def test_single_term_lists_around_every_chunk_and_item_boundary(oracle):
     run({"RGPU_TERM_SPLIT": "32", "RGPU_TERM_MIN_ITEM_BLOCKS": "16"}, {}, "many short items, below a chunk")
     run({"RGPU_TERM_SKETCH": "0"}, {}, "no sketches: every item starts without a threshold")
     run({}, {"blocks_per_item": 96}, "a caller's own item size, not a power of two")
-    run({}, {"blocks_per_item": 8192}, "items of more than 64 chunks: no frontiers")
+    run({}, {"blocks_per_item": 8192}, "items of more than 64 chunks: walked in windows of 64 chunks, each with its frontiers")
 
 
 @pytest.mark.gpu
