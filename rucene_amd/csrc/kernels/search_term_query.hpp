@@ -1,0 +1,426 @@
+// Single-term queries, one workgroup per QUERY (k_search_term_query): the default kernel of the fused single-term call.
+//
+// k_search_term (search_term.hpp) cuts every list into work items of at least 8 wavefronts each, and every item pays the same chain
+// of dependent loads (term -> table -> sketch -> chunk frontiers) before it looks at its first block, finds its live blocks only by
+// position in the list, and hands its partial list to the query's last item across XCDs. Here a query stays inside one workgroup of
+// W waves:
+//   set-up    once: the term, its score table in LDS (shared by the waves), the sketch threshold;
+//   gather    the list's chunk frontiers (SegView::dir_sum), one thread per chunk; for the chunks that survive, the blocks' frontier
+//             words (dir_bmax), one lane per block, together with their store row, header and the doc in front of them. Blocks whose
+//             bound can still enter the top-k go to an LDS queue of capacity TQ_CAP, in block order;
+//   sort      the queue by (bound desc, block asc);
+//   drain     the waves pop entries best bound first from an LDS counter and unpack them (term_blocks_fast's per-block body), up
+//             to PREFETCH_DEPTH rows in flight per wave: every address comes from the queue, none waits for a directory load.
+// The threshold only rises and the queue is sorted by bound, then by block (whose doc in front grows with it): the first popped
+// entry that can no longer enter proves that none behind it can, and the round ends there. A list with more candidates than the
+// queue holds is gathered and drained in rounds from a chunk cursor, each round's gather filtering with the threshold the
+// previous rounds reached. The top-k list lives in LDS (GroupList, shared under its lock) and wave 0 writes the caller's row:
+// no partial lists, no per-query counters in memory, no exchange between XCDs.
+// Queries off the table path (raw norms, deleted docs, a negative weight, a sim table without TERM_FLAG_MONOTONE) run in the same
+// launch: the waves stride over the list's chunks with stream_blocks and offer into the same list.
+#pragma once
+#include "search_term.hpp"
+
+namespace rgpu {
+
+#ifndef RGPU_TERMQ_CAP
+#define RGPU_TERMQ_CAP 256
+#endif
+constexpr int TQ_CAP = RGPU_TERMQ_CAP;  // queue entries per round (a whole chunk of 64 blocks always fits an empty queue)
+constexpr int TQ_CHUNK_UNROLL = 4;      // chunk frontier words per thread per gather window
+#ifndef RGPU_TERMQ_STEP_CHUNKS
+#define RGPU_TERMQ_STEP_CHUNKS 2
+#endif
+constexpr int TQ_STEP_CHUNKS = RGPU_TERMQ_STEP_CHUNKS;  // surviving chunks per wave per gather step
+static_assert(TQ_CAP >= 64 && TQ_CAP <= 65536, "queue positions are u16 and a chunk must fit an empty queue");
+
+// the entry test of term_blocks_fast on raw score bits: a block whose postings' best score is `bound` can enter iff
+// bound >= term_thr_of(tau, lo), where lo = the last doc in front of the block (strict when none of its docs can win a tie)
+__device__ __forceinline__ uint32_t term_thr_of(uint64_t t, int32_t lo) {
+  const uint32_t thi = (uint32_t)(t >> 32);
+  if (!(thi & 0x80000000u)) return 0u;
+  const uint32_t bits = thi & 0x7fffffffu;
+  return key_doc(t) <= lo + 1 ? bits + 1u : bits;
+}
+// the best score any posting behind frontier word w can have under the LDS table (raw bits; all ones: no bound)
+__device__ __forceinline__ uint32_t term_bound_of(const float* cache, uint64_t w) {
+  const uint32_t fmax = (uint32_t)w & 15u;
+  uint32_t bb = 0u;
+#pragma unroll
+  for (int f = 1; f <= SCORE_TABLE_FREQS; ++f) {
+    const uint32_t r = (uint32_t)(w >> (4 + 6 * (f - 1))) & 63u;
+    const uint32_t sc = __float_as_uint(table_score(cache, r, (uint32_t)f));
+    bb = ((uint32_t)f <= fmax && sc > bb) ? sc : bb;
+  }
+  return fmax > (uint32_t)SCORE_TABLE_FREQS ? 0xffffffffu : bb;
+}
+
+
+template <bool LEGACY, bool WIDE, int W>
+__global__ __launch_bounds__(64 * W, (LEGACY || WIDE) ? RGPU_TERM_OTHER_WAVES : RGPU_TERM_FAST_WAVES)
+void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, const DevTerm* __restrict__ terms,
+                         const int32_t* __restrict__ order, int n_queries, int k, unsigned long long* __restrict__ work_slots,
+                         const int32_t* __restrict__ qmap, HitOut* __restrict__ hits, int64_t* __restrict__ totals, int32_t doc_base) {
+  // order[i]: the query of workgroup i (heaviest first); work_slots (nullable): [q] = bytes requested for query q, [n_queries + q] =
+  // FullBlocks unpacked (rgpu_last_search_counters)
+  constexpr int LIST_N = WIDE ? 128 : 64;
+  constexpr int NT = 64 * W;
+  constexpr int DEPTH = PREFETCH_DEPTH;
+  __shared__ __attribute__((aligned(16))) uint8_t slabs[W][TERM_BLOCK_SLAB];
+  __shared__ float cache[WAVE_CACHE_FLOATS];  // the norm cache (64 ranks + the score table, or 256 raw norm bytes)
+  __shared__ uint64_t list[LIST_N];
+  __shared__ uint32_t lock_word;
+  __shared__ uint32_t e_blk[TQ_CAP], e_row[TQ_CAP], e_bound[TQ_CAP];  // the queue, in block order
+  __shared__ int32_t e_lo[TQ_CAP];
+  __shared__ uint16_t e_hdr[TQ_CAP], e_order[TQ_CAP];                 // e_order: queue positions, best bound first
+  __shared__ uint32_t cq[TQ_CHUNK_UNROLL * NT];                       // surviving chunks of the current gather window
+  __shared__ uint32_t cnt[TQ_CHUNK_UNROLL * NT / 64 > W * TQ_STEP_CHUNKS ? TQ_CHUNK_UNROLL * NT / 64 : W * TQ_STEP_CHUNKS];
+  __shared__ uint32_t cursor;
+  __shared__ uint32_t sums[3];  // hits, blocks unpacked, bytes requested
+  __shared__ uint64_t floor_s;
+
+  const int lane = lane_id();
+  const int wave = wave_id();
+  const int tid = (int)threadIdx.x;
+  const int q = order != nullptr ? order[blockIdx.x] : (int)blockIdx.x;
+  if (q >= n_queries) return;
+  const int row = qmap ? qmap[q] : q;
+  HitOut* out = hits + (size_t)row * (size_t)k;
+  const DevQuery Q = queries[q];
+  if (Q.n_terms < 1) {  // clause absent from this leaf: nothing to collect
+    if (wave == 0) {
+      if (lane < k) out[lane] = HitOut{-1, 0.f};
+      if (WIDE && lane + 64 < k) out[lane + 64] = HitOut{-1, 0.f};
+      if (lane == 0) totals[row] = 0;
+    }
+    return;
+  }
+  const DevTerm T = terms[Q.first_term];
+  const bool has_norms = seg.norms != nullptr;
+  const bool tabled = has_norms && seg.n_norm_ranks > 0;
+  const bool fast = tabled && seg.live == nullptr && T.weight >= 0.0f && RGPU_TERM_PRUNE && (T.flags & TERM_FLAG_MONOTONE) != 0u;
+  const float k1 = seg.sim_tables[(size_t)T.sim_table * 257 + 256];
+  const float wk = T.weight * (k1 + 1.0f);
+  const uint8_t* term_rows = seg.bstore + T.bs_base;
+  const GroupList group{list, &lock_word};
+  const int n_chunks = (T.nblocks + 63) >> 6;
+  const uint32_t sum_base = (T.dir_base + 63u) >> 6;
+
+  for (int i = tid; i < LIST_N; i += NT) list[i] = 0ull;
+  if (tid == 0) { lock_word = 0u; sums[0] = sums[1] = sums[2] = 0u; floor_s = 0ull; cursor = 0u; }
+  uint32_t looked = 0, touched = 0;  // per wave (scalar)
+  int count = 0;                     // per wave: hits counted
+  if (wave == 0) {
+    float k1_;
+    load_sim_table(seg, T.sim_table, cache, lane, k1_);
+    if (tabled) build_score_table(cache, wk, lane);
+    // the term's block-max sketch: k real postings of k blocks, scored with this query's table — a threshold to start from
+    if (fast && T.sketch != 0u && seg.sketch != nullptr && k <= TERM_SKETCH_K) {
+      const uint64_t f = sketch_floor<WIDE>(seg.sketch + (size_t)(T.sketch - 1u) * TERM_SKETCH_K, cache, k, lane);
+      if (lane == 0) floor_s = f;
+      touched += 2u * (uint32_t)k;
+    }
+  }
+  __syncthreads();
+  const uint64_t floor = ((uint64_t)(uint32_t)readfirstlane((int)(uint32_t)(floor_s >> 32)) << 32) | (uint32_t)readfirstlane((int)(uint32_t)floor_s);
+  auto tau_now = [&]() -> uint64_t {
+    const uint64_t kth = group_kth<WIDE>(group, k);
+    return kth > floor ? kth : floor;
+  };
+  uint64_t tau = floor;
+
+  if (fast) {
+    count = wave == 0 ? 128 * T.nblocks : 0;  // no deleted docs on this path: every posting is a hit
+    const uint8_t* pn = seg.pnorm + T.pn_base;
+    uint8_t* slab = slabs[wave];
+    int cnext = 0;  // workgroup-uniform: the first chunk not gathered yet
+    while (cnext < n_chunks) {  // rounds
+      int nq = 0;  // entries in the queue (workgroup-uniform)
+      // ---- gather ----
+      while (cnext < n_chunks) {
+        // a window of TQ_CHUNK_UNROLL * NT chunks from cnext: one thread per chunk against its frontier word, strict where the doc in
+        // front of the chunk is at or past the threshold's doc (the list is the same in every wave: nothing is offered while gathering)
+        tau = tau_now();
+        uint64_t pass_m[TQ_CHUNK_UNROLL];
+        uint32_t tb = 0u;
+#pragma unroll
+        for (int u = 0; u < TQ_CHUNK_UNROLL; ++u) {
+          const int c = cnext + u * NT + tid;
+          const bool in = c < n_chunks;
+          const bool whole = in && 64 * c + 64 <= T.nblocks;
+          const bool worded = whole && seg.dir_sum != nullptr;
+          const uint64_t w = worded ? seg.dir_sum[sum_base + (uint32_t)c] : 15ull;
+          const int32_t lo = (in && c > 0) ? seg.dir_last[T.dir_base + 64u * (uint32_t)c - 1u] : -1;
+          tb += (worded ? 8u : 0u) + ((in && c > 0) ? 4u : 0u);
+          pass_m[u] = __ballot(in && term_bound_of(cache, w) >= term_thr_of(tau, lo));
+        }
+        touched += (uint32_t)wave_reduce_add((int)tb);
+#pragma unroll
+        for (int u = 0; u < TQ_CHUNK_UNROLL; ++u)
+          if (lane == 0) cnt[u * W + wave] = (uint32_t)__popcll(pass_m[u]);
+        __syncthreads();
+        {  // survivors in chunk order: (u, wave, lane)
+          const int nc = TQ_CHUNK_UNROLL * W;
+          const int v = lane < nc ? (int)cnt[lane] : 0;
+          const int incl = wave_incl_scan(v);
+#pragma unroll
+          for (int u = 0; u < TQ_CHUNK_UNROLL; ++u) {
+            const int at = readlane(incl - v, u * W + wave);
+            if ((pass_m[u] >> lane) & 1ull) cq[at + mbcnt(pass_m[u])] = (uint32_t)(cnext + u * NT + tid);
+          }
+        }
+        const int n_cq = (int)readfirstlane(wave_reduce_add(lane < TQ_CHUNK_UNROLL * W ? (int)cnt[lane] : 0));
+        const int window_end = min(n_chunks, cnext + TQ_CHUNK_UNROLL * NT);
+        __syncthreads();
+        // the surviving chunks, TQ_STEP_CHUNKS per wave per step: every block's frontier word, store row, header and the doc in front
+        // of it, one lane per block; the blocks that may still enter are appended to the queue in block order. A step whose blocks
+        // do not all fit ends the round at the first chunk that does not fit.
+        int pos = 0;
+        bool full = false;
+        while (pos < n_cq) {
+          uint64_t bm[TQ_STEP_CHUNKS];
+          uint32_t rw[TQ_STEP_CHUNKS], hd[TQ_STEP_CHUNKS];
+          int32_t lo[TQ_STEP_CHUNKS];
+          int ch[TQ_STEP_CHUNKS];
+#pragma unroll
+          for (int s = 0; s < TQ_STEP_CHUNKS; ++s) {
+            const int ci = pos + wave * TQ_STEP_CHUNKS + s;
+            ch[s] = ci < n_cq ? (int)cq[ci] : -1;
+            const int nb = ch[s] < 0 ? 0 : min(64, T.nblocks - 64 * ch[s]);
+            const bool ok = lane < nb;
+            const uint32_t b = T.dir_base + 64u * (uint32_t)(ch[s] < 0 ? 0 : ch[s]) + (uint32_t)lane;
+            bm[s] = ok ? seg.dir_bmax[b] : 0ull;
+            rw[s] = ok ? seg.dir_row[b] : 0u;
+            hd[s] = ok ? (uint32_t)seg.dir_hdr[b] : 0u;
+            lo[s] = (ok && b > T.dir_base) ? seg.dir_last[b - 1u] : -1;
+            touched += 18u * (uint32_t)nb;
+          }
+          uint64_t pm[TQ_STEP_CHUNKS];
+#pragma unroll
+          for (int s = 0; s < TQ_STEP_CHUNKS; ++s) {
+            const int nb = ch[s] < 0 ? 0 : min(64, T.nblocks - 64 * ch[s]);
+            pm[s] = __ballot(lane < nb && term_bound_of(cache, bm[s]) >= term_thr_of(tau, lo[s]));
+            if (lane == 0) cnt[wave * TQ_STEP_CHUNKS + s] = (uint32_t)__popcll(pm[s]);
+          }
+          __syncthreads();
+          const int ns = W * TQ_STEP_CHUNKS;
+          const int v = lane < ns ? (int)cnt[lane] : 0;
+          const int incl = wave_incl_scan(v);
+          const int cut = __popcll(__ballot(lane < ns && nq + incl <= TQ_CAP));  // chunks of this step that fit (a prefix)
+#pragma unroll
+          for (int s = 0; s < TQ_STEP_CHUNKS; ++s) {
+            const int i = wave * TQ_STEP_CHUNKS + s;
+            if (i < cut && ((pm[s] >> lane) & 1ull)) {
+              const int at = nq + readlane(incl - v, i) + mbcnt(pm[s]);
+              e_blk[at] = (uint32_t)(64 * ch[s] + lane);
+              e_row[at] = rw[s];
+              e_hdr[at] = (uint16_t)hd[s];
+              e_lo[at] = lo[s];
+              e_bound[at] = term_bound_of(cache, bm[s]);
+            }
+          }
+          nq += cut > 0 ? readlane(incl, cut - 1) : 0;
+          pos = min(n_cq, pos + cut);
+          __syncthreads();
+          if (cut < ns) { full = true; break; }
+        }
+        if (full && pos < n_cq) { cnext = (int)cq[pos]; break; }  // the round is full: the next one resumes at this chunk
+        cnext = window_end;
+        if (full) break;
+      }
+      if (nq == 0) continue;
+      // ---- sort: queue position -> entry, (bound desc, entry asc); entries are in block order ----
+      for (int i = tid; i < nq; i += NT) {
+        const uint32_t bi = e_bound[i];
+        int r = 0;
+        for (int j = 0; j < nq; ++j) {
+          const uint32_t bj = e_bound[j];
+          r += (bj > bi || (bj == bi && j < i)) ? 1 : 0;
+        }
+        e_order[r] = (uint16_t)i;
+      }
+      if (tid == 0) cursor = 0u;
+      __syncthreads();
+      // ---- drain ----
+      // An entry is re-tested against the list's k-th best of the moment when it is popped. The threshold only rises, and an entry
+      // behind a failed one has a bound at most as large and, at an equal bound, a later block (its doc in front is at least as
+      // large: term_thr_of is at least as strict) — so the first failure ends the round for every wave.
+      auto pop = [&]() -> int {
+        uint32_t p = 0u;
+        if (lane == 0) p = atomicAdd(&cursor, 1u);
+        p = (uint32_t)readfirstlane((int)p);
+        if (p >= (uint32_t)nq) return -1;
+        const int i = (int)e_order[p];
+        if (e_bound[i] >= term_thr_of(tau_now(), e_lo[i])) return i;
+        if (lane == 0) atomicMax(&cursor, (uint32_t)nq);
+        return -1;
+      };
+      auto norms_of = [&](int i) -> uint32_t {
+        return *reinterpret_cast<const uint16_t*>(pn + (128u * e_blk[i] + 2u * (uint32_t)lane));
+      };
+      auto step = [&](int i, const uint4& rows, uint32_t nn) {
+        const uint32_t hdr = (uint32_t)e_hdr[i];
+        const int32_t lo = e_lo[i];
+        touched += encoded_block_bytes(hdr) + 128u;  // both streams' rows + the posting-order norms were requested at the pop
+        // once more against the threshold of the moment: up to DEPTH pops of every wave are in flight, and the list may have risen
+        // since this one was popped
+        tau = tau_now();
+        if (e_bound[i] < term_thr_of(tau, lo)) return;
+        const int bf = hdr_bfreq(hdr);
+        stage_rows(rows, slab, lane);
+        wave_sync();
+        uint32_t f0, f1;
+        bool in_table = true;  // wave-uniform: every freq of the block has a table column
+        if (bf) {
+          extract_pair<LEGACY>(slab + SLAB_STREAM, bf, lane, f0, f1);
+          if (bf > 3) in_table = !__ballot((f0 > f1 ? f0 : f1) > (uint32_t)SCORE_TABLE_FREQS);
+        } else {
+          const uint32_t f = (uint32_t)readlane((int)rows.x, 32);  // all-equal stream: its value
+          f0 = f1 = f;
+          in_table = f <= (uint32_t)SCORE_TABLE_FREQS;
+        }
+        const uint32_t nb0 = nn & 0xffu, nb1 = nn >> 8;
+        float s0, s1;
+        if (in_table) {
+          s0 = table_score(cache, nb0, f0);
+          s1 = table_score(cache, nb1, f1);
+        } else {
+          s0 = bm25_score(wk, (float)(int32_t)f0, cache[nb0]);
+          s1 = bm25_score(wk, (float)(int32_t)f1, cache[nb1]);
+        }
+        looked += 1u;
+        tau = tau_now();
+        const uint32_t thr = term_thr_of(tau, lo);
+        const uint32_t r0 = __float_as_uint(s0), r1 = __float_as_uint(s1);
+        if (__ballot((r0 > r1 ? r0 : r1) >= thr)) {  // the doc deltas only when some posting can still enter
+          uint32_t e0, e1;
+          staged_doc_deltas<LEGACY>(slab, rows, hdr, lane, e0, e1);
+          int32_t d0, d1;
+          deltas_to_docs(e0, e1, lo < 0 ? 0 : lo, d0, d1);
+          const uint64_t key0 = make_key(s0, d0), key1 = make_key(s1, d1);
+          tau = tau_now();
+          if (__ballot((key0 > key1 ? key0 : key1) > tau)) group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor);
+        }
+        wave_sync();  // slab is free for the next block
+      };
+      // a DEPTH-deep ring of row (and norm) loads per wave; slots without an entry reload entry 0 instead of being guarded
+      int slot[DEPTH];
+      uint4 ring[DEPTH];
+      uint32_t nring[DEPTH];
+#pragma unroll
+      for (int j = 0; j < DEPTH; ++j) {
+        slot[j] = pop();
+        const int pj = slot[j] < 0 ? 0 : slot[j];
+        ring[j] = block_rows_load(block_rows_at(term_rows, e_row[pj]), e_hdr[pj], lane);
+        nring[j] = norms_of(pj);
+      }
+      while (slot[0] >= 0) {  // slots fill in order, so an empty slot 0 means an empty ring
+#pragma unroll
+        for (int j = 0; j < DEPTH; ++j) {
+          const uint4 rows = ring[j];
+          const uint32_t nn = nring[j];
+          const int i = slot[j];
+          slot[j] = i >= 0 ? pop() : -1;
+          const int pj = slot[j] < 0 ? 0 : slot[j];
+          ring[j] = block_rows_load(block_rows_at(term_rows, e_row[pj]), e_hdr[pj], lane);
+          nring[j] = norms_of(pj);
+          if (i >= 0) {
+            step(i, rows, nn);
+          }
+        }
+      }
+      __syncthreads();  // every offer of this round is in the list; the queue is free
+    }
+  } else {
+    // off the table path: the waves stride over the list's chunks of 64 blocks and share the list
+    const bool has_live = seg.live != nullptr;
+    uint8_t* slab = slabs[wave];
+    auto on_block = [&](int blk, int32_t d0, int32_t d1, uint32_t f0, uint32_t f1, uint32_t nb0, uint32_t nb1) {
+      looked += 1u;  // the general path decodes every block
+      touched += encoded_block_bytes((uint32_t)seg.dir_hdr[T.dir_base + blk]) + (has_norms ? 128u : 0u);
+      bool v0 = true, v1 = true;
+      if (has_live) {
+        v0 = doc_in_segment(seg, d0) && doc_is_live(seg.live, d0);
+        v1 = doc_in_segment(seg, d1) && doc_is_live(seg.live, d1);
+      }
+      float s0, s1;
+      const uint32_t fmax = f0 > f1 ? f0 : f1;
+      if (tabled && !__ballot((v0 || v1) && fmax > (uint32_t)SCORE_TABLE_FREQS)) {
+        s0 = table_score(cache, nb0, v0 ? f0 : 1u);
+        s1 = table_score(cache, nb1, v1 ? f1 : 1u);
+      } else {
+        s0 = bm25_score(wk, (float)(int32_t)f0, has_norms ? cache[nb0] : k1);
+        s1 = bm25_score(wk, (float)(int32_t)f1, has_norms ? cache[nb1] : k1);
+      }
+      count += __popcll(__ballot(v0)) + __popcll(__ballot(v1));
+      const uint64_t key0 = v0 ? make_key(s0, d0) : 0ull, key1 = v1 ? make_key(s1, d1) : 0ull;
+      if (__ballot((key0 > key1 ? key0 : key1) > tau)) group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor);
+    };
+    for (int c = wave; c < n_chunks; c += W) {
+      const int b0 = 64 * c, b1 = min(T.nblocks, b0 + 64);
+      int32_t base = b0 == 0 ? 0 : seg.dir_last[T.dir_base + b0 - 1];
+      if (has_norms)
+        stream_blocks<LEGACY, true>(term_rows, seg.dir_row, seg.dir_hdr, T.dir_base, seg.pnorm + T.pn_base, b0, b1, slab, lane, base, on_block);
+      else
+        stream_blocks<LEGACY, false>(term_rows, seg.dir_row, seg.dir_hdr, T.dir_base, nullptr, b0, b1, slab, lane, base, on_block);
+    }
+  }
+
+  if (lane == 0) {
+    atomicAdd(&sums[0], (uint32_t)count);
+    atomicAdd(&sums[1], looked);
+    atomicAdd(&sums[2], touched);
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  // the tail and the singleton (postings outside FullBlocks), then the caller's row
+  {
+    const bool has_live = seg.live != nullptr;
+    int tcount = 0;
+    auto collect = [&](int32_t d0, int32_t d1, uint32_t f0, uint32_t f1, uint32_t nb0, uint32_t nb1, bool v0, bool v1) {
+      if (has_live) {
+        v0 = v0 && doc_in_segment(seg, d0) && doc_is_live(seg.live, d0);
+        v1 = v1 && doc_in_segment(seg, d1) && doc_is_live(seg.live, d1);
+      }
+      float s0, s1;
+      const uint32_t fmax = f0 > f1 ? f0 : f1;
+      if (tabled && !__ballot((v0 || v1) && fmax > (uint32_t)SCORE_TABLE_FREQS)) {
+        s0 = table_score(cache, nb0, v0 ? f0 : 1u);
+        s1 = table_score(cache, nb1, v1 ? f1 : 1u);
+      } else {
+        s0 = bm25_score(wk, (float)(int32_t)f0, has_norms ? cache[nb0] : k1);
+        s1 = bm25_score(wk, (float)(int32_t)f1, has_norms ? cache[nb1] : k1);
+      }
+      tcount += __popcll(__ballot(v0)) + __popcll(__ballot(v1));
+      const uint64_t key0 = v0 ? make_key(s0, d0) : 0ull, key1 = v1 ? make_key(s1, d1) : 0ull;
+      tau = tau_now();
+      if (__ballot((key0 > key1 ? key0 : key1) > tau)) group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor);
+    };
+    if (T.df == 1) {
+      const bool v0 = lane == 0;
+      const uint32_t nb0 = (has_norms && v0) ? norm_at(seg, T.singleton_doc) : 0u;
+      collect(T.singleton_doc, 0, (uint32_t)T.singleton_freq, 1u, nb0, 0u, v0, false);
+    } else if (T.tail_n > 0) {
+      int32_t d0, d1;
+      uint32_t f0, f1;
+      tail_load(term_rows, seg.dir_row[T.dir_base + T.nblocks], lane, d0, d1, f0, f1);  // decoded and validated at prepare time
+      const bool v0 = 2 * lane < T.tail_n, v1 = 2 * lane + 1 < T.tail_n;
+      const uint32_t nb0 = (has_norms && v0) ? seg.norms[d0] : 0u, nb1 = (has_norms && v1) ? seg.norms[d1] : 0u;
+      collect(d0, d1, f0, f1, nb0, nb1, v0, v1);
+    }
+    wave_sync();
+    const uint64_t a = list[lane];
+    const uint64_t b = WIDE ? list[64 + lane] : 0ull;
+    if (lane < k) out[lane] = a ? HitOut{key_doc(a) + doc_base, key_score(a)} : HitOut{-1, 0.f};
+    if (WIDE && lane + 64 < k) out[lane + 64] = b ? HitOut{key_doc(b) + doc_base, key_score(b)} : HitOut{-1, 0.f};
+    if (lane == 0) {
+      totals[row] = (int64_t)sums[0] + tcount;
+      if (work_slots != nullptr) {
+        work_slots[q] = (unsigned long long)sums[2];
+        work_slots[n_queries + q] = (unsigned long long)sums[1];
+      }
+    }
+  }
+}
+
+}  // namespace rgpu

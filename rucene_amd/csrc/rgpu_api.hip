@@ -34,6 +34,7 @@
 #include "host/prepared_map.hpp"
 #include "kernels/search_phrase.hpp"
 #include "kernels/search_term.hpp"
+#include "kernels/search_term_query.hpp"
 
 using namespace rgpu;
 
@@ -225,6 +226,10 @@ struct rgpu_ctx {
   bool host_time = false;         // RGPU_HOST_TIME=1: term_batch_fast prints where the calling thread's time goes
   bool stage_by_kernel = true;    // staged plans reach the device through k_stage_copy (RGPU_STAGE_COPY=dma: hipMemcpyAsync)
   bool term_fold = true;          // plan + search in one call, single-term batches: k_search_term folds the item lists itself (RGPU_TERM_FOLD=0: k_merge_items)
+  // the fused single-term call runs k_search_term_query (one workgroup of term_query_waves waves per query) when the library sizes
+  // the items and folds in the launch; RGPU_TERM_KERNEL=items in the environment: k_search_term's work items (A/B)
+  bool term_query_kernel = true;
+  int term_query_waves = 4;       // 2, 4 or 8 (RGPU_TERM_QUERY_WAVES)
   int term_min_item_blocks = 64;  // ... and none of its items shorter than this (RGPU_TERM_MIN_ITEM_BLOCKS)
   int term_target_items = 3000;  // single-term launches: items of the launch's size, at most about this many (RGPU_TERM_TARGET_ITEMS in the environment)
   int term_split = 8;         // single-term queries: at least this many items per query, of 64 blocks or more each (RGPU_TERM_SPLIT in the environment; 1: off)
@@ -1171,6 +1176,8 @@ extern "C" int32_t rgpu_init(int32_t device_ordinal, const rgpu_config* cfg, rgp
   if (const char* e = std::getenv("RGPU_HOST_TIME")) c->host_time = std::atoi(e) != 0;
   if (const char* e = std::getenv("RGPU_STAGE_COPY")) c->stage_by_kernel = std::strcmp(e, "dma") != 0;
   if (const char* e = std::getenv("RGPU_TERM_FOLD")) c->term_fold = std::atoi(e) != 0;
+  if (const char* e = std::getenv("RGPU_TERM_KERNEL")) c->term_query_kernel = std::strcmp(e, "items") != 0;
+  if (const char* e = std::getenv("RGPU_TERM_QUERY_WAVES")) { const int w = std::atoi(e); c->term_query_waves = w <= 2 ? 2 : w >= 8 ? 8 : 4; }
   if (const char* e = std::getenv("RGPU_TERM_MIN_ITEM_BLOCKS")) c->term_min_item_blocks = std::max(8, std::min(4096, std::atoi(e)));
   if (const char* e = std::getenv("RGPU_TERM_SPLIT")) c->term_split = std::max(1, std::min(64, std::atoi(e)));
   if (const char* e = std::getenv("RGPU_COMM_FORCE_GATHER")) { if (std::atoi(e) != 0) c->cfg.comm_force_gather = 1; }
@@ -4746,6 +4753,7 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
   const size_t o_p = st.add((size_t)(nq + 1) * 8);
   const size_t o_m = st.add((size_t)nq * 4);
   const size_t o_sh = st.add((size_t)nq);            // log2 of every query's own item size (0: the launch's)
+  const size_t o_ord = st.add((size_t)nq * 4);       // k_search_term_query: the query of every workgroup, heaviest first
   const size_t o_tau = st.add((size_t)nq * 8);       // per-query shared thresholds ...
   const size_t o_w = st.add((size_t)nq * 16);        // ... and the launch's counters: zeroed by the copy that brings the plan
   const size_t o_done = st.add((size_t)nq * 4);      // ... and the per-query counts of finished items (TermMerge::done)
@@ -4809,6 +4817,20 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
   });
   if (bail) return RGPU_OK;  // (the slot was taken and not marked: it is simply free again)
   if (timed) laps.lap(1);
+  // k_search_term_query: one workgroup per query, no work items — the plan is the queries, their terms and a launch order, longest
+  // lists first (a counting sort on floor(log2(nblocks)))
+  const bool per_query = c->term_query_kernel && c->blocks_per_item_auto && c->term_fold;
+  if (per_query) {
+    int32_t* ho = reinterpret_cast<int32_t*>(c->S->h_stage.p + o_ord);
+    int32_t start[34] = {0};
+    auto bucket = [&](int q) -> int {  // 0: the longest lists
+      const int32_t nb = hq[q].n_terms >= 1 ? ht[hq[q].first_term].nblocks : 0;
+      return nb <= 0 ? 32 : __builtin_clz((uint32_t)nb);
+    };
+    for (int q = 0; q < nq; ++q) ++start[bucket(q) + 1];
+    for (int b = 0; b < 33; ++b) start[b + 1] += start[b];
+    for (int q = 0; q < nq; ++q) ho[start[bucket(q)]++] = q;
+  }
   // items: chunks of a term's blocks; every query's first chunk is scheduled first (search_pass's rule, to the letter)
   int blocks_per_item = c->cfg.blocks_per_item;
   int term_split = 1;
@@ -4818,7 +4840,7 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
   }
   int64_t items = 0;
   uint8_t* hsh = c->S->h_stage.p + o_sh;
-  while (true) {
+  while (!per_query) {
     items = 0;
     const int base_sh = term_item_shift(blocks_per_item);  // 0: not a power of two (a caller's own size) — no per-query sizes then
     const int floor_sh = std::max(1, term_item_shift(c->term_min_item_blocks));
@@ -4841,7 +4863,7 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
     if (items <= 262144 || blocks_per_item >= (1 << 17)) break;
     blocks_per_item *= 2;
   }
-  items += nq;
+  if (!per_query) items += nq;
   if (timed) laps.lap(2);
   if (items > 262144 + (int64_t)nq) return RGPU_OK;  // (blocks_per_item hit its ceiling on an absurd batch: the full path takes it)
   const bool plan_on_device = c->stage_by_kernel && !c->upload_aside && o_id + (size_t)items * sizeof(int4) <= 0xffffffffull;
@@ -4849,14 +4871,14 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
     // zeroes and item descriptors are the copy kernel's work (k_stage_term_plan)
     if (timed) laps.lap(3);
     const size_t n16 = (o_id + 15) / 16;  // (o_id is 256-aligned: everything in front of the descriptors)
-    const TermPlanLayout L{(uint32_t)o_q, (uint32_t)o_p, (uint32_t)o_sh, (uint32_t)o_id, (uint32_t)o_tau, (uint32_t)o_zero_end, nq};
+    const TermPlanLayout L{(uint32_t)o_q, (uint32_t)o_p, (uint32_t)o_sh, (uint32_t)o_id, (uint32_t)o_tau, (uint32_t)o_zero_end, per_query ? 0 : nq};
     TimedLaunch tl(c, stream, "k_stage_term_plan", 0);
-    const unsigned grid = (unsigned)std::min<size_t>(1024, std::max<size_t>((n16 + 255) / 256, ((size_t)nq + 255) / 256));
+    const unsigned grid = (unsigned)std::min<size_t>(1024, std::max<size_t>((n16 + 255) / 256, per_query ? 0 : ((size_t)nq + 255) / 256));
     RGPU_LAUNCH(k_stage_term_plan, dim3(grid), dim3(256), 0, stream, c->S->h_stage.p, c->S->d_stage.p, n16, L);
   } else {
     std::memset(c->S->h_stage.p + o_tau, 0, o_zero_end - o_tau);
     int4* hd = reinterpret_cast<int4*>(c->S->h_stage.p + o_id);
-    for (int q = 0; q < nq; ++q) {  // fill_term_item_desc with the sizes the item loop chose
+    for (int q = 0; q < (per_query ? 0 : nq); ++q) {  // fill_term_item_desc with the sizes the item loop chose
       const int n_mine = 1 + (int)(hp[q + 1] - hp[q]);
       const int ft = hq[q].n_terms >= 1 ? hq[q].first_term : -1;
       const int w = n_mine | ((int)hsh[q] << 24);
@@ -4869,8 +4891,10 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
     HIP_TRY(stage_h2d(c, staged, stream));
   }
   if (timed) laps.lap(4);
-  HIP_TRY(c->S->d_partial_keys.reserve((size_t)items * (size_t)k, 0, stream));
-  HIP_TRY(c->S->d_partial_counts.reserve((size_t)items, 0, stream));
+  if (!per_query) {
+    HIP_TRY(c->S->d_partial_keys.reserve((size_t)items * (size_t)k, 0, stream));
+    HIP_TRY(c->S->d_partial_counts.reserve((size_t)items, 0, stream));
+  }
   unsigned long long* d_tau = reinterpret_cast<unsigned long long*>(c->S->d_stage.p + o_tau);
   unsigned long long* d_work = reinterpret_cast<unsigned long long*>(c->S->d_stage.p + o_w);
   const DevQuery* dq = reinterpret_cast<const DevQuery*>(c->S->d_stage.p + o_q);
@@ -4889,7 +4913,28 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
   // the fold of every query's item lists happens inside k_search_term (TermMerge), unless RGPU_TERM_FOLD=0 asks for k_merge_items
   const TermMerge fold = c->term_fold ? TermMerge{reinterpret_cast<unsigned int*>(c->S->d_stage.p + o_done), dp, hits_dev, totals_dev, nullptr, seg->doc_base, 0, 0}
                                       : TermMerge{};
-  {
+  if (per_query) {
+    // (timed under the TERM search's name: what reads the stats — bench.py's roofline among them — asks for "k_search_term"; the
+    // term_query_launches stat below tells the two kernels apart)
+    TimedLaunch tl(c, stream, "k_search_term", postings);
+    const SegView sv = seg_view(seg);
+    const int32_t* dord = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_ord);
+    auto go = [&](auto kern, int waves) -> hipError_t {
+      RGPU_LAUNCH(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, sv, dq, dt, dord, nq, (int)k, d_work, dm, hits_dev, totals_dev, seg->doc_base);
+      return hipSuccess;
+    };
+    auto pick = [&](auto legacy_c, auto wide_c) -> hipError_t {
+      constexpr bool LG = decltype(legacy_c)::value, WD = decltype(wide_c)::value;
+      if (c->term_query_waves == 2) return go(k_search_term_query<LG, WD, 2>, 2);
+      if (c->term_query_waves == 8) return go(k_search_term_query<LG, WD, 8>, 8);
+      return go(k_search_term_query<LG, WD, 4>, 4);
+    };
+    hipError_t e;
+    if (legacy) e = wide ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{});
+    else e = wide ? pick(std::false_type{}, std::true_type{}) : pick(std::false_type{}, std::false_type{});
+    HIP_TRY(e);
+    c->stats[(size_t)stat_slot(c, "term_query_launches")].launches += 1;
+  } else {
     TimedLaunch tl(c, stream, "k_search_term", postings);
     const unsigned grid = wg_count((items + TERM_WAVES - 1) / TERM_WAVES);
     const size_t lds = term_lds_bytes(wide);
@@ -4906,7 +4951,7 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
     else e = wide ? go(k_search_term<false, true>) : go(k_search_term<false, false>);
     HIP_TRY(e);
   }
-  if (!c->term_fold) {
+  if (!per_query && !c->term_fold) {
     if (wide) launch_merge<true>(c, stream, nq, k, dp, seg->doc_base, hits_dev, totals_dev, nq, nullptr, nullptr, dm);
     else launch_merge<false>(c, stream, nq, k, dp, seg->doc_base, hits_dev, totals_dev, nq, nullptr, nullptr, dm);
   }
