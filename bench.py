@@ -5,6 +5,13 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the rows of the last timed step as DIR/*.npy
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full               # + every figure and check below the headline
+
+A plain run does what the headline needs and nothing else: it builds and uploads the shard, warms up, times the steps, writes
+--dump-outputs and prints the line (`value`, `ms_per_step`, the min / median / max regions, postings decoded / covered per
+second, the one-stream figure). `--full` adds what takes runs of its own: the headline's other stream and planner variants,
+the sustained region, the per-kernel event pass and the roofline built on it, the fused-vs-two-calls check, the run without
+sketches, the CPU baseline and the oracle parity, the sharded overhead, and the configs below.
 
 One "step" = one pass of the hot path over one batch: 1024 single-term BM25 queries (BASELINE.json configs[1],
 SURVEY.md §8(d)) PLANNED (term ids -> term states, BM25 weights: the native batch planner behind the C ABI) and evaluated
@@ -13,7 +20,7 @@ index is segment-sharded (one 10M-doc shard per rank, shard = rank), the query b
 it against its shard, per-shard top-k is all-gathered over RCCL and merged on the GPU — weak scaling: the unit is one
 query evaluated against one 10M-doc segment. Rank 0 prints ONE JSON line.
 
-What the line claims, and how each claim is kept honest:
+What the line claims, and how each claim is kept honest (roofline and parity: --full):
   * `value` (queries/s) has the planning inside the timed region;
   * `roofline.frac` is a BANDWIDTH fraction: bytes the dominant kernel really touched (counted by the kernel:
     rgpu_last_search_counters) / its launch duration (HIP events) / 8 TB/s. What an exhaustive scorer would have had to
@@ -23,7 +30,7 @@ What the line claims, and how each claim is kept honest:
   * every timed batch is compared with the CPU oracle on the full batch (N = 1): bit-exact doc ids and scores for TERM /
     AND; for the 10-clause OR — which the reference itself sums in heap order — doc ids are judged by the oracle's own
     score of every returned doc (oracle/parity.py) and `docs_differing` is reported.
-Under "configs" (N = 1: all; N > 1: and3, i.e. BASELINE configs[4]'s workload): 3-term AND (configs[2]), 10-term OR top-100
+Under "configs" (--full; N = 1: all; N > 1: and3, i.e. BASELINE configs[4]'s workload): 3-term AND (configs[2]), 10-term OR top-100
 (configs[3]), block decode warm (prepared block store) and COLD (.doc bytes -> skip decode -> postings), the positions side (SURVEY
 8(f)3: a materialising .pos decode and two-term exact phrases on the same corpus indexed with positions), and the first four
 out of the Infinity Cache on a 100M-doc shard. `--configs none` skips them.
@@ -159,6 +166,7 @@ HOISTED = [
 ]
 LINE_REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                  "dtype", "data", "config", "roofline")
+LINE_REQUIRED_PLAIN = tuple(k for k in LINE_REQUIRED if k != "roofline")   # the roofline needs the --full kernel pass
 
 
 def _dig(tree, path):
@@ -182,20 +190,21 @@ def _num(v):
     return float("%.5g" % v)
 
 
-def final_line(full, detail_path="bench_detail.json"):
+def final_line(full, detail_path="bench_detail.json", required=LINE_REQUIRED):
     """The ONE stdout line of the contract, from the full result tree: the contract's keys, `roofline` and `cpu_baseline` as
     small objects, the north-star's other targets as top-level scalars — and nothing else (the tree itself goes to
-    `detail_path` and to stderr). Guaranteed: strict JSON that round-trips, < LINE_MAX_BYTES."""
+    `detail_path` and to stderr). Guaranteed: strict JSON that round-trips, < LINE_MAX_BYTES, every key of `required`."""
     line = {}
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"):
         line[key] = _num(full.get(key))
     cfg = full.get("config", {})
     line["config"] = {k: (_short(v, 160) if isinstance(v, str) else v) for k, v in cfg.items()
                       if k in ("workload", "docs_per_shard", "vocab", "n_queries", "k", "doc_format", "parallelism", "device", "timed_regions", "issue")}
-    roof = full.get("roofline") or {}
-    line["roofline"] = {k: (_short(roof[k], 200) if isinstance(roof.get(k), str) else _num(roof.get(k)))
-                        for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms", "kernel_ms_suspect", "bytes_per_launch",
-                                  "bytes_are", "traffic_source", "across_rounds") if k in roof}
+    if "roofline" in full:
+        roof = full["roofline"]
+        line["roofline"] = {k: (_short(roof[k], 200) if isinstance(roof.get(k), str) else _num(roof.get(k)))
+                            for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms", "kernel_ms_suspect", "bytes_per_launch",
+                                      "bytes_are", "traffic_source", "across_rounds") if k in roof}
     if "cpu_baseline" in full:
         cb = full["cpu_baseline"]
         line["cpu_baseline"] = {"value": _num(cb.get("value")), "unit": cb.get("unit"), "cores": cb.get("cores"), "kind": cb.get("kind"),
@@ -229,8 +238,9 @@ def final_line(full, detail_path="bench_detail.json"):
         text = json.dumps(line, allow_nan=False)
     assert len(text.encode()) < LINE_MAX_BYTES, "the final line does not fit %d bytes" % LINE_MAX_BYTES
     assert "\n" not in text and json.loads(text) == json.loads(json.dumps(line)), "the final line does not round-trip"
-    missing = [k for k in LINE_REQUIRED if k not in line or (line[k] is None and k != "vs_baseline")]
-    missing += ["roofline." + k for k in ("bound", "achieved", "peak", "unit", "frac", "traffic") if k not in line["roofline"]]
+    missing = [k for k in required if k not in line or (line[k] is None and k != "vs_baseline")]
+    if "roofline" in required:
+        missing += ["roofline." + k for k in ("bound", "achieved", "peak", "unit", "frac", "traffic") if k not in line.get("roofline", {})]
     assert not missing, "the final line lacks %s" % missing
     return text
 
@@ -284,11 +294,14 @@ def main():
     ap.add_argument("--queries", type=int, default=1024)
     ap.add_argument("--k", type=int, default=0, help="0 = the workload's own (10; 100 for or10)")
     ap.add_argument("--workload", choices=["term", "and3", "or10"], default="term")
-    ap.add_argument("--configs", default="all", help="all | none | comma list of and3,or10,latency,block_decode,cold,positions,out_of_cache (N > 1: and3 only)")
-    ap.add_argument("--big-docs", type=int, default=100_000_000, help="size of the out-of-cache shard")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (see the module docstring); off: the headline alone")
+    ap.add_argument("--configs", default=None,
+                    help="with --full: all (default) | none | comma list of and3,or10,latency,block_decode,cold,positions,out_of_cache (N > 1: and3 only)")
+    ap.add_argument("--big-docs", type=int, default=100_000_000, help="size of the out-of-cache shard (--full)")
     ap.add_argument("--regions", type=int, default=5, help="timed regions of --steps steps per figure; the median region is reported")
     ap.add_argument("--detail", default="", help="where the full result tree goes (default: bench_detail.json next to bench.py, and gpurun_out/ when present)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the oracle parity")
     ap.add_argument("--force-dist", action="store_true",
                     help="developer check: take the N > 1 code path (RCCL all-gather + device merge) with a world of one")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -296,6 +309,9 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or args.regions < 1:
         ap.error("--steps and --regions must be >= 1, --warmup >= 0")
+    if args.configs not in (None, "none") and not args.full:
+        ap.error("--configs %s needs --full: a plain run measures the headline alone" % args.configs)
+    args.configs = args.configs or "all"
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -367,14 +383,15 @@ def main():
             self.local_hits = torch.empty((nq, k), dtype=torch.int64, device="cuda")  # this rank's shard alone (parity checks)
             self.local_totals = torch.empty((nq,), dtype=torch.int64, device="cuda")
 
-    def measure(shard, kind, k, steps, warmup, full):
+    def measure(shard, kind, k, steps, warmup, variants):
         """Times `steps` passes of one batch. rgpu_search_batch_device only enqueues (staging copy + kernels): back-to-back
         steps overlap the host-side work of batch i+1 with the kernels of batch i; every timed region is bracketed by a
         barrier + device-wide synchronize on both sides and runs WITHOUT per-kernel events. N > 1: a step =
         rgpu_search_batch_sharded: search -> ONE RCCL all-gather of the per-shard {top-k, count, status} records -> device
         merge, enqueued in order on one stream without host syncs.
         Figures: "planned" = the batch is planned (ids -> rgpu_query_term[]) again in every step, natively; "resident
-        plan" = planned once. `full` adds the one-stream and object-planner variants of the headline table."""
+        plan" = planned once. `variants` adds the two-call, resident-plan and object-planner variants of the headline table
+        and the sustained region; --full adds the fused-vs-two-calls check and the per-kernel event pass."""
         tids, packed, postings, algo_bytes = shard.batch(kind, k)
         lanes = [Lane(k), Lane(k)]
         state = {"n": 0}
@@ -465,22 +482,23 @@ def main():
             step(packed, 2)
         step_fused(2)
         torch.cuda.synchronize()
-        fused_same = True
-        if not dist_mode:   # the fused call's rows are the two calls' rows
-            a, b = lanes[0], lanes[1]
-            shard.leaf.segment.search_batch_device(packed[0], packed[1], k, a.hits.data_ptr(), a.totals.data_ptr(), a.stream.cuda_stream)
-            shard.searcher.search_uniform_device(OPS[kind], tids, shard.leaf, k, b.hits.data_ptr(), b.totals.data_ptr(), b.stream.cuda_stream)
-            ctx.synchronize()
-            torch.cuda.synchronize()
-            fused_same = bool(torch.equal(a.hits, b.hits)) and bool(torch.equal(a.totals, b.totals))
-        res["fused_same_rows_as_two_calls"] = fused_same
+        if args.full:
+            fused_same = True
+            if not dist_mode:   # the fused call's rows are the two calls' rows
+                a, b = lanes[0], lanes[1]
+                shard.leaf.segment.search_batch_device(packed[0], packed[1], k, a.hits.data_ptr(), a.totals.data_ptr(), a.stream.cuda_stream)
+                shard.searcher.search_uniform_device(OPS[kind], tids, shard.leaf, k, b.hits.data_ptr(), b.totals.data_ptr(), b.stream.cuda_stream)
+                ctx.synchronize()
+                torch.cuda.synchronize()
+                fused_same = bool(torch.equal(a.hits, b.hits)) and bool(torch.equal(a.totals, b.totals))
+            res["fused_same_rows_as_two_calls"] = fused_same
         # the rows of the last timed step behind each planned figure (timed_region ends in a synchronize): --dump-outputs writes
         # those of the figure the headline reports
         res["regions"], res["timed_rows"] = {}, {}
         for name, n_lanes in (("ms_planned_two_streams", 2), ("ms_planned_one_stream", 1)):
             res["regions"][name] = timed(n_lanes, "fused")
             res["timed_rows"][name] = (merged["hits"].clone(), merged["totals"].clone())
-        if full:
+        if variants:
             res["regions"]["ms_two_calls_two_streams"] = timed(2, "array")
             res["regions"]["ms_two_calls_one_stream"] = timed(1, "array")
             res["regions"]["ms_resident_plan_two_streams"] = timed(2, False)
@@ -488,7 +506,7 @@ def main():
             res["regions"]["ms_object_planner_one_stream"] = timed(1, "objects", steps, 3)
         for name, reg in res["regions"].items():
             res[name] = reg["median"]
-        if full and not dist_mode:
+        if variants and not dist_mode:
             # ... and the same step back to back in ONE region of `steps` steps, without warm-up or median: the sustained rate next to
             # the median region. `--steps` sets its length, as it does every timed region's (seconds on end take --steps 100000 or so:
             # the regions above are 0.5 ms long each at --steps 20, and clocks / thermals have no time to settle in them).
@@ -504,22 +522,24 @@ def main():
             gc.enable()
             res["sustained"] = {"steps": n_sus, "seconds": el, "ms_per_step": 1e3 * el / n_sus, "queries_per_sec": nq * n_sus / el,
                                 "note": "the headline's planned two-stream step back to back, one timed region of `steps` steps"}
-        # isolated kernel durations: the same steps (the call the timed regions make) on ONE stream with HIP events around every launch
-        ctx.set_profiling(True)
-        ctx.kernel_stats_reset()
-        for _ in range(steps):
-            step_fused(1)
-        torch.cuda.synchronize()
-        stats = ctx.kernel_stats()
-        # MEDIAN launch duration (rgpu_kernel_stat.median_ms): round 5's mean over K launches read 1.775 ms on the driver's box for a
-        # kernel rocprofv3 times at 0.228 ms — one stalled launch multiplies a mean
-        res["kernels_ms"] = {n: s["median_ms"] for n, s in stats.items() if s["timed_launches"] > 0}
-        res["kernels_ms_min_max_mean"] = {n: [s["min_ms"], s["max_ms"], s["total_ms"] / max(1, s["timed_launches"])] for n, s in stats.items() if s["timed_launches"] > 0}
-        res["launches_per_step"] = {n: s["launches"] / steps for n, s in stats.items() if s["timed_launches"] > 0}
-        res["kernels_ms_per_step"] = {n: s["median_ms"] * s["launches"] / steps for n, s in stats.items() if s["timed_launches"] > 0}
+        if args.full:
+            # isolated kernel durations: the same steps (the call the timed regions make) on ONE stream with HIP events around every launch
+            ctx.set_profiling(True)
+            ctx.kernel_stats_reset()
+            for _ in range(steps):
+                step_fused(1)
+            torch.cuda.synchronize()
+            stats = ctx.kernel_stats()
+            # MEDIAN launch duration (rgpu_kernel_stat.median_ms): round 5's mean over K launches read 1.775 ms on one MI355X for a
+            # kernel rocprofv3 times at 0.228 ms — one stalled launch multiplies a mean
+            res["kernels_ms"] = {n: s["median_ms"] for n, s in stats.items() if s["timed_launches"] > 0}
+            res["kernels_ms_min_max_mean"] = {n: [s["min_ms"], s["max_ms"], s["total_ms"] / max(1, s["timed_launches"])] for n, s in stats.items() if s["timed_launches"] > 0}
+            res["launches_per_step"] = {n: s["launches"] / steps for n, s in stats.items() if s["timed_launches"] > 0}
+            res["kernels_ms_per_step"] = {n: s["median_ms"] * s["launches"] / steps for n, s in stats.items() if s["timed_launches"] > 0}
         res["counters"] = ctx.last_search_counters()   # of the last launch: what it decoded vs what its queries cover
-        ctx.set_profiling(False)
-        ctx.kernel_stats_reset()
+        if args.full:
+            ctx.set_profiling(False)
+            ctx.kernel_stats_reset()
         res["g_hits"] = merged["hits"].cpu().numpy().view(rucene_amd.HIT_DTYPE).reshape(nq, k).copy()
         res["g_totals"] = merged["totals"].cpu().numpy().copy()
         if args.force_dist and world == 1:  # a world of one: the gathered + merged rows must equal the plain local search
@@ -753,16 +773,15 @@ def main():
         finally:
             ctx_n.close()
 
-    def search_config(shard, kind, steps, warmup, full, tag, cpu_budget, cpu_sample, parity_queries):
-        """One search workload on one shard: throughput with planning in the timed region, the dominant kernel's roofline
-        from what it touched, decoded vs covered postings, the CPU leg and parity."""
+    def search_config(shard, kind, steps, warmup, variants, tag, cpu_budget, cpu_sample, parity_queries):
+        """One search workload on one shard: throughput with planning in the timed region, decoded vs covered postings; with
+        --full the dominant kernel's roofline from what it touched, the CPU leg and parity."""
         k = args.k if (args.k and kind == args.workload) else K_OF[kind]
-        r = measure(shard, kind, k, steps, warmup, full)
+        r = measure(shard, kind, k, steps, warmup, variants)
         two_wins = r["ms_planned_two_streams"] <= r["ms_planned_one_stream"]
         ms = r["ms_planned_two_streams"] if two_wins else r["ms_planned_one_stream"]
         dom = DOMINANT[kind]
         c = r["counters"]
-        kms = r["kernels_ms"].get(dom, 0.0)
         reported = "ms_planned_two_streams" if two_wins else "ms_planned_one_stream"
         reg = r["regions"][reported]
         out = {"workload": WORKLOAD_TEXT[kind], "k": k, "steps": steps, "ms_per_step": ms,
@@ -770,41 +789,44 @@ def main():
                "queries_per_sec": nq / (ms * 1e-3),
                "postings_covered_per_step": r["postings"], "postings_decoded_per_step": c["postings_decoded"],
                "postings_decoded_per_sec": c["postings_decoded"] / (ms * 1e-3), "postings_covered_per_sec": r["postings"] / (ms * 1e-3),
-               "issue": "two alternating streams" if two_wins else "one stream", "fused_same_rows_as_two_calls": r["fused_same_rows_as_two_calls"],
-               "kernels_ms_isolated": r["kernels_ms"]}
-        if kind == "or10":
-            # k_or_lazy walks the clauses without a doc bitmap (k_score_terms decodes them) and reads the others' bitmap words;
-            # queries without a bitmap clause, and the ones it hands back, go through k_or_wide (every posting decoded); queries
-            # flagged for the f32 floor are run again by the clause-order kernels
-            or_kernels = [n for n in ("k_score_terms", "k_or_lazy", "k_or_wide", "k_or_windows") if n in r["kernels_ms_per_step"]]
-            kms = sum(r["kernels_ms_per_step"][n] for n in or_kernels)
-            out["kernels_ms_per_step"] = r["kernels_ms_per_step"]
-            if c["touched_bytes"] > 0:
-                out["roofline"] = roofline(" + ".join(or_kernels), kms, c["touched_bytes"] + 8 * k * nq, r["algo_bytes"], tag,
-                                           "touched bytes: encoded bytes + 1 B norm per posting of the walked clauses (each distinct term of the batch "
-                                           "once), max_doc / 8 B of bitmap words per bitmap clause and query, every posting of the queries "
-                                           "k_or_wide took + 8 k B out")
+               "issue": "two alternating streams" if two_wins else "one stream"}
+        if args.full:
+            out["fused_same_rows_as_two_calls"] = r["fused_same_rows_as_two_calls"]
+            out["kernels_ms_isolated"] = r["kernels_ms"]
+            kms = r["kernels_ms"].get(dom, 0.0)
+            if kind == "or10":
+                # k_or_lazy walks the clauses without a doc bitmap (k_score_terms decodes them) and reads the others' bitmap words;
+                # queries without a bitmap clause, and the ones it hands back, go through k_or_wide (every posting decoded); queries
+                # flagged for the f32 floor are run again by the clause-order kernels
+                or_kernels = [n for n in ("k_score_terms", "k_or_lazy", "k_or_wide", "k_or_windows") if n in r["kernels_ms_per_step"]]
+                kms = sum(r["kernels_ms_per_step"][n] for n in or_kernels)
+                out["kernels_ms_per_step"] = r["kernels_ms_per_step"]
+                if c["touched_bytes"] > 0:
+                    out["roofline"] = roofline(" + ".join(or_kernels), kms, c["touched_bytes"] + 8 * k * nq, r["algo_bytes"], tag,
+                                               "touched bytes: encoded bytes + 1 B norm per posting of the walked clauses (each distinct term of the batch "
+                                               "once), max_doc / 8 B of bitmap words per bitmap clause and query, every posting of the queries "
+                                               "k_or_wide took + 8 k B out")
+                else:
+                    out["roofline"] = roofline(" + ".join(or_kernels), kms, r["algo_bytes"], None, tag,
+                                               "scan bytes: every clause's encoded blocks + tails + 1 B norm per posting + 8 k B out")
+            elif kind == "and3":
+                lead_postings = int(shard.seg.terms["doc_freq"][r["tids"]].min(axis=1).sum())
+                touched = c["touched_bytes"] + lead_postings + 8 * k * nq
+                out["roofline"] = roofline(dom, kms, touched, r["algo_bytes"], tag,
+                                           "touched bytes: encoded bytes of every block the kernel decoded (counted by the kernel) + 1 B norm per lead posting + 8 k B out")
             else:
-                out["roofline"] = roofline(" + ".join(or_kernels), kms, r["algo_bytes"], None, tag,
-                                           "scan bytes: every clause's encoded blocks + tails + 1 B norm per posting + 8 k B out")
-        elif kind == "and3":
-            lead_postings = int(shard.seg.terms["doc_freq"][r["tids"]].min(axis=1).sum())
-            touched = c["touched_bytes"] + lead_postings + 8 * k * nq
-            out["roofline"] = roofline(dom, kms, touched, r["algo_bytes"], tag,
-                                       "touched bytes: encoded bytes of every block the kernel decoded (counted by the kernel) + 1 B norm per lead posting + 8 k B out")
-        else:
-            touched = c["touched_bytes"] + 8 * k * nq
-            out["roofline"] = roofline(dom, kms, touched, r["algo_bytes"], tag,
-                                       "touched bytes, counted by the kernel: encoded bytes + norms of every block it unpacked + the directory entries it "
-                                       "requested (18 B per block of every 64-block chunk it visited, 8 B per chunk frontier, 2 B per sketch entry) + 8 k B out")
-            out["roofline"]["pruning"] = "%d of %d FullBlocks unpacked" % (c["blocks_decoded"], int((shard.seg.terms["doc_freq"][r["tids"].reshape(-1)] // 128).sum()))
-        # one isolated launch of the dominant kernel cannot take longer than a whole one-stream step that contains it (+ 20 % for the
-        # events' own cost): when it does, the event timing is off and the roofline says so instead of being believed
-        out["roofline"]["kernel_ms_min_max_mean"] = r["kernels_ms_min_max_mean"].get(dom)
-        out["roofline"]["kernel_ms_suspect"] = bool(kind != "or10" and kms > 1.2 * r["ms_planned_one_stream"])
-        # the step cannot have moved its bytes faster than the memory system allows
-        assert out["roofline"]["bytes_per_launch"] / (ms * 1e-3) / 1e9 <= HBM_PEAK_GBS, "bytes / ms_per_step exceeds the HBM peak"
-        if full:
+                touched = c["touched_bytes"] + 8 * k * nq
+                out["roofline"] = roofline(dom, kms, touched, r["algo_bytes"], tag,
+                                           "touched bytes, counted by the kernel: encoded bytes + norms of every block it unpacked + the directory entries it "
+                                           "requested (18 B per block of every 64-block chunk it visited, 8 B per chunk frontier, 2 B per sketch entry) + 8 k B out")
+                out["roofline"]["pruning"] = "%d of %d FullBlocks unpacked" % (c["blocks_decoded"], int((shard.seg.terms["doc_freq"][r["tids"].reshape(-1)] // 128).sum()))
+            # one isolated launch of the dominant kernel cannot take longer than a whole one-stream step that contains it (+ 20 % for the
+            # events' own cost): when it does, the event timing is off and the roofline says so instead of being believed
+            out["roofline"]["kernel_ms_min_max_mean"] = r["kernels_ms_min_max_mean"].get(dom)
+            out["roofline"]["kernel_ms_suspect"] = bool(kind != "or10" and kms > 1.2 * r["ms_planned_one_stream"])
+            # the step cannot have moved its bytes faster than the memory system allows
+            assert out["roofline"]["bytes_per_launch"] / (ms * 1e-3) / 1e9 <= HBM_PEAK_GBS, "bytes / ms_per_step exceeds the HBM peak"
+        if variants:
             out["streams"] = {k2: r[k2] for k2 in ("ms_planned_two_streams", "ms_planned_one_stream", "ms_two_calls_two_streams", "ms_two_calls_one_stream",
                                                    "ms_resident_plan_two_streams", "ms_resident_plan_one_stream", "ms_object_planner_one_stream")}
             if "sustained" in r:
@@ -814,11 +836,11 @@ def main():
                                       "weights, device descriptors, three enqueues) — the headline; two calls = rgpu_plan_uniform_ids then "
                                       "rgpu_search_batch_device (rounds 3-5's headline); resident plan = planned once, searched every step; "
                                       "object planner = one Python query object per query flattened first (GpuIndexSearcher.pack), then the native planner")
-        if kind == "or10" and world == 1 and not dist_mode:
+        if kind == "or10" and args.full and world == 1 and not dist_mode:
             out["deferred"] = or_deferred_leg(shard, k, steps, r)
-        if kind == "term" and full and world == 1 and not dist_mode:
+        if kind == "term" and variants and world == 1 and not dist_mode:
             out["without_sketches"] = no_sketch_leg(shard, k, steps, r)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             base, ok, info = cpu_baseline_leg(shard, kind, k, r, cpu_budget, cpu_sample, parity_queries)
             out["cpu_baseline"] = base
             out["gpu_over_cpu"] = out["queries_per_sec"] / base["value"]
@@ -1102,7 +1124,7 @@ def main():
 
     # ---- headline: BASELINE configs[1] (or --workload), one 10M-doc shard per rank -----------------------------------------
     shard = Shard(args.docs, rank, rank * args.docs, world)
-    head = search_config(shard, args.workload, args.steps, args.warmup, True, "%s_%s" % (ROUND, args.workload), 8.0, nq, nq)
+    head = search_config(shard, args.workload, args.steps, args.warmup, args.full, "%s_%s" % (ROUND, args.workload), 8.0, nq, nq)
     res = head["_res"]
     ms_per_step = head["ms_per_step"]
     if args.dump_outputs and rank == 0:
@@ -1129,36 +1151,37 @@ def main():
             "issue": "value = %s, every step plans its batch from term ids and enqueues it (one C-ABI call: rgpu_planner_search_uniform_ids_device); inputs (index) resident in HBM" % head["issue"],
         },
         "ms_per_step_min_median_max": head["ms_per_step_min_median_max"],
-        "streams": head["streams"],
-        "roofline": head["roofline"],
-        "kernels_ms_isolated": head["kernels_ms_isolated"],
     }
+    if args.full:
+        out["streams"] = head["streams"]
+        out["roofline"] = head["roofline"]
+        out["kernels_ms_isolated"] = head["kernels_ms_isolated"]
+        out["roofline"]["note"] = ("kernel_ms = average launch duration over K steps issued on one stream (HIP events; a separate pass, the timed "
+                                   "region carries no events). frac = bytes_per_launch (see bytes_are) / kernel_ms / peak. The north-star's >= 40 % "
+                                   "block-decode target is configs.block_decode / configs.cold / configs.out_of_cache")
+        # the fraction at the headline's OPERATING POINT (two launches co-resident on alternating streams): the same bytes over the
+        # step time — next to roofline.frac, which is one isolated launch (kernel_ms may exceed ms_per_step for that reason)
+        # a pruned top-k search, not a stream: better pruning lowers the touched bytes and with them `frac` while the launch gets shorter
+        out["roofline"]["across_rounds"] = ("pruned search: better pruning lowers touched bytes and frac while the launch gets shorter (r05: 36.0 MB / 0.037 ms = 0.12); compare kernel_ms across rounds; streaming kernel: block_decode_frac")
+        out["roofline"]["frac_at_ms_per_step"] = out["roofline"]["bytes_per_launch"] / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS
+        # how far the step is from its kernels: every kernel of one step — the plan's copy kernel (round 6), the dominant kernel, the item
+        # merge where it is still a launch of its own — as isolated median launches, vs the planned step (two streams overlap them: < 1)
+        kp = sum(v for n, v in head["kernels_ms_isolated"].items() if n in (DOMINANT[args.workload], "k_merge_items", "k_merge_lists", "k_stage_copy", "k_stage_term_plan"))
+        out["kernel_plus_merge_ms"] = kp
+        out["step_over_kernels"] = ms_per_step / kp if kp > 0 else None
+        out["step_over_kernels_one_stream"] = head["streams"]["ms_planned_one_stream"] / kp if kp > 0 else None
+        out["fused_same_rows_as_two_calls"] = head["fused_same_rows_as_two_calls"]
     if "without_sketches" in head:
         out["without_sketches"] = head["without_sketches"]
         out["without_sketches_queries_per_sec"] = head["without_sketches"]["queries_per_sec"]
         out["without_sketches_same_rows"] = head["without_sketches"]["same_rows_as_with_sketches"]
-    out["roofline"]["note"] = ("kernel_ms = average launch duration over K steps issued on one stream (HIP events; a separate pass, the timed "
-                               "region carries no events). frac = bytes_per_launch (see bytes_are) / kernel_ms / peak. The north-star's >= 40 % "
-                               "block-decode target is configs.block_decode / configs.cold / configs.out_of_cache")
     for key in ("cpu_baseline", "gpu_over_cpu", "parity_vs_oracle", "parity"):
         if key in head:
             out[key] = head[key]
-    # the fraction at the headline's OPERATING POINT (two launches co-resident on alternating streams): the same bytes over the
-    # step time — next to roofline.frac, which is one isolated launch (kernel_ms may exceed ms_per_step for that reason)
-    # a pruned top-k search, not a stream: better pruning lowers the touched bytes and with them `frac` while the launch gets shorter
-    out["roofline"]["across_rounds"] = ("pruned search: better pruning lowers touched bytes and frac while the launch gets shorter (r05: 36.0 MB / 0.037 ms = 0.12); compare kernel_ms across rounds; streaming kernel: block_decode_frac")
-    out["roofline"]["frac_at_ms_per_step"] = out["roofline"]["bytes_per_launch"] / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS
-    # how far the step is from its kernels: every kernel of one step — the plan's copy kernel (round 6), the dominant kernel, the item
-    # merge where it is still a launch of its own — as isolated median launches, vs the planned step (two streams overlap them: < 1)
-    kp = sum(v for n, v in head["kernels_ms_isolated"].items() if n in (DOMINANT[args.workload], "k_merge_items", "k_merge_lists", "k_stage_copy", "k_stage_term_plan"))
-    out["kernel_plus_merge_ms"] = kp
-    out["step_over_kernels"] = ms_per_step / kp if kp > 0 else None
-    out["step_over_kernels_one_stream"] = head["streams"]["ms_planned_one_stream"] / kp if kp > 0 else None
-    out["fused_same_rows_as_two_calls"] = head["fused_same_rows_as_two_calls"]
-    out["one_stream_ms_per_step"] = head["streams"]["ms_planned_one_stream"]
+    out["one_stream_ms_per_step"] = res["ms_planned_one_stream"]
     if "sustained" in head:
         out["sustained"] = head["sustained"]
-    out["one_stream_queries_per_sec"] = nq / (head["streams"]["ms_planned_one_stream"] * 1e-3)
+    out["one_stream_queries_per_sec"] = nq / (res["ms_planned_one_stream"] * 1e-3)
     # N > 1: the batch is replicated, so the ranks together answer nq queries over an index of world x docs — that rate next to
     # `value` (whose unit is one query against one segment)
     out["whole_index_docs"] = world * args.docs
@@ -1172,7 +1195,7 @@ def main():
 
     def sharded_overhead(shard, kind, k, steps):
         """What rgpu_search_batch_sharded adds to a step in a world of ONE rank (search into the rank's own region of the gather
-        buffer, nothing to gather, the record merge) — the path's own overhead, measured on every N = 1 run (VERDICT r4 item 1:
+        buffer, nothing to gather, the record merge) — the path's own overhead, measured on every --full run with N = 1 (VERDICT r4 item 1:
         0.157 vs 0.093 ms before the in-place record). Planned steps on two alternating streams and on one, local vs sharded."""
         c1 = _lib.Comm(ctx, 1, 0, _lib.comm_unique_id())
         # ... and with the collective REALLY issued (rgpu_config.comm_force_gather: the in-place ncclAllGather of a one-rank
@@ -1236,11 +1259,11 @@ def main():
         ctx_f.close()
         return res
 
-    if world == 1 and not dist_mode:
+    if args.full and world == 1 and not dist_mode:
         out["sharded_overhead"] = sharded_overhead(shard, args.workload, head["k"], 200)
 
-    # ---- north_star's other targets, same run ---------------------------------------------------------------------------------
-    if args.configs == "none":
+    # ---- north_star's other targets, same run (--full) ------------------------------------------------------------------------
+    if not args.full or args.configs == "none":
         want = set()
     elif world != 1 or dist_mode:
         want = {"and3"} if args.configs == "all" else (set(args.configs.split(",")) & {"and3", "or10"})   # BASELINE configs[4]'s workload on every N
@@ -1300,7 +1323,8 @@ def main():
         out["configs"] = configs
     if args.workload == "and3":
         out["and3_queries_per_sec"] = out["queries_per_sec"]
-        out["and3_roofline_frac"] = out["roofline"]["frac"]
+        if "roofline" in out:
+            out["and3_roofline_frac"] = out["roofline"]["frac"]
     if world > 1 and "and3" in configs:
         out["and3_whole_index_queries_per_sec"] = configs["and3"]["queries_per_sec"]
         out["and3_whole_index_docs"] = world * args.docs
@@ -1312,7 +1336,7 @@ def main():
     detail_paths = [args.detail] if args.detail else [os.path.join(ROOT, "bench_detail.json")]
     if not args.detail and os.path.isdir(os.path.join(ROOT, "gpurun_out")):
         detail_paths.append(os.path.join(ROOT, "gpurun_out", "bench_detail.json"))
-    text = final_line(full, os.path.basename(detail_paths[0])) if rank == 0 else ""
+    text = final_line(full, os.path.basename(detail_paths[0]), LINE_REQUIRED if args.full else LINE_REQUIRED_PLAIN) if rank == 0 else ""
     if rank == 0:
         for path in detail_paths:
             try:

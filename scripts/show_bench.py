@@ -23,7 +23,7 @@ print({k: d.get(k) for k in ("value", "ms_per_step", "parity_vs_oracle_full_batc
 print("hoisted", {k: (round(v, 4) if isinstance(v, float) else v) for k, v in d.items() if k.startswith(("and3_", "or10_", "big_", "cold_", "block_decode_", "sloppy2_", "phrase2_", "one_stream", "whole_index"))})
 print("sharded_overhead", d.get("sharded_overhead"))
 print("streams", d.get("streams"))
-print("roofline", rl(d["roofline"]))
+print("roofline", rl(d.get("roofline", {})))   # (a run without --full has none)
 print("parity", d.get("parity"))
 print("cpu", d.get("cpu_baseline"))
 for k, c in d.get("configs", {}).items():

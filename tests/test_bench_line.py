@@ -79,6 +79,23 @@ def test_line_refuses_a_tree_without_the_contract_keys():
         bench.final_line(full)
 
 
+def test_plain_line_needs_no_roofline_and_keeps_the_contract_keys():
+    """a run without --full has no kernel event pass, so no roofline: its line must still carry every other contract key"""
+    full = _tree()
+    for key in ("roofline", "cpu_baseline", "parity", "configs", "streams", "latency_batch_of_one", "sharded_overhead"):
+        full.pop(key, None)
+    line = json.loads(bench.final_line(full, required=bench.LINE_REQUIRED_PLAIN))
+    assert "roofline" not in line and "cpu_baseline" not in line
+    for key in bench.LINE_REQUIRED_PLAIN:
+        assert key in line, key
+    assert line["metric"] == full["metric"] and line["higher_is_better"] is True and abs(line["value"] - full["value"]) <= 1e-4 * full["value"]
+    with pytest.raises(AssertionError):
+        bench.final_line(full)   # the --full requirements still ask for the roofline
+    full["ms_per_step"] = None
+    with pytest.raises(AssertionError):
+        bench.final_line(full, required=bench.LINE_REQUIRED_PLAIN)
+
+
 def test_jsonable_drops_private_keys_and_numpy_types():
     import numpy as np
     tree = {"a": np.float32(1.5), "b": np.arange(3), "_rows": np.zeros(4), "c": {"_x": 1, "y": float("inf")}, 7: (np.int64(2),)}
@@ -120,3 +137,10 @@ def test_steps_below_one_is_refused():
     import subprocess
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
     assert p.returncode == 2 and "--steps" in p.stderr
+
+
+def test_configs_without_full_is_refused():
+    """a plain run measures the headline alone: asking it for configs is an error, not a silent no-op"""
+    import subprocess
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--configs", "and3"], capture_output=True, text=True)
+    assert p.returncode == 2 and "--full" in p.stderr
