@@ -11,9 +11,10 @@ import os
 import numpy as np
 import pytest
 
+from norm_spectrum import _byte315_to_float, bm25_f64  # noqa: F401 (one copy, shared with the norm-spectrum fixtures)
+
 pytestmark = pytest.mark.gpu
 
-K1, B = 1.2, 0.75
 FULL_BLOCKS = 9000           # one item of the largest sizes spans three 4096-block windows
 TAIL = 77                    # VInt tail: df is not a multiple of 128
 DF = 128 * FULL_BLOCKS + TAIL
@@ -25,26 +26,6 @@ WINNERS = [(0, 6, 124), (4095, 9, 120), (4096, 10, 124), (4097, 8, 120), (8191, 
            (FULL_BLOCKS - 1, 9, 124), ("tail", 8, 124)]
 LOSER = (2080, 3, 110)       # mid-chunk (chunk 32, lane 32): above the background, below every winner — pruned for k <= 8
 OUT_OF_TABLE = 1000          # the out-of-table variant: the winner at block 4097 gets this freq (> SCORE_TABLE_FREQS)
-
-
-def _byte315_to_float(b):
-    b = np.asarray(b, dtype=np.uint32)
-    bits = ((b & 0xFF) << 21) + ((63 - 15) << 24)
-    return np.where(b == 0, 0.0, bits.astype(np.uint32).view(np.float32).astype(np.float64))
-
-
-def bm25_f64(df, doc_count, avgdl, freq, norm_byte):
-    """Plain BM25 in float64 (bm25_similarity.rs: idf, the 1 / f^2 length table, k1 (1 - b + b dl / avgdl)); norm_byte None: no norms."""
-    idf = np.log(1.0 + (doc_count - df + 0.5) / (df + 0.5))
-    freq = np.asarray(freq, dtype=np.float64)
-    if norm_byte is None:
-        norm = K1
-    else:
-        nb = np.asarray(norm_byte)
-        f = _byte315_to_float(np.where(nb == 0, 255, nb))
-        length = np.where(nb == 0, f * f, 1.0 / (f * f))  # table[0] = 1 / table[255]
-        norm = K1 * ((1.0 - B) + B * length / avgdl)
-    return idf * (K1 + 1.0) * freq / (freq + norm)
 
 
 def _pos(block):
