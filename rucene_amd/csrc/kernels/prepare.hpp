@@ -618,7 +618,9 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_blocks(const uint8_t* 
     const uint32_t hdr = (uint32_t)readlane((int)my_hdr, j);
     const uint64_t p = t.start_fp + (uint64_t)(uint32_t)readlane((int)my_off, j);
     const uint32_t mis = (uint32_t)(p & 15u);
-    const uint32_t bytes = hdr_nonpf(hdr) ? 0u : mis + encoded_block_bytes(hdr) + 3u;  // (+3: the last row's fifth dword)
+    // (+3: the last row's fifth dword; + 4: the header word keeps no length for an all-equal FREQ stream's VInt and
+    // encoded_block_bytes counts it as one byte — it has up to five, and vint_from_words reads them out of the staged rows)
+    const uint32_t bytes = hdr_nonpf(hdr) ? 0u : mis + encoded_block_bytes(hdr) + 3u + (hdr_bfreq(hdr) ? 0u : 4u);
     const uint8_t* a = doc + (p - mis);
     Staged s;
     s.r0 = make_uint4(0u, 0u, 0u, 0u);
