@@ -135,7 +135,20 @@ typedef struct rgpu_query_term {
 typedef enum rgpu_query_op {
   RGPU_OP_TERM = 0, /* TermQuery                      -> TermScorer (term_scorer.rs:43-67) */
   RGPU_OP_AND = 1,  /* BooleanQuery, all MUST         -> ConjunctionScorer (conjunction_scorer.rs:26-128) */
-  RGPU_OP_OR = 2    /* BooleanQuery, all SHOULD         -> DisjunctionSumScorer (disjunction_scorer.rs:24-104) */
+  RGPU_OP_OR = 2,   /* BooleanQuery, all SHOULD         -> DisjunctionSumScorer (disjunction_scorer.rs:24-104) */
+  RGPU_OP_DISMAX = 3 /* DisjunctionMaxQuery of TermQuerys -> DisjunctionMaxScorer (query/disjunction_max_query.rs:142-161,
+                        scorer/disjunction_scorer.rs:106-185, 246-286): n_terms = 1..RGPU_MAX_QUERY_TERMS disjuncts, weight /
+                        sim_table per clause as for OR. The docs and total_hits are those of the OR query over the same clauses;
+                        a doc's score is max + (sum - max) * tie_breaker_multiplier over the clauses that hold it, sum and max
+                        taken in clause order in f32 — bit-equal to the reference while fewer than 10 disjuncts exist in the leaf
+                        (SimpleQueue, :248-262; one disjunct left = that TermScorer's score). With 10 or more the reference sums in
+                        DisiPriorityQueue order (:264-283) and pins the sum no tighter than 1e-5 relative; the sum stays in clause
+                        order here, and with a multiplier of 0 the score is the maximum bit for bit whatever the count. A dismax
+                        query has no MUST_NOT clauses: rgpu_query.n_must_not carries the BIT PATTERN of the f32
+                        tie_breaker_multiplier (finite, else RGPU_ERR_ILLEGAL_ARGUMENT). No other byte of `op` may be set
+                        (RGPU_ERR_ILLEGAL_ARGUMENT). Served by rgpu_search_batch and its _device / _sharded / _record forms, mixed
+                        freely with the other ops, any k up to RGPU_MAX_K; the planner entry points (rgpu_plan_*,
+                        rgpu_planner_search_*) and rgpu_rescore_batch answer RGPU_ERR_UNSUPPORTED for it */
 } rgpu_query_op;
 /* rgpu_query.op for an OR query may carry BooleanQuery's min_should_match in its second byte:
  * RGPU_OP_OR | (msm << 8). 0 and 1 are the default (any clause matches); msm >= 2 collects only docs held by at least
@@ -192,7 +205,9 @@ typedef struct rgpu_query {
   int32_t n_must_not;  /* MUST_NOT TermQuery clauses, stored right after the positive ones (weight / sim_table unused):
                           BooleanWeight::create_scorer wraps the positive scorer in a ReqNotScorer over their union
                           (query/boolean_query.rs:235-273, scorer/req_not_scorer.rs:20-120). 0 = none;
-                          n_terms + n_should + n_must_not <= RGPU_MAX_QUERY_TERMS */
+                          n_terms + n_should + n_must_not <= RGPU_MAX_QUERY_TERMS.
+                          RGPU_OP_DISMAX: not a count — the bit pattern of the query's f32 tie_breaker_multiplier
+                          (DisjunctionMaxQuery::tie_breaker_multiplier, query/disjunction_max_query.rs:43-48; 0 = the plain maximum) */
 } rgpu_query;
 
 /* sort_field/collapse_top_docs.rs:22-36 ScoreDoc */

@@ -120,6 +120,30 @@ struct BooleanQuery : Query {
   }
 };
 
+// query/disjunction_max_query.rs:43-114: the union of the disjuncts' docs, each scored max + (sum - max) * tie_breaker_multiplier over
+// the disjuncts that hold it (DisjunctionMaxScorer, scorer/disjunction_scorer.rs:106-185, 246-286). TermQuery disjuncts only here
+// (RGPU_OP_DISMAX); a dismax over other queries is the caller's CPU path.
+struct DisjunctionMaxQuery : Query {
+  std::vector<TermQuery> disjuncts;
+  float tie_breaker_multiplier;
+  explicit DisjunctionMaxQuery(std::vector<TermQuery> d, float tie = 0.0f) : disjuncts(std::move(d)), tie_breaker_multiplier(tie) {
+    if (disjuncts.empty()) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "DisjunctionMaxQuery: sub query should not be empty!");  // ::build, :51-68
+  }
+  // DisjunctionMaxQuery::build: a lone disjunct IS that query
+  static std::unique_ptr<Query> build(std::vector<TermQuery> d, float tie = 0.0f) {
+    std::unique_ptr<DisjunctionMaxQuery> q(new DisjunctionMaxQuery(std::move(d), tie));
+    if (q->disjuncts.size() == 1) return std::unique_ptr<Query>(new TermQuery(q->disjuncts[0]));
+    return std::unique_ptr<Query>(q.release());
+  }
+  // rgpu_query.n_must_not of an RGPU_OP_DISMAX query: the multiplier's f32 bit pattern
+  int32_t tie_bits() const {
+    int32_t bits;
+    std::memcpy(&bits, &tie_breaker_multiplier, sizeof bits);
+    return bits;
+  }
+  std::vector<TermQuery> extract_terms() const { return disjuncts; }  // :91-97
+};
+
 // A BooleanQuery whose MUST / SHOULD clauses may themselves be queries (BooleanQuery::build takes Vec<Box<dyn Query>>,
 // boolean_query.rs:40-86). The GPU path serves flat trees of term clauses; `flattened()` folds ONE level — a MUST clause that is
 // a must-only BooleanQuery, a SHOULD clause that is a should-only one (min_should_match <= 1) — into a flat BooleanQuery, or
@@ -706,6 +730,10 @@ class GpuIndexSearcher {
         for (const TermQuery& c : (conj ? b->must_queries : b->should_queries)) clause(c);
         if (conj) for (const TermQuery& c : b->should_queries) clause(c);
         for (const TermQuery& c : b->must_not_queries) clause(c);
+      } else if (auto* d = dynamic_cast<const DisjunctionMaxQuery*>(q)) {
+        // (the planner resolves and weighs the disjuncts as an OR query's clauses; op and tie-breaker are written below)
+        ops.push_back(RGPU_OP_OR); n_terms.push_back(static_cast<int32_t>(d->disjuncts.size())); n_not.push_back(0);
+        for (const TermQuery& c : d->disjuncts) clause(c);
       } else {
         throw Error(RGPU_ERR_UNSUPPORTED, "query type not served by the GPU path");
       }
@@ -738,6 +766,11 @@ class GpuIndexSearcher {
       check(rgpu_plan_batch_ids(planners_[pi], static_cast<int32_t>(queries.size()), ops.data(), n_terms.data(), n_not.data(), ids.data(),
                                 any_boost ? boosts.data() : nullptr, qs->data(), ts->data(), cap));
     ts->resize(ids.size());
+    // the second half of a dismax query's packing (the first: the RGPU_OP_OR entry pushed above): the planner knows no op 3, so it
+    // resolved and weighed the disjuncts as SHOULD clauses — and rewrote a one-clause query to RGPU_OP_TERM; op and the tie-breaker's
+    // bits are written over its records here. pack() writes the same two fields directly.
+    for (size_t i = 0; i < queries.size(); ++i)
+      if (auto* d = dynamic_cast<const DisjunctionMaxQuery*>(queries[i])) { (*qs)[i].op = RGPU_OP_DISMAX; (*qs)[i].n_must_not = d->tie_bits(); }
   }
   void pack(const Query& q, const LeafReader& leaf, std::vector<rgpu_query>* qs, std::vector<rgpu_query_term>* ts) {
     const std::vector<TermQuery>* clauses = nullptr;
@@ -754,6 +787,9 @@ class GpuIndexSearcher {
       clauses = b->must_queries.empty() ? &b->should_queries : &b->must_queries;
       if (!b->must_queries.empty()) opts = &b->should_queries;
       nots = &b->must_not_queries;
+    } else if (auto* d = dynamic_cast<const DisjunctionMaxQuery*>(&q)) {
+      op = RGPU_OP_DISMAX;
+      clauses = &d->disjuncts;
     } else {
       throw Error(RGPU_ERR_UNSUPPORTED, "query type not served by the GPU path");
     }
@@ -762,6 +798,7 @@ class GpuIndexSearcher {
     if (nots) all.insert(all.end(), nots->begin(), nots->end());
     rgpu_query rq{op, static_cast<int32_t>(clauses->size()), static_cast<int32_t>(ts->size()),
                   static_cast<int32_t>(nots ? nots->size() : 0)};
+    if (auto* d = dynamic_cast<const DisjunctionMaxQuery*>(&q)) rq.n_must_not = d->tie_bits();  // RGPU_OP_DISMAX: the tie-breaker's bits
     for (const TermQuery& c : all) {
       rgpu_query_term qt{};
       if (!leaf.term_state(c, &qt.state)) { qt.state = rgpu_term_state{}; qt.state.skip_offset = -1; qt.state.singleton_doc_id = -1; }

@@ -112,9 +112,19 @@ constexpr uint32_t OR_UNTOUCHED = 0xffffffffu;  // accumulator patterns no sum o
 constexpr uint32_t OR_EXCLUDED = 0xfffffffeu;
 static_assert(OR_DENSE_MAX <= OR_WAVES, "wave w of a workgroup builds dense clause w's score table");
 
-__host__ __device__ constexpr size_t or_wave_lds_bytes(int W, bool msm) { return (size_t)(2 * SLAB_STREAM) + (size_t)W * (msm ? 5 : 4); }
-__host__ __device__ constexpr size_t or_lds_bytes(int W, bool msm) {
-  return (size_t)OR_DENSE_MAX * WAVE_CACHE_FLOATS * 4 + (size_t)OR_WAVES * or_wave_lds_bytes(W, msm);
+// (mx: the dismax instantiation keeps a second f32 per doc cell, the running maximum)
+__host__ __device__ constexpr size_t or_wave_lds_bytes(int W, bool msm, bool mx = false) {
+  return (size_t)(2 * SLAB_STREAM) + (size_t)W * (msm ? 5 : 4) + (mx ? (size_t)W * 4 : 0);
+}
+__host__ __device__ constexpr size_t or_lds_bytes(int W, bool msm, bool mx = false) {
+  return (size_t)OR_DENSE_MAX * WAVE_CACHE_FLOATS * 4 + (size_t)OR_WAVES * or_wave_lds_bytes(W, msm, mx);
+}
+constexpr size_t OR_LDS_MAX = 160 * 1024;  // a CU's LDS: the most one workgroup can ask for
+// the widest window (a multiple of 256 docs, at most `want`) whose launch fits a CU's LDS
+inline int or_fit_window(int want, bool msm, bool mx) {
+  int W = want;
+  while (W > 256 && or_lds_bytes(W, msm, mx) > OR_LDS_MAX) W -= 256;
+  return W;
 }
 
 // items = (query, group of `windows_per_item` windows of `W` docs), one per wavefront; items_per_query is a multiple
@@ -123,29 +133,31 @@ __host__ __device__ constexpr size_t or_lds_bytes(int W, bool msm) {
 // HAS_NOT: some query of the launch carries MUST_NOT clauses; HAS_MSM: some query asks for min_should_match > 1
 // (disjunction_scorer.rs:317-329: a doc is a hit only if that many SHOULD clauses hold it — a per-doc clause counter
 // next to the accumulator). Separate instantiations keep the common kernel lean.
-template <bool LEGACY, bool WIDE, bool HAS_NOT, bool HAS_MSM>
-__global__ __launch_bounds__(OR_THREADS, 6) void k_or_windows(SegView seg, const DevQuery* __restrict__ queries,
-                                                              const DevTerm* __restrict__ terms,
-                                                              const int64_t* __restrict__ run_prefix,
-                                                              const ScoredPosting* __restrict__ runs, int n_queries,
-                                                              int windows_per_query, int windows_per_item,
-                                                              int items_per_query, int W, int k,
-                                                              uint64_t* __restrict__ partial_keys,
-                                                              int32_t* __restrict__ partial_counts,
-                                                              unsigned long long* __restrict__ tau_slots,
-                                                              const unsigned long long* __restrict__ ceil_slots = nullptr,
-                                                              const int32_t* __restrict__ qmap = nullptr) {
+// HAS_MAX (k_or_windows_max, without HAS_NOT / HAS_MSM): DisjunctionMaxScorer (disjunction_scorer.rs:106-185) — the same union,
+// the same clause-order sum, and next to it the per-doc maximum of the clause scores; a doc's score is
+// max + (sum - max) * tie_breaker_multiplier (SubScorers::score_max, :246-286), the multiplier's bits in DevQuery::pad.
+template <bool LEGACY, bool WIDE, bool HAS_NOT, bool HAS_MSM, bool HAS_MAX>
+__device__ __forceinline__ void or_windows_body(const SegView& seg, const DevQuery* __restrict__ queries,
+                                                const DevTerm* __restrict__ terms, const int64_t* __restrict__ run_prefix,
+                                                const ScoredPosting* __restrict__ runs, int n_queries, int windows_per_query,
+                                                int windows_per_item, int items_per_query, int W, int k,
+                                                uint64_t* __restrict__ partial_keys, int32_t* __restrict__ partial_counts,
+                                                unsigned long long* __restrict__ tau_slots,
+                                                const unsigned long long* __restrict__ ceil_slots,
+                                                const int32_t* __restrict__ qmap) {
+  static_assert(!HAS_MAX || (!HAS_NOT && !HAS_MSM), "a dismax query has neither MUST_NOT clauses nor a min_should_match");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = lane_id();
   const int wave = wave_id();
   // LDS: [OR_DENSE_MAX score tables (norm cache 64 f32 + 64 x 11 scores)] then per wave [block staging slab | acc[W] f32
-  // | cnt[W] u8 (HAS_MSM)]. An untouched accumulator holds OR_UNTOUCHED, a NaN pattern no sum of scores produces; the
+  // | cnt[W] u8 (HAS_MSM) or mx[W] f32 (HAS_MAX)]. An untouched accumulator holds OR_UNTOUCHED, a NaN pattern no sum of scores produces; the
   // scan at the end of a window puts it back, so there is no per-doc flag array and no clearing pass.
   float* tables = reinterpret_cast<float*>(smem);
-  uint8_t* slice = smem + (size_t)OR_DENSE_MAX * WAVE_CACHE_FLOATS * 4 + (size_t)wave * or_wave_lds_bytes(W, HAS_MSM);
+  uint8_t* slice = smem + (size_t)OR_DENSE_MAX * WAVE_CACHE_FLOATS * 4 + (size_t)wave * or_wave_lds_bytes(W, HAS_MSM, HAS_MAX);
   uint8_t* slab = slice;
   float* acc = reinterpret_cast<float*>(slice + 2 * SLAB_STREAM);
   uint8_t* cnt = reinterpret_cast<uint8_t*>(acc + W);  // HAS_MSM only: SHOULD clauses that hold the doc
+  float* mx = acc + W;  // HAS_MAX only: the largest clause score of the doc; valid wherever acc is not "untouched", so never cleared
   // Workgroup b works on query b % n_queries: a query's workgroups are spread over the whole launch instead of running
   // side by side, so all but the first one or two start from the thresholds the earlier ones published (SharedTau) —
   // query-major order made every wavefront build its own top-k from nothing, ~460 insertions each, which was over half
@@ -187,6 +199,7 @@ __global__ __launch_bounds__(OR_THREADS, 6) void k_or_windows(SegView seg, const
   // (boolean_query.rs:271-273, req_not_scorer.rs:47-63) — their docs are marked excluded before anything is summed.
   const int n_not = HAS_NOT ? Q.pad : 0;
   const int msm = HAS_MSM ? ((Q.op >> 8) & 0xff) : 1;
+  const float tie = HAS_MAX ? __int_as_float(Q.pad) : 0.0f;  // tie_breaker_multiplier (finite: checked by the host)
   const int n_pos = Q.n_terms + n_not;  // clause positions of a window, in summation order
   const bool mine = lane < n_pos;
   const int my_clause = lane < n_not ? Q.n_terms + lane : lane - n_not;
@@ -254,6 +267,7 @@ __global__ __launch_bounds__(OR_THREADS, 6) void k_or_windows(SegView seg, const
         } else if (!HAS_NOT || ab != OR_EXCLUDED) {
           acc[o] = (first ? 0.0f : a) + sc;  // 0.0f + s: the reference's `score = 0; score += s`
           if (HAS_MSM) cnt[o] = first ? (uint8_t)1 : (uint8_t)(cnt[o] + 1);
+          if (HAS_MAX) mx[o] = first ? sc : fmaxf(mx[o], sc);  // score_max = score_max.max(sub_score), from -inf
         }
       }
     };
@@ -335,7 +349,7 @@ __global__ __launch_bounds__(OR_THREADS, 6) void k_or_windows(SegView seg, const
     if (touched_any && RGPU_OR_ABL != 2) {
       for (uint32_t i0 = 0; i0 < wlen; i0 += 256) {  // uniform trip count: the offer is a wave-wide operation
         float4* cell = reinterpret_cast<float4*>(acc + i0 + 4 * lane);
-        const float4 v = *cell;
+        float4 v = *cell;
         const uint32_t r0 = __float_as_uint(v.x), r1 = __float_as_uint(v.y), r2 = __float_as_uint(v.z), r3 = __float_as_uint(v.w);
         if (__ballot((r0 & r1 & r2 & r3) != OR_UNTOUCHED)) {
           // >= OR_EXCLUDED: untouched or excluded — no hit
@@ -349,6 +363,13 @@ __global__ __launch_bounds__(OR_THREADS, 6) void k_or_windows(SegView seg, const
           }
           hits_lane += (int)h0 + (int)h1 + (int)h2 + (int)h3;
           *cell = make_float4(__uint_as_float(OR_UNTOUCHED), __uint_as_float(OR_UNTOUCHED), __uint_as_float(OR_UNTOUCHED), __uint_as_float(OR_UNTOUCHED));
+          if (HAS_MAX) {  // score_max + (score_sum - score_max) * tie: three f32 operations (cells that are no hit hold anything)
+            const float4 m = *reinterpret_cast<const float4*>(mx + i0 + 4 * lane);
+            v.x = m.x + (v.x - m.x) * tie;
+            v.y = m.y + (v.y - m.y) * tie;
+            v.z = m.z + (v.z - m.z) * tie;
+            v.w = m.w + (v.w - m.w) * tie;
+          }
           // candidates: score order bits against the entry threshold's before any key is built
           const uint32_t thi = (uint32_t)(tau >> 32);
           const uint32_t o0 = float_order_bits(v.x), o1 = float_order_bits(v.y), o2 = float_order_bits(v.z), o3 = float_order_bits(v.w);
@@ -375,6 +396,39 @@ __global__ __launch_bounds__(OR_THREADS, 6) void k_or_windows(SegView seg, const
   if (WIDE && lane + 64 < k) pk[lane + 64] = top.b;
   const int count = wave_reduce_add(hits_lane);
   if (lane == 0) partial_counts[item] = count;
+}
+
+template <bool LEGACY, bool WIDE, bool HAS_NOT, bool HAS_MSM>
+__global__ __launch_bounds__(OR_THREADS, 6) void k_or_windows(SegView seg, const DevQuery* __restrict__ queries,
+                                                              const DevTerm* __restrict__ terms,
+                                                              const int64_t* __restrict__ run_prefix,
+                                                              const ScoredPosting* __restrict__ runs, int n_queries,
+                                                              int windows_per_query, int windows_per_item,
+                                                              int items_per_query, int W, int k,
+                                                              uint64_t* __restrict__ partial_keys,
+                                                              int32_t* __restrict__ partial_counts,
+                                                              unsigned long long* __restrict__ tau_slots,
+                                                              const unsigned long long* __restrict__ ceil_slots = nullptr,
+                                                              const int32_t* __restrict__ qmap = nullptr) {
+  or_windows_body<LEGACY, WIDE, HAS_NOT, HAS_MSM, false>(seg, queries, terms, run_prefix, runs, n_queries, windows_per_query, windows_per_item,
+                                                         items_per_query, W, k, partial_keys, partial_counts, tau_slots, ceil_slots, qmap);
+}
+
+// DisjunctionMaxQuery over term clauses: the window kernel with the per-doc maximum next to the sum
+template <bool LEGACY, bool WIDE>
+__global__ __launch_bounds__(OR_THREADS, 6) void k_or_windows_max(SegView seg, const DevQuery* __restrict__ queries,
+                                                                  const DevTerm* __restrict__ terms,
+                                                                  const int64_t* __restrict__ run_prefix,
+                                                                  const ScoredPosting* __restrict__ runs, int n_queries,
+                                                                  int windows_per_query, int windows_per_item,
+                                                                  int items_per_query, int W, int k,
+                                                                  uint64_t* __restrict__ partial_keys,
+                                                                  int32_t* __restrict__ partial_counts,
+                                                                  unsigned long long* __restrict__ tau_slots,
+                                                                  const unsigned long long* __restrict__ ceil_slots = nullptr,
+                                                                  const int32_t* __restrict__ qmap = nullptr) {
+  or_windows_body<LEGACY, WIDE, false, false, true>(seg, queries, terms, run_prefix, runs, n_queries, windows_per_query, windows_per_item,
+                                                    items_per_query, W, k, partial_keys, partial_counts, tau_slots, ceil_slots, qmap);
 }
 
 }  // namespace rgpu

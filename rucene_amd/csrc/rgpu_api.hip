@@ -1806,6 +1806,8 @@ static void ensure_memb_only_locked(rgpu_segment* seg, const rgpu_term_state* co
 }
 
 // ---- search ----------------------------------------------------------------------------------------------------
+// rgpu_query.n_must_not as a clause count: a dismax query has no MUST_NOT clauses, the field carries its tie-breaker there
+static inline int query_n_must_not(const rgpu_query& Q) { return (Q.op & 0xff) == RGPU_OP_DISMAX ? 0 : Q.n_must_not; }
 namespace {
 struct Group {  // queries of one op, in their original order
   int op = 0;
@@ -1813,6 +1815,7 @@ struct Group {  // queries of one op, in their original order
   bool no_lazy = false;         // ... that k_or_lazy already declined (no bitmap clause) or handed back
   bool after_lazy = false;      // ... following a k_or_lazy launch of the same call (rgpu_last_search_counters adds them up)
   std::vector<int64_t> term_bytes;  // or_wide: per clause, the encoded bytes of its postings (rgpu_last_search_counters)
+  bool dismax = false;          // DisjunctionMaxQuery over term clauses: the window kernel's max + tie-breaker instantiation, whatever the clause count
   bool req_opt = false;         // MUST + SHOULD trees under the reference's ReqOptScorer rule: conjunction records + sequential scan
   std::vector<int32_t> qmap;    // original query index
   std::vector<DevQuery> queries;
@@ -1834,6 +1837,8 @@ static void launch_merge(rgpu_ctx* c, hipStream_t s, int n_queries, int k, const
 }
 
 // OR: score every clause once into {doc, score} runs, then accumulate per doc-id window (kernels/search_or.hpp)
+// A dismax group (G.dismax) takes the same path — the same runs, dense clauses, items and merge — through k_or_windows_max, whose
+// accumulator cell is twice as wide: the window is narrowed until the launch fits a CU's LDS, and the plan follows the narrowed one.
 static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* hits_dev, int64_t* totals_dev, hipStream_t stream) {
   rgpu_ctx* c = seg->ctx;
   const int nq = (int)G.queries.size();
@@ -1847,7 +1852,9 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
   // in every window it reaches into, so a sparser list is cheaper through a run. On a Zipfian query those few lists
   // hold most of the postings; every other clause (and every tail) goes through a run. Needs the per-clause LDS score
   // table, i.e. norms held as ranks.
-  const int W = std::min(4096, std::max(256, c->cfg.or_window_docs > 0 ? (c->cfg.or_window_docs + 255) / 256 * 256 : 1024));
+  // (dismax: 512 docs by default — the LDS, and so the workgroups per CU, of the plain kernel's 1024)
+  const int W_cfg = std::min(4096, std::max(256, c->cfg.or_window_docs > 0 ? (c->cfg.or_window_docs + 255) / 256 * 256 : (G.dismax ? 512 : 1024)));
+  const int W = G.dismax ? or_fit_window(W_cfg, false, true) : W_cfg;
   const int dense_max = c->cfg.or_dense_clauses < 0 ? 0 : (c->cfg.or_dense_clauses == 0 ? OR_DENSE_MAX : std::min(c->cfg.or_dense_clauses, OR_DENSE_MAX));
   if (dense_max > 0 && seg->d_norms && seg->n_norm_ranks > 0) {
     for (DevQuery& dq : G.queries) {
@@ -1937,10 +1944,10 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
       RGPU_LAUNCH(k_score_terms<false>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, dt, dip, drp, nt, items1, blocks_per_item, runs_buf.p);
   }
   {
-    TimedLaunch tl(c, stream, "k_or_windows", G.postings);
-    bool has_not = false, has_msm = false;
-    for (const DevQuery& dq : G.queries) { has_not = has_not || dq.pad != 0; has_msm = has_msm || ((dq.op >> 8) & 0xff) > 1; }
-    const size_t lds = or_lds_bytes(W, has_msm);
+    TimedLaunch tl(c, stream, G.dismax ? "k_or_windows_max" : "k_or_windows", G.postings);
+    bool has_not = false, has_msm = false;  // (a dismax query has neither: its DevQuery::pad holds the tie-breaker's bits)
+    if (!G.dismax) for (const DevQuery& dq : G.queries) { has_not = has_not || dq.pad != 0; has_msm = has_msm || ((dq.op >> 8) & 0xff) > 1; }
+    const size_t lds = or_lds_bytes(W, has_msm, G.dismax);
     const unsigned grid = (unsigned)(items2 / OR_WAVES);  // exact: items_per_query is a multiple of OR_WAVES
     auto go = [&](auto kern) -> hipError_t {
       hipError_t e = set_dynamic_lds_once(c, reinterpret_cast<const void*>(kern), lds);
@@ -1951,6 +1958,7 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
     };
     auto pick = [&](auto legacy_tag) -> hipError_t {
       constexpr bool LG = decltype(legacy_tag)::value;
+      if (G.dismax) return wide ? go(k_or_windows_max<LG, true>) : go(k_or_windows_max<LG, false>);
       if (has_msm)  // min_should_match > 1 somewhere: the general instantiation (it also handles MUST_NOT clauses)
         return wide ? go(k_or_windows<LG, true, true, true>) : go(k_or_windows<LG, false, true, true>);
       if (has_not) return wide ? go(k_or_windows<LG, true, true, false>) : go(k_or_windows<LG, false, true, false>);
@@ -2720,7 +2728,15 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
   for (int32_t q = 0; q < n_queries; ++q) {
     const rgpu_query& Q = queries[q];
     const int qop = Q.op & 0xff, qmsm = (Q.op >> 8) & 0xff, qopt = (Q.op >> 16) & 0xff;
-    if (qop < RGPU_OP_TERM || qop > RGPU_OP_OR || (Q.op & ~(0xffffff | RGPU_OP_SHOULD_REQUIRED | RGPU_OP_NESTED_MUST | RGPU_OP_NESTED_AT(63))) != 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown query op");
+    if (qop < RGPU_OP_TERM || qop > RGPU_OP_DISMAX || (Q.op & ~(0xffffff | RGPU_OP_SHOULD_REQUIRED | RGPU_OP_NESTED_MUST | RGPU_OP_NESTED_AT(63))) != 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown query op");
+    if (qop == RGPU_OP_DISMAX) {
+      // DisjunctionMaxQuery: term disjuncts alone, no other byte of `op` means anything; n_must_not carries the tie-breaker's bits
+      if ((Q.op & ~0xff) != 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "RGPU_OP_DISMAX takes no min_should_match, optional-clause or nesting bits");
+      float tie;
+      std::memcpy(&tie, &Q.n_must_not, sizeof tie);
+      if (!std::isfinite(tie)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "RGPU_OP_DISMAX: n_must_not holds the bits of a finite f32 tie_breaker_multiplier");
+    }
+    const int qnot = query_n_must_not(Q);
     if (((uint32_t)Q.op >> 26) != 0 && (!(Q.op & (RGPU_OP_SHOULD_REQUIRED | RGPU_OP_NESTED_MUST)) || (int)((uint32_t)Q.op >> 26) > Q.n_terms))
       return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "RGPU_OP_NESTED_AT: the nested clause's index among the MUST clauses, 0 .. n_terms, with RGPU_OP_SHOULD_REQUIRED / RGPU_OP_NESTED_MUST");
     // "+a +(b c)": the SHOULD clauses as a nested disjunction under MUST (ConjunctionScorer over the MUST clauses and one
@@ -2736,13 +2752,13 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
     if (qmsm > 1 && qop != RGPU_OP_OR && qopt == 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "min_should_match needs SHOULD clauses");
     if (qopt > 0 && qop == RGPU_OP_OR) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "optional SHOULD clauses go with MUST clauses (op TERM / AND); an OR query's clauses are its n_terms");
     // (an OR query of MUST_NOT clauses only: BooleanWeight::create_scorer -> None, boolean_query.rs:274-276 — it matches nothing)
-    const int min_terms = (qop == RGPU_OP_OR && Q.n_must_not > 0) ? 0 : 1;
-    if (Q.n_terms < min_terms || Q.n_terms > RGPU_MAX_QUERY_TERMS || Q.n_must_not < 0 || Q.n_must_not > RGPU_MAX_QUERY_TERMS ||
-        Q.n_terms + qopt + Q.n_must_not > RGPU_MAX_QUERY_TERMS || (qop == RGPU_OP_TERM && Q.n_terms != 1))
+    const int min_terms = (qop == RGPU_OP_OR && qnot > 0) ? 0 : 1;
+    if (Q.n_terms < min_terms || Q.n_terms > RGPU_MAX_QUERY_TERMS || qnot < 0 || qnot > RGPU_MAX_QUERY_TERMS ||
+        Q.n_terms + qopt + qnot > RGPU_MAX_QUERY_TERMS || (qop == RGPU_OP_TERM && Q.n_terms != 1))
       return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad clause count");
-    if (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms + qopt + Q.n_must_not > (int64_t)n_terms_total)
+    if (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms + qopt + qnot > (int64_t)n_terms_total)
       return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "clause range outside terms[]");
-    for (int i = 0; i < Q.n_terms + qopt + Q.n_must_not; ++i) {
+    for (int i = 0; i < Q.n_terms + qopt + qnot; ++i) {
       const rgpu_query_term& t = terms[Q.first_term + i];
       if (i < Q.n_terms + qopt && (t.sim_table < 0 || t.sim_table >= c->n_sim_tables)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
       if (t.state.doc_freq > 0) ptrs.push_back(&t.state);
@@ -2760,7 +2776,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
     if (rc != RGPU_OK) return rc;
     for (int32_t q = 0; q < n_queries; ++q) {
       const rgpu_query& Q = queries[q];
-      const int n_all = Q.n_terms + ((Q.op >> 16) & 0xff) + Q.n_must_not;
+      const int n_all = Q.n_terms + ((Q.op >> 16) & 0xff) + query_n_must_not(Q);
       for (int i = 0; i < n_all; ++i) {
         const rgpu_query_term& t = terms[Q.first_term + i];
         if (t.state.doc_freq < 2) continue;
@@ -2787,7 +2803,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       int64_t min_df = INT64_MAX;
       if (qop == RGPU_OP_OR) {
         if (or_wide_ok && ((Q.op >> 8) & 0xff) <= 1 && Q.n_terms >= 10 && Q.n_terms <= ORX_MAX_TERMS && Q.n_must_not == 0) { n_look = Q.n_terms; min_df = min_df_or; }
-      } else if (Q.n_terms + qopt + Q.n_must_not >= 2) { n_look = Q.n_terms + qopt + Q.n_must_not; min_df = min_df_and; }
+      } else if (qop != RGPU_OP_DISMAX && Q.n_terms + qopt + Q.n_must_not >= 2) { n_look = Q.n_terms + qopt + Q.n_must_not; min_df = min_df_and; }
       // (only while a list's bits stay in an XCD's L2 — max_doc <= 16.7 M, the condition of and_xcd_chunk: measured on the 3-term
       // batch at 100 M docs, where they are 12.5 MB per list and every probe of a sparse list is an HBM sector, 1.94 ms with them
       // against 1.71 walking those clauses; at 10 M docs a batch of "rare AND medium" pairs 0.076 against 0.136 ms)
@@ -2858,6 +2874,10 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
   groups[4].op = RGPU_OP_AND;  // MUST + SHOULD trees scored with ReqOptScorer's sequential rule (k_search_and records + k_req_opt_scan)
   groups[4].req_opt = true;
   int cur_req_opt = 4;
+  groups.emplace_back();
+  groups[5].op = RGPU_OP_DISMAX;  // DisjunctionMaxQuery: a group of its own, never merged into the OR groups, never the heap-order kernels
+  groups[5].dismax = true;
+  int cur_dismax = 5;
   int64_t req_opt_records = 0;
   std::vector<DevTerm> mine, mine_not, mine_opt, mine_suffix;
   std::vector<int64_t> mine_bytes;
@@ -2874,7 +2894,8 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
     for (int i = 0; i < Q.n_terms; ++i) {
       const rgpu_query_term& t = terms[Q.first_term + i];
       if (t.state.doc_freq <= 0) {  // TermWeight::create_scorer -> None for this leaf
-        if (qop != RGPU_OP_OR) dead = true;  // a missing MUST clause kills the conjunction (boolean_query.rs:201-207)
+        // (a missing dismax disjunct drops out like a SHOULD clause: disjunction_max_query.rs:142-161)
+        if (qop != RGPU_OP_OR && qop != RGPU_OP_DISMAX) dead = true;  // a missing MUST clause kills the conjunction (boolean_query.rs:201-207)
         continue;
       }
       DevTerm dt;
@@ -2903,7 +2924,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
         std::stable_sort(mine_opt.begin(), mine_opt.end(), [](const DevTerm& a, const DevTerm& b) { return a.df < b.df; });
       // the nested disjunction has no scorer in this leaf = a MUST weight without a scorer: nothing matches (boolean_query.rs:203-207)
       if (should_required && mine_opt.empty()) mine.clear();
-      for (int i = 0; i < Q.n_must_not && !mine.empty(); ++i) {
+      for (int i = 0; i < query_n_must_not(Q) && !mine.empty(); ++i) {
         const rgpu_query_term& t = terms[Q.first_term + Q.n_terms + qopt + i];
         if (t.state.doc_freq <= 0) continue;
         DevTerm dt;
@@ -2963,6 +2984,12 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       groups.back().op = RGPU_OP_OR;
       cur_group[2] = (int)groups.size() - 1;
     }
+    if (gop == RGPU_OP_DISMAX && groups[(size_t)cur_dismax].postings > or_postings_cap) {
+      groups.emplace_back();
+      groups.back().op = RGPU_OP_DISMAX;
+      groups.back().dismax = true;
+      cur_dismax = (int)groups.size() - 1;
+    }
     // (a required disjunction is a child of the ConjunctionScorer: plain f32 sums, no ReqOptScorer in that tree)
     const bool to_req_opt = gop == RGPU_OP_AND && !mine_opt.empty() && !mine.empty() && c->cfg.req_opt_rule >= 0 && !should_required && !nested_must;
     if (to_req_opt) {  // one record per lead posting: keep a group's records under 1 GiB
@@ -2976,7 +3003,8 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       }
       req_opt_records += lead_df;
     }
-    Group& G = to_wide ? groups[3] : (to_req_opt ? groups[(size_t)cur_req_opt] : groups[(size_t)cur_group[gop]]);
+    Group& G = gop == RGPU_OP_DISMAX ? groups[(size_t)cur_dismax]
+                                     : (to_wide ? groups[3] : (to_req_opt ? groups[(size_t)cur_req_opt] : groups[(size_t)cur_group[gop]]));
     DevQuery dq;
     // the window kernel reads min_should_match from the second byte, the conjunction kernel its optional clause count
     // from the third; device clause order: MUST, MUST_NOT, SHOULD
@@ -2985,7 +3013,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
             (int32_t)((uint32_t)mine_suffix.size() << 26);  // (device side: bits 26.. = MUST clauses added after the nested group)
     dq.first_term = (int32_t)G.terms.size();
     dq.n_terms = (int32_t)mine.size();
-    dq.pad = (int32_t)mine_not.size();
+    dq.pad = gop == RGPU_OP_DISMAX ? Q.n_must_not : (int32_t)mine_not.size();  // dismax: the tie-breaker's bits travel where n_not does
     for (auto& m : mine) { G.terms.push_back(m); G.postings += m.df; }
     if (to_wide) G.term_bytes.insert(G.term_bytes.end(), mine_bytes.begin(), mine_bytes.end());
     for (auto& m : mine_not) { G.terms.push_back(m); G.postings += m.df; }
@@ -3020,7 +3048,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
     const int op = G.op;
     const int nq = (int)G.queries.size();
     if (nq == 0) continue;
-    if (op == RGPU_OP_OR) {
+    if (op == RGPU_OP_OR || op == RGPU_OP_DISMAX) {
       if (single_group && G.terms.empty()) { int32_t rc_i = init_rows(); if (rc_i != RGPU_OK) return rc_i; }  // nothing will be merged
       int32_t rc_or = G.or_wide ? search_or_wide_group(seg, G, k, hits_dev, totals_dev, stream)
                                 : search_or_group(seg, G, k, hits_dev, totals_dev, stream);
@@ -4987,6 +5015,7 @@ static int32_t uniform_args_ok(rgpu_planner* p, rgpu_segment* seg, int32_t op, i
                                const void* hits_dev, const void* totals_dev) {
   if (!p || !seg || !ids || !hits_dev || !totals_dev) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
   if (n_queries <= 0 || n_clauses <= 0 || n_clauses > RGPU_MAX_QUERY_TERMS || (int64_t)n_queries * n_clauses > 0x7fffffff) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad batch shape");
+  if ((op & 0xff) == RGPU_OP_DISMAX) return fail(RGPU_ERR_UNSUPPORTED, "the planner does not plan RGPU_OP_DISMAX: pack rgpu_query / rgpu_query_term and call rgpu_search_batch*");
   if ((op >> 16) != 0 || (op & 0xff) < RGPU_OP_TERM || (op & 0xff) > RGPU_OP_OR || ((op & 0xff) == RGPU_OP_TERM && n_clauses != 1))
     return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a uniform batch is TERM (one clause), AND or OR (optionally RGPU_OP_OR_MSM)");
   if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");

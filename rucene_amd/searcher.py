@@ -5,6 +5,7 @@ argument meaning and error behaviour so tests read like the reference's own (pat
     search/searcher.rs:205-249, 306-363, 487-525, 732-767   IndexSearcher::search, statistics quirk
     search/query/term_query.rs:45-95                         TermQuery::new(term, boost) / create_weight
     search/query/boolean_query.rs:40-86                      BooleanQuery::build(musts, shoulds, ...)
+    search/query/disjunction_max_query.rs:43-114             DisjunctionMaxQuery { disjuncts, tie_breaker_multiplier }
     search/similarity/bm25_similarity.rs:45-177              BM25Similarity::new(k1, b) / compute_weight
     search/collector/top_docs.rs:97-183                      TopDocsCollector::new(k) / top_docs()
     search/statistics.rs                                     CollectionStatistics / TermStatistics
@@ -18,7 +19,7 @@ resolves terms, computes BM25 weights (via the C ABI's host helper) and packs qu
 import numpy as np
 
 from . import _lib
-from ._lib import OP_AND, OP_NESTED_MUST, OP_OR, OP_SHOULD_REQUIRED, OP_TERM, QUERY_DTYPE, QUERY_TERM_DTYPE, TERM_STATE_DTYPE, RgpuError
+from ._lib import OP_AND, OP_DISMAX, OP_NESTED_MUST, OP_OR, OP_SHOULD_REQUIRED, OP_TERM, QUERY_DTYPE, QUERY_TERM_DTYPE, TERM_STATE_DTYPE, RgpuError
 
 
 class CollectionStatistics:
@@ -421,6 +422,37 @@ class BooleanQuery:
         return list(self.must_queries) + list(self.should_queries) + list(self.filter_queries)
 
 
+class DisjunctionMaxQuery:
+    """query/disjunction_max_query.rs:43-114: the union of the disjuncts' docs, each scored max + (sum - max) * tie_breaker_multiplier
+    over the disjuncts that hold it (DisjunctionMaxScorer, scorer/disjunction_scorer.rs:106-185, 246-286). The GPU path serves
+    TermQuery disjuncts (RGPU_OP_DISMAX in include/rucene_gpu.h); any other disjunct is UnsupportedOperation when the query is
+    searched, i.e. the caller's CPU path."""
+
+    def __init__(self, disjuncts, tie_breaker_multiplier=0.0):
+        self.disjuncts = list(disjuncts)
+        self.tie_breaker_multiplier = float(np.float32(tie_breaker_multiplier))
+        if not self.disjuncts:   # DisjunctionMaxQuery::build (:51-68)
+            raise RgpuError(-2, "DisjunctionMaxQuery: sub query should not be empty!")
+
+    @staticmethod
+    def build(disjuncts, tie_breaker_multiplier=0.0):
+        """DisjunctionMaxQuery::build: a lone disjunct IS that query."""
+        q = DisjunctionMaxQuery(disjuncts, tie_breaker_multiplier)
+        return q.disjuncts[0] if len(q.disjuncts) == 1 else q
+
+    def tie_bits(self):
+        """The multiplier's f32 bit pattern as the int32 that rgpu_query.n_must_not carries for RGPU_OP_DISMAX."""
+        return int(np.float32(self.tie_breaker_multiplier).view(np.int32))
+
+    def extract_terms(self):   # :91-97
+        return [t for q in self.disjuncts for t in q.extract_terms()]
+
+    def __str__(self):   # :104-114; the multiplier as Display prints an f32: its shortest round-trip digits, no exponent ("0.1", "1")
+        tie = np.float32(self.tie_breaker_multiplier)
+        shown = "NaN" if np.isnan(tie) else np.format_float_positional(tie, unique=True, trim="-")
+        return "DisjunctionMaxQuery(disjunctions: %s, tie_breaker_multiplier: %s)" % (", ".join(str(q) for q in self.disjuncts), shown)
+
+
 class TopDocs:
     def __init__(self, total_hits, score_docs):
         self._total, self._docs = int(total_hits), score_docs
@@ -510,6 +542,10 @@ class GpuIndexSearcher:
         """-> (op, required / scored clauses, optional SHOULD clauses beside MUST ones, MUST_NOT clauses)"""
         if isinstance(query, TermQuery):
             return OP_TERM, [query], [], []
+        if isinstance(query, DisjunctionMaxQuery):
+            if not all(isinstance(q, TermQuery) for q in query.disjuncts):
+                raise RgpuError(-5, "a DisjunctionMaxQuery is served by the GPU path when every disjunct is a TermQuery")
+            return OP_DISMAX, list(query.disjuncts), [], []   # (the tie-breaker rides in n_must_not: _dismax_fields)
         if isinstance(query, BooleanQuery):
             query = query.normalized()
             if not query.is_flat():
@@ -615,9 +651,19 @@ class GpuIndexSearcher:
             if max(len(t) + len(o) + len(n) for _, t, o, n in flat) > _lib.MAX_QUERY_TERMS:
                 raise RgpuError(-5, "more than %d clauses" % _lib.MAX_QUERY_TERMS)
             boosts = None if all(c.boost == 1.0 for c in clauses) else [c.boost for c in clauses]
-            return self._planner(leaf).plan_batch([f[0] for f in flat], [len(f[1]) for f in flat], [c.term for c in clauses],
-                                                  [len(f[3]) for f in flat], boosts)
+            # (the planner resolves and weighs a dismax query's clauses as an OR query's; its op and tie-breaker are written afterwards)
+            qs, ts = self._planner(leaf).plan_batch([OP_OR if f[0] == OP_DISMAX else f[0] for f in flat], [len(f[1]) for f in flat],
+                                                    [c.term for c in clauses], [len(f[3]) for f in flat], boosts)
+            return self._dismax_fields(queries, qs), ts
         return self._pack_clause_by_clause(queries, leaf, flat)
+
+    @staticmethod
+    def _dismax_fields(queries, qs):
+        """RGPU_OP_DISMAX: op 3 whatever the clause count, n_must_not = the bits of the f32 tie_breaker_multiplier."""
+        for i, q in enumerate(queries):
+            if isinstance(q, DisjunctionMaxQuery):
+                qs[i]["op"], qs[i]["n_must_not"] = OP_DISMAX, q.tie_bits()
+        return qs
 
     def _pack_clause_by_clause(self, queries, leaf, flat=None):
         """pack() one clause at a time in Python: mixed naming schemes, numpy-scalar ids; also what tests hold the native
@@ -647,7 +693,7 @@ class GpuIndexSearcher:
                 ts[pos]["weight"] = w
                 ts[pos]["sim_table"] = table
                 pos += 1
-        return qs, ts
+        return self._dismax_fields(queries, qs), ts
 
     def search_phrase_batch(self, queries, k):
         """IndexSearcher::search(PhraseQuery, TopDocsCollector(k)) for a batch of exact phrases -> (hits, total_hits).

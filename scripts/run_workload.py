@@ -1,5 +1,5 @@
 """Minimal driver for profiling: build the 10M-doc shard, run one workload a few times through the C ABI.
-usage: run_workload.py [term|and3|and2sparse|mustor|mustand|or10|decode|cold|posdec|phrase2|sloppy2] [reps]   (DOCS=... sets the shard size; cold = a fresh segment per repetition:
+usage: run_workload.py [term|and3|and2sparse|mustor|mustand|dismax|or10|decode|cold|posdec|phrase2|sloppy2] [reps]   (DOCS=... sets the shard size; cold = a fresh segment per repetition:
 skip decode + block framing + alignment + tails (k_prepare_terms, k_prepare_blocks), then k_decode_terms, for every df >= 128 term)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -85,6 +85,33 @@ elif kind == "mustor":
         return leaf.segment.search_batch(q2, t2, 10)[1]
     want = count((0, 1)) + count((0, 2)) - count((0, 1, 2))
     print("mustor: hit counts equal |ab| + |ac| - |abc| on %d of %d queries; matches in all: %d" % (int((totals == want).sum()), len(tids), int(totals.sum())))
+elif kind == "dismax":
+    # DisjunctionMaxQuery (RGPU_OP_DISMAX): the or10 batch's clause sets as dismax queries at tie_breaker_multiplier 0.1 through
+    # k_or_windows_max, and the same clauses as plain disjunctions through the clause-order window kernel k_or_windows (a second context
+    # with or_wide = -1: by default a 10-clause OR query takes the heap-order kernels). Launch times from the kernel statistics: the median
+    # of `reps` launches after two warm-up batches. Hit counts are cross-checked: a dismax query matches the union of its clauses.
+    D = rucene_amd.DisjunctionMaxQuery
+    tids = indexgen.log_uniform_ranks(10 * 1024, 1, 10_000, SEED ^ 0x0A).reshape(-1, 10) - 1
+    k = 100
+    def timed(searcher, lf, c, queries, names):
+        qs, ts = searcher.pack(queries, lf)
+        for _ in range(2):
+            lf.segment.search_batch(qs, ts, k)
+        c.kernel_stats_reset()
+        for _ in range(reps):
+            hits, totals = lf.segment.search_batch(qs, ts, k)
+        st = c.kernel_stats()
+        for n in names:
+            print("%s: median %.4f ms (min %.4f, max %.4f) over %d launches" % (n, st[n]["median_ms"], st[n]["min_ms"], st[n]["max_ms"], st[n]["launches"]))
+        return hits, totals
+    dh, dt = timed(s, leaf, ctx, [D([T(int(t)) for t in row], 0.1) for row in tids], ("k_score_terms", "k_or_windows_max", "k_merge_items"))
+    plain = rucene_amd.Context(profile_kernels=True, or_wide=-1, or_window_docs=int(os.environ.get("ORW", "0")), or_dense_clauses=int(os.environ.get("ORD", "0")))
+    leaf2 = rucene_amd.LeafReader.from_synthetic(seg)
+    s2 = rucene_amd.GpuIndexSearcher([leaf2], ctx=plain)
+    oh, ot = timed(s2, leaf2, plain, [B.build([], [T(int(t)) for t in row]) for row in tids], ("k_score_terms", "k_or_windows", "k_merge_items"))
+    print("dismax: hit counts equal the disjunctions' on %d of %d queries; matches in all: %d; every dismax score <= the sum: %s"
+          % (int((dt == ot).sum()), len(tids), int(dt.sum()), bool((dh["score"][:, 0] <= oh["score"][:, 0] * (1 + 1e-5)).all())))
+    plain.close()
 elif kind == "mustand":
     # "+a +(+b +c)" (RGPU_OP_NESTED_MUST): the and3 batch's triples as nested trees; rows against the flat conjunctions' (same docs and
     # counts; scores a + (b + c) against (x + y) + z in cost order: equal within 1e-5, and not always bit for bit)
