@@ -205,10 +205,32 @@ typedef struct rgpu_query {
   int32_t n_must_not;  /* MUST_NOT TermQuery clauses, stored right after the positive ones (weight / sim_table unused):
                           BooleanWeight::create_scorer wraps the positive scorer in a ReqNotScorer over their union
                           (query/boolean_query.rs:235-273, scorer/req_not_scorer.rs:20-120). 0 = none;
-                          n_terms + n_should + n_must_not <= RGPU_MAX_QUERY_TERMS.
+                          n_terms + n_should + n_must_not <= RGPU_MAX_QUERY_TERMS. The second byte may carry a BoostingQuery's
+                          demoting clauses: RGPU_NOT_WITH_DEMOTE(n_not, n_demote), below.
                           RGPU_OP_DISMAX: not a count — the bit pattern of the query's f32 tie_breaker_multiplier
                           (DisjunctionMaxQuery::tie_breaker_multiplier, query/disjunction_max_query.rs:43-48; 0 = the plain maximum) */
 } rgpu_query;
+/* BoostingQuery (query/boosting_query.rs, scorer/boosting_scorer.rs): "rank by `positive`, but multiply a doc's score by
+ * negative_boost if `negative` also holds it". rgpu_query.n_must_not = RGPU_NOT_WITH_DEMOTE(n_not, n_demote): n_not MUST_NOT clauses
+ * in the low byte as before, n_demote demoting TermQuery clauses — the term clauses of the negative query, taken as a union — in the
+ * second byte, stored right after the MUST_NOT clauses. Clause order in terms[]: scored, optional SHOULD, MUST_NOT, demoting;
+ * n_terms + n_should + n_not + n_demote <= RGPU_MAX_QUERY_TERMS. Bits 16 and up must be zero (RGPU_ERR_ILLEGAL_ARGUMENT; a count
+ * above 64 was never accepted, so no accepted value changed its meaning). A demoting clause's sim_table is ignored (the negative
+ * weight is created with needs_scores = false: no idf, no table); its `weight` carries negative_boost — the same value in every
+ * demoting clause of the query, finite, 0 < b < 1 (the constructor's debug_assert, boosting_query.rs:31; inside that range every
+ * score bound the kernels prune with stays valid), anything else RGPU_ERR_ILLEGAL_ARGUMENT.
+ * Iteration, matching, cost and total_hits are the positive query's alone (boosting_scorer.rs:40-81); score() is the positive
+ * score, multiplied once in f32 by negative_boost when a demoting clause holds the doc (:64-71) — however many of them do — bit
+ * equal to the reference. BoostingWeight::create_scorer yields a scorer only where BOTH weights have one (boosting_query.rs:102-118):
+ * in a leaf where no demoting term has a posting the query matches nothing and adds nothing to total_hits. The demoting clauses
+ * iterate postings, not live docs (a collected doc is live anyway).
+ * Positives: RGPU_OP_TERM, RGPU_OP_AND, RGPU_OP_OR (RGPU_OP_OR_MSM too), each with or without MUST_NOT clauses. With
+ * RGPU_OP_WITH_SHOULD, RGPU_OP_SHOULD_REQUIRED or RGPU_OP_NESTED_MUST: RGPU_ERR_UNSUPPORTED. RGPU_OP_DISMAX: unchanged, the field is
+ * its tie-breaker. A disjunction of ten or more present clauses sums in clause order, as without demotion (1e-5 relative).
+ * Served by rgpu_search_batch and its _device / _record / _sharded forms, mixed freely with the other ops, any k up to RGPU_MAX_K;
+ * rgpu_plan_batch_* and rgpu_rescore_batch answer RGPU_ERR_UNSUPPORTED for a non-zero demote byte (the uniform planner calls
+ * have no such field). */
+#define RGPU_NOT_WITH_DEMOTE(n_not, n_demote) ((int32_t)(n_not) | ((int32_t)(n_demote) << 8))
 
 /* sort_field/collapse_top_docs.rs:22-36 ScoreDoc */
 typedef struct rgpu_hit {

@@ -11,6 +11,11 @@ _LIB_NAME = "librucene_gpu.so"
 ABI_VERSION = 6
 OP_TERM, OP_AND, OP_OR = 0, 1, 2
 OP_DISMAX = 3                  # RGPU_OP_DISMAX: DisjunctionMaxQuery of term clauses; rgpu_query.n_must_not = the f32 tie-breaker's bits
+def not_with_demote(n_not, n_demote):
+    """RGPU_NOT_WITH_DEMOTE: rgpu_query.n_must_not of a BoostingQuery — MUST_NOT clauses in the low byte, demoting clauses in the second"""
+    return int(n_not) | (int(n_demote) << 8)
+
+
 OP_SHOULD_REQUIRED = 1 << 24   # RGPU_OP_SHOULD_REQUIRED: the optional SHOULD clauses are a nested disjunction under MUST
 OP_NESTED_MUST = 1 << 25       # RGPU_OP_NESTED_MUST: ... are a nested conjunction under MUST (its own sum, formed first)
 MAX_K = 1024

@@ -144,6 +144,34 @@ struct DisjunctionMaxQuery : Query {
   std::vector<TermQuery> extract_terms() const { return disjuncts; }  // :91-97
 };
 
+// query/boosting_query.rs:29-118, scorer/boosting_scorer.rs:40-81: the positive query's docs, counts and scores, a doc's score
+// multiplied once by negative_boost where the negative query also holds it; a leaf in which the negative query has no scorer matches
+// nothing. Served here (RGPU_NOT_WITH_DEMOTE): a positive that is a TermQuery or a BooleanQuery packing to TERM / AND / OR (with or
+// without MUST_NOT clauses), a negative that is a TermQuery or a should-only BooleanQuery with min_should_match <= 1, and
+// 0 < negative_boost < 1 (BoostingScorer::new's debug_assert); anything else is UnsupportedOperation when the query is searched — the
+// caller's CPU path.
+struct BoostingQuery : Query {
+  std::shared_ptr<const Query> positive, negative;
+  float negative_boost;
+  BoostingQuery(std::shared_ptr<const Query> pos, std::shared_ptr<const Query> neg, float boost)
+      : positive(std::move(pos)), negative(std::move(neg)), negative_boost(boost) {}
+  // the positive query as the GPU path takes it (a TermQuery or a BooleanQuery without optional or nested clauses), else Unsupported
+  const Query* served_positive() const {
+    if (!(negative_boost > 0.0f && negative_boost < 1.0f)) throw Error(RGPU_ERR_UNSUPPORTED, "a BoostingQuery is served by the GPU path for 0 < negative_boost < 1");
+    if (dynamic_cast<const TermQuery*>(positive.get())) return positive.get();
+    if (auto* b = dynamic_cast<const BooleanQuery*>(positive.get()))
+      if ((b->must_queries.empty() || b->should_queries.empty()) && !b->should_required && !b->nested_must) return b;
+    throw Error(RGPU_ERR_UNSUPPORTED, "a BoostingQuery is served by the GPU path when its positive query is a term or a flat TERM / AND / OR boolean query");
+  }
+  // the negative query as a union of term clauses, else Unsupported
+  std::vector<TermQuery> demoting_terms() const {
+    if (auto* t = dynamic_cast<const TermQuery*>(negative.get())) return {*t};
+    if (auto* b = dynamic_cast<const BooleanQuery*>(negative.get()))
+      if (b->must_queries.empty() && b->must_not_queries.empty() && !b->should_queries.empty() && b->min_should_match <= 1) return b->should_queries;
+    throw Error(RGPU_ERR_UNSUPPORTED, "a BoostingQuery is served by the GPU path when its negative query is a term or a flat disjunction of terms");
+  }
+};
+
 // A BooleanQuery whose MUST / SHOULD clauses may themselves be queries (BooleanQuery::build takes Vec<Box<dyn Query>>,
 // boolean_query.rs:40-86). The GPU path serves flat trees of term clauses; `flattened()` folds ONE level — a MUST clause that is
 // a must-only BooleanQuery, a SHOULD clause that is a should-only one (min_should_match <= 1) — into a flat BooleanQuery, or
@@ -717,7 +745,11 @@ class GpuIndexSearcher {
       boosts.push_back(c.boost);
       any_boost = any_boost || c.boost != 1.0f;
     };
-    for (const Query* q : queries) {
+    for (const Query* q0 : queries) {
+      // (a BoostingQuery is planned as its positive query, the demoting clauses as further MUST_NOT clauses; the count's second byte
+      // and the boost are written below)
+      const BoostingQuery* bo = dynamic_cast<const BoostingQuery*>(q0);
+      const Query* q = bo ? bo->served_positive() : q0;
       if (auto* t = dynamic_cast<const TermQuery*>(q)) {
         ops.push_back(RGPU_OP_TERM); n_terms.push_back(1); n_not.push_back(0);
         clause(*t);
@@ -736,6 +768,13 @@ class GpuIndexSearcher {
         for (const TermQuery& c : d->disjuncts) clause(c);
       } else {
         throw Error(RGPU_ERR_UNSUPPORTED, "query type not served by the GPU path");
+      }
+      if (bo) {
+        const std::vector<TermQuery> dem = bo->demoting_terms();
+        if (n_terms.back() + ((ops.back() >> 16) & 0xff) + n_not.back() + static_cast<int32_t>(dem.size()) > RGPU_MAX_QUERY_TERMS)
+          throw Error(RGPU_ERR_UNSUPPORTED, "more than RGPU_MAX_QUERY_TERMS clauses in one query");
+        n_not.back() += static_cast<int32_t>(dem.size());
+        for (const TermQuery& c : dem) clause(c);
       }
     }
     const LeafReader& sl = leaves_[stats_leaf_];
@@ -771,8 +810,24 @@ class GpuIndexSearcher {
     // bits are written over its records here. pack() writes the same two fields directly.
     for (size_t i = 0; i < queries.size(); ++i)
       if (auto* d = dynamic_cast<const DisjunctionMaxQuery*>(queries[i])) { (*qs)[i].op = RGPU_OP_DISMAX; (*qs)[i].n_must_not = d->tie_bits(); }
+    // a BoostingQuery's second half: the last n_demote of the clauses planned as MUST_NOT are the demoting ones
+    for (size_t i = 0; i < queries.size(); ++i)
+      if (auto* bo = dynamic_cast<const BoostingQuery*>(queries[i])) demote_fields(*bo, &(*qs)[i], ts);
   }
-  void pack(const Query& q, const LeafReader& leaf, std::vector<rgpu_query>* qs, std::vector<rgpu_query_term>* ts) {
+  // RGPU_NOT_WITH_DEMOTE: the demoting clauses' count moves to the second byte of n_must_not, their weight is negative_boost, their
+  // table is never read
+  static void demote_fields(const BoostingQuery& bo, rgpu_query* rq, std::vector<rgpu_query_term>* ts) {
+    const int32_t n_dem = static_cast<int32_t>(bo.demoting_terms().size()), n_not = rq->n_must_not - n_dem;
+    rq->n_must_not = RGPU_NOT_WITH_DEMOTE(n_not, n_dem);
+    for (int32_t i = 0; i < n_dem; ++i) {
+      rgpu_query_term& t = (*ts)[static_cast<size_t>(rq->first_term + rq->n_terms + n_not + i)];
+      t.weight = bo.negative_boost;
+      t.sim_table = 0;
+    }
+  }
+  void pack(const Query& q0, const LeafReader& leaf, std::vector<rgpu_query>* qs, std::vector<rgpu_query_term>* ts) {
+    const BoostingQuery* bo = dynamic_cast<const BoostingQuery*>(&q0);
+    const Query& q = bo ? *bo->served_positive() : q0;
     const std::vector<TermQuery>* clauses = nullptr;
     const std::vector<TermQuery>* opts = nullptr;  // SHOULD clauses beside MUST ones
     const std::vector<TermQuery>* nots = nullptr;
@@ -798,6 +853,12 @@ class GpuIndexSearcher {
     if (nots) all.insert(all.end(), nots->begin(), nots->end());
     rgpu_query rq{op, static_cast<int32_t>(clauses->size()), static_cast<int32_t>(ts->size()),
                   static_cast<int32_t>(nots ? nots->size() : 0)};
+    if (bo) {  // the demoting clauses behind the MUST_NOT ones (counted as such until demote_fields splits the field)
+      const std::vector<TermQuery> dem = bo->demoting_terms();
+      all.insert(all.end(), dem.begin(), dem.end());
+      rq.n_must_not += static_cast<int32_t>(dem.size());
+      if (all.size() > static_cast<size_t>(RGPU_MAX_QUERY_TERMS)) throw Error(RGPU_ERR_UNSUPPORTED, "more than RGPU_MAX_QUERY_TERMS clauses in one query");
+    }
     if (auto* d = dynamic_cast<const DisjunctionMaxQuery*>(&q)) rq.n_must_not = d->tie_bits();  // RGPU_OP_DISMAX: the tie-breaker's bits
     for (const TermQuery& c : all) {
       rgpu_query_term qt{};
@@ -807,6 +868,7 @@ class GpuIndexSearcher {
       qt.sim_table = w.second;
       ts->push_back(qt);
     }
+    if (bo) demote_fields(*bo, &rq, ts);
     qs->push_back(rq);
   }
 

@@ -171,7 +171,11 @@ struct SeqRec {
 
 // HAS_NOT / HAS_OPT: some query of the launch carries MUST_NOT / optional SHOULD clauses (separate instantiations keep the
 // common kernel lean). Clause order on the device: [MUST x n_terms][MUST_NOT x pad][SHOULD x (op >> 16)].
-template <bool LEGACY, bool WIDE, bool HAS_NOT, bool HAS_OPT>
+// HAS_DEM (with HAS_NOT, without HAS_OPT): some query of the launch is a BoostingQuery (query/boosting_query.rs:102-118,
+// scorer/boosting_scorer.rs:40-81). DevQuery::pad = n_not | n_dem << 8, device clause order [MUST][MUST_NOT x n_not][demoting x n_dem]:
+// a candidate found in a demoting clause stays, counts, and has its finished f32 sum multiplied once by negative_boost (the first
+// demoting clause's DevTerm::weight) before its key is formed. The instantiations without HAS_DEM are the code they were.
+template <bool LEGACY, bool WIDE, bool HAS_NOT, bool HAS_OPT, bool HAS_DEM = false>
 __global__ __launch_bounds__(AND_WG_THREADS, AND_WAVES_PER_SIMD) void k_search_and(SegView seg, const DevQuery* __restrict__ queries,
                                                            const DevTerm* __restrict__ terms,
                                                            const int64_t* __restrict__ item_prefix, int n_queries,
@@ -196,6 +200,7 @@ __global__ __launch_bounds__(AND_WG_THREADS, AND_WAVES_PER_SIMD) void k_search_a
   // emit_out != null: nothing is collected here. Without HAS_OPT (phrases): int32 doc ids appended to the query's list
   // at emit_prefix[q] in any order, emit_count[q] the cursor. With HAS_OPT (the exact ReqOptScorer rule): one SeqRec per
   // lead posting at emit_prefix[q] + the posting's ordinal — doc order, no cursor.
+  static_assert(!HAS_DEM || (HAS_NOT && !HAS_OPT), "demoting clauses sit behind the MUST_NOT clauses of a tree without optional clauses");
   int32_t* const emit_docs = HAS_OPT ? nullptr : static_cast<int32_t*>(emit_out);
   SeqRec* const seq_out = HAS_OPT ? static_cast<SeqRec*>(emit_out) : nullptr;
   __shared__ __attribute__((aligned(16))) uint8_t slabs[AND_WG_WAVES][2 * SLAB_STREAM];  // FullBlock staging only: tails arrive decoded
@@ -275,11 +280,14 @@ __global__ __launch_bounds__(AND_WG_THREADS, AND_WAVES_PER_SIMD) void k_search_a
     // a separate sum, as DisjunctionSumScorer does, which is added to the required sum at the end; a miss costs nothing.
     // The reference's sequential "skip the optional clause for low scorers after 100 docs" rule is NOT applied:
     // scores are the exact sums, >= the reference's)
-    const int n_req_not = HAS_NOT ? Q.n_terms + Q.pad : Q.n_terms;
+    const int n_req_not = HAS_NOT ? Q.n_terms + (HAS_DEM ? (Q.pad & 0xff) : Q.pad) : Q.n_terms;
     // (HAS_OPT) behind the optional / nested group: the MUST clauses that ConjunctionScorer::score adds AFTER the nested child
     // (rgpu_api.hip search_pass: the children's stable cost order) — required like the first ones, added to (first sum + group sum)
     const int n_opt_end = HAS_OPT ? n_req_not + ((Q.op >> 16) & 0xff) : n_req_not;
-    const int n_clauses = HAS_OPT ? n_opt_end + (int)((uint32_t)Q.op >> 26) : n_req_not;
+    // (HAS_DEM) the demoting clauses (BoostingScorer's negative side, a union): probed like the MUST_NOT clauses, for the candidates
+    // still alive; a find sets the candidate's bit in dem_hit (bit 0 / 1: candidate 0 / 1), a miss costs nothing
+    const int n_clauses = HAS_OPT ? n_opt_end + (int)((uint32_t)Q.op >> 26) : (HAS_DEM ? n_req_not + ((Q.pad >> 8) & 0xff) : n_req_not);
+    uint32_t dem_hit = 0u;
     float r0 = 0.f, r1 = 0.f;  // required sums, parked while s0 / s1 collect the optional sum
     bool in_opt = false;
     // RGPU_OP_SHOULD_REQUIRED ("+a +(b c)": the SHOULD clauses are a DisjunctionSumScorer among the ConjunctionScorer's children,
@@ -302,24 +310,26 @@ __global__ __launch_bounds__(AND_WG_THREADS, AND_WAVES_PER_SIMD) void k_search_a
       if (!(__ballot(a0) | __ballot(a1))) break;
       const bool excl = HAS_NOT && ti >= Q.n_terms && ti < n_req_not;  // wave-uniform
       const bool opt = HAS_OPT && ti >= n_req_not && ti < n_opt_end;    // wave-uniform
+      const bool dem = HAS_DEM && ti >= n_req_not;                      // wave-uniform
       if (HAS_OPT && opt && !in_opt) { r0 = s0; r1 = s1; s0 = 0.f; s1 = 0.f; in_opt = true; }
       if (HAS_OPT && ti >= n_opt_end && in_opt) {  // the group's sum joins; the rest add to it
         s0 = r0 + s0; s1 = r1 + s1; in_opt = false;
         if (need_any) { a0 = a0 && (any_opt & 1u) != 0u; a1 = a1 && (any_opt & 2u) != 0u; }
       }
       const DevTerm T = terms[Q.first_term + ti];
-      if (!excl) {
+      if (!excl && !dem) {  // (neither a MUST_NOT nor a demoting clause scores: needs_scores = false, boosting_query.rs:96)
         use_table(T.sim_table);
         wk = T.weight * (k1 + 1.0f);
       }
       // what finding / missing a candidate in this clause means (the norm is looked up on the spot: finds are rare, and
       // two more registers held across the block loop are not)
       auto found = [&](uint32_t which, bool& alive, float& s, uint32_t fq, uint32_t nb) {
+        if (HAS_DEM && dem) { dem_hit |= which; return; }
         if (excl) alive = false; else s += bm25_score(wk, (float)(int32_t)fq, has_norms ? cache[nb] : k1);
         if (HAS_OPT && opt) any_opt |= which;
       };
       const uint32_t n0 = nn & 0xffu, n1 = nn >> 8;
-      auto missed = [&](bool& alive) { if (!excl && (!opt || need_all)) alive = false; };
+      auto missed = [&](bool& alive) { if (!excl && !dem && (!opt || need_all)) alive = false; };
       if (T.df == 1) {
         if (a0) { if (d0 == T.singleton_doc) found(1u, a0, s0, (uint32_t)T.singleton_freq, n0); else missed(a0); }
         if (a1) { if (d1 == T.singleton_doc) found(2u, a1, s1, (uint32_t)T.singleton_freq, n1); else missed(a1); }
@@ -541,6 +551,11 @@ __global__ __launch_bounds__(AND_WG_THREADS, AND_WAVES_PER_SIMD) void k_search_a
         if (a1) emit_docs[base_at + n0c + mbcnt(m1)] = doc_is_live(seg.live, d1) ? d1 : (d1 | (int32_t)0x80000000);
       }
       return;
+    }
+    if (HAS_DEM && dem_hit != 0u) {  // BoostingScorer::score: one f32 multiply on the finished positive score (boosting_scorer.rs:64-71)
+      const float nb = terms[Q.first_term + n_req_not].weight;  // (dem_hit != 0: the query has a demoting clause)
+      if (dem_hit & 1u) s0 *= nb;
+      if (dem_hit & 2u) s1 *= nb;
     }
     count += __popcll(__ballot(a0)) + __popcll(__ballot(a1));
     topk_offer<WIDE>(top, a0 ? below(make_key(s0, d0), ceil) : 0ull, tau, k, lane, floor);

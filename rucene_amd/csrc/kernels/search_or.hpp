@@ -112,18 +112,19 @@ constexpr uint32_t OR_UNTOUCHED = 0xffffffffu;  // accumulator patterns no sum o
 constexpr uint32_t OR_EXCLUDED = 0xfffffffeu;
 static_assert(OR_DENSE_MAX <= OR_WAVES, "wave w of a workgroup builds dense clause w's score table");
 
-// (mx: the dismax instantiation keeps a second f32 per doc cell, the running maximum)
-__host__ __device__ constexpr size_t or_wave_lds_bytes(int W, bool msm, bool mx = false) {
-  return (size_t)(2 * SLAB_STREAM) + (size_t)W * (msm ? 5 : 4) + (mx ? (size_t)W * 4 : 0);
+// (mx: the dismax instantiation keeps a second f32 per doc cell, the running maximum; dem: the boosting instantiation one bit per
+// doc, "a demoting clause holds it")
+__host__ __device__ constexpr size_t or_wave_lds_bytes(int W, bool msm, bool mx = false, bool dem = false) {
+  return (size_t)(2 * SLAB_STREAM) + (size_t)W * (msm ? 5 : 4) + (mx ? (size_t)W * 4 : 0) + (dem ? (size_t)W / 8 : 0);
 }
-__host__ __device__ constexpr size_t or_lds_bytes(int W, bool msm, bool mx = false) {
-  return (size_t)OR_DENSE_MAX * WAVE_CACHE_FLOATS * 4 + (size_t)OR_WAVES * or_wave_lds_bytes(W, msm, mx);
+__host__ __device__ constexpr size_t or_lds_bytes(int W, bool msm, bool mx = false, bool dem = false) {
+  return (size_t)OR_DENSE_MAX * WAVE_CACHE_FLOATS * 4 + (size_t)OR_WAVES * or_wave_lds_bytes(W, msm, mx, dem);
 }
 constexpr size_t OR_LDS_MAX = 160 * 1024;  // a CU's LDS: the most one workgroup can ask for
 // the widest window (a multiple of 256 docs, at most `want`) whose launch fits a CU's LDS
-inline int or_fit_window(int want, bool msm, bool mx) {
+inline int or_fit_window(int want, bool msm, bool mx, bool dem = false) {
   int W = want;
-  while (W > 256 && or_lds_bytes(W, msm, mx) > OR_LDS_MAX) W -= 256;
+  while (W > 256 && or_lds_bytes(W, msm, mx, dem) > OR_LDS_MAX) W -= 256;
   return W;
 }
 
@@ -136,7 +137,12 @@ inline int or_fit_window(int want, bool msm, bool mx) {
 // HAS_MAX (k_or_windows_max, without HAS_NOT / HAS_MSM): DisjunctionMaxScorer (disjunction_scorer.rs:106-185) — the same union,
 // the same clause-order sum, and next to it the per-doc maximum of the clause scores; a doc's score is
 // max + (sum - max) * tie_breaker_multiplier (SubScorers::score_max, :246-286), the multiplier's bits in DevQuery::pad.
-template <bool LEGACY, bool WIDE, bool HAS_NOT, bool HAS_MSM, bool HAS_MAX>
+// HAS_DEM (k_or_windows_dem, with HAS_NOT and HAS_MSM): BoostingQuery over a disjunction (query/boosting_query.rs:102-118,
+// scorer/boosting_scorer.rs:40-81). DevQuery::pad = n_not | n_dem << 8; the n_dem demoting clauses are stored behind the MUST_NOT
+// clauses and take the clause positions behind the SHOULD clauses. Their runs add nothing: each posting sets the doc's bit in a
+// per-wave window bitmask, and the scan multiplies a collected doc's finished sum once by negative_boost (the first demoting
+// clause's DevTerm::weight). A doc that only a demoting clause holds is no hit.
+template <bool LEGACY, bool WIDE, bool HAS_NOT, bool HAS_MSM, bool HAS_MAX, bool HAS_DEM = false>
 __device__ __forceinline__ void or_windows_body(const SegView& seg, const DevQuery* __restrict__ queries,
                                                 const DevTerm* __restrict__ terms, const int64_t* __restrict__ run_prefix,
                                                 const ScoredPosting* __restrict__ runs, int n_queries, int windows_per_query,
@@ -146,6 +152,7 @@ __device__ __forceinline__ void or_windows_body(const SegView& seg, const DevQue
                                                 const unsigned long long* __restrict__ ceil_slots,
                                                 const int32_t* __restrict__ qmap) {
   static_assert(!HAS_MAX || (!HAS_NOT && !HAS_MSM), "a dismax query has neither MUST_NOT clauses nor a min_should_match");
+  static_assert(!HAS_DEM || (HAS_NOT && HAS_MSM && !HAS_MAX), "the boosting instantiation is the general one plus the demotion bits");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = lane_id();
   const int wave = wave_id();
@@ -153,11 +160,13 @@ __device__ __forceinline__ void or_windows_body(const SegView& seg, const DevQue
   // | cnt[W] u8 (HAS_MSM) or mx[W] f32 (HAS_MAX)]. An untouched accumulator holds OR_UNTOUCHED, a NaN pattern no sum of scores produces; the
   // scan at the end of a window puts it back, so there is no per-doc flag array and no clearing pass.
   float* tables = reinterpret_cast<float*>(smem);
-  uint8_t* slice = smem + (size_t)OR_DENSE_MAX * WAVE_CACHE_FLOATS * 4 + (size_t)wave * or_wave_lds_bytes(W, HAS_MSM, HAS_MAX);
+  uint8_t* slice = smem + (size_t)OR_DENSE_MAX * WAVE_CACHE_FLOATS * 4 + (size_t)wave * or_wave_lds_bytes(W, HAS_MSM, HAS_MAX, HAS_DEM);
   uint8_t* slab = slice;
   float* acc = reinterpret_cast<float*>(slice + 2 * SLAB_STREAM);
   uint8_t* cnt = reinterpret_cast<uint8_t*>(acc + W);  // HAS_MSM only: SHOULD clauses that hold the doc
   float* mx = acc + W;  // HAS_MAX only: the largest clause score of the doc; valid wherever acc is not "untouched", so never cleared
+  // HAS_DEM only (behind cnt): one bit per doc of the window, set by the demoting clauses' postings; zero between windows
+  uint32_t* dbits = reinterpret_cast<uint32_t*>(slice + 2 * SLAB_STREAM + (size_t)W * 5);
   // Workgroup b works on query b % n_queries: a query's workgroups are spread over the whole launch instead of running
   // side by side, so all but the first one or two start from the thresholds the earlier ones published (SharedTau) —
   // query-major order made every wavefront build its own top-k from nothing, ~460 insertions each, which was over half
@@ -197,13 +206,17 @@ __device__ __forceinline__ void or_windows_body(const SegView& seg, const DevQue
   // window — one lane-parallel binary search over all clauses at once. The n_not MUST_NOT clauses (stored after the
   // n_terms SHOULD clauses) take lanes 0 .. n_not-1 so that a window meets them first: ReqNotScorer over the disjunction
   // (boolean_query.rs:271-273, req_not_scorer.rs:47-63) — their docs are marked excluded before anything is summed.
-  const int n_not = HAS_NOT ? Q.pad : 0;
+  const int n_not = HAS_NOT ? (HAS_DEM ? (Q.pad & 0xff) : Q.pad) : 0;
+  const int n_dem = HAS_DEM ? ((Q.pad >> 8) & 0xff) : 0;
+  // negative_boost (0 < b < 1: checked by the host)
+  const float demote = (HAS_DEM && n_dem > 0) ? terms[Q.first_term + Q.n_terms + n_not].weight : 1.0f;
   const int msm = HAS_MSM ? ((Q.op >> 8) & 0xff) : 1;
   const float tie = HAS_MAX ? __int_as_float(Q.pad) : 0.0f;  // tie_breaker_multiplier (finite: checked by the host)
-  const int n_pos = Q.n_terms + n_not;  // clause positions of a window, in summation order
+  const int n_sum = Q.n_terms + n_not;  // behind them (HAS_DEM): the demoting clauses, stored at their own positions
+  const int n_pos = n_sum + n_dem;  // clause positions of a window, in summation order
   const bool mine = lane < n_pos;
-  const int my_clause = lane < n_not ? Q.n_terms + lane : lane - n_not;
-  const bool my_dense = mine && lane >= n_not && my_clause < 16 && ((dense_mask >> my_clause) & 1u);  // (a dense clause is one of the first 16)
+  const int my_clause = lane < n_not ? Q.n_terms + lane : (lane < n_sum ? lane - n_not : lane);
+  const bool my_dense = mine && lane >= n_not && lane < n_sum && my_clause < 16 && ((dense_mask >> my_clause) & 1u);  // (a dense clause is one of the first 16)
   const int64_t my_base = mine ? run_prefix[Q.first_term + my_clause] : 0;
   int my_len = 0;
   if (mine) { const DevTerm* Tm = terms + Q.first_term + my_clause; my_len = my_dense ? Tm->tail_n : Tm->df; }
@@ -237,6 +250,7 @@ __device__ __forceinline__ void or_windows_body(const SegView& seg, const DevQue
   }
 
   for (int i = lane; i < W; i += 64) acc[i] = __uint_as_float(OR_UNTOUCHED);
+  if (HAS_DEM) for (int i = lane; i < W / 32; i += 64) dbits[i] = 0u;
   wave_sync();
   for (int win = win0; win < win1; ++win) {
     const int32_t w0 = win * W;
@@ -252,6 +266,7 @@ __device__ __forceinline__ void or_windows_body(const SegView& seg, const DevQue
       if ((active0 >> t) & 1ull) pre[t] = runs[(int64_t)readlane64((uint64_t)my_at, t) + lane];  // wave-uniform branch
     }
     bool touched_any = false;  // wave-uniform: some accumulator of this window was written
+    bool marked_any = false;   // wave-uniform (HAS_DEM): some demotion bit of this window was set
 
     // one posting into the window's accumulator (all docs of one clause are distinct: no two lanes meet)
     auto add = [&](int32_t doc, float sc, bool valid, bool prohibited) {
@@ -286,13 +301,18 @@ __device__ __forceinline__ void or_windows_body(const SegView& seg, const DevQue
         while (true) {
           const bool in = e.doc < w1;
           const int n = __popcll(__ballot(in));  // runs are doc-sorted: the in-window entries are a prefix
-          add(e.doc, e.score, in, t < n_not);
+          if (HAS_DEM && t >= n_sum) {  // wave-uniform: a demoting clause only marks (lanes of one run can meet in one word)
+            const uint32_t o = (uint32_t)(e.doc - w0);
+            if (in && o < wlen) atomicOr(&dbits[o >> 5], 1u << (o & 31u));
+          } else {
+            add(e.doc, e.score, in, t < n_not);
+          }
           taken += n;
           if (n < 64) { next = readlane(e.doc, n); break; }  // the entry now under the cursor (or the sentinel)
           e = runs[(int64_t)readlane64((uint64_t)my_at, t) + taken + lane];  // a stretch longer than 64: the rare case
         }
         if (lane == t) { my_at += taken; my_next = next; }
-        touched_any = true;
+        if (HAS_DEM && t >= n_sum) marked_any = true; else touched_any = true;
         wave_sync();
       }
       // ---- the clause's FullBlocks, when it is a dense one
@@ -362,6 +382,13 @@ __device__ __forceinline__ void or_windows_body(const SegView& seg, const DevQue
             h3 = h3 && (int)(c4 >> 24) >= msm;
           }
           hits_lane += (int)h0 + (int)h1 + (int)h2 + (int)h3;
+          if (HAS_DEM && marked_any) {  // BoostingScorer::score (boosting_scorer.rs:64-71): s *= negative_boost, once, on the finished sum
+            const uint32_t m4 = dbits[(i0 + 4u * (uint32_t)lane) >> 5] >> ((4u * (uint32_t)lane) & 31u);
+            if (m4 & 1u) v.x *= demote;
+            if (m4 & 2u) v.y *= demote;
+            if (m4 & 4u) v.z *= demote;
+            if (m4 & 8u) v.w *= demote;
+          }
           *cell = make_float4(__uint_as_float(OR_UNTOUCHED), __uint_as_float(OR_UNTOUCHED), __uint_as_float(OR_UNTOUCHED), __uint_as_float(OR_UNTOUCHED));
           if (HAS_MAX) {  // score_max + (score_sum - score_max) * tie: three f32 operations (cells that are no hit hold anything)
             const float4 m = *reinterpret_cast<const float4*>(mx + i0 + 4 * lane);
@@ -389,6 +416,10 @@ __device__ __forceinline__ void or_windows_body(const SegView& seg, const DevQue
       }
       wave_sync();
     }
+    if (HAS_DEM && marked_any) {  // the bits go back to zero, whether the window was scanned or not
+      for (int i = lane; i < W / 32; i += 64) dbits[i] = 0u;
+      wave_sync();
+    }
   }
   shared.publish<WIDE>(top, k, lane);
   uint64_t* pk = partial_keys + (size_t)item * (size_t)k;
@@ -411,6 +442,23 @@ __global__ __launch_bounds__(OR_THREADS, 6) void k_or_windows(SegView seg, const
                                                               const unsigned long long* __restrict__ ceil_slots = nullptr,
                                                               const int32_t* __restrict__ qmap = nullptr) {
   or_windows_body<LEGACY, WIDE, HAS_NOT, HAS_MSM, false>(seg, queries, terms, run_prefix, runs, n_queries, windows_per_query, windows_per_item,
+                                                         items_per_query, W, k, partial_keys, partial_counts, tau_slots, ceil_slots, qmap);
+}
+
+// BoostingQuery over a disjunction: the general window kernel (MUST_NOT, min_should_match) with the demotion bitmask
+template <bool LEGACY, bool WIDE>
+__global__ __launch_bounds__(OR_THREADS, 6) void k_or_windows_dem(SegView seg, const DevQuery* __restrict__ queries,
+                                                                  const DevTerm* __restrict__ terms,
+                                                                  const int64_t* __restrict__ run_prefix,
+                                                                  const ScoredPosting* __restrict__ runs, int n_queries,
+                                                                  int windows_per_query, int windows_per_item,
+                                                                  int items_per_query, int W, int k,
+                                                                  uint64_t* __restrict__ partial_keys,
+                                                                  int32_t* __restrict__ partial_counts,
+                                                                  unsigned long long* __restrict__ tau_slots,
+                                                                  const unsigned long long* __restrict__ ceil_slots = nullptr,
+                                                                  const int32_t* __restrict__ qmap = nullptr) {
+  or_windows_body<LEGACY, WIDE, true, true, false, true>(seg, queries, terms, run_prefix, runs, n_queries, windows_per_query, windows_per_item,
                                                          items_per_query, W, k, partial_keys, partial_counts, tau_slots, ceil_slots, qmap);
 }
 

@@ -1806,8 +1806,18 @@ static void ensure_memb_only_locked(rgpu_segment* seg, const rgpu_term_state* co
 }
 
 // ---- search ----------------------------------------------------------------------------------------------------
-// rgpu_query.n_must_not as a clause count: a dismax query has no MUST_NOT clauses, the field carries its tie-breaker there
-static inline int query_n_must_not(const rgpu_query& Q) { return (Q.op & 0xff) == RGPU_OP_DISMAX ? 0 : Q.n_must_not; }
+// rgpu_query.n_must_not, split: the MUST_NOT clause count in its low byte, the demoting clause count (RGPU_NOT_WITH_DEMOTE: a
+// BoostingQuery's negative term clauses, stored behind the MUST_NOT ones) in its second byte; `stray` = some other bit is set (a
+// negative value included). A dismax query has neither kind of clause: the field carries its tie-breaker there.
+struct NotCounts {
+  int n_not, n_demote;
+  bool stray;
+  int all() const { return n_not + n_demote; }
+};
+static inline NotCounts query_not_counts(const rgpu_query& Q) {
+  if ((Q.op & 0xff) == RGPU_OP_DISMAX) return NotCounts{0, 0, false};
+  return NotCounts{Q.n_must_not & 0xff, (Q.n_must_not >> 8) & 0xff, ((uint32_t)Q.n_must_not >> 16) != 0u};
+}
 namespace {
 struct Group {  // queries of one op, in their original order
   int op = 0;
@@ -1817,6 +1827,7 @@ struct Group {  // queries of one op, in their original order
   std::vector<int64_t> term_bytes;  // or_wide: per clause, the encoded bytes of its postings (rgpu_last_search_counters)
   bool dismax = false;          // DisjunctionMaxQuery over term clauses: the window kernel's max + tie-breaker instantiation, whatever the clause count
   bool req_opt = false;         // MUST + SHOULD trees under the reference's ReqOptScorer rule: conjunction records + sequential scan
+  bool demote = false;          // BoostingQuery: conjunctions / disjunctions with demoting clauses — the HAS_DEM instantiations, groups of their own
   std::vector<int32_t> qmap;    // original query index
   std::vector<DevQuery> queries;
   std::vector<DevTerm> terms;
@@ -1854,7 +1865,8 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
   // table, i.e. norms held as ranks.
   // (dismax: 512 docs by default — the LDS, and so the workgroups per CU, of the plain kernel's 1024)
   const int W_cfg = std::min(4096, std::max(256, c->cfg.or_window_docs > 0 ? (c->cfg.or_window_docs + 255) / 256 * 256 : (G.dismax ? 512 : 1024)));
-  const int W = G.dismax ? or_fit_window(W_cfg, false, true) : W_cfg;
+  // (boosting: W / 8 bytes of demotion bits per wavefront on top of the general kernel's cells — narrowed the same way)
+  const int W = G.dismax ? or_fit_window(W_cfg, false, true) : (G.demote ? or_fit_window(W_cfg, true, false, true) : W_cfg);
   const int dense_max = c->cfg.or_dense_clauses < 0 ? 0 : (c->cfg.or_dense_clauses == 0 ? OR_DENSE_MAX : std::min(c->cfg.or_dense_clauses, OR_DENSE_MAX));
   if (dense_max > 0 && seg->d_norms && seg->n_norm_ranks > 0) {
     for (DevQuery& dq : G.queries) {
@@ -1944,10 +1956,11 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
       RGPU_LAUNCH(k_score_terms<false>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, dt, dip, drp, nt, items1, blocks_per_item, runs_buf.p);
   }
   {
-    TimedLaunch tl(c, stream, G.dismax ? "k_or_windows_max" : "k_or_windows", G.postings);
+    TimedLaunch tl(c, stream, G.dismax ? "k_or_windows_max" : (G.demote ? "k_or_windows_dem" : "k_or_windows"), G.postings);
     bool has_not = false, has_msm = false;  // (a dismax query has neither: its DevQuery::pad holds the tie-breaker's bits)
     if (!G.dismax) for (const DevQuery& dq : G.queries) { has_not = has_not || dq.pad != 0; has_msm = has_msm || ((dq.op >> 8) & 0xff) > 1; }
-    const size_t lds = or_lds_bytes(W, has_msm, G.dismax);
+    if (G.demote) has_msm = true;  // (the boosting instantiation is the general one: MUST_NOT and min_should_match)
+    const size_t lds = or_lds_bytes(W, has_msm, G.dismax, G.demote);
     const unsigned grid = (unsigned)(items2 / OR_WAVES);  // exact: items_per_query is a multiple of OR_WAVES
     auto go = [&](auto kern) -> hipError_t {
       hipError_t e = set_dynamic_lds_once(c, reinterpret_cast<const void*>(kern), lds);
@@ -1959,6 +1972,7 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
     auto pick = [&](auto legacy_tag) -> hipError_t {
       constexpr bool LG = decltype(legacy_tag)::value;
       if (G.dismax) return wide ? go(k_or_windows_max<LG, true>) : go(k_or_windows_max<LG, false>);
+      if (G.demote) return wide ? go(k_or_windows_dem<LG, true>) : go(k_or_windows_dem<LG, false>);
       if (has_msm)  // min_should_match > 1 somewhere: the general instantiation (it also handles MUST_NOT clauses)
         return wide ? go(k_or_windows<LG, true, true, true>) : go(k_or_windows<LG, false, true, true>);
       if (has_not) return wide ? go(k_or_windows<LG, true, true, false>) : go(k_or_windows<LG, false, true, false>);
@@ -2736,7 +2750,11 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       std::memcpy(&tie, &Q.n_must_not, sizeof tie);
       if (!std::isfinite(tie)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "RGPU_OP_DISMAX: n_must_not holds the bits of a finite f32 tie_breaker_multiplier");
     }
-    const int qnot = query_n_must_not(Q);
+    const NotCounts qn = query_not_counts(Q);
+    if (qn.stray) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "n_must_not: a MUST_NOT count, or RGPU_NOT_WITH_DEMOTE(n_not, n_demote) — bits 16 and up are zero");
+    const int qnot = qn.all();  // the clauses behind the scored and the optional ones
+    if (qn.n_demote > 0 && (qopt != 0 || (Q.op & (RGPU_OP_SHOULD_REQUIRED | RGPU_OP_NESTED_MUST)) != 0))
+      return fail(RGPU_ERR_UNSUPPORTED, "demoting clauses go with TERM, AND and OR positives (with or without MUST_NOT clauses), not with optional or nested clauses");
     if (((uint32_t)Q.op >> 26) != 0 && (!(Q.op & (RGPU_OP_SHOULD_REQUIRED | RGPU_OP_NESTED_MUST)) || (int)((uint32_t)Q.op >> 26) > Q.n_terms))
       return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "RGPU_OP_NESTED_AT: the nested clause's index among the MUST clauses, 0 .. n_terms, with RGPU_OP_SHOULD_REQUIRED / RGPU_OP_NESTED_MUST");
     // "+a +(b c)": the SHOULD clauses as a nested disjunction under MUST (ConjunctionScorer over the MUST clauses and one
@@ -2753,7 +2771,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
     if (qopt > 0 && qop == RGPU_OP_OR) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "optional SHOULD clauses go with MUST clauses (op TERM / AND); an OR query's clauses are its n_terms");
     // (an OR query of MUST_NOT clauses only: BooleanWeight::create_scorer -> None, boolean_query.rs:274-276 — it matches nothing)
     const int min_terms = (qop == RGPU_OP_OR && qnot > 0) ? 0 : 1;
-    if (Q.n_terms < min_terms || Q.n_terms > RGPU_MAX_QUERY_TERMS || qnot < 0 || qnot > RGPU_MAX_QUERY_TERMS ||
+    if (Q.n_terms < min_terms || Q.n_terms > RGPU_MAX_QUERY_TERMS || qn.n_not > RGPU_MAX_QUERY_TERMS || qnot > RGPU_MAX_QUERY_TERMS ||
         Q.n_terms + qopt + qnot > RGPU_MAX_QUERY_TERMS || (qop == RGPU_OP_TERM && Q.n_terms != 1))
       return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad clause count");
     if (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms + qopt + qnot > (int64_t)n_terms_total)
@@ -2761,6 +2779,11 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
     for (int i = 0; i < Q.n_terms + qopt + qnot; ++i) {
       const rgpu_query_term& t = terms[Q.first_term + i];
       if (i < Q.n_terms + qopt && (t.sim_table < 0 || t.sim_table >= c->n_sim_tables)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
+      if (i >= Q.n_terms + qopt + qn.n_not) {  // a demoting clause: `weight` is negative_boost (boosting_query.rs:31: 0 < b < 1), one value per query
+        const float b = t.weight, b0 = terms[Q.first_term + Q.n_terms + qopt + qn.n_not].weight;
+        if (!(b > 0.0f && b < 1.0f) || std::memcmp(&b, &b0, sizeof b) != 0)
+          return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a demoting clause's weight is the query's negative_boost: the same finite value in each, 0 < b < 1");
+      }
       if (t.state.doc_freq > 0) ptrs.push_back(&t.state);
       // the term's prepared structures, looked up ONCE per clause and call (by value: a later look-up may grow the table)
       if (t.state.doc_freq >= 2 && !need_prepare) {
@@ -2776,7 +2799,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
     if (rc != RGPU_OK) return rc;
     for (int32_t q = 0; q < n_queries; ++q) {
       const rgpu_query& Q = queries[q];
-      const int n_all = Q.n_terms + ((Q.op >> 16) & 0xff) + query_n_must_not(Q);
+      const int n_all = Q.n_terms + ((Q.op >> 16) & 0xff) + query_not_counts(Q).all();
       for (int i = 0; i < n_all; ++i) {
         const rgpu_query_term& t = terms[Q.first_term + i];
         if (t.state.doc_freq < 2) continue;
@@ -2799,11 +2822,12 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
     for (int32_t q = 0; q < n_queries; ++q) {
       const rgpu_query& Q = queries[q];
       const int qop = Q.op & 0xff, qopt = (Q.op >> 16) & 0xff;
+      const int qbehind = query_not_counts(Q).all();  // MUST_NOT and demoting clauses: dense ones get doc bitmaps under the same rules
       int n_look = 0;
       int64_t min_df = INT64_MAX;
       if (qop == RGPU_OP_OR) {
-        if (or_wide_ok && ((Q.op >> 8) & 0xff) <= 1 && Q.n_terms >= 10 && Q.n_terms <= ORX_MAX_TERMS && Q.n_must_not == 0) { n_look = Q.n_terms; min_df = min_df_or; }
-      } else if (qop != RGPU_OP_DISMAX && Q.n_terms + qopt + Q.n_must_not >= 2) { n_look = Q.n_terms + qopt + Q.n_must_not; min_df = min_df_and; }
+        if (or_wide_ok && ((Q.op >> 8) & 0xff) <= 1 && Q.n_terms >= 10 && Q.n_terms <= ORX_MAX_TERMS && qbehind == 0) { n_look = Q.n_terms; min_df = min_df_or; }
+      } else if (qop != RGPU_OP_DISMAX && Q.n_terms + qopt + qbehind >= 2) { n_look = Q.n_terms + qopt + qbehind; min_df = min_df_and; }
       // (only while a list's bits stay in an XCD's L2 — max_doc <= 16.7 M, the condition of and_xcd_chunk: measured on the 3-term
       // batch at 100 M docs, where they are 12.5 MB per list and every probe of a sparse list is an HBM sector, 1.94 ms with them
       // against 1.71 walking those clauses; at 10 M docs a batch of "rare AND medium" pairs 0.076 against 0.136 ms)
@@ -2843,7 +2867,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
     rucene::FlatFpMap<uint32_t> fresh;  // doc_start_fp -> 1 + sketch index, for the clauses of this call
     for (int32_t q = 0; q < n_queries; ++q) {
       const rgpu_query& Q = queries[q];
-      if ((Q.op & 0xff) != RGPU_OP_TERM || ((Q.op >> 16) & 0xff) != 0 || Q.n_must_not != 0) continue;
+      if ((Q.op & 0xff) != RGPU_OP_TERM || ((Q.op >> 16) & 0xff) != 0 || query_not_counts(Q).all() != 0) continue;
       const rgpu_query_term& t = terms[Q.first_term];
       const TermInfo& ti = tinfo[(size_t)Q.first_term];
       if (t.state.doc_freq < 2 || ti.sketch != 0 || ti.nblocks < TERM_SKETCH_MIN_BLOCKS || fresh.find(t.state.doc_start_fp)) continue;
@@ -2878,8 +2902,17 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
   groups[5].op = RGPU_OP_DISMAX;  // DisjunctionMaxQuery: a group of its own, never merged into the OR groups, never the heap-order kernels
   groups[5].dismax = true;
   int cur_dismax = 5;
+  // BoostingQuery: conjunctions (a TERM positive is a conjunction of one clause) and disjunctions with demoting clauses, each kind in
+  // a group of its own — only their launches take the HAS_DEM instantiations, every other launch runs the code it ran before
+  groups.emplace_back();
+  groups[6].op = RGPU_OP_AND;
+  groups[6].demote = true;
+  groups.emplace_back();
+  groups[7].op = RGPU_OP_OR;
+  groups[7].demote = true;
+  int cur_demote_or = 7;
   int64_t req_opt_records = 0;
-  std::vector<DevTerm> mine, mine_not, mine_opt, mine_suffix;
+  std::vector<DevTerm> mine, mine_not, mine_opt, mine_suffix, mine_dem;
   std::vector<int64_t> mine_bytes;
   for (int32_t q = 0; q < n_queries; ++q) {
     const rgpu_query& Q = queries[q];
@@ -2889,7 +2922,9 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
     mine_not.clear();
     mine_opt.clear();
     mine_suffix.clear();
+    mine_dem.clear();
     mine_bytes.clear();
+    const NotCounts qn = query_not_counts(Q);
     bool dead = false;
     for (int i = 0; i < Q.n_terms; ++i) {
       const rgpu_query_term& t = terms[Q.first_term + i];
@@ -2924,7 +2959,19 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
         std::stable_sort(mine_opt.begin(), mine_opt.end(), [](const DevTerm& a, const DevTerm& b) { return a.df < b.df; });
       // the nested disjunction has no scorer in this leaf = a MUST weight without a scorer: nothing matches (boolean_query.rs:203-207)
       if (should_required && mine_opt.empty()) mine.clear();
-      for (int i = 0; i < query_n_must_not(Q) && !mine.empty(); ++i) {
+      // Demoting clauses (BoostingWeight::create_scorer, boosting_query.rs:102-118): absent terms drop out of the union; when none is
+      // left the negative weight has no scorer here, and the query matches nothing in this leaf
+      for (int i = 0; i < qn.n_demote && !mine.empty(); ++i) {
+        const int at = Q.first_term + Q.n_terms + qopt + qn.n_not + i;
+        const rgpu_query_term& t = terms[at];
+        if (t.state.doc_freq <= 0) continue;
+        DevTerm dt;
+        rc = make_dev_term(seg, t.state, t.weight, 0, &dt, true, &tinfo[(size_t)at]);  // weight: negative_boost (the kernels read the first one's); no table
+        if (rc != RGPU_OK) return rc;
+        mine_dem.push_back(dt);
+      }
+      if (qn.n_demote > 0 && mine_dem.empty()) mine.clear();
+      for (int i = 0; i < qn.n_not && !mine.empty(); ++i) {
         const rgpu_query_term& t = terms[Q.first_term + Q.n_terms + qopt + i];
         if (t.state.doc_freq <= 0) continue;
         DevTerm dt;
@@ -2963,11 +3010,13 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       std::stable_sort(mine.begin(), mine.end(), [](const DevTerm& a, const DevTerm& b) { return a.df < b.df; });
     }
     // a term with prohibited / optional clauses runs as a one-clause conjunction (the lead-driven kernel probes them)
-    const int gop = (qop == RGPU_OP_TERM && (!mine_not.empty() || !mine_opt.empty() || nested_flat)) ? (int)RGPU_OP_AND : qop;
+    // (... and so does a term with demoting clauses: never k_search_term; the query keeps its group when the leaf emptied it)
+    const bool demoting = qn.n_demote > 0;
+    const int gop = (qop == RGPU_OP_TERM && (!mine_not.empty() || !mine_opt.empty() || nested_flat || demoting)) ? (int)RGPU_OP_AND : qop;
     // disjunction_scorer.rs:41-45: >= 10 children and min_should_match <= 1 -> the heap; weights must be >= +0 (the
     // kernel's "untouched" accumulator is -0.0f)
     // (the fixed-point kernels keep per-clause state for up to 16 clauses; a longer disjunction takes the clause-order kernel)
-    bool to_wide = or_wide_ok && gop == RGPU_OP_OR && mine.size() >= 10 && mine.size() <= (size_t)ORX_MAX_TERMS && qmsm <= 1 && mine_not.empty();
+    bool to_wide = or_wide_ok && gop == RGPU_OP_OR && mine.size() >= 10 && mine.size() <= (size_t)ORX_MAX_TERMS && qmsm <= 1 && mine_not.empty() && !demoting;
     for (size_t i = 0; to_wide && i < mine.size(); ++i)  // scores within [0, weight * (k1 + 1)]: what the fixed-point scale relies on
       to_wide = !std::signbit(mine[i].weight) && mine[i].weight <= 3.0e38f && c->sim_nonneg[(size_t)mine[i].sim_table];
     if (to_wide) {
@@ -2979,7 +3028,13 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       for (const DevTerm& m : mine) any_blocks = any_blocks || m.nblocks > 0 || m.tail_n > 0;
       to_wide = any_blocks && seg->dir_used > 0 && seg->bstore.p != nullptr && seg->pnorm.p != nullptr;
     }
-    if (gop == RGPU_OP_OR && !to_wide && groups[(size_t)cur_group[2]].postings > or_postings_cap) {
+    if (gop == RGPU_OP_OR && demoting && groups[(size_t)cur_demote_or].postings > or_postings_cap) {
+      groups.emplace_back();
+      groups.back().op = RGPU_OP_OR;
+      groups.back().demote = true;
+      cur_demote_or = (int)groups.size() - 1;
+    }
+    if (gop == RGPU_OP_OR && !to_wide && !demoting && groups[(size_t)cur_group[2]].postings > or_postings_cap) {
       groups.emplace_back();
       groups.back().op = RGPU_OP_OR;
       cur_group[2] = (int)groups.size() - 1;
@@ -3004,6 +3059,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       req_opt_records += lead_df;
     }
     Group& G = gop == RGPU_OP_DISMAX ? groups[(size_t)cur_dismax]
+               : demoting ? groups[(size_t)(gop == RGPU_OP_OR ? cur_demote_or : 6)]
                                      : (to_wide ? groups[3] : (to_req_opt ? groups[(size_t)cur_req_opt] : groups[(size_t)cur_group[gop]]));
     DevQuery dq;
     // the window kernel reads min_should_match from the second byte, the conjunction kernel its optional clause count
@@ -3013,10 +3069,12 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
             (int32_t)((uint32_t)mine_suffix.size() << 26);  // (device side: bits 26.. = MUST clauses added after the nested group)
     dq.first_term = (int32_t)G.terms.size();
     dq.n_terms = (int32_t)mine.size();
-    dq.pad = gop == RGPU_OP_DISMAX ? Q.n_must_not : (int32_t)mine_not.size();  // dismax: the tie-breaker's bits travel where n_not does
+    // dismax: the tie-breaker's bits travel where n_not does; boosting: n_not | n_dem << 8
+    dq.pad = gop == RGPU_OP_DISMAX ? Q.n_must_not : (int32_t)(mine_not.size() | (mine_dem.size() << 8));
     for (auto& m : mine) { G.terms.push_back(m); G.postings += m.df; }
     if (to_wide) G.term_bytes.insert(G.term_bytes.end(), mine_bytes.begin(), mine_bytes.end());
     for (auto& m : mine_not) { G.terms.push_back(m); G.postings += m.df; }
+    for (auto& m : mine_dem) { G.terms.push_back(m); G.postings += m.df; }  // (never next to optional clauses or a suffix)
     for (auto& m : mine_opt) { G.terms.push_back(m); G.postings += m.df; }
     for (auto& m : mine_suffix) { G.terms.push_back(m); G.postings += m.df; }
     G.qmap.push_back(q);
@@ -3066,7 +3124,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       for (int i = 0; i < nq; ++i) order[(size_t)i] = i;
       auto key_of = [&](int i) -> uint64_t {
         const DevQuery& q0 = G.queries[(size_t)i];
-        const int n_all = q0.n_terms + q0.pad + ((q0.op >> 16) & 0xff) + (int)((uint32_t)q0.op >> 26);
+        const int n_all = q0.n_terms + (G.demote ? (q0.pad & 0xff) + (q0.pad >> 8) : q0.pad) + ((q0.op >> 16) & 0xff) + (int)((uint32_t)q0.op >> 26);
         return n_all >= 2 && q0.n_terms >= 1 ? G.terms[(size_t)(q0.first_term + 1)].start_fp : 0ull;
       };
       std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key_of(a) > key_of(b); });
@@ -3132,7 +3190,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       bool any = false;
       clause_bitmaps.assign(G.terms.size(), TermBitmap{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0});
       for (const DevQuery& q0 : G.queries) {
-        const int n_all = q0.n_terms + q0.pad + ((q0.op >> 16) & 0xff) + (int)((uint32_t)q0.op >> 26);
+        const int n_all = q0.n_terms + (G.demote ? (q0.pad & 0xff) + (q0.pad >> 8) : q0.pad) + ((q0.op >> 16) & 0xff) + (int)((uint32_t)q0.op >> 26);
         for (int i = 1; i < n_all; ++i) {
           const DevTerm& t = G.terms[(size_t)(q0.first_term + i)];
           if (t.df < min_df) {
@@ -3204,7 +3262,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       c->last_counted_postings = G.postings;
       c->last_counted_loose = 0;
       for (const DevQuery& q0 : G.queries) if (q0.n_terms >= 1) { const DevTerm& t0 = G.terms[(size_t)q0.first_term]; c->last_counted_loose += t0.df == 1 ? 1 : t0.tail_n; }
-      TimedLaunch tl(c, stream, "k_search_and", G.postings);
+      TimedLaunch tl(c, stream, G.demote ? "k_search_and_dem" : "k_search_and", G.postings);
       // (whole rounds of 8 x AND_XCD_CHUNK workgroups: the kernel deals chunks of workgroups to the XCDs, search_and.hpp)
       const int xcd_chunk = and_xcd_chunk(seg);
       const unsigned grid = wg_count(and_grid((items + AND_WG_WAVES - 1) / AND_WG_WAVES, xcd_chunk));
@@ -3224,7 +3282,10 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       };
       bool has_not = false, has_opt = false;
       for (const DevQuery& q : G.queries) { has_not = has_not || q.pad != 0; has_opt = has_opt || ((q.op >> 16) & 0xff) != 0; }
-      if (has_opt) {  // one instantiation serves MUST_NOT too (rare trees: keep the instantiation count down)
+      if (G.demote) {  // (a group of BoostingQuerys: no optional clauses; the instantiation serves MUST_NOT too)
+        if (legacy) { if (wide) go(k_search_and<true, true, true, false, true>); else go(k_search_and<true, false, true, false, true>); }
+        else { if (wide) go(k_search_and<false, true, true, false, true>); else go(k_search_and<false, false, true, false, true>); }
+      } else if (has_opt) {  // one instantiation serves MUST_NOT too (rare trees: keep the instantiation count down)
         if (legacy) { if (wide) go(k_search_and<true, true, true, true>); else go(k_search_and<true, false, true, true>); }
         else { if (wide) go(k_search_and<false, true, true, true>); else go(k_search_and<false, false, true, true>); }
       } else if (has_not) {
@@ -3919,7 +3980,7 @@ extern "C" int32_t rgpu_rescore_batch(rgpu_segment* seg, const rgpu_query* queri
   for (int32_t q = 0; q < n_queries; ++q) {
     const rgpu_query& Q = queries[q];
     const int qop = Q.op & 0xff;
-    if (qop < RGPU_OP_TERM || qop > RGPU_OP_OR || (Q.op >> 8) > 1 || Q.n_must_not != 0)
+    if (qop < RGPU_OP_TERM || qop > RGPU_OP_OR || (Q.op >> 8) > 1 || Q.n_must_not != 0)  // (MUST_NOT or demoting clauses: any bit of the field)
       return fail(RGPU_ERR_UNSUPPORTED, "rescore queries are TERM, all-MUST or all-SHOULD term queries");
     if (Q.n_terms < 1 || Q.n_terms > RGPU_MAX_QUERY_TERMS || (qop == RGPU_OP_TERM && Q.n_terms != 1)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad clause count");
     if (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms > (int64_t)n_terms_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "clause range outside terms[]");

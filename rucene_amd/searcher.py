@@ -6,6 +6,7 @@ argument meaning and error behaviour so tests read like the reference's own (pat
     search/query/term_query.rs:45-95                         TermQuery::new(term, boost) / create_weight
     search/query/boolean_query.rs:40-86                      BooleanQuery::build(musts, shoulds, ...)
     search/query/disjunction_max_query.rs:43-114             DisjunctionMaxQuery { disjuncts, tie_breaker_multiplier }
+    search/query/boosting_query.rs:29-118                    BoostingQuery::build(positive, negative, negative_boost)
     search/similarity/bm25_similarity.rs:45-177              BM25Similarity::new(k1, b) / compute_weight
     search/collector/top_docs.rs:97-183                      TopDocsCollector::new(k) / top_docs()
     search/statistics.rs                                     CollectionStatistics / TermStatistics
@@ -453,6 +454,44 @@ class DisjunctionMaxQuery:
         return "DisjunctionMaxQuery(disjunctions: %s, tie_breaker_multiplier: %s)" % (", ".join(str(q) for q in self.disjuncts), shown)
 
 
+class BoostingQuery:
+    """query/boosting_query.rs:29-118, scorer/boosting_scorer.rs:40-81: the positive query's docs, counts and scores, a doc's score
+    multiplied once by negative_boost where the negative query also holds it; a leaf in which the negative query has no scorer
+    matches nothing. The GPU path serves (RGPU_NOT_WITH_DEMOTE in include/rucene_gpu.h) a positive that is a TermQuery or a flat
+    BooleanQuery packing to TERM / AND / OR (with or without MUST_NOT clauses), a negative that is a TermQuery or a should-only flat
+    BooleanQuery with min_should_match <= 1, and 0 < negative_boost < 1 (BoostingScorer::new's debug_assert); anything else is
+    UnsupportedOperation when the query is searched, i.e. the caller's CPU path."""
+
+    def __init__(self, positive, negative, negative_boost):
+        self.positive, self.negative = positive, negative
+        self.negative_boost = float(np.float32(negative_boost))
+
+    @staticmethod
+    def build(positive, negative, negative_boost):
+        return BoostingQuery(positive, negative, negative_boost)
+
+    def demoting_terms(self):
+        """The negative query as a union of TermQuery clauses, or None when it is not of that shape."""
+        n = self.negative
+        if isinstance(n, TermQuery):
+            return [n]
+        if (isinstance(n, BooleanQuery) and n.is_flat() and n.should_queries and n.min_should_match <= 1
+                and not (n.must_queries or n.must_not_queries or n.filter_queries)):
+            return list(n.should_queries)
+        return None
+
+    def boost_bits(self):
+        """negative_boost's f32 bit pattern (what every demoting clause's `weight` carries)."""
+        return int(np.float32(self.negative_boost).view(np.int32))
+
+    def extract_terms(self):   # :62-64
+        return self.positive.extract_terms()
+
+    def __str__(self):   # :71-79
+        shown = np.format_float_positional(np.float32(self.negative_boost), unique=True, trim="-")
+        return "BoostingQuery(positive: %s, negative: %s, negative_boost: %s)" % (self.positive, self.negative, shown)
+
+
 class TopDocs:
     def __init__(self, total_hits, score_docs):
         self._total, self._docs = int(total_hits), score_docs
@@ -539,9 +578,25 @@ class GpuIndexSearcher:
         return self._weights[key]
 
     def _flatten(self, query):
-        """-> (op, required / scored clauses, optional SHOULD clauses beside MUST ones, MUST_NOT clauses)"""
+        """-> (op, required / scored clauses, optional SHOULD clauses beside MUST ones, MUST_NOT clauses — a BoostingQuery's demoting
+        clauses behind them: _boosting_fields)"""
         if isinstance(query, TermQuery):
             return OP_TERM, [query], [], []
+        if isinstance(query, BoostingQuery):
+            demoting = query.demoting_terms()
+            if demoting is None:
+                raise RgpuError(-5, "a BoostingQuery is served by the GPU path when its negative query is a term or a flat disjunction of terms")
+            if not 0.0 < query.negative_boost < 1.0:   # (NaN fails both comparisons)
+                raise RgpuError(-5, "a BoostingQuery is served by the GPU path for 0 < negative_boost < 1")
+            if not isinstance(query.positive, (TermQuery, BooleanQuery)):
+                raise RgpuError(-5, "a BoostingQuery is served by the GPU path when its positive query is a term or a flat boolean query")
+            positive = query.positive.normalized() if isinstance(query.positive, BooleanQuery) else query.positive
+            if isinstance(positive, BooleanQuery) and not positive.is_flat():
+                raise RgpuError(-5, "a BoostingQuery over nested boolean clauses is not served by the GPU path")
+            op, clauses, opts, nots = self._flatten(positive)
+            if opts or (op & ~0xffff):
+                raise RgpuError(-5, "a BoostingQuery over MUST + SHOULD clauses is not served by the GPU path")
+            return op, clauses, [], list(nots) + demoting
         if isinstance(query, DisjunctionMaxQuery):
             if not all(isinstance(q, TermQuery) for q in query.disjuncts):
                 raise RgpuError(-5, "a DisjunctionMaxQuery is served by the GPU path when every disjunct is a TermQuery")
@@ -654,7 +709,7 @@ class GpuIndexSearcher:
             # (the planner resolves and weighs a dismax query's clauses as an OR query's; its op and tie-breaker are written afterwards)
             qs, ts = self._planner(leaf).plan_batch([OP_OR if f[0] == OP_DISMAX else f[0] for f in flat], [len(f[1]) for f in flat],
                                                     [c.term for c in clauses], [len(f[3]) for f in flat], boosts)
-            return self._dismax_fields(queries, qs), ts
+            return self._boosting_fields(queries, self._dismax_fields(queries, qs), ts)
         return self._pack_clause_by_clause(queries, leaf, flat)
 
     @staticmethod
@@ -664,6 +719,20 @@ class GpuIndexSearcher:
             if isinstance(q, DisjunctionMaxQuery):
                 qs[i]["op"], qs[i]["n_must_not"] = OP_DISMAX, q.tie_bits()
         return qs
+
+    @staticmethod
+    def _boosting_fields(queries, qs, ts):
+        """RGPU_NOT_WITH_DEMOTE: the last n_demote of the clauses planned as MUST_NOT are the demoting ones — the count moves to the
+        field's second byte, their weight is negative_boost, their table is never read."""
+        for i, q in enumerate(queries):
+            if isinstance(q, BoostingQuery):
+                n_dem = len(q.demoting_terms())
+                n_not = int(qs[i]["n_must_not"]) - n_dem
+                qs[i]["n_must_not"] = n_not | (n_dem << 8)
+                at = int(qs[i]["first_term"]) + int(qs[i]["n_terms"]) + n_not
+                ts["weight"][at:at + n_dem] = np.float32(q.negative_boost)
+                ts["sim_table"][at:at + n_dem] = 0
+        return qs, ts
 
     def _pack_clause_by_clause(self, queries, leaf, flat=None):
         """pack() one clause at a time in Python: mixed naming schemes, numpy-scalar ids; also what tests hold the native
@@ -693,7 +762,7 @@ class GpuIndexSearcher:
                 ts[pos]["weight"] = w
                 ts[pos]["sim_table"] = table
                 pos += 1
-        return self._dismax_fields(queries, qs), ts
+        return self._boosting_fields(queries, self._dismax_fields(queries, qs), ts)
 
     def search_phrase_batch(self, queries, k):
         """IndexSearcher::search(PhraseQuery, TopDocsCollector(k)) for a batch of exact phrases -> (hits, total_hits).

@@ -1,5 +1,5 @@
 """Minimal driver for profiling: build the 10M-doc shard, run one workload a few times through the C ABI.
-usage: run_workload.py [term|and3|and2sparse|mustor|mustand|dismax|or10|decode|cold|posdec|phrase2|sloppy2] [reps]   (DOCS=... sets the shard size; cold = a fresh segment per repetition:
+usage: run_workload.py [term|and3|and2sparse|mustor|mustand|dismax|boosting|or10|decode|cold|posdec|phrase2|sloppy2] [reps]   (DOCS=... sets the shard size; cold = a fresh segment per repetition:
 skip decode + block framing + alignment + tails (k_prepare_terms, k_prepare_blocks), then k_decode_terms, for every df >= 128 term)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -112,6 +112,43 @@ elif kind == "dismax":
     print("dismax: hit counts equal the disjunctions' on %d of %d queries; matches in all: %d; every dismax score <= the sum: %s"
           % (int((dt == ot).sum()), len(tids), int(dt.sum()), bool((dh["score"][:, 0] <= oh["score"][:, 0] * (1 + 1e-5)).all())))
     plain.close()
+elif kind == "boosting":
+    # BoostingQuery (RGPU_NOT_WITH_DEMOTE): the and3 batch's conjunctions and the term batch's terms, each with one demoting term
+    # (log-uniform ranks 1..1000) at negative_boost 0.5 - two batches through k_search_and's HAS_DEM instantiation - next to the same
+    # positives alone (k_search_and / k_search_term) on the same build. Launch times from the kernel statistics: the median of `reps`
+    # launches after two warm-up batches. Hit counts are cross-checked: demotion never changes which docs match (every demoting term
+    # of the synthetic shard has postings).
+    Bo = rucene_amd.BoostingQuery
+    k = 10
+    and_ids = indexgen.log_uniform_ranks(3 * 1024, 1, 1000, SEED ^ 0xA3).reshape(-1, 3) - 1
+    term_ids = indexgen.log_uniform_ranks(1024, 1, 10_000, SEED).reshape(-1) - 1
+    dem_ids = indexgen.log_uniform_ranks(2 * 1024, 1, 1000, SEED ^ 0xB0).reshape(2, -1) - 1
+    def timed(queries, names):
+        qs, ts = s.pack(queries, leaf)
+        for _ in range(2):
+            leaf.segment.search_batch(qs, ts, k)
+        ctx.kernel_stats_reset()
+        for _ in range(reps):
+            hits, totals = leaf.segment.search_batch(qs, ts, k)
+        st = ctx.kernel_stats()
+        for n in names:
+            if n in st:
+                print("%s: median %.4f ms (min %.4f, max %.4f) over %d launches" % (n, st[n]["median_ms"], st[n]["min_ms"], st[n]["max_ms"], st[n]["launches"]))
+        return hits, totals
+    and_pos = [B.build([T(int(t)) for t in row], []) for row in and_ids]
+    term_pos = [T(int(t)) for t in term_ids]
+    print("-- 1024 x (3-term AND + one demoting term)")
+    bh, bt = timed([Bo(q, T(int(d)), 0.5) for q, d in zip(and_pos, dem_ids[0])], ("k_search_and_dem", "k_merge_items"))
+    print("-- the same conjunctions alone")
+    ph, pt = timed(and_pos, ("k_search_and", "k_merge_items"))
+    print("boosting: AND hit counts equal the positives' on %d of %d queries; every score <= the positive's: %s"
+          % (int((bt == pt).sum()), len(and_pos), bool((bh["score"][:, 0] <= ph["score"][:, 0]).all())))
+    print("-- 1024 x (TERM + one demoting term)")
+    bh, bt = timed([Bo(q, T(int(d)), 0.5) for q, d in zip(term_pos, dem_ids[1])], ("k_search_and_dem", "k_merge_items"))
+    print("-- the same terms alone")
+    ph, pt = timed(term_pos, ("k_search_term", "k_merge_items"))
+    print("boosting: TERM hit counts equal the positives' on %d of %d queries; every score <= the positive's: %s"
+          % (int((bt == pt).sum()), len(term_pos), bool((bh["score"][:, 0] <= ph["score"][:, 0]).all())))
 elif kind == "mustand":
     # "+a +(+b +c)" (RGPU_OP_NESTED_MUST): the and3 batch's triples as nested trees; rows against the flat conjunctions' (same docs and
     # counts; scores a + (b + c) against (x + y) + z in cost order: equal within 1e-5, and not always bit for bit)
