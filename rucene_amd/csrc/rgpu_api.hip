@@ -1866,7 +1866,11 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
   // (dismax: 512 docs by default — the LDS, and so the workgroups per CU, of the plain kernel's 1024)
   const int W_cfg = std::min(4096, std::max(256, c->cfg.or_window_docs > 0 ? (c->cfg.or_window_docs + 255) / 256 * 256 : (G.dismax ? 512 : 1024)));
   // (boosting: W / 8 bytes of demotion bits per wavefront on top of the general kernel's cells — narrowed the same way)
-  const int W = G.dismax ? or_fit_window(W_cfg, false, true) : (G.demote ? or_fit_window(W_cfg, true, false, true) : W_cfg);
+  // (min_should_match > 1 somewhere in the group: a counter byte per doc next to the accumulator — 4096-doc windows no longer fit)
+  bool has_not = false, has_msm = false;  // (a dismax query has neither: its DevQuery::pad holds the tie-breaker's bits)
+  if (!G.dismax) for (const DevQuery& dq : G.queries) { has_not = has_not || dq.pad != 0; has_msm = has_msm || ((dq.op >> 8) & 0xff) > 1; }
+  if (G.demote) has_msm = true;  // (the boosting instantiation is the general one: MUST_NOT and min_should_match)
+  const int W = G.dismax ? or_fit_window(W_cfg, false, true) : (G.demote ? or_fit_window(W_cfg, true, false, true) : or_fit_window(W_cfg, has_msm, false));
   const int dense_max = c->cfg.or_dense_clauses < 0 ? 0 : (c->cfg.or_dense_clauses == 0 ? OR_DENSE_MAX : std::min(c->cfg.or_dense_clauses, OR_DENSE_MAX));
   if (dense_max > 0 && seg->d_norms && seg->n_norm_ranks > 0) {
     for (DevQuery& dq : G.queries) {
@@ -1957,9 +1961,6 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
   }
   {
     TimedLaunch tl(c, stream, G.dismax ? "k_or_windows_max" : (G.demote ? "k_or_windows_dem" : "k_or_windows"), G.postings);
-    bool has_not = false, has_msm = false;  // (a dismax query has neither: its DevQuery::pad holds the tie-breaker's bits)
-    if (!G.dismax) for (const DevQuery& dq : G.queries) { has_not = has_not || dq.pad != 0; has_msm = has_msm || ((dq.op >> 8) & 0xff) > 1; }
-    if (G.demote) has_msm = true;  // (the boosting instantiation is the general one: MUST_NOT and min_should_match)
     const size_t lds = or_lds_bytes(W, has_msm, G.dismax, G.demote);
     const unsigned grid = (unsigned)(items2 / OR_WAVES);  // exact: items_per_query is a multiple of OR_WAVES
     auto go = [&](auto kern) -> hipError_t {
