@@ -574,10 +574,17 @@ int32_t rgpu_plan_uniform_bytes(rgpu_planner* planner, int32_t op, int32_t n_que
  * does from the top (search/searcher.rs:487-525: create_normalized_weight -> TermQuery::create_weight, term_query.rs:58-95;
  * then per leaf TermWeight::create_scorer, :145-163, and the collector loop). Same rows as the two calls, bit for bit; enqueue-
  * only like rgpu_search_batch_device (rgpu_config.or_deferred applies). Single-term batches whose terms are all prepared take
- * a one-pass path (planner entry -> device descriptor, two enqueues: the host's share of a 1024-query batch drops from ~63
- * to ~13 us); every other batch is planned and searched as the two calls would. Flat-table planners only. The planner keeps a
- * memo of finished descriptors for that path (65536 records, 5 MB of host memory, allocated by the first such call; emptied
- * whenever the segment's prepared terms change). */
+ * a one-pass path (planner entry -> device descriptor: the host's share of a 1024-query batch drops from ~63 to ~13 us);
+ * every other batch is planned and searched as the two calls would. Flat-table planners only. The planner keeps a memo of
+ * finished descriptors for that path (65536 records, about 7 MB of host memory, allocated by the first such call; emptied whenever
+ * the segment's prepared terms change), and the context keeps the descriptors themselves on the device: an append-only arena
+ * of 262144 records (16 MB; RGPU_TERM_ARENA_RECORDS in the environment of rgpu_init), written once per term by the call that
+ * first names it, on that call's stream. A step in steady state then sends 8 bytes per query and makes ONE enqueue (the search
+ * kernel); a call that names records another stream uploaded and that are not known complete makes its stream wait for that
+ * upload's event. A new arena generation (fresh buffer, emptied memo) starts when the prepared terms, the segment or the
+ * similarity table change, or the arena is full; a retired generation's buffer is freed once every call that read it has been
+ * waited for (at the latest by rgpu_synchronize, rgpu_segment_free, rgpu_shutdown). RGPU_TERM_PLAN=staged in the environment
+ * of rgpu_init: the whole plan is staged every step instead (A/B; what RGPU_STAGE_COPY=dma and RGPU_UPLOAD_ASIDE=1 also do). */
 int32_t rgpu_planner_search_uniform_ids_device(rgpu_planner* planner, rgpu_segment* seg, int32_t op, int32_t n_queries, int32_t n_clauses,
                                                const int64_t* term_ids, int32_t k, void* hits_dev, void* total_hits_dev, void* hip_stream);
 /* ... and as rgpu_search_batch_sharded: this rank's plan + search -> the all-gather of the shards' records -> the merge. */

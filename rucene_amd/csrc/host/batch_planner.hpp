@@ -162,6 +162,59 @@ class BatchPlanner {
     return true;
   }
 
+  // for_each_flat_memo for records that ALSO live in an append-only arena outside this planner (host/term_arena.hpp: the device-resident
+  // term descriptors). Beside its record a memo entry keeps where the arena holds it and the arena generation that index belongs to;
+  // an entry placed under another generation than `arena_gen` is a miss like any other (made and placed again — the old index is an
+  // orphan, never handed out again). place(rec) -> the record's index in the arena, or < 0: give up (the entry is dropped, returns
+  // false at once; so does make() < 0). use(i, rec or null, index) in id order. Same table, same key rule and same lock as
+  // for_each_flat_memo; entries that function made carry no place and are placed on their first use here.
+  template <class Rec, class Make, class Place, class Use>
+  bool for_each_flat_memo_placed(const int64_t* ids, int64_t n, const MemoKey& key, uint32_t arena_gen, Make&& make, Place&& place, Use&& use) {
+    static_assert(std::is_trivially_copyable<Rec>::value && sizeof(Rec) <= FLAT_MEMO_REC, "a plain record of at most FLAT_MEMO_REC bytes");
+    std::lock_guard<std::mutex> g(mu_);
+    if (flat_memo_.empty() || !(flat_memo_key_ == key) || flat_memo_rec_ != sizeof(Rec)) {
+      if (flat_memo_.empty() || ++flat_memo_gen_ == 0) {
+        flat_memo_.assign(FLAT_MEMO_SLOTS, FlatMemoSlot{});
+        flat_memo_gen_ = 1;
+      }
+      flat_memo_key_ = key;
+      flat_memo_rec_ = sizeof(Rec);
+    }
+    if (flat_memo_place_.empty()) flat_memo_place_.assign(FLAT_MEMO_SLOTS, FlatMemoPlace{});
+    const uint32_t gen = flat_memo_gen_;
+    const int64_t n_leaf = (int64_t)leaf_states_.size();
+    const int64_t n_stats = own_stats_ ? (int64_t)stats_df_.size() : n_leaf;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t id = ids[i];
+      if (id < 0 || id >= n_leaf) { use(i, static_cast<const Rec*>(nullptr), (int32_t)-1); continue; }
+      const size_t at = (size_t)(((uint64_t)id * 0x9E3779B97F4A7C15ull) >> (64 - FLAT_MEMO_BITS));
+      FlatMemoSlot& e = flat_memo_[at];
+      FlatMemoPlace& p = flat_memo_place_[at];
+      Rec* rec = reinterpret_cast<Rec*>(e.rec);
+      if (e.id != id || e.gen != gen || (e.held && (p.id != id || p.memo_gen != gen || p.arena_gen != arena_gen))) {
+        const rgpu_term_state& st = leaf_states_[(size_t)id];
+        int32_t held = 0;
+        p = FlatMemoPlace{};
+        if (st.doc_freq > 0) {
+          int32_t df = 0;
+          if (id < n_stats) df = own_stats_ ? stats_df_[(size_t)id] : st.doc_freq;
+          held = make(st, idf_of(df > 0 ? df : 0), rec);
+          if (held < 0) { e.gen = 0; return false; }
+          if (held) {
+            const int64_t where = place(static_cast<const Rec*>(rec));
+            if (where < 0) { e.gen = 0; return false; }
+            p = FlatMemoPlace{id, gen, (uint32_t)where, arena_gen};
+          }
+        }
+        e.id = id;
+        e.gen = gen;
+        e.held = held;
+      }
+      use(i, e.held ? rec : static_cast<const Rec*>(nullptr), e.held ? (int32_t)p.index : (int32_t)-1);
+    }
+    return true;
+  }
+
   // The flat-table planner's per-clause work WITHOUT the arrays in between (the fused plan + search entry points write device
   // descriptors straight from it): f(i, state, weight) for every id, boost 1, under the planner's lock. An id outside the
   // table, or a term the leaf does not hold, arrives with doc_freq = 0 (TermWeight::create_scorer -> None).
@@ -206,6 +259,10 @@ class BatchPlanner {
   static constexpr size_t FLAT_MEMO_SLOTS = (size_t)1 << FLAT_MEMO_BITS;
   static constexpr size_t FLAT_MEMO_REC = 64;
   struct FlatMemoSlot { int64_t id = -1; uint32_t gen = 0; int32_t held = 0; alignas(8) unsigned char rec[FLAT_MEMO_REC] = {}; };
+  // where an arena outside the planner holds a slot's record (for_each_flat_memo_placed); it names the entry it belongs to, so an entry
+  // for_each_flat_memo has rewritten since is not taken for placed
+  struct FlatMemoPlace { int64_t id = -1; uint32_t memo_gen = 0; uint32_t index = 0; uint32_t arena_gen = 0; };
+  std::vector<FlatMemoPlace> flat_memo_place_;  // (empty until the first for_each_flat_memo_placed)
   uint32_t flat_memo_gen_ = 0;  // the generation the current key's records carry (0: no slot is valid)
   std::vector<FlatMemoSlot> flat_memo_;  // (empty until the first for_each_flat_memo: 5 MB)
   MemoKey flat_memo_key_{{0, 0, 0, 0}};

@@ -60,9 +60,12 @@ template <bool LEGACY, bool WIDE, int W>
 __global__ __launch_bounds__(64 * W, (LEGACY || WIDE) ? RGPU_TERM_OTHER_WAVES : RGPU_TERM_FAST_WAVES)
 void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, const DevTerm* __restrict__ terms,
                          const int32_t* __restrict__ order, int n_queries, int k, unsigned long long* __restrict__ work_slots,
-                         const int32_t* __restrict__ qmap, HitOut* __restrict__ hits, int64_t* __restrict__ totals, int32_t doc_base) {
+                         const int32_t* __restrict__ qmap, HitOut* __restrict__ hits, int64_t* __restrict__ totals, int32_t doc_base,
+                         const TermLaunch* __restrict__ launch) {
   // order[i]: the query of workgroup i (heaviest first); work_slots (nullable): [q] = bytes requested for query q, [n_queries + q] =
-  // FullBlocks unpacked (rgpu_last_search_counters)
+  // FullBlocks unpacked (rgpu_last_search_counters).
+  // launch (nullable; pinned host memory): workgroup i's whole plan is launch[i] — `terms` is then the context's descriptor arena and
+  // `queries`, `order` and `qmap` are not read: one read over the bus and one of device memory instead of order -> query -> term
   constexpr int LIST_N = WIDE ? 128 : 64;
   constexpr int NT = 64 * W;
   constexpr int DEPTH = PREFETCH_DEPTH;
@@ -82,20 +85,32 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
   const int lane = lane_id();
   const int wave = wave_id();
   const int tid = (int)threadIdx.x;
-  const int q = order != nullptr ? order[blockIdx.x] : (int)blockIdx.x;
-  if (q >= n_queries) return;
-  const int row = qmap ? qmap[q] : q;
+  int q, row, rec;
+  if (launch != nullptr) {
+    if ((int)blockIdx.x >= n_queries) return;
+    const TermLaunch L = launch[blockIdx.x];
+    q = row = L.row;
+    rec = L.rec;
+  } else {
+    q = order != nullptr ? order[blockIdx.x] : (int)blockIdx.x;
+    if (q >= n_queries) return;
+    row = qmap ? qmap[q] : q;
+    const DevQuery Q = queries[q];
+    rec = Q.n_terms < 1 ? -1 : Q.first_term;
+  }
   HitOut* out = hits + (size_t)row * (size_t)k;
-  const DevQuery Q = queries[q];
-  if (Q.n_terms < 1) {  // clause absent from this leaf: nothing to collect
+  if (rec < 0) {  // clause absent from this leaf: nothing to collect
     if (wave == 0) {
       if (lane < k) out[lane] = HitOut{-1, 0.f};
       if (WIDE && lane + 64 < k) out[lane + 64] = HitOut{-1, 0.f};
-      if (lane == 0) totals[row] = 0;
+      if (lane == 0) {
+        totals[row] = 0;
+        if (work_slots != nullptr) { work_slots[q] = 0ull; work_slots[n_queries + q] = 0ull; }  // (nobody zeroes them ahead of a launch-record step)
+      }
     }
     return;
   }
-  const DevTerm T = terms[Q.first_term];
+  const DevTerm T = terms[rec];
   const bool has_norms = seg.norms != nullptr;
   const bool tabled = has_norms && seg.n_norm_ranks > 0;
   const bool fast = tabled && seg.live == nullptr && T.weight >= 0.0f && RGPU_TERM_PRUNE && (T.flags & TERM_FLAG_MONOTONE) != 0u;

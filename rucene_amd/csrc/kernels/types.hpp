@@ -124,6 +124,13 @@ struct TermBitmap {
   int32_t pad;
 };
 
+// One workgroup of k_search_term_query when the term descriptors live on the device (rgpu_api.hip term_batch_resident): the whole
+// per-step plan of a query, in launch order, read straight from pinned host memory.
+struct TermLaunch {
+  int32_t rec;  // the term's DevTerm in the descriptor arena; -1: the leaf does not hold the term
+  int32_t row;  // the caller's row (and the query's work-counter slot)
+};
+
 struct DevQuery {
   int32_t op;
   int32_t n_terms;     // positive clauses (MUST or SHOULD) that exist in this leaf

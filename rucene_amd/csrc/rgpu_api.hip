@@ -32,6 +32,7 @@
 #include "host/flat_fp_map.hpp"
 #include "host/host_threads.hpp"
 #include "host/prepared_map.hpp"
+#include "host/term_arena.hpp"
 #include "kernels/search_phrase.hpp"
 #include "kernels/search_term.hpp"
 #include "kernels/search_term_query.hpp"
@@ -229,6 +230,11 @@ struct rgpu_ctx {
   // the fused single-term call runs k_search_term_query (one workgroup of term_query_waves waves per query) when the library sizes
   // the items and folds in the launch; RGPU_TERM_KERNEL=items in the environment: k_search_term's work items (A/B)
   bool term_query_kernel = true;
+  // ... and reads its plan as one TermLaunch per query from the pinned stage, the term descriptors staying on the device in `arena`
+  // (term_batch_resident); RGPU_TERM_PLAN=staged in the environment: the whole plan is staged every step, as before (A/B)
+  bool term_plan_resident = true;
+  rucene::TermArena arena;             // the descriptor arena's bookkeeping (host/term_arena.hpp); RGPU_TERM_ARENA_RECORDS sizes it
+  std::vector<void*> arena_spares;     // buffers of retired generations, kept for the next turnover (at most ARENA_SPARES_MAX)
   int term_query_waves = 4;       // 2, 4 or 8 (RGPU_TERM_QUERY_WAVES)
   int term_min_item_blocks = 64;  // ... and none of its items shorter than this (RGPU_TERM_MIN_ITEM_BLOCKS)
   int term_target_items = 3000;  // single-term launches: items of the launch's size, at most about this many (RGPU_TERM_TARGET_ITEMS in the environment)
@@ -398,6 +404,65 @@ static int32_t settle_pending(rgpu_ctx* c) {
   return RGPU_OK;
 }
 
+// ---- the descriptor arena's device side (host/term_arena.hpp has the rules) ------------------------------------------------
+constexpr size_t ARENA_SPARES_MAX = 4;
+static_assert(N_SCRATCH <= rucene::TermArena::MAX_SLOTS, "one arena tag per scratch slot");
+static void arena_give_back(rgpu_ctx* c, void* buf) {
+  if (c->arena_spares.size() < ARENA_SPARES_MAX) c->arena_spares.push_back(buf);
+  else (void)hipFree(buf);
+}
+static void arena_release_retired(rgpu_ctx* c) {
+  if (c->arena.retired() != 0) c->arena.release_retired([&](void* buf) { arena_give_back(c, buf); });
+}
+// the slot's event has been waited for: its generation tag goes, uploads its stream carried are complete, and a retired generation
+// nobody reads any more hands its buffer back
+static void arena_slot_waited(rgpu_ctx* c, int slot) {
+  if (!c->arena.slot_tagged(slot)) return;
+  c->arena.slot_waited(slot);
+  arena_release_retired(c);
+}
+// ... after a device-wide wait
+static void arena_all_waited(rgpu_ctx* c) {
+  c->arena.all_waited();
+  arena_release_retired(c);
+}
+// a buffer for the generation that has just started: a spare one (its old contents are never read: indices start at 0 again and a
+// record is read only after its own upload), or a fresh allocation
+static hipError_t arena_new_buffer(rgpu_ctx* c) {
+  void* buf = nullptr;
+  if (!c->arena_spares.empty()) { buf = c->arena_spares.back(); c->arena_spares.pop_back(); }
+  else {
+    const hipError_t e = hipMalloc(&buf, (size_t)c->arena.capacity() * sizeof(DevTerm));
+    if (e != hipSuccess) return e;
+  }
+  c->arena.set_buffer(buf);
+  return hipSuccess;
+}
+// wait for the busy slots that still read a retired generation (all = false) or any generation (all = true)
+static hipError_t arena_wait_slots(rgpu_ctx* c, bool all) {
+  for (int i = 0; i < N_SCRATCH; ++i) {
+    if (!(all ? c->arena.slot_tagged(i) : c->arena.slot_holds_retired(i))) continue;
+    if (c->scr[i].busy) {
+      const hipError_t e = hipEventSynchronize(c->scr[i].done);
+      if (e != hipSuccess) return e;
+      c->scr[i].busy = false;
+    }
+    arena_slot_waited(c, i);
+  }
+  return hipSuccess;
+}
+// everything goes (segment close, context close): the caller has waited for the work it enqueued
+static void arena_drop(rgpu_ctx* c, bool keep_spares) {
+  (void)arena_wait_slots(c, true);
+  c->arena.retire_current();
+  arena_release_retired(c);
+  if (!keep_spares) {
+    for (void* b : c->arena_spares) (void)hipFree(b);
+    c->arena_spares.clear();
+    while (void* e = c->arena.take_spare_event()) (void)hipEventDestroy((hipEvent_t)e);
+  }
+}
+
 // ---- scratch slots -------------------------------------------------------------------------------------------------
 // take the next slot (waiting for the work that used it N_SCRATCH calls ago) ...
 static hipError_t scratch_take(rgpu_ctx* c) {
@@ -414,6 +479,7 @@ static hipError_t scratch_take(rgpu_ctx* c) {
     if (e != hipSuccess) return e;
     sc->busy = false;
   }
+  arena_slot_waited(c, (int)(sc - c->scr));  // (also when somebody else waited for the slot's event and cleared `busy`)
   c->S = sc;
   if (c->last_counted == sc) { c->last_counted = nullptr; c->last_counted_words = nullptr; }  // (its counters may live in the slot's stage: gone with the reuse)
   return hipSuccess;
@@ -623,6 +689,7 @@ static int32_t enforce_prepared_budget(rgpu_segment* seg) {
   HIP_TRY(hipDeviceSynchronize());
   for (auto& sc : c->scr) sc.busy = false;
   for (auto& cs : c->ceil_slots) cs.busy = false;
+  arena_all_waited(c);
   seg->prepared.clear();
   seg->dir_used = seg->bstore_used = seg->pnorm_used = seg->sketch_used = 0;  // the arrays keep their capacity and are refilled from the start
   c->stats[(size_t)stat_slot(c, "prepared_store_evictions")].launches += 1;  // (read by tests / callers through rgpu_kernel_stats)
@@ -1177,6 +1244,8 @@ extern "C" int32_t rgpu_init(int32_t device_ordinal, const rgpu_config* cfg, rgp
   if (const char* e = std::getenv("RGPU_STAGE_COPY")) c->stage_by_kernel = std::strcmp(e, "dma") != 0;
   if (const char* e = std::getenv("RGPU_TERM_FOLD")) c->term_fold = std::atoi(e) != 0;
   if (const char* e = std::getenv("RGPU_TERM_KERNEL")) c->term_query_kernel = std::strcmp(e, "items") != 0;
+  if (const char* e = std::getenv("RGPU_TERM_PLAN")) c->term_plan_resident = std::strcmp(e, "staged") != 0;
+  if (const char* e = std::getenv("RGPU_TERM_ARENA_RECORDS")) c->arena = rucene::TermArena((uint32_t)std::max(1, std::min(1 << 24, std::atoi(e))));
   if (const char* e = std::getenv("RGPU_TERM_QUERY_WAVES")) { const int w = std::atoi(e); c->term_query_waves = w <= 2 ? 2 : w >= 8 ? 8 : 4; }
   if (const char* e = std::getenv("RGPU_TERM_MIN_ITEM_BLOCKS")) c->term_min_item_blocks = std::max(8, std::min(4096, std::atoi(e)));
   if (const char* e = std::getenv("RGPU_TERM_SPLIT")) c->term_split = std::max(1, std::min(64, std::atoi(e)));
@@ -1200,6 +1269,7 @@ extern "C" void rgpu_shutdown(rgpu_ctx* c) {
   c->pending_or.clear();  // (nobody will read those batches any more)
   (void)hipStreamSynchronize(c->stream);
   drain_events(c);
+  arena_drop(c, false);
   for (auto e : c->free_events) (void)hipEventDestroy(e);
   c->sim_tables.release(); for (auto& cs : c->ceil_slots) { cs.d.release(); if (cs.done) (void)hipEventDestroy(cs.done); } c->d_runs.release(); c->pos_counts.release(); c->pos_tiles.release(); c->phrase_docs.release(); c->phrase_keys.release(); c->phrase_redo.release(); c->phrase_count.release(); c->host_api_hits.release(); c->host_api_totals.release(); c->host_api_rows.release();
   for (auto& sc : c->scr) sc.release();
@@ -1222,6 +1292,7 @@ extern "C" int32_t rgpu_synchronize(rgpu_ctx* c) {
   const int32_t rc = settle_pending(c);  // (rgpu_config.or_deferred: flags of OR batches nobody has looked at yet; waits for those batches)
   if (rc != RGPU_OK) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->arena.retired() != 0) HIP_TRY(arena_wait_slots(c, false));  // (a retired descriptor generation does not outlive a synchronize)
   return RGPU_OK;
 }
 
@@ -1426,6 +1497,7 @@ extern "C" void rgpu_segment_free(rgpu_segment* s) {
   (void)hipSetDevice(s->ctx->device);
   { std::lock_guard<std::mutex> g(s->ctx->mu); (void)settle_pending(s->ctx); }  // (closures of deferred OR batches name the segment)
   (void)hipStreamSynchronize(s->ctx->stream);
+  { std::lock_guard<std::mutex> g(s->ctx->mu); arena_drop(s->ctx, true); }  // (its term descriptors name this segment's store)
   if (s->d_doc) (void)hipFree(s->d_doc);
   if (s->d_norms) (void)hipFree(s->d_norms);
   if (s->d_rank_to_norm) (void)hipFree(s->d_rank_to_norm);
@@ -1472,6 +1544,7 @@ extern "C" int32_t rgpu_segment_release_prepared_terms(rgpu_segment* seg) {
   HIP_TRY(hipDeviceSynchronize());  // batches in flight on any stream still read the directories
   for (auto& sc : c->scr) sc.busy = false;
   for (auto& cs : c->ceil_slots) cs.busy = false;
+  arena_all_waited(c);
   seg->prepared.clear();
   seg->dir_used = seg->bstore_used = seg->pnorm_used = seg->sketch_used = 0;  // the arrays keep their capacity and are refilled from the start
   for (void* b : seg->bitmap_allocs) (void)hipFree(b);
@@ -4823,6 +4896,163 @@ struct HostLaps {
     *this = HostLaps{};
   }
 };
+// The fused single-term step with the term descriptors RESIDENT on the device (the default; RGPU_TERM_PLAN=staged: the staged plan
+// below). What a step sends is 8 bytes per query — TermLaunch{record, row} in launch order, which k_search_term_query reads straight
+// from the pinned stage — and nothing is copied: no stage kernel, no DevQuery / DevTerm / order / qmap arrays. The descriptors live in
+// the context's arena (host/term_arena.hpp has the ownership rules), written once each:
+//   * a memo miss appends the record to the current generation and to this call's stage; the call then runs k_stage_term_plan — the
+//     stage copy, with the arena as its destination — on ITS stream ahead of its search kernel, and records an event behind it;
+//   * a call on another stream that names records of an upload not known complete makes its stream wait for that event
+//     (hipStreamWaitEvent) before its search kernel. Uploads become known complete when a slot marked behind them on their stream
+//     is waited for, which scratch_take does anyway: a steady state makes no event call for the arena;
+//   * nothing in a generation is ever overwritten, and a generation's buffer is handed back only when no busy scratch slot carries
+//     its number — so a launch in flight on either stream reads what its plan named, whatever the memo does meanwhile.
+// *staged: the call is not for this path after all (more distinct terms than the arena holds): the caller stages the plan.
+template <class Make>
+static int32_t term_batch_resident(rgpu_segment* seg, rucene::BatchPlanner* P, int32_t nq, const int64_t* ids, int32_t k, HitOut* hits_dev,
+                                   int64_t* totals_dev, hipStream_t stream, const rucene::BatchPlanner::MemoKey& memo_key, Make& make_term,
+                                   HostLaps* laps, bool* taken, bool* staged) {
+  rgpu_ctx* c = seg->ctx;
+  rucene::TermArena& A = c->arena;
+  *staged = false;
+  if (A.begin(rucene::TermArena::Key{{memo_key.w[0], memo_key.w[1], memo_key.w[2], memo_key.w[3]}})) HIP_TRY(arena_new_buffer(c));
+  Stager st(c);
+  const size_t o_l = st.add((size_t)nq * sizeof(TermLaunch));
+  const size_t o_up = st.add((size_t)nq * sizeof(DevTerm));  // records this call places (at most one per query)
+  HIP_TRY(c->S->h_stage.reserve(st.used));
+  HIP_TRY(c->S->d_stage.reserve((size_t)nq * 16, 0, stream));  // the launch's counters: the kernel stores every one of them
+  if (laps) laps->lap(0);
+  TermLaunch* hl = reinterpret_cast<TermLaunch*>(c->S->h_stage.p + o_l);
+  DevTerm* hup = reinterpret_cast<DevTerm*>(c->S->h_stage.p + o_up);
+  static thread_local std::vector<int32_t> recs;
+  static thread_local std::vector<uint8_t> buckets;
+  recs.resize((size_t)nq);
+  buckets.resize((size_t)nq);
+  int64_t postings = 0, total_blocks = 0, loose = 0;
+  int32_t start[34];
+  int32_t n_up = 0;
+  int64_t first_up = -1;
+  uint32_t lo = 0xffffffffu, hi = 0u;
+  // records placed by a pass whose upload is never enqueued (a term the fast pass does not take, a failed call) must not be named by
+  // a later call: the generation ends with them
+  struct Unplace {
+    rucene::TermArena& A;
+    const int32_t& n_up;
+    bool armed = true;
+    ~Unplace() { if (armed && n_up > 0) A.turn_over(); }
+  } unplace{A, n_up};
+  for (int attempt = 0;; ++attempt) {
+    postings = total_blocks = loose = 0;
+    std::memset(start, 0, sizeof start);
+    n_up = 0;
+    first_up = -1;
+    lo = 0xffffffffu;
+    hi = 0u;
+    bool full = false;
+    // the memo pass counts the launch order's buckets (0: the longest lists; floor(log2(nblocks))) on the way
+    const bool ok = P->for_each_flat_memo_placed<DevTerm>(ids, nq, memo_key, A.generation(), make_term, [&](const DevTerm* t) -> int64_t {
+      const int64_t at = A.append();
+      if (at < 0) { full = true; return -1; }
+      if (first_up < 0) first_up = at;  // (appends of one pass are consecutive: the context's lock is held)
+      hup[n_up++] = *t;
+      return at;
+    }, [&](int64_t q, const DevTerm* t, int32_t rec) {
+      int b = 32;
+      if (t) {
+        postings += t->df;
+        total_blocks += t->nblocks;
+        loose += t->df == 1 ? 1 : t->tail_n;
+        if (t->nblocks > 0) b = __builtin_clz((uint32_t)t->nblocks);
+        lo = std::min(lo, (uint32_t)rec);
+        hi = std::max(hi, (uint32_t)rec);
+      }
+      recs[(size_t)q] = rec;
+      buckets[(size_t)q] = (uint8_t)b;
+      ++start[b + 1];
+    });
+    if (ok) break;
+    if (!full) return RGPU_OK;  // (the full path takes the call; the slot was taken and not marked: it is simply free again)
+    // the generation is full: a fresh one, and the pass again (every entry misses). A batch that does not fit an empty arena is staged.
+    n_up = 0;
+    A.turn_over();
+    if (attempt == 1) { *staged = true; return RGPU_OK; }
+    HIP_TRY(arena_new_buffer(c));
+  }
+  if (laps) laps->lap(1);
+  for (int b = 0; b < 33; ++b) start[b + 1] += start[b];
+  for (int q = 0; q < nq; ++q) hl[start[buckets[(size_t)q]]++] = TermLaunch{recs[(size_t)q], q};
+  if (laps) { laps->lap(2); laps->lap(3); }
+  const DevTerm* d_arena = static_cast<const DevTerm*>(A.buffer());
+  if (n_up > 0) {
+    {
+      // k_stage_term_plan's second job: the new records, from the stage to their place in the arena (no zero range, no item descriptors)
+      TimedLaunch tl(c, stream, "k_stage_term_plan", 0);
+      const size_t n16 = (size_t)n_up * (sizeof(DevTerm) / 16);
+      const TermPlanLayout L{0u, 0u, 0u, 0u, 0u, 0u, 0};
+      const unsigned grid = (unsigned)std::min<size_t>(1024, (n16 + 255) / 256);
+      RGPU_LAUNCH(k_stage_term_plan, dim3(grid), dim3(256), 0, stream, c->S->h_stage.p + o_up,
+                  reinterpret_cast<uint8_t*>(const_cast<DevTerm*>(d_arena + first_up)), n16, L);
+    }
+    HIP_TRY(launch_status());
+    void* ev = A.take_spare_event();
+    if (!ev) {
+      hipEvent_t e = nullptr;
+      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      ev = e;
+    }
+    const hipError_t er = hipEventRecord((hipEvent_t)ev, stream);
+    if (er != hipSuccess) { A.give_spare_event(ev); HIP_TRY(er); }
+    A.note_upload((uint32_t)first_up, (uint32_t)(first_up + n_up), (uint64_t)(uintptr_t)stream, ev);
+  }
+  unplace.armed = false;  // (what this pass placed is on its way)
+  if (A.pending_uploads() != 0 && lo <= hi) {
+    hipError_t ew = hipSuccess;
+    A.for_each_wait((uint64_t)(uintptr_t)stream, lo, hi, [&](void* ev) {
+      const hipError_t e = hipStreamWaitEvent(stream, (hipEvent_t)ev, 0);
+      if (ew == hipSuccess) ew = e;
+    });
+    HIP_TRY(ew);
+  }
+  if (laps) laps->lap(4);
+  unsigned long long* d_work = reinterpret_cast<unsigned long long*>(c->S->d_stage.p);
+  c->last_counted = c->S;
+  c->last_counted_words = d_work;
+  c->last_counted_op = RGPU_OP_TERM;
+  c->last_counted_queries = nq;
+  c->last_counted_postings = postings;
+  c->last_counted_dir_blocks = total_blocks;
+  c->last_counted_loose = loose;
+  const bool wide = k > 64;
+  const bool legacy = seg->version < 1;
+  {
+    TimedLaunch tl(c, stream, "k_search_term", postings);  // (under the TERM search's name, like the staged plan's launch below)
+    const SegView sv = seg_view(seg);
+    auto go = [&](auto kern, int waves) -> hipError_t {
+      RGPU_LAUNCH(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, sv, (const DevQuery*)nullptr, d_arena, (const int32_t*)nullptr, nq, (int)k, d_work,
+                  (const int32_t*)nullptr, hits_dev, totals_dev, seg->doc_base, (const TermLaunch*)hl);
+      return hipSuccess;
+    };
+    auto pick = [&](auto legacy_c, auto wide_c) -> hipError_t {
+      constexpr bool LG = decltype(legacy_c)::value, WD = decltype(wide_c)::value;
+      if (c->term_query_waves == 2) return go(k_search_term_query<LG, WD, 2>, 2);
+      if (c->term_query_waves == 8) return go(k_search_term_query<LG, WD, 8>, 8);
+      return go(k_search_term_query<LG, WD, 4>, 4);
+    };
+    hipError_t e;
+    if (legacy) e = wide ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{});
+    else e = wide ? pick(std::false_type{}, std::true_type{}) : pick(std::false_type{}, std::false_type{});
+    HIP_TRY(e);
+    c->stats[(size_t)stat_slot(c, "term_query_launches")].launches += 1;
+  }
+  if (laps) laps->lap(5);
+  HIP_TRY(launch_status());
+  HIP_TRY(scratch_mark(c, stream));
+  A.slot_marked((int)(c->S - c->scr), (uint64_t)(uintptr_t)stream);
+  c->stats[(size_t)stat_slot(c, "fused_term_batches")].launches += 1;
+  if (laps) { laps->lap(6); laps->done(); }
+  *taken = true;
+  return RGPU_OK;
+}
 static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32_t nq, const int64_t* ids, int32_t k, HitOut* hits_dev,
                                int64_t* totals_dev, hipStream_t stream, bool* taken) {
   rgpu_ctx* c = seg->ctx;
@@ -4837,37 +5067,13 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
   const uint32_t flags = c->sim_monotone[(size_t)sim_table] ? TERM_FLAG_MONOTONE : 0u;
   c->pass = rgpu_ctx::Pass{};
   SCRATCH_TAKE(c);
-  Stager st(c);
-  const size_t o_q = st.add((size_t)nq * sizeof(DevQuery));
-  const size_t o_t = st.add((size_t)nq * sizeof(DevTerm));
-  const size_t o_p = st.add((size_t)(nq + 1) * 8);
-  const size_t o_m = st.add((size_t)nq * 4);
-  const size_t o_sh = st.add((size_t)nq);            // log2 of every query's own item size (0: the launch's)
-  const size_t o_ord = st.add((size_t)nq * 4);       // k_search_term_query: the query of every workgroup, heaviest first
-  const size_t o_tau = st.add((size_t)nq * 8);       // per-query shared thresholds ...
-  const size_t o_w = st.add((size_t)nq * 16);        // ... and the launch's counters: zeroed by the copy that brings the plan
-  const size_t o_done = st.add((size_t)nq * 4);      // ... and the per-query counts of finished items (TermMerge::done)
-  const size_t o_zero_end = st.add(0);               // (the three above are one range: [o_tau, o_zero_end))
-  // ... and the item descriptors, LAST: their number is known only once the terms have been read (at most 262144 + nq, the item
-  // loop's cap), the stage has room for the worst case and the copy takes what is used
-  const size_t o_id = st.add(((size_t)262144 + (size_t)nq) * sizeof(int4));
-  HIP_TRY(c->S->h_stage.reserve(st.used));
-  HIP_TRY(c->S->d_stage.reserve(st.used, 0, stream));
-  if (timed) laps.lap(0);
-  DevQuery* hq = reinterpret_cast<DevQuery*>(c->S->h_stage.p + o_q);
-  DevTerm* ht = reinterpret_cast<DevTerm*>(c->S->h_stage.p + o_t);
-  int64_t* hp = reinterpret_cast<int64_t*>(c->S->h_stage.p + o_p);
-  int32_t* hm = reinterpret_cast<int32_t*>(c->S->h_stage.p + o_m);
-  int32_t nt = 0;
-  int64_t postings = 0, total_blocks = 0, loose = 0;
-  bool bail = false;
   const int32_t max_doc = seg->max_doc;
   const bool has_freqs = seg->has_freqs;
   // term id -> finished descriptor through the planner's memo (host/batch_planner.hpp for_each_flat_memo): a descriptor is a function
   // of the planner's tables (immutable), the segment and what its prepared store holds (uid, epoch), and the flags below
   const rucene::BatchPlanner::MemoKey memo_key{{seg->uid, seg->prepared.epoch, (uint64_t)(uint32_t)sim_table | ((uint64_t)flags << 32),
                                                 (uint64_t)want_sketch | ((uint64_t)need_norms << 1) | ((uint64_t)has_freqs << 2) | ((uint64_t)(uint32_t)max_doc << 8)}};
-  bail = !P->for_each_flat_memo<DevTerm>(ids, nq, memo_key, [&](const rgpu_term_state& s0, float idf, DevTerm* out) -> int32_t {
+  auto make_term = [&](const rgpu_term_state& s0, float idf, DevTerm* out) -> int32_t {
     DevTerm t;
     t.start_fp = (uint64_t)std::max<int64_t>(0, s0.doc_start_fp);
     t.pn_base = 0;
@@ -4896,7 +5102,39 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
     }
     *out = t;
     return 1;
-  }, [&](int64_t q, const DevTerm* t) {
+  };
+  // k_search_term_query: one workgroup per query, no work items
+  const bool per_query = c->term_query_kernel && c->blocks_per_item_auto && c->term_fold;
+  if (per_query && c->term_plan_resident && c->stage_by_kernel && !c->upload_aside) {
+    bool staged_after_all = false;
+    const int32_t rc = term_batch_resident(seg, P, nq, ids, k, hits_dev, totals_dev, stream, memo_key, make_term, timed ? &laps : nullptr, taken, &staged_after_all);
+    if (!staged_after_all) return rc;
+  }
+  Stager st(c);
+  const size_t o_q = st.add((size_t)nq * sizeof(DevQuery));
+  const size_t o_t = st.add((size_t)nq * sizeof(DevTerm));
+  const size_t o_p = st.add((size_t)(nq + 1) * 8);
+  const size_t o_m = st.add((size_t)nq * 4);
+  const size_t o_sh = st.add((size_t)nq);            // log2 of every query's own item size (0: the launch's)
+  const size_t o_ord = st.add((size_t)nq * 4);       // k_search_term_query: the query of every workgroup, heaviest first
+  const size_t o_tau = st.add((size_t)nq * 8);       // per-query shared thresholds ...
+  const size_t o_w = st.add((size_t)nq * 16);        // ... and the launch's counters: zeroed by the copy that brings the plan
+  const size_t o_done = st.add((size_t)nq * 4);      // ... and the per-query counts of finished items (TermMerge::done)
+  const size_t o_zero_end = st.add(0);               // (the three above are one range: [o_tau, o_zero_end))
+  // ... and the item descriptors, LAST: their number is known only once the terms have been read (at most 262144 + nq, the item
+  // loop's cap), the stage has room for the worst case and the copy takes what is used
+  const size_t o_id = st.add(((size_t)262144 + (size_t)nq) * sizeof(int4));
+  HIP_TRY(c->S->h_stage.reserve(st.used));
+  HIP_TRY(c->S->d_stage.reserve(st.used, 0, stream));
+  if (timed) laps.lap(0);
+  DevQuery* hq = reinterpret_cast<DevQuery*>(c->S->h_stage.p + o_q);
+  DevTerm* ht = reinterpret_cast<DevTerm*>(c->S->h_stage.p + o_t);
+  int64_t* hp = reinterpret_cast<int64_t*>(c->S->h_stage.p + o_p);
+  int32_t* hm = reinterpret_cast<int32_t*>(c->S->h_stage.p + o_m);
+  int32_t nt = 0;
+  int64_t postings = 0, total_blocks = 0, loose = 0;
+  bool bail = false;
+  bail = !P->for_each_flat_memo<DevTerm>(ids, nq, memo_key, make_term, [&](int64_t q, const DevTerm* t) {
     hm[q] = (int32_t)q;
     if (!t) { hq[q] = DevQuery{RGPU_OP_TERM, 0, nt, 0}; return; }  // TermWeight::create_scorer -> None for this leaf
     hq[q] = DevQuery{RGPU_OP_TERM, 1, nt, 0};
@@ -4907,9 +5145,8 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
   });
   if (bail) return RGPU_OK;  // (the slot was taken and not marked: it is simply free again)
   if (timed) laps.lap(1);
-  // k_search_term_query: one workgroup per query, no work items — the plan is the queries, their terms and a launch order, longest
-  // lists first (a counting sort on floor(log2(nblocks)))
-  const bool per_query = c->term_query_kernel && c->blocks_per_item_auto && c->term_fold;
+  // k_search_term_query — the plan is the queries, their terms and a launch order, longest lists first (a counting sort on
+  // floor(log2(nblocks)))
   if (per_query) {
     int32_t* ho = reinterpret_cast<int32_t*>(c->S->h_stage.p + o_ord);
     int32_t start[34] = {0};
@@ -5010,7 +5247,8 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
     const SegView sv = seg_view(seg);
     const int32_t* dord = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_ord);
     auto go = [&](auto kern, int waves) -> hipError_t {
-      RGPU_LAUNCH(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, sv, dq, dt, dord, nq, (int)k, d_work, dm, hits_dev, totals_dev, seg->doc_base);
+      RGPU_LAUNCH(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, sv, dq, dt, dord, nq, (int)k, d_work, dm, hits_dev, totals_dev, seg->doc_base,
+                  (const TermLaunch*)nullptr);
       return hipSuccess;
     };
     auto pick = [&](auto legacy_c, auto wide_c) -> hipError_t {
