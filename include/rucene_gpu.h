@@ -33,7 +33,7 @@ extern "C" {
                                    wavefront. Disjunctions of 10..16 SHOULD clauses take the fixed-point kernels, longer ones the
                                    clause-order kernel */
 #define RGPU_MAX_PHRASE_TERMS 16 /* terms of one phrase */
-#define RGPU_MAX_K 1024   /* k above 128 costs ceil(k / 128) passes of the search (phrases: of the collector only); rescoring: k <= 128 */
+#define RGPU_MAX_K 1024   /* k above 128 costs ceil(k / 128) passes of the search (phrases: of the collector only); rgpu_rescore_batch: k <= 128 */
 
 /* error.rs:24-91 ErrorKind */
 typedef enum rgpu_status {
@@ -681,6 +681,22 @@ typedef struct rgpu_rescore_request {  /* RescoreRequest (rescorer.rs:67-93), on
 int32_t rgpu_rescore_batch(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
                            int32_t n_terms_total, const rgpu_rescore_request* requests, int32_t k, rgpu_hit* hits_inout,
                            int32_t finish);
+/* The same rescoring with a PhraseQuery as the second query (QueryRescorer::iterative_rescore takes any Query; with a phrase it
+ * advances an ExactPhraseScorer / SloppyPhraseScorer from hit to hit, rescorer.rs:229-298). Calling protocol, rows, window clipping
+ * (min(window_size, k, 128)) and `finish` as rgpu_rescore_batch; k up to RGPU_MAX_K. queries / terms as rgpu_search_phrase_batch
+ * (`next_limit` is ignored: no BulkScorer drives the scorer; live docs are not consulted, as the reference rescorer does not).
+ * A hit matches when every term of the phrase holds its doc and the exact phrase frequency is > 0 (slop 0) or the sloppy frequency
+ * is > f32::EPSILON (slop > 0); its second score is BM25(phrase or sloppy frequency, norm), the bits rgpu_search_phrase_batch
+ * returns for that doc — a match that scores 0 (boost 0) is still a match. A leaf where some term has doc_freq 0 matches nothing.
+ * Refused, hits_inout untouched: the arguments rgpu_search_phrase_batch and rgpu_rescore_batch refuse (RGPU_ERR_ILLEGAL_ARGUMENT);
+ * no positions attached (RGPU_ERR_ILLEGAL_STATE); a hit doc that holds a term more often than the position lists do, as in phrase
+ * search (RGPU_ERR_UNSUPPORTED); a SLOPPY phrase that names a term twice (RGPU_ERR_UNSUPPORTED): SloppyPhraseScorer derives its
+ * repetition groups once per leaf from the first doc it evaluates (init_first_time, phrase_scorer.rs:807-820), which in a rescoring
+ * is the first conjunction match at or behind the leaf's first window hit and need not be a hit at all — reproducing it needs a
+ * conjunction advance of its own, which is out of scope. Exact phrases that repeat a term ("a b a") carry no such state: served. */
+int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
+                                  const rgpu_phrase_term* terms, int32_t n_terms_total,
+                                  const rgpu_rescore_request* requests, int32_t k, rgpu_hit* hits_inout, int32_t finish);
 
 /* ---- measurement ------------------------------------------------------------------------------------------ */
 typedef struct rgpu_kernel_stat {

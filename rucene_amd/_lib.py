@@ -57,7 +57,7 @@ STATUS_NAMES = {0: "OK", -1: "IllegalState", -2: "IllegalArgument", -3: "Unexpec
 # every symbol include/rucene_gpu.h declares (tests/test_abi.py checks the header and this list agree)
 EXPORTS = [
     "rgpu_init", "rgpu_shutdown", "rgpu_last_error", "rgpu_abi_version", "rgpu_device_name", "rgpu_segment_upload",
-    "rgpu_segment_upload_field", "rgpu_segment_release_prepared_terms", "rgpu_segment_get_footprint", "rgpu_segment_attach_positions", "rgpu_segment_attach_payloads", "rgpu_decode_positions", "rgpu_decode_positions_device", "rgpu_search_phrase_batch", "rgpu_rescore_batch",
+    "rgpu_segment_upload_field", "rgpu_segment_release_prepared_terms", "rgpu_segment_get_footprint", "rgpu_segment_attach_positions", "rgpu_segment_attach_payloads", "rgpu_decode_positions", "rgpu_decode_positions_device", "rgpu_search_phrase_batch", "rgpu_rescore_batch", "rgpu_rescore_phrase_batch",
     "rgpu_segment_free", "rgpu_segment_version", "rgpu_segment_prepare_terms", "rgpu_decode_terms",
     "rgpu_decode_terms_device", "rgpu_advance_batch", "rgpu_sim_table_upload", "rgpu_search_batch",
     "rgpu_search_batch_device", "rgpu_merge_topk_device", "rgpu_bm25_compute_weight", "rgpu_bm25_encode_norm", "rgpu_bm25_term_weights",
@@ -153,6 +153,7 @@ def lib():
         "rgpu_decode_positions_device": (i32, [vp, vp, vp, C.c_int64, vp, vp]),
         "rgpu_search_phrase_batch": (i32, [vp, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_rescore_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32]),
+        "rgpu_rescore_phrase_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32]),
         "rgpu_decode_terms": (i32, [vp, vp, i64, vp, vp]),
         "rgpu_decode_terms_device": (i32, [vp, vp, i64, vp, vp, vp]),
         "rgpu_advance_batch": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -694,6 +695,16 @@ class Segment:
         r = np.ascontiguousarray(requests, dtype=RESCORE_REQUEST_DTYPE)
         h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).copy()
         _check(lib().rgpu_rescore_batch(self._h, q.ctypes.data, q.size, t.ctypes.data, t.size, r.ctypes.data, h.shape[1], h.ctypes.data, int(finish)))
+        return h
+
+    def rescore_phrase_batch(self, queries, terms, requests, hits, finish=True):
+        """QueryRescorer with PhraseQuery rows (packed as for search_phrase_batch) over first-pass rows `hits` [n][k] (modified copy
+        returned): rgpu_rescore_phrase_batch. A refusal raises and leaves `hits` as it was."""
+        q = np.ascontiguousarray(queries, dtype=PHRASE_QUERY_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=PHRASE_TERM_DTYPE)
+        r = np.ascontiguousarray(requests, dtype=RESCORE_REQUEST_DTYPE)
+        h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).copy()
+        _check(lib().rgpu_rescore_phrase_batch(self._h, q.ctypes.data, q.size, t.ctypes.data, t.size, r.ctypes.data, h.shape[1], h.ctypes.data, int(finish)))
         return h
 
     def release_prepared_terms(self):

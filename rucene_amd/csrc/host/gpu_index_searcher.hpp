@@ -358,7 +358,7 @@ struct PhraseQuery : Query {
 
 // RescoreRequest (search/scorer/rescorer.rs:67-116): how a second query's score is folded into the first pass's
 struct RescoreRequest {
-  const Query* query = nullptr;  // TermQuery, or an all-MUST / all-SHOULD BooleanQuery
+  const Query* query = nullptr;  // TermQuery, an all-MUST / all-SHOULD BooleanQuery, or a PhraseQuery (sloppy: no repeated term)
   float query_weight = 1.0f, rescore_weight = 1.0f;
   rgpu_rescore_mode mode = RGPU_RESCORE_TOTAL;
   int32_t window_size = 0;  // 0: the whole row
@@ -641,19 +641,7 @@ class GpuIndexSearcher {
       if (!leaf.pos_bytes) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "phrase search needs a positions field (LeafReader::pos_bytes)");
       std::vector<rgpu_phrase_query> qs;
       std::vector<rgpu_phrase_term> ts;
-      for (const PhraseQuery* q : queries) {
-        std::vector<TermStatistics> stats;
-        for (const TermQuery& t : q->terms) stats.push_back(term_statistics(t));
-        const BM25SimWeight w = sim_.compute_weight(stats_, stats.data(), static_cast<int32_t>(stats.size()), q->boost);
-        if (sim_table_ < 0) check(sim_table_ = rgpu_sim_table_upload(ctx_, w.cache.data(), w.k1));
-        qs.push_back(rgpu_phrase_query{static_cast<int32_t>(q->terms.size()), static_cast<int32_t>(ts.size()), w.weight, sim_table_, q->slop, next_limit});
-        for (size_t i = 0; i < q->terms.size(); ++i) {
-          rgpu_phrase_term pt{};
-          if (!leaf.positions_state(q->terms[i], &pt.state, &pt.positions)) { pt.state = rgpu_term_state{}; pt.state.skip_offset = -1; pt.state.singleton_doc_id = -1; }
-          pt.position = q->positions[i];
-          ts.push_back(pt);
-        }
-      }
+      pack_phrases(queries, leaf, &qs, &ts);
       leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
       leaf_totals[li].assign(static_cast<size_t>(nq), 0);
       check(rgpu_search_phrase_batch(leaf.segment, qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
@@ -663,7 +651,7 @@ class GpuIndexSearcher {
   }
 
   // QueryRescorer::rescore (search/scorer/rescorer.rs:118-226) for a batch: row i of `first_pass` is re-ranked by
-  // requests[i]. One device call per leaf; the last one sorts the windows and re-weights the tails.
+  // requests[i]. One device call per kind of query and leaf; the last leaf's sorts the windows and re-weights the tails.
   std::vector<TopDocs> rescore(const std::vector<TopDocs>& first_pass, const std::vector<RescoreRequest>& requests, size_t k) {
     const int32_t nq = static_cast<int32_t>(first_pass.size());
     if (requests.size() != first_pass.size()) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "one rescore request per row");
@@ -676,12 +664,60 @@ class GpuIndexSearcher {
       reqs.push_back(rgpu_rescore_request{r.query_weight, r.rescore_weight, static_cast<int32_t>(r.mode),
                                           r.window_size > 0 ? r.window_size : static_cast<int32_t>(k)});
     }
-    for (size_t li = 0; li < leaves_.size(); ++li) {
-      std::vector<rgpu_query> qs;
-      std::vector<rgpu_query_term> ts;
-      for (const RescoreRequest& r : requests) pack(*r.query, leaves_[li], &qs, &ts);
-      check(rgpu_rescore_batch(leaves_[li].segment, qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), reqs.data(),
-                               static_cast<int32_t>(k), rows.data(), li + 1 == leaves_.size() ? 1 : 0));
+    // rows by kind: PhraseQuery rows go through rgpu_rescore_phrase_batch, the others through rgpu_rescore_batch (a row's result
+    // does not depend on the other rows, so the two sub-batches are rescored apart and scattered back)
+    std::vector<size_t> plain, phrase;
+    std::vector<const PhraseQuery*> phrases;
+    for (size_t q = 0; q < requests.size(); ++q) {
+      if (!requests[q].query) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "a rescore request needs a query");
+      if (const PhraseQuery* pq = dynamic_cast<const PhraseQuery*>(requests[q].query)) {
+        // refused before any leaf is touched (a leaf that lacks the term would serve the row, the next one not)
+        for (size_t i = 1; pq->slop > 0 && i < pq->terms.size(); ++i)
+          for (size_t j = 0; j < i; ++j)
+            if (pq->terms[i].term == pq->terms[j].term && pq->terms[i].text == pq->terms[j].text)
+              throw Error(RGPU_ERR_UNSUPPORTED, "phrase rescoring: a sloppy phrase that names a term twice is not served");
+        phrase.push_back(q);
+        phrases.push_back(pq);
+      }
+      else plain.push_back(q);
+    }
+    auto gather = [&](const std::vector<size_t>& which, std::vector<rgpu_hit>* sub, std::vector<rgpu_rescore_request>* sub_reqs) {
+      for (size_t q : which) {
+        sub->insert(sub->end(), rows.begin() + static_cast<std::ptrdiff_t>(q * k), rows.begin() + static_cast<std::ptrdiff_t>((q + 1) * k));
+        sub_reqs->push_back(reqs[q]);
+      }
+    };
+    auto scatter = [&](const std::vector<size_t>& which, const std::vector<rgpu_hit>& sub) {
+      for (size_t i = 0; i < which.size(); ++i)
+        std::copy(sub.begin() + static_cast<std::ptrdiff_t>(i * k), sub.begin() + static_cast<std::ptrdiff_t>((i + 1) * k),
+                  rows.begin() + static_cast<std::ptrdiff_t>(which[i] * k));
+    };
+    if (!plain.empty()) {
+      std::vector<rgpu_hit> sub;
+      std::vector<rgpu_rescore_request> sub_reqs;
+      gather(plain, &sub, &sub_reqs);
+      for (size_t li = 0; li < leaves_.size(); ++li) {
+        std::vector<rgpu_query> qs;
+        std::vector<rgpu_query_term> ts;
+        for (size_t q : plain) pack(*requests[q].query, leaves_[li], &qs, &ts);
+        check(rgpu_rescore_batch(leaves_[li].segment, qs.data(), static_cast<int32_t>(plain.size()), ts.data(), static_cast<int32_t>(ts.size()),
+                                 sub_reqs.data(), static_cast<int32_t>(k), sub.data(), li + 1 == leaves_.size() ? 1 : 0));
+      }
+      scatter(plain, sub);
+    }
+    if (!phrase.empty()) {
+      std::vector<rgpu_hit> sub;
+      std::vector<rgpu_rescore_request> sub_reqs;
+      gather(phrase, &sub, &sub_reqs);
+      for (size_t li = 0; li < leaves_.size(); ++li) {
+        if (!leaves_[li].pos_bytes) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "phrase rescoring needs a positions field (LeafReader::pos_bytes)");
+        std::vector<rgpu_phrase_query> qs;
+        std::vector<rgpu_phrase_term> ts;
+        pack_phrases(phrases, leaves_[li], &qs, &ts);
+        check(rgpu_rescore_phrase_batch(leaves_[li].segment, qs.data(), static_cast<int32_t>(phrase.size()), ts.data(), static_cast<int32_t>(ts.size()),
+                                        sub_reqs.data(), static_cast<int32_t>(k), sub.data(), li + 1 == leaves_.size() ? 1 : 0));
+      }
+      scatter(phrase, sub);
     }
     std::vector<TopDocs> out;
     for (int32_t q = 0; q < nq; ++q) {
@@ -696,6 +732,26 @@ class GpuIndexSearcher {
   }
 
  private:
+  // PhraseQuery objects -> the rgpu_phrase_query[] / rgpu_phrase_term[] of one leaf (rgpu_search_phrase_batch, rgpu_rescore_phrase_batch)
+  void pack_phrases(const std::vector<const PhraseQuery*>& queries, const LeafReader& leaf, std::vector<rgpu_phrase_query>* qs_out,
+                    std::vector<rgpu_phrase_term>* ts_out) {
+    std::vector<rgpu_phrase_query>& qs = *qs_out;
+    std::vector<rgpu_phrase_term>& ts = *ts_out;
+    for (const PhraseQuery* q : queries) {
+      std::vector<TermStatistics> stats;
+      for (const TermQuery& t : q->terms) stats.push_back(term_statistics(t));
+      const BM25SimWeight w = sim_.compute_weight(stats_, stats.data(), static_cast<int32_t>(stats.size()), q->boost);
+      if (sim_table_ < 0) check(sim_table_ = rgpu_sim_table_upload(ctx_, w.cache.data(), w.k1));
+      qs.push_back(rgpu_phrase_query{static_cast<int32_t>(q->terms.size()), static_cast<int32_t>(ts.size()), w.weight, sim_table_, q->slop, next_limit});
+      for (size_t i = 0; i < q->terms.size(); ++i) {
+        rgpu_phrase_term pt{};
+        if (!leaf.positions_state(q->terms[i], &pt.state, &pt.positions)) { pt.state = rgpu_term_state{}; pt.state.skip_offset = -1; pt.state.singleton_doc_id = -1; }
+        pt.position = q->positions[i];
+        ts.push_back(pt);
+      }
+    }
+  }
+
   // TopDocsCollector::finish_parallel (top_docs.rs:157-172) over a handful of leaves: canonical order
   std::vector<TopDocs> merge_leaves(const std::vector<std::vector<rgpu_hit>>& leaf_hits, const std::vector<std::vector<int64_t>>& leaf_totals,
                                     int32_t nq, size_t k) const {

@@ -1502,4 +1502,87 @@ __global__ __launch_bounds__(WG_THREADS) void k_rescore_sort(const RescoreParams
   if (lane + 64 < n) row[lane + 64] = HitOut{key_doc(top.b), key_score(top.b)};
 }
 
+// ---- QueryRescorer with a PhraseQuery as its second query (rescorer.rs:229-298 drives an Exact- / SloppyPhraseScorer from hit to
+// hit: a hit matches when the scorer, advanced to its doc, lands on it) ---------------------------------------------------------
+// The window's hits become the candidate slots of the phrase match kernels above (k_phrase_match_lanes, k_phrase_match,
+// k_sloppy_match_lanes, k_sloppy_match), which write one key per slot; k_rescore_phrase_combine turns the keys back into hits.
+// Row q owns the slots [q * S, q * S + S), S = k rounded up to a multiple of 64 (a 64-candidate wavefront's slots belong to one query).
+//
+// k_rescore_phrase_candidates: one wavefront per slot. The conjunction that feeds the match kernels in a search guarantees that
+// every term holds a candidate doc; a first-pass hit guarantees nothing, so the wavefront looks the hit's doc up in every term of
+// the phrase (cost order; step 1 of phrase_doc_positions without the freq bookkeeping) and stops at the first term that lacks it.
+// The slot takes the leaf-local doc when every term holds it, else -1 — "never checked" to the match kernels, key 0. Also -1: a
+// hit of another leaf, a hit past the window, a padding hit / slot, every hit of a row whose phrase has a term absent from the
+// leaf (the host gives such a row no terms). Bounds: slot < n_queries * S; a hit is read only for i < min(window, k); every
+// directory index is inside the term's [dir_base, dir_base + nblocks] (the tail's row only when tail_n > 0).
+template <bool LEGACY>
+__global__ __launch_bounds__(WG_THREADS) void k_rescore_phrase_candidates(SegView seg, const DevQuery* __restrict__ queries,
+                                                                          const DevTerm* __restrict__ terms,
+                                                                          const RescoreParams* __restrict__ params, int n_queries, int k, int S,
+                                                                          const HitOut* __restrict__ hits, int32_t* __restrict__ emit_docs) {
+  __shared__ __attribute__((aligned(16))) uint8_t slabs[WG_WAVES][2 * SLAB_STREAM];
+  const int lane = lane_id();
+  const int wave = wave_id();
+  const int64_t slot = (int64_t)blockIdx.x * WG_WAVES + wave;
+  if (slot >= (int64_t)n_queries * S) return;
+  const int q = (int)(slot / S), i = (int)(slot - (int64_t)q * S);
+  int32_t out = -1;
+  if (i < k && i < params[q].window) {
+    const HitOut h = hits[(int64_t)q * k + i];
+    const int32_t doc = h.doc - seg.doc_base;
+    const DevQuery Q = queries[q];
+    if (h.doc >= 0 && doc >= 0 && doc < seg.max_doc && Q.n_terms > 0) {
+      uint8_t* slab = slabs[wave];
+      bool all = true;
+      for (int c = 0; c < Q.n_terms && all; ++c) {
+        const DevTerm T = terms[Q.first_term + c];
+        if (T.df == 1) {
+          all = T.singleton_doc == doc;
+          continue;
+        }
+        const int blk = find_block_wave(seg.dir_last, T.dir_base, 0, T.nblocks, doc, lane);
+        int32_t e0 = 0, e1 = 0;
+        uint32_t g0, g1;
+        bool v0 = true, v1 = true;
+        if (blk < T.nblocks) {
+          const int32_t base = blk == 0 ? 0 : seg.dir_last[T.dir_base + blk - 1];
+          const BlockPair bp = decode_block<LEGACY>(seg.bstore + T.bs_base, seg.dir_row[T.dir_base + blk], seg.dir_hdr[T.dir_base + blk], slab, lane);
+          deltas_to_docs(bp.d0, bp.d1, base, e0, e1);
+        } else if (T.tail_n > 0) {
+          tail_load(seg.bstore + T.bs_base, seg.dir_row[T.dir_base + T.nblocks], lane, e0, e1, g0, g1);
+          v0 = 2 * lane < T.tail_n; v1 = 2 * lane + 1 < T.tail_n;
+        } else {
+          v0 = v1 = false;  // the doc lies behind the term's last posting
+        }
+        all = (__ballot(v0 && e0 == doc) | __ballot(v1 && e1 == doc)) != 0ull;
+      }
+      if (all) out = doc;
+    }
+  }
+  if (lane == 0) emit_docs[slot] = out;
+}
+
+// k_rescore_phrase_combine: one lane per hit. A window hit of this leaf takes combine_score (rescorer.rs:337-352) — a non-zero key
+// is a match, whatever its score (a phrase with boost 0 scores 0 and still matches: AVG, MIN and MULTIPLY tell the two apart);
+// a hit past the window takes the query weight in the finishing call; another leaf's hit is left to that leaf's call: every hit
+// is multiplied by query_weight exactly once over the calls of a rescoring, as in k_rescore.
+__global__ __launch_bounds__(256) void k_rescore_phrase_combine(SegView seg, const RescoreParams* __restrict__ params, int n_queries, int k, int S,
+                                                                const uint64_t* __restrict__ keys, HitOut* __restrict__ hits, int finish) {
+  const int64_t at = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (at >= (int64_t)n_queries * k) return;
+  const int q = (int)(at / k), i = (int)(at - (int64_t)q * k);
+  const RescoreParams R = params[q];
+  const HitOut h = hits[at];
+  if (h.doc < 0) return;
+  const float first = h.score * R.query_weight;
+  if (i >= R.window) {
+    if (finish) hits[at].score = first;
+    return;
+  }
+  const int32_t doc = h.doc - seg.doc_base;
+  if (doc < 0 || doc >= seg.max_doc) return;
+  const uint64_t key = keys[(int64_t)q * S + i];
+  hits[at].score = key != 0ull ? rescore_combine(R.mode, first, key_score(key) * R.rescore_weight) : first;
+}
+
 }  // namespace rgpu

@@ -3672,6 +3672,150 @@ extern "C" int32_t rgpu_decode_positions(rgpu_segment* seg, const rgpu_term_stat
   return rc;
 }
 
+// ---- the match stage of a phrase search: one key per candidate slot into c->phrase_keys ------------------------------------------
+// The kernels read an array of candidate slots (emit_prefix / emit_count / emit_docs = c->phrase_count / c->phrase_docs) and do not
+// care what filled it: the conjunction of a phrase search (rgpu_search_phrase_batch) or the window of a rescoring
+// (rgpu_rescore_phrase_batch). The caller has zeroed c->d_err and reserved c->phrase_keys and c->phrase_redo (redo_cap slots).
+struct PhraseMatchStage {
+  const DevQuery* d_q;
+  const DevTerm* d_t;
+  const PosTerm* d_pt;
+  const int64_t* d_ep;
+  const int32_t* d_sl;
+  SloppyGroups* d_gr;
+  int32_t n_queries;
+  int64_t slots;     // a multiple of 64, every query's share too
+  int64_t redo_cap;
+  bool any_exact, any_sloppy;
+  bool sloppy_rpts;  // some sloppy phrase names a term twice
+  // k_sloppy_groups (a search only: a rescoring refuses sloppy phrases that repeat a term and leaves the groups at "none")
+  bool with_groups;
+  PhraseCut* d_cut0;
+  const int64_t* d_cp0;
+  const int32_t* d_nl0;
+  int64_t collect_items;
+};
+static int64_t phrase_redo_cap(int64_t slots) {
+  // (developer knob: RGPU_PHRASE_REDO_CAP=<n> shrinks the list of left-over candidates, so that a test reaches the pass that runs without it)
+  int64_t redo_cap = PHRASE_REDO_LIST_CAP;
+  if (const char* e = std::getenv("RGPU_PHRASE_REDO_CAP")) redo_cap = std::max<int64_t>(0, std::min<int64_t>(redo_cap, std::atoll(e)));
+  return std::min<int64_t>(slots, redo_cap);
+}
+static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const PhraseMatchStage& a) {
+  rgpu_ctx* c = seg->ctx;
+  const SegView sv = seg_view(seg);
+  const bool legacy = seg->version < 1;
+  // One wavefront per candidate slot, first with the small position lists / pools (seven wavefronts per SIMD). A doc that holds
+  // a term more often than those hold positions (rare: Rucene clamps freqs to 10) leaves PHRASE_REDO in its slot: one look at
+  // the flag, then the wide instantiations over the marked candidates only.
+  // (one wavefront per slot: at most PHRASE_LAUNCH_SLOTS slots per launch — a grid of more than 2^32 work-items is cut short)
+  auto per_slot = [&](int64_t n, auto launch) {
+    for (int64_t s0 = 0; s0 < n; s0 += PHRASE_LAUNCH_SLOTS) {
+      const int64_t s1 = std::min(n, s0 + PHRASE_LAUNCH_SLOTS);
+      launch(dim3(wg_count((s1 - s0 + WG_WAVES - 1) / WG_WAVES)), s0, s1);
+    }
+  };
+  // (list: null = every slot of the launch; else the listed slots — the ones a 64-candidate kernel handed on)
+  auto exact = [&](auto kern, const int64_t* list, int64_t n) {
+    per_slot(n, [&](dim3 grid, int64_t s0, int64_t s1) {
+      RGPU_LAUNCH(kern, grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl, (int)a.n_queries, s1,
+                  (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err, c->d_err + 3, list, s0);
+    });
+  };
+  auto sloppy = [&](auto kern, const int64_t* list, int64_t n) {
+    per_slot(n, [&](dim3 grid, int64_t s0, int64_t s1) {
+      RGPU_LAUNCH(kern, grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl, a.d_gr, (int)a.n_queries, s1,
+                  (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err, c->d_err + 3, list, s0);
+    });
+  };
+  auto sloppy_groups = [&]() {  // the repetition groups of each query's first candidate doc (phrases with a repeated term)
+    TimedLaunch tl(c, stream, "k_sloppy_groups", 0);
+    if (a.collect_items > 0)  // every sloppy query's smallest live candidate, chunk by chunk
+      RGPU_LAUNCH(k_phrase_cutoff_items<2>, dim3(wg_count((a.collect_items + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, a.d_cp0, a.d_ep,
+                  c->phrase_count.p, c->phrase_keys.p, (const int32_t*)c->phrase_docs.p, a.d_sl, a.d_nl0, (int)a.n_queries, a.collect_items, a.d_cut0);
+    const unsigned ggrid = wg_count((a.n_queries + WG_WAVES - 1) / WG_WAVES);
+    auto go = [&](auto kern) {
+      RGPU_LAUNCH(kern, dim3(ggrid), dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl,
+                  (int)a.n_queries, (int64_t)seg->pos_len, a.d_gr, c->d_err, (const PhraseCut*)a.d_cut0);
+    };
+    if (legacy) go(k_sloppy_groups<true>); else go(k_sloppy_groups<false>);
+  };
+  const int64_t* const all_slots = nullptr;
+  const int64_t groups = a.slots / 64;
+  const dim3 lanes_grid(wg_count((groups + WG_WAVES - 1) / WG_WAVES));
+  // ---- first pass. Packed (.doc version 1) segments: 64 candidates per wavefront; what those kernels hand on is listed.
+  // Legacy segments (the packed streams of a block are laid out differently): one candidate per wavefront throughout.
+  if (a.any_exact) {
+    if (legacy) {
+      TimedLaunch tl(c, stream, "k_phrase_match", 0);
+      exact(k_phrase_match<true, PHRASE_SMALL_CAP, false>, all_slots, a.slots);
+    } else {
+      TimedLaunch tl(c, stream, "k_phrase_match_lanes", 0);
+      RGPU_LAUNCH(k_phrase_match_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl,
+                  (int)a.n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)a.redo_cap, c->d_err + 2);
+    }
+  }
+  if (a.any_sloppy) {
+    if (legacy) {
+      if (a.with_groups) sloppy_groups();
+      TimedLaunch tl(c, stream, "k_sloppy_match", 0);
+      sloppy(k_sloppy_match<true, SLOPPY_SMALL_POOL, false>, all_slots, a.slots);
+    } else {
+      if (a.sloppy_rpts) sloppy_groups();  // the repetition groups: k_sloppy_rpt_lanes (and what it hands on) needs them
+      {
+        TimedLaunch tl(c, stream, "k_sloppy_match_lanes", 0);
+        RGPU_LAUNCH(k_sloppy_match_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl,
+                    (int)a.n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)a.redo_cap, c->d_err + 2,
+                    a.sloppy_rpts ? 1 : 0);
+      }
+      if (a.sloppy_rpts) {  // phrases that repeat a term: the scorer's repeats machinery per lane
+        TimedLaunch tl(c, stream, "k_sloppy_rpt_lanes", 0);
+        RGPU_LAUNCH(k_sloppy_rpt_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl,
+                    a.d_gr, (int)a.n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)a.redo_cap, c->d_err + 2);
+      }
+    }
+  }
+  // ---- which candidates wait for another pass (bits PHRASE_REDO_*): one look per stage that can raise one
+  int listed = 0, redo = 0;  // d_err[2]: slots on the list, d_err[3]: the bits
+  auto redo_bits = [&]() -> int32_t {
+    int two[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(two, c->d_err + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    listed = two[0];
+    redo = two[1];
+    return RGPU_OK;
+  };
+  int32_t rc = redo_bits();
+  if (rc != RGPU_OK) return rc;
+  // the one-candidate kernels over the listed slots (or, should the list have overflowed, over every slot)
+  const bool by_list = !legacy && (int64_t)listed <= a.redo_cap;
+  const int64_t* const left = by_list ? (const int64_t*)c->phrase_redo.p : all_slots;
+  const int64_t n_left = by_list ? (int64_t)listed : a.slots;
+  if (HostClock::on() && (redo & (PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES)))
+    std::fprintf(stderr, "[phrase] %d of %lld candidate slots left for the one-candidate kernels\n", listed, (long long)a.slots);
+  if (redo & PHRASE_REDO_LANES) {
+    TimedLaunch tl(c, stream, "k_phrase_match(left by the 64-candidate kernel)", 0);
+    exact(k_phrase_match<false, PHRASE_SMALL_CAP, true>, left, n_left);
+  }
+  if (redo & PHRASE_REDO_SLOPPY_LANES) {
+    TimedLaunch tl(c, stream, "k_sloppy_match(left by the 64-candidate kernel)", 0);  // (the groups are there: computed in front of the 64-candidate kernels)
+    sloppy(k_sloppy_match<false, SLOPPY_SMALL_POOL, true>, left, n_left);
+  }
+  if (redo & (PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES)) {
+    rc = redo_bits();
+    if (rc != RGPU_OK) return rc;
+  }
+  if (redo & PHRASE_REDO_WIDE) {
+    TimedLaunch tl(c, stream, "k_phrase_match(wide lists)", 0);
+    if (legacy) exact(k_phrase_match<true, PHRASE_LIST_CAP, true>, left, n_left); else exact(k_phrase_match<false, PHRASE_LIST_CAP, true>, left, n_left);
+  }
+  if (redo & PHRASE_REDO_SLOPPY) {
+    TimedLaunch tl(c, stream, "k_sloppy_match(wide pool)", 0);
+    if (legacy) sloppy(k_sloppy_match<true, SLOPPY_POOL, true>, left, n_left); else sloppy(k_sloppy_match<false, SLOPPY_POOL, true>, left, n_left);
+  }
+  return RGPU_OK;
+}
+
 extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
                                             const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
                                             int64_t* total_hits_out) {
@@ -3838,10 +3982,7 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
     HIP_TRY(stage_h2d(c, st.used, stream));
     HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
     HIP_TRY(c->phrase_keys.reserve((size_t)slots + 64, 0, stream));
-    // (developer knob: RGPU_PHRASE_REDO_CAP=<n> shrinks the list of left-over candidates, so that a test reaches the pass that runs without it)
-    int64_t redo_cap = PHRASE_REDO_LIST_CAP;
-    if (const char* e = std::getenv("RGPU_PHRASE_REDO_CAP")) redo_cap = std::max<int64_t>(0, std::min<int64_t>(redo_cap, std::atoll(e)));
-    redo_cap = std::min<int64_t>(slots, redo_cap);
+    const int64_t redo_cap = phrase_redo_cap(slots);
     HIP_TRY(c->phrase_redo.reserve((size_t)redo_cap + 64, 0, stream));
     HIP_TRY(c->phrase_count.reserve((size_t)n_queries, 0, stream));
     HIP_TRY(hipMemsetAsync(c->phrase_count.p, 0, (size_t)n_queries * 8, stream));
@@ -3877,117 +4018,11 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
     const int32_t* d_nl = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_nl);
     SloppyGroups* d_gr = reinterpret_cast<SloppyGroups*>(c->S->d_stage.p + o_gr);
     if (slots > 0) {
-      // One wavefront per candidate slot, first with the small position lists / pools (seven wavefronts per SIMD). A doc that holds
-      // a term more often than those hold positions (rare: Rucene clamps freqs to 10) leaves PHRASE_REDO in its slot: one look at
-      // the flag, then the wide instantiations over the marked candidates only.
-      // (one wavefront per slot: at most PHRASE_LAUNCH_SLOTS slots per launch — a grid of more than 2^32 work-items is cut short)
-      auto per_slot = [&](int64_t n, auto launch) {
-        for (int64_t s0 = 0; s0 < n; s0 += PHRASE_LAUNCH_SLOTS) {
-          const int64_t s1 = std::min(n, s0 + PHRASE_LAUNCH_SLOTS);
-          launch(dim3(wg_count((s1 - s0 + WG_WAVES - 1) / WG_WAVES)), s0, s1);
-        }
-      };
-      // (list: null = every slot of the launch; else the listed slots — the ones a 64-candidate kernel handed on)
-      auto exact = [&](auto kern, const int64_t* list, int64_t n) {
-        per_slot(n, [&](dim3 grid, int64_t s0, int64_t s1) {
-          RGPU_LAUNCH(kern, grid, dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_pt, d_ep, c->phrase_count.p, c->phrase_docs.p, d_sl, (int)n_queries, s1,
-                      (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err, c->d_err + 3, list, s0);
-        });
-      };
-      auto sloppy = [&](auto kern, const int64_t* list, int64_t n) {
-        per_slot(n, [&](dim3 grid, int64_t s0, int64_t s1) {
-          RGPU_LAUNCH(kern, grid, dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_pt, d_ep, c->phrase_count.p, c->phrase_docs.p, d_sl, d_gr, (int)n_queries, s1,
-                      (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err, c->d_err + 3, list, s0);
-        });
-      };
-      auto sloppy_groups = [&]() {  // the repetition groups of each query's first candidate doc (phrases with a repeated term)
-        TimedLaunch tl(c, stream, "k_sloppy_groups", 0);
-        PhraseCut* d_cut0 = reinterpret_cast<PhraseCut*>(c->S->d_stage.p + o_cut);
-        const int64_t* d_cp0 = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_cp);
-        const int32_t* d_nl0 = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_nl);
-        if (collect_items > 0)  // every sloppy query's smallest live candidate, chunk by chunk
-          RGPU_LAUNCH(k_phrase_cutoff_items<2>, dim3(wg_count((collect_items + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, d_cp0, d_ep,
-                      c->phrase_count.p, c->phrase_keys.p, (const int32_t*)c->phrase_docs.p, d_sl, d_nl0, (int)n_queries, collect_items, d_cut0);
-        const unsigned ggrid = wg_count((n_queries + WG_WAVES - 1) / WG_WAVES);
-        auto go = [&](auto kern) {
-          RGPU_LAUNCH(kern, dim3(ggrid), dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_pt, d_ep, c->phrase_count.p, c->phrase_docs.p, d_sl,
-                      (int)n_queries, (int64_t)seg->pos_len, d_gr, c->d_err, (const PhraseCut*)d_cut0);
-        };
-        if (legacy) go(k_sloppy_groups<true>); else go(k_sloppy_groups<false>);
-      };
-      const int64_t* const all_slots = nullptr;
-      const int64_t groups = slots / 64;
-      const dim3 lanes_grid(wg_count((groups + WG_WAVES - 1) / WG_WAVES));
-      // ---- first pass. Packed (.doc version 1) segments: 64 candidates per wavefront; what those kernels hand on is listed.
-      // Legacy segments (the packed streams of a block are laid out differently): one candidate per wavefront throughout.
-      if (any_exact) {
-        if (legacy) {
-          TimedLaunch tl(c, stream, "k_phrase_match", 0);
-          exact(k_phrase_match<true, PHRASE_SMALL_CAP, false>, all_slots, slots);
-        } else {
-          TimedLaunch tl(c, stream, "k_phrase_match_lanes", 0);
-          RGPU_LAUNCH(k_phrase_match_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_pt, d_ep, c->phrase_count.p, c->phrase_docs.p, d_sl,
-                      (int)n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)redo_cap, c->d_err + 2);
-        }
-      }
-      if (any_sloppy) {
-        if (legacy) {
-          sloppy_groups();
-          TimedLaunch tl(c, stream, "k_sloppy_match", 0);
-          sloppy(k_sloppy_match<true, SLOPPY_SMALL_POOL, false>, all_slots, slots);
-        } else {
-          if (sloppy_rpts) sloppy_groups();  // the repetition groups: k_sloppy_rpt_lanes (and what it hands on) needs them
-          {
-            TimedLaunch tl(c, stream, "k_sloppy_match_lanes", 0);
-            RGPU_LAUNCH(k_sloppy_match_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_pt, d_ep, c->phrase_count.p, c->phrase_docs.p, d_sl,
-                        (int)n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)redo_cap, c->d_err + 2,
-                        sloppy_rpts ? 1 : 0);
-          }
-          if (sloppy_rpts) {  // phrases that repeat a term: the scorer's repeats machinery per lane
-            TimedLaunch tl(c, stream, "k_sloppy_rpt_lanes", 0);
-            RGPU_LAUNCH(k_sloppy_rpt_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_pt, d_ep, c->phrase_count.p, c->phrase_docs.p, d_sl,
-                        d_gr, (int)n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)redo_cap, c->d_err + 2);
-          }
-        }
-      }
-      // ---- which candidates wait for another pass (bits PHRASE_REDO_*): one look per stage that can raise one
-      int listed = 0, redo = 0;  // d_err[2]: slots on the list, d_err[3]: the bits
-      auto redo_bits = [&]() -> int32_t {
-        int two[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(two, c->d_err + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        listed = two[0];
-        redo = two[1];
-        return RGPU_OK;
-      };
-      rc = redo_bits();
+      PhraseMatchStage ms{d_q, d_t, d_pt, d_ep, d_sl, d_gr, n_queries, slots, redo_cap, any_exact, any_sloppy, sloppy_rpts, true,
+                          reinterpret_cast<PhraseCut*>(c->S->d_stage.p + o_cut), reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_cp),
+                          reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_nl), collect_items};
+      rc = phrase_match_stage(seg, stream, ms);
       if (rc != RGPU_OK) return rc;
-      // the one-candidate kernels over the listed slots (or, should the list have overflowed, over every slot)
-      const bool by_list = !legacy && (int64_t)listed <= redo_cap;
-      const int64_t* const left = by_list ? (const int64_t*)c->phrase_redo.p : all_slots;
-      const int64_t n_left = by_list ? (int64_t)listed : slots;
-      if (HostClock::on() && (redo & (PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES)))
-        std::fprintf(stderr, "[phrase] %d of %lld candidate slots left for the one-candidate kernels\n", listed, (long long)slots);
-      if (redo & PHRASE_REDO_LANES) {
-        TimedLaunch tl(c, stream, "k_phrase_match(left by the 64-candidate kernel)", 0);
-        exact(k_phrase_match<false, PHRASE_SMALL_CAP, true>, left, n_left);
-      }
-      if (redo & PHRASE_REDO_SLOPPY_LANES) {
-        TimedLaunch tl(c, stream, "k_sloppy_match(left by the 64-candidate kernel)", 0);  // (the groups are there: computed in front of the 64-candidate kernels)
-        sloppy(k_sloppy_match<false, SLOPPY_SMALL_POOL, true>, left, n_left);
-      }
-      if (redo & (PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES)) {
-        rc = redo_bits();
-        if (rc != RGPU_OK) return rc;
-      }
-      if (redo & PHRASE_REDO_WIDE) {
-        TimedLaunch tl(c, stream, "k_phrase_match(wide lists)", 0);
-        if (legacy) exact(k_phrase_match<true, PHRASE_LIST_CAP, true>, left, n_left); else exact(k_phrase_match<false, PHRASE_LIST_CAP, true>, left, n_left);
-      }
-      if (redo & PHRASE_REDO_SLOPPY) {
-        TimedLaunch tl(c, stream, "k_sloppy_match(wide pool)", 0);
-        if (legacy) sloppy(k_sloppy_match<true, SLOPPY_POOL, true>, left, n_left); else sloppy(k_sloppy_match<false, SLOPPY_POOL, true>, left, n_left);
-      }
     }
     if (chunked) {
       const int64_t* d_cp = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_cp);
@@ -4118,6 +4153,175 @@ extern "C" int32_t rgpu_rescore_batch(rgpu_segment* seg, const rgpu_query* queri
     RGPU_LAUNCH(k_rescore_sort, dim3(wg_count((n_queries + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, d_r, (int)n_queries, (int)k, c->host_api_hits.p);
   }
   HIP_TRY(launch_status());
+  HIP_TRY(hipMemcpyAsync(hits_inout, c->host_api_hits.p, n_hits * sizeof(HitOut), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return RGPU_OK;
+}
+
+// QueryRescorer whose second query is a PhraseQuery: the window's hits are the candidate slots of the phrase match stage.
+extern "C" int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
+                                             const rgpu_phrase_term* terms, int32_t n_terms_total, const rgpu_rescore_request* requests,
+                                             int32_t k, rgpu_hit* hits_inout, int32_t finish) {
+  if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !requests || !hits_inout)
+    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "phrase rescoring: k must be in 1..RGPU_MAX_K");
+  if (!seg->has_positions || !seg->d_pos) return fail(RGPU_ERR_ILLEGAL_STATE, "phrase rescoring needs a positions field with its .pos file attached");
+  rgpu_ctx* c = seg->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t stream = c->stream;
+  // ---- validate (every refusal comes before hits_inout is touched)
+  std::vector<const rgpu_term_state*> ptrs;
+  std::vector<RescoreParams> rp((size_t)n_queries);
+  auto same_term = [](const rgpu_term_state& a, const rgpu_term_state& b) {  // as rgpu_search_phrase_batch fills PosTerm::same_as
+    return a.doc_start_fp == b.doc_start_fp && a.doc_freq == b.doc_freq && a.singleton_doc_id == b.singleton_doc_id && a.total_term_freq == b.total_term_freq;
+  };
+  for (int32_t q = 0; q < n_queries; ++q) {
+    const rgpu_phrase_query& Q = queries[q];
+    if (Q.n_terms < 2 || Q.n_terms > RGPU_MAX_PHRASE_TERMS) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a phrase has 2..RGPU_MAX_PHRASE_TERMS terms");
+    if (Q.slop < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "Slop must be >= 0");  // PhraseQuery::new (phrase_query.rs:77)
+    if (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms > (int64_t)n_terms_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "term range outside terms[]");
+    if (Q.sim_table < 0 || Q.sim_table >= c->n_sim_tables) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
+    const rgpu_rescore_request& r = requests[q];
+    if (r.mode < RGPU_RESCORE_AVG || r.mode > RGPU_RESCORE_MULTIPLY || r.window_size < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad rescore request");
+    rp[(size_t)q] = RescoreParams{r.query_weight, r.rescore_weight, r.mode, std::min(std::min(r.window_size, k), RGPU_PASS_K)};
+    for (int i = 0; i < Q.n_terms; ++i) {
+      const rgpu_phrase_term& t = terms[Q.first_term + i];
+      if (t.state.doc_freq > 0) {
+        if (t.positions.pos_start_fp < 0 || (size_t)t.positions.pos_start_fp >= seg->pos_len) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "pos_start_fp outside the .pos file");
+        if (t.state.total_term_freq < t.state.doc_freq) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "total_term_freq below doc_freq");
+      }
+    }
+  }
+  for (int32_t q = 0; q < n_queries; ++q) {
+    const rgpu_phrase_query& Q = queries[q];
+    bool dead = false;  // a term absent from the leaf: create_scorer -> None, the row is served (nothing matches), whatever its terms
+    for (int i = 0; i < Q.n_terms; ++i) {
+      const rgpu_phrase_term& t = terms[Q.first_term + i];
+      if (t.state.doc_freq > 0) ptrs.push_back(&t.state); else dead = true;
+    }
+    // SloppyPhraseScorer finds its repetition groups on the first doc it evaluates in the leaf (init_first_time,
+    // phrase_scorer.rs:807-820): in a rescoring that is a conjunction match at or behind the first window hit, not a hit.
+    // (Only a row that is alive here is looked at, as rgpu_search_phrase_batch fills same_as: absent terms all look alike.)
+    if (Q.slop > 0 && !dead)
+      for (int i = 1; i < Q.n_terms; ++i)
+        for (int j = 0; j < i; ++j)
+          if (same_term(terms[Q.first_term + j].state, terms[Q.first_term + i].state))
+            return fail(RGPU_ERR_UNSUPPORTED, "phrase rescoring: a sloppy phrase that names a term twice is not served");
+  }
+  int32_t rc = prepare_terms_locked(seg, ptrs.data(), ptrs.size());
+  if (rc != RGPU_OK) return rc;
+  // ---- plan: row q owns the candidate slots [q * S, q * S + S)
+  const int S = (k + 63) & ~63;
+  const int64_t slots = (int64_t)n_queries * S;
+  std::vector<DevQuery> dq((size_t)n_queries);
+  std::vector<DevTerm> dt;
+  std::vector<PosTerm> pt;
+  std::vector<int64_t> emit_prefix((size_t)n_queries + 1);
+  std::vector<unsigned long long> emit_count((size_t)n_queries);
+  std::vector<int32_t> slops((size_t)n_queries, 0);
+  bool any_sloppy = false, any_exact = false;
+  for (int32_t q = 0; q < n_queries; ++q) {
+    const rgpu_phrase_query& Q = queries[q];
+    emit_prefix[(size_t)q] = (int64_t)q * S;
+    emit_count[(size_t)q] = (unsigned long long)rp[(size_t)q].window;
+    dq[(size_t)q] = DevQuery{RGPU_OP_AND, 0, (int32_t)dt.size(), 0};
+    bool dead = false;
+    for (int i = 0; i < Q.n_terms; ++i) dead = dead || terms[Q.first_term + i].state.doc_freq <= 0;
+    if (dead) continue;  // PhraseWeight::create_scorer -> None (phrase_query.rs:275-283): no hit of the row matches in this leaf
+    std::vector<int> order((size_t)Q.n_terms);
+    for (int i = 0; i < Q.n_terms; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return terms[Q.first_term + a].state.doc_freq < terms[Q.first_term + b].state.doc_freq; });
+    for (int i : order) {  // cost order (conjunction_scorer.rs:30), as in rgpu_search_phrase_batch
+      const rgpu_phrase_term& t = terms[Q.first_term + i];
+      DevTerm d;
+      rc = make_dev_term(seg, t.state, Q.weight, Q.sim_table, &d);
+      if (rc != RGPU_OK) return rc;
+      dt.push_back(d);
+      PosTerm p{};
+      p.pos_start_fp = (uint64_t)t.positions.pos_start_fp;
+      p.total_term_freq = t.state.total_term_freq;
+      p.last_pos_block_fp = t.state.total_term_freq < 128 ? t.positions.pos_start_fp
+                            : (t.state.total_term_freq == 128 ? -1 : t.positions.pos_start_fp + t.positions.last_pos_block_offset);
+      p.phrase_pos = t.position;
+      p.query_ord = i;
+      p.same_as = i;
+      for (int j = 0; j < i; ++j)
+        if (same_term(terms[Q.first_term + j].state, t.state)) { p.same_as = j; break; }  // (exact phrases only: "a b a")
+      pt.push_back(p);
+    }
+    slops[(size_t)q] = Q.slop;
+    (Q.slop > 0 ? any_sloppy : any_exact) = true;
+    dq[(size_t)q].n_terms = Q.n_terms;
+  }
+  emit_prefix[(size_t)n_queries] = slots;
+  SCRATCH_TAKE(c);
+  Stager st(c);
+  const size_t o_q = st.add((size_t)n_queries * sizeof(DevQuery));
+  const size_t o_t = st.add(std::max<size_t>(1, dt.size()) * sizeof(DevTerm));
+  const size_t o_pt = st.add(std::max<size_t>(1, pt.size()) * sizeof(PosTerm));
+  const size_t o_ep = st.add((size_t)(n_queries + 1) * 8);
+  const size_t o_ec = st.add((size_t)n_queries * 8);
+  const size_t o_sl = st.add((size_t)n_queries * 4);
+  const size_t o_gr = st.add((size_t)n_queries * sizeof(SloppyGroups));
+  const size_t o_r = st.add((size_t)n_queries * sizeof(RescoreParams));
+  HIP_TRY(c->S->h_stage.reserve(st.used));
+  HIP_TRY(c->S->d_stage.reserve(st.used, 0, stream));
+  std::memcpy(c->S->h_stage.p + o_q, dq.data(), (size_t)n_queries * sizeof(DevQuery));
+  if (!dt.empty()) std::memcpy(c->S->h_stage.p + o_t, dt.data(), dt.size() * sizeof(DevTerm));
+  if (!pt.empty()) std::memcpy(c->S->h_stage.p + o_pt, pt.data(), pt.size() * sizeof(PosTerm));
+  std::memcpy(c->S->h_stage.p + o_ep, emit_prefix.data(), (size_t)(n_queries + 1) * 8);
+  std::memcpy(c->S->h_stage.p + o_ec, emit_count.data(), (size_t)n_queries * 8);
+  std::memcpy(c->S->h_stage.p + o_sl, slops.data(), (size_t)n_queries * 4);
+  std::memset(c->S->h_stage.p + o_gr, 0xff, (size_t)n_queries * sizeof(SloppyGroups));  // "no repetition group": k_sloppy_match reads the region
+  std::memcpy(c->S->h_stage.p + o_r, rp.data(), (size_t)n_queries * sizeof(RescoreParams));
+  HIP_TRY(stage_h2d(c, st.used, stream));
+  const size_t n_hits = (size_t)n_queries * (size_t)k;
+  HIP_TRY(c->host_api_hits.reserve(n_hits, 0, stream));
+  HIP_TRY(hipMemcpyAsync(c->host_api_hits.p, hits_inout, n_hits * sizeof(HitOut), hipMemcpyHostToDevice, stream));
+  HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
+  HIP_TRY(c->phrase_keys.reserve((size_t)slots + 64, 0, stream));
+  const int64_t redo_cap = phrase_redo_cap(slots);
+  HIP_TRY(c->phrase_redo.reserve((size_t)redo_cap + 64, 0, stream));
+  HIP_TRY(c->phrase_count.reserve((size_t)n_queries, 0, stream));
+  HIP_TRY(hipMemcpyAsync(c->phrase_count.p, c->S->d_stage.p + o_ec, (size_t)n_queries * 8, hipMemcpyDeviceToDevice, stream));
+  // (a 64-candidate kernel leaves the slots behind a row's window unwritten, and a batch of absent-term rows launches none)
+  HIP_TRY(hipMemsetAsync(c->phrase_keys.p, 0, (size_t)slots * 8, stream));
+  HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));
+  const DevQuery* d_q = reinterpret_cast<const DevQuery*>(c->S->d_stage.p + o_q);
+  const DevTerm* d_t = reinterpret_cast<const DevTerm*>(c->S->d_stage.p + o_t);
+  const PosTerm* d_pt = reinterpret_cast<const PosTerm*>(c->S->d_stage.p + o_pt);
+  const int64_t* d_ep = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_ep);
+  const int32_t* d_sl = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_sl);
+  SloppyGroups* d_gr = reinterpret_cast<SloppyGroups*>(c->S->d_stage.p + o_gr);
+  RescoreParams* d_r = reinterpret_cast<RescoreParams*>(c->S->d_stage.p + o_r);
+  const SegView sv = seg_view(seg);
+  {
+    TimedLaunch tl(c, stream, "k_rescore_phrase_candidates", 0);
+    const unsigned grid = wg_count((slots + WG_WAVES - 1) / WG_WAVES);
+    if (seg->version < 1) RGPU_LAUNCH(k_rescore_phrase_candidates<true>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_r, (int)n_queries, (int)k, S, c->host_api_hits.p, c->phrase_docs.p);
+    else RGPU_LAUNCH(k_rescore_phrase_candidates<false>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_r, (int)n_queries, (int)k, S, c->host_api_hits.p, c->phrase_docs.p);
+  }
+  if (any_exact || any_sloppy) {
+    PhraseMatchStage ms{d_q, d_t, d_pt, d_ep, d_sl, d_gr, n_queries, slots, redo_cap, any_exact, any_sloppy, false, false, nullptr, nullptr, nullptr, 0};
+    rc = phrase_match_stage(seg, stream, ms);
+    if (rc != RGPU_OK) return rc;
+  }
+  {
+    TimedLaunch tl(c, stream, "k_rescore_phrase_combine", 0);
+    RGPU_LAUNCH(k_rescore_phrase_combine, dim3(wg_count((n_hits + 255) / 256)), dim3(256), 0, stream, sv, d_r, (int)n_queries, (int)k, S, c->phrase_keys.p, c->host_api_hits.p, finish ? 1 : 0);
+  }
+  if (finish) {
+    TimedLaunch tl(c, stream, "k_rescore_sort", 0);
+    RGPU_LAUNCH(k_rescore_sort, dim3(wg_count((n_queries + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, d_r, (int)n_queries, (int)k, c->host_api_hits.p);
+  }
+  HIP_TRY(launch_status());
+  int err = 0;
+  HIP_TRY(hipMemcpyAsync(&err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (err != 0)  // (hits_inout stays as it came)
+    return fail(err, err == RGPU_ERR_UNSUPPORTED ? "a hit doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)"
+                                                 : (err == RGPU_ERR_ILLEGAL_STATE ? "internal: a candidate doc was not found again" : "corrupt position data in .pos"));
   HIP_TRY(hipMemcpyAsync(hits_inout, c->host_api_hits.p, n_hits * sizeof(HitOut), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   return RGPU_OK;

@@ -801,16 +801,32 @@ class GpuIndexSearcher:
 
     def rescore_batch(self, hits, rescore_queries, query_weight=1.0, rescore_weight=1.0, mode=_lib.RESCORE_TOTAL, window_size=None):
         """QueryRescorer::rescore (search/scorer/rescorer.rs:376-390) for a batch: row i of `hits` (a first pass's output) is
-        re-ranked by rescore_queries[i] — TermQuery or an all-MUST / all-SHOULD BooleanQuery. One call per leaf, the last
-        one sorts the windows and re-weights the tails."""
+        re-ranked by rescore_queries[i] — a TermQuery, an all-MUST / all-SHOULD BooleanQuery, or a PhraseQuery (exact, or sloppy
+        without a repeated term; k up to 128 when the batch holds other kinds than phrases). A batch may mix the kinds: the
+        phrase rows go through rgpu_rescore_phrase_batch, the others through rgpu_rescore_batch, and a row's result does not
+        depend on the other rows. One call per kind and leaf, the last leaf's sorts the windows and re-weights the tails."""
         k = hits.shape[1]
         req = np.zeros(len(rescore_queries), dtype=_lib.RESCORE_REQUEST_DTYPE)
         req["query_weight"], req["rescore_weight"], req["mode"] = query_weight, rescore_weight, mode
         req["window_size"] = k if window_size is None else window_size
-        out = hits
-        for i, leaf in enumerate(self.leaves):
-            qs, ts = self.pack(rescore_queries, leaf)
-            out = leaf.segment.rescore_batch(qs, ts, req, out, finish=(i == len(self.leaves) - 1))
+        is_phrase = np.array([isinstance(q, PhraseQuery) for q in rescore_queries], dtype=bool)
+        for q in rescore_queries:   # refused before any leaf is touched (a leaf that lacks the term would serve the row, the next one not)
+            if isinstance(q, PhraseQuery) and q.slop > 0 and len(set(q.terms)) < len(q.terms):
+                raise RgpuError(-5, "phrase rescoring: a sloppy phrase that names a term twice is not served")
+        out = np.ascontiguousarray(hits, dtype=_lib.HIT_DTYPE).copy()
+        for phrase, rows in ((False, np.flatnonzero(~is_phrase)), (True, np.flatnonzero(is_phrase))):
+            if rows.size == 0:
+                continue
+            mine, part = [rescore_queries[i] for i in rows], out[rows]
+            for i, leaf in enumerate(self.leaves):
+                finish = i == len(self.leaves) - 1
+                if phrase:
+                    qs, ts = self.pack_phrases(mine, leaf)
+                    part = leaf.segment.rescore_phrase_batch(qs, ts, req[rows], part, finish=finish)
+                else:
+                    qs, ts = self.pack(mine, leaf)
+                    part = leaf.segment.rescore_batch(qs, ts, req[rows], part, finish=finish)
+            out[rows] = part
         return out
 
     def search_batch(self, queries, k):

@@ -362,6 +362,56 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
         Ok(true)
     }
 
+    /// The phrase's terms in one leaf, in the query's order: postings + position-stream pointers (a term absent from the leaf:
+    /// doc_freq = 0, which tells the library what PhraseWeight::create_scorer -> None tells the reference)
+    fn phrase_terms(&self, leaf: &LeafReaderContext<'_, C>, terms: &[Term], positions: &[i32]) -> Result<Vec<RgpuPhraseTerm>> {
+        let mut pterms = Vec::with_capacity(terms.len());
+        for (t, pos) in terms.iter().zip(positions.iter()) {
+            let st = self.block_state(leaf, t)?;
+            let ptrs = match &st {
+                Some(s) => RgpuTermPositions { pos_start_fp: s.pos_start_fp, pay_start_fp: s.pay_start_fp, last_pos_block_offset: s.last_pos_block_offset },
+                None => RgpuTermPositions { pos_start_fp: 0, pay_start_fp: 0, last_pos_block_offset: -1 },
+            };
+            pterms.push(RgpuPhraseTerm { state: Self::term_state(&st), positions: ptrs, position: *pos, reserved: 0 });
+        }
+        Ok(pterms)
+    }
+
+    /// QueryRescorer::rescore (rescorer.rs:376-390) of one first-pass row with a PhraseQuery as the second query: `row` is the
+    /// first pass's (doc, score) list, best first, at most RGPU_MAX_K long; on Ok(true) it holds the rescored row —
+    /// iterative_rescore (:229-298) with an Exact- / SloppyPhraseScorer advanced from hit to hit, combine_score, the window sorted
+    /// (score desc, doc asc), the tail re-weighted (combine_docs). mode: RescoreMode's ordinal (0 Avg .. 4 Multiply). One
+    /// rgpu_rescore_phrase_batch per leaf, the last one finishing. window_size is RescoreRequest::window_size as the reference
+    /// means it: the number of leading hits that are rescored, 0 = none (every hit only takes query_weight); it is clipped to the
+    /// row's length (the C++ host mirror's "0 = the whole row" is that mirror's own shorthand). Ok(false): not served here — another field, a leaf without
+    /// positions, a sloppy phrase that names a term twice (its repetition groups depend on a doc that is no hit) — and `row` is
+    /// untouched: the caller runs QueryRescorer on the CPU searcher.
+    pub fn rescore_phrase(&self, p: &PhraseQuery, query_weight: f32, rescore_weight: f32, mode: i32, window_size: usize,
+                          row: &mut Vec<(DocId, f32)>) -> Result<bool> {
+        let (field, terms, positions, slop) = p.parts();
+        let k = row.len();
+        if field != self.field || terms.len() < 2 || terms.len() > RGPU_MAX_PHRASE_TERMS as usize || terms.len() != positions.len()
+            || k == 0 || k > RGPU_MAX_K as usize || self.leaves.iter().any(|l| !l.has_positions) {
+            return Ok(false);
+        }
+        if slop > 0 && terms.iter().enumerate().any(|(i, t)| terms[..i].iter().any(|u| u.bytes == t.bytes)) { return Ok(false); }
+        let term_refs: Vec<&Term> = terms.iter().collect();
+        let (weight, sim_table) = self.weight_of(&term_refs, 1.0)?;
+        let req = RgpuRescoreRequest { query_weight, rescore_weight, mode, window_size: window_size.min(k) as i32 };
+        let mut hits: Vec<RgpuHit> = row.iter().map(|&(doc, score)| RgpuHit { doc, score }).collect();
+        let leaves = self.cpu.reader().leaves();
+        let n_leaves = leaves.len();
+        for (i, leaf) in leaves.into_iter().enumerate() {
+            let pterms = self.phrase_terms(&leaf, terms, positions)?;
+            let q = RgpuPhraseQuery { n_terms: pterms.len() as i32, first_term: 0, weight, sim_table, slop, next_limit: self.next_limit };
+            check(unsafe { rgpu_rescore_phrase_batch(self.leaves[leaf.ord].seg, &q, 1, pterms.as_ptr(), pterms.len() as i32, &req, k as i32,
+                                                     hits.as_mut_ptr(), if i + 1 == n_leaves { 1 } else { 0 }) }, self.ctx)?;
+        }
+        row.clear();
+        row.extend(hits.iter().filter(|h| h.doc >= 0).map(|h| (h.doc, h.score)));
+        Ok(true)
+    }
+
     /// PhraseQuery { any slop } on a positions field (payloads / offsets included): terms + phrase offsets from the query,
     /// weight = summed idf x boost as PhraseQuery::create_weight (phrase_query.rs:136-186; its boost is 1.0). Per leaf as
     /// PhraseWeight::create_scorer (:268-333): a term absent from the leaf -> no scorer for that leaf (doc_freq = 0 tells the
@@ -375,15 +425,7 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
         let term_refs: Vec<&Term> = terms.iter().collect();
         let (weight, sim_table) = self.weight_of(&term_refs, 1.0)?;
         for leaf in self.cpu.reader().leaves() {
-            let mut pterms = Vec::with_capacity(terms.len());
-            for (t, pos) in terms.iter().zip(positions.iter()) {
-                let st = self.block_state(&leaf, t)?;
-                let ptrs = match &st {
-                    Some(s) => RgpuTermPositions { pos_start_fp: s.pos_start_fp, pay_start_fp: s.pay_start_fp, last_pos_block_offset: s.last_pos_block_offset },
-                    None => RgpuTermPositions { pos_start_fp: 0, pay_start_fp: 0, last_pos_block_offset: -1 },
-                };
-                pterms.push(RgpuPhraseTerm { state: Self::term_state(&st), positions: ptrs, position: *pos, reserved: 0 });
-            }
+            let pterms = self.phrase_terms(&leaf, terms, positions)?;
             let q = RgpuPhraseQuery { n_terms: pterms.len() as i32, first_term: 0, weight, sim_table, slop, next_limit: self.next_limit };
             let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
             let mut total: i64 = 0;
