@@ -32,6 +32,7 @@
 #include "host/flat_fp_map.hpp"
 #include "host/host_threads.hpp"
 #include "host/prepared_map.hpp"
+#include "host/stage_layout.hpp"
 #include "host/term_arena.hpp"
 #include "kernels/search_phrase.hpp"
 #include "kernels/search_term.hpp"
@@ -77,6 +78,7 @@ static inline unsigned wg_count(unsigned long long n) { return n > 0xffffffffull
     hipError_t _e = (expr);                                                                                \
     if (_e != hipSuccess) return fail(RGPU_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
+#define RGPU_TRY(expr) do { const int32_t rc_ = (expr); if (rc_ != RGPU_OK) return rc_; } while (0)
 // scratch_take() may have to settle a deferred disjunction batch first (rgpu_config.or_deferred): when THAT fails, the call that
 // happened to need the slot reports the deferred batch's own status and message (it used to become a generic
 // "hipErrorUnknown" attributed to the unrelated later call)
@@ -580,18 +582,28 @@ static hipError_t stage_h2d(rgpu_ctx* c, size_t bytes, hipStream_t s) {
 }
 
 // ---- staging: pack several host arrays into one pinned buffer, one H2D copy ---------------------------------
-struct Stager {
+// Two phases (host/stage_layout.hpp): a Stager only lays regions out; the pointers into the slot's h_stage / d_stage come from a
+// Staged, which sizes both buffers to the layout when it is made — no pointer exists before the buffers can hold it.
+struct Stager : rucene::StageLayout { rgpu_ctx* c; explicit Stager(rgpu_ctx* c_) : c(c_) {} };
+struct Staged : rucene::StageView {
   rgpu_ctx* c;
-  size_t used = 0;
-  std::vector<std::pair<size_t, size_t>> parts;  // offset, bytes
-  explicit Stager(rgpu_ctx* c_) : c(c_) {}
-  size_t add(size_t bytes) {
-    used = (used + 255) & ~size_t(255);
-    size_t off = used;
-    used += bytes;
-    return off;
+  size_t used;
+  int32_t rc = RGPU_OK;  // the sizing's status (STAGE_SIZED returns it when it is not RGPU_OK)
+  explicit Staged(const Stager& st) : rucene::StageView{&st.c->S->h_stage.p, &st.c->S->d_stage.p}, c(st.c), used(st.used) {
+    const char* what = "c->S->h_stage.reserve(st.used): ";
+    hipError_t e = c->S->h_stage.reserve(used);
+    if (e == hipSuccess) { what = "c->S->d_stage.reserve(st.used, 0, stream): "; e = c->S->d_stage.reserve(used, 0, c->stream); }
+    if (e != hipSuccess) rc = fail(RGPU_ERR_RUNTIME, what + std::string(hipGetErrorString(e)));
+  }
+  // a put() that did not fit its region fails the call here, before anything reaches the device
+  int32_t check() { return overrun ? fail(RGPU_ERR_ILLEGAL_STATE, "internal: a staged array is longer than the region laid out for it") : RGPU_OK; }
+  int32_t upload(hipStream_t s) {
+    RGPU_TRY(check());
+    const hipError_t e = stage_h2d(c, used, s);
+    return e == hipSuccess ? RGPU_OK : fail(RGPU_ERR_RUNTIME, std::string("stage_h2d(c, st.used, stream): ") + hipGetErrorString(e));
   }
 };
+#define STAGE_SIZED(sg, st) Staged sg(st); RGPU_TRY(sg.rc)  // the only way a Staged is made: nobody fills buffers that failed to grow
 
 static SegView seg_view(const rgpu_segment* s) {
   SegView v;
@@ -1129,19 +1141,18 @@ static int32_t prepare_norms_locked(rgpu_segment* seg, const rgpu_term_state* co
   int64_t n_items = 0, postings = 0;
   prep_items(work, &item_prefix, &n_items, &postings);
   Stager st(c);
-  const size_t o_work = st.add(work.size() * sizeof(PrepTerm));
-  const size_t o_items = st.add(item_prefix.size() * 8);
-  HIP_TRY(c->S->h_stage.reserve(st.used));
-  HIP_TRY(c->S->d_stage.reserve(st.used, 0, c->stream));
-  std::memcpy(c->S->h_stage.p + o_work, work.data(), work.size() * sizeof(PrepTerm));
-  std::memcpy(c->S->h_stage.p + o_items, item_prefix.data(), item_prefix.size() * 8);
+  const auto r_work = st.add<PrepTerm>(work.size());
+  const auto r_items = st.add<int64_t>(item_prefix.size());
+  STAGE_SIZED(sg, st);
+  sg.put(r_work, work);
+  sg.put(r_items, item_prefix);
+  RGPU_TRY(sg.check());
   HIP_TRY(hipMemcpyAsync(c->S->d_stage.p, c->S->h_stage.p, st.used, hipMemcpyHostToDevice, c->stream));
   {
     TimedLaunch tl(c, c->stream, "k_prepare_norms", postings);
     const unsigned grid = wg_count((n_items + PREP_WAVES - 1) / PREP_WAVES);
     auto go = [&](auto kern) {
-      RGPU_LAUNCH(kern, dim3(grid), dim3(PREP_THREADS), 0, c->stream, seg_view(seg), reinterpret_cast<const PrepTerm*>(c->S->d_stage.p + o_work),
-                         reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_items), (int)work.size(), n_items, seg->pnorm.p, seg->dir_bmax.p,
+      RGPU_LAUNCH(kern, dim3(grid), dim3(PREP_THREADS), 0, c->stream, seg_view(seg), sg.dev(r_work), sg.dev(r_items), (int)work.size(), n_items, seg->pnorm.p, seg->dir_bmax.p,
                          seg->n_norm_ranks > 0 ? 1 : 0);
     };
     if (seg->version < 1) go(k_prepare_norms<true>); else go(k_prepare_norms<false>);
@@ -1149,8 +1160,7 @@ static int32_t prepare_norms_locked(rgpu_segment* seg, const rgpu_term_state* co
   {  // ... and one level up: the frontier of every whole chunk of 64 blocks (what k_search_term tests first)
     TimedLaunch tl(c, c->stream, "k_chunk_frontiers", postings / 128);
     const unsigned grid = wg_count((n_items + PREP_WAVES - 1) / PREP_WAVES);
-    RGPU_LAUNCH(k_chunk_frontiers, dim3(grid), dim3(PREP_THREADS), 0, c->stream, reinterpret_cast<const PrepTerm*>(c->S->d_stage.p + o_work),
-                reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_items), (int)work.size(), n_items, seg->dir_bmax.p, seg->dir_sum.p);
+    RGPU_LAUNCH(k_chunk_frontiers, dim3(grid), dim3(PREP_THREADS), 0, c->stream, sg.dev(r_work), sg.dev(r_items), (int)work.size(), n_items, seg->dir_bmax.p, seg->dir_sum.p);
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(launch_status());
@@ -1586,8 +1596,7 @@ static int32_t decode_terms_impl(rgpu_segment* seg, const rgpu_term_state* terms
   // is validated once): it writes their postings straight to the caller's arrays; k_decode_terms serves the rest.
   std::vector<uint8_t> fused;
   const DecodeSink sink{out_of.data(), docs_dev, freqs_dev, &fused};
-  int32_t rc = prepare_terms_locked(seg, ptrs.data(), ptrs.size(), false, &sink);
-  if (rc != RGPU_OK) return rc;
+  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size(), false, &sink));
   std::vector<int64_t> rest;
   for (int64_t i = 0; i < n_terms; ++i)
     if (terms[i].doc_freq > 0 && !(i < (int64_t)fused.size() && fused[(size_t)i])) rest.push_back(i);
@@ -1595,14 +1604,11 @@ static int32_t decode_terms_impl(rgpu_segment* seg, const rgpu_term_state* terms
   const int64_t nr = (int64_t)rest.size();
   SCRATCH_TAKE(c);  // callers synchronize the stream before they return
   Stager st(c);
-  const size_t o_terms = st.add((size_t)nr * sizeof(DevTerm));
-  const size_t o_items = st.add((size_t)(nr + 1) * 8);
-  const size_t o_out = st.add((size_t)(nr + 1) * 8);
-  HIP_TRY(c->S->h_stage.reserve(st.used));
-  HIP_TRY(c->S->d_stage.reserve(st.used, 0, c->stream));
-  DevTerm* ht = reinterpret_cast<DevTerm*>(c->S->h_stage.p + o_terms);
-  int64_t* hitems = reinterpret_cast<int64_t*>(c->S->h_stage.p + o_items);
-  int64_t* hout = reinterpret_cast<int64_t*>(c->S->h_stage.p + o_out);
+  const auto r_terms = st.add<DevTerm>((size_t)nr);
+  const auto r_items = st.add<int64_t>((size_t)nr + 1), r_out = st.add<int64_t>((size_t)nr + 1);
+  STAGE_SIZED(sg, st);
+  DevTerm* ht = sg.host(r_terms);
+  int64_t *hitems = sg.host(r_items), *hout = sg.host(r_out);
   int64_t items = 0, postings = 0;
 #ifndef RGPU_DEC_BPI
 #define RGPU_DEC_BPI 16
@@ -1611,8 +1617,7 @@ static int32_t decode_terms_impl(rgpu_segment* seg, const rgpu_term_state* terms
   for (int64_t j = 0; j < nr; ++j) {
     if (j + 16 < nr) seg->prepared.prefetch(terms[rest[(size_t)(j + 16)]].doc_start_fp);
     const int64_t i = rest[(size_t)j];
-    rc = make_dev_term(seg, terms[i], 0.f, 0, &ht[j], false);
-    if (rc != RGPU_OK) return rc;
+    RGPU_TRY(make_dev_term(seg, terms[i], 0.f, 0, &ht[j], false));
     hitems[j] = items;
     hout[j] = out_of[(size_t)i];
     items += ht[j].nblocks == 0 ? 1 : (ht[j].nblocks + dec_blocks_per_item - 1) / dec_blocks_per_item;
@@ -1620,16 +1625,13 @@ static int32_t decode_terms_impl(rgpu_segment* seg, const rgpu_term_state* terms
   }
   hitems[nr] = items;
   hout[nr] = out;
-  HIP_TRY(stage_h2d(c, st.used, stream));
+  RGPU_TRY(sg.upload(stream));
   const unsigned grid = wg_count((items + WG_WAVES - 1) / WG_WAVES);
   {
     TimedLaunch tl(c, stream, "k_decode_terms", postings);
     auto args = [&](auto kern) {
-      RGPU_LAUNCH(kern, dim3(grid), dim3(WG_THREADS), 0, stream, seg_view(seg),
-                         reinterpret_cast<const DevTerm*>(c->S->d_stage.p + o_terms),
-                         reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_items),
-                         reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_out), (int)nr, items, dec_blocks_per_item, docs_dev,
-                         freqs_dev);
+      RGPU_LAUNCH(kern, dim3(grid), dim3(WG_THREADS), 0, stream, seg_view(seg), sg.dev(r_terms), sg.dev(r_items), sg.dev(r_out), (int)nr, items,
+                         dec_blocks_per_item, docs_dev, freqs_dev);
     };
     if (seg->version >= 1) args(k_decode_terms<false>); else args(k_decode_terms<true>);
   }
@@ -1993,21 +1995,19 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
   for (int q = 0; q <= nq; ++q) merge_prefix[(size_t)q] = (int64_t)q * ipq;
 
   Stager st(c);
-  const size_t o_q = st.add((size_t)nq * sizeof(DevQuery));
-  const size_t o_t = st.add((size_t)nt * sizeof(DevTerm));
-  const size_t o_ip = st.add((size_t)(nt + 1) * 8);
-  const size_t o_rp = st.add((size_t)(nt + 1) * 8);
-  const size_t o_mp = st.add((size_t)(nq + 1) * 8);
-  const size_t o_m = st.add((size_t)nq * 4);
-  HIP_TRY(c->S->h_stage.reserve(st.used));
-  HIP_TRY(c->S->d_stage.reserve(st.used, 0, stream));
-  std::memcpy(c->S->h_stage.p + o_q, G.queries.data(), (size_t)nq * sizeof(DevQuery));
-  std::memcpy(c->S->h_stage.p + o_t, G.terms.data(), (size_t)nt * sizeof(DevTerm));
-  std::memcpy(c->S->h_stage.p + o_ip, item_prefix.data(), (size_t)(nt + 1) * 8);
-  std::memcpy(c->S->h_stage.p + o_rp, run_prefix.data(), (size_t)(nt + 1) * 8);
-  std::memcpy(c->S->h_stage.p + o_mp, merge_prefix.data(), (size_t)(nq + 1) * 8);
-  std::memcpy(c->S->h_stage.p + o_m, G.qmap.data(), (size_t)nq * 4);
-  HIP_TRY(stage_h2d(c, st.used, stream));
+  const auto r_q = st.add<DevQuery>((size_t)nq);
+  const auto r_t = st.add<DevTerm>((size_t)nt);
+  const auto r_ip = st.add<int64_t>((size_t)nt + 1), r_rp = st.add<int64_t>((size_t)nt + 1);
+  const auto r_mp = st.add<int64_t>((size_t)nq + 1);
+  const auto r_m = st.add<int32_t>((size_t)nq);
+  STAGE_SIZED(sg, st);
+  sg.put(r_q, G.queries);
+  sg.put(r_t, G.terms);
+  sg.put(r_ip, item_prefix);
+  sg.put(r_rp, run_prefix);
+  sg.put(r_mp, merge_prefix);
+  sg.put(r_m, G.qmap);
+  RGPU_TRY(sg.upload(stream));
   // the scored runs: the slot's own buffer (the group then only marks its slot, like a TERM / AND group), or — a group whose runs
   // would pin gigabytes in every slot — the context's, with a stream sync at the end
   const bool own_runs = (size_t)postings + 64 <= RUNS_PER_SLOT_MAX;
@@ -2017,12 +2017,10 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
   HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, (size_t)nq * 8, stream));
   HIP_TRY(c->S->d_partial_keys.reserve((size_t)items2 * (size_t)k, 0, stream));
   HIP_TRY(c->S->d_partial_counts.reserve((size_t)items2, 0, stream));
-  const DevQuery* dq = reinterpret_cast<const DevQuery*>(c->S->d_stage.p + o_q);
-  const DevTerm* dt = reinterpret_cast<const DevTerm*>(c->S->d_stage.p + o_t);
-  const int64_t* dip = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_ip);
-  const int64_t* drp = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_rp);
-  const int64_t* dmp = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_mp);
-  const int32_t* dm = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_m);
+  const DevQuery* dq = sg.dev(r_q);
+  const DevTerm* dt = sg.dev(r_t);
+  const int64_t *dip = sg.dev(r_ip), *drp = sg.dev(r_rp), *dmp = sg.dev(r_mp);
+  const int32_t* dm = sg.dev(r_m);
   const SegView sv = seg_view(seg);
   {
     TimedLaunch tl(c, stream, "k_score_terms", G.postings);
@@ -2279,49 +2277,46 @@ static int32_t search_or_lazy_group(rgpu_segment* seg, Group& G, int32_t k, HitO
     std::vector<int32_t> qmap((size_t)nq);
     for (int q = 0; q < nq; ++q) qmap[(size_t)q] = G.qmap[(size_t)lq_of[(size_t)q]];
     Stager st(c);
-    const size_t o_q = st.add((size_t)nq * sizeof(LazyQuery));
-    const size_t o_r = st.add(std::max<size_t>(1, run_of.size()) * sizeof(LazyRun));
-    const size_t o_t = st.add(std::max<size_t>(1, uniq.size()) * sizeof(DevTerm));
-    const size_t o_ip = st.add((size_t)(nu + 1) * 8);
-    const size_t o_rp = st.add((size_t)(nu + 1) * 8);
-    const size_t o_l = st.add(lz.size() * sizeof(LazyClause));
-    const size_t o_mp = st.add((size_t)(nq + 1) * 8);
-    const size_t o_m = st.add((size_t)nq * 4);
-    const size_t o_fi = st.add((size_t)nq * 8);
-    const size_t o_fl = st.add((size_t)nq * 4);   // low flags (k_merge_items)
-    const size_t o_bl = st.add((size_t)nq * 4);   // bail flags (k_or_lazy)
-    const size_t o_ct = st.add(16 + (size_t)nq * 16);  // (+ per query, variant builds: evaluated docs, lazy-only docs)
-    const size_t o_sn = st.add(64 * sizeof(ScoredPosting));
-    HIP_TRY(c->S->h_stage.reserve(st.used));
-    HIP_TRY(c->S->d_stage.reserve(st.used, 0, stream));
-    std::memset(c->S->h_stage.p + o_fl, 0, st.used - o_fl);
-    std::memcpy(c->S->h_stage.p + o_q, lq.data(), (size_t)nq * sizeof(LazyQuery));
-    if (!run_of.empty()) std::memcpy(c->S->h_stage.p + o_r, run_of.data(), run_of.size() * sizeof(LazyRun));
-    if (!uniq.empty()) std::memcpy(c->S->h_stage.p + o_t, uniq.data(), uniq.size() * sizeof(DevTerm));
-    std::memcpy(c->S->h_stage.p + o_ip, item_prefix.data(), (size_t)(nu + 1) * 8);
-    std::memcpy(c->S->h_stage.p + o_rp, run_prefix.data(), (size_t)(nu + 1) * 8);
-    std::memcpy(c->S->h_stage.p + o_l, lz.data(), lz.size() * sizeof(LazyClause));
-    std::memcpy(c->S->h_stage.p + o_mp, merge_prefix.data(), (size_t)(nq + 1) * 8);
-    std::memcpy(c->S->h_stage.p + o_m, qmap.data(), (size_t)nq * 4);
-    std::memcpy(c->S->h_stage.p + o_fi, fixed_info.data(), (size_t)nq * 8);
-    for (int i = 0; i < 64; ++i) reinterpret_cast<ScoredPosting*>(c->S->h_stage.p + o_sn)[i] = ScoredPosting{0x7fffffff, 0.0f};
+    const auto r_q = st.add<LazyQuery>((size_t)nq);
+    const auto r_r = st.add<LazyRun>(std::max<size_t>(1, run_of.size()));
+    const auto r_t = st.add<DevTerm>(std::max<size_t>(1, uniq.size()));
+    const auto r_ip = st.add<int64_t>((size_t)nu + 1), r_rp = st.add<int64_t>((size_t)nu + 1);
+    const auto r_l = st.add<LazyClause>(lz.size());
+    const auto r_mp = st.add<int64_t>((size_t)nq + 1);
+    const auto r_m = st.add<int32_t>((size_t)nq);
+    const auto r_fi = st.add<int32_t>((size_t)nq * 2);  // {exponent, floor} per query: an int2 on the device
+    const auto r_fl = st.add<int32_t>((size_t)nq), r_bl = st.add<int32_t>((size_t)nq);  // low flags (k_merge_items), bail flags (k_or_lazy)
+    const auto r_ct = st.add<unsigned long long>(2 + (size_t)nq * 2);  // (+ per query, variant builds: evaluated docs, lazy-only docs)
+    const auto r_sn = st.add<ScoredPosting>(64);
+    STAGE_SIZED(sg, st);
+    sg.fill(st.from(r_fl), 0);
+    sg.put(r_q, lq);
+    sg.put(r_r, run_of);
+    sg.put(r_t, uniq);
+    sg.put(r_ip, item_prefix);
+    sg.put(r_rp, run_prefix);
+    sg.put(r_l, lz);
+    sg.put(r_mp, merge_prefix);
+    sg.put(r_m, qmap);
+    sg.put(r_fi, fixed_info);
+    for (int i = 0; i < 64; ++i) sg.host(r_sn)[i] = ScoredPosting{0x7fffffff, 0.0f};
     HOST_STAMP(h2);
-    HIP_TRY(stage_h2d(c, st.used, stream));
+    RGPU_TRY(sg.upload(stream));
     const bool own_runs = (size_t)run_slots + 128 <= RUNS_PER_SLOT_MAX;
     DevVec<ScoredPosting>& runs_buf = own_runs ? c->S->d_runs : c->d_runs;
     HIP_TRY(runs_buf.reserve((size_t)run_slots + 128, 0, stream));
     // 64 sentinel entries behind the runs: what a clause slot without a clause looks at
-    HIP_TRY(hipMemcpyAsync(runs_buf.p + run_slots, c->S->d_stage.p + o_sn, 64 * sizeof(ScoredPosting), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(runs_buf.p + run_slots, sg.dev(r_sn), 64 * sizeof(ScoredPosting), hipMemcpyDeviceToDevice, stream));
     // per query: the shared threshold slot, then the histogram of finished totals (LZ_HIST u32 counters)
     HIP_TRY(c->S->d_tau.reserve((size_t)nq * (1 + LZ_HIST / 2), 0, stream));
     HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, (size_t)nq * (1 + LZ_HIST / 2) * 8, stream));
     uint32_t* d_hist = reinterpret_cast<uint32_t*>(c->S->d_tau.p + nq);
     HIP_TRY(c->S->d_partial_keys.reserve((size_t)lists * (size_t)k, 0, stream));
     HIP_TRY(c->S->d_partial_counts.reserve((size_t)lists, 0, stream));
-    const int64_t* dmp = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_mp);
-    const int32_t* dm = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_m);
-    int32_t* dbl = reinterpret_cast<int32_t*>(c->S->d_stage.p + o_bl);
-    unsigned long long* dct = reinterpret_cast<unsigned long long*>(c->S->d_stage.p + o_ct);
+    const int64_t* dmp = sg.dev(r_mp);
+    const int32_t* dm = sg.dev(r_m);
+    int32_t* dbl = sg.dev(r_bl);
+    unsigned long long* dct = sg.dev(r_ct);
     const SegView sv = seg_view(seg);
     c->last_counted = nullptr;
     c->last_counted_op = RGPU_OP_OR;
@@ -2332,9 +2327,8 @@ static int32_t search_or_lazy_group(rgpu_segment* seg, Group& G, int32_t k, HitO
     if (nu > 0) {
       TimedLaunch tl(c, stream, "k_score_terms", walked_postings);
       const unsigned grid = wg_count((items1 + WG_WAVES - 1) / WG_WAVES);
-      const DevTerm* dt = reinterpret_cast<const DevTerm*>(c->S->d_stage.p + o_t);
-      const int64_t* dip = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_ip);
-      const int64_t* drp = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_rp);
+      const DevTerm* dt = sg.dev(r_t);
+      const int64_t *dip = sg.dev(r_ip), *drp = sg.dev(r_rp);
       if (legacy)
         RGPU_LAUNCH(k_score_terms<true>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, dt, dip, drp, nu, items1, blocks_per_item, runs_buf.p);
       else
@@ -2349,9 +2343,7 @@ static int32_t search_or_lazy_group(rgpu_segment* seg, Group& G, int32_t k, HitO
         auto go = [&](auto kern) -> hipError_t {
           hipError_t e = set_dynamic_lds_once(c, reinterpret_cast<const void*>(kern), lds);
           if (e != hipSuccess) return e;
-          RGPU_LAUNCH(kern, dim3(grid), dim3(LZ_THREADS), lds, stream, sv, reinterpret_cast<const LazyQuery*>(c->S->d_stage.p + o_q),
-                             reinterpret_cast<const LazyRun*>(c->S->d_stage.p + o_r), runs_buf.p, reinterpret_cast<const LazyClause*>(c->S->d_stage.p + o_l),
-                             (int64_t)run_slots, nq, wpq, wpi, ipq, g0, C, (int)k, c->S->d_partial_keys.p, c->S->d_partial_counts.p, c->S->d_tau.p, dbl, dct, d_hist);
+          RGPU_LAUNCH(kern, dim3(grid), dim3(LZ_THREADS), lds, stream, sv, sg.dev(r_q), sg.dev(r_r), runs_buf.p, sg.dev(r_l), (int64_t)run_slots, nq, wpq, wpi, ipq, g0, C, (int)k, c->S->d_partial_keys.p, c->S->d_partial_counts.p, c->S->d_tau.p, dbl, dct, d_hist);
           return hipSuccess;
         };
         return wide ? go(k_or_lazy<true, STEPS>) : go(k_or_lazy<false, STEPS>);
@@ -2371,8 +2363,8 @@ static int32_t search_or_lazy_group(rgpu_segment* seg, Group& G, int32_t k, HitO
         HIP_TRY(launch_part(0, ipq));
       }
     }
-    const int2* dfi = reinterpret_cast<const int2*>(c->S->d_stage.p + o_fi);
-    int32_t* dfl = reinterpret_cast<int32_t*>(c->S->d_stage.p + o_fl);
+    const int2* dfi = reinterpret_cast<const int2*>(sg.dev(r_fi));
+    int32_t* dfl = sg.dev(r_fl);
     // many lists per query, few queries: fold them sixteen at a time first. (Not for the usual large batch — 64 lists per query:
     // measured there, k_premerge_items 0.078 + k_merge_items 0.055 ms against 0.109 for k_merge_items alone)
     if (ipq >= 256 && (int64_t)nq * ipq <= 262144) {
@@ -2558,29 +2550,28 @@ static int32_t search_or_wide_group(rgpu_segment* seg, Group& G, int32_t k, HitO
   for (int q = 0; q <= nq; ++q) merge_prefix[(size_t)q] = (int64_t)q * ipq * ORX_WAVES;
 
   Stager st(c);
-  const size_t o_q = st.add((size_t)nq * sizeof(DevQuery));
-  const size_t o_t = st.add((size_t)nt * sizeof(DevTerm));
-  const size_t o_mp = st.add((size_t)(nq + 1) * 8);
-  const size_t o_m = st.add((size_t)nq * 4);
-  const size_t o_fi = st.add((size_t)nq * 8);
-  const size_t o_fl = st.add((size_t)nq * 4);  // written by k_merge_items, read back below
-  HIP_TRY(c->S->h_stage.reserve(st.used));
-  HIP_TRY(c->S->d_stage.reserve(st.used, 0, stream));
-  std::memcpy(c->S->h_stage.p + o_q, G.queries.data(), (size_t)nq * sizeof(DevQuery));
-  std::memcpy(c->S->h_stage.p + o_t, G.terms.data(), (size_t)nt * sizeof(DevTerm));
-  std::memcpy(c->S->h_stage.p + o_mp, merge_prefix.data(), (size_t)(nq + 1) * 8);
-  std::memcpy(c->S->h_stage.p + o_m, G.qmap.data(), (size_t)nq * 4);
-  std::memcpy(c->S->h_stage.p + o_fi, fixed_info.data(), (size_t)nq * 8);
-  std::memset(c->S->h_stage.p + o_fl, 0, (size_t)nq * 4);
-  HIP_TRY(stage_h2d(c, st.used, stream));
+  const auto r_q = st.add<DevQuery>((size_t)nq);
+  const auto r_t = st.add<DevTerm>((size_t)nt);
+  const auto r_mp = st.add<int64_t>((size_t)nq + 1);
+  const auto r_m = st.add<int32_t>((size_t)nq);
+  const auto r_fi = st.add<int32_t>((size_t)nq * 2);  // {exponent, floor} per query: an int2 on the device
+  const auto r_fl = st.add<int32_t>((size_t)nq);       // written by k_merge_items, read back below
+  STAGE_SIZED(sg, st);
+  sg.put(r_q, G.queries);
+  sg.put(r_t, G.terms);
+  sg.put(r_mp, merge_prefix);
+  sg.put(r_m, G.qmap);
+  sg.put(r_fi, fixed_info);
+  sg.fill(r_fl, 0);
+  RGPU_TRY(sg.upload(stream));
   HIP_TRY(c->S->d_tau.reserve((size_t)nq, 0, stream));
   HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, (size_t)nq * 8, stream));
   HIP_TRY(c->S->d_partial_keys.reserve((size_t)lists * (size_t)k, 0, stream));
   HIP_TRY(c->S->d_partial_counts.reserve((size_t)lists, 0, stream));
-  const DevQuery* dq = reinterpret_cast<const DevQuery*>(c->S->d_stage.p + o_q);
-  const DevTerm* dt = reinterpret_cast<const DevTerm*>(c->S->d_stage.p + o_t);
-  const int64_t* dmp = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_mp);
-  const int32_t* dm = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_m);
+  const DevQuery* dq = sg.dev(r_q);
+  const DevTerm* dt = sg.dev(r_t);
+  const int64_t* dmp = sg.dev(r_mp);
+  const int32_t* dm = sg.dev(r_m);
   const SegView sv = seg_view(seg);
   c->last_counted = nullptr;  // nothing to read back: the wide kernel decodes every posting of every clause
   c->last_counted_op = RGPU_OP_OR;
@@ -2610,8 +2601,8 @@ static int32_t search_or_wide_group(rgpu_segment* seg, Group& G, int32_t k, HitO
     if (legacy) HIP_TRY(wide ? go(k_or_wide<true, true>) : go(k_or_wide<true, false>));
     else HIP_TRY(wide ? go(k_or_wide<false, true>) : go(k_or_wide<false, false>));
   }
-  const int2* dfi = reinterpret_cast<const int2*>(c->S->d_stage.p + o_fi);
-  int32_t* dfl = reinterpret_cast<int32_t*>(c->S->d_stage.p + o_fl);
+  const int2* dfi = reinterpret_cast<const int2*>(sg.dev(r_fi));
+  int32_t* dfl = sg.dev(r_fl);
   if (wide) launch_merge<true>(c, stream, nq, k, dmp, seg->doc_base, hits_dev, totals_dev, 0, dfi, dfl, dm);
   else launch_merge<false>(c, stream, nq, k, dmp, seg->doc_base, hits_dev, totals_dev, 0, dfi, dfl, dm);
   HIP_TRY(launch_status());
@@ -3248,15 +3239,15 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
     }
     // plan + thresholds in one staged copy; the merge writes the caller's rows in place (qmap)
     Stager st(c);
-    const size_t o_q = st.add((size_t)nq * sizeof(DevQuery));
-    const size_t o_t = st.add(std::max<size_t>(1, G.terms.size()) * sizeof(DevTerm));
-    const size_t o_p = st.add((size_t)(nq + 1) * 8);
-    const size_t o_m = st.add((size_t)nq * 4);
-    const size_t o_tau = st.add((size_t)nq * 8);  // the per-query shared thresholds: zeroed by the same copy that brings the plan
+    const auto r_q = st.add<DevQuery>((size_t)nq);
+    const auto r_t = st.add<DevTerm>(std::max<size_t>(1, G.terms.size()));
+    const auto r_p = st.add<int64_t>((size_t)nq + 1);
+    const auto r_m = st.add<int32_t>((size_t)nq);
+    const auto r_tau = st.add<unsigned long long>((size_t)nq);  // the per-query shared thresholds: zeroed by the same copy that brings the plan
     const bool term_fold = op == RGPU_OP_TERM && c->term_fold && !G.req_opt;  // k_search_term folds the item lists itself (TermMerge)
-    const size_t o_done = term_fold ? st.add((size_t)nq * 4) : 0;             // ... counting every query's finished items here
+    const auto r_done = st.add_if<unsigned int>(term_fold, (size_t)nq);       // ... counting every query's finished items here
     // ReqOptScorer's rule: one record per lead posting, query after query
-    const size_t o_sp = G.req_opt ? st.add((size_t)(nq + 1) * 8) : 0;
+    const auto r_sp = st.add_if<int64_t>(G.req_opt, (size_t)nq + 1);
     // conjunctions: the doc bitmaps of the clauses behind the lead (parallel to the DevTerm array)
     std::vector<TermBitmap> clause_bitmaps;
     if (op == RGPU_OP_AND && c->cfg.and_bitmaps >= 0 && (seg->bitmaps.size() > 0 || seg->memb_only.size() > 0)) {
@@ -3287,8 +3278,8 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       }
       if (!any) clause_bitmaps.clear();
     }
-    const size_t o_bm = clause_bitmaps.empty() ? 0 : st.add(clause_bitmaps.size() * sizeof(TermBitmap));
-    const size_t o_id = op == RGPU_OP_TERM ? st.add((size_t)items * sizeof(int4)) : 0;  // k_search_term's item descriptors
+    const auto r_bm = st.add_if<TermBitmap>(!clause_bitmaps.empty(), clause_bitmaps.size());
+    const auto r_id = st.add_if<int4>(op == RGPU_OP_TERM, (size_t)items);  // k_search_term's item descriptors
     std::vector<int64_t> seq_prefix;
     if (G.req_opt) {
       seq_prefix.assign((size_t)nq + 1, 0);
@@ -3297,21 +3288,20 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
         seq_prefix[(size_t)q + 1] = seq_prefix[(size_t)q] + (dq0.n_terms >= 1 ? (int64_t)G.terms[(size_t)dq0.first_term].df : 0);
       }
     }
-    HIP_TRY(c->S->h_stage.reserve(st.used));
-    HIP_TRY(c->S->d_stage.reserve(st.used, 0, stream));
-    std::memcpy(c->S->h_stage.p + o_q, G.queries.data(), (size_t)nq * sizeof(DevQuery));
-    if (!G.terms.empty()) std::memcpy(c->S->h_stage.p + o_t, G.terms.data(), G.terms.size() * sizeof(DevTerm));
-    std::memcpy(c->S->h_stage.p + o_p, G.item_prefix.data(), (size_t)(nq + 1) * 8);
-    std::memcpy(c->S->h_stage.p + o_m, G.qmap.data(), (size_t)nq * 4);
-    std::memset(c->S->h_stage.p + o_tau, 0, (size_t)nq * 8);
-    if (term_fold) std::memset(c->S->h_stage.p + o_done, 0, (size_t)nq * 4);
-    if (G.req_opt) std::memcpy(c->S->h_stage.p + o_sp, seq_prefix.data(), (size_t)(nq + 1) * 8);
-    if (!clause_bitmaps.empty()) std::memcpy(c->S->h_stage.p + o_bm, clause_bitmaps.data(), clause_bitmaps.size() * sizeof(TermBitmap));
-    if (op == RGPU_OP_TERM) fill_term_item_desc(reinterpret_cast<int4*>(c->S->h_stage.p + o_id), G.queries.data(), G.terms.data(), G.item_prefix.data(), nq, blocks_per_item, term_split, c->term_min_item_blocks);
-    HIP_TRY(stage_h2d(c, st.used, stream));
+    STAGE_SIZED(sg, st);
+    sg.put(r_q, G.queries);
+    sg.put(r_t, G.terms);
+    sg.put(r_p, G.item_prefix);
+    sg.put(r_m, G.qmap);
+    sg.fill(r_tau, 0);
+    sg.fill(r_done, 0);
+    sg.put(r_sp, seq_prefix);  // (empty without req_opt, as the region is)
+    sg.put(r_bm, clause_bitmaps);
+    if (op == RGPU_OP_TERM) fill_term_item_desc(sg.host(r_id), G.queries.data(), G.terms.data(), G.item_prefix.data(), nq, blocks_per_item, term_split, c->term_min_item_blocks);
+    RGPU_TRY(sg.upload(stream));
     HIP_TRY(c->S->d_partial_keys.reserve((size_t)items * (size_t)k, 0, stream));
     HIP_TRY(c->S->d_partial_counts.reserve((size_t)items, 0, stream));
-    unsigned long long* d_tau = reinterpret_cast<unsigned long long*>(c->S->d_stage.p + o_tau);
+    unsigned long long* d_tau = sg.dev(r_tau);
 #ifdef RGPU_EXP_KEEP_TAU  // developer experiment (variant builds only): a launch starts from the thresholds the previous launch of
     {                     // the SAME batch ended with — what the kernel costs when every item knows its query's final k-th key
       static unsigned long long* keep = nullptr;
@@ -3319,10 +3309,10 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       if ((size_t)nq * 8 <= ((size_t)1 << 20)) d_tau = keep;
     }
 #endif
-    const DevQuery* dq = reinterpret_cast<const DevQuery*>(c->S->d_stage.p + o_q);
-    const DevTerm* dt = reinterpret_cast<const DevTerm*>(c->S->d_stage.p + o_t);
-    const int64_t* dp = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_p);
-    const int32_t* dm = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_m);
+    const DevQuery* dq = sg.dev(r_q);
+    const DevTerm* dt = sg.dev(r_t);
+    const int64_t* dp = sg.dev(r_p);
+    const int32_t* dm = sg.dev(r_m);
     const SegView sv = seg_view(seg);
     if (op == RGPU_OP_AND) {
       HIP_TRY(c->S->d_touched.reserve((size_t)nq * 2, 0, stream));
@@ -3345,14 +3335,14 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       if (G.req_opt) {  // records instead of a collector (in the slot's own run buffer: the group only marks its slot)
         static_assert(sizeof(SeqRec) == 2 * sizeof(ScoredPosting), "SeqRec records are laid over the run scratch");
         HIP_TRY(c->S->d_runs.reserve((size_t)seq_prefix[(size_t)nq] * 2 + 64, 0, stream));  // (a group's records stay under 1 GiB: req_opt_records)
-        d_sp = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_sp);
+        d_sp = sg.dev(r_sp);
         d_seq = c->S->d_runs.p;
       }
       auto go = [&](auto kern) {
         RGPU_LAUNCH(kern, dim3(grid), dim3(AND_WG_THREADS), 0, stream, sv, dq, dt, dp, nq, items, blocks_per_item, (int)k,
                            c->S->d_partial_keys.p, c->S->d_partial_counts.p, d_tau, c->S->d_touched.p,
                            d_sp, (unsigned long long*)nullptr, d_seq, c->pass.ceil_in, dm,
-                           clause_bitmaps.empty() ? (const TermBitmap*)nullptr : reinterpret_cast<const TermBitmap*>(c->S->d_stage.p + o_bm), xcd_chunk);
+                           clause_bitmaps.empty() ? (const TermBitmap*)nullptr : sg.dev(r_bm), xcd_chunk);
       };
       bool has_not = false, has_opt = false;
       for (const DevQuery& q : G.queries) { has_not = has_not || q.pad != 0; has_opt = has_opt || ((q.op >> 16) & 0xff) != 0; }
@@ -3380,7 +3370,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       c->last_counted_dir_blocks = 0;
       c->last_counted_loose = 0;
       for (const DevTerm& t0 : G.terms) { c->last_counted_dir_blocks += t0.nblocks; c->last_counted_loose += t0.df == 1 ? 1 : t0.tail_n; }
-      const TermMerge fold = term_fold ? TermMerge{reinterpret_cast<unsigned int*>(c->S->d_stage.p + o_done), dp, hits_dev, totals_dev, c->pass.ceil_out,
+      const TermMerge fold = term_fold ? TermMerge{sg.dev(r_done), dp, hits_dev, totals_dev, c->pass.ceil_out,
                                                    seg->doc_base, c->pass.stride, c->pass.col0}
                                        : TermMerge{};
       TimedLaunch tl(c, stream, "k_search_term", G.postings);
@@ -3389,7 +3379,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       auto go = [&](auto kern) -> hipError_t {
         hipError_t e = set_dynamic_lds_once(c, reinterpret_cast<const void*>(kern), lds);
         if (e != hipSuccess) return e;
-        RGPU_LAUNCH(kern, dim3(grid), dim3(TERM_THREADS), lds, stream, sv, dq, dt, reinterpret_cast<const int4*>(c->S->d_stage.p + o_id), nq, items,
+        RGPU_LAUNCH(kern, dim3(grid), dim3(TERM_THREADS), lds, stream, sv, dq, dt, sg.dev(r_id), nq, items,
                            blocks_per_item, (int)k, c->S->d_partial_keys.p, c->S->d_partial_counts.p, d_tau, c->S->d_touched.p, c->pass.ceil_in, dm, fold);
         return hipSuccess;
       };
@@ -3402,7 +3392,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
       TimedLaunch tl(c, stream, "k_req_opt_scan", G.postings);
       const unsigned grid = wg_count((nq + WG_WAVES - 1) / WG_WAVES);
       const SeqRec* d_seq = reinterpret_cast<const SeqRec*>(c->S->d_runs.p);
-      const int64_t* d_sp = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_sp);
+      const int64_t* d_sp = sg.dev(r_sp);
       if (wide) RGPU_LAUNCH(k_req_opt_scan<true>, dim3(grid), dim3(WG_THREADS), 0, stream, d_seq, d_sp, nq, (int)k, seg->doc_base, dm, hits_dev, totals_dev,
                                    c->pass.stride, c->pass.col0, c->pass.ceil_in, c->pass.ceil_out);
       else RGPU_LAUNCH(k_req_opt_scan<false>, dim3(grid), dim3(WG_THREADS), 0, stream, d_seq, d_sp, nq, (int)k, seg->doc_base, dm, hits_dev, totals_dev,
@@ -3551,6 +3541,16 @@ extern "C" int32_t rgpu_segment_attach_payloads(rgpu_segment* seg, const uint8_t
 }
 
 // BlockPostingIterator::{next, next_position} to exhaustion for every given term (kernels/decode_positions.hpp): ends synchronised
+// where a term's positions lie in .pos (a phrase's planner adds phrase_pos / query_ord / same_as: emit_phrase)
+static PosTerm pos_term_of(const rgpu_term_state& st, const rgpu_term_positions& pos) {
+  PosTerm p{};
+  p.pos_start_fp = (uint64_t)pos.pos_start_fp;
+  p.total_term_freq = st.total_term_freq;
+  // posting_reader.rs:1195-1203: fewer than 128 positions -> all VInts; exactly 128 -> one packed block, no trailing one
+  p.last_pos_block_fp = st.total_term_freq < 128 ? pos.pos_start_fp : (st.total_term_freq == 128 ? -1 : pos.pos_start_fp + pos.last_pos_block_offset);
+  return p;
+}
+
 static int32_t decode_positions_impl(rgpu_segment* seg, const rgpu_term_state* terms, const rgpu_term_positions* positions, int64_t n_terms,
                                      int32_t* positions_dev, hipStream_t stream) {
   rgpu_ctx* c = seg->ctx;
@@ -3568,8 +3568,7 @@ static int32_t decode_positions_impl(rgpu_segment* seg, const rgpu_term_state* t
   }
   if (expect == 0) return RGPU_OK;
   if (expect > 0xfffffff0ll) return fail(RGPU_ERR_UNSUPPORTED, "one call decodes at most 2^32 positions: split the term list");
-  int32_t rc = prepare_terms_locked(seg, ptrs.data(), ptrs.size(), false);  // stage A: directory (with dir_pos), block store, tails
-  if (rc != RGPU_OK) return rc;
+  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size(), false));  // stage A: directory (with dir_pos), block store, tails
   std::vector<DevTerm> dt;
   std::vector<PosTerm> pt;
   std::vector<int64_t> item_prefix;
@@ -3578,16 +3577,9 @@ static int32_t decode_positions_impl(rgpu_segment* seg, const rgpu_term_state* t
     const rgpu_term_state& st = terms[i];
     if (st.doc_freq == 0) continue;
     DevTerm d;
-    rc = make_dev_term(seg, st, 0.f, 0, &d, false);
-    if (rc != RGPU_OK) return rc;
-    PosTerm p{};
-    p.pos_start_fp = (uint64_t)positions[i].pos_start_fp;
-    p.total_term_freq = st.total_term_freq;
-    // posting_reader.rs:1195-1203: fewer than 128 positions -> all VInts; exactly 128 -> one packed block, no trailing one
-    p.last_pos_block_fp = st.total_term_freq < 128 ? positions[i].pos_start_fp
-                          : (st.total_term_freq == 128 ? -1 : positions[i].pos_start_fp + positions[i].last_pos_block_offset);
+    RGPU_TRY(make_dev_term(seg, st, 0.f, 0, &d, false));
     dt.push_back(d);
-    pt.push_back(p);
+    pt.push_back(pos_term_of(st, positions[i]));
     item_prefix.push_back(items);
     items += (int64_t)d.nblocks + ((d.df == 1 || d.tail_n > 0) ? 1 : 0);
   }
@@ -3595,22 +3587,21 @@ static int32_t decode_positions_impl(rgpu_segment* seg, const rgpu_term_state* t
   const int nt = (int)dt.size();
   SCRATCH_TAKE(c);
   Stager st(c);
-  const size_t o_t = st.add(dt.size() * sizeof(DevTerm));
-  const size_t o_pt = st.add(pt.size() * sizeof(PosTerm));
-  const size_t o_ip = st.add(item_prefix.size() * 8);
-  HIP_TRY(c->S->h_stage.reserve(st.used));
-  HIP_TRY(c->S->d_stage.reserve(st.used, 0, stream));
-  std::memcpy(c->S->h_stage.p + o_t, dt.data(), dt.size() * sizeof(DevTerm));
-  std::memcpy(c->S->h_stage.p + o_pt, pt.data(), pt.size() * sizeof(PosTerm));
-  std::memcpy(c->S->h_stage.p + o_ip, item_prefix.data(), item_prefix.size() * 8);
-  HIP_TRY(stage_h2d(c, st.used, stream));
+  const auto r_t = st.add<DevTerm>(dt.size());
+  const auto r_pt = st.add<PosTerm>(pt.size());
+  const auto r_ip = st.add<int64_t>(item_prefix.size());
+  STAGE_SIZED(sg, st);
+  sg.put(r_t, dt);
+  sg.put(r_pt, pt);
+  sg.put(r_ip, item_prefix);
+  RGPU_TRY(sg.upload(stream));
   const int64_t n_tiles = (items + SCAN_TILE - 1) / SCAN_TILE;
   HIP_TRY(c->pos_counts.reserve((size_t)items + 64, 0, stream));
   HIP_TRY(c->pos_tiles.reserve((size_t)n_tiles + 8, 0, stream));
   HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));
-  const DevTerm* d_t = reinterpret_cast<const DevTerm*>(c->S->d_stage.p + o_t);
-  const PosTerm* d_pt = reinterpret_cast<const PosTerm*>(c->S->d_stage.p + o_pt);
-  const int64_t* d_ip = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_ip);
+  const DevTerm* d_t = sg.dev(r_t);
+  const PosTerm* d_pt = sg.dev(r_pt);
+  const int64_t* d_ip = sg.dev(r_ip);
   unsigned long long* d_tiles = c->pos_tiles.p + 8;
   unsigned long long* d_total = c->pos_tiles.p + 1;
   const SegView sv = seg_view(seg);
@@ -3785,8 +3776,7 @@ static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const P
     redo = two[1];
     return RGPU_OK;
   };
-  int32_t rc = redo_bits();
-  if (rc != RGPU_OK) return rc;
+  RGPU_TRY(redo_bits());
   // the one-candidate kernels over the listed slots (or, should the list have overflowed, over every slot)
   const bool by_list = !legacy && (int64_t)listed <= a.redo_cap;
   const int64_t* const left = by_list ? (const int64_t*)c->phrase_redo.p : all_slots;
@@ -3801,10 +3791,7 @@ static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const P
     TimedLaunch tl(c, stream, "k_sloppy_match(left by the 64-candidate kernel)", 0);  // (the groups are there: computed in front of the 64-candidate kernels)
     sloppy(k_sloppy_match<false, SLOPPY_SMALL_POOL, true>, left, n_left);
   }
-  if (redo & (PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES)) {
-    rc = redo_bits();
-    if (rc != RGPU_OK) return rc;
-  }
+  if (redo & (PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES)) RGPU_TRY(redo_bits());
   if (redo & PHRASE_REDO_WIDE) {
     TimedLaunch tl(c, stream, "k_phrase_match(wide lists)", 0);
     if (legacy) exact(k_phrase_match<true, PHRASE_LIST_CAP, true>, left, n_left); else exact(k_phrase_match<false, PHRASE_LIST_CAP, true>, left, n_left);
@@ -3814,6 +3801,63 @@ static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const P
     if (legacy) sloppy(k_sloppy_match<true, SLOPPY_POOL, true>, left, n_left); else sloppy(k_sloppy_match<false, SLOPPY_POOL, true>, left, n_left);
   }
   return RGPU_OK;
+}
+
+// ---- the plan in front of it, shared by the phrase search and the phrase rescoring -----------------------------------------------
+// Term equality: how PosTerm::same_as tells repeated terms (repeating_terms, phrase_scorer.rs:909-931)
+static bool same_term(const rgpu_term_state& a, const rgpu_term_state& b) {
+  return a.doc_start_fp == b.doc_start_fp && a.doc_freq == b.doc_freq && a.singleton_doc_id == b.singleton_doc_id && a.total_term_freq == b.total_term_freq;
+}
+// a query's own fields (`searching`: next_limit is looked at, a rescoring has no use for it) ...
+static int32_t check_phrase_query(const rgpu_ctx* c, const rgpu_phrase_query& Q, int32_t n_terms_total, bool searching) {
+  if (Q.n_terms < 2 || Q.n_terms > RGPU_MAX_PHRASE_TERMS) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a phrase has 2..RGPU_MAX_PHRASE_TERMS terms");
+  if (Q.slop < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "Slop must be >= 0");  // PhraseQuery::new (phrase_query.rs:77)
+  if (searching && Q.next_limit < RGPU_NEXT_LIMIT_ZERO) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "rgpu_phrase_query.next_limit: 0 (the searcher's default), n > 0, -1 (none) or RGPU_NEXT_LIMIT_ZERO");
+  if (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms > (int64_t)n_terms_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "term range outside terms[]");
+  if (Q.sim_table < 0 || Q.sim_table >= c->n_sim_tables) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
+  return RGPU_OK;
+}
+// ... and its terms: those the leaf holds go to `ptrs` for the preparation, the ones of a row with an absent term too
+static int32_t check_phrase_terms(const rgpu_segment* seg, const rgpu_phrase_query& Q, const rgpu_phrase_term* terms, std::vector<const rgpu_term_state*>* ptrs) {
+  for (int i = 0; i < Q.n_terms; ++i) {
+    const rgpu_phrase_term& t = terms[Q.first_term + i];
+    if (t.state.doc_freq <= 0) continue;
+    if (t.positions.pos_start_fp < 0 || (size_t)t.positions.pos_start_fp >= seg->pos_len) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "pos_start_fp outside the .pos file");
+    if (t.state.total_term_freq < t.state.doc_freq) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "total_term_freq below doc_freq");
+    ptrs->push_back(&t.state);
+  }
+  return RGPU_OK;
+}
+static bool phrase_is_dead(const rgpu_phrase_query& Q, const rgpu_phrase_term* terms) {  // a term absent from the leaf
+  for (int i = 0; i < Q.n_terms; ++i) if (terms[Q.first_term + i].state.doc_freq <= 0) return true;
+  return false;
+}
+// One query's clauses behind `dt` / `pt`, rarest term first: it drives the conjunction (conjunction_scorer.rs:30). *dead: nothing was
+// pushed, PhraseWeight::create_scorer -> None (phrase_query.rs:275-283) — no doc of this leaf matches.
+static int32_t emit_phrase(const rgpu_segment* seg, const rgpu_phrase_query& Q, const rgpu_phrase_term* terms, std::vector<DevTerm>* dt, std::vector<PosTerm>* pt, bool* dead) {
+  *dead = phrase_is_dead(Q, terms);
+  if (*dead) return RGPU_OK;
+  const rgpu_phrase_term* mine = terms + Q.first_term;
+  int order[RGPU_MAX_PHRASE_TERMS];
+  for (int i = 0; i < Q.n_terms; ++i) order[i] = i;
+  std::stable_sort(order, order + Q.n_terms, [&](int a, int b) { return mine[a].state.doc_freq < mine[b].state.doc_freq; });
+  for (int o = 0; o < Q.n_terms; ++o) {
+    const int i = order[o];
+    dt->emplace_back();
+    RGPU_TRY(make_dev_term(seg, mine[i].state, Q.weight, Q.sim_table, &dt->back()));
+    PosTerm p = pos_term_of(mine[i].state, mine[i].positions);
+    p.phrase_pos = mine[i].position;
+    p.query_ord = i;  // PhrasePositions::ord: the sloppy scorer keeps the query's order (phrase_query.rs:324-331 does not sort)
+    p.same_as = i;    // ... and tells repeated terms by Term equality
+    for (int j = 0; j < i; ++j) if (same_term(mine[j].state, mine[i].state)) { p.same_as = j; break; }
+    pt->push_back(p);
+  }
+  return RGPU_OK;
+}
+// what the match stage left in d_err[0], in the caller's words
+static int32_t phrase_match_status(int err, const char* held_too_often, const char* not_found_again) {
+  if (err == 0) return RGPU_OK;
+  return fail(err, err == RGPU_ERR_UNSUPPORTED ? held_too_often : (err == RGPU_ERR_ILLEGAL_STATE ? not_found_again : "corrupt position data in .pos"));
 }
 
 extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
@@ -3830,23 +3874,10 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
   // ---- validate, resolve, plan
   std::vector<const rgpu_term_state*> ptrs;
   for (int32_t q = 0; q < n_queries; ++q) {
-    const rgpu_phrase_query& Q = queries[q];
-    if (Q.n_terms < 2 || Q.n_terms > RGPU_MAX_PHRASE_TERMS) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a phrase has 2..RGPU_MAX_PHRASE_TERMS terms");
-    if (Q.slop < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "Slop must be >= 0");  // PhraseQuery::new (phrase_query.rs:77)
-    if (Q.next_limit < RGPU_NEXT_LIMIT_ZERO) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "rgpu_phrase_query.next_limit: 0 (the searcher's default), n > 0, -1 (none) or RGPU_NEXT_LIMIT_ZERO");
-    if (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms > (int64_t)n_terms_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "term range outside terms[]");
-    if (Q.sim_table < 0 || Q.sim_table >= c->n_sim_tables) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
-    for (int i = 0; i < Q.n_terms; ++i) {
-      const rgpu_phrase_term& t = terms[Q.first_term + i];
-      if (t.state.doc_freq > 0) {
-        if (t.positions.pos_start_fp < 0 || (size_t)t.positions.pos_start_fp >= seg->pos_len) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "pos_start_fp outside the .pos file");
-        if (t.state.total_term_freq < t.state.doc_freq) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "total_term_freq below doc_freq");
-        ptrs.push_back(&t.state);
-      }
-    }
+    RGPU_TRY(check_phrase_query(c, queries[q], n_terms_total, true));
+    RGPU_TRY(check_phrase_terms(seg, queries[q], terms, &ptrs));
   }
-  int32_t rc = prepare_terms_locked(seg, ptrs.data(), ptrs.size());
-  if (rc != RGPU_OK) return rc;
+  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
   // the conjunction that finds a phrase's candidates answers a dense clause from its doc bitmap, as a BooleanQuery's does
   const int64_t bitmap_df = (c->cfg.and_bitmaps >= 0 && c->n_sim_tables > 0) ? bitmap_min_df_and(seg) : INT64_MAX;
   if (bitmap_df != INT64_MAX) {
@@ -3860,7 +3891,7 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
         if (st.doc_freq >= bitmap_df && !seg->bitmaps.find(st.doc_start_fp)) { dense.push_back(&st); dense_sim.push_back(Q.sim_table); }
       }
     }
-    if (!dense.empty()) { rc = ensure_bitmaps_locked(seg, dense.data(), dense_sim.data(), dense.size()); if (rc != RGPU_OK) return rc; }
+    if (!dense.empty()) RGPU_TRY(ensure_bitmaps_locked(seg, dense.data(), dense_sim.data(), dense.size()));
   }
   std::vector<DevQuery> dq((size_t)n_queries);
   std::vector<DevTerm> dt;
@@ -3886,33 +3917,8 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
     collect_prefix[(size_t)q] = collect_items;
     dq[(size_t)q] = DevQuery{RGPU_OP_AND, 0, (int32_t)dt.size(), 0};
     bool dead = false;
-    for (int i = 0; i < Q.n_terms; ++i) dead = dead || terms[Q.first_term + i].state.doc_freq <= 0;
-    if (dead) continue;  // PhraseWeight::create_scorer -> None (phrase_query.rs:275-283)
-    std::vector<int> order((size_t)Q.n_terms);
-    for (int i = 0; i < Q.n_terms; ++i) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return terms[Q.first_term + a].state.doc_freq < terms[Q.first_term + b].state.doc_freq; });
-    for (int i : order) {  // the conjunction is driven by the rarest term (conjunction_scorer.rs:30)
-      const rgpu_phrase_term& t = terms[Q.first_term + i];
-      DevTerm d;
-      rc = make_dev_term(seg, t.state, Q.weight, Q.sim_table, &d);
-      if (rc != RGPU_OK) return rc;
-      dt.push_back(d);
-      PosTerm p{};
-      p.pos_start_fp = (uint64_t)t.positions.pos_start_fp;
-      p.total_term_freq = t.state.total_term_freq;
-      // posting_reader.rs:1195-1203: fewer than 128 positions -> all VInts; exactly 128 -> one packed block, no trailing one
-      p.last_pos_block_fp = t.state.total_term_freq < 128 ? t.positions.pos_start_fp
-                            : (t.state.total_term_freq == 128 ? -1 : t.positions.pos_start_fp + t.positions.last_pos_block_offset);
-      p.phrase_pos = t.position;
-      p.query_ord = i;  // PhrasePositions::ord: the sloppy scorer keeps the query's order (phrase_query.rs:324-331 does not sort)
-      p.same_as = i;    // ... and tells repeated terms by Term equality (repeating_terms, phrase_scorer.rs:909-931)
-      for (int j = 0; j < i; ++j) {
-        const rgpu_term_state& o = terms[Q.first_term + j].state;
-        if (o.doc_start_fp == t.state.doc_start_fp && o.doc_freq == t.state.doc_freq && o.singleton_doc_id == t.state.singleton_doc_id &&
-            o.total_term_freq == t.state.total_term_freq) { p.same_as = j; break; }
-      }
-      pt.push_back(p);
-    }
+    RGPU_TRY(emit_phrase(seg, Q, terms, &dt, &pt, &dead));
+    if (dead) continue;
     slops[(size_t)q] = Q.slop;
     limits[(size_t)q] = Q.next_limit == 0 ? 500000 /* searcher.rs:47 DEFAULT_DISMATCH_NEXT_LIMIT */
                                           : (Q.next_limit == RGPU_NEXT_LIMIT_ZERO ? 0 /* DefaultIndexSearcher::new(reader, Some(0)) */ : Q.next_limit);
@@ -3935,17 +3941,16 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
   if (items > 0) {
     SCRATCH_TAKE(c);
     Stager st(c);
-    const size_t o_q = st.add((size_t)n_queries * sizeof(DevQuery));
-    const size_t o_t = st.add(dt.size() * sizeof(DevTerm));
-    const size_t o_pt = st.add(pt.size() * sizeof(PosTerm));
-    const size_t o_ip = st.add((size_t)(n_queries + 1) * 8);
-    const size_t o_ep = st.add((size_t)(n_queries + 1) * 8);
-    const size_t o_sl = st.add((size_t)n_queries * 4);
-    const size_t o_nl = st.add((size_t)n_queries * 4);
-    const size_t o_gr = st.add((size_t)n_queries * sizeof(SloppyGroups));  // written by k_sloppy_groups
-    const size_t o_cp = st.add((size_t)(n_queries + 1) * 8);                // the chunked collector's items
-    const size_t o_ab = st.add((size_t)n_queries * 4);                      // k_phrase_cutoff's flags (zeroed by the copy)
-    const size_t o_cut = st.add((size_t)n_queries * sizeof(PhraseCut));     // ... and what its chunked form reduces into
+    const size_t nq = (size_t)n_queries;
+    const auto r_q = st.add<DevQuery>(nq);
+    const auto r_t = st.add<DevTerm>(dt.size());
+    const auto r_pt = st.add<PosTerm>(pt.size());
+    const auto r_ip = st.add<int64_t>(nq + 1), r_ep = st.add<int64_t>(nq + 1);
+    const auto r_sl = st.add<int32_t>(nq), r_nl = st.add<int32_t>(nq);
+    const auto r_gr = st.add<SloppyGroups>(nq);  // written by k_sloppy_groups
+    const auto r_cp = st.add<int64_t>(nq + 1);   // the chunked collector's items
+    const auto r_ab = st.add<int32_t>(nq);       // k_phrase_cutoff's flags (zeroed by the copy)
+    const auto r_cut = st.add<PhraseCut>(nq);    // ... and what its chunked form reduces into
     std::vector<TermBitmap> clause_bitmaps;  // parallel to dt: the clauses behind a query's lead that have a doc bitmap
     if (bitmap_df != INT64_MAX && seg->bitmaps.size() > 0) {
       bool any = false;
@@ -3962,24 +3967,23 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
       }
       if (!any) clause_bitmaps.clear();
     }
-    const size_t o_bm = clause_bitmaps.empty() ? 0 : st.add(clause_bitmaps.size() * sizeof(TermBitmap));
-    HIP_TRY(c->S->h_stage.reserve(st.used));
-    HIP_TRY(c->S->d_stage.reserve(st.used, 0, stream));
-    std::memcpy(c->S->h_stage.p + o_q, dq.data(), (size_t)n_queries * sizeof(DevQuery));
-    std::memcpy(c->S->h_stage.p + o_t, dt.data(), dt.size() * sizeof(DevTerm));
-    std::memcpy(c->S->h_stage.p + o_pt, pt.data(), pt.size() * sizeof(PosTerm));
-    std::memcpy(c->S->h_stage.p + o_sl, slops.data(), (size_t)n_queries * 4);
-    std::memcpy(c->S->h_stage.p + o_nl, limits.data(), (size_t)n_queries * 4);
-    std::memcpy(c->S->h_stage.p + o_ip, item_prefix.data(), (size_t)(n_queries + 1) * 8);
-    std::memcpy(c->S->h_stage.p + o_ep, emit_prefix.data(), (size_t)(n_queries + 1) * 8);
-    std::memcpy(c->S->h_stage.p + o_cp, collect_prefix.data(), (size_t)(n_queries + 1) * 8);
-    std::memset(c->S->h_stage.p + o_ab, 0, (size_t)n_queries * 4);
-    for (int32_t q = 0; q < n_queries; ++q) reinterpret_cast<PhraseCut*>(c->S->h_stage.p + o_cut)[q] = PhraseCut{0x7fffffff, 0x7fffffff, 0ull};
+    const auto r_bm = st.add_if<TermBitmap>(!clause_bitmaps.empty(), clause_bitmaps.size());
+    STAGE_SIZED(sg, st);
+    sg.put(r_q, dq);
+    sg.put(r_t, dt);
+    sg.put(r_pt, pt);
+    sg.put(r_sl, slops);
+    sg.put(r_nl, limits);
+    sg.put(r_ip, item_prefix);
+    sg.put(r_ep, emit_prefix);
+    sg.put(r_cp, collect_prefix);
+    sg.fill(r_ab, 0);
+    for (size_t q = 0; q < nq; ++q) sg.host(r_cut)[q] = PhraseCut{0x7fffffff, 0x7fffffff, 0ull};
     // "no repetition group" for every query (grp = -1): k_sloppy_groups only runs when some phrase repeats a term, k_sloppy_match
     // reads the region either way (the copy used to carry whatever the pinned buffer held)
-    std::memset(c->S->h_stage.p + o_gr, 0xff, (size_t)n_queries * sizeof(SloppyGroups));
-    if (!clause_bitmaps.empty()) std::memcpy(c->S->h_stage.p + o_bm, clause_bitmaps.data(), clause_bitmaps.size() * sizeof(TermBitmap));
-    HIP_TRY(stage_h2d(c, st.used, stream));
+    sg.fill(r_gr, 0xff);
+    sg.put(r_bm, clause_bitmaps);
+    RGPU_TRY(sg.upload(stream));
     HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
     HIP_TRY(c->phrase_keys.reserve((size_t)slots + 64, 0, stream));
     const int64_t redo_cap = phrase_redo_cap(slots);
@@ -3995,11 +3999,12 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
     HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, (size_t)n_queries * 8, stream));
     HIP_TRY(hipMemsetAsync(c->S->d_touched.p, 0, (size_t)n_queries * 16, stream));
     HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));  // [0]: error code, [3]: "a candidate needs the wide lists"
-    const DevQuery* d_q = reinterpret_cast<const DevQuery*>(c->S->d_stage.p + o_q);
-    const DevTerm* d_t = reinterpret_cast<const DevTerm*>(c->S->d_stage.p + o_t);
-    const PosTerm* d_pt = reinterpret_cast<const PosTerm*>(c->S->d_stage.p + o_pt);
-    const int64_t* d_ip = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_ip);
-    const int64_t* d_ep = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_ep);
+    const DevQuery* d_q = sg.dev(r_q);
+    const DevTerm* d_t = sg.dev(r_t);
+    const PosTerm* d_pt = sg.dev(r_pt);
+    const int64_t *d_ip = sg.dev(r_ip), *d_ep = sg.dev(r_ep), *d_cp = sg.dev(r_cp);
+    const int32_t *d_sl = sg.dev(r_sl), *d_nl = sg.dev(r_nl);
+    PhraseCut* d_cut = sg.dev(r_cut);
     const SegView sv = seg_view(seg);
     const bool legacy = seg->version < 1;
     {
@@ -4010,28 +4015,21 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
         RGPU_LAUNCH(kern, dim3(grid), dim3(AND_WG_THREADS), 0, stream, sv, d_q, d_t, d_ip, (int)n_queries, items, blocks_per_item, k_emit,
                            c->S->d_partial_keys.p, c->S->d_partial_counts.p, c->S->d_tau.p, c->S->d_touched.p, d_ep, c->phrase_count.p,
                            (void*)c->phrase_docs.p, (const unsigned long long*)nullptr, (const int32_t*)nullptr,
-                           clause_bitmaps.empty() ? (const TermBitmap*)nullptr : reinterpret_cast<const TermBitmap*>(c->S->d_stage.p + o_bm), xcd_chunk);
+                           clause_bitmaps.empty() ? (const TermBitmap*)nullptr : sg.dev(r_bm), xcd_chunk);
       };
       if (legacy) go(k_search_and<true, false, false, false>); else go(k_search_and<false, false, false, false>);
     }
-    const int32_t* d_sl = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_sl);
-    const int32_t* d_nl = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_nl);
-    SloppyGroups* d_gr = reinterpret_cast<SloppyGroups*>(c->S->d_stage.p + o_gr);
     if (slots > 0) {
-      PhraseMatchStage ms{d_q, d_t, d_pt, d_ep, d_sl, d_gr, n_queries, slots, redo_cap, any_exact, any_sloppy, sloppy_rpts, true,
-                          reinterpret_cast<PhraseCut*>(c->S->d_stage.p + o_cut), reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_cp),
-                          reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_nl), collect_items};
-      rc = phrase_match_stage(seg, stream, ms);
-      if (rc != RGPU_OK) return rc;
+      PhraseMatchStage ms{d_q, d_t, d_pt, d_ep, d_sl, sg.dev(r_gr), n_queries, slots, redo_cap, any_exact, any_sloppy, sloppy_rpts, true,
+                          d_cut, d_cp, d_nl, collect_items};
+      RGPU_TRY(phrase_match_stage(seg, stream, ms));
     }
     if (chunked) {
-      const int64_t* d_cp = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_cp);
-      int32_t* d_ab = reinterpret_cast<int32_t*>(c->S->d_stage.p + o_ab);
+      int32_t* d_ab = sg.dev(r_ab);
       {
       TimedLaunch tl(c, stream, "k_phrase_collect", 0);
       const unsigned grid = wg_count((collect_items + WG_WAVES - 1) / WG_WAVES);
       if (any_cutoff) {  // the two-phase rule's cut-off, chunk by chunk: first collected doc, candidates in front of it, the decision
-        PhraseCut* d_cut = reinterpret_cast<PhraseCut*>(c->S->d_stage.p + o_cut);
         RGPU_LAUNCH(k_phrase_cutoff_items<0>, dim3(grid), dim3(WG_THREADS), 0, stream, d_cp, d_ep, c->phrase_count.p, c->phrase_keys.p,
                            (const int32_t*)c->phrase_docs.p, d_sl, d_nl, (int)n_queries, collect_items, d_cut);
         RGPU_LAUNCH(k_phrase_cutoff_items<1>, dim3(grid), dim3(WG_THREADS), 0, stream, d_cp, d_ep, c->phrase_count.p, c->phrase_keys.p,
@@ -4066,14 +4064,23 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
   hipError_t e2 = hipMemcpyAsync(total_hits_out, c->host_api_totals.p, (size_t)n_queries * 8, hipMemcpyDeviceToHost, stream);
   hipError_t e3 = hipStreamSynchronize(stream);
   if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(RGPU_ERR_RUNTIME, "device to host copy failed");
-  if (err != 0)
-    return fail(err, err == RGPU_ERR_UNSUPPORTED ? "a doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)"
-                                                 : (err == RGPU_ERR_ILLEGAL_STATE ? "internal: a conjunction match was not found again" : "corrupt position data in .pos"));
-  return RGPU_OK;
+  return phrase_match_status(err, "a doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)",
+                             "internal: a conjunction match was not found again");
 }
 
 // ---- QueryRescorer ------------------------------------------------------------------------------------------------------------
 static_assert(sizeof(RescoreParams) == sizeof(rgpu_rescore_request), "RescoreParams mirrors rgpu_rescore_request");
+// a row's request, as the kernels read it: the window is cut to the row and to what one pass sorts
+static int32_t rescore_params_of(const rgpu_rescore_request& r, int32_t k, RescoreParams* out) {
+  if (r.mode < RGPU_RESCORE_AVG || r.mode > RGPU_RESCORE_MULTIPLY || r.window_size < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad rescore request");
+  *out = RescoreParams{r.query_weight, r.rescore_weight, r.mode, std::min(std::min(r.window_size, k), RGPU_PASS_K)};
+  return RGPU_OK;
+}
+// `finish`: every row's window back into score order
+static void launch_rescore_sort(rgpu_ctx* c, hipStream_t stream, RescoreParams* d_r, int32_t n_queries, int32_t k) {
+  TimedLaunch tl(c, stream, "k_rescore_sort", 0);
+  RGPU_LAUNCH(k_rescore_sort, dim3(wg_count((n_queries + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, d_r, (int)n_queries, (int)k, c->host_api_hits.p);
+}
 extern "C" int32_t rgpu_rescore_batch(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
                                       int32_t n_terms_total, const rgpu_rescore_request* requests, int32_t k, rgpu_hit* hits_inout,
                                       int32_t finish) {
@@ -4093,17 +4100,14 @@ extern "C" int32_t rgpu_rescore_batch(rgpu_segment* seg, const rgpu_query* queri
       return fail(RGPU_ERR_UNSUPPORTED, "rescore queries are TERM, all-MUST or all-SHOULD term queries");
     if (Q.n_terms < 1 || Q.n_terms > RGPU_MAX_QUERY_TERMS || (qop == RGPU_OP_TERM && Q.n_terms != 1)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad clause count");
     if (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms > (int64_t)n_terms_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "clause range outside terms[]");
-    const rgpu_rescore_request& r = requests[q];
-    if (r.mode < RGPU_RESCORE_AVG || r.mode > RGPU_RESCORE_MULTIPLY || r.window_size < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad rescore request");
-    rp[(size_t)q] = RescoreParams{r.query_weight, r.rescore_weight, r.mode, std::min(std::min(r.window_size, k), RGPU_PASS_K)};
+    RGPU_TRY(rescore_params_of(requests[q], k, &rp[(size_t)q]));
     for (int i = 0; i < Q.n_terms; ++i) {
       const rgpu_query_term& t = terms[Q.first_term + i];
       if (t.sim_table < 0 || t.sim_table >= c->n_sim_tables) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
       if (t.state.doc_freq > 0) ptrs.push_back(&t.state);
     }
   }
-  int32_t rc = prepare_terms_locked(seg, ptrs.data(), ptrs.size());
-  if (rc != RGPU_OK) return rc;
+  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
   std::vector<DevQuery> dq((size_t)n_queries);
   std::vector<DevTerm> dt;
   std::vector<DevTerm> mine;
@@ -4116,8 +4120,7 @@ extern "C" int32_t rgpu_rescore_batch(rgpu_segment* seg, const rgpu_query* queri
       const rgpu_query_term& t = terms[Q.first_term + i];
       if (t.state.doc_freq <= 0) { if (qop != RGPU_OP_OR) dead = true; continue; }  // create_scorer -> None: the query matches nothing here
       DevTerm d;
-      rc = make_dev_term(seg, t.state, t.weight, t.sim_table, &d);
-      if (rc != RGPU_OK) return rc;
+      RGPU_TRY(make_dev_term(seg, t.state, t.weight, t.sim_table, &d));
       mine.push_back(d);
     }
     if (dead) mine.clear();
@@ -4127,31 +4130,27 @@ extern "C" int32_t rgpu_rescore_batch(rgpu_segment* seg, const rgpu_query* queri
   }
   SCRATCH_TAKE(c);
   Stager st(c);
-  const size_t o_q = st.add((size_t)n_queries * sizeof(DevQuery));
-  const size_t o_t = st.add(std::max<size_t>(1, dt.size()) * sizeof(DevTerm));
-  const size_t o_r = st.add((size_t)n_queries * sizeof(RescoreParams));
-  HIP_TRY(c->S->h_stage.reserve(st.used));
-  HIP_TRY(c->S->d_stage.reserve(st.used, 0, stream));
-  std::memcpy(c->S->h_stage.p + o_q, dq.data(), (size_t)n_queries * sizeof(DevQuery));
-  if (!dt.empty()) std::memcpy(c->S->h_stage.p + o_t, dt.data(), dt.size() * sizeof(DevTerm));
-  std::memcpy(c->S->h_stage.p + o_r, rp.data(), (size_t)n_queries * sizeof(RescoreParams));
-  HIP_TRY(stage_h2d(c, st.used, stream));
+  const auto r_q = st.add<DevQuery>((size_t)n_queries);
+  const auto r_t = st.add<DevTerm>(std::max<size_t>(1, dt.size()));
+  const auto r_r = st.add<RescoreParams>((size_t)n_queries);
+  STAGE_SIZED(sg, st);
+  sg.put(r_q, dq);
+  sg.put(r_t, dt);
+  sg.put(r_r, rp);
+  RGPU_TRY(sg.upload(stream));
   const size_t n_hits = (size_t)n_queries * (size_t)k;
   HIP_TRY(c->host_api_hits.reserve(n_hits, 0, stream));
   HIP_TRY(hipMemcpyAsync(c->host_api_hits.p, hits_inout, n_hits * sizeof(HitOut), hipMemcpyHostToDevice, stream));
-  const DevQuery* d_q = reinterpret_cast<const DevQuery*>(c->S->d_stage.p + o_q);
-  const DevTerm* d_t = reinterpret_cast<const DevTerm*>(c->S->d_stage.p + o_t);
-  RescoreParams* d_r = reinterpret_cast<RescoreParams*>(c->S->d_stage.p + o_r);
+  const DevQuery* d_q = sg.dev(r_q);
+  const DevTerm* d_t = sg.dev(r_t);
+  RescoreParams* d_r = sg.dev(r_r);
   {
     TimedLaunch tl(c, stream, "k_rescore", 0);
     const unsigned grid = wg_count((n_hits + WG_WAVES - 1) / WG_WAVES);
     if (seg->version < 1) RGPU_LAUNCH(k_rescore<true>, dim3(grid), dim3(WG_THREADS), 0, stream, seg_view(seg), d_q, d_t, d_r, (int)n_queries, (int)k, c->host_api_hits.p, finish ? 1 : 0);
     else RGPU_LAUNCH(k_rescore<false>, dim3(grid), dim3(WG_THREADS), 0, stream, seg_view(seg), d_q, d_t, d_r, (int)n_queries, (int)k, c->host_api_hits.p, finish ? 1 : 0);
   }
-  if (finish) {
-    TimedLaunch tl(c, stream, "k_rescore_sort", 0);
-    RGPU_LAUNCH(k_rescore_sort, dim3(wg_count((n_queries + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, d_r, (int)n_queries, (int)k, c->host_api_hits.p);
-  }
+  if (finish) launch_rescore_sort(c, stream, d_r, n_queries, k);
   HIP_TRY(launch_status());
   HIP_TRY(hipMemcpyAsync(hits_inout, c->host_api_hits.p, n_hits * sizeof(HitOut), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
@@ -4173,44 +4172,24 @@ extern "C" int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phras
   // ---- validate (every refusal comes before hits_inout is touched)
   std::vector<const rgpu_term_state*> ptrs;
   std::vector<RescoreParams> rp((size_t)n_queries);
-  auto same_term = [](const rgpu_term_state& a, const rgpu_term_state& b) {  // as rgpu_search_phrase_batch fills PosTerm::same_as
-    return a.doc_start_fp == b.doc_start_fp && a.doc_freq == b.doc_freq && a.singleton_doc_id == b.singleton_doc_id && a.total_term_freq == b.total_term_freq;
-  };
   for (int32_t q = 0; q < n_queries; ++q) {
-    const rgpu_phrase_query& Q = queries[q];
-    if (Q.n_terms < 2 || Q.n_terms > RGPU_MAX_PHRASE_TERMS) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a phrase has 2..RGPU_MAX_PHRASE_TERMS terms");
-    if (Q.slop < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "Slop must be >= 0");  // PhraseQuery::new (phrase_query.rs:77)
-    if (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms > (int64_t)n_terms_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "term range outside terms[]");
-    if (Q.sim_table < 0 || Q.sim_table >= c->n_sim_tables) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
-    const rgpu_rescore_request& r = requests[q];
-    if (r.mode < RGPU_RESCORE_AVG || r.mode > RGPU_RESCORE_MULTIPLY || r.window_size < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad rescore request");
-    rp[(size_t)q] = RescoreParams{r.query_weight, r.rescore_weight, r.mode, std::min(std::min(r.window_size, k), RGPU_PASS_K)};
-    for (int i = 0; i < Q.n_terms; ++i) {
-      const rgpu_phrase_term& t = terms[Q.first_term + i];
-      if (t.state.doc_freq > 0) {
-        if (t.positions.pos_start_fp < 0 || (size_t)t.positions.pos_start_fp >= seg->pos_len) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "pos_start_fp outside the .pos file");
-        if (t.state.total_term_freq < t.state.doc_freq) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "total_term_freq below doc_freq");
-      }
-    }
+    RGPU_TRY(check_phrase_query(c, queries[q], n_terms_total, false));
+    RGPU_TRY(rescore_params_of(requests[q], k, &rp[(size_t)q]));
+    RGPU_TRY(check_phrase_terms(seg, queries[q], terms, &ptrs));
   }
   for (int32_t q = 0; q < n_queries; ++q) {
     const rgpu_phrase_query& Q = queries[q];
-    bool dead = false;  // a term absent from the leaf: create_scorer -> None, the row is served (nothing matches), whatever its terms
-    for (int i = 0; i < Q.n_terms; ++i) {
-      const rgpu_phrase_term& t = terms[Q.first_term + i];
-      if (t.state.doc_freq > 0) ptrs.push_back(&t.state); else dead = true;
-    }
     // SloppyPhraseScorer finds its repetition groups on the first doc it evaluates in the leaf (init_first_time,
     // phrase_scorer.rs:807-820): in a rescoring that is a conjunction match at or behind the first window hit, not a hit.
-    // (Only a row that is alive here is looked at, as rgpu_search_phrase_batch fills same_as: absent terms all look alike.)
-    if (Q.slop > 0 && !dead)
+    // (A row with a term absent from the leaf is served whatever its terms — create_scorer -> None, nothing matches — and
+    // emit_phrase fills same_as for live rows only: absent terms all look alike.)
+    if (Q.slop > 0 && !phrase_is_dead(Q, terms))
       for (int i = 1; i < Q.n_terms; ++i)
         for (int j = 0; j < i; ++j)
           if (same_term(terms[Q.first_term + j].state, terms[Q.first_term + i].state))
             return fail(RGPU_ERR_UNSUPPORTED, "phrase rescoring: a sloppy phrase that names a term twice is not served");
   }
-  int32_t rc = prepare_terms_locked(seg, ptrs.data(), ptrs.size());
-  if (rc != RGPU_OK) return rc;
+  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
   // ---- plan: row q owns the candidate slots [q * S, q * S + S)
   const int S = (k + 63) & ~63;
   const int64_t slots = (int64_t)n_queries * S;
@@ -4226,30 +4205,9 @@ extern "C" int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phras
     emit_prefix[(size_t)q] = (int64_t)q * S;
     emit_count[(size_t)q] = (unsigned long long)rp[(size_t)q].window;
     dq[(size_t)q] = DevQuery{RGPU_OP_AND, 0, (int32_t)dt.size(), 0};
-    bool dead = false;
-    for (int i = 0; i < Q.n_terms; ++i) dead = dead || terms[Q.first_term + i].state.doc_freq <= 0;
-    if (dead) continue;  // PhraseWeight::create_scorer -> None (phrase_query.rs:275-283): no hit of the row matches in this leaf
-    std::vector<int> order((size_t)Q.n_terms);
-    for (int i = 0; i < Q.n_terms; ++i) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return terms[Q.first_term + a].state.doc_freq < terms[Q.first_term + b].state.doc_freq; });
-    for (int i : order) {  // cost order (conjunction_scorer.rs:30), as in rgpu_search_phrase_batch
-      const rgpu_phrase_term& t = terms[Q.first_term + i];
-      DevTerm d;
-      rc = make_dev_term(seg, t.state, Q.weight, Q.sim_table, &d);
-      if (rc != RGPU_OK) return rc;
-      dt.push_back(d);
-      PosTerm p{};
-      p.pos_start_fp = (uint64_t)t.positions.pos_start_fp;
-      p.total_term_freq = t.state.total_term_freq;
-      p.last_pos_block_fp = t.state.total_term_freq < 128 ? t.positions.pos_start_fp
-                            : (t.state.total_term_freq == 128 ? -1 : t.positions.pos_start_fp + t.positions.last_pos_block_offset);
-      p.phrase_pos = t.position;
-      p.query_ord = i;
-      p.same_as = i;
-      for (int j = 0; j < i; ++j)
-        if (same_term(terms[Q.first_term + j].state, t.state)) { p.same_as = j; break; }  // (exact phrases only: "a b a")
-      pt.push_back(p);
-    }
+    bool dead = false;  // (no hit of the row matches in this leaf)
+    RGPU_TRY(emit_phrase(seg, Q, terms, &dt, &pt, &dead));  // (same_as != query_ord: exact phrases only here, "a b a")
+    if (dead) continue;
     slops[(size_t)q] = Q.slop;
     (Q.slop > 0 ? any_sloppy : any_exact) = true;
     dq[(size_t)q].n_terms = Q.n_terms;
@@ -4257,25 +4215,24 @@ extern "C" int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phras
   emit_prefix[(size_t)n_queries] = slots;
   SCRATCH_TAKE(c);
   Stager st(c);
-  const size_t o_q = st.add((size_t)n_queries * sizeof(DevQuery));
-  const size_t o_t = st.add(std::max<size_t>(1, dt.size()) * sizeof(DevTerm));
-  const size_t o_pt = st.add(std::max<size_t>(1, pt.size()) * sizeof(PosTerm));
-  const size_t o_ep = st.add((size_t)(n_queries + 1) * 8);
-  const size_t o_ec = st.add((size_t)n_queries * 8);
-  const size_t o_sl = st.add((size_t)n_queries * 4);
-  const size_t o_gr = st.add((size_t)n_queries * sizeof(SloppyGroups));
-  const size_t o_r = st.add((size_t)n_queries * sizeof(RescoreParams));
-  HIP_TRY(c->S->h_stage.reserve(st.used));
-  HIP_TRY(c->S->d_stage.reserve(st.used, 0, stream));
-  std::memcpy(c->S->h_stage.p + o_q, dq.data(), (size_t)n_queries * sizeof(DevQuery));
-  if (!dt.empty()) std::memcpy(c->S->h_stage.p + o_t, dt.data(), dt.size() * sizeof(DevTerm));
-  if (!pt.empty()) std::memcpy(c->S->h_stage.p + o_pt, pt.data(), pt.size() * sizeof(PosTerm));
-  std::memcpy(c->S->h_stage.p + o_ep, emit_prefix.data(), (size_t)(n_queries + 1) * 8);
-  std::memcpy(c->S->h_stage.p + o_ec, emit_count.data(), (size_t)n_queries * 8);
-  std::memcpy(c->S->h_stage.p + o_sl, slops.data(), (size_t)n_queries * 4);
-  std::memset(c->S->h_stage.p + o_gr, 0xff, (size_t)n_queries * sizeof(SloppyGroups));  // "no repetition group": k_sloppy_match reads the region
-  std::memcpy(c->S->h_stage.p + o_r, rp.data(), (size_t)n_queries * sizeof(RescoreParams));
-  HIP_TRY(stage_h2d(c, st.used, stream));
+  const auto r_q = st.add<DevQuery>((size_t)n_queries);
+  const auto r_t = st.add<DevTerm>(std::max<size_t>(1, dt.size()));
+  const auto r_pt = st.add<PosTerm>(std::max<size_t>(1, pt.size()));
+  const auto r_ep = st.add<int64_t>((size_t)n_queries + 1);
+  const auto r_ec = st.add<unsigned long long>((size_t)n_queries);
+  const auto r_sl = st.add<int32_t>((size_t)n_queries);
+  const auto r_gr = st.add<SloppyGroups>((size_t)n_queries);
+  const auto r_r = st.add<RescoreParams>((size_t)n_queries);
+  STAGE_SIZED(sg, st);
+  sg.put(r_q, dq);
+  sg.put(r_t, dt);
+  sg.put(r_pt, pt);
+  sg.put(r_ep, emit_prefix);
+  sg.put(r_ec, emit_count);
+  sg.put(r_sl, slops);
+  sg.fill(r_gr, 0xff);  // "no repetition group": k_sloppy_match reads the region
+  sg.put(r_r, rp);
+  RGPU_TRY(sg.upload(stream));
   const size_t n_hits = (size_t)n_queries * (size_t)k;
   HIP_TRY(c->host_api_hits.reserve(n_hits, 0, stream));
   HIP_TRY(hipMemcpyAsync(c->host_api_hits.p, hits_inout, n_hits * sizeof(HitOut), hipMemcpyHostToDevice, stream));
@@ -4284,17 +4241,13 @@ extern "C" int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phras
   const int64_t redo_cap = phrase_redo_cap(slots);
   HIP_TRY(c->phrase_redo.reserve((size_t)redo_cap + 64, 0, stream));
   HIP_TRY(c->phrase_count.reserve((size_t)n_queries, 0, stream));
-  HIP_TRY(hipMemcpyAsync(c->phrase_count.p, c->S->d_stage.p + o_ec, (size_t)n_queries * 8, hipMemcpyDeviceToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(c->phrase_count.p, sg.dev(r_ec), (size_t)n_queries * 8, hipMemcpyDeviceToDevice, stream));
   // (a 64-candidate kernel leaves the slots behind a row's window unwritten, and a batch of absent-term rows launches none)
   HIP_TRY(hipMemsetAsync(c->phrase_keys.p, 0, (size_t)slots * 8, stream));
   HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));
-  const DevQuery* d_q = reinterpret_cast<const DevQuery*>(c->S->d_stage.p + o_q);
-  const DevTerm* d_t = reinterpret_cast<const DevTerm*>(c->S->d_stage.p + o_t);
-  const PosTerm* d_pt = reinterpret_cast<const PosTerm*>(c->S->d_stage.p + o_pt);
-  const int64_t* d_ep = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_ep);
-  const int32_t* d_sl = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_sl);
-  SloppyGroups* d_gr = reinterpret_cast<SloppyGroups*>(c->S->d_stage.p + o_gr);
-  RescoreParams* d_r = reinterpret_cast<RescoreParams*>(c->S->d_stage.p + o_r);
+  const DevQuery* d_q = sg.dev(r_q);
+  const DevTerm* d_t = sg.dev(r_t);
+  RescoreParams* d_r = sg.dev(r_r);
   const SegView sv = seg_view(seg);
   {
     TimedLaunch tl(c, stream, "k_rescore_phrase_candidates", 0);
@@ -4303,25 +4256,22 @@ extern "C" int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phras
     else RGPU_LAUNCH(k_rescore_phrase_candidates<false>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_r, (int)n_queries, (int)k, S, c->host_api_hits.p, c->phrase_docs.p);
   }
   if (any_exact || any_sloppy) {
-    PhraseMatchStage ms{d_q, d_t, d_pt, d_ep, d_sl, d_gr, n_queries, slots, redo_cap, any_exact, any_sloppy, false, false, nullptr, nullptr, nullptr, 0};
-    rc = phrase_match_stage(seg, stream, ms);
-    if (rc != RGPU_OK) return rc;
+    PhraseMatchStage ms{d_q, d_t, sg.dev(r_pt), sg.dev(r_ep), sg.dev(r_sl), sg.dev(r_gr), n_queries, slots, redo_cap, any_exact, any_sloppy, false, false,
+                        nullptr, nullptr, nullptr, 0};
+    RGPU_TRY(phrase_match_stage(seg, stream, ms));
   }
   {
     TimedLaunch tl(c, stream, "k_rescore_phrase_combine", 0);
     RGPU_LAUNCH(k_rescore_phrase_combine, dim3(wg_count((n_hits + 255) / 256)), dim3(256), 0, stream, sv, d_r, (int)n_queries, (int)k, S, c->phrase_keys.p, c->host_api_hits.p, finish ? 1 : 0);
   }
-  if (finish) {
-    TimedLaunch tl(c, stream, "k_rescore_sort", 0);
-    RGPU_LAUNCH(k_rescore_sort, dim3(wg_count((n_queries + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, d_r, (int)n_queries, (int)k, c->host_api_hits.p);
-  }
+  if (finish) launch_rescore_sort(c, stream, d_r, n_queries, k);
   HIP_TRY(launch_status());
   int err = 0;
   HIP_TRY(hipMemcpyAsync(&err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  if (err != 0)  // (hits_inout stays as it came)
-    return fail(err, err == RGPU_ERR_UNSUPPORTED ? "a hit doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)"
-                                                 : (err == RGPU_ERR_ILLEGAL_STATE ? "internal: a candidate doc was not found again" : "corrupt position data in .pos"));
+  // (a refusal here too leaves hits_inout as it came)
+  RGPU_TRY(phrase_match_status(err, "a hit doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)",
+                               "internal: a candidate doc was not found again"));
   HIP_TRY(hipMemcpyAsync(hits_inout, c->host_api_hits.p, n_hits * sizeof(HitOut), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   return RGPU_OK;
