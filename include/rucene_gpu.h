@@ -659,7 +659,46 @@ int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* que
                                  const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
                                  int64_t* total_hits_out);
 
-/* ---- second-pass scoring (QueryRescorer) ------------------------------------------------------------------------------ */
+/* BooleanQuery with exact PhraseQuery clauses among its required clauses: +"a b" +c -d #e. BooleanWeight::create_scorer
+ * (boolean_query.rs:196-279) builds a ConjunctionScorer over must_weights — the MUST weights in query order, then the FILTER weights
+ * (needs_scores = false: they score 0.0) — sorted stably by cost (conjunction_scorer.rs:27-42: a term's cost is its doc_freq in
+ * the leaf, an ExactPhraseScorer's the smallest doc_freq among its terms, phrase_scorer.rs:270-272), sums the children's scores in
+ * that order in f32 (:87-95), and wraps the result in a ReqNotScorer over the MUST_NOT clauses (:264-266). None of these scorers is
+ * two-phase, so next_limit plays no part and deleted docs are simply not collected.
+ * Served: 1..RGPU_MAX_BOOL_PHRASES exact phrases (MUST or FILTER: a FILTER phrase carries weight 0) beside any number of MUST /
+ * FILTER term clauses and MUST_NOT term clauses; the DISTINCT terms of a query (phrase terms, required terms, MUST_NOT terms) number
+ * at most RGPU_MAX_QUERY_TERMS; k up to RGPU_MAX_K. A leaf that lacks a phrase term or a required term matches nothing; a MUST_NOT
+ * term it lacks excludes nothing.
+ * NOT served (the caller keeps these on its CPU path): sloppy phrase clauses (slop > 0 -> RGPU_ERR_UNSUPPORTED: as a child of a
+ * conjunction the reference's SloppyPhraseScorer matches on its approximation and scores a stale sloppy_freq, which is not
+ * reproduced); phrase clauses under SHOULD or MUST_NOT; SHOULD clauses of any kind beside a required phrase (ReqOptScorer); nested
+ * BooleanQuery clauses beside a phrase; more than RGPU_MAX_BOOL_PHRASES phrases — none of them can be written in this struct. */
+#define RGPU_MAX_BOOL_PHRASES 4
+typedef struct rgpu_phrase_bool_query {
+  int32_t n_phrases;     /* 1..RGPU_MAX_BOOL_PHRASES required exact phrases (slop must be 0; next_limit is ignored) */
+  int32_t first_phrase;  /* ... index of the first one in `phrases` */
+  int32_t n_terms;       /* required term clauses: the MUST clauses in query order, then the FILTER clauses with weight 0 */
+  int32_t first_term;    /* index of the first one in `terms`; the n_must_not MUST_NOT term clauses follow the required ones */
+  int32_t n_must_not;
+  int32_t phrase_slot[RGPU_MAX_BOOL_PHRASES]; /* position of phrase i in BooleanWeight::must_weights (MUST clauses in query order, then
+                                                 FILTER clauses), 0 <= slot < n_phrases + n_terms; the required term clauses take the
+                                                 other positions in order */
+  int32_t reserved[3];
+} rgpu_phrase_bool_query;
+/* One leaf of IndexSearcher::search(BooleanQuery over phrases and terms, TopDocsCollector(k)). `phrases` / `phrase_terms` as the
+ * queries / terms of rgpu_search_phrase_batch, `terms` as those of rgpu_search_batch. Outputs and calling protocol as
+ * rgpu_search_batch; docs, scores and total_hits are bit-exact with the CPU scorers.
+ * Refused, nothing written: what rgpu_search_phrase_batch refuses, a phrase_slot out of range or named twice, index ranges
+ * outside the arrays (RGPU_ERR_ILLEGAL_ARGUMENT); no positions attached (RGPU_ERR_ILLEGAL_STATE); slop > 0, n_phrases outside
+ * 1..RGPU_MAX_BOOL_PHRASES, more than RGPU_MAX_QUERY_TERMS distinct terms, a doc that holds a phrase term more than 1024 times
+ * (RGPU_ERR_UNSUPPORTED). */
+int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_phrase_bool_query* queries, int32_t n_queries,
+                                      const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                      const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                      const rgpu_query_term* terms, int32_t n_terms_total,
+                                      int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out);
+
+/* ---- second-pass scoring (QueryRescorer)------------------------------------------------------------------------------ */
 /* search/scorer/rescorer.rs: QueryRescorer re-ranks the top `window_size` hits of a first pass with a second query —
  * per hit the second query's scorer is advanced to the doc and the two scores are combined (combine_score :337-352:
  * mode.combine(first * query_weight, second * rescore_weight), or first * query_weight when the second query does not

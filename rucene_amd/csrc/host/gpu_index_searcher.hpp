@@ -356,6 +356,45 @@ struct PhraseQuery : Query {
   }
 };
 
+// BooleanQuery with exact PhraseQuery clauses among its required clauses: +"a b" +c -d #e (rgpu_search_phrase_bool_batch).
+// `required`: BooleanWeight::must_weights — the MUST clauses in query order (must()), then the FILTER clauses (filter(): they
+// score 0); a clause is a phrase or a term. Only the shapes the GPU path serves can be written here: no SHOULD clause, no phrase
+// under MUST_NOT, no nested BooleanQuery; a sloppy phrase clause or more than RGPU_MAX_BOOL_PHRASES phrases is UnsupportedOperation
+// when the query is searched — the caller's CPU path (inside a conjunction the reference's SloppyPhraseScorer matches on its
+// approximation and scores a stale sloppy_freq, which is not reproduced).
+struct PhraseBooleanQuery : Query {
+  struct Required {
+    std::shared_ptr<PhraseQuery> phrase;  // null: a term clause
+    TermQuery term{int64_t(-1)};
+    bool filter = false;
+  };
+  std::vector<Required> required;
+  std::vector<TermQuery> must_not_queries;
+  PhraseBooleanQuery& must(PhraseQuery p) { return add(Required{std::make_shared<PhraseQuery>(std::move(p)), TermQuery(int64_t(-1)), false}); }
+  PhraseBooleanQuery& must(TermQuery t) { return add(Required{nullptr, std::move(t), false}); }
+  PhraseBooleanQuery& filter(PhraseQuery p) { return add(Required{std::make_shared<PhraseQuery>(std::move(p)), TermQuery(int64_t(-1)), true}); }
+  PhraseBooleanQuery& filter(TermQuery t) { return add(Required{nullptr, std::move(t), true}); }
+  PhraseBooleanQuery& must_not(TermQuery t) { must_not_queries.push_back(std::move(t)); return *this; }
+  // refused before any leaf is touched
+  void check_served() const {
+    int n_phrases = 0;
+    for (const Required& r : required) {
+      if (!r.phrase) continue;
+      ++n_phrases;
+      if (r.phrase->slop > 0) throw Error(RGPU_ERR_UNSUPPORTED, "a sloppy phrase inside a boolean query is not served by the GPU path");
+    }
+    if (n_phrases < 1 || n_phrases > RGPU_MAX_BOOL_PHRASES) throw Error(RGPU_ERR_UNSUPPORTED, "a boolean query over phrases holds 1..RGPU_MAX_BOOL_PHRASES phrases");
+  }
+
+ private:
+  PhraseBooleanQuery& add(Required r) {  // (FILTER clauses stand behind the MUST clauses in must_weights)
+    auto at = required.end();
+    if (!r.filter) at = std::find_if(required.begin(), required.end(), [](const Required& x) { return x.filter; });
+    required.insert(at, std::move(r));
+    return *this;
+  }
+};
+
 // RescoreRequest (search/scorer/rescorer.rs:67-116): how a second query's score is folded into the first pass's
 struct RescoreRequest {
   const Query* query = nullptr;  // TermQuery, an all-MUST / all-SHOULD BooleanQuery, or a PhraseQuery (sloppy: no repeated term)
@@ -614,7 +653,33 @@ class GpuIndexSearcher {
   }
 
   // the batched form the hardware wants: one launch set per leaf for many queries
+  // (PhraseQuery rows go through rgpu_search_phrase_batch, PhraseBooleanQuery rows through rgpu_search_phrase_bool_batch, the rest
+  // through rgpu_search_batch: one call per kind and leaf, rows keep their order)
   std::vector<TopDocs> search_many(const std::vector<const Query*>& queries, size_t k) {
+    std::vector<size_t> phrase_rows, bool_rows, plain_rows;
+    for (size_t i = 0; i < queries.size(); ++i) {
+      if (dynamic_cast<const PhraseQuery*>(queries[i])) phrase_rows.push_back(i);
+      else if (dynamic_cast<const PhraseBooleanQuery*>(queries[i])) bool_rows.push_back(i);
+      else plain_rows.push_back(i);
+    }
+    if (!phrase_rows.empty() || !bool_rows.empty()) {
+      std::vector<TopDocs> out(queries.size());
+      auto place = [&](const std::vector<size_t>& rows, std::vector<TopDocs> got) { for (size_t i = 0; i < rows.size(); ++i) out[rows[i]] = std::move(got[i]); };
+      std::vector<const PhraseBooleanQuery*> bools;
+      for (size_t i : bool_rows) { bools.push_back(static_cast<const PhraseBooleanQuery*>(queries[i])); bools.back()->check_served(); }
+      if (!plain_rows.empty()) {
+        std::vector<const Query*> plain;
+        for (size_t i : plain_rows) plain.push_back(queries[i]);
+        place(plain_rows, search_many(plain, k));
+      }
+      if (!phrase_rows.empty()) {
+        std::vector<const PhraseQuery*> phrases;
+        for (size_t i : phrase_rows) phrases.push_back(static_cast<const PhraseQuery*>(queries[i]));
+        place(phrase_rows, search_phrases(phrases, k));
+      }
+      if (!bools.empty()) place(bool_rows, search_phrase_bools(bools, k));
+      return out;
+    }
     const int32_t nq = static_cast<int32_t>(queries.size());
     std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
     std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
@@ -646,6 +711,60 @@ class GpuIndexSearcher {
       leaf_totals[li].assign(static_cast<size_t>(nq), 0);
       check(rgpu_search_phrase_batch(leaf.segment, qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
                                      leaf_hits[li].data(), leaf_totals[li].data()));
+    }
+    return merge_leaves(leaf_hits, leaf_totals, nq, k);
+  }
+
+  // IndexSearcher::search(BooleanQuery over phrases and terms, TopDocsCollector(k)) for a batch: rgpu_search_phrase_bool_batch per leaf.
+  // A FILTER clause rides with weight 0 (needs_scores = false); phrase_slot[i] = the phrase's index in `required`.
+  std::vector<TopDocs> search_phrase_bools(const std::vector<const PhraseBooleanQuery*>& queries, size_t k) {
+    const int32_t nq = static_cast<int32_t>(queries.size());
+    for (const PhraseBooleanQuery* q : queries) q->check_served();
+    std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
+    std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
+    for (size_t li = 0; li < leaves_.size(); ++li) {
+      const LeafReader& leaf = leaves_[li];
+      if (!leaf.pos_bytes) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "phrase search needs a positions field (LeafReader::pos_bytes)");
+      std::vector<rgpu_phrase_bool_query> qs;
+      std::vector<const PhraseQuery*> phrases;
+      std::vector<bool> filtered;
+      std::vector<rgpu_query_term> ts;
+      auto term_clause = [&](const TermQuery& c, bool scoring) {
+        rgpu_query_term qt{};
+        if (!leaf.term_state(c, &qt.state)) { qt.state = rgpu_term_state{}; qt.state.skip_offset = -1; qt.state.singleton_doc_id = -1; }
+        auto w = weight_of(c);
+        qt.weight = scoring ? w.first : 0.0f;
+        qt.sim_table = w.second;
+        ts.push_back(qt);
+      };
+      for (const PhraseBooleanQuery* q : queries) {
+        rgpu_phrase_bool_query bq{};
+        bq.first_phrase = static_cast<int32_t>(phrases.size());
+        bq.first_term = static_cast<int32_t>(ts.size());
+        for (size_t s = 0; s < q->required.size(); ++s) {
+          const PhraseBooleanQuery::Required& r = q->required[s];
+          if (r.phrase) {
+            bq.phrase_slot[bq.n_phrases++] = static_cast<int32_t>(s);
+            phrases.push_back(r.phrase.get());
+            filtered.push_back(r.filter);
+          } else {
+            term_clause(r.term, !r.filter);
+            bq.n_terms++;
+          }
+        }
+        for (const TermQuery& c : q->must_not_queries) term_clause(c, false);
+        bq.n_must_not = static_cast<int32_t>(q->must_not_queries.size());
+        qs.push_back(bq);
+      }
+      std::vector<rgpu_phrase_query> ps;
+      std::vector<rgpu_phrase_term> pts;
+      pack_phrases(phrases, leaf, &ps, &pts);
+      for (size_t i = 0; i < ps.size(); ++i) { if (filtered[i]) ps[i].weight = 0.0f; ps[i].next_limit = 0; }
+      leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
+      leaf_totals[li].assign(static_cast<size_t>(nq), 0);
+      check(rgpu_search_phrase_bool_batch(leaf.segment, qs.data(), nq, ps.data(), static_cast<int32_t>(ps.size()), pts.data(), static_cast<int32_t>(pts.size()),
+                                          ts.empty() ? nullptr : ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
+                                          leaf_hits[li].data(), leaf_totals[li].data()));
     }
     return merge_leaves(leaf_hits, leaf_totals, nq, k);
   }

@@ -35,6 +35,8 @@
 #include "host/stage_layout.hpp"
 #include "host/term_arena.hpp"
 #include "kernels/search_phrase.hpp"
+#include "kernels/search_phrase_bool.hpp"
+#include "host/phrase_bool_plan.hpp"
 #include "kernels/search_term.hpp"
 #include "kernels/search_term_query.hpp"
 
@@ -4066,6 +4068,270 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
   if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(RGPU_ERR_RUNTIME, "device to host copy failed");
   return phrase_match_status(err, "a doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)",
                              "internal: a conjunction match was not found again");
+}
+
+// ---- BooleanQuery with exact PhraseQuery clauses among its required clauses: +"a b" +c -d #e ------------------------------------
+// (include/rucene_gpu.h rgpu_search_phrase_bool_batch; the plan: host/phrase_bool_plan.hpp; the two kernels of its own:
+// kernels/search_phrase_bool.hpp.) Launch sequence, all on the call's stream:
+//   1. k_search_and in emit mode over every query's DISTINCT required terms -> plane 0's candidate docs. MUST_NOT terms are removed
+//      here, through the HAS_NOT instantiation: the prohibited probe clears a0 / a1 before the emit branch is reached, and
+//      DevQuery::pad is what n_req_not is computed from whether the kernel emits or collects;
+//   2. k_phrase_bool_fanout (batches with a query of more than one phrase): plane 0's docs and count to the other planes;
+//   3. phrase_match_stage over the virtual queries (query, phrase), plane-major — exact kernels only;
+//   4. k_phrase_bool_score: the reference-order f32 sum over plane 0's key;
+//   5. the phrase collectors over plane 0.
+// Unsupported shapes (see the header): sloppy clauses, phrases under SHOULD / MUST_NOT, SHOULD clauses or nested BooleanQuery clauses
+// beside a phrase, more than RGPU_MAX_BOOL_PHRASES phrases.
+static_assert(PHRASE_BOOL_MAX_PLANES == RGPU_MAX_BOOL_PHRASES, "k_phrase_bool_score keeps one key per plane in registers");
+extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_phrase_bool_query* queries, int32_t n_queries,
+                                                 const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                                 const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                                 const rgpu_query_term* terms, int32_t n_terms_total,
+                                                 int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
+  if (!seg || !queries || n_queries <= 0 || !phrases || n_phrases_total <= 0 || !phrase_terms || n_phrase_terms_total <= 0 || n_terms_total < 0 ||
+      (n_terms_total > 0 && !terms) || !hits_out || !total_hits_out)
+    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "boolean query over phrases: k must be in 1..RGPU_MAX_K");
+  if (!seg->has_positions || !seg->d_pos) return fail(RGPU_ERR_ILLEGAL_STATE, "a boolean query over phrases needs a positions field with its .pos file attached");
+  rgpu_ctx* c = seg->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t stream = c->stream;
+  // ---- validate, plan
+  const size_t nq = (size_t)n_queries;
+  std::vector<const rgpu_term_state*> ptrs;
+  std::vector<rgpu_host::PhraseBoolPlan> plans(nq);
+  int max_planes = 1;
+  bool any_not = false;
+  for (int32_t q = 0; q < n_queries; ++q) {
+    const rgpu_phrase_bool_query& Q = queries[q];
+    if (Q.n_phrases < 1 || Q.n_phrases > RGPU_MAX_BOOL_PHRASES) return fail(RGPU_ERR_UNSUPPORTED, "a boolean query over phrases holds 1..RGPU_MAX_BOOL_PHRASES phrases");
+    if (Q.first_phrase < 0 || (int64_t)Q.first_phrase + Q.n_phrases > (int64_t)n_phrases_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "phrase range outside phrases[]");
+    if (Q.n_terms < 0 || Q.n_must_not < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "negative clause count");
+    if (Q.n_terms + (int64_t)Q.n_must_not > 0 && (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms + Q.n_must_not > (int64_t)n_terms_total))
+      return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "clause range outside terms[]");
+    for (int i = 0; i < Q.n_phrases; ++i) {
+      const rgpu_phrase_query& P = phrases[Q.first_phrase + i];
+      RGPU_TRY(check_phrase_query(c, P, n_phrase_terms_total, false));
+      RGPU_TRY(check_phrase_terms(seg, P, phrase_terms, &ptrs));
+    }
+    for (int i = 0; i < Q.n_terms + Q.n_must_not; ++i) {
+      const rgpu_query_term& t = terms[Q.first_term + i];
+      if (i < Q.n_terms && (t.sim_table < 0 || t.sim_table >= c->n_sim_tables)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
+      if (t.state.doc_freq > 0) ptrs.push_back(&t.state);
+    }
+    plans[(size_t)q] = rgpu_host::plan_phrase_bool(Q, phrases, phrase_terms, terms);
+    const rgpu_host::PhraseBoolPlan& P = plans[(size_t)q];
+    if (P.status != RGPU_OK) return fail(P.status, P.why);
+    if (!P.dead) { max_planes = std::max(max_planes, (int)Q.n_phrases); any_not = any_not || !P.must_not.empty(); }
+  }
+  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
+  // the candidate conjunction answers a dense clause from its doc bitmap, as a phrase search's does
+  const int64_t bitmap_df = (c->cfg.and_bitmaps >= 0 && c->n_sim_tables > 0) ? bitmap_min_df_and(seg) : INT64_MAX;
+  if (bitmap_df != INT64_MAX) {
+    std::vector<const rgpu_term_state*> dense;
+    std::vector<int32_t> dense_sim;
+    for (int32_t q = 0; q < n_queries; ++q) {
+      const rgpu_host::PhraseBoolPlan& P = plans[(size_t)q];
+      if (P.dead) continue;
+      for (const rgpu_term_state* st : P.conj)
+        if (st->doc_freq >= bitmap_df && !seg->bitmaps.find(st->doc_start_fp)) { dense.push_back(st); dense_sim.push_back(phrases[queries[q].first_phrase].sim_table); }
+    }
+    if (!dense.empty()) RGPU_TRY(ensure_bitmaps_locked(seg, dense.data(), dense_sim.data(), dense.size()));
+  }
+  // ---- the launch's arrays. Virtual queries (query, phrase) are plane-major: v = j * n_queries + q
+  const size_t nv = nq * (size_t)max_planes;
+  std::vector<DevQuery> cq(nq, DevQuery{RGPU_OP_AND, 0, 0, 0});  // the candidate conjunction: [distinct required terms][MUST_NOT x pad]
+  std::vector<DevTerm> cdt;
+  std::vector<DevQuery> vq(nv, DevQuery{RGPU_OP_AND, 0, 0, 0});  // the match stage: one phrase each
+  std::vector<DevTerm> pdt;
+  std::vector<PosTerm> ppt;
+  std::vector<PhraseBoolDev> pbd(nq, PhraseBoolDev{0, 0, 0, 0});  // the scoring kernel
+  std::vector<int32_t> order;
+  std::vector<DevTerm> sdt;
+  std::vector<int64_t> item_prefix(nq + 1), emit_prefix(nv + 1), collect_prefix(nq + 1);
+  int64_t lead_blocks = 0;
+  for (const rgpu_host::PhraseBoolPlan& P : plans) if (!P.dead) lead_blocks += P.lead_df / 128;
+  const int blocks_per_item = and_item_blocks(c, lead_blocks);
+  int64_t items = 0, collect_items = 0;
+  for (int32_t q = 0; q < n_queries; ++q) {
+    const rgpu_phrase_bool_query& Q = queries[q];
+    const rgpu_host::PhraseBoolPlan& P = plans[(size_t)q];
+    item_prefix[(size_t)q] = items;
+    collect_prefix[(size_t)q] = collect_items;
+    if (P.dead) continue;
+    const int32_t conj_sim = phrases[Q.first_phrase].sim_table;  // (an emitting conjunction loads its lead's table and scores nothing)
+    cq[(size_t)q] = DevQuery{RGPU_OP_AND, (int32_t)P.conj.size(), (int32_t)cdt.size(), (int32_t)P.must_not.size()};
+    for (const rgpu_term_state* st : P.conj) { cdt.emplace_back(); RGPU_TRY(make_dev_term(seg, *st, 0.0f, conj_sim, &cdt.back())); }
+    for (const rgpu_term_state* st : P.must_not) { cdt.emplace_back(); RGPU_TRY(make_dev_term(seg, *st, 0.0f, conj_sim, &cdt.back())); }
+    const DevTerm& lead = cdt[(size_t)cq[(size_t)q].first_term];
+    items += lead.nblocks == 0 ? 1 : (lead.nblocks + blocks_per_item - 1) / blocks_per_item;
+    collect_items += ((int64_t)lead.df + PHRASE_COLLECT_CHUNK - 1) / PHRASE_COLLECT_CHUNK;
+    for (int j = 0; j < Q.n_phrases; ++j) {
+      const size_t v = (size_t)j * nq + (size_t)q;
+      vq[v] = DevQuery{RGPU_OP_AND, 0, (int32_t)pdt.size(), 0};
+      bool dead = false;
+      RGPU_TRY(emit_phrase(seg, phrases[Q.first_phrase + j], phrase_terms, &pdt, &ppt, &dead));  // (dead: the plan has said so already)
+      vq[v].n_terms = dead ? 0 : phrases[Q.first_phrase + j].n_terms;
+    }
+    pbd[(size_t)q] = PhraseBoolDev{Q.n_phrases, (int32_t)order.size(), (int32_t)P.order.size(), 0};
+    const int32_t first_clause = (int32_t)sdt.size();
+    for (int i = 0; i < Q.n_terms; ++i) {
+      const rgpu_query_term& t = terms[Q.first_term + i];
+      sdt.emplace_back();
+      RGPU_TRY(make_dev_term(seg, t.state, t.weight, t.sim_table, &sdt.back()));
+    }
+    for (int32_t o : P.order) order.push_back(o < 0 ? o : first_clause + o);
+  }
+  item_prefix[nq] = items;
+  collect_prefix[nq] = collect_items;
+  int64_t slots = 0;
+  for (int j = 0; j < max_planes; ++j)
+    for (size_t q = 0; q < nq; ++q) {
+      emit_prefix[(size_t)j * nq + q] = slots;
+      if (!plans[q].dead && j < queries[q].n_phrases) slots += plans[q].plane_slots;
+    }
+  emit_prefix[nv] = slots;
+  const int64_t groups0 = emit_prefix[nq] / 64;  // plane 0's 64-slot groups
+  HIP_TRY(c->host_api_hits.reserve(nq * (size_t)k, 0, stream));
+  HIP_TRY(c->host_api_totals.reserve(nq, 0, stream));
+  HIP_TRY(hipMemsetAsync(c->host_api_totals.p, 0, nq * 8, stream));
+  RGPU_LAUNCH(k_init_hits, dim3(wg_count((nq * (size_t)k + 255) / 256)), dim3(256), 0, stream, c->host_api_hits.p, (int64_t)n_queries, (int)k, (int)k, 0);
+  int err = 0;
+  if (items > 0) {
+    SCRATCH_TAKE(c);
+    Stager st(c);
+    const auto r_cq = st.add<DevQuery>(nq), r_vq = st.add<DevQuery>(nv);
+    const auto r_cdt = st.add<DevTerm>(cdt.size()), r_pdt = st.add<DevTerm>(pdt.size()), r_sdt = st.add<DevTerm>(std::max<size_t>(1, sdt.size()));
+    const auto r_ppt = st.add<PosTerm>(ppt.size());
+    const auto r_pb = st.add<PhraseBoolDev>(nq);
+    const auto r_or = st.add<int32_t>(order.size());
+    const auto r_ip = st.add<int64_t>(nq + 1), r_ep = st.add<int64_t>(nv + 1), r_cp = st.add<int64_t>(nq + 1);
+    const auto r_sl = st.add<int32_t>(nv);  // slop 0 throughout
+    const auto r_nl = st.add<int32_t>(nq);  // no next_limit: no scorer here is two-phase
+    const auto r_ab = st.add<int32_t>(nq);  // nothing is abandoned
+    const auto r_gr = st.add<SloppyGroups>(nv);
+    std::vector<TermBitmap> clause_bitmaps;  // parallel to cdt: the required clauses behind a query's lead that have a doc bitmap
+    if (bitmap_df != INT64_MAX && seg->bitmaps.size() > 0) {
+      bool any = false;
+      clause_bitmaps.assign(cdt.size(), TermBitmap{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0});
+      for (const DevQuery& q0 : cq) {
+        for (int i = 1; i < q0.n_terms; ++i) {
+          const DevTerm& t = cdt[(size_t)(q0.first_term + i)];
+          if (t.df < bitmap_df) continue;
+          const BitmapInfo* bm = seg->bitmaps.find((int64_t)t.start_fp);
+          if (!bm || !bm->usable || bm->df != t.df) continue;
+          clause_bitmaps[(size_t)(q0.first_term + i)] = TermBitmap{bm->words, bm->ranks, bm->freqs, bm->ovf, bm->nib, bm->memb, bm->n_ovf, 0};
+          any = true;
+        }
+      }
+      if (!any) clause_bitmaps.clear();
+    }
+    const auto r_bm = st.add_if<TermBitmap>(!clause_bitmaps.empty(), clause_bitmaps.size());
+    STAGE_SIZED(sg, st);
+    sg.put(r_cq, cq);
+    sg.put(r_vq, vq);
+    sg.put(r_cdt, cdt);
+    sg.put(r_pdt, pdt);
+    sg.put(r_sdt, sdt);
+    sg.put(r_ppt, ppt);
+    sg.put(r_pb, pbd);
+    sg.put(r_or, order);
+    sg.put(r_ip, item_prefix);
+    sg.put(r_ep, emit_prefix);
+    sg.put(r_cp, collect_prefix);
+    sg.fill(r_sl, 0);
+    sg.fill(r_nl, 0xff);
+    sg.fill(r_ab, 0);
+    sg.fill(r_gr, 0xff);
+    sg.put(r_bm, clause_bitmaps);
+    RGPU_TRY(sg.upload(stream));
+    HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
+    HIP_TRY(c->phrase_keys.reserve((size_t)slots + 64, 0, stream));
+    const int64_t redo_cap = phrase_redo_cap(slots);  // (sized from the slots of ALL planes: any of them may hand candidates on)
+    HIP_TRY(c->phrase_redo.reserve((size_t)redo_cap + 64, 0, stream));
+    HIP_TRY(c->phrase_count.reserve(nv, 0, stream));
+    HIP_TRY(hipMemsetAsync(c->phrase_count.p, 0, nv * 8, stream));
+    HIP_TRY(hipMemsetAsync(c->phrase_keys.p, 0, (size_t)slots * 8, stream));  // (a 64-candidate group past a query's count is never written)
+    const int k_emit = std::min<int>(k, 64);
+    const bool chunked = k <= RGPU_PASS_K && collect_items > 0;
+    HIP_TRY(c->S->d_partial_keys.reserve(std::max((size_t)items * (size_t)k_emit, chunked ? (size_t)collect_items * (size_t)k : (size_t)0), 0, stream));
+    HIP_TRY(c->S->d_partial_counts.reserve((size_t)std::max(items, chunked ? collect_items : (int64_t)0), 0, stream));
+    HIP_TRY(c->S->d_tau.reserve(nq, 0, stream));
+    HIP_TRY(c->S->d_touched.reserve(nq * 2, 0, stream));
+    HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, nq * 8, stream));
+    HIP_TRY(hipMemsetAsync(c->S->d_touched.p, 0, nq * 16, stream));
+    HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));
+    const int64_t *d_ip = sg.dev(r_ip), *d_ep = sg.dev(r_ep), *d_cp = sg.dev(r_cp);
+    const int32_t *d_sl = sg.dev(r_sl), *d_nl = sg.dev(r_nl);
+    const PhraseBoolDev* d_pb = sg.dev(r_pb);
+    const SegView sv = seg_view(seg);
+    const bool legacy = seg->version < 1;
+    {
+      TimedLaunch tl(c, stream, "k_search_and(phrase-bool candidates)", 0);
+      const int xcd_chunk = and_xcd_chunk(seg);
+      const unsigned grid = wg_count(and_grid((items + AND_WG_WAVES - 1) / AND_WG_WAVES, xcd_chunk));
+      auto go = [&](auto kern) {
+        RGPU_LAUNCH(kern, dim3(grid), dim3(AND_WG_THREADS), 0, stream, sv, (const DevQuery*)sg.dev(r_cq), (const DevTerm*)sg.dev(r_cdt), d_ip, (int)n_queries, items,
+                    blocks_per_item, k_emit, c->S->d_partial_keys.p, c->S->d_partial_counts.p, c->S->d_tau.p, c->S->d_touched.p, d_ep, c->phrase_count.p,
+                    (void*)c->phrase_docs.p, (const unsigned long long*)nullptr, (const int32_t*)nullptr,
+                    clause_bitmaps.empty() ? (const TermBitmap*)nullptr : sg.dev(r_bm), xcd_chunk);
+      };
+      if (any_not) { if (legacy) go(k_search_and<true, false, true, false>); else go(k_search_and<false, false, true, false>); }
+      else { if (legacy) go(k_search_and<true, false, false, false>); else go(k_search_and<false, false, false, false>); }
+    }
+    if (groups0 > 0) {
+      const unsigned ggrid = wg_count((groups0 + WG_WAVES - 1) / WG_WAVES);
+      if (max_planes > 1) {
+        TimedLaunch tl(c, stream, "k_phrase_bool_fanout", 0);
+        RGPU_LAUNCH(k_phrase_bool_fanout, dim3(ggrid), dim3(WG_THREADS), 0, stream, d_pb, d_ep, c->phrase_count.p, c->phrase_docs.p, (int)n_queries, groups0);
+      }
+      PhraseMatchStage ms{sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ppt), d_ep, d_sl, sg.dev(r_gr), (int32_t)nv, slots, redo_cap, true, false, false, false,
+                          nullptr, nullptr, nullptr, 0};
+      RGPU_TRY(phrase_match_stage(seg, stream, ms));
+      {
+        TimedLaunch tl(c, stream, "k_phrase_bool_score", 0);
+        auto go = [&](auto kern) {
+          RGPU_LAUNCH(kern, dim3(ggrid), dim3(WG_THREADS), 0, stream, sv, d_pb, (const int32_t*)sg.dev(r_or), (const DevTerm*)sg.dev(r_sdt), d_ep,
+                      (const unsigned long long*)c->phrase_count.p, (int)n_queries, groups0, c->phrase_keys.p, c->d_err);
+        };
+        if (legacy) go(k_phrase_bool_score<true>); else go(k_phrase_bool_score<false>);
+      }
+    }
+    if (chunked) {
+      {
+        TimedLaunch tl(c, stream, "k_phrase_collect", 0);
+        const unsigned grid = wg_count((collect_items + WG_WAVES - 1) / WG_WAVES);
+        if (k > 64)
+          RGPU_LAUNCH(k_phrase_collect_items<true>, dim3(grid), dim3(WG_THREADS), 0, stream, d_cp, d_ep, c->phrase_count.p, c->phrase_keys.p,
+                      (const int32_t*)sg.dev(r_ab), (int)n_queries, collect_items, (int)k, c->S->d_partial_keys.p, c->S->d_partial_counts.p);
+        else
+          RGPU_LAUNCH(k_phrase_collect_items<false>, dim3(grid), dim3(WG_THREADS), 0, stream, d_cp, d_ep, c->phrase_count.p, c->phrase_keys.p,
+                      (const int32_t*)sg.dev(r_ab), (int)n_queries, collect_items, (int)k, c->S->d_partial_keys.p, c->S->d_partial_counts.p);
+      }
+      if (k > 64) launch_merge<true>(c, stream, n_queries, k, d_cp, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
+      else launch_merge<false>(c, stream, n_queries, k, d_cp, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
+    } else {
+      TimedLaunch tl(c, stream, "k_phrase_collect", 0);
+      const unsigned grid = wg_count((n_queries + WG_WAVES - 1) / WG_WAVES);
+      if (k > 64)
+        RGPU_LAUNCH(k_phrase_collect<true>, dim3(grid), dim3(WG_THREADS), 0, stream, d_ep, c->phrase_count.p, c->phrase_keys.p,
+                    (const int32_t*)c->phrase_docs.p, d_sl, d_nl, (int)n_queries, (int)k, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
+      else
+        RGPU_LAUNCH(k_phrase_collect<false>, dim3(grid), dim3(WG_THREADS), 0, stream, d_ep, c->phrase_count.p, c->phrase_keys.p,
+                    (const int32_t*)c->phrase_docs.p, d_sl, d_nl, (int)n_queries, (int)k, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
+    }
+    HIP_TRY(launch_status());
+    // a refused call writes nothing: the match stage's verdict first, the rows after it
+    HIP_TRY(hipMemcpyAsync(&err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    RGPU_TRY(phrase_match_status(err, "a doc holds one of an exact phrase's terms more than 1024 times", "internal: a conjunction match was not found again"));
+  }
+  hipError_t e1 = hipMemcpyAsync(hits_out, c->host_api_hits.p, nq * (size_t)k * sizeof(HitOut), hipMemcpyDeviceToHost, stream);
+  hipError_t e2 = hipMemcpyAsync(total_hits_out, c->host_api_totals.p, nq * 8, hipMemcpyDeviceToHost, stream);
+  hipError_t e3 = hipStreamSynchronize(stream);
+  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(RGPU_ERR_RUNTIME, "device to host copy failed");
+  return RGPU_OK;
 }
 
 // ---- QueryRescorer ------------------------------------------------------------------------------------------------------------

@@ -274,6 +274,8 @@ class BooleanQuery:
             raise RgpuError(-2, "boolean query should at least contain one inner query!")
         if len(must_nots) == 0 and len(musts) + len(shoulds) + len(filters) == 1:
             if filters:   # ConstantScoreQuery::with_boost(filter, 0.0) (boolean_query.rs:70-73): every match scores 0
+                if isinstance(filters[0], PhraseQuery):
+                    return PhraseQuery(filters[0].terms, filters[0].positions, 0.0, filters[0].slop)
                 return TermQuery(filters[0].term, 0.0)
             return (list(musts) + list(shoulds))[0]
         if msm > 255:
@@ -282,8 +284,9 @@ class BooleanQuery:
             msm = 0   # nothing for it to count (beside MUST clauses it has no effect anyway: ReqOptScorer only advances the optional scorer)
         # (a clause that is itself a BooleanQuery builds, as it does in the reference: whether the GPU path serves the tree is
         # decided when it is searched — GpuIndexSearcher.flatten_nested / cpu_fallback)
-        if any(not isinstance(q, (TermQuery, BooleanQuery)) for q in list(musts) + list(shoulds) + list(must_nots) + list(filters)):
-            raise RgpuError(-5, "only term and boolean clauses are known to this mirror")
+        # (so does a PhraseQuery clause: GpuIndexSearcher.phrase_bool_parts says which trees over phrases the GPU path serves)
+        if any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery)) for q in list(musts) + list(shoulds) + list(must_nots) + list(filters)):
+            raise RgpuError(-5, "only term, phrase and boolean clauses are known to this mirror")
         return BooleanQuery(list(musts), list(shoulds), msm, list(must_nots), list(filters))
 
     def normalized(self):
@@ -415,12 +418,19 @@ class BooleanQuery:
             return None
         return c
 
+    def has_phrases(self):
+        """some clause of this query (not of a nested one) is a PhraseQuery"""
+        return any(isinstance(q, PhraseQuery) for q in self.must_queries + self.should_queries + self.must_not_queries + self.filter_queries)
+
     def required_clauses(self):
         """MUST clauses followed by the FILTER clauses as zero-weight MUST clauses (BooleanWeight puts both into must_weights)."""
         return list(self.must_queries) + [TermQuery(f.term, 0.0) for f in self.filter_queries]
 
-    def extract_terms(self):  # boolean_query.rs:124-145: MUST, SHOULD and FILTER clauses only
-        return list(self.must_queries) + list(self.should_queries) + list(self.filter_queries)
+    def extract_terms(self):  # boolean_query.rs:124-145: MUST, SHOULD and FILTER clauses only (a phrase clause: its terms)
+        out = []
+        for q in list(self.must_queries) + list(self.should_queries) + list(self.filter_queries):
+            out.extend(TermQuery(t, q.boost) for t in q.terms) if isinstance(q, PhraseQuery) else out.append(q)
+        return out
 
 
 class DisjunctionMaxQuery:
@@ -829,12 +839,89 @@ class GpuIndexSearcher:
             out[rows] = part
         return out
 
+    @staticmethod
+    def phrase_bool_parts(query):
+        """A BooleanQuery with PhraseQuery clauses -> (required clauses in BooleanWeight::must_weights order: MUST clauses in query
+        order, then FILTER clauses; how many of them are MUST clauses; MUST_NOT TermQuery clauses) when the GPU path serves the tree
+        (rgpu_search_phrase_bool_batch), else UnsupportedOperation: a sloppy phrase clause (inside a conjunction the reference matches
+        it on its approximation and scores a stale sloppy_freq — not reproduced), a phrase under SHOULD or MUST_NOT, a SHOULD clause
+        of any kind beside a required phrase (ReqOptScorer), a nested BooleanQuery clause beside a phrase, more than 4 phrases."""
+        if any(isinstance(q, PhraseQuery) for q in query.should_queries + query.must_not_queries):
+            raise RgpuError(-5, "a phrase clause under SHOULD or MUST_NOT is not served by the GPU path")
+        if query.should_queries:
+            raise RgpuError(-5, "SHOULD clauses beside a required phrase are not served by the GPU path")
+        required = list(query.must_queries) + list(query.filter_queries)
+        if any(isinstance(q, BooleanQuery) for q in required + query.must_not_queries):
+            raise RgpuError(-5, "nested boolean clauses beside a phrase are not served by the GPU path")
+        phrases = [q for q in required if isinstance(q, PhraseQuery)]
+        if any(q.slop > 0 for q in phrases):
+            raise RgpuError(-5, "a sloppy phrase inside a boolean query is not served by the GPU path")
+        if len(phrases) > _lib.MAX_BOOL_PHRASES:
+            raise RgpuError(-5, "more than %d phrases in one boolean query" % _lib.MAX_BOOL_PHRASES)
+        return required, len(query.must_queries), list(query.must_not_queries)
+
+    def pack_phrase_bool(self, queries, leaf):
+        """BooleanQuery objects with phrase clauses -> the (rgpu_phrase_bool_query[], rgpu_phrase_query[], rgpu_phrase_term[],
+        rgpu_query_term[]) of rgpu_search_phrase_bool_batch for one leaf. A FILTER clause rides with weight 0 (needs_scores = false)."""
+        parts = [self.phrase_bool_parts(q) for q in queries]
+        phrase_qs, filtered, term_cs = [], [], []
+        qs = np.zeros(len(queries), dtype=_lib.PHRASE_BOOL_QUERY_DTYPE)
+        for i, (required, n_must, nots) in enumerate(parts):
+            slots = [s for s, c in enumerate(required) if isinstance(c, PhraseQuery)]
+            mine = [TermQuery(c.term, c.boost if s < n_must else 0.0) for s, c in enumerate(required) if not isinstance(c, PhraseQuery)]
+            qs[i]["n_phrases"], qs[i]["first_phrase"] = len(slots), len(phrase_qs)
+            qs[i]["n_terms"], qs[i]["first_term"], qs[i]["n_must_not"] = len(mine), len(term_cs), len(nots)
+            qs[i]["phrase_slot"][:len(slots)] = slots
+            phrase_qs += [required[s] for s in slots]
+            filtered += [s >= n_must for s in slots]
+            term_cs += mine + nots
+        ps, pts = self.pack_phrases(phrase_qs, leaf)
+        ps["weight"][np.array(filtered, dtype=bool)] = 0.0
+        ps["next_limit"] = 0
+        byte_terms = [c.term for c in term_cs if isinstance(c.term, bytes)]
+        if byte_terms:
+            leaf.resolve(byte_terms)
+            self.leaves[self._stats_leaf].resolve(byte_terms)
+        ts = np.zeros(len(term_cs), dtype=QUERY_TERM_DTYPE)
+        for at, c in enumerate(term_cs):
+            w, table = self._weight(c.term, c.boost)
+            st = leaf.term_state(c.term)
+            if st is not None:
+                ts[at]["state"] = st
+            else:
+                ts[at]["state"]["doc_freq"] = 0
+                ts[at]["state"]["skip_offset"] = -1
+                ts[at]["state"]["singleton_doc_id"] = -1
+            ts[at]["weight"], ts[at]["sim_table"] = w, table
+        return qs, ps, pts, ts
+
     def search_batch(self, queries, k):
-        """-> (hits[n][k] structured {doc, score}, total_hits[n]) merged over all leaves."""
-        per_leaf = []
-        for leaf in self.leaves:
-            qs, ts = self.pack(queries, leaf)
-            per_leaf.append(leaf.segment.search_batch(qs, ts, k))
+        """-> (hits[n][k] structured {doc, score}, total_hits[n]) merged over all leaves. A batch may mix term / boolean / dismax /
+        boosting queries (rgpu_search_batch), PhraseQuery rows (rgpu_search_phrase_batch) and BooleanQuery rows with phrase clauses
+        (rgpu_search_phrase_bool_batch): one call per kind and leaf, rows keep their order."""
+        kinds = [1 if isinstance(q, PhraseQuery) else (2 if isinstance(q, BooleanQuery) and q.has_phrases() else 0) for q in queries]
+        if not any(kinds):
+            per_leaf = []
+            for leaf in self.leaves:
+                qs, ts = self.pack(queries, leaf)
+                per_leaf.append(leaf.segment.search_batch(qs, ts, k))
+        else:
+            rows = [np.flatnonzero(np.array(kinds) == kind) for kind in (0, 1, 2)]
+            groups = [[queries[i] for i in r] for r in rows]
+            for q in groups[2]:   # refused before any leaf is touched
+                self.phrase_bool_parts(q)
+            per_leaf = []
+            for leaf in self.leaves:
+                hits, totals = np.zeros((len(queries), k), dtype=_lib.HIT_DTYPE), np.zeros(len(queries), dtype=np.int64)
+                if groups[0]:
+                    qs, ts = self.pack(groups[0], leaf)
+                    hits[rows[0]], totals[rows[0]] = leaf.segment.search_batch(qs, ts, k)
+                if groups[1]:
+                    qs, ts = self.pack_phrases(groups[1], leaf)
+                    hits[rows[1]], totals[rows[1]] = leaf.segment.search_phrase_batch(qs, ts, k)
+                if groups[2]:
+                    hits[rows[2]], totals[rows[2]] = leaf.segment.search_phrase_bool_batch(*self.pack_phrase_bool(groups[2], leaf), k)
+                per_leaf.append((hits, totals))
         if len(per_leaf) == 1:
             return per_leaf[0]
         return self._merge_leaves(per_leaf, len(queries), k)

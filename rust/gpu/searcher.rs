@@ -344,6 +344,12 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
     fn try_gpu(&self, query: &dyn Query<C>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
         if k == 0 || k > RGPU_MAX_K as usize { return Ok(false); }
         if let Some(p) = query.as_any().downcast_ref::<PhraseQuery>() { return self.try_phrase(p, top, k); }
+        if let Some(b) = query.as_any().downcast_ref::<BooleanQuery<C>>() {
+            let (must, should, filter, must_not, _) = b.clauses();
+            if must.iter().chain(should).chain(filter).chain(must_not).any(|q| q.as_any().downcast_ref::<PhraseQuery>().is_some()) {
+                return self.try_phrase_bool(b, top, k);
+            }
+        }
         let flat = match self.flatten(query) { Some(f) => f, None => return Ok(false) };
         let n = flat.n_clauses();
         if n > RGPU_MAX_QUERY_TERMS as usize { return Ok(false); }
@@ -431,6 +437,82 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             let mut total: i64 = 0;
             check(unsafe { rgpu_search_phrase_batch(self.leaves[leaf.ord].seg, &q, 1, pterms.as_ptr(), pterms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total) },
                   self.ctx)?;
+            Self::hand_over(top, &hits, total);
+        }
+        Ok(true)
+    }
+
+    /// BooleanQuery whose MUST / FILTER clauses hold 1..=RGPU_MAX_BOOL_PHRASES exact PhraseQuery clauses beside TermQuery clauses, with
+    /// MUST_NOT TermQuery clauses: "+\"a b\" +c -d #e" -> rgpu_search_phrase_bool_batch per leaf. phrase_slot = the phrase's index in
+    /// BooleanWeight::must_weights (MUST clauses in query order, then FILTER clauses, boolean_query.rs:96-125); a FILTER clause rides
+    /// with weight 0 (needs_scores = false). The library sorts the children by cost per leaf and sums in that order, as
+    /// ConjunctionScorer does. Ok(false) — the CPU searcher — under try_phrase's rules (another field, a leaf without positions, a
+    /// phrase of the wrong size) and for every shape the library does not serve: a sloppy phrase clause (inside a conjunction the CPU
+    /// matches it on its approximation and scores a stale sloppy_freq), a phrase under SHOULD or MUST_NOT, a SHOULD clause or a
+    /// nested BooleanQuery beside a phrase, more than RGPU_MAX_BOOL_PHRASES phrases, more than RGPU_MAX_QUERY_TERMS clause terms.
+    fn try_phrase_bool(&self, b: &BooleanQuery<C>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
+        let (must, should, filter, must_not, _) = b.clauses();
+        if !should.is_empty() || self.leaves.iter().any(|l| !l.has_positions) { return Ok(false); }
+        let term_of = |q: &Box<dyn Query<C>>| q.as_any().downcast_ref::<TermQuery>().filter(|t| t.term.field == self.field);
+        let mut phrases: Vec<(&PhraseQuery, usize, bool)> = Vec::new(); // (the phrase, its slot in must_weights, under FILTER)
+        let mut required: Vec<(&TermQuery, bool)> = Vec::new();
+        for (slot, q) in must.iter().chain(filter.iter()).enumerate() {
+            let filtering = slot >= must.len();
+            if let Some(p) = q.as_any().downcast_ref::<PhraseQuery>() {
+                let (field, terms, positions, slop) = p.parts();
+                if field != self.field || slop != 0 || terms.len() < 2 || terms.len() > RGPU_MAX_PHRASE_TERMS as usize || terms.len() != positions.len() {
+                    return Ok(false);
+                }
+                phrases.push((p, slot, filtering));
+            } else if let Some(t) = term_of(q) {
+                required.push((t, filtering));
+            } else {
+                return Ok(false);
+            }
+        }
+        if phrases.is_empty() || phrases.len() > RGPU_MAX_BOOL_PHRASES as usize { return Ok(false); }
+        let mut prohibited: Vec<&TermQuery> = Vec::with_capacity(must_not.len());
+        for q in must_not {
+            match term_of(q) { Some(t) => prohibited.push(t), None => return Ok(false) }
+        }
+        let n_phrase_terms: usize = phrases.iter().map(|(p, _, _)| p.parts().1.len()).sum();
+        if n_phrase_terms + required.len() + prohibited.len() > RGPU_MAX_QUERY_TERMS as usize { return Ok(false); }
+        let mut phrase_weights = Vec::with_capacity(phrases.len());
+        for (p, _, filtering) in &phrases {
+            let term_refs: Vec<&Term> = p.parts().1.iter().collect();
+            let (weight, sim_table) = self.weight_of(&term_refs, 1.0)?;
+            phrase_weights.push((if *filtering { 0.0 } else { weight }, sim_table));
+        }
+        let mut term_weights = Vec::with_capacity(required.len());
+        for (t, filtering) in &required {
+            let (weight, sim_table) = self.weight_of(&[&t.term], t.boost)?;
+            term_weights.push((if *filtering { 0.0 } else { weight }, sim_table));
+        }
+        let mut bq = RgpuPhraseBoolQuery { n_phrases: phrases.len() as i32, first_phrase: 0, n_terms: required.len() as i32, first_term: 0,
+                                           n_must_not: prohibited.len() as i32, phrase_slot: [0; 4], reserved: [0; 3] };
+        for (i, (_, slot, _)) in phrases.iter().enumerate() { bq.phrase_slot[i] = *slot as i32; }
+        for leaf in self.cpu.reader().leaves() {
+            let mut pqs = Vec::with_capacity(phrases.len());
+            let mut pterms: Vec<RgpuPhraseTerm> = Vec::with_capacity(n_phrase_terms);
+            for (i, (p, _, _)) in phrases.iter().enumerate() {
+                let (_, terms, positions, _) = p.parts();
+                let mine = self.phrase_terms(&leaf, terms, positions)?;
+                pqs.push(RgpuPhraseQuery { n_terms: mine.len() as i32, first_term: pterms.len() as i32, weight: phrase_weights[i].0, sim_table: phrase_weights[i].1,
+                                           slop: 0, next_limit: 0 });
+                pterms.extend(mine);
+            }
+            let mut terms = Vec::with_capacity(required.len() + prohibited.len());
+            for (i, (t, _)) in required.iter().enumerate() {
+                terms.push(RgpuQueryTerm { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: term_weights[i].0, sim_table: term_weights[i].1 });
+            }
+            for t in &prohibited {
+                terms.push(RgpuQueryTerm { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: 0.0, sim_table: 0 }); // never scored
+            }
+            let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
+            let mut total: i64 = 0;
+            check(unsafe { rgpu_search_phrase_bool_batch(self.leaves[leaf.ord].seg, &bq, 1, pqs.as_ptr(), pqs.len() as i32, pterms.as_ptr(), pterms.len() as i32,
+                                                         if terms.is_empty() { std::ptr::null() } else { terms.as_ptr() }, terms.len() as i32, k as i32,
+                                                         hits.as_mut_ptr(), &mut total) }, self.ctx)?;
             Self::hand_over(top, &hits, total);
         }
         Ok(true)
