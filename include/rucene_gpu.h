@@ -698,6 +698,47 @@ int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_phrase_bool_
                                       const rgpu_query_term* terms, int32_t n_terms_total,
                                       int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out);
 
+/* BooleanQuery whose clauses are all SHOULD (and MUST_NOT) with exact PhraseQuery clauses among them: "a b" "c d" e -f.
+ * BooleanWeight::create_scorer builds ONE DisjunctionSumScorer over the SHOULD scorers that exist in the leaf, even for a single one
+ * (boolean_query.rs:217-234), and wraps it in a ReqNotScorer over the MUST_NOT clauses (:235-251, :270-275). With fewer than ten
+ * children the scorer is the SimpleQueue arm (disjunction_scorer.rs:41): a doc's score is 0.0f32, then += each child that sits on
+ * the doc, in clause order (:213-225); min_should_match counts the children on the doc (:317-329). ExactPhraseScorer's
+ * approximate_next / approximate_advance are its real next / advance — do_next runs to an actual phrase match
+ * (phrase_scorer.rs:255-294) — so inside a disjunction an exact phrase is a plain iterator over its matching docs whose score() is
+ * BM25(phrase freq, norm) (:245-251). Nothing is two-phase, next_limit plays no part, deleted docs are simply not collected.
+ * Served: no MUST and no FILTER clause; 1..9 SHOULD clauses in all, of which 1..RGPU_MAX_BOOL_PHRASES are exact phrases and the rest
+ * TermQuery clauses, at any positions; any number of MUST_NOT term clauses while the query's DISTINCT terms number at most
+ * RGPU_MAX_QUERY_TERMS; min_should_match 0..255; k up to RGPU_MAX_K. A phrase with a term the leaf lacks and a term clause the leaf
+ * lacks drop out of the disjunction (min_should_match stays as it is); a query whose every SHOULD clause dropped out matches nothing;
+ * a MUST_NOT term the leaf lacks excludes nothing. A phrase of weight 0 still matches its docs (they score +0.0 and count).
+ * NOT served (RGPU_ERR_UNSUPPORTED, the caller keeps these on its CPU path): a sloppy phrase clause (two-phase: as a child the
+ * reference's SloppyPhraseScorer matches on its approximation and scores a stale sloppy_freq); ten or more SHOULD clauses with a
+ * phrase among them (the heap-order arm); more than RGPU_MAX_BOOL_PHRASES phrases; more than RGPU_MAX_QUERY_TERMS distinct terms; a
+ * doc that holds a phrase term more than 1024 times. A phrase under MUST_NOT cannot be written in this struct. */
+typedef struct rgpu_phrase_or_query {
+  int32_t n_phrases;         /* 1..RGPU_MAX_BOOL_PHRASES exact SHOULD phrases (slop must be 0; next_limit is ignored) */
+  int32_t first_phrase;      /* ... index of the first one in `phrases` */
+  int32_t n_terms;           /* SHOULD term clauses, in query order; n_phrases + n_terms <= 9 */
+  int32_t first_term;        /* index of the first one in `terms`; the n_must_not MUST_NOT term clauses follow the SHOULD ones */
+  int32_t n_must_not;
+  int32_t min_should_match;  /* 0..255 (BooleanQuery::build makes 0 a 1: both collect every doc a clause holds) */
+  int32_t phrase_slot[RGPU_MAX_BOOL_PHRASES]; /* position of phrase i in BooleanWeight::should_weights (the SHOULD clauses in query
+                                                 order), 0 <= slot < n_phrases + n_terms; the term clauses take the other positions in
+                                                 order */
+  int32_t reserved[2];
+} rgpu_phrase_or_query;
+/* One leaf of IndexSearcher::search(BooleanQuery over SHOULD phrases and terms, TopDocsCollector(k)). `phrases` / `phrase_terms` as
+ * the queries / terms of rgpu_search_phrase_batch, `terms` as those of rgpu_search_batch. Outputs and calling protocol as
+ * rgpu_search_batch; docs, scores and total_hits are bit-exact with the CPU scorers.
+ * Refused, nothing written: what rgpu_search_phrase_batch refuses, a phrase_slot out of range or named twice, index ranges
+ * outside the arrays, a negative clause count, min_should_match outside 0..255, an unknown sim_table (RGPU_ERR_ILLEGAL_ARGUMENT); no
+ * positions attached (RGPU_ERR_ILLEGAL_STATE); the shapes listed above as not served, k above RGPU_MAX_K (RGPU_ERR_UNSUPPORTED). */
+int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phrase_or_query* queries, int32_t n_queries,
+                                    const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                    const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                    const rgpu_query_term* terms, int32_t n_terms_total,
+                                    int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out);
+
 /* ---- second-pass scoring (QueryRescorer)------------------------------------------------------------------------------ */
 /* search/scorer/rescorer.rs: QueryRescorer re-ranks the top `window_size` hits of a first pass with a second query —
  * per hit the second query's scorer is advanced to the doc and the two scores are combined (combine_score :337-352:

@@ -40,6 +40,10 @@ MAX_BOOL_PHRASES = 4   # RGPU_MAX_BOOL_PHRASES
 PHRASE_BOOL_QUERY_DTYPE = np.dtype([("n_phrases", "<i4"), ("first_phrase", "<i4"), ("n_terms", "<i4"), ("first_term", "<i4"), ("n_must_not", "<i4"),
                                     ("phrase_slot", "<i4", (MAX_BOOL_PHRASES,)), ("reserved", "<i4", (3,))], align=True)
 assert PHRASE_BOOL_QUERY_DTYPE.itemsize == 48
+PHRASE_OR_QUERY_DTYPE = np.dtype([("n_phrases", "<i4"), ("first_phrase", "<i4"), ("n_terms", "<i4"), ("first_term", "<i4"), ("n_must_not", "<i4"),
+                                  ("min_should_match", "<i4"), ("phrase_slot", "<i4", (MAX_BOOL_PHRASES,)), ("reserved", "<i4", (2,))], align=True)
+assert PHRASE_OR_QUERY_DTYPE.itemsize == 48
+PHRASE_OR_MAX_SHOULD = 9   # ten or more SHOULD clauses sum in heap order (disjunction_scorer.rs:41-45)
 FIELD_INFO_DTYPE = np.dtype([("number", "<i4"), ("index_options", "<i4"), ("has_payloads", "<i4"), ("flags", "<i4")], align=True)
 FIELD_STATS_DTYPE = np.dtype([("num_terms", "<i8"), ("sum_total_term_freq", "<i8"), ("sum_doc_freq", "<i8"), ("doc_count", "<i4"),
                               ("longs_size", "<i4")], align=True)
@@ -61,7 +65,7 @@ STATUS_NAMES = {0: "OK", -1: "IllegalState", -2: "IllegalArgument", -3: "Unexpec
 # every symbol include/rucene_gpu.h declares (tests/test_abi.py checks the header and this list agree)
 EXPORTS = [
     "rgpu_init", "rgpu_shutdown", "rgpu_last_error", "rgpu_abi_version", "rgpu_device_name", "rgpu_segment_upload",
-    "rgpu_segment_upload_field", "rgpu_segment_release_prepared_terms", "rgpu_segment_get_footprint", "rgpu_segment_attach_positions", "rgpu_segment_attach_payloads", "rgpu_decode_positions", "rgpu_decode_positions_device", "rgpu_search_phrase_batch", "rgpu_search_phrase_bool_batch", "rgpu_rescore_batch", "rgpu_rescore_phrase_batch",
+    "rgpu_segment_upload_field", "rgpu_segment_release_prepared_terms", "rgpu_segment_get_footprint", "rgpu_segment_attach_positions", "rgpu_segment_attach_payloads", "rgpu_decode_positions", "rgpu_decode_positions_device", "rgpu_search_phrase_batch", "rgpu_search_phrase_bool_batch", "rgpu_search_phrase_or_batch", "rgpu_rescore_batch", "rgpu_rescore_phrase_batch",
     "rgpu_segment_free", "rgpu_segment_version", "rgpu_segment_prepare_terms", "rgpu_decode_terms",
     "rgpu_decode_terms_device", "rgpu_advance_batch", "rgpu_sim_table_upload", "rgpu_search_batch",
     "rgpu_search_batch_device", "rgpu_merge_topk_device", "rgpu_bm25_compute_weight", "rgpu_bm25_encode_norm", "rgpu_bm25_term_weights",
@@ -157,6 +161,7 @@ def lib():
         "rgpu_decode_positions_device": (i32, [vp, vp, vp, C.c_int64, vp, vp]),
         "rgpu_search_phrase_batch": (i32, [vp, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_phrase_bool_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
+        "rgpu_search_phrase_or_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_rescore_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32]),
         "rgpu_rescore_phrase_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32]),
         "rgpu_decode_terms": (i32, [vp, vp, i64, vp, vp]),
@@ -705,6 +710,20 @@ class Segment:
         totals = np.zeros(q.size, dtype=np.int64)
         _check(lib().rgpu_search_phrase_bool_batch(self._h, q.ctypes.data, q.size, p.ctypes.data, p.size, pt.ctypes.data, pt.size,
                                                    t.ctypes.data if t.size else None, t.size, k, hits.ctypes.data, totals.ctypes.data))
+        return hits, totals
+
+    def search_phrase_or_batch(self, queries, phrases, phrase_terms, terms, k):
+        """BooleanQuery rows of SHOULD / MUST_NOT clauses with exact phrases among the SHOULD ones (rgpu_search_phrase_or_batch):
+        `queries` PHRASE_OR_QUERY_DTYPE, `phrases` / `phrase_terms` as for search_phrase_batch, `terms` QUERY_TERM_DTYPE (may be
+        empty). A refusal raises and returns nothing."""
+        q = np.ascontiguousarray(queries, dtype=PHRASE_OR_QUERY_DTYPE)
+        p = np.ascontiguousarray(phrases, dtype=PHRASE_QUERY_DTYPE)
+        pt = np.ascontiguousarray(phrase_terms, dtype=PHRASE_TERM_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=QUERY_TERM_DTYPE)
+        hits = np.zeros((q.size, k), dtype=HIT_DTYPE)
+        totals = np.zeros(q.size, dtype=np.int64)
+        _check(lib().rgpu_search_phrase_or_batch(self._h, q.ctypes.data, q.size, p.ctypes.data, p.size, pt.ctypes.data, pt.size,
+                                                 t.ctypes.data if t.size else None, t.size, k, hits.ctypes.data, totals.ctypes.data))
         return hits, totals
 
     def rescore_batch(self, queries, terms, requests, hits, finish=True):

@@ -395,6 +395,38 @@ struct PhraseBooleanQuery : Query {
   }
 };
 
+// BooleanQuery whose clauses are all SHOULD / MUST_NOT with exact PhraseQuery clauses among the SHOULD ones: "a b" "c d" e -f
+// (rgpu_search_phrase_or_batch). `should`: BooleanWeight::should_weights — the SHOULD clauses in query order, a phrase or a term each:
+// ONE DisjunctionSumScorer over those that exist in the leaf (boolean_query.rs:217-234), summed in that order. Only the shapes the GPU
+// path serves can be written here (no MUST, no FILTER, no phrase under MUST_NOT, no nested BooleanQuery); a sloppy phrase clause, more
+// than RGPU_MAX_BOOL_PHRASES phrases or ten or more SHOULD clauses (the heap-order arm) are UnsupportedOperation when the query is
+// searched — the caller's CPU path.
+struct PhraseDisjunctionQuery : Query {
+  struct Should {
+    std::shared_ptr<PhraseQuery> phrase;  // null: a term clause
+    TermQuery term{int64_t(-1)};
+  };
+  std::vector<Should> should_queries;
+  std::vector<TermQuery> must_not_queries;
+  int32_t min_should_match = 1;  // BooleanQuery::build: 0 becomes 1 when there is no MUST clause
+  PhraseDisjunctionQuery& should(PhraseQuery p) { should_queries.push_back(Should{std::make_shared<PhraseQuery>(std::move(p)), TermQuery(int64_t(-1))}); return *this; }
+  PhraseDisjunctionQuery& should(TermQuery t) { should_queries.push_back(Should{nullptr, std::move(t)}); return *this; }
+  PhraseDisjunctionQuery& must_not(TermQuery t) { must_not_queries.push_back(std::move(t)); return *this; }
+  PhraseDisjunctionQuery& min_should(int32_t n) { min_should_match = n > 0 ? n : 1; return *this; }
+  // refused before any leaf is touched
+  void check_served() const {
+    int n_phrases = 0;
+    for (const Should& c : should_queries) {
+      if (!c.phrase) continue;
+      ++n_phrases;
+      if (c.phrase->slop > 0) throw Error(RGPU_ERR_UNSUPPORTED, "a sloppy phrase inside a boolean query is not served by the GPU path");
+    }
+    if (n_phrases < 1 || n_phrases > RGPU_MAX_BOOL_PHRASES) throw Error(RGPU_ERR_UNSUPPORTED, "a disjunction over phrases holds 1..RGPU_MAX_BOOL_PHRASES phrases");
+    if (should_queries.size() > 9) throw Error(RGPU_ERR_UNSUPPORTED, "ten or more SHOULD clauses with a phrase among them sum in heap order");
+    if (min_should_match > 255) throw Error(RGPU_ERR_UNSUPPORTED, "min_should_match above 255");
+  }
+};
+
 // RescoreRequest (search/scorer/rescorer.rs:67-116): how a second query's score is folded into the first pass's
 struct RescoreRequest {
   const Query* query = nullptr;  // TermQuery, an all-MUST / all-SHOULD BooleanQuery, or a PhraseQuery (sloppy: no repeated term)
@@ -653,20 +685,24 @@ class GpuIndexSearcher {
   }
 
   // the batched form the hardware wants: one launch set per leaf for many queries
-  // (PhraseQuery rows go through rgpu_search_phrase_batch, PhraseBooleanQuery rows through rgpu_search_phrase_bool_batch, the rest
-  // through rgpu_search_batch: one call per kind and leaf, rows keep their order)
+  // (PhraseQuery rows go through rgpu_search_phrase_batch, PhraseBooleanQuery rows through rgpu_search_phrase_bool_batch,
+  // PhraseDisjunctionQuery rows through rgpu_search_phrase_or_batch, the rest through rgpu_search_batch: one call per kind and leaf,
+  // rows keep their order)
   std::vector<TopDocs> search_many(const std::vector<const Query*>& queries, size_t k) {
-    std::vector<size_t> phrase_rows, bool_rows, plain_rows;
+    std::vector<size_t> phrase_rows, bool_rows, or_rows, plain_rows;
     for (size_t i = 0; i < queries.size(); ++i) {
       if (dynamic_cast<const PhraseQuery*>(queries[i])) phrase_rows.push_back(i);
       else if (dynamic_cast<const PhraseBooleanQuery*>(queries[i])) bool_rows.push_back(i);
+      else if (dynamic_cast<const PhraseDisjunctionQuery*>(queries[i])) or_rows.push_back(i);
       else plain_rows.push_back(i);
     }
-    if (!phrase_rows.empty() || !bool_rows.empty()) {
+    if (!phrase_rows.empty() || !bool_rows.empty() || !or_rows.empty()) {
       std::vector<TopDocs> out(queries.size());
       auto place = [&](const std::vector<size_t>& rows, std::vector<TopDocs> got) { for (size_t i = 0; i < rows.size(); ++i) out[rows[i]] = std::move(got[i]); };
       std::vector<const PhraseBooleanQuery*> bools;
       for (size_t i : bool_rows) { bools.push_back(static_cast<const PhraseBooleanQuery*>(queries[i])); bools.back()->check_served(); }
+      std::vector<const PhraseDisjunctionQuery*> ors;
+      for (size_t i : or_rows) { ors.push_back(static_cast<const PhraseDisjunctionQuery*>(queries[i])); ors.back()->check_served(); }
       if (!plain_rows.empty()) {
         std::vector<const Query*> plain;
         for (size_t i : plain_rows) plain.push_back(queries[i]);
@@ -678,6 +714,7 @@ class GpuIndexSearcher {
         place(phrase_rows, search_phrases(phrases, k));
       }
       if (!bools.empty()) place(bool_rows, search_phrase_bools(bools, k));
+      if (!ors.empty()) place(or_rows, search_phrase_ors(ors, k));
       return out;
     }
     const int32_t nq = static_cast<int32_t>(queries.size());
@@ -765,6 +802,59 @@ class GpuIndexSearcher {
       check(rgpu_search_phrase_bool_batch(leaf.segment, qs.data(), nq, ps.data(), static_cast<int32_t>(ps.size()), pts.data(), static_cast<int32_t>(pts.size()),
                                           ts.empty() ? nullptr : ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
                                           leaf_hits[li].data(), leaf_totals[li].data()));
+    }
+    return merge_leaves(leaf_hits, leaf_totals, nq, k);
+  }
+
+  // IndexSearcher::search(BooleanQuery of SHOULD phrases and terms, TopDocsCollector(k)) for a batch: rgpu_search_phrase_or_batch per
+  // leaf. phrase_slot[i] = the phrase's index in `should_queries`.
+  std::vector<TopDocs> search_phrase_ors(const std::vector<const PhraseDisjunctionQuery*>& queries, size_t k) {
+    const int32_t nq = static_cast<int32_t>(queries.size());
+    for (const PhraseDisjunctionQuery* q : queries) q->check_served();
+    std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
+    std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
+    for (size_t li = 0; li < leaves_.size(); ++li) {
+      const LeafReader& leaf = leaves_[li];
+      if (!leaf.pos_bytes) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "phrase search needs a positions field (LeafReader::pos_bytes)");
+      std::vector<rgpu_phrase_or_query> qs;
+      std::vector<const PhraseQuery*> phrases;
+      std::vector<rgpu_query_term> ts;
+      auto term_clause = [&](const TermQuery& c) {
+        rgpu_query_term qt{};
+        if (!leaf.term_state(c, &qt.state)) { qt.state = rgpu_term_state{}; qt.state.skip_offset = -1; qt.state.singleton_doc_id = -1; }
+        auto w = weight_of(c);
+        qt.weight = w.first;
+        qt.sim_table = w.second;
+        ts.push_back(qt);
+      };
+      for (const PhraseDisjunctionQuery* q : queries) {
+        rgpu_phrase_or_query oq{};
+        oq.first_phrase = static_cast<int32_t>(phrases.size());
+        oq.first_term = static_cast<int32_t>(ts.size());
+        oq.min_should_match = q->min_should_match;
+        for (size_t s = 0; s < q->should_queries.size(); ++s) {
+          const PhraseDisjunctionQuery::Should& c = q->should_queries[s];
+          if (c.phrase) {
+            oq.phrase_slot[oq.n_phrases++] = static_cast<int32_t>(s);
+            phrases.push_back(c.phrase.get());
+          } else {
+            term_clause(c.term);
+            oq.n_terms++;
+          }
+        }
+        for (const TermQuery& c : q->must_not_queries) term_clause(c);
+        oq.n_must_not = static_cast<int32_t>(q->must_not_queries.size());
+        qs.push_back(oq);
+      }
+      std::vector<rgpu_phrase_query> ps;
+      std::vector<rgpu_phrase_term> pts;
+      pack_phrases(phrases, leaf, &ps, &pts);
+      for (rgpu_phrase_query& p : ps) p.next_limit = 0;
+      leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
+      leaf_totals[li].assign(static_cast<size_t>(nq), 0);
+      check(rgpu_search_phrase_or_batch(leaf.segment, qs.data(), nq, ps.data(), static_cast<int32_t>(ps.size()), pts.data(), static_cast<int32_t>(pts.size()),
+                                        ts.empty() ? nullptr : ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
+                                        leaf_hits[li].data(), leaf_totals[li].data()));
     }
     return merge_leaves(leaf_hits, leaf_totals, nq, k);
   }

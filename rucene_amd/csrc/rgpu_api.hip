@@ -37,6 +37,8 @@
 #include "kernels/search_phrase.hpp"
 #include "kernels/search_phrase_bool.hpp"
 #include "host/phrase_bool_plan.hpp"
+#include "kernels/search_phrase_or.hpp"
+#include "host/phrase_or_plan.hpp"
 #include "kernels/search_term.hpp"
 #include "kernels/search_term_query.hpp"
 
@@ -251,6 +253,11 @@ struct rgpu_ctx {
   DevVec<uint64_t> phrase_keys;            // ... and their keys (0 = phrase freq 0)
   DevVec<int64_t> phrase_redo;             // ... and the slots the 64-candidate kernel left for the one-candidate kernel (PHRASE_REDO_LIST_CAP)
   DevVec<unsigned long long> phrase_count;  // ... how many each query's conjunction produced
+  // rgpu_search_phrase_or_batch: what the run-building kernels read in every pass of a call (the slot that staged the match stage's
+  // plan may come round again before the last pass): the virtual queries' slot prefix, their PhraseRunDev, the bucket counts / offsets
+  DevVec<int64_t> phrase_or_prefix;
+  DevVec<PhraseRunDev> phrase_or_runs;
+  DevVec<uint32_t> phrase_or_buckets;
   DevVec<HitOut> host_api_hits;  // rgpu_search_batch (blocking, host outputs): device-side result rows
   DevVec<int64_t> host_api_totals;
   HostPinned host_api_rows;  // ... of a SMALL batch: pinned host memory the merge kernels write straight into (no copy operations behind them)
@@ -1283,7 +1290,7 @@ extern "C" void rgpu_shutdown(rgpu_ctx* c) {
   drain_events(c);
   arena_drop(c, false);
   for (auto e : c->free_events) (void)hipEventDestroy(e);
-  c->sim_tables.release(); for (auto& cs : c->ceil_slots) { cs.d.release(); if (cs.done) (void)hipEventDestroy(cs.done); } c->d_runs.release(); c->pos_counts.release(); c->pos_tiles.release(); c->phrase_docs.release(); c->phrase_keys.release(); c->phrase_redo.release(); c->phrase_count.release(); c->host_api_hits.release(); c->host_api_totals.release(); c->host_api_rows.release();
+  c->sim_tables.release(); for (auto& cs : c->ceil_slots) { cs.d.release(); if (cs.done) (void)hipEventDestroy(cs.done); } c->d_runs.release(); c->pos_counts.release(); c->pos_tiles.release(); c->phrase_docs.release(); c->phrase_keys.release(); c->phrase_redo.release(); c->phrase_count.release(); c->phrase_or_prefix.release(); c->phrase_or_runs.release(); c->phrase_or_buckets.release(); c->host_api_hits.release(); c->host_api_totals.release(); c->host_api_rows.release();
   for (auto& sc : c->scr) sc.release();
   if (c->d_err) (void)hipFree(c->d_err);
   if (c->upload) { (void)hipStreamSynchronize(c->upload); (void)hipStreamDestroy(c->upload); }
@@ -1924,10 +1931,22 @@ static void launch_merge(rgpu_ctx* c, hipStream_t s, int n_queries, int k, const
                      c->pass.ceil_out);
 }
 
+// The optional hook of search_or_group (rgpu_search_phrase_or_batch): some clauses are exact phrases — pseudo terms (df = the run's
+// capacity, no blocks, no tail, no flags) whose runs `fill` writes between k_score_terms and the window kernel. A pseudo term gets NO
+// k_score_terms item (that kernel would write its sentinels at df and, for df == 1, a bogus singleton posting); its capacity enters
+// the run plan through df like any clause's length.
+namespace {
+struct OrPhraseRuns {
+  std::vector<uint8_t> pseudo;  // parallel to Group::terms: 1 = a phrase clause's pseudo term
+  std::function<int32_t(const int64_t* d_run_prefix, ScoredPosting* runs)> fill;
+};
+}  // namespace
+
 // OR: score every clause once into {doc, score} runs, then accumulate per doc-id window (kernels/search_or.hpp)
 // A dismax group (G.dismax) takes the same path — the same runs, dense clauses, items and merge — through k_or_windows_max, whose
 // accumulator cell is twice as wide: the window is narrowed until the launch fits a CU's LDS, and the plan follows the narrowed one.
-static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* hits_dev, int64_t* totals_dev, hipStream_t stream) {
+static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* hits_dev, int64_t* totals_dev, hipStream_t stream,
+                               const OrPhraseRuns* phrase_runs = nullptr) {
   rgpu_ctx* c = seg->ctx;
   const int nq = (int)G.queries.size();
   const int nt = (int)G.terms.size();
@@ -1976,6 +1995,7 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
       item_prefix[(size_t)j] = items1;
       const DevTerm& t = G.terms[(size_t)j];
       const bool dense = (t.flags & TERM_FLAG_OR_DENSE) != 0u;
+      if (phrase_runs && phrase_runs->pseudo[(size_t)j]) continue;  // a phrase clause: no item (its run is filled by the hook)
       items1 += (t.nblocks == 0 || dense) ? 1 : (t.nblocks + blocks_per_item - 1) / blocks_per_item;
     }
     item_prefix[(size_t)nt] = items1;
@@ -2024,7 +2044,7 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
   const int64_t *dip = sg.dev(r_ip), *drp = sg.dev(r_rp), *dmp = sg.dev(r_mp);
   const int32_t* dm = sg.dev(r_m);
   const SegView sv = seg_view(seg);
-  {
+  if (items1 > 0) {  // (always, unless every clause of the group is a phrase)
     TimedLaunch tl(c, stream, "k_score_terms", G.postings);
     const unsigned grid = wg_count((items1 + WG_WAVES - 1) / WG_WAVES);
     if (legacy)
@@ -2032,6 +2052,7 @@ static int32_t search_or_group(rgpu_segment* seg, Group& G, int32_t k, HitOut* h
     else
       RGPU_LAUNCH(k_score_terms<false>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, dt, dip, drp, nt, items1, blocks_per_item, runs_buf.p);
   }
+  if (phrase_runs) RGPU_TRY(phrase_runs->fill(drp, runs_buf.p));
   {
     TimedLaunch tl(c, stream, G.dismax ? "k_or_windows_max" : (G.demote ? "k_or_windows_dem" : "k_or_windows"), G.postings);
     const size_t lds = or_lds_bytes(W, has_msm, G.dismax, G.demote);
@@ -4329,6 +4350,308 @@ extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_p
   }
   hipError_t e1 = hipMemcpyAsync(hits_out, c->host_api_hits.p, nq * (size_t)k * sizeof(HitOut), hipMemcpyDeviceToHost, stream);
   hipError_t e2 = hipMemcpyAsync(total_hits_out, c->host_api_totals.p, nq * 8, hipMemcpyDeviceToHost, stream);
+  hipError_t e3 = hipStreamSynchronize(stream);
+  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(RGPU_ERR_RUNTIME, "device to host copy failed");
+  return RGPU_OK;
+}
+
+// ---- BooleanQuery of SHOULD / MUST_NOT clauses with exact PhraseQuery clauses among the SHOULD ones: "a b" "c d" e -f -------------
+// (include/rucene_gpu.h rgpu_search_phrase_or_batch; the plan: host/phrase_or_plan.hpp; the run-building kernels:
+// kernels/search_phrase_or.hpp.) Launch sequence, all on the call's stream:
+//   1. k_search_and in emit mode, one "virtual query" per (query, phrase that exists in the leaf) -> that phrase's candidate docs
+//      (the conjunction of its terms, as rgpu_search_phrase_batch finds them);
+//   2. phrase_match_stage over the virtual queries — exact kernels only: one make_key(BM25(phrase freq, norm), doc) or 0 per slot.
+//      Once per call; its verdict (a doc that holds a phrase term more than 1024 times ...) is looked at before anything else runs;
+//   3. search_or_group over a Group of op OR: clauses in query order, a pseudo DevTerm (df = capacity) at every phrase position,
+//      MUST_NOT terms behind them (DevQuery::pad), min_should_match in op bits 8... Its hook fills the phrase clauses' runs between
+//      k_score_terms and k_or_windows: k_phrase_run_fill, _count, _scan, _scatter, _sort;
+//   4. k > RGPU_PASS_K: step 3 once per pass of 128 hits, as search_impl runs its passes (rgpu_ctx::Pass, ceiling slots). The keys of
+//      step 2 stay in c->phrase_keys; what the run-building kernels read besides lives in buffers of the context's, not in the scratch
+//      slot that staged steps 1-2 (four passes later that slot is somebody else's).
+extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phrase_or_query* queries, int32_t n_queries,
+                                               const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                               const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                               const rgpu_query_term* terms, int32_t n_terms_total,
+                                               int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
+  if (!seg || !queries || n_queries <= 0 || !phrases || n_phrases_total <= 0 || !phrase_terms || n_phrase_terms_total <= 0 || n_terms_total < 0 ||
+      (n_terms_total > 0 && !terms) || !hits_out || !total_hits_out)
+    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "disjunction over phrases: k must be in 1..RGPU_MAX_K");
+  if (!seg->has_positions || !seg->d_pos) return fail(RGPU_ERR_ILLEGAL_STATE, "a disjunction over phrases needs a positions field with its .pos file attached");
+  rgpu_ctx* c = seg->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t stream = c->stream;
+  // ---- validate, plan
+  const size_t nq = (size_t)n_queries;
+  std::vector<const rgpu_term_state*> ptrs;
+  std::vector<rgpu_host::PhraseOrPlan> plans(nq);
+  std::vector<int32_t> first_virtual(nq + 1, 0);  // virtual query (query q, phrase j) = first_virtual[q] + j
+  for (int32_t q = 0; q < n_queries; ++q) {
+    const rgpu_phrase_or_query& Q = queries[q];
+    if (Q.n_phrases < 1 || Q.n_phrases > RGPU_MAX_BOOL_PHRASES) return fail(RGPU_ERR_UNSUPPORTED, "a disjunction over phrases holds 1..RGPU_MAX_BOOL_PHRASES phrases");
+    if (Q.first_phrase < 0 || (int64_t)Q.first_phrase + Q.n_phrases > (int64_t)n_phrases_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "phrase range outside phrases[]");
+    if (Q.n_terms < 0 || Q.n_must_not < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "negative clause count");
+    if (Q.n_terms + (int64_t)Q.n_must_not > 0 && (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms + Q.n_must_not > (int64_t)n_terms_total))
+      return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "clause range outside terms[]");
+    for (int i = 0; i < Q.n_phrases; ++i) {
+      const rgpu_phrase_query& P = phrases[Q.first_phrase + i];
+      RGPU_TRY(check_phrase_query(c, P, n_phrase_terms_total, false));
+      RGPU_TRY(check_phrase_terms(seg, P, phrase_terms, &ptrs));
+    }
+    for (int64_t i = 0; i < (int64_t)Q.n_terms + Q.n_must_not; ++i) {
+      const rgpu_query_term& t = terms[Q.first_term + i];
+      if (i < Q.n_terms && (t.sim_table < 0 || t.sim_table >= c->n_sim_tables)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
+      if (t.state.doc_freq > 0) ptrs.push_back(&t.state);
+    }
+    plans[(size_t)q] = rgpu_host::plan_phrase_or(Q, phrases, phrase_terms, terms);
+    if (plans[(size_t)q].status != RGPU_OK) return fail(plans[(size_t)q].status, plans[(size_t)q].why);
+    first_virtual[(size_t)q + 1] = first_virtual[(size_t)q] + Q.n_phrases;
+  }
+  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
+  // the candidate conjunctions answer a dense clause from its doc bitmap, as a phrase search's do
+  const int64_t bitmap_df = (c->cfg.and_bitmaps >= 0 && c->n_sim_tables > 0) ? bitmap_min_df_and(seg) : INT64_MAX;
+  if (bitmap_df != INT64_MAX) {
+    std::vector<const rgpu_term_state*> dense;
+    std::vector<int32_t> dense_sim;
+    for (int32_t q = 0; q < n_queries; ++q) {
+      const rgpu_host::PhraseOrPlan& P = plans[(size_t)q];
+      if (P.dead) continue;
+      for (int j = 0; j < queries[q].n_phrases; ++j) {
+        if (P.capacity[(size_t)j] <= 0) continue;
+        const rgpu_phrase_query& ph = phrases[queries[q].first_phrase + j];
+        for (int i = 0; i < ph.n_terms; ++i) {
+          const rgpu_term_state& st = phrase_terms[ph.first_term + i].state;
+          if (st.doc_freq >= bitmap_df && !seg->bitmaps.find(st.doc_start_fp)) { dense.push_back(&st); dense_sim.push_back(ph.sim_table); }
+        }
+      }
+    }
+    if (!dense.empty()) RGPU_TRY(ensure_bitmaps_locked(seg, dense.data(), dense_sim.data(), dense.size()));
+  }
+  // ---- the match stage's arrays (one virtual query per phrase) and the disjunction's Group
+  const size_t nv = (size_t)first_virtual[nq];
+  std::vector<DevQuery> vq(nv, DevQuery{RGPU_OP_AND, 0, 0, 0});
+  std::vector<DevTerm> pdt;
+  std::vector<PosTerm> ppt;
+  std::vector<int64_t> item_prefix(nv + 1), emit_prefix(nv + 1);
+  std::vector<PhraseRunDev> prd(nv, PhraseRunDev{0, 0});
+  int64_t lead_blocks = 0;
+  for (const rgpu_host::PhraseOrPlan& P : plans) if (!P.dead) for (int32_t cap : P.capacity) lead_blocks += cap / 128;
+  const int blocks_per_item = and_item_blocks(c, lead_blocks);
+  Group G0;
+  G0.op = RGPU_OP_OR;
+  OrPhraseRuns hook;
+  int64_t items = 0, slots = 0;
+  for (int32_t q = 0; q < n_queries; ++q) {
+    const rgpu_phrase_or_query& Q = queries[q];
+    const rgpu_host::PhraseOrPlan& P = plans[(size_t)q];
+    for (int j = 0; j < Q.n_phrases; ++j) {
+      const size_t v = (size_t)first_virtual[(size_t)q] + (size_t)j;
+      item_prefix[v] = items;
+      emit_prefix[v] = slots;
+      vq[v].first_term = (int32_t)pdt.size();
+      if (P.dead || P.capacity[(size_t)j] <= 0) continue;
+      const rgpu_phrase_query& ph = phrases[Q.first_phrase + j];
+      bool dead = false;
+      RGPU_TRY(emit_phrase(seg, ph, phrase_terms, &pdt, &ppt, &dead));  // (dead: the plan has said so already)
+      if (dead) continue;
+      vq[v].n_terms = ph.n_terms;
+      const DevTerm& lead = pdt[(size_t)vq[v].first_term];
+      if (lead.df != P.capacity[(size_t)j]) return fail(RGPU_ERR_ILLEGAL_STATE, "internal: a phrase's lead term is not its rarest");
+      items += lead.nblocks == 0 ? 1 : (lead.nblocks + blocks_per_item - 1) / blocks_per_item;
+      slots += ((int64_t)lead.df + 63) & ~(int64_t)63;  // (the 64 slots of a wavefront belong to one virtual query)
+    }
+    // DisjunctionSumScorer's children in query order, pseudo terms at the phrase positions; the MUST_NOT terms behind them
+    DevQuery dq{RGPU_OP_OR | (P.min_should_match > 1 ? P.min_should_match << 8 : 0), 0, (int32_t)G0.terms.size(), 0};
+    if (!P.dead) {
+      for (int32_t o : P.order) {
+        DevTerm t;
+        if (o >= 0) {
+          const rgpu_query_term& qt = terms[Q.first_term + o];
+          RGPU_TRY(make_dev_term(seg, qt.state, qt.weight, qt.sim_table, &t));
+        } else {
+          std::memset(&t, 0, sizeof t);
+          t.df = P.capacity[(size_t)~o];
+          t.singleton_doc = -1;
+          t.sim_table = phrases[Q.first_phrase + ~o].sim_table;  // (never read: the clause has no k_score_terms item and is never dense)
+          prd[(size_t)first_virtual[(size_t)q] + (size_t)~o] = PhraseRunDev{(int32_t)G0.terms.size(), t.df};
+        }
+        G0.terms.push_back(t);
+        hook.pseudo.push_back(o < 0 ? 1 : 0);
+        G0.postings += t.df;
+      }
+      for (const rgpu_term_state* st : P.must_not) {
+        DevTerm t;
+        RGPU_TRY(make_dev_term(seg, *st, 0.0f, 0, &t));  // needs_scores = false: weight and table are never read
+        G0.terms.push_back(t);
+        hook.pseudo.push_back(0);
+        G0.postings += t.df;
+      }
+      dq.n_terms = (int32_t)P.order.size();
+      dq.pad = (int32_t)P.must_not.size();
+    }
+    G0.queries.push_back(dq);
+    G0.qmap.push_back(q);
+  }
+  item_prefix[nv] = items;
+  emit_prefix[nv] = slots;
+  HIP_TRY(c->host_api_hits.reserve(nq * (size_t)k, 0, stream));
+  HIP_TRY(c->host_api_totals.reserve(nq, 0, stream));
+  HitOut* hits_dev = c->host_api_hits.p;
+  int64_t* totals_dev = c->host_api_totals.p;
+  const int n_buckets = (int)(((int64_t)seg->max_doc + PHRASE_OR_BUCKET - 1) / PHRASE_OR_BUCKET);
+  const size_t n_cells = nv * (size_t)std::max(1, n_buckets);
+  if (items > 0) {
+    // ---- 1. + 2.: candidates and keys, once per call
+    SCRATCH_TAKE(c);
+    Stager st(c);
+    const auto r_vq = st.add<DevQuery>(nv);
+    const auto r_pdt = st.add<DevTerm>(pdt.size());
+    const auto r_ppt = st.add<PosTerm>(ppt.size());
+    const auto r_ip = st.add<int64_t>(nv + 1), r_ep = st.add<int64_t>(nv + 1);
+    const auto r_sl = st.add<int32_t>(nv);  // slop 0 throughout
+    const auto r_gr = st.add<SloppyGroups>(nv);
+    std::vector<TermBitmap> clause_bitmaps;  // parallel to pdt: the clauses behind a phrase's lead that have a doc bitmap
+    if (bitmap_df != INT64_MAX && seg->bitmaps.size() > 0) {
+      bool any = false;
+      clause_bitmaps.assign(pdt.size(), TermBitmap{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0});
+      for (const DevQuery& q0 : vq) {
+        for (int i = 1; i < q0.n_terms; ++i) {
+          const DevTerm& t = pdt[(size_t)(q0.first_term + i)];
+          if (t.df < bitmap_df) continue;
+          const BitmapInfo* bm = seg->bitmaps.find((int64_t)t.start_fp);
+          if (!bm || !bm->usable || bm->df != t.df) continue;
+          clause_bitmaps[(size_t)(q0.first_term + i)] = TermBitmap{bm->words, bm->ranks, bm->freqs, bm->ovf, bm->nib, bm->memb, bm->n_ovf, 0};
+          any = true;
+        }
+      }
+      if (!any) clause_bitmaps.clear();
+    }
+    const auto r_bm = st.add_if<TermBitmap>(!clause_bitmaps.empty(), clause_bitmaps.size());
+    STAGE_SIZED(sg, st);
+    sg.put(r_vq, vq);
+    sg.put(r_pdt, pdt);
+    sg.put(r_ppt, ppt);
+    sg.put(r_ip, item_prefix);
+    sg.put(r_ep, emit_prefix);
+    sg.fill(r_sl, 0);
+    sg.fill(r_gr, 0xff);
+    sg.put(r_bm, clause_bitmaps);
+    RGPU_TRY(sg.upload(stream));
+    HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
+    HIP_TRY(c->phrase_keys.reserve((size_t)slots + 64, 0, stream));
+    const int64_t redo_cap = phrase_redo_cap(slots);
+    HIP_TRY(c->phrase_redo.reserve((size_t)redo_cap + 64, 0, stream));
+    HIP_TRY(c->phrase_count.reserve(nv, 0, stream));
+    HIP_TRY(hipMemsetAsync(c->phrase_count.p, 0, nv * 8, stream));
+    HIP_TRY(hipMemsetAsync(c->phrase_keys.p, 0, (size_t)slots * 8, stream));  // (a 64-candidate group past a query's count is never written)
+    const int k_emit = std::min<int>(k, 64);  // the conjunction only emits candidates: its (empty) top-k lists are the narrow kind
+    HIP_TRY(c->S->d_partial_keys.reserve((size_t)items * (size_t)k_emit, 0, stream));
+    HIP_TRY(c->S->d_partial_counts.reserve((size_t)items, 0, stream));
+    HIP_TRY(c->S->d_tau.reserve(nv, 0, stream));
+    HIP_TRY(c->S->d_touched.reserve(nv * 2, 0, stream));
+    HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, nv * 8, stream));
+    HIP_TRY(hipMemsetAsync(c->S->d_touched.p, 0, nv * 16, stream));
+    HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));
+    const SegView sv = seg_view(seg);
+    const bool legacy = seg->version < 1;
+    {
+      TimedLaunch tl(c, stream, "k_search_and(phrase-or candidates)", 0);
+      const int xcd_chunk = and_xcd_chunk(seg);
+      const unsigned grid = wg_count(and_grid((items + AND_WG_WAVES - 1) / AND_WG_WAVES, xcd_chunk));
+      auto go = [&](auto kern) {
+        RGPU_LAUNCH(kern, dim3(grid), dim3(AND_WG_THREADS), 0, stream, sv, (const DevQuery*)sg.dev(r_vq), (const DevTerm*)sg.dev(r_pdt), (const int64_t*)sg.dev(r_ip),
+                    (int)nv, items, blocks_per_item, k_emit, c->S->d_partial_keys.p, c->S->d_partial_counts.p, c->S->d_tau.p, c->S->d_touched.p,
+                    (const int64_t*)sg.dev(r_ep), c->phrase_count.p, (void*)c->phrase_docs.p, (const unsigned long long*)nullptr, (const int32_t*)nullptr,
+                    clause_bitmaps.empty() ? (const TermBitmap*)nullptr : sg.dev(r_bm), xcd_chunk);
+      };
+      if (legacy) go(k_search_and<true, false, false, false>); else go(k_search_and<false, false, false, false>);
+    }
+    PhraseMatchStage ms{sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ppt), sg.dev(r_ep), sg.dev(r_sl), sg.dev(r_gr), (int32_t)nv, slots, redo_cap, true, false, false, false,
+                        nullptr, nullptr, nullptr, 0};
+    RGPU_TRY(phrase_match_stage(seg, stream, ms));
+    HIP_TRY(launch_status());
+    // a refused call writes nothing: the match stage's verdict before the disjunction runs (the sync also frees the slot's stage)
+    int err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    RGPU_TRY(phrase_match_status(err, "a doc holds one of an exact phrase's terms more than 1024 times", "internal: a conjunction match was not found again"));
+    // what the run-building kernels read in every pass
+    HIP_TRY(c->phrase_or_prefix.reserve(nv + 1, 0, stream));
+    HIP_TRY(c->phrase_or_runs.reserve(nv, 0, stream));
+    HIP_TRY(c->phrase_or_buckets.reserve(2 * n_cells, 0, stream));
+    HIP_TRY(hipMemcpyAsync(c->phrase_or_prefix.p, emit_prefix.data(), (nv + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(c->phrase_or_runs.p, prd.data(), nv * sizeof(PhraseRunDev), hipMemcpyHostToDevice, stream));
+  }
+  // ---- 3.: the hook of search_or_group — the phrase clauses' runs (bounds: kernels/search_phrase_or.hpp)
+  hook.fill = [&](const int64_t* d_run_prefix, ScoredPosting* runs) -> int32_t {
+    if (items <= 0 || n_buckets <= 0) return RGPU_OK;  // (no phrase exists in this leaf: the group holds no pseudo term)
+    const PhraseRunDev* d_pr = c->phrase_or_runs.p;
+    uint32_t* counts = c->phrase_or_buckets.p;
+    uint32_t* offsets = counts + n_cells;
+    const int groups_per_clause = (n_buckets + 63) / 64;  // k_phrase_run_sort: one wavefront per (clause, 64 buckets)
+    const int64_t groups = slots / 64, sort_items = (int64_t)nv * groups_per_clause;
+    const unsigned ggrid = wg_count((groups + WG_WAVES - 1) / WG_WAVES);
+    HIP_TRY(hipMemsetAsync(counts, 0, n_cells * sizeof(uint32_t), stream));
+    {
+      TimedLaunch tl(c, stream, "k_phrase_run_fill", 0);
+      RGPU_LAUNCH(k_phrase_run_fill, dim3((unsigned)nv, PHRASE_OR_FILL_SPLIT), dim3(WG_THREADS), 0, stream, d_pr, d_run_prefix, runs);
+    }
+    {
+      TimedLaunch tl(c, stream, "k_phrase_run_count", 0);
+      RGPU_LAUNCH(k_phrase_run_place<false>, dim3(ggrid), dim3(WG_THREADS), 0, stream, d_pr, (const int64_t*)c->phrase_or_prefix.p,
+                  (const unsigned long long*)c->phrase_count.p, (const uint64_t*)c->phrase_keys.p, (int)nv, groups, seg->max_doc, n_buckets, counts,
+                  (const uint32_t*)offsets, d_run_prefix, runs);
+    }
+    {
+      TimedLaunch tl(c, stream, "k_phrase_run_scan", 0);
+      RGPU_LAUNCH(k_phrase_run_scan, dim3(wg_count((nv + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, (int)nv, n_buckets, counts, offsets);
+    }
+    {
+      TimedLaunch tl(c, stream, "k_phrase_run_scatter", 0);
+      RGPU_LAUNCH(k_phrase_run_place<true>, dim3(ggrid), dim3(WG_THREADS), 0, stream, d_pr, (const int64_t*)c->phrase_or_prefix.p,
+                  (const unsigned long long*)c->phrase_count.p, (const uint64_t*)c->phrase_keys.p, (int)nv, groups, seg->max_doc, n_buckets, counts,
+                  (const uint32_t*)offsets, d_run_prefix, runs);
+    }
+    {
+      TimedLaunch tl(c, stream, "k_phrase_run_sort", 0);
+      RGPU_LAUNCH(k_phrase_run_sort, dim3(wg_count((sort_items + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, d_pr, sort_items, n_buckets,
+                  groups_per_clause, (const uint32_t*)counts, (const uint32_t*)offsets, d_run_prefix, runs);
+    }
+    return RGPU_OK;
+  };
+  // one pass: defaults for every row (a leaf that holds no clause of any query merges nothing), then the group
+  auto one_pass = [&](int32_t k_pass) -> int32_t {
+    HIP_TRY(hipMemsetAsync(totals_dev, 0, nq * 8, stream));
+    RGPU_LAUNCH(k_init_hits, dim3(wg_count((nq * (size_t)k_pass + 255) / 256)), dim3(256), 0, stream, hits_dev, (int64_t)n_queries, (int)k_pass,
+                c->pass.stride > 0 ? c->pass.stride : (int)k_pass, c->pass.col0);
+    if (c->pass.ceil_out) HIP_TRY(hipMemsetAsync(c->pass.ceil_out, 0, nq * 8, stream));
+    Group G = G0;  // (search_or_group marks dense clauses in the group it is given)
+    return search_or_group(seg, G, k_pass, hits_dev, totals_dev, stream, &hook);
+  };
+  c->pass = rgpu_ctx::Pass{};
+  int32_t rc = RGPU_OK;
+  if (k <= RGPU_PASS_K) {
+    rc = one_pass(k);
+  } else {  // search_impl's passes: pass p collects the best hits strictly below the worst hit of pass p - 1
+    rgpu_ctx::CeilSlot& cs = c->ceil_slots[c->ceil_next];
+    c->ceil_next = (c->ceil_next + 1) % N_SCRATCH;
+    if (cs.busy) { HIP_TRY(hipEventSynchronize(cs.done)); cs.busy = false; }
+    HIP_TRY(cs.d.reserve(nq * 2, 0, stream));
+    int flip = 0;
+    for (int32_t col0 = 0; col0 < k && rc == RGPU_OK; col0 += RGPU_PASS_K, flip ^= 1) {
+      c->pass.stride = k;
+      c->pass.col0 = col0;
+      c->pass.ceil_in = col0 == 0 ? nullptr : cs.d.p + (size_t)(flip ^ 1) * nq;
+      c->pass.ceil_out = cs.d.p + (size_t)flip * nq;
+      rc = one_pass(std::min<int32_t>(RGPU_PASS_K, k - col0));
+    }
+    c->pass = rgpu_ctx::Pass{};
+  }
+  if (rc != RGPU_OK) { (void)hipStreamSynchronize(stream); return rc; }
+  HIP_TRY(launch_status());
+  hipError_t e1 = hipMemcpyAsync(hits_out, hits_dev, nq * (size_t)k * sizeof(HitOut), hipMemcpyDeviceToHost, stream);
+  hipError_t e2 = hipMemcpyAsync(total_hits_out, totals_dev, nq * 8, hipMemcpyDeviceToHost, stream);
   hipError_t e3 = hipStreamSynchronize(stream);
   if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(RGPU_ERR_RUNTIME, "device to host copy failed");
   return RGPU_OK;

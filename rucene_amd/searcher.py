@@ -878,6 +878,10 @@ class GpuIndexSearcher:
         ps, pts = self.pack_phrases(phrase_qs, leaf)
         ps["weight"][np.array(filtered, dtype=bool)] = 0.0
         ps["next_limit"] = 0
+        return qs, ps, pts, self._pack_term_clauses(term_cs, leaf)
+
+    def _pack_term_clauses(self, term_cs, leaf):
+        """TermQuery clauses -> rgpu_query_term[] for one leaf (a term the leaf lacks: doc_freq 0)"""
         byte_terms = [c.term for c in term_cs if isinstance(c.term, bytes)]
         if byte_terms:
             leaf.resolve(byte_terms)
@@ -893,23 +897,72 @@ class GpuIndexSearcher:
                 ts[at]["state"]["skip_offset"] = -1
                 ts[at]["state"]["singleton_doc_id"] = -1
             ts[at]["weight"], ts[at]["sim_table"] = w, table
-        return qs, ps, pts, ts
+        return ts
+
+    @staticmethod
+    def phrase_or_parts(query):
+        """A BooleanQuery without MUST and FILTER clauses, with PhraseQuery clauses -> (SHOULD clauses in query order, i.e.
+        BooleanWeight::should_weights; MUST_NOT TermQuery clauses; min_should_match) when the GPU path serves the tree
+        (rgpu_search_phrase_or_batch), else UnsupportedOperation: a sloppy phrase clause (two-phase), a phrase under MUST_NOT, a nested
+        BooleanQuery clause, more than 4 phrases, ten or more SHOULD clauses (the reference then sums in heap order)."""
+        if query.must_queries or query.filter_queries:
+            raise RgpuError(-5, "phrase_or_parts: a disjunction has no MUST and no FILTER clause (phrase_bool_parts)")
+        if any(isinstance(q, PhraseQuery) for q in query.must_not_queries):
+            raise RgpuError(-5, "a phrase clause under MUST_NOT is not served by the GPU path")
+        if any(isinstance(q, BooleanQuery) for q in query.should_queries + query.must_not_queries):
+            raise RgpuError(-5, "nested boolean clauses beside a phrase are not served by the GPU path")
+        phrases = [q for q in query.should_queries if isinstance(q, PhraseQuery)]
+        if any(q.slop > 0 for q in phrases):
+            raise RgpuError(-5, "a sloppy phrase inside a boolean query is not served by the GPU path")
+        if len(phrases) > _lib.MAX_BOOL_PHRASES:
+            raise RgpuError(-5, "more than %d phrases in one boolean query" % _lib.MAX_BOOL_PHRASES)
+        if len(query.should_queries) > _lib.PHRASE_OR_MAX_SHOULD:
+            raise RgpuError(-5, "ten or more SHOULD clauses with a phrase among them sum in heap order")
+        return list(query.should_queries), list(query.must_not_queries), query.min_should_match
+
+    def pack_phrase_or(self, queries, leaf):
+        """BooleanQuery objects of SHOULD / MUST_NOT clauses with phrase clauses -> the (rgpu_phrase_or_query[], rgpu_phrase_query[],
+        rgpu_phrase_term[], rgpu_query_term[]) of rgpu_search_phrase_or_batch for one leaf."""
+        parts = [self.phrase_or_parts(q) for q in queries]
+        phrase_qs, term_cs = [], []
+        qs = np.zeros(len(queries), dtype=_lib.PHRASE_OR_QUERY_DTYPE)
+        for i, (shoulds, nots, msm) in enumerate(parts):
+            slots = [s for s, c in enumerate(shoulds) if isinstance(c, PhraseQuery)]
+            mine = [c for c in shoulds if not isinstance(c, PhraseQuery)]
+            qs[i]["n_phrases"], qs[i]["first_phrase"] = len(slots), len(phrase_qs)
+            qs[i]["n_terms"], qs[i]["first_term"], qs[i]["n_must_not"] = len(mine), len(term_cs), len(nots)
+            qs[i]["min_should_match"] = msm
+            qs[i]["phrase_slot"][:len(slots)] = slots
+            phrase_qs += [shoulds[s] for s in slots]
+            term_cs += mine + nots
+        ps, pts = self.pack_phrases(phrase_qs, leaf)
+        ps["next_limit"] = 0
+        return qs, ps, pts, self._pack_term_clauses(term_cs, leaf)
 
     def search_batch(self, queries, k):
         """-> (hits[n][k] structured {doc, score}, total_hits[n]) merged over all leaves. A batch may mix term / boolean / dismax /
-        boosting queries (rgpu_search_batch), PhraseQuery rows (rgpu_search_phrase_batch) and BooleanQuery rows with phrase clauses
-        (rgpu_search_phrase_bool_batch): one call per kind and leaf, rows keep their order."""
-        kinds = [1 if isinstance(q, PhraseQuery) else (2 if isinstance(q, BooleanQuery) and q.has_phrases() else 0) for q in queries]
+        boosting queries (rgpu_search_batch), PhraseQuery rows (rgpu_search_phrase_batch), BooleanQuery rows with phrases among their
+        required clauses (rgpu_search_phrase_bool_batch) and BooleanQuery rows of SHOULD / MUST_NOT clauses with phrases among the
+        SHOULD ones (rgpu_search_phrase_or_batch): one call per kind and leaf, rows keep their order."""
+        def kind(q):
+            if isinstance(q, PhraseQuery):
+                return 1
+            if isinstance(q, BooleanQuery) and q.has_phrases():   # no MUST, no FILTER: the disjunction route; else phrase_bool_parts decides
+                return 2 if (q.must_queries or q.filter_queries) else 3
+            return 0
+        kinds = [kind(q) for q in queries]
         if not any(kinds):
             per_leaf = []
             for leaf in self.leaves:
                 qs, ts = self.pack(queries, leaf)
                 per_leaf.append(leaf.segment.search_batch(qs, ts, k))
         else:
-            rows = [np.flatnonzero(np.array(kinds) == kind) for kind in (0, 1, 2)]
+            rows = [np.flatnonzero(np.array(kinds) == kd) for kd in (0, 1, 2, 3)]
             groups = [[queries[i] for i in r] for r in rows]
             for q in groups[2]:   # refused before any leaf is touched
                 self.phrase_bool_parts(q)
+            for q in groups[3]:
+                self.phrase_or_parts(q)
             per_leaf = []
             for leaf in self.leaves:
                 hits, totals = np.zeros((len(queries), k), dtype=_lib.HIT_DTYPE), np.zeros(len(queries), dtype=np.int64)
@@ -921,6 +974,8 @@ class GpuIndexSearcher:
                     hits[rows[1]], totals[rows[1]] = leaf.segment.search_phrase_batch(qs, ts, k)
                 if groups[2]:
                     hits[rows[2]], totals[rows[2]] = leaf.segment.search_phrase_bool_batch(*self.pack_phrase_bool(groups[2], leaf), k)
+                if groups[3]:
+                    hits[rows[3]], totals[rows[3]] = leaf.segment.search_phrase_or_batch(*self.pack_phrase_or(groups[3], leaf), k)
                 per_leaf.append((hits, totals))
         if len(per_leaf) == 1:
             return per_leaf[0]

@@ -347,6 +347,8 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
         if let Some(b) = query.as_any().downcast_ref::<BooleanQuery<C>>() {
             let (must, should, filter, must_not, _) = b.clauses();
             if must.iter().chain(should).chain(filter).chain(must_not).any(|q| q.as_any().downcast_ref::<PhraseQuery>().is_some()) {
+                // no MUST and no FILTER clause: one DisjunctionSumScorer over the SHOULD clauses; else the conjunction's rules decide
+                if must.is_empty() && filter.is_empty() { return self.try_phrase_or(b, top, k); }
                 return self.try_phrase_bool(b, top, k);
             }
         }
@@ -513,6 +515,80 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             check(unsafe { rgpu_search_phrase_bool_batch(self.leaves[leaf.ord].seg, &bq, 1, pqs.as_ptr(), pqs.len() as i32, pterms.as_ptr(), pterms.len() as i32,
                                                          if terms.is_empty() { std::ptr::null() } else { terms.as_ptr() }, terms.len() as i32, k as i32,
                                                          hits.as_mut_ptr(), &mut total) }, self.ctx)?;
+            Self::hand_over(top, &hits, total);
+        }
+        Ok(true)
+    }
+
+    /// BooleanQuery without MUST and FILTER clauses whose 1..=9 SHOULD clauses hold 1..=RGPU_MAX_BOOL_PHRASES exact PhraseQuery clauses
+    /// beside TermQuery clauses, with MUST_NOT TermQuery clauses and any min_should_match up to 255: "\"a b\" \"c d\" e -f" ->
+    /// rgpu_search_phrase_or_batch per leaf. phrase_slot = the phrase's index in BooleanWeight::should_weights (the SHOULD clauses in
+    /// query order); the library drops the clauses a leaf lacks and sums the others in that order, as DisjunctionSumScorer's
+    /// SimpleQueue arm does (disjunction_scorer.rs:213-225). Ok(false) — the CPU searcher — under try_phrase's rules (another field,
+    /// a leaf without positions, a phrase of the wrong size) and for every shape the library does not serve: a sloppy phrase clause
+    /// (two-phase), ten or more SHOULD clauses (the heap-order arm), a phrase under MUST_NOT, a nested BooleanQuery, more than
+    /// RGPU_MAX_BOOL_PHRASES phrases, more than RGPU_MAX_QUERY_TERMS clause terms.
+    fn try_phrase_or(&self, b: &BooleanQuery<C>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
+        let (must, should, filter, must_not, min_should_match) = b.clauses();
+        if !must.is_empty() || !filter.is_empty() || should.is_empty() || should.len() > 9 || min_should_match < 0 || min_should_match > 255
+            || self.leaves.iter().any(|l| !l.has_positions) {
+            return Ok(false);
+        }
+        let term_of = |q: &Box<dyn Query<C>>| q.as_any().downcast_ref::<TermQuery>().filter(|t| t.term.field == self.field);
+        let mut phrases: Vec<(&PhraseQuery, usize)> = Vec::new(); // (the phrase, its slot in should_weights)
+        let mut optional: Vec<&TermQuery> = Vec::new();
+        for (slot, q) in should.iter().enumerate() {
+            if let Some(p) = q.as_any().downcast_ref::<PhraseQuery>() {
+                let (field, terms, positions, slop) = p.parts();
+                if field != self.field || slop != 0 || terms.len() < 2 || terms.len() > RGPU_MAX_PHRASE_TERMS as usize || terms.len() != positions.len() {
+                    return Ok(false);
+                }
+                phrases.push((p, slot));
+            } else if let Some(t) = term_of(q) {
+                optional.push(t);
+            } else {
+                return Ok(false);
+            }
+        }
+        if phrases.is_empty() || phrases.len() > RGPU_MAX_BOOL_PHRASES as usize { return Ok(false); }
+        let mut prohibited: Vec<&TermQuery> = Vec::with_capacity(must_not.len());
+        for q in must_not {
+            match term_of(q) { Some(t) => prohibited.push(t), None => return Ok(false) }
+        }
+        let n_phrase_terms: usize = phrases.iter().map(|(p, _)| p.parts().1.len()).sum();
+        if n_phrase_terms + optional.len() + prohibited.len() > RGPU_MAX_QUERY_TERMS as usize { return Ok(false); }
+        let mut phrase_weights = Vec::with_capacity(phrases.len());
+        for (p, _) in &phrases {
+            let term_refs: Vec<&Term> = p.parts().1.iter().collect();
+            phrase_weights.push(self.weight_of(&term_refs, 1.0)?);
+        }
+        let mut term_weights = Vec::with_capacity(optional.len());
+        for t in &optional { term_weights.push(self.weight_of(&[&t.term], t.boost)?); }
+        let mut oq = RgpuPhraseOrQuery { n_phrases: phrases.len() as i32, first_phrase: 0, n_terms: optional.len() as i32, first_term: 0,
+                                         n_must_not: prohibited.len() as i32, min_should_match, phrase_slot: [0; 4], reserved: [0; 2] };
+        for (i, (_, slot)) in phrases.iter().enumerate() { oq.phrase_slot[i] = *slot as i32; }
+        for leaf in self.cpu.reader().leaves() {
+            let mut pqs = Vec::with_capacity(phrases.len());
+            let mut pterms: Vec<RgpuPhraseTerm> = Vec::with_capacity(n_phrase_terms);
+            for (i, (p, _)) in phrases.iter().enumerate() {
+                let (_, terms, positions, _) = p.parts();
+                let mine = self.phrase_terms(&leaf, terms, positions)?;
+                pqs.push(RgpuPhraseQuery { n_terms: mine.len() as i32, first_term: pterms.len() as i32, weight: phrase_weights[i].0, sim_table: phrase_weights[i].1,
+                                           slop: 0, next_limit: 0 });
+                pterms.extend(mine);
+            }
+            let mut terms = Vec::with_capacity(optional.len() + prohibited.len());
+            for (i, t) in optional.iter().enumerate() {
+                terms.push(RgpuQueryTerm { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: term_weights[i].0, sim_table: term_weights[i].1 });
+            }
+            for t in &prohibited {
+                terms.push(RgpuQueryTerm { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: 0.0, sim_table: 0 }); // never scored
+            }
+            let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
+            let mut total: i64 = 0;
+            check(unsafe { rgpu_search_phrase_or_batch(self.leaves[leaf.ord].seg, &oq, 1, pqs.as_ptr(), pqs.len() as i32, pterms.as_ptr(), pterms.len() as i32,
+                                                       if terms.is_empty() { std::ptr::null() } else { terms.as_ptr() }, terms.len() as i32, k as i32,
+                                                       hits.as_mut_ptr(), &mut total) }, self.ctx)?;
             Self::hand_over(top, &hits, total);
         }
         Ok(true)
