@@ -354,6 +354,60 @@ int32_t rgpu_search_batch_device(rgpu_segment* seg, const rgpu_query* queries, i
                                  const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, void* hits_dev,
                                  void* total_hits_dev, void* hip_stream);
 
+/* ---- doc sets: cached filters as FILTER / MUST_NOT masks --------------------------------------------------------------- */
+/* What stands beside term clauses in production queries is a filter that is not a term: an ACL, a category set, a date range, a
+ * FilterQuery function — most often one LRUQueryCache has already turned into a per-leaf bit set (search/cache/query_cache.rs:
+ * 301-372 fills a FixedBitSet from a non-scoring weight without consulting live docs; :434-452 hands it out as
+ * ConstantScoreScorer(0.0) under FILTER / MUST_NOT clauses; query/filter_query.rs:155-233 does the same with a predicate).
+ * rgpu_docset is that set for ONE segment, in HBM, as FixedBitSet words: bit (doc & 63) of u64 word (doc >> 6), ceil(max_doc / 64)
+ * words, no bit at or past max_doc — the layout of rgpu_segment_upload's live_docs.
+ *
+ * The equivalence the masked calls rest on: for a query Q with a scorer of its own, doc sets F / X and live docs L,
+ * FilterQuery(Q, F) and the BooleanQuery "Q's clauses, #F, -X" collect the same docs, report the same total_hits and produce the
+ * same f32 scores as Q alone on a leaf whose live docs are L AND F AND NOT X — provided Q contributes a MUST or FILTER clause of
+ * its own and, for -X, min_should_match <= 1 (boolean_query.rs:235-251 reuses the outer min_should_match for the MUST_NOT union).
+ * The filter scorer adds + 0.0 somewhere in ConjunctionScorer::score (conjunction_scorer.rs:87-95): x + 0.0 == x bit for bit for
+ * every x but -0.0 (which becomes +0.0 in the reference: the one deviation). NOT equivalent, and refused by the mirrors: SHOULD
+ * clauses whose only required clause is a doc set ("b c #F": the reference matches all of F), a lone #F, and sloppy phrases
+ * (next_limit counts deleted docs but not docs outside a conjoined filter). Only rgpu_search_batch and rgpu_search_batch_device
+ * have masked forms: the phrase, phrase-bool, phrase-or, rescore, planner and sharded / record entry points do not.
+ *
+ * Ownership: a doc set belongs to the segment it was made for (using it with another one: RGPU_ERR_ILLEGAL_ARGUMENT) and is
+ * freed before it. rgpu_docset_free waits for the masked searches in flight that read the set. Every constructor returns a
+ * finished set (it ends synchronised). Doc sets are not part of rgpu_segment_footprint: rgpu_docset_bytes. */
+typedef struct rgpu_docset rgpu_docset;
+/* BitDocIdSet: ceil(max_doc / 64) words from the host. A bit at or past max_doc: RGPU_ERR_ILLEGAL_ARGUMENT. */
+int32_t rgpu_docset_from_words(rgpu_segment* seg, const uint64_t* words, rgpu_docset** out_set);
+/* Leaf-local doc ids in any order, repeats allowed; n_docs = 0: the empty set. An id outside [0, max_doc): RGPU_ERR_ILLEGAL_ARGUMENT. */
+int32_t rgpu_docset_from_docs(rgpu_segment* seg, const int32_t* docs, int64_t n_docs, rgpu_docset** out_set);
+/* The cache fill: out_sets[q] = the docs queries[q] matches in this leaf, live docs NOT applied (query_cache.rs:335-342), nothing
+ * scored (weights are ignored). Served: RGPU_OP_TERM, flat RGPU_OP_AND, flat RGPU_OP_OR with min_should_match <= 1 and any clause
+ * count, each with or without MUST_NOT term clauses. A clause absent from the leaf behaves as in BooleanWeight::create_scorer:
+ * the AND becomes the empty set, the SHOULD clause drops out. RGPU_ERR_UNSUPPORTED: any other op, min_should_match >= 2, a demote
+ * byte, RGPU_OP_WITH_SHOULD / nested flags. A batch with a conjunction of two or more distinct terms runs the search's conjunction
+ * kernel and needs a similarity table uploaded (RGPU_ERR_ILLEGAL_STATE otherwise). On failure no set is returned. */
+int32_t rgpu_docset_collect_batch(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
+                                  int32_t n_terms_total, rgpu_docset** out_sets);
+/* AND of all_of, minus every none_of; n_all = 0: the complement of the none_of inside [0, max_doc) (n_all = n_none = 0: every doc). */
+int32_t rgpu_docset_combine(rgpu_segment* seg, rgpu_docset* const* all_of, int32_t n_all, rgpu_docset* const* none_of, int32_t n_none,
+                            rgpu_docset** out_set);
+int32_t rgpu_docset_cardinality(const rgpu_docset* set, int64_t* n_out);
+/* words_out: ceil(max_doc / 64) u64 */
+int32_t rgpu_docset_words(rgpu_docset* set, uint64_t* words_out);
+/* HBM bytes the set holds (its words, and the `live AND set` words a masked search on a segment with deletions has formed) */
+int64_t rgpu_docset_bytes(const rgpu_docset* set);
+void rgpu_docset_free(rgpu_docset* set);
+/* rgpu_search_batch / rgpu_search_batch_device restricted to `set`: bit for bit the rows and totals those calls return on a segment
+ * uploaded with live_docs = live AND set, for every op and flag they accept and any k up to RGPU_MAX_K. A masked batch runs as a
+ * batch on a segment with deletions does: single-term queries take the exhaustive path (no block-max pruning under a mask), the
+ * heap-order disjunction kernels are not used. rgpu_config.or_deferred does not apply: a masked call never defers. The first masked
+ * use of a set on a segment with deletions forms live AND set (one pass over the words, kept with the set). */
+int32_t rgpu_search_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_query* queries, int32_t n_queries,
+                                 const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out);
+int32_t rgpu_search_batch_device_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_query* queries, int32_t n_queries,
+                                        const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, void* hits_dev,
+                                        void* total_hits_dev, void* hip_stream);
+
 /* TopDocsCollector::finish_parallel (collector/top_docs.rs:157-172): merge n_lists per-leaf / per-shard
  * top-k lists (layout [list][query][k], device memory) into [query][k] under the canonical order and sum
  * the hit counts ([list][query] -> [query]). Enqueue-only on hip_stream, like rgpu_search_batch_device. */

@@ -2,6 +2,7 @@
 for host buffers, raw integers for device pointers / hipStream_t handles."""
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -75,6 +76,8 @@ EXPORTS = [
     "rgpu_search_batch_sharded", "rgpu_comm_status", "rgpu_comm_reserve", "rgpu_comm_gathers_issued", "rgpu_comm_init_all", "rgpu_search_batch_sharded_all", "rgpu_record_bytes",
     "rgpu_search_batch_record_device", "rgpu_merge_records_device", "rgpu_last_search_counters",
     "rgpu_planner_create", "rgpu_planner_create_flat", "rgpu_planner_destroy", "rgpu_planner_sim_table", "rgpu_planner_set_sim_table", "rgpu_plan_uniform_ids",
+    "rgpu_docset_from_words", "rgpu_docset_from_docs", "rgpu_docset_collect_batch", "rgpu_docset_combine", "rgpu_docset_cardinality", "rgpu_docset_words",
+    "rgpu_docset_bytes", "rgpu_docset_free", "rgpu_search_batch_masked", "rgpu_search_batch_device_masked",
     "rgpu_plan_uniform_bytes", "rgpu_plan_batch_ids", "rgpu_plan_batch_bytes", "rgpu_planner_search_uniform_ids_device", "rgpu_planner_search_uniform_ids_sharded",
 ]
 
@@ -171,6 +174,16 @@ def lib():
         "rgpu_search_batch": (i32, [vp, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_batch_device": (i32, [vp, vp, i32, vp, i32, i32, vp, vp, vp]),
         "rgpu_merge_topk_device": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "rgpu_docset_from_words": (i32, [vp, vp, C.POINTER(vp)]),
+        "rgpu_docset_from_docs": (i32, [vp, vp, i64, C.POINTER(vp)]),
+        "rgpu_docset_collect_batch": (i32, [vp, vp, i32, vp, i32, vp]),
+        "rgpu_docset_combine": (i32, [vp, vp, i32, vp, i32, C.POINTER(vp)]),
+        "rgpu_docset_cardinality": (i32, [vp, C.POINTER(i64)]),
+        "rgpu_docset_words": (i32, [vp, vp]),
+        "rgpu_docset_bytes": (i64, [vp]),
+        "rgpu_docset_free": (None, [vp]),
+        "rgpu_search_batch_masked": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp]),
+        "rgpu_search_batch_device_masked": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp]),
         "rgpu_bm25_compute_weight": (i32, [f32, f32, i64, i64, i64, vp, i32, f32, vp, vp, vp]),
         "rgpu_bm25_encode_norm": (C.c_uint8, [f32, i32]),
         "rgpu_bm25_term_weights": (i32, [i64, i64, vp, i64, f32, vp]),
@@ -642,6 +655,42 @@ class Comm:
             pass
 
 
+class DocSet:
+    """rgpu_docset: a set of ONE segment's doc ids in HBM as FixedBitSet words (the layout of live docs). Made by
+    Segment.docset_from_words / docset_from_docs / docset_collect_batch / docset_combine; freed before its segment."""
+
+    def __init__(self, segment, handle):
+        self.segment = segment
+        self._h = handle
+        segment._docsets.append(weakref.ref(self))
+
+    @property
+    def cardinality(self):
+        n = C.c_int64(0)
+        _check(lib().rgpu_docset_cardinality(self._h, C.byref(n)))
+        return int(n.value)
+
+    @property
+    def nbytes(self):
+        return int(lib().rgpu_docset_bytes(self._h))
+
+    def words(self):
+        out = np.zeros((max(self.segment.max_doc, 0) + 63) // 64, dtype=np.uint64)
+        _check(lib().rgpu_docset_words(self._h, out.ctypes.data if out.size else None))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().rgpu_docset_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Segment:
     """rgpu_segment: one uploaded leaf (.doc bytes, norms, live docs in HBM)."""
 
@@ -655,7 +704,7 @@ class Segment:
                                                doc_base, None if lv is None else lv.ctypes.data, index_options, C.byref(h)))
         self._h = h
         self.max_doc, self.doc_base = max_doc, doc_base
-        import weakref
+        self._docsets = []  # weakrefs: doc sets are freed before the segment they belong to
         ctx._segments.append(weakref.ref(self))
 
     @property
@@ -782,6 +831,53 @@ class Segment:
         _check(lib().rgpu_search_batch(self._h, q.ctypes.data, q.size, t.ctypes.data, t.size, k, hits.ctypes.data, totals.ctypes.data))
         return hits, totals
 
+    def docset_from_words(self, words):
+        """rgpu_docset_from_words: ceil(max_doc / 64) u64 FixedBitSet words -> DocSet"""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        if w.size != (max(self.max_doc, 0) + 63) // 64:
+            raise ValueError("a doc set of this segment has %d words" % ((max(self.max_doc, 0) + 63) // 64))
+        h = C.c_void_p()
+        _check(lib().rgpu_docset_from_words(self._h, w.ctypes.data if w.size else None, C.byref(h)))
+        return DocSet(self, h)
+
+    def docset_from_docs(self, docs):
+        """rgpu_docset_from_docs: leaf-local doc ids in any order, repeats allowed -> DocSet"""
+        d = np.ascontiguousarray(docs, dtype=np.int32)
+        h = C.c_void_p()
+        _check(lib().rgpu_docset_from_docs(self._h, d.ctypes.data if d.size else None, d.size, C.byref(h)))
+        return DocSet(self, h)
+
+    def docset_collect_batch(self, queries, terms):
+        """rgpu_docset_collect_batch (the query cache's fill): one DocSet per query, live docs not applied"""
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=QUERY_TERM_DTYPE)
+        out = (C.c_void_p * max(q.size, 1))()
+        _check(lib().rgpu_docset_collect_batch(self._h, q.ctypes.data, q.size, t.ctypes.data, t.size, out))
+        return [DocSet(self, C.c_void_p(out[i])) for i in range(q.size)]
+
+    def docset_combine(self, all_of=(), none_of=()):
+        """rgpu_docset_combine: AND of all_of, minus every none_of (no all_of: the complement of the none_of)"""
+        a = (C.c_void_p * max(len(all_of), 1))(*[d._h for d in all_of])
+        x = (C.c_void_p * max(len(none_of), 1))(*[d._h for d in none_of])
+        h = C.c_void_p()
+        _check(lib().rgpu_docset_combine(self._h, a if len(all_of) else None, len(all_of), x if len(none_of) else None, len(none_of), C.byref(h)))
+        return DocSet(self, h)
+
+    def search_batch_masked(self, docset, queries, terms, k):
+        """rgpu_search_batch_masked: search_batch restricted to `docset` (a DocSet of this segment)"""
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=QUERY_TERM_DTYPE)
+        hits = np.zeros((q.size, max(k, 1)), dtype=HIT_DTYPE)
+        totals = np.zeros(q.size, dtype=np.int64)
+        _check(lib().rgpu_search_batch_masked(self._h, docset._h, q.ctypes.data, q.size, t.ctypes.data, t.size, k, hits.ctypes.data, totals.ctypes.data))
+        return hits, totals
+
+    def search_batch_device_masked(self, docset, queries, terms, k, hits_ptr, totals_ptr, stream=0):
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=QUERY_TERM_DTYPE)
+        _check(lib().rgpu_search_batch_device_masked(self._h, docset._h, q.ctypes.data, q.size, t.ctypes.data, t.size, k, hits_ptr, totals_ptr,
+                                                     stream or None))
+
     def search_batch_record_device(self, queries, terms, k, record_ptr, stream=0):
         """This shard's record ([hits][counts][status], record_bytes(n_queries, k) bytes of device memory); enqueue-only."""
         q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE)
@@ -796,6 +892,11 @@ class Segment:
 
     def close(self):
         if getattr(self, "_h", None):
+            for ref in self._docsets:
+                ds = ref()
+                if ds is not None:
+                    ds.close()
+            self._docsets = []
             lib().rgpu_segment_free(self._h)
             self._h = None
 

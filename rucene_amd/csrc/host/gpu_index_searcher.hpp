@@ -31,6 +31,7 @@
 
 #include "../../../include/rucene_gpu.h"
 #include "bm25_similarity.hpp"
+#include "docset_plan.hpp"
 
 namespace rucene {
 
@@ -428,6 +429,52 @@ struct PhraseDisjunctionQuery : Query {
 };
 
 // RescoreRequest (search/scorer/rescorer.rs:67-116): how a second query's score is folded into the first pass's
+// A filter that is not a term, as the query cache holds it (search/cache/query_cache.rs:301-372): a handle to one doc set per leaf,
+// owned by the GpuIndexSearcher that made it (cache_filter / filter_from_docs / filter_from_bits) until drop_filter or its end.
+struct CachedFilter {
+  uint64_t id = 0;
+};
+// `query` restricted to the docs every one of `filters` holds and none of `excludes` holds (rgpu_search_batch_masked). Two spellings:
+//   FilteredQuery::filter_query(Q, {F ...})          FilterQuery(Q, F) (query/filter_query.rs:155-233): Q needs a scorer of its own, no more
+//   FilteredQuery::clauses(Q, {F ...}, {X ...})      the BooleanQuery "Q's clauses, #F, -X": the rows are the reference's when Q brings a
+//                                                    MUST or FILTER clause of its own ("b c #F" is ReqOptScorer(F, b | c) there and matches
+//                                                    ALL of F) and, for -X, min_should_match <= 1 (boolean_query.rs:235-251)
+// Anything else — a phrase underneath included: a sloppy phrase's next_limit counts deleted docs, not docs outside a filter, and the
+// phrase entry points have no masked form — is UnsupportedOperation, i.e. cpu_fallback. `query` is not owned.
+struct FilteredQuery : Query {
+  const Query* query = nullptr;
+  std::vector<CachedFilter> filters, excludes;
+  bool as_filter_query = false;
+  static FilteredQuery filter_query(const Query& q, std::vector<CachedFilter> f) {
+    FilteredQuery out;
+    out.query = &q;
+    out.filters = std::move(f);
+    out.as_filter_query = true;
+    return out;
+  }
+  static FilteredQuery clauses(const Query& q, std::vector<CachedFilter> f, std::vector<CachedFilter> x = {}) {
+    FilteredQuery out;
+    out.query = &q;
+    out.filters = std::move(f);
+    out.excludes = std::move(x);
+    return out;
+  }
+  void check_served() const;  // (below PhraseBooleanQuery / PhraseDisjunctionQuery's definitions)
+};
+inline void FilteredQuery::check_served() const {
+  if (!query || (filters.empty() && excludes.empty()) || (as_filter_query && (filters.empty() || !excludes.empty())))
+    throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "a filtered query takes a query and at least one cached filter");
+  if (dynamic_cast<const PhraseQuery*>(query) || dynamic_cast<const PhraseBooleanQuery*>(query) || dynamic_cast<const PhraseDisjunctionQuery*>(query))
+    throw Error(RGPU_ERR_UNSUPPORTED, "a filtered phrase is not served by the GPU path");
+  if (dynamic_cast<const FilteredQuery*>(query) || dynamic_cast<const NestedBooleanQuery*>(query))
+    throw Error(RGPU_ERR_UNSUPPORTED, "a filtered query over a nested or another filtered query is not served by the GPU path");
+  if (as_filter_query) return;
+  if (const BooleanQuery* b = dynamic_cast<const BooleanQuery*>(query)) {
+    if (b->must_queries.empty()) throw Error(RGPU_ERR_UNSUPPORTED, "a doc set as the only required clause is not served by the GPU path (the reference matches all of it)");
+    if (!excludes.empty() && b->min_should_match > 1) throw Error(RGPU_ERR_UNSUPPORTED, "a MUST_NOT doc set beside min_should_match >= 2 is not served by the GPU path");
+  }
+}
+
 struct RescoreRequest {
   const Query* query = nullptr;  // TermQuery, an all-MUST / all-SHOULD BooleanQuery, or a PhraseQuery (sloppy: no repeated term)
   float query_weight = 1.0f, rescore_weight = 1.0f;
@@ -632,6 +679,8 @@ class GpuIndexSearcher {
   }
   ~GpuIndexSearcher() {
     for (rgpu_planner* p : planners_) rgpu_planner_destroy(p);
+    for (auto& m : masks_) for (rgpu_docset* d : m.second) rgpu_docset_free(d);   // doc sets go before their segments
+    for (auto& f : filters_) for (rgpu_docset* d : f.second) rgpu_docset_free(d);
     for (auto& l : leaves_) rgpu_segment_free(l.segment);
     rgpu_shutdown(ctx_);
   }
@@ -658,6 +707,78 @@ class GpuIndexSearcher {
   // hand the query to the host's CPU searcher — where rust/gpu/searcher.rs calls DefaultIndexSearcher::search
   bool flatten_nested = false;
   std::function<void(const Query&, TopDocsCollector&)> cpu_fallback;
+
+  // ---- cached filters: doc sets in HBM as FILTER / MUST_NOT masks (include/rucene_gpu.h rgpu_docset_*) ---------------------------
+  // LRUQueryCache::do_cache on the GPU: per leaf the docs `query` matches, live docs NOT applied (query_cache.rs:335-342). A TermQuery
+  // or a flat BooleanQuery that packs to TERM / AND / OR with min_should_match <= 1 (MUST_NOT term clauses allowed); anything else is
+  // UnsupportedOperation from the library.
+  CachedFilter cache_filter(const Query& query) {
+    std::vector<rgpu_docset*> sets(leaves_.size(), nullptr);
+    try {
+      for (size_t li = 0; li < leaves_.size(); ++li) {
+        std::vector<rgpu_query> qs;
+        std::vector<rgpu_query_term> ts;
+        plan({&query}, li, &qs, &ts);
+        check(rgpu_docset_collect_batch(leaves_[li].segment, qs.data(), 1, ts.data(), static_cast<int32_t>(ts.size()), &sets[li]));
+      }
+    } catch (...) {
+      for (rgpu_docset* d : sets) rgpu_docset_free(d);
+      throw;
+    }
+    return keep(std::move(sets));
+  }
+  // GLOBAL doc ids in any order, repeats allowed, split by the leaves' doc bases
+  CachedFilter filter_from_docs(const std::vector<int64_t>& global_docs) {
+    std::vector<std::vector<int32_t>> per_leaf(leaves_.size());
+    for (int64_t d : global_docs) {
+      size_t li = 0;
+      while (li < leaves_.size() && !(d >= leaves_[li].doc_base && d < static_cast<int64_t>(leaves_[li].doc_base) + leaves_[li].max_doc)) ++li;
+      if (li == leaves_.size()) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "a doc id outside every leaf");
+      per_leaf[li].push_back(static_cast<int32_t>(d - leaves_[li].doc_base));
+    }
+    std::vector<rgpu_docset*> sets(leaves_.size(), nullptr);
+    try {
+      for (size_t li = 0; li < leaves_.size(); ++li)
+        check(rgpu_docset_from_docs(leaves_[li].segment, per_leaf[li].data(), static_cast<int64_t>(per_leaf[li].size()), &sets[li]));
+    } catch (...) {
+      for (rgpu_docset* d : sets) rgpu_docset_free(d);
+      throw;
+    }
+    return keep(std::move(sets));
+  }
+  // FixedBitSet words, ceil(max_doc / 64) per leaf (what a cached BitDocIdSet holds)
+  CachedFilter filter_from_bits(const std::vector<const uint64_t*>& per_leaf_words) {
+    if (per_leaf_words.size() != leaves_.size()) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "a cached filter holds one bit set per leaf");
+    std::vector<rgpu_docset*> sets(leaves_.size(), nullptr);
+    try {
+      for (size_t li = 0; li < leaves_.size(); ++li) check(rgpu_docset_from_words(leaves_[li].segment, per_leaf_words[li], &sets[li]));
+    } catch (...) {
+      for (rgpu_docset* d : sets) rgpu_docset_free(d);
+      throw;
+    }
+    return keep(std::move(sets));
+  }
+  int64_t filter_cardinality(CachedFilter f) const {
+    int64_t n = 0;
+    for (rgpu_docset* d : sets_of(f)) {
+      int64_t c = 0;
+      check(rgpu_docset_cardinality(d, &c));
+      n += c;
+    }
+    return n;
+  }
+  // frees the filter's doc sets and every memoised combination that names it
+  void drop_filter(CachedFilter f) {
+    for (auto it = masks_.begin(); it != masks_.end();) {
+      const bool names = std::count(it->first.first.begin(), it->first.first.end(), f.id) || std::count(it->first.second.begin(), it->first.second.end(), f.id);
+      if (names) { for (rgpu_docset* d : it->second) rgpu_docset_free(d); it = masks_.erase(it); }
+      else ++it;
+    }
+    auto at = filters_.find(f.id);
+    if (at == filters_.end()) return;
+    for (rgpu_docset* d : at->second) rgpu_docset_free(d);
+    filters_.erase(at);
+  }
 
   // IndexSearcher::search(query, collector) for a TopDocsCollector
   void search(const Query& query, TopDocsCollector& collector) {
@@ -688,7 +809,11 @@ class GpuIndexSearcher {
   // (PhraseQuery rows go through rgpu_search_phrase_batch, PhraseBooleanQuery rows through rgpu_search_phrase_bool_batch,
   // PhraseDisjunctionQuery rows through rgpu_search_phrase_or_batch, the rest through rgpu_search_batch: one call per kind and leaf,
   // rows keep their order)
+  // FilteredQuery rows are grouped by their combination of doc sets (host/docset_plan.hpp: caller order kept inside a group) and searched
+  // masked, one rgpu_search_batch_masked per group and leaf; every other row goes the way it went.
   std::vector<TopDocs> search_many(const std::vector<const Query*>& queries, size_t k) {
+    for (const Query* q : queries)
+      if (dynamic_cast<const FilteredQuery*>(q)) return search_filtered(queries, k);
     std::vector<size_t> phrase_rows, bool_rows, or_rows, plain_rows;
     for (size_t i = 0; i < queries.size(); ++i) {
       if (dynamic_cast<const PhraseQuery*>(queries[i])) phrase_rows.push_back(i);
@@ -961,6 +1086,80 @@ class GpuIndexSearcher {
     }
   }
 
+  CachedFilter keep(std::vector<rgpu_docset*> sets) {
+    CachedFilter f;
+    f.id = ++next_filter_id_;
+    filters_[f.id] = std::move(sets);
+    return f;
+  }
+  const std::vector<rgpu_docset*>& sets_of(CachedFilter f) const {
+    auto at = filters_.find(f.id);
+    if (at == filters_.end()) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "a cached filter belongs to the searcher that made it (and is gone after drop_filter)");
+    return at->second;
+  }
+  // one doc set per leaf for a combination of filters and excludes: a single filter is its own mask; anything else is combined once per
+  // combination and leaf (rgpu_docset_combine) and kept
+  const std::vector<rgpu_docset*>& masks_of(const rgpu_host::DocsetKey& key) {
+    if (key.filters.size() == 1 && key.excludes.empty()) return sets_of(CachedFilter{key.filters[0]});
+    const auto mk = std::make_pair(key.filters, key.excludes);
+    auto at = masks_.find(mk);
+    if (at != masks_.end()) return at->second;
+    std::vector<rgpu_docset*> made(leaves_.size(), nullptr);
+    try {
+      for (size_t li = 0; li < leaves_.size(); ++li) {
+        std::vector<rgpu_docset*> all, none;
+        for (uint64_t id : key.filters) all.push_back(sets_of(CachedFilter{id})[li]);
+        for (uint64_t id : key.excludes) none.push_back(sets_of(CachedFilter{id})[li]);
+        check(rgpu_docset_combine(leaves_[li].segment, all.data(), static_cast<int32_t>(all.size()), none.data(), static_cast<int32_t>(none.size()), &made[li]));
+      }
+    } catch (...) {
+      for (rgpu_docset* d : made) rgpu_docset_free(d);
+      throw;
+    }
+    return masks_.emplace(mk, std::move(made)).first->second;
+  }
+  std::vector<TopDocs> search_filtered(const std::vector<const Query*>& queries, size_t k) {
+    std::vector<rgpu_host::DocsetKey> keys(queries.size());
+    std::vector<const Query*> inner(queries.size());
+    for (size_t i = 0; i < queries.size(); ++i) {   // refused before any leaf is touched
+      inner[i] = queries[i];
+      if (const FilteredQuery* f = dynamic_cast<const FilteredQuery*>(queries[i])) {
+        f->check_served();
+        std::vector<uint64_t> fs, xs;
+        for (CachedFilter c : f->filters) { sets_of(c); fs.push_back(c.id); }
+        for (CachedFilter c : f->excludes) { sets_of(c); xs.push_back(c.id); }
+        keys[i] = rgpu_host::docset_key(std::move(fs), std::move(xs));
+        inner[i] = f->query;
+      }
+    }
+    std::vector<TopDocs> out(queries.size());
+    for (const rgpu_host::DocsetGroup& grp : rgpu_host::group_by_docset_key(keys)) {
+      std::vector<const Query*> part;
+      for (int32_t r : grp.rows) part.push_back(inner[static_cast<size_t>(r)]);
+      std::vector<TopDocs> got;
+      if (grp.key.empty()) {
+        got = search_many(part, k);
+      } else {
+        const std::vector<rgpu_docset*>& masks = masks_of(grp.key);
+        const int32_t nq = static_cast<int32_t>(part.size());
+        std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
+        std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
+        for (size_t li = 0; li < leaves_.size(); ++li) {
+          std::vector<rgpu_query> qs;
+          std::vector<rgpu_query_term> ts;
+          plan(part, li, &qs, &ts);
+          leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
+          leaf_totals[li].assign(static_cast<size_t>(nq), 0);
+          check(rgpu_search_batch_masked(leaves_[li].segment, masks[li], qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
+                                         leaf_hits[li].data(), leaf_totals[li].data()));
+        }
+        got = merge_leaves(leaf_hits, leaf_totals, nq, k);
+      }
+      for (size_t i = 0; i < grp.rows.size(); ++i) out[static_cast<size_t>(grp.rows[i])] = std::move(got[i]);
+    }
+    return out;
+  }
+
   // TopDocsCollector::finish_parallel (top_docs.rs:157-172) over a handful of leaves: canonical order
   std::vector<TopDocs> merge_leaves(const std::vector<std::vector<rgpu_hit>>& leaf_hits, const std::vector<std::vector<int64_t>>& leaf_totals,
                                     int32_t nq, size_t k) const {
@@ -1144,6 +1343,9 @@ class GpuIndexSearcher {
   CollectionStatistics stats_;
   int32_t sim_table_ = -1;
   std::vector<rgpu_planner*> planners_;  // per leaf and naming scheme (2 * leaf + by-bytes), created on first use
+  std::map<uint64_t, std::vector<rgpu_docset*>> filters_;  // CachedFilter::id -> one doc set per leaf
+  std::map<std::pair<std::vector<uint64_t>, std::vector<uint64_t>>, std::vector<rgpu_docset*>> masks_;  // (filters, excludes) -> combined sets per leaf
+  uint64_t next_filter_id_ = 0;
 };
 
 }  // namespace rucene

@@ -1,0 +1,173 @@
+// Doc sets: a set of ONE segment's doc ids in HBM as FixedBitSet words (bit doc & 63 of u64 word doc >> 6, ceil(max_doc / 64)
+// words, no bit at or past max_doc) — the layout of SegView::live, so every collecting kernel reads one as its live docs.
+// GPU counterpart of the query cache's fill (search/cache/query_cache.rs:301-372: a non-scoring weight's matches collected once per
+// leaf into a FixedBitSet, BitSetLeafCollector :520-536) and of the bit-set algebra behind FILTER / MUST_NOT clauses that are not terms.
+//   k_docset_from_docs     host-given ids (any order, repeats) -> bits; ids outside the segment are counted, not written
+//   k_docset_lists<CLEAR>  (set row, term) jobs: the term's prepared list decoded block by block, bits set — or cleared (MUST_NOT)
+//   k_docset_from_emitted  the candidate lists k_search_and leaves in emit mode -> bits (conjunctions)
+//   k_docset_combine       AND of sets, minus sets, inside [0, max_doc), optionally AND live docs; counts the result
+// The kernels view the words as u32 (little endian: bit doc & 31 of u32 word doc >> 5 is the same bit).
+#pragma once
+#include "decode.hpp"
+#include "decode_terms.hpp"
+#include "types.hpp"
+
+namespace rgpu {
+
+constexpr int DOCSET_THREADS = 256;
+constexpr int DOCSET_WAVES = DOCSET_THREADS / 64;
+constexpr int DOCSET_BLOCKS_PER_ITEM = 4;   // 128-posting blocks one wavefront of k_docset_lists decodes (the last item of a term: + its tail)
+constexpr int DOCSET_MAX_OPERANDS = 16;     // sets on either side of one k_docset_combine launch
+
+// ids outside [0, max_doc) are counted in status[0] (the host refuses the call) and never touch memory. One atomic per id: the ids
+// arrive in no order, so there is nothing to combine in registers (repeats of one id are idempotent).
+__global__ __launch_bounds__(DOCSET_THREADS) void k_docset_from_docs(const int32_t* __restrict__ docs, int64_t n, int32_t max_doc,
+                                                                      uint32_t* __restrict__ words, unsigned int* __restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * DOCSET_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const int32_t d = docs[i];
+  if ((uint32_t)d >= (uint32_t)max_doc) { atomicAdd(status, 1u); return; }
+  atomicOr(words + ((uint32_t)d >> 5), 1u << (d & 31));
+}
+
+struct DocsetJob {
+  uint32_t term;   // index into the launch's DevTerm array
+  uint32_t row;    // index into the launch's row pointers (the set the bits go to)
+};
+
+// The 128 postings of a block as the wavefront holds them — lane l: postings 2l and 2l + 1, doc ids ascending along that order — to
+// ONE atomic per distinct 32-bit word. A word's bits are gathered in registers first: every lane merges its two postings when they
+// share a word, a segmented suffix OR over the lanes (keyed on the lane's first word, five shuffles) collects a word's run, and the
+// lane that touches a word first issues the atomic — through its second posting when the run starts there. Estimate: a list that holds one doc
+// in g has 128 postings over 128 * g / 32 = 4 g words, so g <= 8 gives <= 32 atomics per block (0.25 per posting) where one atomic per
+// posting (k_bitmap_memb's shape) gives 128; past g = 32 every posting has a word of its own and the two shapes meet.
+// v0 / v1: the posting exists (a prefix of the order); docs outside the segment are dropped (corrupt lists never write out of bounds).
+template <bool CLEAR>
+__device__ __forceinline__ void docset_block_bits(uint32_t* __restrict__ words, int32_t max_doc, int32_t d0, int32_t d1, bool v0, bool v1, int lane) {
+  constexpr uint32_t NONE = 0xffffffffu;
+  v0 = v0 && (uint32_t)d0 < (uint32_t)max_doc;
+  v1 = v1 && (uint32_t)d1 < (uint32_t)max_doc;
+  uint32_t wa = v0 ? (uint32_t)d0 >> 5 : NONE, ma = v0 ? 1u << (d0 & 31) : 0u;
+  uint32_t wb = v1 ? (uint32_t)d1 >> 5 : NONE, mb = v1 ? 1u << (d1 & 31) : 0u;
+  if (!v0) { wa = wb; ma = mb; }             // (only a damaged list: the lane's one posting is its first and its last)
+  if (!v1 || wb == wa) { ma |= (wb == wa ? mb : 0u); wb = wa; mb = ma; }  // one word in this lane: first == last
+  // s = OR of ma over this lane and the lanes right behind it whose FIRST word is wa
+  uint32_t s = ma;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t ow = (uint32_t)__shfl_down((int)wa, off), os = (uint32_t)__shfl_down((int)s, off);
+    if (lane + off < 64 && ow == wa) s |= os;
+  }
+  const uint32_t prev_wa = (uint32_t)__shfl_up((int)wa, 1), prev_wb = (uint32_t)__shfl_up((int)wb, 1);
+  const uint32_t next_wa = (uint32_t)__shfl_down((int)wa, 1), next_s = (uint32_t)__shfl_down((int)s, 1);
+  // the first word: this lane starts its run unless the lane before touches the word (as its first or as its last word)
+  const bool head_a = wa != NONE && (lane == 0 || (prev_wa != wa && prev_wb != wa));
+  // the last word, when it is another one: its run starts here, and goes on with the next lanes' first words
+  const bool head_b = wb != wa && wb != NONE;
+  const uint32_t bits_b = mb | ((lane < 63 && next_wa == wb) ? next_s : 0u);
+  if (head_a && s != 0u) { if (CLEAR) atomicAnd(words + wa, ~s); else atomicOr(words + wa, s); }
+  if (head_b && bits_b != 0u) { if (CLEAR) atomicAnd(words + wb, ~bits_b); else atomicOr(words + wb, bits_b); }
+}
+
+// Items = (job, chunk of DOCSET_BLOCKS_PER_ITEM blocks) as in k_decode_terms, decoded with the same device functions (both .doc
+// formats, all-equal blocks, the prepared VInt tail, the singleton of the term-dictionary entry, docs-only fields); live docs are NOT
+// consulted (query_cache.rs:335-342). CLEAR runs as a launch of its own behind the setting launch of the same rows.
+template <bool LEGACY, bool CLEAR>
+__global__ __launch_bounds__(DOCSET_THREADS) void k_docset_lists(SegView seg, const DevTerm* __restrict__ terms, const DocsetJob* __restrict__ jobs,
+                                                                 const int64_t* __restrict__ item_prefix, int n_jobs, int64_t n_items,
+                                                                 uint32_t* const* __restrict__ rows) {
+  __shared__ __attribute__((aligned(16))) uint8_t slabs[DOCSET_WAVES][SLAB_BYTES];
+  const int lane = lane_id();
+  const int wave = wave_id();
+  const int64_t item = (int64_t)blockIdx.x * DOCSET_WAVES + wave;
+  if (item >= n_items) return;
+  const int j = upper_slot_wave(item_prefix, n_jobs, item, lane);
+  const int chunk = (int)(item - item_prefix[j]);
+  const DocsetJob J = jobs[j];
+  const DevTerm T = terms[J.term];
+  uint32_t* const words = rows[J.row];
+  uint8_t* slab = slabs[wave];
+  const int b0 = chunk * DOCSET_BLOCKS_PER_ITEM;
+  const int b1 = min(T.nblocks, b0 + DOCSET_BLOCKS_PER_ITEM);
+  int32_t base = b0 == 0 ? 0 : seg.dir_last[T.dir_base + b0 - 1];
+  const uint8_t* term_rows = seg.bstore + T.bs_base;
+  stream_blocks<LEGACY, false, 1>(term_rows, seg.dir_row, seg.dir_hdr, T.dir_base, nullptr, b0, b1, slab, lane, base,
+                                  [&](int, int32_t d0, int32_t d1, uint32_t, uint32_t, uint32_t, uint32_t) {
+                                    docset_block_bits<CLEAR>(words, seg.max_doc, d0, d1, true, true, lane);
+                                  });
+  if (b1 == T.nblocks) {
+    if (T.df == 1) {
+      docset_block_bits<CLEAR>(words, seg.max_doc, T.singleton_doc, 0, lane == 0, false, lane);
+    } else if (T.tail_n > 0) {
+      int32_t d0, d1;
+      uint32_t f0, f1;
+      tail_load(term_rows, seg.dir_row[T.dir_base + T.nblocks], lane, d0, d1, f0, f1);  // decoded and validated at prepare time
+      docset_block_bits<CLEAR>(words, seg.max_doc, d0, d1, 2 * lane < T.tail_n, 2 * lane + 1 < T.tail_n, lane);
+    }
+  }
+}
+
+// k_search_and in emit mode leaves query q's matches at docs[emit_prefix[q] .. + emit_count[q]) in any order, deleted docs with the
+// sign bit set: they belong in the set all the same. One thread per slot; slots behind a query's count are skipped.
+__global__ __launch_bounds__(DOCSET_THREADS) void k_docset_from_emitted(const int32_t* __restrict__ docs, const int64_t* __restrict__ emit_prefix,
+                                                                         const unsigned long long* __restrict__ emit_count, int n_queries,
+                                                                         int64_t n_slots, int32_t max_doc, uint32_t* const* __restrict__ rows) {
+  const int64_t slot = (int64_t)blockIdx.x * DOCSET_THREADS + threadIdx.x;
+  if (slot >= n_slots) return;
+  const int q = upper_slot(emit_prefix, n_queries, slot);
+  if ((unsigned long long)(slot - emit_prefix[q]) >= emit_count[q]) return;
+  const int32_t d = docs[slot] & 0x7fffffff;
+  if ((uint32_t)d >= (uint32_t)max_doc) return;
+  atomicOr(rows[q] + ((uint32_t)d >> 5), 1u << (d & 31));
+}
+
+struct DocsetCombineArgs {
+  const uint64_t* all_of[DOCSET_MAX_OPERANDS];
+  const uint64_t* none_of[DOCSET_MAX_OPERANDS];
+  const uint64_t* live;   // nullable: AND the segment's live docs (the mask of a masked search)
+  int32_t n_all, n_none;
+  int32_t max_doc;
+};
+
+// out = AND all_of, AND NOT every none_of, AND (doc < max_doc) [AND live]; n_all = 0 starts from all ones. A lane handles two u64
+// words with 16-byte loads and one 16-byte store; the last word of an odd count is handled alone with 8-byte accesses (the operands'
+// allocations end with their last word). `out` may be one of the operands (element-wise). The result's bits are counted: popcount,
+// wave reduction, one atomic add per workgroup into *cardinality (the caller zeroes it).
+__global__ __launch_bounds__(DOCSET_THREADS) void k_docset_combine(DocsetCombineArgs a, uint64_t* out,  // (may alias an operand)
+                                                                    unsigned long long* __restrict__ cardinality) {
+  __shared__ int wave_counts[DOCSET_WAVES];
+  const int64_t n_words = ((int64_t)a.max_doc + 63) >> 6;
+  const int64_t w0 = 2 * ((int64_t)blockIdx.x * DOCSET_THREADS + threadIdx.x);
+  int count = 0;
+  if (w0 < n_words) {
+    const bool pair = w0 + 1 < n_words;
+    uint64_t x = ~0ull, y = ~0ull;
+    auto load2 = [&](const uint64_t* p, uint64_t& u, uint64_t& v) {
+      if (pair) { const ulonglong2 t = *reinterpret_cast<const ulonglong2*>(p + w0); u = t.x; v = t.y; }
+      else { u = p[w0]; v = 0ull; }
+    };
+    for (int i = 0; i < a.n_all; ++i) { uint64_t u, v; load2(a.all_of[i], u, v); x &= u; y &= v; }
+    for (int i = 0; i < a.n_none; ++i) { uint64_t u, v; load2(a.none_of[i], u, v); x &= ~u; y &= ~v; }
+    if (a.live != nullptr) { uint64_t u, v; load2(a.live, u, v); x &= u; y &= v; }
+    // the bits at and past max_doc of the last word
+    const int tail = a.max_doc & 63;
+    const uint64_t tail_mask = tail == 0 ? ~0ull : ((1ull << tail) - 1ull);
+    if (w0 == n_words - 1) x &= tail_mask;
+    if (!pair) y = 0ull;
+    else if (w0 + 1 == n_words - 1) y &= tail_mask;
+    if (pair) { ulonglong2 t; t.x = x; t.y = y; *reinterpret_cast<ulonglong2*>(out + w0) = t; }
+    else out[w0] = x;
+    count = __popcll(x) + __popcll(y);
+  }
+  const int wsum = wave_reduce_add(count);
+  if (lane_id() == 0) wave_counts[wave_id()] = wsum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int total = 0;
+#pragma unroll
+    for (int i = 0; i < DOCSET_WAVES; ++i) total += wave_counts[i];
+    if (total != 0) atomicAdd(cardinality, (unsigned long long)total);
+  }
+}
+
+}  // namespace rgpu

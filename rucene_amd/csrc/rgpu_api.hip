@@ -41,6 +41,8 @@
 #include "host/phrase_or_plan.hpp"
 #include "kernels/search_term.hpp"
 #include "kernels/search_term_query.hpp"
+#include "kernels/docset.hpp"
+#include "host/docset_plan.hpp"
 
 using namespace rgpu;
 
@@ -304,6 +306,9 @@ struct rgpu_segment {
   uint8_t* d_rank_to_norm = nullptr;
   int32_t n_norm_ranks = 0;
   uint64_t* d_live = nullptr;
+  // rgpu_search_batch*_masked: the doc set's `live AND set` words, installed under ctx->mu for the duration of ONE call (MaskScope) and
+  // null otherwise. Everything that asks "which docs does this search collect" reads live_words(), never d_live
+  const uint64_t* call_mask = nullptr;
   int32_t max_doc = 0, doc_base = 0, version = 1;
   bool has_freqs = true;  // false: IndexOptions::Docs (no freq blocks, plain-delta tails, every freq 1)
   DevVec<int32_t> dir_last;
@@ -614,6 +619,11 @@ struct Staged : rucene::StageView {
 };
 #define STAGE_SIZED(sg, st) Staged sg(st); RGPU_TRY(sg.rc)  // the only way a Staged is made: nobody fills buffers that failed to grow
 
+// The live docs a search of this segment collects under: the segment's own, or the mask of the masked call that is running (ctx->mu
+// held). The ONE place the kernels' SegView::live and the host's pruning decisions (sketches, the heap-order disjunction kernels, the
+// fused TERM call's fast path) read them from; d_live itself is named only where it is uploaded, freed, sized and combined into a mask.
+static inline const uint64_t* live_words(const rgpu_segment* s) { return s->call_mask ? s->call_mask : s->d_live; }
+
 static SegView seg_view(const rgpu_segment* s) {
   SegView v;
   v.doc = s->d_doc;
@@ -621,7 +631,7 @@ static SegView seg_view(const rgpu_segment* s) {
   v.rank_to_norm = s->d_rank_to_norm;
   v.pnorm = s->d_norms ? s->pnorm.p : nullptr;
   v.n_norm_ranks = s->n_norm_ranks;
-  v.live = s->d_live;
+  v.live = live_words(s);
   v.dir_last = s->dir_last.p;
   v.dir_off = s->dir_off.p;
   v.dir_row = s->dir_row.p;
@@ -2899,7 +2909,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
   }
   // (the fixed-point kernels rank by exact totals and round to f32 afterwards: across passes that would need a ceiling in
   // their own key space — deep result pages of a >= 10-clause disjunction go through the clause-order kernel instead)
-  const bool or_wide_ok = c->cfg.or_wide >= 0 && seg->d_norms && seg->n_norm_ranks > 0 && !seg->d_live && k_total <= RGPU_PASS_K;
+  const bool or_wide_ok = c->cfg.or_wide >= 0 && seg->d_norms && seg->n_norm_ranks > 0 && !live_words(seg) && k_total <= RGPU_PASS_K;
   if ((c->cfg.or_bitmaps >= 0 || c->cfg.and_bitmaps >= 0) && c->n_sim_tables > 0) {
     // doc bitmaps for the dense terms of the disjunctions k_or_lazy can take, and of conjunctions (k_search_and answers a
     // candidate of such a clause with one bit instead of walking the list's blocks)
@@ -2949,7 +2959,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
   // block-max sketches (search_term.hpp) for the long lists single-term queries name: built once per term, from the frontier words
   // stage B left in the directory and the table of the query that names the term first. Like the bitmaps an accelerator, never a
   // requirement: a failure to build one only means the query starts without a threshold.
-  if (c->term_sketches && seg->d_norms && seg->n_norm_ranks > 0 && !seg->d_live && c->n_sim_tables > 0) {
+  if (c->term_sketches && seg->d_norms && seg->n_norm_ranks > 0 && !live_words(seg) && c->n_sim_tables > 0) {
     std::vector<SketchJob> jobs;
     std::vector<int64_t> job_fp;
     rucene::FlatFpMap<uint32_t> fresh;  // doc_start_fp -> 1 + sketch index, for the clauses of this call
@@ -3455,14 +3465,10 @@ extern "C" int32_t rgpu_search_batch_device(rgpu_segment* seg, const rgpu_query*
   return rc;
 }
 
-extern "C" int32_t rgpu_search_batch(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
-                                     int32_t n_terms_total, int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
-  if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !hits_out || !total_hits_out)
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
+// rgpu_search_batch behind its argument checks (ctx mutex held, device set): shared with rgpu_search_batch_masked
+static int32_t search_batch_host_locked(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
+                                        int32_t n_terms_total, int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
   rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
   // device-side result rows of the blocking variant live in the context (grow-only): the call ends with a stream
   // sync, so they are free again when it returns
   // IndexSearcher::search is ONE query per call (search/searcher.rs:487-525): a batch of one is a launch-latency exercise — 66 us
@@ -3495,6 +3501,467 @@ extern "C" int32_t rgpu_search_batch(rgpu_segment* seg, const rgpu_query* querie
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) rc = fail(RGPU_ERR_RUNTIME, "device to host copy failed");
   }
   return rc;
+}
+
+extern "C" int32_t rgpu_search_batch(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
+                                     int32_t n_terms_total, int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
+  if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !hits_out || !total_hits_out)
+    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
+  rgpu_ctx* c = seg->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  return search_batch_host_locked(seg, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out);
+}
+
+// ---- doc sets: cached filters as FILTER / MUST_NOT masks (include/rucene_gpu.h rgpu_docset_*; the plan: host/docset_plan.hpp; the
+// kernels: kernels/docset.hpp) -----------------------------------------------------------------------------------------------------
+// Every constructor ends synchronised on the context's stream, so a finished set can be read from any stream without an event. A
+// masked search installs `live AND set` as the segment's live docs for the duration of the call (MaskScope, under ctx->mu): the
+// kernels take SegView by value, and every host decision asks live_words(). Launch sequences:
+//   from_words        copy, k_docset_combine (the count)
+//   from_docs         copy, k_docset_from_docs, k_docset_combine (the count)
+//   collect_batch     term preparation as a search; k_docset_lists<set>, k_docset_lists<clear> for TERM / OR rows; k_search_and in
+//                     emit mode (MUST_NOT clauses through its HAS_NOT instantiation) and k_docset_from_emitted for AND rows; one
+//                     k_docset_combine per row (the count)
+//   combine           k_docset_combine, once per DOCSET_MAX_OPERANDS operands of a side
+//   masked search     first use of a set on a segment with deletions: k_docset_combine (live AND set), kept; then the search
+struct rgpu_docset {
+  rgpu_ctx* ctx = nullptr;
+  uint64_t seg_uid = 0;
+  int32_t max_doc = 0;
+  size_t n_words = 0;
+  uint64_t* d_words = nullptr;           // n_words u64 (the allocation is never empty)
+  uint64_t* d_mask = nullptr;            // live AND set: formed by the first masked search when the segment has deletions
+  unsigned long long* d_count = nullptr; // [0]: cardinality (k_docset_combine), [1]: ids out of range (k_docset_from_docs) / a count nobody reads; 4 words
+  int64_t cardinality = 0;
+  std::vector<hipEvent_t> in_flight;     // one per masked search enqueued and not yet seen finished
+};
+
+static size_t docset_alloc_bytes(size_t n_words) { return std::max<size_t>(16, (n_words * 8 + 15) & ~size_t(15)); }
+
+static int32_t docset_new(rgpu_segment* seg, rgpu_docset** out) {
+  rgpu_docset* d = new rgpu_docset();
+  d->ctx = seg->ctx;
+  d->seg_uid = seg->uid;
+  d->max_doc = seg->max_doc;
+  d->n_words = (size_t)rgpu_host::docset_word_count(seg->max_doc);
+  hipError_t e = hipMalloc(&d->d_words, docset_alloc_bytes(d->n_words));
+  if (e == hipSuccess) e = hipMalloc(&d->d_count, 32);
+  if (e == hipSuccess) e = hipMemsetAsync(d->d_words, 0, docset_alloc_bytes(d->n_words), seg->ctx->stream);
+  if (e != hipSuccess) {
+    if (d->d_words) (void)hipFree(d->d_words);
+    if (d->d_count) (void)hipFree(d->d_count);
+    delete d;
+    return fail(RGPU_ERR_RUNTIME, std::string("doc set allocation: ") + hipGetErrorString(e));
+  }
+  *out = d;
+  return RGPU_OK;
+}
+static void docset_delete(rgpu_docset* d) {
+  if (!d) return;
+  for (hipEvent_t ev : d->in_flight) { (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
+  if (d->d_words) (void)hipFree(d->d_words);
+  if (d->d_mask) (void)hipFree(d->d_mask);
+  if (d->d_count) (void)hipFree(d->d_count);
+  delete d;
+}
+
+// out = AND all_of, minus every none_of, inside [0, max_doc) [AND live]; *d_count += its cardinality. Enqueue-only.
+static int32_t docset_combine_launch(rgpu_ctx* c, hipStream_t stream, int32_t max_doc, const uint64_t* const* all_of, int32_t n_all,
+                                     const uint64_t* const* none_of, int32_t n_none, const uint64_t* live, uint64_t* out,
+                                     unsigned long long* d_count) {
+  HIP_TRY(hipMemsetAsync(d_count, 0, 8, stream));
+  const int64_t n_words = rgpu_host::docset_word_count(max_doc);
+  if (n_words == 0) return RGPU_OK;
+  const unsigned grid = wg_count(((unsigned long long)(n_words + 1) / 2 + DOCSET_THREADS - 1) / DOCSET_THREADS);
+  int32_t a = 0, x = 0;
+  bool first = true;
+  while (first || a < n_all || x < n_none) {  // rounds of DOCSET_MAX_OPERANDS per side; later rounds start from what the earlier ones left
+    DocsetCombineArgs args;
+    std::memset(&args, 0, sizeof args);
+    args.max_doc = max_doc;
+    if (!first) args.all_of[args.n_all++] = out;
+    while (a < n_all && args.n_all < DOCSET_MAX_OPERANDS) args.all_of[args.n_all++] = all_of[a++];
+    while (x < n_none && args.n_none < DOCSET_MAX_OPERANDS) args.none_of[args.n_none++] = none_of[x++];
+    const bool last = a >= n_all && x >= n_none;
+    args.live = last ? live : nullptr;
+    if (!last) HIP_TRY(hipMemsetAsync(d_count, 0, 8, stream));
+    TimedLaunch tl(c, stream, "k_docset_combine", 0);
+    RGPU_LAUNCH(k_docset_combine, dim3(grid), dim3(DOCSET_THREADS), 0, stream, args, out, last ? d_count : d_count + 1);
+    first = false;
+  }
+  HIP_TRY(launch_status());
+  return RGPU_OK;
+}
+// the bits past max_doc cleared (there are none unless a caller's words had some: refused before), the set counted; ends synchronised
+static int32_t docset_finish(rgpu_docset* d, hipStream_t stream) {
+  const uint64_t* self[1] = {d->d_words};
+  RGPU_TRY(docset_combine_launch(d->ctx, stream, d->max_doc, self, 1, nullptr, 0, nullptr, d->d_words, d->d_count));
+  unsigned long long n = 0;
+  HIP_TRY(hipMemcpyAsync(&n, d->d_count, 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  d->cardinality = (int64_t)n;
+  return RGPU_OK;
+}
+static int32_t docset_check(const rgpu_segment* seg, const rgpu_docset* set) {
+  if (set->seg_uid != seg->uid || set->ctx != seg->ctx) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "the doc set belongs to another segment");
+  return RGPU_OK;
+}
+
+extern "C" int32_t rgpu_docset_from_words(rgpu_segment* seg, const uint64_t* words, rgpu_docset** out_set) {
+  if (!seg || !out_set || (!words && seg->max_doc > 0)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  *out_set = nullptr;
+  if (!rgpu_host::docset_words_valid(words, seg->max_doc)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a bit at or past max_doc is set");
+  rgpu_ctx* c = seg->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  rgpu_docset* d = nullptr;
+  RGPU_TRY(docset_new(seg, &d));
+  int32_t rc = RGPU_OK;
+  if (d->n_words > 0 && hipMemcpyAsync(d->d_words, words, d->n_words * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    rc = fail(RGPU_ERR_RUNTIME, "copy of the doc set's words failed");
+  if (rc == RGPU_OK) rc = docset_finish(d, c->stream);
+  if (rc != RGPU_OK) { (void)hipStreamSynchronize(c->stream); docset_delete(d); return rc; }
+  *out_set = d;
+  return RGPU_OK;
+}
+
+extern "C" int32_t rgpu_docset_from_docs(rgpu_segment* seg, const int32_t* docs, int64_t n_docs, rgpu_docset** out_set) {
+  if (!seg || !out_set || n_docs < 0 || (!docs && n_docs > 0)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  *out_set = nullptr;
+  rgpu_ctx* c = seg->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  rgpu_docset* d = nullptr;
+  RGPU_TRY(docset_new(seg, &d));
+  int32_t* d_docs = nullptr;
+  auto run = [&]() -> int32_t {
+    if (n_docs > 0) {
+      HIP_TRY(hipMalloc(&d_docs, (size_t)n_docs * 4));
+      HIP_TRY(hipMemcpyAsync(d_docs, docs, (size_t)n_docs * 4, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemsetAsync(d->d_count + 1, 0, 8, c->stream));
+      {
+        TimedLaunch tl(c, c->stream, "k_docset_from_docs", n_docs);
+        RGPU_LAUNCH(k_docset_from_docs, dim3(wg_count(((unsigned long long)n_docs + DOCSET_THREADS - 1) / DOCSET_THREADS)), dim3(DOCSET_THREADS), 0, c->stream,
+                    d_docs, n_docs, seg->max_doc, reinterpret_cast<uint32_t*>(d->d_words), reinterpret_cast<unsigned int*>(d->d_count + 1));
+      }
+      HIP_TRY(launch_status());
+      unsigned int bad = 0;
+      HIP_TRY(hipMemcpyAsync(&bad, d->d_count + 1, 4, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      if (bad != 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a doc id outside [0, max_doc)");
+    }
+    return docset_finish(d, c->stream);
+  };
+  const int32_t rc = run();
+  if (rc != RGPU_OK) (void)hipStreamSynchronize(c->stream);
+  if (d_docs) (void)hipFree(d_docs);
+  if (rc != RGPU_OK) { docset_delete(d); return rc; }
+  *out_set = d;
+  return RGPU_OK;
+}
+
+extern "C" int32_t rgpu_docset_combine(rgpu_segment* seg, rgpu_docset* const* all_of, int32_t n_all, rgpu_docset* const* none_of, int32_t n_none,
+                                       rgpu_docset** out_set) {
+  if (!seg || !out_set || n_all < 0 || n_none < 0 || (n_all > 0 && !all_of) || (n_none > 0 && !none_of)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  *out_set = nullptr;
+  std::vector<const uint64_t*> a, x;
+  for (int32_t i = 0; i < n_all; ++i) { if (!all_of[i]) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null doc set"); RGPU_TRY(docset_check(seg, all_of[i])); a.push_back(all_of[i]->d_words); }
+  for (int32_t i = 0; i < n_none; ++i) { if (!none_of[i]) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null doc set"); RGPU_TRY(docset_check(seg, none_of[i])); x.push_back(none_of[i]->d_words); }
+  rgpu_ctx* c = seg->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  rgpu_docset* d = nullptr;
+  RGPU_TRY(docset_new(seg, &d));
+  int32_t rc = docset_combine_launch(c, c->stream, d->max_doc, a.data(), n_all, x.data(), n_none, nullptr, d->d_words, d->d_count);
+  unsigned long long n = 0;
+  if (rc == RGPU_OK && (hipMemcpyAsync(&n, d->d_count, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess))
+    rc = fail(RGPU_ERR_RUNTIME, "doc set combine failed");
+  if (rc != RGPU_OK) { (void)hipStreamSynchronize(c->stream); docset_delete(d); return rc; }
+  d->cardinality = (int64_t)n;
+  *out_set = d;
+  return RGPU_OK;
+}
+
+extern "C" int32_t rgpu_docset_cardinality(const rgpu_docset* set, int64_t* n_out) {
+  if (!set || !n_out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
+  *n_out = set->cardinality;
+  return RGPU_OK;
+}
+extern "C" int64_t rgpu_docset_bytes(const rgpu_docset* set) {
+  if (!set) return 0;
+  return (int64_t)docset_alloc_bytes(set->n_words) * (set->d_mask ? 2 : 1) + 32;
+}
+extern "C" int32_t rgpu_docset_words(rgpu_docset* set, uint64_t* words_out) {
+  if (!set || (!words_out && set->n_words > 0)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
+  if (set->n_words == 0) return RGPU_OK;
+  std::lock_guard<std::mutex> g(set->ctx->mu);
+  HIP_TRY(hipSetDevice(set->ctx->device));
+  HIP_TRY(hipMemcpy(words_out, set->d_words, set->n_words * 8, hipMemcpyDeviceToHost));
+  return RGPU_OK;
+}
+extern "C" void rgpu_docset_free(rgpu_docset* set) {
+  if (!set) return;
+  (void)hipSetDevice(set->ctx->device);
+  std::lock_guard<std::mutex> g(set->ctx->mu);  // (a masked call in another thread finishes enqueueing first)
+  docset_delete(set);  // waits for every masked search in flight that reads the set
+}
+
+extern "C" int32_t rgpu_docset_collect_batch(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
+                                             int32_t n_terms_total, rgpu_docset** out_sets) {
+  if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !out_sets) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  for (int32_t q = 0; q < n_queries; ++q) out_sets[q] = nullptr;
+  rgpu_ctx* c = seg->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t stream = c->stream;
+  // ---- plan: refusals come before anything is allocated
+  std::vector<rgpu_host::DocsetQueryPlan> plans((size_t)n_queries);
+  std::vector<const rgpu_term_state*> ptrs;
+  bool any_conj = false;
+  for (int32_t q = 0; q < n_queries; ++q) {
+    plans[(size_t)q] = rgpu_host::plan_docset_query(queries[q], terms, n_terms_total);
+    const rgpu_host::DocsetQueryPlan& P = plans[(size_t)q];
+    if (P.status != RGPU_OK) return fail(P.status, P.why);
+    for (const std::vector<const rgpu_term_state*>* side : {&P.positive, &P.negative})
+      for (const rgpu_term_state* st : *side) {
+        RGPU_TRY(validate_state(seg, *st));
+        if (st->doc_freq == 1 && (st->singleton_doc_id < 0 || st->singleton_doc_id >= seg->max_doc)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "singleton_doc_id out of range");
+        ptrs.push_back(st);
+      }
+    any_conj = any_conj || P.conjunction;
+  }
+  if (any_conj && c->n_sim_tables <= 0)
+    return fail(RGPU_ERR_ILLEGAL_STATE, "collecting a conjunction runs the search's conjunction kernel: upload a similarity table first (rgpu_sim_table_upload)");
+  // (a conjunction's lead is walked with its posting-order norms, as in a search; the list kernel needs the blocks alone)
+  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size(), any_conj));
+  std::vector<rgpu_docset*> sets((size_t)n_queries, nullptr);
+  auto drop = [&](int32_t rc) { (void)hipStreamSynchronize(stream); for (rgpu_docset* d : sets) docset_delete(d); return rc; };
+  for (int32_t q = 0; q < n_queries; ++q) { const int32_t rc = docset_new(seg, &sets[(size_t)q]); if (rc != RGPU_OK) return drop(rc); }
+  std::vector<uint32_t*> rows((size_t)n_queries);
+  for (int32_t q = 0; q < n_queries; ++q) rows[(size_t)q] = reinterpret_cast<uint32_t*>(sets[(size_t)q]->d_words);
+  const SegView sv = seg_view(seg);
+  const bool legacy = seg->version < 1;
+  auto lists = [&]() -> int32_t {  // ---- TERM / OR rows: bits set list by list, then the MUST_NOT lists cleared
+    const rgpu_host::DocsetJobs J = rgpu_host::plan_docset_jobs(plans, DOCSET_BLOCKS_PER_ITEM);
+    if (J.set.empty()) return RGPU_OK;
+    std::vector<DevTerm> dt;
+    std::vector<DocsetJob> js, jc;
+    std::vector<int64_t> ps, pc;
+    int64_t postings = 0;
+    for (const std::vector<rgpu_host::DocsetListJob>* side : {&J.set, &J.clear})
+      for (const rgpu_host::DocsetListJob& j : *side) {
+        dt.emplace_back();
+        RGPU_TRY(make_dev_term(seg, *j.term, 0.0f, 0, &dt.back(), false));
+        // (the plan sized the job from doc_freq; the prepared term must agree, or items would run past its blocks)
+        if (rgpu_host::docset_term_items(dt.back().df, DOCSET_BLOCKS_PER_ITEM) != j.n_items || (dt.back().df >= 2 && dt.back().nblocks != dt.back().df / 128))
+          return fail(RGPU_ERR_ILLEGAL_STATE, "internal: a prepared term disagrees with its doc_freq");
+        (side == &J.set ? js : jc).push_back(DocsetJob{(uint32_t)(dt.size() - 1), (uint32_t)j.row});
+        (side == &J.set ? ps : pc).push_back(j.first_item);
+        postings += j.term->doc_freq;
+      }
+    ps.push_back(J.set_items);
+    pc.push_back(J.clear_items);
+    SCRATCH_TAKE(c);
+    Stager st(c);
+    const auto r_t = st.add<DevTerm>(dt.size());
+    const auto r_js = st.add<DocsetJob>(js.size()), r_jc = st.add<DocsetJob>(std::max<size_t>(1, jc.size()));
+    const auto r_ps = st.add<int64_t>(ps.size()), r_pc = st.add<int64_t>(pc.size());
+    const auto r_rows = st.add<uint32_t*>(rows.size());
+    STAGE_SIZED(sg, st);
+    sg.put(r_t, dt);
+    sg.put(r_js, js);
+    sg.put(r_jc, jc);
+    sg.put(r_ps, ps);
+    sg.put(r_pc, pc);
+    sg.put(r_rows, rows);
+    RGPU_TRY(sg.upload(stream));
+    {
+      TimedLaunch tl(c, stream, "k_docset_lists", postings);
+      const unsigned grid = wg_count(((unsigned long long)J.set_items + DOCSET_WAVES - 1) / DOCSET_WAVES);
+      if (legacy) RGPU_LAUNCH((k_docset_lists<true, false>), dim3(grid), dim3(DOCSET_THREADS), 0, stream, sv, (const DevTerm*)sg.dev(r_t), (const DocsetJob*)sg.dev(r_js),
+                              (const int64_t*)sg.dev(r_ps), (int)js.size(), J.set_items, (uint32_t* const*)sg.dev(r_rows));
+      else RGPU_LAUNCH((k_docset_lists<false, false>), dim3(grid), dim3(DOCSET_THREADS), 0, stream, sv, (const DevTerm*)sg.dev(r_t), (const DocsetJob*)sg.dev(r_js),
+                       (const int64_t*)sg.dev(r_ps), (int)js.size(), J.set_items, (uint32_t* const*)sg.dev(r_rows));
+    }
+    if (!jc.empty()) {
+      TimedLaunch tl(c, stream, "k_docset_lists", 0);
+      const unsigned grid = wg_count(((unsigned long long)J.clear_items + DOCSET_WAVES - 1) / DOCSET_WAVES);
+      if (legacy) RGPU_LAUNCH((k_docset_lists<true, true>), dim3(grid), dim3(DOCSET_THREADS), 0, stream, sv, (const DevTerm*)sg.dev(r_t), (const DocsetJob*)sg.dev(r_jc),
+                              (const int64_t*)sg.dev(r_pc), (int)jc.size(), J.clear_items, (uint32_t* const*)sg.dev(r_rows));
+      else RGPU_LAUNCH((k_docset_lists<false, true>), dim3(grid), dim3(DOCSET_THREADS), 0, stream, sv, (const DevTerm*)sg.dev(r_t), (const DocsetJob*)sg.dev(r_jc),
+                       (const int64_t*)sg.dev(r_pc), (int)jc.size(), J.clear_items, (uint32_t* const*)sg.dev(r_rows));
+    }
+    HIP_TRY(launch_status());
+    HIP_TRY(scratch_mark(c, stream));
+    return RGPU_OK;
+  };
+  auto conjunctions = [&]() -> int32_t {  // ---- AND rows: k_search_and emits the matches (deleted docs included, marked), scattered into bits
+    if (!any_conj) return RGPU_OK;
+    const size_t nq = (size_t)n_queries;
+    std::vector<DevQuery> dq(nq, DevQuery{RGPU_OP_AND, 0, 0, 0});
+    std::vector<DevTerm> dt;
+    std::vector<int64_t> item_prefix(nq + 1), emit_prefix(nq + 1);
+    int64_t lead_blocks = 0;
+    for (const rgpu_host::DocsetQueryPlan& P : plans) if (P.conjunction) lead_blocks += P.positive[0]->doc_freq / 128;
+    const int blocks_per_item = and_item_blocks(c, lead_blocks);
+    int64_t items = 0, slots = 0;
+    bool any_not = false;
+    for (size_t q = 0; q < nq; ++q) {
+      const rgpu_host::DocsetQueryPlan& P = plans[q];
+      item_prefix[q] = items;
+      emit_prefix[q] = slots;
+      dq[q].first_term = (int32_t)dt.size();
+      if (!P.conjunction) continue;
+      int32_t sim = terms[queries[q].first_term].sim_table;  // (an emitting conjunction loads its lead's table and scores nothing)
+      if (sim < 0 || sim >= c->n_sim_tables) sim = 0;
+      dq[q] = DevQuery{RGPU_OP_AND, (int32_t)P.positive.size(), (int32_t)dt.size(), (int32_t)P.negative.size()};
+      for (const rgpu_term_state* st : P.positive) { dt.emplace_back(); RGPU_TRY(make_dev_term(seg, *st, 0.0f, sim, &dt.back())); }
+      for (const rgpu_term_state* st : P.negative) { dt.emplace_back(); RGPU_TRY(make_dev_term(seg, *st, 0.0f, sim, &dt.back())); }
+      any_not = any_not || !P.negative.empty();
+      const DevTerm& lead = dt[(size_t)dq[q].first_term];
+      items += lead.nblocks == 0 ? 1 : (lead.nblocks + blocks_per_item - 1) / blocks_per_item;
+      slots += ((int64_t)lead.df + 63) & ~(int64_t)63;  // the lead's doc_freq bounds the matches
+    }
+    item_prefix[nq] = items;
+    emit_prefix[nq] = slots;
+    if (items == 0) return RGPU_OK;
+    SCRATCH_TAKE(c);
+    Stager st(c);
+    const auto r_q = st.add<DevQuery>(nq);
+    const auto r_t = st.add<DevTerm>(dt.size());
+    const auto r_ip = st.add<int64_t>(nq + 1), r_ep = st.add<int64_t>(nq + 1);
+    const auto r_rows = st.add<uint32_t*>(rows.size());
+    STAGE_SIZED(sg, st);
+    sg.put(r_q, dq);
+    sg.put(r_t, dt);
+    sg.put(r_ip, item_prefix);
+    sg.put(r_ep, emit_prefix);
+    sg.put(r_rows, rows);
+    RGPU_TRY(sg.upload(stream));
+    HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
+    HIP_TRY(c->phrase_count.reserve(nq, 0, stream));
+    HIP_TRY(hipMemsetAsync(c->phrase_count.p, 0, nq * 8, stream));
+    const int k_emit = 1;  // nothing is collected: the (empty) top-k lists are the narrowest kind
+    HIP_TRY(c->S->d_partial_keys.reserve((size_t)items * (size_t)k_emit, 0, stream));
+    HIP_TRY(c->S->d_partial_counts.reserve((size_t)items, 0, stream));
+    HIP_TRY(c->S->d_tau.reserve(nq, 0, stream));
+    HIP_TRY(c->S->d_touched.reserve(nq * 2, 0, stream));
+    HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, nq * 8, stream));
+    HIP_TRY(hipMemsetAsync(c->S->d_touched.p, 0, nq * 16, stream));
+    {
+      TimedLaunch tl(c, stream, "k_search_and(doc set candidates)", 0);
+      const int xcd_chunk = and_xcd_chunk(seg);
+      const unsigned grid = wg_count(and_grid((items + AND_WG_WAVES - 1) / AND_WG_WAVES, xcd_chunk));
+      auto go = [&](auto kern) {
+        RGPU_LAUNCH(kern, dim3(grid), dim3(AND_WG_THREADS), 0, stream, sv, (const DevQuery*)sg.dev(r_q), (const DevTerm*)sg.dev(r_t), (const int64_t*)sg.dev(r_ip),
+                    (int)n_queries, items, blocks_per_item, k_emit, c->S->d_partial_keys.p, c->S->d_partial_counts.p, c->S->d_tau.p, c->S->d_touched.p,
+                    (const int64_t*)sg.dev(r_ep), c->phrase_count.p, (void*)c->phrase_docs.p, (const unsigned long long*)nullptr, (const int32_t*)nullptr,
+                    (const TermBitmap*)nullptr, xcd_chunk);
+      };
+      if (any_not) { if (legacy) go(k_search_and<true, false, true, false>); else go(k_search_and<false, false, true, false>); }
+      else { if (legacy) go(k_search_and<true, false, false, false>); else go(k_search_and<false, false, false, false>); }
+    }
+    if (slots > 0) {
+      TimedLaunch tl(c, stream, "k_docset_from_emitted", 0);
+      RGPU_LAUNCH(k_docset_from_emitted, dim3(wg_count(((unsigned long long)slots + DOCSET_THREADS - 1) / DOCSET_THREADS)), dim3(DOCSET_THREADS), 0, stream,
+                  (const int32_t*)c->phrase_docs.p, (const int64_t*)sg.dev(r_ep), (const unsigned long long*)c->phrase_count.p, (int)n_queries, slots, seg->max_doc,
+                  (uint32_t* const*)sg.dev(r_rows));
+    }
+    HIP_TRY(launch_status());
+    HIP_TRY(scratch_mark(c, stream));
+    return RGPU_OK;
+  };
+  int32_t rc = lists();
+  if (rc == RGPU_OK) rc = conjunctions();
+  for (int32_t q = 0; q < n_queries && rc == RGPU_OK; ++q) rc = docset_finish(sets[(size_t)q], stream);
+  if (rc != RGPU_OK) return drop(rc);
+  for (int32_t q = 0; q < n_queries; ++q) out_sets[q] = sets[(size_t)q];
+  return RGPU_OK;
+}
+
+// ---- masked search -----------------------------------------------------------------------------------------------------------------
+// The mask of a masked call: the set itself when the segment has no deletions, else `live AND set`, formed by k_docset_combine the
+// first time the set is used and kept (segments are immutable). Ends synchronised when it forms one, so that any stream may read it.
+static int32_t docset_mask_locked(rgpu_segment* seg, rgpu_docset* set, const uint64_t** mask_out) {
+  if (!seg->d_live) { *mask_out = set->d_words; return RGPU_OK; }
+  if (!set->d_mask) {
+    rgpu_ctx* c = seg->ctx;
+    uint64_t* m = nullptr;
+    HIP_TRY(hipMalloc(&m, docset_alloc_bytes(set->n_words)));
+    const uint64_t* self[1] = {set->d_words};
+    int32_t rc = hipMemsetAsync(m, 0, docset_alloc_bytes(set->n_words), c->stream) == hipSuccess ? RGPU_OK : fail(RGPU_ERR_RUNTIME, "memset of a doc set's mask failed");
+    if (rc == RGPU_OK) rc = docset_combine_launch(c, c->stream, set->max_doc, self, 1, nullptr, 0, seg->d_live, m, set->d_count + 1);
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == RGPU_OK) rc = fail(RGPU_ERR_RUNTIME, "forming a doc set's mask failed");
+    if (rc != RGPU_OK) { (void)hipFree(m); return rc; }
+    set->d_mask = m;
+  }
+  *mask_out = set->d_mask;
+  return RGPU_OK;
+}
+// installs the mask for the rest of the scope. Before it: closures pending from earlier (unmasked, or differently masked) calls are
+// settled — a redo they launch reads the segment's live docs as they were when the batch was enqueued. Inside it nothing is deferred
+// (the entry points leave defer_or false), so no closure of a masked call ever runs outside its scope.
+struct MaskScope {
+  rgpu_segment* seg;
+  MaskScope(rgpu_segment* s, const uint64_t* mask) : seg(s) { seg->call_mask = mask; }
+  ~MaskScope() { seg->call_mask = nullptr; }
+};
+// one event per masked call behind its work on `s`: rgpu_docset_free waits for them (events seen finished are recycled here)
+static void docset_mark_in_flight(rgpu_docset* set, hipStream_t s) {
+  size_t kept = 0;
+  hipEvent_t ev = nullptr;
+  for (hipEvent_t e : set->in_flight) {
+    if (hipEventQuery(e) == hipSuccess) { if (!ev) ev = e; else (void)hipEventDestroy(e); }
+    else set->in_flight[kept++] = e;
+  }
+  (void)hipGetLastError();  // (hipErrorNotReady of the queries is not an error)
+  set->in_flight.resize(kept);
+  if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipStreamSynchronize(s); return; }
+  if (hipEventRecord(ev, s) == hipSuccess) set->in_flight.push_back(ev);
+  else { (void)hipEventDestroy(ev); (void)hipStreamSynchronize(s); }
+}
+
+extern "C" int32_t rgpu_search_batch_device_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_query* queries, int32_t n_queries,
+                                                   const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, void* hits_dev,
+                                                   void* totals_dev, void* hip_stream) {
+  if (!seg || !set || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !hits_dev || !totals_dev)
+    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  RGPU_TRY(docset_check(seg, set));
+  rgpu_ctx* c = seg->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  RGPU_TRY(settle_pending(c));
+  const uint64_t* mask = nullptr;
+  RGPU_TRY(docset_mask_locked(seg, set, &mask));
+  c->defer_or = false;  // a masked call never defers: its redo would run later, outside the scope
+  int32_t rc;
+  {
+    MaskScope scope(seg, mask);
+    rc = search_impl(seg, queries, n_queries, terms, n_terms_total, k, (HitOut*)hits_dev, (int64_t*)totals_dev, s);
+  }
+  docset_mark_in_flight(set, s);
+  return rc;
+}
+
+extern "C" int32_t rgpu_search_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_query* queries, int32_t n_queries,
+                                            const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
+                                            int64_t* total_hits_out) {
+  if (!seg || !set || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !hits_out || !total_hits_out)
+    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
+  RGPU_TRY(docset_check(seg, set));
+  rgpu_ctx* c = seg->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  RGPU_TRY(settle_pending(c));
+  const uint64_t* mask = nullptr;
+  RGPU_TRY(docset_mask_locked(seg, set, &mask));
+  c->defer_or = false;
+  MaskScope scope(seg, mask);
+  return search_batch_host_locked(seg, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out);
 }
 
 extern "C" int32_t rgpu_merge_topk_device(rgpu_ctx* c, const void* hits_dev, const void* totals_dev, int32_t n_lists, int32_t n_queries,
@@ -5805,7 +6272,7 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
   if (timed) laps.start();
   const int32_t sim_table = P->sim_table();
   if (!P->flat() || k > RGPU_PASS_K || c->prepared_budget != 0 || sim_table < 0 || sim_table >= c->n_sim_tables || seg->dir_used == 0) return RGPU_OK;
-  const bool want_sketch = c->term_sketches && seg->d_norms && seg->n_norm_ranks > 0 && !seg->d_live;
+  const bool want_sketch = c->term_sketches && seg->d_norms && seg->n_norm_ranks > 0 && !live_words(seg);
   const bool need_norms = seg->d_norms != nullptr;
   const uint32_t flags = c->sim_monotone[(size_t)sim_table] ? TERM_FLAG_MONOTONE : 0u;
   c->pass = rgpu_ctx::Pass{};

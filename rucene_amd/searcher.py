@@ -253,6 +253,38 @@ class PhraseQuery:
             raise RgpuError(-2, "Must have as many terms as positions")
 
 
+class CachedFilter:
+    """A filter that is not a term, as the query cache holds it: one doc set per leaf of a searcher, in HBM (rgpu_docset). What
+    LRUQueryCache::do_cache leaves behind for a cached weight (search/cache/query_cache.rs:301-372) — made by
+    GpuIndexSearcher.cache_filter (the GPU collects a term / boolean query's matches, live docs not applied), filter_from_docs
+    (global doc ids, e.g. a PointRangeQuery's matches or an ACL) or filter_from_bits (FixedBitSet words per leaf). Goes under
+    `filters=` / `must_nots=` of BooleanQuery.build and into FilterQuery."""
+
+    def __init__(self, searcher, sets):
+        self.searcher, self.sets = searcher, list(sets)
+
+    def cardinality(self):
+        return sum(s.cardinality for s in self.sets)
+
+    def close(self):
+        for s in self.sets:
+            s.close()
+
+
+class FilterQuery:
+    """query/filter_query.rs:155-233: `query`'s docs and scores, restricted to the docs every one of `filters` (CachedFilter)
+    holds. Served by the GPU path when `query` is a term / boolean / dismax / boosting query (rgpu_search_batch_masked); a phrase
+    underneath is UnsupportedOperation, i.e. the caller's CPU path."""
+
+    def __init__(self, query, filters):
+        self.query, self.filters = query, list(filters)
+        if not self.filters or not all(isinstance(f, CachedFilter) for f in self.filters):
+            raise RgpuError(-2, "FilterQuery takes a query and at least one CachedFilter")
+
+    def extract_terms(self):
+        return self.query.extract_terms()
+
+
 class BooleanQuery:
     """Only the trees the GPU path serves: all-SHOULD with any min_should_match (OR), or MUST clauses (AND) with optional
     SHOULD clauses beside them (ReqOptScorer, boolean_query.rs:253-262 — its sequential skipping rule included unless the
@@ -272,7 +304,9 @@ class BooleanQuery:
         msm = min_should_match if min_should_match > 0 else (1 if len(musts) == 0 else 0)
         if len(musts) + len(shoulds) + len(filters) + len(must_nots) == 0:
             raise RgpuError(-2, "boolean query should at least contain one inner query!")
-        if len(must_nots) == 0 and len(musts) + len(shoulds) + len(filters) == 1:
+        if any(isinstance(q, CachedFilter) for q in list(musts) + list(shoulds)):
+            raise RgpuError(-2, "a CachedFilter does not score: it goes under filters= or must_nots=")
+        if len(must_nots) == 0 and len(musts) + len(shoulds) + len(filters) == 1 and not (filters and isinstance(filters[0], CachedFilter)):
             if filters:   # ConstantScoreQuery::with_boost(filter, 0.0) (boolean_query.rs:70-73): every match scores 0
                 if isinstance(filters[0], PhraseQuery):
                     return PhraseQuery(filters[0].terms, filters[0].positions, 0.0, filters[0].slop)
@@ -285,7 +319,9 @@ class BooleanQuery:
         # (a clause that is itself a BooleanQuery builds, as it does in the reference: whether the GPU path serves the tree is
         # decided when it is searched — GpuIndexSearcher.flatten_nested / cpu_fallback)
         # (so does a PhraseQuery clause: GpuIndexSearcher.phrase_bool_parts says which trees over phrases the GPU path serves)
-        if any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery)) for q in list(musts) + list(shoulds) + list(must_nots) + list(filters)):
+        # (a CachedFilter under FILTER / MUST_NOT is a doc-set clause: GpuIndexSearcher.search_batch peels it off and masks the search)
+        if any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery)) for q in list(musts) + list(shoulds)) or \
+                any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, CachedFilter)) for q in list(must_nots) + list(filters)):
             raise RgpuError(-5, "only term, phrase and boolean clauses are known to this mirror")
         return BooleanQuery(list(musts), list(shoulds), msm, list(must_nots), list(filters))
 
@@ -429,6 +465,8 @@ class BooleanQuery:
     def extract_terms(self):  # boolean_query.rs:124-145: MUST, SHOULD and FILTER clauses only (a phrase clause: its terms)
         out = []
         for q in list(self.must_queries) + list(self.should_queries) + list(self.filter_queries):
+            if isinstance(q, CachedFilter):
+                continue   # a set of docs names no term
             out.extend(TermQuery(t, q.boost) for t in q.terms) if isinstance(q, PhraseQuery) else out.append(q)
         return out
 
@@ -563,6 +601,7 @@ class GpuIndexSearcher:
         self._weights = {}
         self._planners = {}       # per leaf: the native batch planner
         self._stats_terms = None  # override_statistics: another leaf's term table / dictionary
+        self._masks = {}          # (filter sets, exclude sets) key -> (the CachedFilters, one combined DocSet per leaf)
 
     def max_doc(self):
         return sum(leaf.max_doc for leaf in self.leaves)
@@ -939,11 +978,113 @@ class GpuIndexSearcher:
         ps["next_limit"] = 0
         return qs, ps, pts, self._pack_term_clauses(term_cs, leaf)
 
+    # ---- doc sets: cached filters as FILTER / MUST_NOT masks ---------------------------------------------------------------------
+    def _cached(self, sets):
+        if len(sets) != len(self.leaves):
+            raise RgpuError(-2, "a cached filter holds one doc set per leaf")
+        return CachedFilter(self, sets)
+
+    def cache_filter(self, query):
+        """LRUQueryCache::do_cache for a query the GPU can collect itself (rgpu_docset_collect_batch): a TermQuery or a flat
+        BooleanQuery that packs to TERM / AND / OR with min_should_match <= 1, MUST_NOT term clauses allowed. Per leaf the docs the
+        query matches, live docs NOT applied (query_cache.rs:335-342). Anything else: UnsupportedOperation."""
+        op, _clauses, opts, _nots = self._flatten(query)
+        if opts or op not in (OP_TERM, OP_AND, OP_OR):
+            raise RgpuError(-5, "a filter is collected on the GPU from a term query or a flat all-MUST / all-SHOULD boolean query")
+        return self._cached([leaf.segment.docset_collect_batch(*self.pack([query], leaf))[0] for leaf in self.leaves])
+
+    def filter_from_docs(self, global_doc_ids):
+        """A filter from GLOBAL doc ids (any order, repeats allowed), split by the leaves' doc bases."""
+        ids = np.asarray(global_doc_ids, dtype=np.int64).ravel()
+        if ids.size and (ids.min() < 0 or ids.max() >= max(leaf.doc_base + leaf.max_doc for leaf in self.leaves)):
+            raise RgpuError(-2, "a doc id outside the index")
+        sets, taken = [], 0
+        for leaf in self.leaves:
+            mine = ids[(ids >= leaf.doc_base) & (ids < leaf.doc_base + leaf.max_doc)]
+            taken += mine.size
+            sets.append(leaf.segment.docset_from_docs((mine - leaf.doc_base).astype(np.int32)))
+        if taken != ids.size:
+            raise RgpuError(-2, "a doc id outside every leaf")
+        return self._cached(sets)
+
+    def filter_from_bits(self, per_leaf_words):
+        """A filter from FixedBitSet words, one u64 array of ceil(max_doc / 64) words per leaf (what a cached BitDocIdSet holds)."""
+        if len(per_leaf_words) != len(self.leaves):
+            raise RgpuError(-2, "a cached filter holds one bit set per leaf")
+        return self._cached([leaf.segment.docset_from_words(w) for leaf, w in zip(self.leaves, per_leaf_words)])
+
+    def _peel(self, query):
+        """query -> (the query without its doc-set clauses, (FILTER CachedFilters, MUST_NOT CachedFilters)). The rest, searched on
+        live docs AND filters AND NOT excludes, collects the reference's docs, counts and f32 scores when (1) it contributes a MUST
+        or FILTER clause of its own — "b c #F" is ReqOptScorer(F, b | c) in the reference and matches ALL of F, a lone #F likewise —
+        and (2) for -X, min_should_match <= 1 (boolean_query.rs:235-251 reuses it for the MUST_NOT union). FilterQuery(Q, F) asks
+        only that Q has a scorer of its own. Phrases are not served under a mask (a sloppy phrase's next_limit counts deleted docs,
+        not docs outside a filter; the phrase entry points have no masked form). Anything else: UnsupportedOperation."""
+        if isinstance(query, FilterQuery):
+            inner, (f, x) = self._peel(query.query)
+            if isinstance(inner, PhraseQuery) or (isinstance(inner, BooleanQuery) and inner.has_phrases()):
+                raise RgpuError(-5, "a filtered phrase is not served by the GPU path")
+            return inner, (f + list(query.filters), x)
+        if not isinstance(query, BooleanQuery):
+            return query, ([], [])
+        f = [q for q in query.filter_queries if isinstance(q, CachedFilter)]
+        x = [q for q in query.must_not_queries if isinstance(q, CachedFilter)]
+        if not f and not x:
+            return query, ([], [])
+        filters = [q for q in query.filter_queries if not isinstance(q, CachedFilter)]
+        must_nots = [q for q in query.must_not_queries if not isinstance(q, CachedFilter)]
+        if not (query.must_queries or filters):
+            raise RgpuError(-5, "a doc set as the only required clause is not served by the GPU path (the reference matches all of it)")
+        if x and query.min_should_match > 1:
+            raise RgpuError(-5, "a MUST_NOT doc set beside min_should_match >= 2 is not served by the GPU path")
+        rest = BooleanQuery.build(list(query.must_queries), list(query.should_queries), filters=filters, must_nots=must_nots,
+                                  min_should_match=query.min_should_match)
+        if isinstance(rest, PhraseQuery) or (isinstance(rest, BooleanQuery) and rest.has_phrases()):
+            raise RgpuError(-5, "a filtered phrase is not served by the GPU path")
+        return rest, (f, x)
+
+    def _mask(self, filters, excludes):
+        """One DocSet per leaf for a (filters, excludes) combination: combined once per combination and leaf
+        (rgpu_docset_combine), memoised on the searcher; a single filter without excludes is its own mask."""
+        for c in filters + excludes:
+            if c.searcher is not self:
+                raise RgpuError(-2, "a cached filter belongs to the searcher that made it")
+        key = (tuple(sorted({id(c) for c in filters})), tuple(sorted({id(c) for c in excludes})))
+        if key not in self._masks:
+            if len(key[0]) == 1 and not key[1]:
+                sets = filters[0].sets
+            else:
+                fs, xs = list({id(c): c for c in filters}.values()), list({id(c): c for c in excludes}.values())
+                sets = [leaf.segment.docset_combine([c.sets[i] for c in fs], [c.sets[i] for c in xs]) for i, leaf in enumerate(self.leaves)]
+            self._masks[key] = (filters + excludes, sets)   # (the CachedFilters stay alive as long as their ids are keys)
+        return key, self._masks[key][1]
+
     def search_batch(self, queries, k):
         """-> (hits[n][k] structured {doc, score}, total_hits[n]) merged over all leaves. A batch may mix term / boolean / dismax /
         boosting queries (rgpu_search_batch), PhraseQuery rows (rgpu_search_phrase_batch), BooleanQuery rows with phrases among their
         required clauses (rgpu_search_phrase_bool_batch) and BooleanQuery rows of SHOULD / MUST_NOT clauses with phrases among the
-        SHOULD ones (rgpu_search_phrase_or_batch): one call per kind and leaf, rows keep their order."""
+        SHOULD ones (rgpu_search_phrase_or_batch): one call per kind and leaf, rows keep their order. Rows with doc-set clauses
+        (CachedFilter under FILTER / MUST_NOT, FilterQuery) are grouped by their combination of sets and searched masked
+        (rgpu_search_batch_masked), one call per group and leaf."""
+        peeled = [self._peel(q) for q in queries]   # (refused before any leaf is touched)
+        if not any(f or x for _, (f, x) in peeled):
+            per_leaf = self._rows_per_leaf(queries, k, None)
+        else:
+            groups = {}   # key -> (masks per leaf or None, caller rows): first appearance first, caller order inside a group
+            for i, (_, (f, x)) in enumerate(peeled):
+                key, masks = self._mask(f, x) if (f or x) else (None, None)
+                groups.setdefault(key, (masks, []))[1].append(i)
+            per_leaf = [(np.zeros((len(queries), k), dtype=_lib.HIT_DTYPE), np.zeros(len(queries), dtype=np.int64)) for _ in self.leaves]
+            for masks, rows in groups.values():
+                part = self._rows_per_leaf([peeled[i][0] for i in rows], k, masks)
+                for (hits, totals), (h, t) in zip(per_leaf, part):
+                    hits[rows], totals[rows] = h, t
+        if len(per_leaf) == 1:
+            return per_leaf[0]
+        return self._merge_leaves(per_leaf, len(queries), k)
+
+    def _rows_per_leaf(self, queries, k, masks):
+        """[(hits, totals)] per leaf for queries without doc-set clauses; masks: one DocSet per leaf the search is restricted to"""
         def kind(q):
             if isinstance(q, PhraseQuery):
                 return 1
@@ -953,10 +1094,12 @@ class GpuIndexSearcher:
         kinds = [kind(q) for q in queries]
         if not any(kinds):
             per_leaf = []
-            for leaf in self.leaves:
+            for i, leaf in enumerate(self.leaves):
                 qs, ts = self.pack(queries, leaf)
-                per_leaf.append(leaf.segment.search_batch(qs, ts, k))
+                per_leaf.append(leaf.segment.search_batch(qs, ts, k) if masks is None else leaf.segment.search_batch_masked(masks[i], qs, ts, k))
         else:
+            if masks is not None:
+                raise RgpuError(-5, "a filtered phrase is not served by the GPU path")
             rows = [np.flatnonzero(np.array(kinds) == kd) for kd in (0, 1, 2, 3)]
             groups = [[queries[i] for i in r] for r in rows]
             for q in groups[2]:   # refused before any leaf is touched
@@ -977,9 +1120,7 @@ class GpuIndexSearcher:
                 if groups[3]:
                     hits[rows[3]], totals[rows[3]] = leaf.segment.search_phrase_or_batch(*self.pack_phrase_or(groups[3], leaf), k)
                 per_leaf.append((hits, totals))
-        if len(per_leaf) == 1:
-            return per_leaf[0]
-        return self._merge_leaves(per_leaf, len(queries), k)
+        return per_leaf
 
     def _merge_leaves(self, per_leaf, n_queries, k):
         # TopDocsCollector::finish_parallel (top_docs.rs:157-172) on the device: [leaf][query][k] -> [query][k]

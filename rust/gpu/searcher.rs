@@ -62,6 +62,20 @@ struct GpuLeaf {
     has_positions: bool,   // .pos attached (rgpu_segment_attach_positions): PhraseQuery can be served
 }
 
+/// A filter that is not a term, as the query cache holds it: one doc set per leaf (by LeafReaderContext::ord), in HBM. What
+/// CachingWrapperWeight::cache leaves for a leaf (search/cache/query_cache.rs:301-372) — made by `cache_filter_bits` from the cached
+/// FixedBitSet words or by `cache_filter_query` on the GPU — and what `try_filtered` takes as FILTER / MUST_NOT sets. Keep it beside the
+/// cache entry it mirrors (same key, same eviction); it is freed before the searcher that made it (doc sets go before their segments).
+pub struct GpuCachedFilter {
+    sets: Vec<*mut RgpuDocset>,
+}
+
+impl Drop for GpuCachedFilter {
+    fn drop(&mut self) {
+        for s in self.sets.drain(..) { unsafe { rgpu_docset_free(s) }; } // waits for the masked searches in flight that read the set
+    }
+}
+
 /// One flat clause list — what the C ABI takes (rgpu_query + rgpu_query_term[]): MUST / SHOULD first, then MUST_NOT.
 struct FlatQuery<'q> {
     op: i32,
@@ -601,6 +615,88 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
     /// any batch the library refuses with RGPU_ERR_UNSUPPORTED) runs through DefaultIndexSearcher::search one by one.
     /// (A batch of identical shape whose terms are known by id or bytes can skip this per-clause work altogether:
     /// rgpu_planner_create + rgpu_plan_uniform_ids / rgpu_plan_batch_bytes resolve, weigh and pack natively.)
+    /// The cached BitDocIdSet of every leaf (`FixedBitSet::bits`, ceil(max_doc / 64) words each, by LeafReaderContext::ord) -> doc sets.
+    pub fn cache_filter_bits(&self, per_leaf_words: &[&[u64]]) -> Result<GpuCachedFilter> {
+        if per_leaf_words.len() != self.leaves.len() { bail!(ErrorKind::IllegalArgument("one bit set per leaf".into())); }
+        let mut made = GpuCachedFilter { sets: Vec::with_capacity(self.leaves.len()) };
+        for (leaf, words) in self.leaves.iter().zip(per_leaf_words.iter()) {
+            let mut set: *mut RgpuDocset = std::ptr::null_mut();
+            check(unsafe { rgpu_docset_from_words(leaf.seg, words.as_ptr(), &mut set) }, self.ctx)?;
+            made.sets.push(set);
+        }
+        Ok(made)
+    }
+
+    /// LRUQueryCache::do_cache on the GPU for a query that flattens to TERM / all-MUST / all-SHOULD (msm <= 1) with or without MUST_NOT
+    /// terms: per leaf the docs it matches, live docs not applied (query_cache.rs:335-342). None: not such a query — fill on the CPU.
+    pub fn cache_filter_query(&self, query: &dyn Query<C>) -> Result<Option<GpuCachedFilter>> {
+        let flat = match self.flatten(query) { Some(f) => f, None => return Ok(None) };
+        let base = flat.op & 0xff;
+        if !flat.optional.is_empty() || (flat.op >> 8) != 0 || !(base == RGPU_OP_TERM || base == RGPU_OP_AND || base == RGPU_OP_OR) { return Ok(None); }
+        let n = flat.n_clauses();
+        if n > RGPU_MAX_QUERY_TERMS as usize { return Ok(None); }
+        let table = self.sim_table(self.cpu.collections_statistics(&self.field).ok_or_else(|| Error::from(ErrorKind::IllegalState("no statistics".into())))?)?;
+        let mut made = GpuCachedFilter { sets: Vec::with_capacity(self.leaves.len()) };
+        for leaf in self.cpu.reader().leaves() {
+            let mut terms = Vec::with_capacity(n);
+            for t in flat.clauses() {
+                terms.push(RgpuQueryTerm { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: 0.0, sim_table: table }); // nothing is scored
+            }
+            let q = RgpuQuery { op: flat.op, n_terms: flat.positive.len() as i32, first_term: 0, n_must_not: flat.must_not.len() as i32 };
+            let mut set: *mut RgpuDocset = std::ptr::null_mut();
+            check(unsafe { rgpu_docset_collect_batch(self.leaves[leaf.ord].seg, &q, 1, terms.as_ptr(), n as i32, &mut set) }, self.ctx)?;
+            made.sets.push(set);
+        }
+        Ok(Some(made))
+    }
+
+    /// `query` restricted to the docs every one of `filters` holds and none of `excludes` holds: rgpu_search_batch_masked per leaf.
+    /// `as_filter_query`: the caller holds FilterQuery(query, filters) (query/filter_query.rs:155-233), which asks only that `query`
+    /// has a scorer of its own; otherwise the sets are FILTER / MUST_NOT clauses of the BooleanQuery `query` was taken out of, and the
+    /// rows are the reference's only when (1) what is left contributes a MUST or FILTER clause — "b c #F" is ReqOptScorer(F, b | c) in
+    /// the reference and matches ALL of F — and (2) for a MUST_NOT set, min_should_match <= 1 (boolean_query.rs:235-251 reuses it for
+    /// the MUST_NOT union). Ok(false): not served here — the CPU searcher takes the whole query (phrases have no masked entry point:
+    /// a sloppy phrase's next_limit counts deleted docs, not docs outside a filter).
+    pub fn try_filtered(&self, query: &dyn Query<C>, filters: &[&GpuCachedFilter], excludes: &[&GpuCachedFilter], as_filter_query: bool,
+                        top: &mut TopDocsCollector, k: usize) -> Result<bool> {
+        if k == 0 || k > RGPU_MAX_K as usize || (filters.is_empty() && excludes.is_empty()) { return Ok(false); }
+        if filters.iter().chain(excludes.iter()).any(|f| f.sets.len() != self.leaves.len()) { bail!(ErrorKind::IllegalArgument("a cached filter of another searcher".into())); }
+        let flat = match self.flatten(query) { Some(f) => f, None => return Ok(false) }; // (a PhraseQuery, a tree over phrases: not flat)
+        let base = flat.op & 0xff;
+        let msm = (flat.op >> 8) & 0xff;
+        if !as_filter_query {
+            if !(base == RGPU_OP_TERM || base == RGPU_OP_AND) { return Ok(false); }   // no required clause of its own
+            if !excludes.is_empty() && msm > 1 { return Ok(false); }
+        }
+        let n = flat.n_clauses();
+        if n > RGPU_MAX_QUERY_TERMS as usize { return Ok(false); }
+        let weights = self.clause_weights(&flat)?;
+        for leaf in self.cpu.reader().leaves() {
+            let seg = self.leaves[leaf.ord].seg;
+            // one set per leaf: the single filter itself, or the AND of the filters minus the excludes (a serving layer memoises this per
+            // combination and leaf, as the Python and C++ mirrors do)
+            let all: Vec<*mut RgpuDocset> = filters.iter().map(|f| f.sets[leaf.ord]).collect();
+            let none: Vec<*mut RgpuDocset> = excludes.iter().map(|f| f.sets[leaf.ord]).collect();
+            let mut combined: *mut RgpuDocset = std::ptr::null_mut();
+            let mask = if all.len() == 1 && none.is_empty() { all[0] } else {
+                check(unsafe { rgpu_docset_combine(seg, all.as_ptr(), all.len() as i32, none.as_ptr(), none.len() as i32, &mut combined) }, self.ctx)?;
+                combined
+            };
+            let mut terms = Vec::with_capacity(n);
+            for (i, t) in flat.clauses().enumerate() {
+                terms.push(RgpuQueryTerm { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: weights[i].0, sim_table: weights[i].1 });
+            }
+            let q = RgpuQuery { op: flat.op, n_terms: flat.positive.len() as i32, first_term: 0, n_must_not: flat.must_not.len() as i32 };
+            let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
+            let mut total: i64 = 0;
+            let rc = unsafe { rgpu_search_batch_masked(seg, mask, &q, 1, terms.as_ptr(), n as i32, k as i32, hits.as_mut_ptr(), &mut total) };
+            if !combined.is_null() { unsafe { rgpu_docset_free(combined) }; }
+            check(rc, self.ctx)?;
+            Self::hand_over(top, &hits, total);
+        }
+        Ok(true)
+    }
+
     pub fn search_many(&self, queries: &[&dyn Query<C>], collectors: &mut [TopDocsCollector]) -> Result<()> {
         assert_eq!(queries.len(), collectors.len());
         if queries.is_empty() { return Ok(()); }
