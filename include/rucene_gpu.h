@@ -408,6 +408,59 @@ int32_t rgpu_search_batch_device_masked(rgpu_segment* seg, rgpu_docset* set, con
                                         const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, void* hits_dev,
                                         void* total_hits_dev, void* hip_stream);
 
+/* ---- point ranges: numeric range filters built as doc sets -------------------------------------------------------------- */
+/* PointRangeQuery (search/query/point_range_query.rs): create_scorer (:503-561) collects the docs that hold a point inside the
+ * closed range — visit_by_packed_value (:626-640) compares unsigned bytes, both ends inclusive — without consulting live docs,
+ * and hands the set out as ConstantScoreScorer(0.0) (PointRangeWeight::new :482; nothing normalises the weight, searcher.rs:
+ * 709-722). Under MUST and FILTER the clause therefore adds + 0.0 and under MUST_NOT it only removes docs: the doc-set
+ * equivalences of the masked searches above, with the same conditions and the same -0.0 deviation.
+ *
+ * rgpu_points holds the points of ONE field of ONE segment in HBM; rgpu_docset_from_point_ranges builds the doc sets of ranges
+ * from it on the device. Points arrive as flat (doc, packed value) arrays: what an IntersectVisitor whose compare() always
+ * answers CellCrossesQuery sees from PointValues::intersect — this library reads no .dim / .dii file.
+ *
+ * ONE dimension only, bytes_per_dim 4 (IntPoint, FloatPoint) or 8 (LongPoint, DoublePoint); anything else is
+ * RGPU_ERR_ILLEGAL_ARGUMENT at attach, and a caller with more dimensions keeps the query on its CPU path
+ * (RGPU_ERR_UNSUPPORTED in the mirrors). Why: PointRangeIntersectVisitor::compare (:642-664) compares a cell against
+ * lower_point[offset..] WITHOUT an end, so for every dimension but the last a cell whose maximum equals the lower bound is
+ * judged CellOutsideQuery — what a multi-dimensional query matches depends on the BKD cell layout and cannot be reproduced from
+ * the points alone. With one dimension the slice is the whole value and the result is the plain set.
+ *
+ * Ownership: points belong to the segment they were attached to and are freed before it; they are not part of
+ * rgpu_segment_footprint (rgpu_points_info.hbm_bytes). */
+typedef struct rgpu_points rgpu_points;
+/* docs[i] in [0, max_doc) in any order, a doc may repeat (a multi-valued field); values: n_points * bytes_per_dim sortable bytes
+ * (IntPoint::encode_dimension etc., core/util/numeric.rs:163-218). n_points = 0 is legal. A doc outside the segment or a
+ * bytes_per_dim other than 4 or 8: RGPU_ERR_ILLEGAL_ARGUMENT, nothing is kept. The arrays are sorted on the host once and held in
+ * two orders: by doc (the keys; the doc ids too unless the field is dense, i.e. holds exactly one point per doc of the segment) and
+ * by value (the doc ids; the sorted keys stay on the host). */
+int32_t rgpu_points_attach(rgpu_segment* seg, int32_t bytes_per_dim, const int32_t* docs, const uint8_t* values, int64_t n_points,
+                           rgpu_points** out_points);
+typedef struct rgpu_points_info {
+  int64_t n_points;
+  int64_t doc_count;     /* distinct docs holding a point */
+  int64_t hbm_bytes;
+  uint8_t min_value[8];  /* first bytes_per_dim bytes; zero when n_points = 0 */
+  uint8_t max_value[8];
+  int32_t bytes_per_dim;
+  int32_t dense;
+} rgpu_points_info;
+int32_t rgpu_points_get_info(const rgpu_points* points, rgpu_points_info* out);
+void rgpu_points_free(rgpu_points* points);
+typedef struct rgpu_point_range {
+  uint8_t lower[8];      /* first bytes_per_dim bytes are used */
+  uint8_t upper[8];
+} rgpu_point_range;
+/* out_sets[r] = the docs of the segment that hold a point p with lower[r] <= p <= upper[r] in unsigned byte order; live docs are
+ * NOT applied (a point on a deleted doc is in the set: the masked searches drop it). lower > upper: the empty set. The sets are
+ * ordinary doc sets, finished and synchronised. On failure no set is returned.
+ * path: 0 = the library chooses per range, 1 = always the value-ordered scatter (one atomic per matching point), 2 = always the
+ * doc-ordered scan (one pass over the column per 16 ranges). Under 0: no launch for a range without a matching point, the
+ * every-doc form when a dense field's [min, max] is covered, the scatter below a measured share of n_points and the scan at or
+ * above it. Every path gives the same words. */
+int32_t rgpu_docset_from_point_ranges(rgpu_points* points, const rgpu_point_range* ranges, int32_t n_ranges, int32_t path,
+                                      rgpu_docset** out_sets);
+
 /* TopDocsCollector::finish_parallel (collector/top_docs.rs:157-172): merge n_lists per-leaf / per-shard
  * top-k lists (layout [list][query][k], device memory) into [query][k] under the canonical order and sum
  * the hit counts ([list][query] -> [query]). Enqueue-only on hip_stream, like rgpu_search_batch_device. */

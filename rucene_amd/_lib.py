@@ -78,6 +78,7 @@ EXPORTS = [
     "rgpu_planner_create", "rgpu_planner_create_flat", "rgpu_planner_destroy", "rgpu_planner_sim_table", "rgpu_planner_set_sim_table", "rgpu_plan_uniform_ids",
     "rgpu_docset_from_words", "rgpu_docset_from_docs", "rgpu_docset_collect_batch", "rgpu_docset_combine", "rgpu_docset_cardinality", "rgpu_docset_words",
     "rgpu_docset_bytes", "rgpu_docset_free", "rgpu_search_batch_masked", "rgpu_search_batch_device_masked",
+    "rgpu_points_attach", "rgpu_points_get_info", "rgpu_points_free", "rgpu_docset_from_point_ranges",
     "rgpu_plan_uniform_bytes", "rgpu_plan_batch_ids", "rgpu_plan_batch_bytes", "rgpu_planner_search_uniform_ids_device", "rgpu_planner_search_uniform_ids_sharded",
 ]
 
@@ -102,6 +103,11 @@ FOOTPRINT_DTYPE = np.dtype([(n, "<i8") for n in ("doc_file_bytes", "norms_bytes"
                                                  "block_store_bytes", "posting_norms_bytes", "prepared_terms", "doc_bitmap_bytes", "doc_bitmap_terms", "doc_bitmap_refused")], align=True)
 PLAN_STATS_DTYPE = np.dtype([("max_doc", "<i8"), ("doc_count", "<i8"), ("sum_total_term_freq", "<i8"), ("k1", "<f4"), ("b", "<f4")], align=True)
 assert SEARCH_COUNTERS_DTYPE.itemsize == 40 and PLAN_STATS_DTYPE.itemsize == 32
+POINTS_INFO_DTYPE = np.dtype([("n_points", "<i8"), ("doc_count", "<i8"), ("hbm_bytes", "<i8"), ("min_value", "u1", (8,)), ("max_value", "u1", (8,)),
+                              ("bytes_per_dim", "<i4"), ("dense", "<i4")], align=True)
+POINT_RANGE_DTYPE = np.dtype([("lower", "u1", (8,)), ("upper", "u1", (8,))], align=True)
+assert POINTS_INFO_DTYPE.itemsize == 48 and POINT_RANGE_DTYPE.itemsize == 16
+POINTS_PATH_AUTO, POINTS_PATH_SCATTER, POINTS_PATH_SCAN = 0, 1, 2   # rgpu_docset_from_point_ranges' path
 
 
 class _KernelStat(C.Structure):
@@ -182,6 +188,10 @@ def lib():
         "rgpu_docset_words": (i32, [vp, vp]),
         "rgpu_docset_bytes": (i64, [vp]),
         "rgpu_docset_free": (None, [vp]),
+        "rgpu_points_attach": (i32, [vp, i32, vp, vp, i64, C.POINTER(vp)]),
+        "rgpu_points_get_info": (i32, [vp, vp]),
+        "rgpu_points_free": (None, [vp]),
+        "rgpu_docset_from_point_ranges": (i32, [vp, vp, i32, i32, vp]),
         "rgpu_search_batch_masked": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_batch_device_masked": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp]),
         "rgpu_bm25_compute_weight": (i32, [f32, f32, i64, i64, i64, vp, i32, f32, vp, vp, vp]),
@@ -691,6 +701,53 @@ class DocSet:
             pass
 
 
+def point_ranges(bounds, bytes_per_dim):
+    """[(lower bytes, upper bytes)] -> POINT_RANGE_DTYPE[]; every bound holds exactly bytes_per_dim sortable bytes"""
+    out = np.zeros(len(bounds), dtype=POINT_RANGE_DTYPE)
+    for i, (lo, hi) in enumerate(bounds):
+        lo, hi = bytes(lo), bytes(hi)
+        if len(lo) != bytes_per_dim or len(hi) != bytes_per_dim:
+            raise RgpuError(-2, "a bound of %d / %d bytes on points of %d bytes" % (len(lo), len(hi), bytes_per_dim))
+        out[i]["lower"][:bytes_per_dim] = np.frombuffer(lo, np.uint8)
+        out[i]["upper"][:bytes_per_dim] = np.frombuffer(hi, np.uint8)
+    return out
+
+
+class Points:
+    """rgpu_points: the one-dimensional points of ONE field of ONE segment in HBM (Segment.attach_points); range_docsets builds
+    the doc sets of closed ranges over them on the device. Freed before its segment."""
+
+    def __init__(self, segment, handle, bytes_per_dim):
+        self.segment, self._h, self.bytes_per_dim = segment, handle, bytes_per_dim
+        segment._points.append(weakref.ref(self))
+
+    def info(self):
+        out = np.zeros(1, dtype=POINTS_INFO_DTYPE)
+        _check(lib().rgpu_points_get_info(self._h, out.ctypes.data))
+        d = {k: int(out[0][k]) for k in ("n_points", "doc_count", "hbm_bytes", "bytes_per_dim", "dense")}
+        d["min_value"], d["max_value"] = out[0]["min_value"][:self.bytes_per_dim].tobytes(), out[0]["max_value"][:self.bytes_per_dim].tobytes()
+        return d
+
+    def range_docsets(self, bounds, path=POINTS_PATH_AUTO):
+        """rgpu_docset_from_point_ranges: one DocSet per (lower bytes, upper bytes) pair, or per row of a POINT_RANGE_DTYPE array"""
+        r = bounds if isinstance(bounds, np.ndarray) and bounds.dtype == POINT_RANGE_DTYPE else point_ranges(bounds, self.bytes_per_dim)
+        r = np.ascontiguousarray(r)
+        out = (C.c_void_p * max(r.size, 1))()
+        _check(lib().rgpu_docset_from_point_ranges(self._h, r.ctypes.data if r.size else None, r.size, int(path), out))
+        return [DocSet(self.segment, C.c_void_p(out[i])) for i in range(r.size)]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().rgpu_points_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Segment:
     """rgpu_segment: one uploaded leaf (.doc bytes, norms, live docs in HBM)."""
 
@@ -705,6 +762,7 @@ class Segment:
         self._h = h
         self.max_doc, self.doc_base = max_doc, doc_base
         self._docsets = []  # weakrefs: doc sets are freed before the segment they belong to
+        self._points = []   # weakrefs: points likewise
         ctx._segments.append(weakref.ref(self))
 
     @property
@@ -863,6 +921,17 @@ class Segment:
         _check(lib().rgpu_docset_combine(self._h, a if len(all_of) else None, len(all_of), x if len(none_of) else None, len(none_of), C.byref(h)))
         return DocSet(self, h)
 
+    def attach_points(self, bytes_per_dim, docs, values):
+        """rgpu_points_attach: (doc, packed value) pairs of one one-dimensional point field -> Points. `values`: n * bytes_per_dim
+        sortable bytes (a u8 array of that size or shape [n, bytes_per_dim])."""
+        d = np.ascontiguousarray(docs, dtype=np.int32).ravel()
+        v = np.ascontiguousarray(values, dtype=np.uint8).ravel()
+        if bytes_per_dim > 0 and v.size != d.size * bytes_per_dim:
+            raise RgpuError(-2, "points: %d value bytes for %d docs of %d bytes" % (v.size, d.size, bytes_per_dim))
+        h = C.c_void_p()
+        _check(lib().rgpu_points_attach(self._h, int(bytes_per_dim), d.ctypes.data if d.size else None, v.ctypes.data if v.size else None, d.size, C.byref(h)))
+        return Points(self, h, int(bytes_per_dim))
+
     def search_batch_masked(self, docset, queries, terms, k):
         """rgpu_search_batch_masked: search_batch restricted to `docset` (a DocSet of this segment)"""
         q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE)
@@ -897,6 +966,11 @@ class Segment:
                 if ds is not None:
                     ds.close()
             self._docsets = []
+            for ref in self._points:
+                pts = ref()
+                if pts is not None:
+                    pts.close()
+            self._points = []
             lib().rgpu_segment_free(self._h)
             self._h = None
 

@@ -26,6 +26,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -475,6 +476,73 @@ inline void FilteredQuery::check_served() const {
   }
 }
 
+// search/query/point_range_query.rs: the docs holding a point of `field` with lower <= value <= upper, both ends inclusive, in unsigned
+// byte order of the sortable bytes. ONE dimension (4 or 8 bytes per bound). It does not score — ConstantScoreScorer(0.0) under MUST and
+// FILTER alike, PointRangeWeight::new :482 — so it is served as a doc set: GpuIndexSearcher::range_filter builds the CachedFilter on
+// the GPU from attached points and range_clauses spells "Q's clauses, +/#ranges, -ranges" as a FilteredQuery. Alone, under SHOULD, as
+// the only required clause or beside a phrase it is UnsupportedOperation (cpu_fallback), as the same shapes with a CachedFilter are.
+struct PointRangeQuery : Query {
+  std::string field;
+  std::vector<uint8_t> lower, upper;
+  int32_t num_dims;   // more than one: UnsupportedOperation at range_filter (what it matches depends on the BKD cell layout)
+  PointRangeQuery(std::string f, std::vector<uint8_t> lo, std::vector<uint8_t> hi, int32_t dims = 1)
+      : field(std::move(f)), lower(std::move(lo)), upper(std::move(hi)), num_dims(dims) {
+    if (num_dims < 1 || lower.size() % static_cast<size_t>(num_dims) != 0)   // PointRangeQuery::new :384-390
+      throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "lowerPoint is not a fixed multiple of numDims");
+    if (lower.size() != upper.size() || lower.empty())   // :391-397
+      throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "lowerPoint and upperPoint have different lengths");
+  }
+};
+// encode_dimension of the four one-dimensional point types (core/util/numeric.rs:163-218): the sign bit flipped, big-endian; floats
+// through sortable_float_bits / sortable_double_bits first (bits ^ ((bits >> 31) & 0x7fffffff), arithmetic shift)
+struct IntPoint {
+  static std::vector<uint8_t> encode(int32_t v) {
+    const uint32_t u = static_cast<uint32_t>(v) ^ 0x80000000u;
+    return {static_cast<uint8_t>(u >> 24), static_cast<uint8_t>(u >> 16), static_cast<uint8_t>(u >> 8), static_cast<uint8_t>(u)};
+  }
+  static PointRangeQuery new_range_query(std::string field, int32_t lo, int32_t hi) { return PointRangeQuery(std::move(field), encode(lo), encode(hi)); }
+  static PointRangeQuery new_exact_query(std::string field, int32_t v) { return new_range_query(std::move(field), v, v); }
+};
+struct LongPoint {
+  static std::vector<uint8_t> encode(int64_t v) {
+    const uint64_t u = static_cast<uint64_t>(v) ^ 0x8000000000000000ull;
+    std::vector<uint8_t> out(8);
+    for (int i = 0; i < 8; ++i) out[static_cast<size_t>(i)] = static_cast<uint8_t>(u >> (56 - 8 * i));
+    return out;
+  }
+  static PointRangeQuery new_range_query(std::string field, int64_t lo, int64_t hi) { return PointRangeQuery(std::move(field), encode(lo), encode(hi)); }
+  static PointRangeQuery new_exact_query(std::string field, int64_t v) { return new_range_query(std::move(field), v, v); }
+};
+struct FloatPoint {
+  static std::vector<uint8_t> encode(float v) {
+    uint32_t bits;
+    std::memcpy(&bits, &v, 4);
+    const uint32_t sortable = bits ^ ((bits & 0x80000000u) ? 0x7fffffffu : 0u);
+    return IntPoint::encode(static_cast<int32_t>(sortable));
+  }
+  static PointRangeQuery new_range_query(std::string field, float lo, float hi) { return PointRangeQuery(std::move(field), encode(lo), encode(hi)); }
+  static PointRangeQuery new_exact_query(std::string field, float v) { return new_range_query(std::move(field), v, v); }
+};
+struct DoublePoint {
+  static std::vector<uint8_t> encode(double v) {
+    uint64_t bits;
+    std::memcpy(&bits, &v, 8);
+    const uint64_t sortable = bits ^ ((bits & 0x8000000000000000ull) ? 0x7fffffffffffffffull : 0ull);
+    return LongPoint::encode(static_cast<int64_t>(sortable));
+  }
+  static PointRangeQuery new_range_query(std::string field, double lo, double hi) { return PointRangeQuery(std::move(field), encode(lo), encode(hi)); }
+  static PointRangeQuery new_exact_query(std::string field, double v) { return new_range_query(std::move(field), v, v); }
+};
+// one leaf's points of a field for GpuIndexSearcher::attach_points: n_points (doc, value) pairs, values n_points * bytes_per_dim
+// sortable bytes; absent() for a leaf without the field
+struct LeafPoints {
+  const int32_t* docs = nullptr;
+  const uint8_t* values = nullptr;
+  int64_t n_points = -1;   // -1: the leaf does not hold the field
+  static LeafPoints absent() { return LeafPoints(); }
+  static LeafPoints of(const int32_t* d, const uint8_t* v, int64_t n) { LeafPoints p; p.docs = d; p.values = v; p.n_points = n; return p; }
+};
+
 struct RescoreRequest {
   const Query* query = nullptr;  // TermQuery, an all-MUST / all-SHOULD BooleanQuery, or a PhraseQuery (sloppy: no repeated term)
   float query_weight = 1.0f, rescore_weight = 1.0f;
@@ -681,6 +749,7 @@ class GpuIndexSearcher {
     for (rgpu_planner* p : planners_) rgpu_planner_destroy(p);
     for (auto& m : masks_) for (rgpu_docset* d : m.second) rgpu_docset_free(d);   // doc sets go before their segments
     for (auto& f : filters_) for (rgpu_docset* d : f.second) rgpu_docset_free(d);
+    for (auto& p : points_) for (rgpu_points* h : p.second.per_leaf) rgpu_points_free(h);   // points too
     for (auto& l : leaves_) rgpu_segment_free(l.segment);
     rgpu_shutdown(ctx_);
   }
@@ -780,6 +849,83 @@ class GpuIndexSearcher {
     filters_.erase(at);
   }
 
+  // ---- point ranges: numeric range filters built as doc sets (include/rucene_gpu.h rgpu_points_*) -----------------------------------
+  // The one-dimensional points of `field`, one LeafPoints per leaf (absent(): the leaf lacks the field — the reference has no scorer
+  // there: nothing matches under MUST / FILTER, nothing is excluded under MUST_NOT). IndexDirectory attaches nothing: no .dim reader.
+  void attach_points(const std::string& field, int32_t bytes_per_dim, const std::vector<LeafPoints>& per_leaf) {
+    if (per_leaf.size() != leaves_.size()) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "points are attached per leaf");
+    FieldPoints fp;
+    fp.bytes_per_dim = bytes_per_dim;
+    fp.per_leaf.assign(leaves_.size(), nullptr);
+    try {
+      for (size_t li = 0; li < leaves_.size(); ++li)
+        if (per_leaf[li].n_points >= 0)
+          check(rgpu_points_attach(leaves_[li].segment, bytes_per_dim, per_leaf[li].docs, per_leaf[li].values, per_leaf[li].n_points, &fp.per_leaf[li]));
+    } catch (...) {
+      for (rgpu_points* h : fp.per_leaf) rgpu_points_free(h);
+      throw;
+    }
+    auto old = points_.find(field);
+    if (old != points_.end()) {
+      for (auto it = range_filters_.begin(); it != range_filters_.end();) {
+        if (std::get<0>(it->first) == field) { drop_filter(it->second); it = range_filters_.erase(it); }
+        else ++it;
+      }
+      for (rgpu_points* h : old->second.per_leaf) rgpu_points_free(h);
+      points_.erase(old);
+    }
+    points_[field] = std::move(fp);
+  }
+  // The memo of range_filter is not bounded here: every distinct range leaves ceil(max_doc / 64) * 8 bytes per leaf in HBM until
+  // drop_range_filters() (or drop_filter of one) — a caller whose ranges move with every query calls it between batches.
+  void drop_range_filters() {
+    for (auto& kv : range_filters_) drop_filter(kv.second);
+    range_filters_.clear();
+  }
+  // PointRangeQuery -> CachedFilter, built on the GPU (rgpu_docset_from_point_ranges), memoised per (field, lower, upper). A field never
+  // attached: UnsupportedOperation; bounds whose length is not the field's: IllegalArgument (point_range_query.rs:510-522).
+  // path: rgpu_docset_from_point_ranges' (0 = the library chooses).
+  CachedFilter range_filter(const PointRangeQuery& q, int32_t path = 0) {
+    if (q.num_dims != 1) throw Error(RGPU_ERR_UNSUPPORTED, "a multi-dimensional point range is not served by the GPU path");
+    auto at = points_.find(q.field);
+    if (at == points_.end()) throw Error(RGPU_ERR_UNSUPPORTED, "no points are attached for field " + q.field + ": the range stays on the CPU path");
+    const FieldPoints& fp = at->second;
+    if (static_cast<int32_t>(q.lower.size()) != fp.bytes_per_dim)
+      throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "field " + q.field + " was indexed with another bytesPerDim than this query has");
+    const auto key = std::make_tuple(q.field, q.lower, q.upper);
+    auto have = range_filters_.find(key);
+    if (have != range_filters_.end()) return have->second;
+    rgpu_point_range r;
+    std::memset(&r, 0, sizeof r);
+    std::memcpy(r.lower, q.lower.data(), q.lower.size());
+    std::memcpy(r.upper, q.upper.data(), q.upper.size());
+    std::vector<rgpu_docset*> sets(leaves_.size(), nullptr);
+    try {
+      for (size_t li = 0; li < leaves_.size(); ++li) {
+        if (fp.per_leaf[li]) check(rgpu_docset_from_point_ranges(fp.per_leaf[li], &r, 1, path, &sets[li]));
+        else check(rgpu_docset_from_docs(leaves_[li].segment, nullptr, 0, &sets[li]));   // no such field in this leaf: the empty set
+      }
+    } catch (...) {
+      for (rgpu_docset* d : sets) rgpu_docset_free(d);
+      throw;
+    }
+    const CachedFilter f = keep(std::move(sets));
+    range_filters_[key] = f;
+    return f;
+  }
+  // "Q's clauses, +range / #range for every `required`, -range for every `must_not`": a range under MUST and one under FILTER both
+  // add + 0.0 to the sum, so both are filters; FilteredQuery::check_served applies the unchanged rules (Q brings a MUST or FILTER
+  // clause of its own, ...). The two differ in ONE place, BooleanQuery::build's default: "+range #a b" has min_should_match 0 (a MUST
+  // clause stands), "#range #a b" has 1. Q is built without the ranges, so build it with the min_should_match the whole query has —
+  // here that takes no care: beside required clauses the SHOULD side is ReqOptScorer's optional scorer, and a disjunction with
+  // min_should_match 0 and 1 matches the same docs (BooleanQuery::build above stores 0 whenever a MUST or FILTER clause stands).
+  FilteredQuery range_clauses(const Query& q, const std::vector<const PointRangeQuery*>& required, const std::vector<const PointRangeQuery*>& must_not = {}) {
+    std::vector<CachedFilter> f, x;
+    for (const PointRangeQuery* r : required) f.push_back(range_filter(*r));
+    for (const PointRangeQuery* r : must_not) x.push_back(range_filter(*r));
+    return FilteredQuery::clauses(q, std::move(f), std::move(x));
+  }
+
   // IndexSearcher::search(query, collector) for a TopDocsCollector
   void search(const Query& query, TopDocsCollector& collector) {
     try {
@@ -812,6 +958,8 @@ class GpuIndexSearcher {
   // FilteredQuery rows are grouped by their combination of doc sets (host/docset_plan.hpp: caller order kept inside a group) and searched
   // masked, one rgpu_search_batch_masked per group and leaf; every other row goes the way it went.
   std::vector<TopDocs> search_many(const std::vector<const Query*>& queries, size_t k) {
+    for (const Query* q : queries)
+      if (dynamic_cast<const PointRangeQuery*>(q)) throw Error(RGPU_ERR_UNSUPPORTED, "a lone point range is not served by the GPU path (the reference matches all of it)");
     for (const Query* q : queries)
       if (dynamic_cast<const FilteredQuery*>(q)) return search_filtered(queries, k);
     std::vector<size_t> phrase_rows, bool_rows, or_rows, plain_rows;
@@ -1344,6 +1492,12 @@ class GpuIndexSearcher {
   int32_t sim_table_ = -1;
   std::vector<rgpu_planner*> planners_;  // per leaf and naming scheme (2 * leaf + by-bytes), created on first use
   std::map<uint64_t, std::vector<rgpu_docset*>> filters_;  // CachedFilter::id -> one doc set per leaf
+  struct FieldPoints {
+    int32_t bytes_per_dim = 0;
+    std::vector<rgpu_points*> per_leaf;  // null: the leaf lacks the field
+  };
+  std::map<std::string, FieldPoints> points_;
+  std::map<std::tuple<std::string, std::vector<uint8_t>, std::vector<uint8_t>>, CachedFilter> range_filters_;  // the memo of range_filter
   std::map<std::pair<std::vector<uint64_t>, std::vector<uint64_t>>, std::vector<rgpu_docset*>> masks_;  // (filters, excludes) -> combined sets per leaf
   uint64_t next_filter_id_ = 0;
 };

@@ -35,6 +35,33 @@ struct DocsetJob {
   uint32_t row;    // index into the launch's row pointers (the set the bits go to)
 };
 
+constexpr uint32_t DOCSET_NO_WORD = 0xffffffffu;
+
+// The gathering step of docset_block_bits (below) as a variant of its own for callers that bring words and masks (k_points_scan) —
+// kept beside it, not under it, so that what k_docset_lists runs compiles to what it was; it sets bits only. Every lane holds a
+// first word wa with the bits ma and a last word wb with the bits mb — wb == wa (then mb == ma) when the lane touches one word —
+// the words ascending, not strictly, along (lane, first / last). A mask may be ZERO in any lane (a point outside the range keeps its
+// word, so the runs of a word stay contiguous); DOCSET_NO_WORD marks lanes that hold nothing and may only stand on a suffix of the lanes.
+__device__ __forceinline__ void docset_wave_masks(uint32_t* __restrict__ words, uint32_t wa, uint32_t ma, uint32_t wb, uint32_t mb, int lane) {
+  constexpr uint32_t NONE = DOCSET_NO_WORD;
+  // s = OR of ma over this lane and the lanes right behind it whose FIRST word is wa
+  uint32_t s = ma;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t ow = (uint32_t)__shfl_down((int)wa, off), os = (uint32_t)__shfl_down((int)s, off);
+    if (lane + off < 64 && ow == wa) s |= os;
+  }
+  const uint32_t prev_wa = (uint32_t)__shfl_up((int)wa, 1), prev_wb = (uint32_t)__shfl_up((int)wb, 1);
+  const uint32_t next_wa = (uint32_t)__shfl_down((int)wa, 1), next_s = (uint32_t)__shfl_down((int)s, 1);
+  // the first word: this lane starts its run unless the lane before touches the word (as its first or as its last word)
+  const bool head_a = wa != NONE && (lane == 0 || (prev_wa != wa && prev_wb != wa));
+  // the last word, when it is another one: its run starts here, and goes on with the next lanes' first words
+  const bool head_b = wb != wa && wb != NONE;
+  const uint32_t bits_b = mb | ((lane < 63 && next_wa == wb) ? next_s : 0u);
+  if (head_a && s != 0u) atomicOr(words + wa, s);
+  if (head_b && bits_b != 0u) atomicOr(words + wb, bits_b);
+}
+
 // The 128 postings of a block as the wavefront holds them — lane l: postings 2l and 2l + 1, doc ids ascending along that order — to
 // ONE atomic per distinct 32-bit word. A word's bits are gathered in registers first: every lane merges its two postings when they
 // share a word, a segmented suffix OR over the lanes (keyed on the lane's first word, five shuffles) collects a word's run, and the

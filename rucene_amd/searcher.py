@@ -253,11 +253,84 @@ class PhraseQuery:
             raise RgpuError(-2, "Must have as many terms as positions")
 
 
+class PointRangeQuery:
+    """search/query/point_range_query.rs: the docs that hold a point of `field` with lower <= value <= upper, both ends inclusive,
+    in unsigned byte order of the sortable bytes. ONE dimension: `lower_bytes` / `upper_bytes` are one encoded value each (4 or 8
+    bytes; IntPoint / LongPoint / FloatPoint / DoublePoint below build them); a query built with num_dims > 1 is
+    UnsupportedOperation (what it matches depends on the BKD cell layout: include/rucene_gpu.h). It does not score: ConstantScoreScorer(0.0) under
+    MUST and FILTER alike (PointRangeWeight::new :482 — nothing normalises the weight), so GpuIndexSearcher turns the clause into
+    a doc set (range_filter) and searches masked; under SHOULD, alone, or beside a phrase it is UnsupportedOperation."""
+
+    def __init__(self, field, lower_bytes, upper_bytes, num_dims=1):
+        self.field, self.lower, self.upper, self.num_dims = str(field), bytes(lower_bytes), bytes(upper_bytes), int(num_dims)
+        if self.num_dims < 1 or len(self.lower) % self.num_dims:   # PointRangeQuery::new :384-390
+            raise RgpuError(-2, "lowerPoint is not a fixed multiple of numDims")
+        if len(self.lower) != len(self.upper):   # :391-397
+            raise RgpuError(-2, "lowerPoint has length=%d but upperPoint has different length=%d" % (len(self.lower), len(self.upper)))
+        if len(self.lower) == 0:
+            raise RgpuError(-2, "a point range needs bounds")
+
+    def extract_terms(self):
+        return []
+
+    def __str__(self):
+        return "PointRangeQuery(field: %s, lower: %s, upper: %s)" % (self.field, self.lower.hex(), self.upper.hex())
+
+
+class _Point:
+    """One-dimensional point types: encode = encode_dimension (the sortable bytes), new_range_query / new_exact_query as in the
+    reference (point_range_query.rs:83-310)."""
+    BYTES = 0
+
+    @classmethod
+    def new_range_query(cls, field, lower, upper):
+        return PointRangeQuery(field, cls.encode(lower), cls.encode(upper))
+
+    @classmethod
+    def new_exact_query(cls, field, value):
+        return cls.new_range_query(field, value, value)
+
+
+class IntPoint(_Point):
+    BYTES = 4
+
+    @staticmethod
+    def encode(value):   # core/util/numeric.rs:190-197 int2sortable_bytes: the sign bit flipped, big-endian
+        return (((int(value) & 0xFFFFFFFF) ^ 0x80000000)).to_bytes(4, "big")
+
+
+class LongPoint(_Point):
+    BYTES = 8
+
+    @staticmethod
+    def encode(value):   # numeric.rs:208-218 long2sortable_bytes
+        return ((int(value) & 0xFFFFFFFFFFFFFFFF) ^ 0x8000000000000000).to_bytes(8, "big")
+
+
+class FloatPoint(_Point):
+    BYTES = 4
+
+    @staticmethod
+    def encode(value):   # numeric.rs:171-186 float2sortable_int (bits ^ ((bits >> 31) & 0x7fffffff), arithmetic shift), then int2sortable_bytes
+        bits = int(np.array([value], dtype=np.float32).view(np.int32)[0])
+        return IntPoint.encode(bits ^ ((bits >> 31) & 0x7FFFFFFF))
+
+
+class DoublePoint(_Point):
+    BYTES = 8
+
+    @staticmethod
+    def encode(value):   # numeric.rs:163-182 double2sortable_long, then long2sortable_bytes
+        bits = int(np.array([value], dtype=np.float64).view(np.int64)[0])
+        return LongPoint.encode(bits ^ ((bits >> 63) & 0x7FFFFFFFFFFFFFFF))
+
+
 class CachedFilter:
     """A filter that is not a term, as the query cache holds it: one doc set per leaf of a searcher, in HBM (rgpu_docset). What
     LRUQueryCache::do_cache leaves behind for a cached weight (search/cache/query_cache.rs:301-372) — made by
-    GpuIndexSearcher.cache_filter (the GPU collects a term / boolean query's matches, live docs not applied), filter_from_docs
-    (global doc ids, e.g. a PointRangeQuery's matches or an ACL) or filter_from_bits (FixedBitSet words per leaf). Goes under
+    GpuIndexSearcher.cache_filter (the GPU collects a term / boolean query's matches, live docs not applied), range_filter (a
+    PointRangeQuery over attached points, built on the GPU), filter_from_docs (global doc ids, e.g. an ACL) or filter_from_bits
+    (FixedBitSet words per leaf). Goes under
     `filters=` / `must_nots=` of BooleanQuery.build and into FilterQuery."""
 
     def __init__(self, searcher, sets):
@@ -306,7 +379,9 @@ class BooleanQuery:
             raise RgpuError(-2, "boolean query should at least contain one inner query!")
         if any(isinstance(q, CachedFilter) for q in list(musts) + list(shoulds)):
             raise RgpuError(-2, "a CachedFilter does not score: it goes under filters= or must_nots=")
-        if len(must_nots) == 0 and len(musts) + len(shoulds) + len(filters) == 1 and not (filters and isinstance(filters[0], CachedFilter)):
+        if any(isinstance(q, PointRangeQuery) for q in shoulds):
+            raise RgpuError(-5, "a point range under SHOULD is not served by the GPU path")
+        if len(must_nots) == 0 and len(musts) + len(shoulds) + len(filters) == 1 and not (filters and isinstance(filters[0], (CachedFilter, PointRangeQuery))):
             if filters:   # ConstantScoreQuery::with_boost(filter, 0.0) (boolean_query.rs:70-73): every match scores 0
                 if isinstance(filters[0], PhraseQuery):
                     return PhraseQuery(filters[0].terms, filters[0].positions, 0.0, filters[0].slop)
@@ -320,8 +395,10 @@ class BooleanQuery:
         # decided when it is searched — GpuIndexSearcher.flatten_nested / cpu_fallback)
         # (so does a PhraseQuery clause: GpuIndexSearcher.phrase_bool_parts says which trees over phrases the GPU path serves)
         # (a CachedFilter under FILTER / MUST_NOT is a doc-set clause: GpuIndexSearcher.search_batch peels it off and masks the search)
-        if any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery)) for q in list(musts) + list(shoulds)) or \
-                any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, CachedFilter)) for q in list(must_nots) + list(filters)):
+        # (a PointRangeQuery under MUST / FILTER / MUST_NOT likewise: GpuIndexSearcher.range_filter makes its doc set)
+        if any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, PointRangeQuery)) for q in list(musts)) or \
+                any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery)) for q in list(shoulds)) or \
+                any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, CachedFilter, PointRangeQuery)) for q in list(must_nots) + list(filters)):
             raise RgpuError(-5, "only term, phrase and boolean clauses are known to this mirror")
         return BooleanQuery(list(musts), list(shoulds), msm, list(must_nots), list(filters))
 
@@ -568,6 +645,8 @@ class GpuIndexSearcher:
     """IndexSearcher over GPU-resident leaves. `search(query, collector)` mirrors searcher.rs:487-525;
     `search_batch` is the batched form the hardware wants (one launch set per leaf for many queries)."""
 
+    range_filter_capacity = 256   # memoised range filters kept from one search_batch to the next (range_filter); set per searcher
+
     def __init__(self, leaves, ctx=None, similarity=None, next_limit=None, flatten_nested=False, cpu_fallback=None):
         """flatten_nested: fold one level of nested BooleanQuery clauses (BooleanQuery.flattened: same docs and counts, scores
         within 1e-5 of the reference's — off by default because it is not bit-exact). cpu_fallback(query, collector): what
@@ -602,6 +681,8 @@ class GpuIndexSearcher:
         self._planners = {}       # per leaf: the native batch planner
         self._stats_terms = None  # override_statistics: another leaf's term table / dictionary
         self._masks = {}          # (filter sets, exclude sets) key -> (the CachedFilters, one combined DocSet per leaf)
+        self._points = {}         # field -> (bytes per value, one _lib.Points per leaf or None)
+        self._range_filters = {}  # (field, lower, upper) -> CachedFilter, least recently used first
 
     def max_doc(self):
         return sum(leaf.max_doc for leaf in self.leaves)
@@ -631,6 +712,9 @@ class GpuIndexSearcher:
         clauses behind them: _boosting_fields)"""
         if isinstance(query, TermQuery):
             return OP_TERM, [query], [], []
+        if isinstance(query, PointRangeQuery) or (isinstance(query, BooleanQuery) and any(
+                isinstance(q, PointRangeQuery) for q in list(query.must_queries) + list(query.filter_queries) + list(query.must_not_queries))):
+            raise RgpuError(-5, "a point range clause is served as a doc set (search_batch peels it off): it packs to no clause")
         if isinstance(query, BoostingQuery):
             demoting = query.demoting_terms()
             if demoting is None:
@@ -1013,34 +1097,134 @@ class GpuIndexSearcher:
             raise RgpuError(-2, "a cached filter holds one bit set per leaf")
         return self._cached([leaf.segment.docset_from_words(w) for leaf, w in zip(self.leaves, per_leaf_words)])
 
-    def _peel(self, query):
+    def attach_points(self, field, per_leaf, bytes_per_dim=None):
+        """The one-dimensional points of `field`: per leaf a (docs, values) pair — leaf-local doc ids in any order, a doc may repeat,
+        and the sortable bytes of the values as a u8 array [n, bytes] (or n byte strings) — or None for a leaf without the field
+        (the reference has no scorer there: nothing matches under MUST / FILTER, nothing is excluded under MUST_NOT). open_directory
+        attaches nothing: this mirror reads no .dim file."""
+        if len(per_leaf) != len(self.leaves):
+            raise RgpuError(-2, "points are attached per leaf")
+        held, width = [], bytes_per_dim
+        for leaf, pair in zip(self.leaves, per_leaf):
+            if pair is None:
+                held.append(None)
+                continue
+            docs, values = pair
+            if isinstance(values, (list, tuple)):
+                values = np.frombuffer(b"".join(bytes(v) for v in values), np.uint8).reshape(len(values), -1) if len(values) else np.zeros((0, width or 4), np.uint8)
+            values = np.asarray(values, dtype=np.uint8)
+            w = values.shape[1] if values.ndim == 2 else width
+            if w is None or (width is not None and w != width):
+                raise RgpuError(-2, "the values of a point field have one width (pass [n, bytes] arrays, or bytes_per_dim)")
+            width = w
+            held.append(leaf.segment.attach_points(w, docs, values))
+        if width is None:
+            raise RgpuError(-2, "no leaf holds the field")
+        old = self._points.pop(field, None)
+        for key in [k for k in self._range_filters if k[0] == field]:
+            del self._range_filters[key]
+        self._points[field] = (int(width), held)
+        if old:
+            for pts in old[1]:
+                if pts is not None:
+                    pts.close()
+
+    def range_filter(self, query, path=0):
+        """PointRangeQuery -> CachedFilter, built on the GPU from the attached points (rgpu_docset_from_point_ranges), one set per
+        leaf; memoised per (field, lower, upper). A field never attached: UnsupportedOperation; bounds whose length is not the
+        field's: IllegalArgument (point_range_query.rs:510-522). The memo holds the `range_filter_capacity` most recently used
+        ranges (search_batch trims it before it peels a batch; drop_range_filters empties it): a range that moves with every query
+        would otherwise leave ceil(max_doc / 64) * 8 bytes per leaf in HBM per query. A CachedFilter the caller still holds stays
+        usable after it left the memo; its sets are freed with its last reference."""
+        return self._range_filters_for([query], path)[0]
+
+    def _check_ranges(self, queries):
+        """what can be wrong with a PointRangeQuery, before anything is built: dimensions, field, width"""
+        for q in queries:
+            if q.num_dims != 1:
+                raise RgpuError(-5, "a multi-dimensional point range is not served by the GPU path (its matches depend on the BKD cell layout)")
+            if q.field not in self._points:
+                raise RgpuError(-5, "no points are attached for field %r: the range stays on the CPU path" % q.field)
+            width = self._points[q.field][0]
+            if len(q.lower) != width:
+                raise RgpuError(-2, "field=%r was indexed with bytesPerDim=%d but this query has bytesPerDim=%d" % (q.field, width, len(q.lower)))
+
+    def _range_filters_for(self, queries, path=0):
+        """the memoised CachedFilters of `queries` (PointRangeQuery); the missing ones of a field are built in ONE call per leaf"""
+        self._check_ranges(queries)
+        todo = {}
+        for q in queries:
+            key = (q.field, q.lower, q.upper)
+            if key in self._range_filters:
+                self._range_filters[key] = self._range_filters.pop(key)   # most recently used last
+            else:
+                todo.setdefault(q.field, {})[key] = None
+        for field, keys in todo.items():
+            keys = list(keys)
+            width, held = self._points[field]
+            bounds = _lib.point_ranges([(k[1], k[2]) for k in keys], width)
+            per_leaf = []
+            for leaf, pts in zip(self.leaves, held):
+                if pts is None:   # no such field in this leaf: the empty set
+                    per_leaf.append([leaf.segment.docset_from_docs(np.zeros(0, np.int32)) for _ in keys])
+                else:
+                    per_leaf.append(pts.range_docsets(bounds, path))
+            for j, key in enumerate(keys):
+                self._range_filters[key] = self._cached([sets[j] for sets in per_leaf])
+        return [self._range_filters[(q.field, q.lower, q.upper)] for q in queries]
+
+    def drop_range_filters(self, keep=0):
+        """Forget all but the `keep` most recently used memoised range filters, and every memoised combination (_mask) that names a
+        forgotten one: their doc sets are freed once nobody else holds the CachedFilter."""
+        while len(self._range_filters) > max(0, int(keep)):
+            gone = self._range_filters.pop(next(iter(self._range_filters)))
+            for key in [k for k in self._masks if id(gone) in k[0] or id(gone) in k[1]]:
+                del self._masks[key]
+
+    def _peel(self, query, build=True):
         """query -> (the query without its doc-set clauses, (FILTER CachedFilters, MUST_NOT CachedFilters)). The rest, searched on
         live docs AND filters AND NOT excludes, collects the reference's docs, counts and f32 scores when (1) it contributes a MUST
         or FILTER clause of its own — "b c #F" is ReqOptScorer(F, b | c) in the reference and matches ALL of F, a lone #F likewise —
         and (2) for -X, min_should_match <= 1 (boolean_query.rs:235-251 reuses it for the MUST_NOT union). FilterQuery(Q, F) asks
         only that Q has a scorer of its own. Phrases are not served under a mask (a sloppy phrase's next_limit counts deleted docs,
-        not docs outside a filter; the phrase entry points have no masked form). Anything else: UnsupportedOperation."""
+        not docs outside a filter; the phrase entry points have no masked form). Anything else: UnsupportedOperation.
+        A PointRangeQuery under MUST / FILTER / MUST_NOT is checked first (dimensions, field, width), the rules above are applied, and
+        only then is its doc set built; build=False stops short of that (the sets are then the queries themselves) — search_batch
+        runs it over the whole batch first, so a refused row launches nothing. min_should_match stays the query's own: "+range #a b"
+        has 0 (it had a MUST clause), where build() would give the rest "#a b" 1."""
         if isinstance(query, FilterQuery):
-            inner, (f, x) = self._peel(query.query)
+            inner, (f, x) = self._peel(query.query, build)
             if isinstance(inner, PhraseQuery) or (isinstance(inner, BooleanQuery) and inner.has_phrases()):
                 raise RgpuError(-5, "a filtered phrase is not served by the GPU path")
             return inner, (f + list(query.filters), x)
+        if isinstance(query, PointRangeQuery):
+            raise RgpuError(-5, "a lone point range is not served by the GPU path (the reference matches all of it)")
         if not isinstance(query, BooleanQuery):
             return query, ([], [])
-        f = [q for q in query.filter_queries if isinstance(q, CachedFilter)]
-        x = [q for q in query.must_not_queries if isinstance(q, CachedFilter)]
+        sets = (CachedFilter, PointRangeQuery)
+        f = [q for q in list(query.must_queries) + list(query.filter_queries) if isinstance(q, sets)]   # a range under MUST adds + 0.0 as under FILTER
+        x = [q for q in query.must_not_queries if isinstance(q, sets)]
         if not f and not x:
             return query, ([], [])
-        filters = [q for q in query.filter_queries if not isinstance(q, CachedFilter)]
-        must_nots = [q for q in query.must_not_queries if not isinstance(q, CachedFilter)]
-        if not (query.must_queries or filters):
+        self._check_ranges([q for q in f + x if isinstance(q, PointRangeQuery)])
+        musts = [q for q in query.must_queries if not isinstance(q, sets)]
+        filters = [q for q in query.filter_queries if not isinstance(q, sets)]
+        must_nots = [q for q in query.must_not_queries if not isinstance(q, sets)]
+        if not (musts or filters):
             raise RgpuError(-5, "a doc set as the only required clause is not served by the GPU path (the reference matches all of it)")
         if x and query.min_should_match > 1:
             raise RgpuError(-5, "a MUST_NOT doc set beside min_should_match >= 2 is not served by the GPU path")
-        rest = BooleanQuery.build(list(query.must_queries), list(query.should_queries), filters=filters, must_nots=must_nots,
+        rest = BooleanQuery.build(musts, list(query.should_queries), filters=filters, must_nots=must_nots,
                                   min_should_match=query.min_should_match)
+        if isinstance(rest, BooleanQuery) and rest.min_should_match != query.min_should_match:
+            # (the peeled clauses were the only MUST ones: build() has derived the default of a query without MUST clauses)
+            rest = BooleanQuery(musts, list(query.should_queries), query.min_should_match, must_nots, filters)
         if isinstance(rest, PhraseQuery) or (isinstance(rest, BooleanQuery) and rest.has_phrases()):
             raise RgpuError(-5, "a filtered phrase is not served by the GPU path")
+        if build:
+            made = iter(self._range_filters_for([q for q in f + x if isinstance(q, PointRangeQuery)]))
+            f = [next(made) if isinstance(q, PointRangeQuery) else q for q in f]
+            x = [next(made) if isinstance(q, PointRangeQuery) else q for q in x]
         return rest, (f, x)
 
     def _mask(self, filters, excludes):
@@ -1066,7 +1250,11 @@ class GpuIndexSearcher:
         SHOULD ones (rgpu_search_phrase_or_batch): one call per kind and leaf, rows keep their order. Rows with doc-set clauses
         (CachedFilter under FILTER / MUST_NOT, FilterQuery) are grouped by their combination of sets and searched masked
         (rgpu_search_batch_masked), one call per group and leaf."""
-        peeled = [self._peel(q) for q in queries]   # (refused before any leaf is touched)
+        for q in queries:   # refused before any leaf is touched and before any range's set is built
+            self._peel(q, build=False)
+        if getattr(self, "_range_filters", None):   # (a batch on a searcher that never built a range filter goes the way it went)
+            self.drop_range_filters(keep=self.range_filter_capacity)
+        peeled = [self._peel(q) for q in queries]
         if not any(f or x for _, (f, x) in peeled):
             per_leaf = self._rows_per_leaf(queries, k, None)
         else:

@@ -20,10 +20,11 @@ use std::collections::HashMap;
 use std::ops::Deref;
 use std::sync::Mutex;
 
+use core::codec::points::{IntersectVisitor, PointValues, Relation};
 use core::codec::postings::blocktree::BlockTermState;
 use core::codec::{Codec, TermIterator, Terms};
 use core::doc::Term;
-use core::index::reader::{IndexReader, LeafReaderContext};
+use core::index::reader::{IndexReader, LeafReader, LeafReaderContext};
 use core::search::collector::{SearchCollector, TopDocsCollector};
 use core::search::query::{BooleanQuery, PhraseQuery, Query, TermQuery};
 use core::search::searcher::{DefaultIndexSearcher, IndexSearcher, SearchPlanBuilder};
@@ -73,6 +74,41 @@ pub struct GpuCachedFilter {
 impl Drop for GpuCachedFilter {
     fn drop(&mut self) {
         for s in self.sets.drain(..) { unsafe { rgpu_docset_free(s) }; } // waits for the masked searches in flight that read the set
+    }
+}
+
+/// What PointValues::intersect shows a visitor whose compare() always answers CellCrossesQuery: every (doc, packed value) of the field,
+/// leaf by BKD leaf — the flat arrays rgpu_points_attach takes. One enumeration per leaf and field, at attach time.
+struct AllPointsVisitor {
+    docs: Vec<i32>,
+    values: Vec<u8>,
+}
+
+impl IntersectVisitor for AllPointsVisitor {
+    fn visit(&mut self, _doc_id: DocId) -> Result<()> {
+        bail!(ErrorKind::IllegalState("visit() without a value: compare() never answers CellInsideQuery".into()))
+    }
+    fn visit_by_packed_value(&mut self, doc_id: DocId, packed_value: &[u8]) -> Result<()> {
+        self.docs.push(doc_id);
+        self.values.extend_from_slice(packed_value);
+        Ok(())
+    }
+    fn compare(&self, _min_packed_value: &[u8], _max_packed_value: &[u8]) -> Relation {
+        Relation::CellCrossesQuery
+    }
+}
+
+/// The one-dimensional points of one field, resident in HBM: one rgpu_points per leaf (null: the leaf has no such field), made by
+/// `attach_points`, read by `try_range_filter`. Freed before the searcher that made it (points go before their segments).
+pub struct GpuPoints {
+    field: String,
+    bytes_per_dim: usize,
+    per_leaf: Vec<*mut RgpuPoints>,
+}
+
+impl Drop for GpuPoints {
+    fn drop(&mut self) {
+        for p in self.per_leaf.drain(..) { if !p.is_null() { unsafe { rgpu_points_free(p) }; } }
     }
 }
 
@@ -645,6 +681,58 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             let q = RgpuQuery { op: flat.op, n_terms: flat.positive.len() as i32, first_term: 0, n_must_not: flat.must_not.len() as i32 };
             let mut set: *mut RgpuDocset = std::ptr::null_mut();
             check(unsafe { rgpu_docset_collect_batch(self.leaves[leaf.ord].seg, &q, 1, terms.as_ptr(), n as i32, &mut set) }, self.ctx)?;
+            made.sets.push(set);
+        }
+        Ok(Some(made))
+    }
+
+    /// Upload the points of `field` for every leaf: PointValues::intersect with a visitor that takes every cell
+    /// (AllPointsVisitor), then rgpu_points_attach. Ok(None): the field has more than one dimension in some leaf, or values that are
+    /// not 4 or 8 bytes wide — such ranges stay on the CPU path (what a multi-dimensional PointRangeQuery matches depends on the
+    /// BKD cell layout: PointRangeIntersectVisitor::compare, point_range_query.rs:642-664, slices lower_point without an end).
+    pub fn attach_points(&self, field: &str) -> Result<Option<GpuPoints>> {
+        let mut made = GpuPoints { field: field.to_string(), bytes_per_dim: 0, per_leaf: Vec::with_capacity(self.leaves.len()) };
+        for leaf in self.cpu.reader().leaves() {
+            let values = match leaf.reader.point_values() { Some(v) => v, None => { made.per_leaf.push(std::ptr::null_mut()); continue; } };
+            if leaf.reader.field_info(field).map_or(true, |fi| fi.point_dimension_count == 0) { made.per_leaf.push(std::ptr::null_mut()); continue; }
+            let dims = values.num_dimensions(field)?;
+            let width = values.bytes_per_dimension(field)?;
+            if dims != 1 || !(width == 4 || width == 8) || (made.bytes_per_dim != 0 && made.bytes_per_dim != width) { return Ok(None); }
+            made.bytes_per_dim = width;
+            let mut all = AllPointsVisitor { docs: Vec::new(), values: Vec::new() };
+            values.intersect(field, &mut all)?;
+            let mut points: *mut RgpuPoints = std::ptr::null_mut();
+            check(unsafe { rgpu_points_attach(self.leaves[leaf.ord].seg, width as i32, all.docs.as_ptr(), all.values.as_ptr(), all.docs.len() as i64, &mut points) }, self.ctx)?;
+            made.per_leaf.push(points);
+        }
+        if made.bytes_per_dim == 0 { return Ok(None); } // no leaf holds the field
+        Ok(Some(made))
+    }
+
+    /// PointRangeQuery(points.field, lower, upper) as a cached filter: per leaf the docs holding a point inside the closed range,
+    /// built on the GPU (rgpu_docset_from_point_ranges, the library chooses scatter or scan), live docs not applied — what
+    /// create_scorer (point_range_query.rs:503-561) collects. A leaf without the field gives the empty set, as the reference's missing
+    /// scorer does. The result goes to `try_filtered`: a range under MUST or FILTER among `filters` (both add + 0.0), under MUST_NOT
+    /// among `excludes`. `try_filtered`'s `query` is the BooleanQuery WITHOUT its range clauses: build it with the min_should_match
+    /// the whole query has ("+range #a b" has 0 where BooleanQuery::build gives "#a b" 1; beside required clauses both match the
+    /// same docs — ReqOptScorer's optional side — but a caller that forwards min_should_match elsewhere must keep the original).
+    /// A serving layer memoises the filter per (field, lower, upper) with a bound of its own: every distinct range is
+    /// ceil(max_doc / 64) * 8 bytes per leaf in HBM until the GpuCachedFilter is dropped. Ok(None): bounds of another width than one value —
+    /// the CPU searcher reports the reference's IllegalArgument (:510-522) itself.
+    pub fn try_range_filter(&self, points: &GpuPoints, lower: &[u8], upper: &[u8]) -> Result<Option<GpuCachedFilter>> {
+        if points.per_leaf.len() != self.leaves.len() { bail!(ErrorKind::IllegalArgument("points of another searcher".into())); }
+        if lower.len() != points.bytes_per_dim || upper.len() != points.bytes_per_dim { return Ok(None); }
+        let mut range = RgpuPointRange { lower: [0u8; 8], upper: [0u8; 8] };
+        range.lower[..lower.len()].copy_from_slice(lower);
+        range.upper[..upper.len()].copy_from_slice(upper);
+        let mut made = GpuCachedFilter { sets: Vec::with_capacity(self.leaves.len()) };
+        for (leaf, &pts) in self.leaves.iter().zip(points.per_leaf.iter()) {
+            let mut set: *mut RgpuDocset = std::ptr::null_mut();
+            if pts.is_null() {
+                check(unsafe { rgpu_docset_from_docs(leaf.seg, std::ptr::null(), 0, &mut set) }, self.ctx)?;
+            } else {
+                check(unsafe { rgpu_docset_from_point_ranges(pts, &range, 1, 0, &mut set) }, self.ctx)?;
+            }
             made.sets.push(set);
         }
         Ok(Some(made))
