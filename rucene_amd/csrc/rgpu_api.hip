@@ -1851,6 +1851,46 @@ static int32_t ensure_bitmaps_locked(rgpu_segment* seg, const rgpu_term_state* c
   }
   return RGPU_OK;
 }
+// A clause's doc bitmap as k_search_and reads it, or the null one (words == null): none built, built and found unusable, or built
+// for another term state at the same file pointer.
+constexpr TermBitmap NO_BITMAP{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+static TermBitmap bitmap_of(rgpu_segment* seg, const DevTerm& t) {
+  const BitmapInfo* bm = seg->bitmaps.find((int64_t)t.start_fp);
+  if (!bm || !bm->usable || bm->df != t.df) return NO_BITMAP;
+  return TermBitmap{bm->words, bm->ranks, bm->freqs, bm->ovf, bm->nib, bm->memb, bm->n_ovf, 0};
+}
+// The emitting conjunctions (phrase candidates): builds the bitmaps their dense clauses still lack. `sts` / `sim_tables`: every
+// clause of every conjunction, the caller only enumerates them. -> the doc_freq from which a clause is answered from its bitmap,
+// INT64_MAX when conjunctions use none (clause_bitmap_table's min_df).
+static int32_t ensure_and_bitmaps_locked(rgpu_segment* seg, const std::vector<const rgpu_term_state*>& sts, const std::vector<int32_t>& sim_tables, int64_t* min_df) {
+  const rgpu_ctx* c = seg->ctx;
+  *min_df = (c->cfg.and_bitmaps >= 0 && c->n_sim_tables > 0) ? bitmap_min_df_and(seg) : INT64_MAX;
+  if (*min_df == INT64_MAX) return RGPU_OK;
+  std::vector<const rgpu_term_state*> dense;
+  std::vector<int32_t> dense_sim;
+  for (size_t i = 0; i < sts.size(); ++i)
+    if (sts[i]->doc_freq >= *min_df && !seg->bitmaps.find(sts[i]->doc_start_fp)) { dense.push_back(sts[i]); dense_sim.push_back(sim_tables[i]); }
+  if (dense.empty()) return RGPU_OK;
+  return ensure_bitmaps_locked(seg, dense.data(), dense_sim.data(), dense.size());
+}
+// ... and the table k_search_and takes, parallel to `terms`: the bitmaps of clauses 1 .. n_terms - 1 of every query (the lead is
+// walked). Empty when no clause has one.
+static std::vector<TermBitmap> clause_bitmap_table(rgpu_segment* seg, const std::vector<DevQuery>& queries, const std::vector<DevTerm>& terms, int64_t min_df) {
+  std::vector<TermBitmap> table;
+  if (min_df == INT64_MAX || seg->bitmaps.size() == 0) return table;
+  bool any = false;
+  table.assign(terms.size(), NO_BITMAP);
+  for (const DevQuery& q : queries) {
+    for (int i = 1; i < q.n_terms; ++i) {
+      const DevTerm& t = terms[(size_t)(q.first_term + i)];
+      if (t.df < min_df) continue;
+      table[(size_t)(q.first_term + i)] = bitmap_of(seg, t);
+      any = any || table[(size_t)(q.first_term + i)].words != nullptr;
+    }
+  }
+  if (!any) table.clear();
+  return table;
+}
 
 // Membership bits for conjunction clauses too sparse for a full bitmap (ctx mutex held; ends synchronised): see k_bitmap_memb.
 // Round 6 measured where k_search_and's cycles go on the 1024 x 3-term batch (-DRGPU_AND_TIME): the 6 % of the lead blocks whose
@@ -3305,9 +3345,9 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
             }
             continue;
           }
-          const BitmapInfo* bm = seg->bitmaps.find((int64_t)t.start_fp);
-          if (!bm || !bm->usable || bm->df != t.df) continue;
-          clause_bitmaps[(size_t)(q0.first_term + i)] = TermBitmap{bm->words, bm->ranks, bm->freqs, bm->ovf, bm->nib, bm->memb, bm->n_ovf, 0};
+          const TermBitmap bm = bitmap_of(seg, t);
+          if (!bm.words) continue;
+          clause_bitmaps[(size_t)(q0.first_term + i)] = bm;
           any = true;
         }
       }
@@ -3467,6 +3507,33 @@ extern "C" int32_t rgpu_search_batch_device(rgpu_segment* seg, const rgpu_query*
   return rc;
 }
 
+// ---- the device-side rows of a blocking call: c->host_api_hits ([n_queries][k]) and c->host_api_totals, grow-only ---------------
+// Every row's defaults - total 0 and "no hit" in every column: what a query that launches nothing, or a leaf that holds none of
+// its clauses, returns. `pass`: one pass of a k > RGPU_PASS_K call, which fills `width` columns from `col0` on of rows `stride`
+// wide; null: the whole rows of k columns.
+struct RowColumns { int32_t width, stride, col0; };
+static int32_t api_rows_default(rgpu_ctx* c, hipStream_t stream, int32_t n_queries, int32_t k, const RowColumns* pass = nullptr) {
+  const size_t nq = (size_t)n_queries;
+  const RowColumns cols = pass ? *pass : RowColumns{k, k, 0};
+  HIP_TRY(c->host_api_hits.reserve(nq * (size_t)k, 0, stream));
+  HIP_TRY(c->host_api_totals.reserve(nq, 0, stream));
+  HIP_TRY(hipMemsetAsync(c->host_api_totals.p, 0, nq * 8, stream));
+  RGPU_LAUNCH(k_init_hits, dim3(wg_count((nq * (size_t)cols.width + 255) / 256)), dim3(256), 0, stream, c->host_api_hits.p, (int64_t)n_queries, (int)cols.width,
+              (int)cols.stride, (int)cols.col0);
+  return RGPU_OK;
+}
+// ... and the rows out to the caller's arrays; ends synchronised. `verdict`: also fetch the phrase match stage's verdict
+// (c->d_err[0]) in the same round - one synchronise less for a call that is content to have written its rows when it refuses
+// (rgpu_search_phrase_batch; include/rucene_gpu.h says per call what a refusal leaves).
+static int32_t api_rows_read_back(rgpu_ctx* c, hipStream_t stream, int32_t n_queries, int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out, int* verdict = nullptr) {
+  hipError_t e0 = verdict ? hipMemcpyAsync(verdict, c->d_err, sizeof(int), hipMemcpyDeviceToHost, stream) : hipSuccess;
+  hipError_t e1 = hipMemcpyAsync(hits_out, c->host_api_hits.p, (size_t)n_queries * (size_t)k * sizeof(HitOut), hipMemcpyDeviceToHost, stream);
+  hipError_t e2 = hipMemcpyAsync(total_hits_out, c->host_api_totals.p, (size_t)n_queries * 8, hipMemcpyDeviceToHost, stream);
+  hipError_t e3 = hipStreamSynchronize(stream);
+  if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(RGPU_ERR_RUNTIME, "device to host copy failed");
+  return RGPU_OK;
+}
+
 // rgpu_search_batch behind its argument checks (ctx mutex held, device set): shared with rgpu_search_batch_masked
 static int32_t search_batch_host_locked(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
                                         int32_t n_terms_total, int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
@@ -3493,16 +3560,8 @@ static int32_t search_batch_host_locked(rgpu_segment* seg, const rgpu_query* que
   }
   HIP_TRY(c->host_api_hits.reserve((size_t)n_queries * (size_t)k, 0, c->stream));
   HIP_TRY(c->host_api_totals.reserve((size_t)n_queries, 0, c->stream));
-  HitOut* d_hits = c->host_api_hits.p;
-  int64_t* d_tot = c->host_api_totals.p;
-  int32_t rc = search_impl(seg, queries, n_queries, terms, n_terms_total, k, d_hits, d_tot, c->stream);
-  if (rc == RGPU_OK) {
-    hipError_t e1 = hipMemcpyAsync(hits_out, d_hits, (size_t)n_queries * (size_t)k * sizeof(HitOut), hipMemcpyDeviceToHost, c->stream);
-    hipError_t e2 = hipMemcpyAsync(total_hits_out, d_tot, (size_t)n_queries * 8, hipMemcpyDeviceToHost, c->stream);
-    hipError_t e3 = hipStreamSynchronize(c->stream);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) rc = fail(RGPU_ERR_RUNTIME, "device to host copy failed");
-  }
-  return rc;
+  RGPU_TRY(search_impl(seg, queries, n_queries, terms, n_terms_total, k, c->host_api_hits.p, c->host_api_totals.p, c->stream));
+  return api_rows_read_back(c, c->stream, n_queries, k, hits_out, total_hits_out);
 }
 
 extern "C" int32_t rgpu_search_batch(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
@@ -3514,6 +3573,99 @@ extern "C" int32_t rgpu_search_batch(rgpu_segment* seg, const rgpu_query* querie
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(hipSetDevice(c->device));
   return search_batch_host_locked(seg, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out);
+}
+
+static int64_t phrase_redo_cap(int64_t slots) {
+  // (developer knob: RGPU_PHRASE_REDO_CAP=<n> shrinks the list of left-over candidates, so that a test reaches the pass that runs without it)
+  int64_t redo_cap = PHRASE_REDO_LIST_CAP;
+  if (const char* e = std::getenv("RGPU_PHRASE_REDO_CAP")) redo_cap = std::max<int64_t>(0, std::min<int64_t>(redo_cap, std::atoll(e)));
+  return std::min<int64_t>(slots, redo_cap);
+}
+// ---- the set-up of phrase_match_stage (below, with the exact phrases), in front of the launch that fills the slots - and_emit_stage
+// runs it among its own memsets, a rescoring by itself - and whether or not the stage will have a slot to look at:
+// the callers read d_err afterwards.
+// `zero_keys`: zero c->phrase_keys. The match kernels write a key (or 0) to every slot below a query's count and to none above it:
+// a 64-candidate group past a query's count is never written. rgpu_rescore_phrase_batch needs the zeroes: k_rescore_phrase_combine
+// reads a row's slots by position, a 64-candidate kernel leaves the slots behind a row's window unwritten, and a batch of
+// absent-term rows launches no match kernel at all. rgpu_search_phrase_bool_batch and _phrase_or_batch ask for them too:
+// k_phrase_bool_score and k_phrase_run_place walk the slots by 64-slot group (both also look at the count; the zeroes are kept as
+// the second line they have been). rgpu_search_phrase_batch does without the memset: its collectors read emit_count[q] slots of
+// query q and nothing behind them.
+static int32_t phrase_match_setup(rgpu_ctx* c, hipStream_t stream, int64_t slots, bool zero_keys, int64_t* redo_cap) {
+  HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
+  HIP_TRY(c->phrase_keys.reserve((size_t)slots + 64, 0, stream));
+  *redo_cap = phrase_redo_cap(slots);
+  HIP_TRY(c->phrase_redo.reserve((size_t)*redo_cap + 64, 0, stream));
+  if (zero_keys) HIP_TRY(hipMemsetAsync(c->phrase_keys.p, 0, (size_t)slots * 8, stream));
+  HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));  // [0]: error code, [2]: slots on the redo list, [3]: "a candidate needs the wide lists"
+  return RGPU_OK;
+}
+
+// ---- the candidate stage: k_search_and in emit mode ------------------------------------------------------------------------------
+// A conjunction that collects nothing: the docs that hold every required clause of (virtual) query q (and none of its MUST_NOT
+// clauses, DevQuery::pad) go to c->phrase_docs from slot emit_prefix[q] on, their number to c->phrase_count[q]. What reads the
+// slots afterwards is the caller's business: phrase_match_stage (rgpu_search_phrase_batch, _phrase_bool_batch, _phrase_or_batch)
+// or k_docset_from_emitted (rgpu_docset_collect_batch).
+// A query's share of the launch, from the conjunction's lead (its first, rarest, clause): work items of `blocks_per_item` lead
+// blocks ...
+static inline int64_t lead_items(const DevTerm& lead, int blocks_per_item) { return lead.nblocks == 0 ? 1 : (lead.nblocks + blocks_per_item - 1) / blocks_per_item; }
+// ... candidate slots: the lead's doc_freq bounds the matches; whole groups of 64 (the 64 slots of a k_phrase_match_lanes wavefront
+// belong to one query) ...
+static inline int64_t lead_slots(const DevTerm& lead) { return rgpu_host::pb_round_up_64((int64_t)lead.df); }
+// ... and items of the chunked collector (k_phrase_collect_items)
+static inline int64_t lead_collect_chunks(const DevTerm& lead) { return ((int64_t)lead.df + PHRASE_COLLECT_CHUNK - 1) / PHRASE_COLLECT_CHUNK; }
+struct AndEmitStage {
+  const char* name;  // of the launch in the kernel statistics
+  const DevQuery* d_q;
+  const DevTerm* d_t;
+  const int64_t* d_ip;     // items in front of each query's
+  const int64_t* d_ep;     // slots in front of each query's
+  const TermBitmap* d_bm;  // clause_bitmap_table, or null
+  int32_t n_queries;       // the conjunctions (virtual queries where a query runs several)
+  // entries of c->phrase_count to reserve and zero: n_queries, or more where later stages count slots of their own behind the
+  // conjunctions' (rgpu_search_phrase_bool_batch: one plane per phrase, k_phrase_bool_fanout fills planes 1..)
+  size_t n_counts;
+  int64_t items, slots;
+  int blocks_per_item;
+  int k_emit;    // width of the (empty) top-k lists the kernel keeps all the same: the narrowest kind the caller's k allows
+  bool any_not;  // some query has MUST_NOT clauses: the HAS_NOT instantiation
+  // least sizes of c->S->d_partial_keys / d_partial_counts: the kernel's own lists need items * k_emit and items; the chunked phrase
+  // collector reuses both buffers behind it and needs them larger (0: no such need)
+  size_t partial_keys, partial_counts;
+  // phrase_match_stage comes behind (the phrase callers): the stage runs phrase_match_setup, zeroing the keys or not, between its
+  // memset of the counts and those of the thresholds, and hands the set-up's *redo_cap on. Every memset of the call then stands in
+  // front of the conjunction, the large one (the keys) second as it always has: with the set-up called by the callers in front of
+  // this stage - the same memsets, the keys first - rgpu_search_phrase_bool_batch took 0.05 - 0.07 ms of 2.15 longer per call, none
+  // of it inside a kernel (the phrase-bool launch sequence).
+  int64_t* redo_cap = nullptr;
+  bool zero_keys = false;
+};
+static int32_t and_emit_stage(rgpu_segment* seg, hipStream_t stream, const AndEmitStage& a) {
+  rgpu_ctx* c = seg->ctx;
+  const size_t nq = (size_t)a.n_queries;
+  HIP_TRY(c->phrase_docs.reserve((size_t)a.slots + 64, 0, stream));  // (phrase_match_setup reserves it too: a doc-set call runs no set-up, a rescoring not this stage)
+  HIP_TRY(c->phrase_count.reserve(a.n_counts, 0, stream));
+  HIP_TRY(c->S->d_partial_keys.reserve(std::max((size_t)a.items * (size_t)a.k_emit, a.partial_keys), 0, stream));
+  HIP_TRY(c->S->d_partial_counts.reserve(std::max((size_t)a.items, a.partial_counts), 0, stream));
+  HIP_TRY(c->S->d_tau.reserve(nq, 0, stream));  // (thresholds and counted words: per conjunction)
+  HIP_TRY(c->S->d_touched.reserve(nq * 2, 0, stream));
+  HIP_TRY(hipMemsetAsync(c->phrase_count.p, 0, a.n_counts * 8, stream));
+  if (a.redo_cap) RGPU_TRY(phrase_match_setup(c, stream, a.slots, a.zero_keys, a.redo_cap));
+  HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, nq * 8, stream));
+  HIP_TRY(hipMemsetAsync(c->S->d_touched.p, 0, nq * 16, stream));
+  TimedLaunch tl(c, stream, a.name, 0);
+  const SegView sv = seg_view(seg);
+  const int xcd_chunk = and_xcd_chunk(seg);
+  const unsigned grid = wg_count(and_grid((a.items + AND_WG_WAVES - 1) / AND_WG_WAVES, xcd_chunk));
+  auto go = [&](auto kern) {
+    RGPU_LAUNCH(kern, dim3(grid), dim3(AND_WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_ip, (int)a.n_queries, a.items, a.blocks_per_item, a.k_emit,
+                c->S->d_partial_keys.p, c->S->d_partial_counts.p, c->S->d_tau.p, c->S->d_touched.p, a.d_ep, c->phrase_count.p, (void*)c->phrase_docs.p,
+                (const unsigned long long*)nullptr, (const int32_t*)nullptr, a.d_bm, xcd_chunk);
+  };
+  const bool legacy = seg->version < 1;
+  if (a.any_not) { if (legacy) go(k_search_and<true, false, true, false>); else go(k_search_and<false, false, true, false>); }
+  else { if (legacy) go(k_search_and<true, false, false, false>); else go(k_search_and<false, false, false, false>); }
+  return RGPU_OK;
 }
 
 // ---- doc sets: cached filters as FILTER / MUST_NOT masks (include/rucene_gpu.h rgpu_docset_*; the plan: host/docset_plan.hpp; the
@@ -4013,8 +4165,8 @@ extern "C" int32_t rgpu_docset_collect_batch(rgpu_segment* seg, const rgpu_query
       for (const rgpu_term_state* st : P.negative) { dt.emplace_back(); RGPU_TRY(make_dev_term(seg, *st, 0.0f, sim, &dt.back())); }
       any_not = any_not || !P.negative.empty();
       const DevTerm& lead = dt[(size_t)dq[q].first_term];
-      items += lead.nblocks == 0 ? 1 : (lead.nblocks + blocks_per_item - 1) / blocks_per_item;
-      slots += ((int64_t)lead.df + 63) & ~(int64_t)63;  // the lead's doc_freq bounds the matches
+      items += lead_items(lead, blocks_per_item);
+      slots += lead_slots(lead);
     }
     item_prefix[nq] = items;
     emit_prefix[nq] = slots;
@@ -4032,29 +4184,9 @@ extern "C" int32_t rgpu_docset_collect_batch(rgpu_segment* seg, const rgpu_query
     sg.put(r_ep, emit_prefix);
     sg.put(r_rows, rows);
     RGPU_TRY(sg.upload(stream));
-    HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
-    HIP_TRY(c->phrase_count.reserve(nq, 0, stream));
-    HIP_TRY(hipMemsetAsync(c->phrase_count.p, 0, nq * 8, stream));
-    const int k_emit = 1;  // nothing is collected: the (empty) top-k lists are the narrowest kind
-    HIP_TRY(c->S->d_partial_keys.reserve((size_t)items * (size_t)k_emit, 0, stream));
-    HIP_TRY(c->S->d_partial_counts.reserve((size_t)items, 0, stream));
-    HIP_TRY(c->S->d_tau.reserve(nq, 0, stream));
-    HIP_TRY(c->S->d_touched.reserve(nq * 2, 0, stream));
-    HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, nq * 8, stream));
-    HIP_TRY(hipMemsetAsync(c->S->d_touched.p, 0, nq * 16, stream));
-    {
-      TimedLaunch tl(c, stream, "k_search_and(doc set candidates)", 0);
-      const int xcd_chunk = and_xcd_chunk(seg);
-      const unsigned grid = wg_count(and_grid((items + AND_WG_WAVES - 1) / AND_WG_WAVES, xcd_chunk));
-      auto go = [&](auto kern) {
-        RGPU_LAUNCH(kern, dim3(grid), dim3(AND_WG_THREADS), 0, stream, sv, (const DevQuery*)sg.dev(r_q), (const DevTerm*)sg.dev(r_t), (const int64_t*)sg.dev(r_ip),
-                    (int)n_queries, items, blocks_per_item, k_emit, c->S->d_partial_keys.p, c->S->d_partial_counts.p, c->S->d_tau.p, c->S->d_touched.p,
-                    (const int64_t*)sg.dev(r_ep), c->phrase_count.p, (void*)c->phrase_docs.p, (const unsigned long long*)nullptr, (const int32_t*)nullptr,
-                    (const TermBitmap*)nullptr, xcd_chunk);
-      };
-      if (any_not) { if (legacy) go(k_search_and<true, false, true, false>); else go(k_search_and<false, false, true, false>); }
-      else { if (legacy) go(k_search_and<true, false, false, false>); else go(k_search_and<false, false, false, false>); }
-    }
+    // (no clause bitmaps: every clause is walked; nothing is collected: k_emit 1, the narrowest kind of list)
+    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{"k_search_and(doc set candidates)", sg.dev(r_q), sg.dev(r_t), sg.dev(r_ip), sg.dev(r_ep), nullptr, n_queries, nq,
+                                                      items, slots, blocks_per_item, 1, any_not, 0, 0}));
     if (slots > 0) {
       TimedLaunch tl(c, stream, "k_docset_from_emitted", 0);
       RGPU_LAUNCH(k_docset_from_emitted, dim3(wg_count(((unsigned long long)slots + DOCSET_THREADS - 1) / DOCSET_THREADS)), dim3(DOCSET_THREADS), 0, stream,
@@ -4347,8 +4479,11 @@ extern "C" int32_t rgpu_decode_positions(rgpu_segment* seg, const rgpu_term_stat
 
 // ---- the match stage of a phrase search: one key per candidate slot into c->phrase_keys ------------------------------------------
 // The kernels read an array of candidate slots (emit_prefix / emit_count / emit_docs = c->phrase_count / c->phrase_docs) and do not
-// care what filled it: the conjunction of a phrase search (rgpu_search_phrase_batch) or the window of a rescoring
-// (rgpu_rescore_phrase_batch). The caller has zeroed c->d_err and reserved c->phrase_keys and c->phrase_redo (redo_cap slots).
+// care what filled it: and_emit_stage (the conjunction of rgpu_search_phrase_batch, _phrase_bool_batch and _phrase_or_batch) or
+// k_rescore_phrase_candidates (the window of rgpu_rescore_phrase_batch). phrase_match_setup has run in front of whatever fills
+// the slots (and_emit_stage runs it; a rescoring calls it): it reserves c->phrase_docs, c->phrase_keys and c->phrase_redo (redo_cap slots) and zeroes c->d_err. What
+// comes behind the stage: phrase_collect_stage, k_phrase_bool_score, the run-building kernels of a disjunction,
+// k_rescore_phrase_combine; the callers read the verdict, d_err[0], afterwards (phrase_match_status).
 struct PhraseMatchStage {
   const DevQuery* d_q;
   const DevTerm* d_t;
@@ -4358,7 +4493,7 @@ struct PhraseMatchStage {
   SloppyGroups* d_gr;
   int32_t n_queries;
   int64_t slots;     // a multiple of 64, every query's share too
-  int64_t redo_cap;
+  int64_t redo_cap;  // phrase_match_setup's
   bool any_exact, any_sloppy;
   bool sloppy_rpts;  // some sloppy phrase names a term twice
   // k_sloppy_groups (a search only: a rescoring refuses sloppy phrases that repeat a term and leaves the groups at "none")
@@ -4368,14 +4503,9 @@ struct PhraseMatchStage {
   const int32_t* d_nl0;
   int64_t collect_items;
 };
-static int64_t phrase_redo_cap(int64_t slots) {
-  // (developer knob: RGPU_PHRASE_REDO_CAP=<n> shrinks the list of left-over candidates, so that a test reaches the pass that runs without it)
-  int64_t redo_cap = PHRASE_REDO_LIST_CAP;
-  if (const char* e = std::getenv("RGPU_PHRASE_REDO_CAP")) redo_cap = std::max<int64_t>(0, std::min<int64_t>(redo_cap, std::atoll(e)));
-  return std::min<int64_t>(slots, redo_cap);
-}
 static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const PhraseMatchStage& a) {
   rgpu_ctx* c = seg->ctx;
+  if (a.slots == 0 || !(a.any_exact || a.any_sloppy)) return RGPU_OK;  // no slot, or no live phrase to look at one: d_err stays "fine"
   const SegView sv = seg_view(seg);
   const bool legacy = seg->version < 1;
   // One wavefront per candidate slot, first with the small position lists / pools (seven wavefronts per SIMD). A doc that holds
@@ -4541,6 +4671,92 @@ static int32_t phrase_match_status(int err, const char* held_too_often, const ch
   if (err == 0) return RGPU_OK;
   return fail(err, err == RGPU_ERR_UNSUPPORTED ? held_too_often : (err == RGPU_ERR_ILLEGAL_STATE ? not_found_again : "corrupt position data in .pos"));
 }
+// ... fetched by itself, synchronised: the calls that look at the verdict before they write anything to the caller's arrays
+static int32_t phrase_match_verdict(rgpu_ctx* c, hipStream_t stream, const char* held_too_often, const char* not_found_again) {
+  int err = 0;
+  HIP_TRY(hipMemcpyAsync(&err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return phrase_match_status(err, held_too_often, not_found_again);
+}
+
+// ---- the collectors behind it: every query's best k keys (its candidate slots: and_emit_stage's) into the call's rows --------------
+// k <= RGPU_PASS_K: one wavefront per chunk of PHRASE_COLLECT_CHUNK candidates (lead_collect_chunks), k_merge_items folds a query's
+// lists; deeper pages (or nothing to chunk): one wavefront per query, in passes. The chunked collector's lists live in
+// c->S->d_partial_keys / d_partial_counts: and_emit_stage is asked for collect_items * k and collect_items of them.
+static bool phrase_collect_chunked(int32_t k, int64_t collect_items) { return k <= RGPU_PASS_K && collect_items > 0; }
+struct PhraseCollectStage {
+  const int64_t* d_ep;  // slots in front of each query's
+  const int64_t* d_cp;  // chunks in front of each query's
+  const int32_t* d_sl;  // slops
+  const int32_t* d_nl;  // next_limit per query, -1: none
+  int32_t n_queries, k;
+  int64_t collect_items;
+  // Some sloppy query has a next_limit (the two-phase rule: a query whose first collected doc has more than next_limit candidates
+  // in front of it yields nothing): k_phrase_cutoff_items finds, chunk by chunk, the first collected doc and the candidates in
+  // front of it into d_cut, k_phrase_cutoff_decide sets the flags. Without: d_ab is all zero (nothing is abandoned), d_cut unused.
+  bool any_cutoff;
+  int32_t* d_ab;
+  PhraseCut* d_cut;
+};
+static void phrase_collect_stage(rgpu_segment* seg, hipStream_t stream, const PhraseCollectStage& a) {
+  rgpu_ctx* c = seg->ctx;
+  const bool wide = a.k > 64;  // the wide top-k lists
+  if (phrase_collect_chunked(a.k, a.collect_items)) {
+    {
+      TimedLaunch tl(c, stream, "k_phrase_collect", 0);
+      const unsigned grid = wg_count((a.collect_items + WG_WAVES - 1) / WG_WAVES);
+      if (a.any_cutoff) {
+        RGPU_LAUNCH(k_phrase_cutoff_items<0>, dim3(grid), dim3(WG_THREADS), 0, stream, a.d_cp, a.d_ep, c->phrase_count.p, c->phrase_keys.p,
+                    (const int32_t*)c->phrase_docs.p, a.d_sl, a.d_nl, (int)a.n_queries, a.collect_items, a.d_cut);
+        RGPU_LAUNCH(k_phrase_cutoff_items<1>, dim3(grid), dim3(WG_THREADS), 0, stream, a.d_cp, a.d_ep, c->phrase_count.p, c->phrase_keys.p,
+                    (const int32_t*)c->phrase_docs.p, a.d_sl, a.d_nl, (int)a.n_queries, a.collect_items, a.d_cut);
+        RGPU_LAUNCH(k_phrase_cutoff_decide, dim3(wg_count((a.n_queries + 255) / 256)), dim3(256), 0, stream, c->phrase_count.p, a.d_sl, a.d_nl, (int)a.n_queries,
+                    a.d_cut, a.d_ab);
+      }
+      const auto collect_items = wide ? k_phrase_collect_items<true> : k_phrase_collect_items<false>;
+      RGPU_LAUNCH(collect_items, dim3(grid), dim3(WG_THREADS), 0, stream, a.d_cp, a.d_ep, c->phrase_count.p, c->phrase_keys.p, (const int32_t*)a.d_ab,
+                  (int)a.n_queries, a.collect_items, (int)a.k, c->S->d_partial_keys.p, c->S->d_partial_counts.p);
+    }
+    if (wide) launch_merge<true>(c, stream, a.n_queries, a.k, a.d_cp, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
+    else launch_merge<false>(c, stream, a.n_queries, a.k, a.d_cp, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
+  } else {
+    TimedLaunch tl(c, stream, "k_phrase_collect", 0);
+    const auto collect = wide ? k_phrase_collect<true> : k_phrase_collect<false>;
+    RGPU_LAUNCH(collect, dim3(wg_count((a.n_queries + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, a.d_ep, c->phrase_count.p, c->phrase_keys.p,
+                (const int32_t*)c->phrase_docs.p, a.d_sl, a.d_nl, (int)a.n_queries, (int)a.k, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
+  }
+}
+
+// ---- a boolean query over phrases, as rgpu_search_phrase_bool_batch and rgpu_search_phrase_or_batch take one: its own fields, its
+// phrases and its term clauses (those the leaf holds go to `ptrs` for the preparation). `noun`: what the caller's messages call it.
+struct PhraseClauseArrays {
+  const rgpu_phrase_query* phrases;
+  int32_t n_phrases_total;
+  const rgpu_phrase_term* phrase_terms;
+  int32_t n_phrase_terms_total;
+  const rgpu_query_term* terms;
+  int32_t n_terms_total;
+};
+template <typename BoolQuery>
+static int32_t check_phrases_query(const rgpu_segment* seg, const BoolQuery& Q, const char* noun, const PhraseClauseArrays& a, std::vector<const rgpu_term_state*>* ptrs) {
+  const rgpu_ctx* c = seg->ctx;
+  if (Q.n_phrases < 1 || Q.n_phrases > RGPU_MAX_BOOL_PHRASES) return fail(RGPU_ERR_UNSUPPORTED, std::string(noun) + " holds 1..RGPU_MAX_BOOL_PHRASES phrases");
+  if (Q.first_phrase < 0 || (int64_t)Q.first_phrase + Q.n_phrases > (int64_t)a.n_phrases_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "phrase range outside phrases[]");
+  if (Q.n_terms < 0 || Q.n_must_not < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "negative clause count");
+  if (Q.n_terms + (int64_t)Q.n_must_not > 0 && (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms + Q.n_must_not > (int64_t)a.n_terms_total))
+    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "clause range outside terms[]");
+  for (int i = 0; i < Q.n_phrases; ++i) {
+    const rgpu_phrase_query& P = a.phrases[Q.first_phrase + i];
+    RGPU_TRY(check_phrase_query(c, P, a.n_phrase_terms_total, false));
+    RGPU_TRY(check_phrase_terms(seg, P, a.phrase_terms, ptrs));
+  }
+  for (int64_t i = 0; i < (int64_t)Q.n_terms + Q.n_must_not; ++i) {
+    const rgpu_query_term& t = a.terms[Q.first_term + i];
+    if (i < Q.n_terms && (t.sim_table < 0 || t.sim_table >= c->n_sim_tables)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
+    if (t.state.doc_freq > 0) ptrs->push_back(&t.state);
+  }
+  return RGPU_OK;
+}
 
 extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
                                             const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
@@ -4561,19 +4777,15 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
   }
   RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
   // the conjunction that finds a phrase's candidates answers a dense clause from its doc bitmap, as a BooleanQuery's does
-  const int64_t bitmap_df = (c->cfg.and_bitmaps >= 0 && c->n_sim_tables > 0) ? bitmap_min_df_and(seg) : INT64_MAX;
-  if (bitmap_df != INT64_MAX) {
-    std::vector<const rgpu_term_state*> dense;
-    std::vector<int32_t> dense_sim;
-    for (int32_t q = 0; q < n_queries; ++q) {
-      const rgpu_phrase_query& Q = queries[q];
-      if (Q.n_terms < 2) continue;
-      for (int i = 0; i < Q.n_terms; ++i) {
-        const rgpu_term_state& st = terms[Q.first_term + i].state;
-        if (st.doc_freq >= bitmap_df && !seg->bitmaps.find(st.doc_start_fp)) { dense.push_back(&st); dense_sim.push_back(Q.sim_table); }
-      }
-    }
-    if (!dense.empty()) RGPU_TRY(ensure_bitmaps_locked(seg, dense.data(), dense_sim.data(), dense.size()));
+  int64_t bitmap_df = INT64_MAX;
+  {
+    std::vector<const rgpu_term_state*> clauses;
+    std::vector<int32_t> clause_sim;
+    clauses.reserve((size_t)n_terms_total);
+    clause_sim.reserve((size_t)n_terms_total);
+    for (int32_t q = 0; q < n_queries; ++q)
+      for (int i = 0; i < queries[q].n_terms; ++i) { clauses.push_back(&terms[queries[q].first_term + i].state); clause_sim.push_back(queries[q].sim_table); }
+    RGPU_TRY(ensure_and_bitmaps_locked(seg, clauses, clause_sim, &bitmap_df));
   }
   std::vector<DevQuery> dq((size_t)n_queries);
   std::vector<DevTerm> dt;
@@ -4608,18 +4820,15 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
     if (Q.slop > 0) for (size_t i = pt.size() - (size_t)Q.n_terms; i < pt.size(); ++i) sloppy_rpts = sloppy_rpts || pt[i].same_as != pt[i].query_ord;
     dq[(size_t)q].n_terms = Q.n_terms;
     const DevTerm& lead = dt[(size_t)dq[(size_t)q].first_term];
-    items += lead.nblocks == 0 ? 1 : (lead.nblocks + blocks_per_item - 1) / blocks_per_item;
-    slots += ((int64_t)lead.df + 63) & ~(int64_t)63;  // (k_phrase_match_lanes: the 64 slots of a wavefront belong to one query)
-    collect_items += ((int64_t)lead.df + PHRASE_COLLECT_CHUNK - 1) / PHRASE_COLLECT_CHUNK;  // the lead's doc_freq bounds the candidates
+    items += lead_items(lead, blocks_per_item);
+    slots += lead_slots(lead);
+    collect_items += lead_collect_chunks(lead);
     any_cutoff = any_cutoff || (Q.slop > 0 && limits[(size_t)q] >= 0);
   }
   item_prefix[(size_t)n_queries] = items;
   emit_prefix[(size_t)n_queries] = slots;
   collect_prefix[(size_t)n_queries] = collect_items;
-  HIP_TRY(c->host_api_hits.reserve((size_t)n_queries * (size_t)k, 0, stream));
-  HIP_TRY(c->host_api_totals.reserve((size_t)n_queries, 0, stream));
-  HIP_TRY(hipMemsetAsync(c->host_api_totals.p, 0, (size_t)n_queries * 8, stream));
-  RGPU_LAUNCH(k_init_hits, dim3(wg_count(((size_t)n_queries * k + 255) / 256)), dim3(256), 0, stream, c->host_api_hits.p, (int64_t)n_queries, (int)k, (int)k, 0);
+  RGPU_TRY(api_rows_default(c, stream, n_queries, k));
   if (items > 0) {
     SCRATCH_TAKE(c);
     Stager st(c);
@@ -4633,22 +4842,7 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
     const auto r_cp = st.add<int64_t>(nq + 1);   // the chunked collector's items
     const auto r_ab = st.add<int32_t>(nq);       // k_phrase_cutoff's flags (zeroed by the copy)
     const auto r_cut = st.add<PhraseCut>(nq);    // ... and what its chunked form reduces into
-    std::vector<TermBitmap> clause_bitmaps;  // parallel to dt: the clauses behind a query's lead that have a doc bitmap
-    if (bitmap_df != INT64_MAX && seg->bitmaps.size() > 0) {
-      bool any = false;
-      clause_bitmaps.assign(dt.size(), TermBitmap{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0});
-      for (const DevQuery& q0 : dq) {
-        for (int i = 1; i < q0.n_terms; ++i) {
-          const DevTerm& t = dt[(size_t)(q0.first_term + i)];
-          if (t.df < bitmap_df) continue;
-          const BitmapInfo* bm = seg->bitmaps.find((int64_t)t.start_fp);
-          if (!bm || !bm->usable || bm->df != t.df) continue;
-          clause_bitmaps[(size_t)(q0.first_term + i)] = TermBitmap{bm->words, bm->ranks, bm->freqs, bm->ovf, bm->nib, bm->memb, bm->n_ovf, 0};
-          any = true;
-        }
-      }
-      if (!any) clause_bitmaps.clear();
-    }
+    const std::vector<TermBitmap> clause_bitmaps = clause_bitmap_table(seg, dq, dt, bitmap_df);
     const auto r_bm = st.add_if<TermBitmap>(!clause_bitmaps.empty(), clause_bitmaps.size());
     STAGE_SIZED(sg, st);
     sg.put(r_q, dq);
@@ -4666,86 +4860,26 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
     sg.fill(r_gr, 0xff);
     sg.put(r_bm, clause_bitmaps);
     RGPU_TRY(sg.upload(stream));
-    HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
-    HIP_TRY(c->phrase_keys.reserve((size_t)slots + 64, 0, stream));
-    const int64_t redo_cap = phrase_redo_cap(slots);
-    HIP_TRY(c->phrase_redo.reserve((size_t)redo_cap + 64, 0, stream));
-    HIP_TRY(c->phrase_count.reserve((size_t)n_queries, 0, stream));
-    HIP_TRY(hipMemsetAsync(c->phrase_count.p, 0, (size_t)n_queries * 8, stream));
-    const int k_emit = std::min<int>(k, 64);  // the conjunction only emits candidates: its (empty) top-k lists are the narrow kind
-    const bool chunked = k <= RGPU_PASS_K && collect_items > 0;  // (deeper pages: the one-wavefront collector's passes)
-    HIP_TRY(c->S->d_partial_keys.reserve(std::max((size_t)items * (size_t)k_emit, chunked ? (size_t)collect_items * (size_t)k : (size_t)0), 0, stream));
-    HIP_TRY(c->S->d_partial_counts.reserve((size_t)std::max(items, chunked ? collect_items : (int64_t)0), 0, stream));
-    HIP_TRY(c->S->d_tau.reserve((size_t)n_queries, 0, stream));
-    HIP_TRY(c->S->d_touched.reserve((size_t)n_queries * 2, 0, stream));
-    HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, (size_t)n_queries * 8, stream));
-    HIP_TRY(hipMemsetAsync(c->S->d_touched.p, 0, (size_t)n_queries * 16, stream));
-    HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));  // [0]: error code, [3]: "a candidate needs the wide lists"
     const DevQuery* d_q = sg.dev(r_q);
     const DevTerm* d_t = sg.dev(r_t);
-    const PosTerm* d_pt = sg.dev(r_pt);
-    const int64_t *d_ip = sg.dev(r_ip), *d_ep = sg.dev(r_ep), *d_cp = sg.dev(r_cp);
+    const int64_t *d_ep = sg.dev(r_ep), *d_cp = sg.dev(r_cp);
     const int32_t *d_sl = sg.dev(r_sl), *d_nl = sg.dev(r_nl);
     PhraseCut* d_cut = sg.dev(r_cut);
-    const SegView sv = seg_view(seg);
-    const bool legacy = seg->version < 1;
-    {
-      TimedLaunch tl(c, stream, "k_search_and(phrase candidates)", 0);
-      const int xcd_chunk = and_xcd_chunk(seg);
-      const unsigned grid = wg_count(and_grid((items + AND_WG_WAVES - 1) / AND_WG_WAVES, xcd_chunk));
-      auto go = [&](auto kern) {
-        RGPU_LAUNCH(kern, dim3(grid), dim3(AND_WG_THREADS), 0, stream, sv, d_q, d_t, d_ip, (int)n_queries, items, blocks_per_item, k_emit,
-                           c->S->d_partial_keys.p, c->S->d_partial_counts.p, c->S->d_tau.p, c->S->d_touched.p, d_ep, c->phrase_count.p,
-                           (void*)c->phrase_docs.p, (const unsigned long long*)nullptr, (const int32_t*)nullptr,
-                           clause_bitmaps.empty() ? (const TermBitmap*)nullptr : sg.dev(r_bm), xcd_chunk);
-      };
-      if (legacy) go(k_search_and<true, false, false, false>); else go(k_search_and<false, false, false, false>);
-    }
-    if (slots > 0) {
-      PhraseMatchStage ms{d_q, d_t, d_pt, d_ep, d_sl, sg.dev(r_gr), n_queries, slots, redo_cap, any_exact, any_sloppy, sloppy_rpts, true,
-                          d_cut, d_cp, d_nl, collect_items};
-      RGPU_TRY(phrase_match_stage(seg, stream, ms));
-    }
-    if (chunked) {
-      int32_t* d_ab = sg.dev(r_ab);
-      {
-      TimedLaunch tl(c, stream, "k_phrase_collect", 0);
-      const unsigned grid = wg_count((collect_items + WG_WAVES - 1) / WG_WAVES);
-      if (any_cutoff) {  // the two-phase rule's cut-off, chunk by chunk: first collected doc, candidates in front of it, the decision
-        RGPU_LAUNCH(k_phrase_cutoff_items<0>, dim3(grid), dim3(WG_THREADS), 0, stream, d_cp, d_ep, c->phrase_count.p, c->phrase_keys.p,
-                           (const int32_t*)c->phrase_docs.p, d_sl, d_nl, (int)n_queries, collect_items, d_cut);
-        RGPU_LAUNCH(k_phrase_cutoff_items<1>, dim3(grid), dim3(WG_THREADS), 0, stream, d_cp, d_ep, c->phrase_count.p, c->phrase_keys.p,
-                           (const int32_t*)c->phrase_docs.p, d_sl, d_nl, (int)n_queries, collect_items, d_cut);
-        RGPU_LAUNCH(k_phrase_cutoff_decide, dim3(wg_count((n_queries + 255) / 256)), dim3(256), 0, stream, c->phrase_count.p, d_sl, d_nl, (int)n_queries,
-                           d_cut, d_ab);
-      }
-      if (k > 64)
-        RGPU_LAUNCH(k_phrase_collect_items<true>, dim3(grid), dim3(WG_THREADS), 0, stream, d_cp, d_ep, c->phrase_count.p, c->phrase_keys.p,
-                           (const int32_t*)d_ab, (int)n_queries, collect_items, (int)k, c->S->d_partial_keys.p, c->S->d_partial_counts.p);
-      else
-        RGPU_LAUNCH(k_phrase_collect_items<false>, dim3(grid), dim3(WG_THREADS), 0, stream, d_cp, d_ep, c->phrase_count.p, c->phrase_keys.p,
-                           (const int32_t*)d_ab, (int)n_queries, collect_items, (int)k, c->S->d_partial_keys.p, c->S->d_partial_counts.p);
-      }
-      if (k > 64) launch_merge<true>(c, stream, n_queries, k, d_cp, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
-      else launch_merge<false>(c, stream, n_queries, k, d_cp, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
-    } else {
-      TimedLaunch tl(c, stream, "k_phrase_collect", 0);
-      const unsigned grid = wg_count((n_queries + WG_WAVES - 1) / WG_WAVES);
-      if (k > 64)
-        RGPU_LAUNCH(k_phrase_collect<true>, dim3(grid), dim3(WG_THREADS), 0, stream, d_ep, c->phrase_count.p, c->phrase_keys.p,
-                           (const int32_t*)c->phrase_docs.p, d_sl, d_nl, (int)n_queries, (int)k, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
-      else
-        RGPU_LAUNCH(k_phrase_collect<false>, dim3(grid), dim3(WG_THREADS), 0, stream, d_ep, c->phrase_count.p, c->phrase_keys.p,
-                           (const int32_t*)c->phrase_docs.p, d_sl, d_nl, (int)n_queries, (int)k, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
-    }
+    const bool chunked = phrase_collect_chunked(k, collect_items);
+    int64_t redo_cap = 0;
+    // (k_emit: the conjunction only emits candidates, its (empty) top-k lists are the narrow kind)
+    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{"k_search_and(phrase candidates)", d_q, d_t, sg.dev(r_ip), d_ep, clause_bitmaps.empty() ? nullptr : sg.dev(r_bm),
+                                                      n_queries, nq, items, slots, blocks_per_item, std::min<int>(k, 64), false,
+                                                      chunked ? (size_t)collect_items * (size_t)k : 0, chunked ? (size_t)collect_items : 0,
+                                                      &redo_cap, false /* the collectors read a query's first emit_count slots only */}));
+    RGPU_TRY(phrase_match_stage(seg, stream, PhraseMatchStage{d_q, d_t, sg.dev(r_pt), d_ep, d_sl, sg.dev(r_gr), n_queries, slots, redo_cap, any_exact, any_sloppy,
+                                                              sloppy_rpts, true, d_cut, d_cp, d_nl, collect_items}));
+    phrase_collect_stage(seg, stream, PhraseCollectStage{d_ep, d_cp, d_sl, d_nl, n_queries, k, collect_items, any_cutoff, sg.dev(r_ab), d_cut});
     HIP_TRY(launch_status());
   }
+  // the verdict in the same round as the rows (nothing launched: nothing to ask, and d_err may hold another call's)
   int err = 0;
-  hipError_t e0 = items > 0 ? hipMemcpyAsync(&err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, stream) : hipSuccess;
-  hipError_t e1 = hipMemcpyAsync(hits_out, c->host_api_hits.p, (size_t)n_queries * (size_t)k * sizeof(HitOut), hipMemcpyDeviceToHost, stream);
-  hipError_t e2 = hipMemcpyAsync(total_hits_out, c->host_api_totals.p, (size_t)n_queries * 8, hipMemcpyDeviceToHost, stream);
-  hipError_t e3 = hipStreamSynchronize(stream);
-  if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(RGPU_ERR_RUNTIME, "device to host copy failed");
+  RGPU_TRY(api_rows_read_back(c, stream, n_queries, k, hits_out, total_hits_out, items > 0 ? &err : nullptr));
   return phrase_match_status(err, "a doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)",
                              "internal: a conjunction match was not found again");
 }
@@ -4753,13 +4887,15 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
 // ---- BooleanQuery with exact PhraseQuery clauses among its required clauses: +"a b" +c -d #e ------------------------------------
 // (include/rucene_gpu.h rgpu_search_phrase_bool_batch; the plan: host/phrase_bool_plan.hpp; the two kernels of its own:
 // kernels/search_phrase_bool.hpp.) Launch sequence, all on the call's stream:
-//   1. k_search_and in emit mode over every query's DISTINCT required terms -> plane 0's candidate docs. MUST_NOT terms are removed
+//   1. and_emit_stage (with phrase_match_setup among its memsets in front of the launch: keys zeroed, the redo list sized from the
+//      slots of all planes, d_err zeroed): k_search_and in emit mode over every query's DISTINCT required terms -> plane 0's candidate docs (dense
+//      clauses from their doc bitmaps: ensure_and_bitmaps_locked, clause_bitmap_table). MUST_NOT terms are removed
 //      here, through the HAS_NOT instantiation: the prohibited probe clears a0 / a1 before the emit branch is reached, and
 //      DevQuery::pad is what n_req_not is computed from whether the kernel emits or collects;
 //   2. k_phrase_bool_fanout (batches with a query of more than one phrase): plane 0's docs and count to the other planes;
 //   3. phrase_match_stage over the virtual queries (query, phrase), plane-major — exact kernels only;
 //   4. k_phrase_bool_score: the reference-order f32 sum over plane 0's key;
-//   5. the phrase collectors over plane 0.
+//   5. phrase_collect_stage over plane 0; the verdict (phrase_match_verdict), then api_rows_read_back.
 // Unsupported shapes (see the header): sloppy clauses, phrases under SHOULD / MUST_NOT, SHOULD clauses or nested BooleanQuery clauses
 // beside a phrase, more than RGPU_MAX_BOOL_PHRASES phrases.
 static_assert(PHRASE_BOOL_MAX_PLANES == RGPU_MAX_BOOL_PHRASES, "k_phrase_bool_score keeps one key per plane in registers");
@@ -4783,23 +4919,10 @@ extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_p
   std::vector<rgpu_host::PhraseBoolPlan> plans(nq);
   int max_planes = 1;
   bool any_not = false;
+  const PhraseClauseArrays arrays{phrases, n_phrases_total, phrase_terms, n_phrase_terms_total, terms, n_terms_total};
   for (int32_t q = 0; q < n_queries; ++q) {
     const rgpu_phrase_bool_query& Q = queries[q];
-    if (Q.n_phrases < 1 || Q.n_phrases > RGPU_MAX_BOOL_PHRASES) return fail(RGPU_ERR_UNSUPPORTED, "a boolean query over phrases holds 1..RGPU_MAX_BOOL_PHRASES phrases");
-    if (Q.first_phrase < 0 || (int64_t)Q.first_phrase + Q.n_phrases > (int64_t)n_phrases_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "phrase range outside phrases[]");
-    if (Q.n_terms < 0 || Q.n_must_not < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "negative clause count");
-    if (Q.n_terms + (int64_t)Q.n_must_not > 0 && (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms + Q.n_must_not > (int64_t)n_terms_total))
-      return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "clause range outside terms[]");
-    for (int i = 0; i < Q.n_phrases; ++i) {
-      const rgpu_phrase_query& P = phrases[Q.first_phrase + i];
-      RGPU_TRY(check_phrase_query(c, P, n_phrase_terms_total, false));
-      RGPU_TRY(check_phrase_terms(seg, P, phrase_terms, &ptrs));
-    }
-    for (int i = 0; i < Q.n_terms + Q.n_must_not; ++i) {
-      const rgpu_query_term& t = terms[Q.first_term + i];
-      if (i < Q.n_terms && (t.sim_table < 0 || t.sim_table >= c->n_sim_tables)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
-      if (t.state.doc_freq > 0) ptrs.push_back(&t.state);
-    }
+    RGPU_TRY(check_phrases_query(seg, Q, "a boolean query over phrases", arrays, &ptrs));
     plans[(size_t)q] = rgpu_host::plan_phrase_bool(Q, phrases, phrase_terms, terms);
     const rgpu_host::PhraseBoolPlan& P = plans[(size_t)q];
     if (P.status != RGPU_OK) return fail(P.status, P.why);
@@ -4807,17 +4930,17 @@ extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_p
   }
   RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
   // the candidate conjunction answers a dense clause from its doc bitmap, as a phrase search's does
-  const int64_t bitmap_df = (c->cfg.and_bitmaps >= 0 && c->n_sim_tables > 0) ? bitmap_min_df_and(seg) : INT64_MAX;
-  if (bitmap_df != INT64_MAX) {
-    std::vector<const rgpu_term_state*> dense;
-    std::vector<int32_t> dense_sim;
+  int64_t bitmap_df = INT64_MAX;
+  {
+    std::vector<const rgpu_term_state*> clauses;
+    std::vector<int32_t> clause_sim;
+    clauses.reserve(ptrs.size());  // (every clause of a conjunction is a live term: ptrs holds them all)
+    clause_sim.reserve(ptrs.size());
     for (int32_t q = 0; q < n_queries; ++q) {
-      const rgpu_host::PhraseBoolPlan& P = plans[(size_t)q];
-      if (P.dead) continue;
-      for (const rgpu_term_state* st : P.conj)
-        if (st->doc_freq >= bitmap_df && !seg->bitmaps.find(st->doc_start_fp)) { dense.push_back(st); dense_sim.push_back(phrases[queries[q].first_phrase].sim_table); }
+      if (plans[(size_t)q].dead) continue;
+      for (const rgpu_term_state* st : plans[(size_t)q].conj) { clauses.push_back(st); clause_sim.push_back(phrases[queries[q].first_phrase].sim_table); }
     }
-    if (!dense.empty()) RGPU_TRY(ensure_bitmaps_locked(seg, dense.data(), dense_sim.data(), dense.size()));
+    RGPU_TRY(ensure_and_bitmaps_locked(seg, clauses, clause_sim, &bitmap_df));
   }
   // ---- the launch's arrays. Virtual queries (query, phrase) are plane-major: v = j * n_queries + q
   const size_t nv = nq * (size_t)max_planes;
@@ -4845,8 +4968,8 @@ extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_p
     for (const rgpu_term_state* st : P.conj) { cdt.emplace_back(); RGPU_TRY(make_dev_term(seg, *st, 0.0f, conj_sim, &cdt.back())); }
     for (const rgpu_term_state* st : P.must_not) { cdt.emplace_back(); RGPU_TRY(make_dev_term(seg, *st, 0.0f, conj_sim, &cdt.back())); }
     const DevTerm& lead = cdt[(size_t)cq[(size_t)q].first_term];
-    items += lead.nblocks == 0 ? 1 : (lead.nblocks + blocks_per_item - 1) / blocks_per_item;
-    collect_items += ((int64_t)lead.df + PHRASE_COLLECT_CHUNK - 1) / PHRASE_COLLECT_CHUNK;
+    items += lead_items(lead, blocks_per_item);
+    collect_items += lead_collect_chunks(lead);
     for (int j = 0; j < Q.n_phrases; ++j) {
       const size_t v = (size_t)j * nq + (size_t)q;
       vq[v] = DevQuery{RGPU_OP_AND, 0, (int32_t)pdt.size(), 0};
@@ -4873,11 +4996,7 @@ extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_p
     }
   emit_prefix[nv] = slots;
   const int64_t groups0 = emit_prefix[nq] / 64;  // plane 0's 64-slot groups
-  HIP_TRY(c->host_api_hits.reserve(nq * (size_t)k, 0, stream));
-  HIP_TRY(c->host_api_totals.reserve(nq, 0, stream));
-  HIP_TRY(hipMemsetAsync(c->host_api_totals.p, 0, nq * 8, stream));
-  RGPU_LAUNCH(k_init_hits, dim3(wg_count((nq * (size_t)k + 255) / 256)), dim3(256), 0, stream, c->host_api_hits.p, (int64_t)n_queries, (int)k, (int)k, 0);
-  int err = 0;
+  RGPU_TRY(api_rows_default(c, stream, n_queries, k));
   if (items > 0) {
     SCRATCH_TAKE(c);
     Stager st(c);
@@ -4891,22 +5010,7 @@ extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_p
     const auto r_nl = st.add<int32_t>(nq);  // no next_limit: no scorer here is two-phase
     const auto r_ab = st.add<int32_t>(nq);  // nothing is abandoned
     const auto r_gr = st.add<SloppyGroups>(nv);
-    std::vector<TermBitmap> clause_bitmaps;  // parallel to cdt: the required clauses behind a query's lead that have a doc bitmap
-    if (bitmap_df != INT64_MAX && seg->bitmaps.size() > 0) {
-      bool any = false;
-      clause_bitmaps.assign(cdt.size(), TermBitmap{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0});
-      for (const DevQuery& q0 : cq) {
-        for (int i = 1; i < q0.n_terms; ++i) {
-          const DevTerm& t = cdt[(size_t)(q0.first_term + i)];
-          if (t.df < bitmap_df) continue;
-          const BitmapInfo* bm = seg->bitmaps.find((int64_t)t.start_fp);
-          if (!bm || !bm->usable || bm->df != t.df) continue;
-          clause_bitmaps[(size_t)(q0.first_term + i)] = TermBitmap{bm->words, bm->ranks, bm->freqs, bm->ovf, bm->nib, bm->memb, bm->n_ovf, 0};
-          any = true;
-        }
-      }
-      if (!any) clause_bitmaps.clear();
-    }
+    const std::vector<TermBitmap> clause_bitmaps = clause_bitmap_table(seg, cq, cdt, bitmap_df);  // (the required clauses: MUST_NOT ones are walked)
     const auto r_bm = st.add_if<TermBitmap>(!clause_bitmaps.empty(), clause_bitmaps.size());
     STAGE_SIZED(sg, st);
     sg.put(r_cq, cq);
@@ -4926,102 +5030,50 @@ extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_p
     sg.fill(r_gr, 0xff);
     sg.put(r_bm, clause_bitmaps);
     RGPU_TRY(sg.upload(stream));
-    HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
-    HIP_TRY(c->phrase_keys.reserve((size_t)slots + 64, 0, stream));
-    const int64_t redo_cap = phrase_redo_cap(slots);  // (sized from the slots of ALL planes: any of them may hand candidates on)
-    HIP_TRY(c->phrase_redo.reserve((size_t)redo_cap + 64, 0, stream));
-    HIP_TRY(c->phrase_count.reserve(nv, 0, stream));
-    HIP_TRY(hipMemsetAsync(c->phrase_count.p, 0, nv * 8, stream));
-    HIP_TRY(hipMemsetAsync(c->phrase_keys.p, 0, (size_t)slots * 8, stream));  // (a 64-candidate group past a query's count is never written)
-    const int k_emit = std::min<int>(k, 64);
-    const bool chunked = k <= RGPU_PASS_K && collect_items > 0;
-    HIP_TRY(c->S->d_partial_keys.reserve(std::max((size_t)items * (size_t)k_emit, chunked ? (size_t)collect_items * (size_t)k : (size_t)0), 0, stream));
-    HIP_TRY(c->S->d_partial_counts.reserve((size_t)std::max(items, chunked ? collect_items : (int64_t)0), 0, stream));
-    HIP_TRY(c->S->d_tau.reserve(nq, 0, stream));
-    HIP_TRY(c->S->d_touched.reserve(nq * 2, 0, stream));
-    HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, nq * 8, stream));
-    HIP_TRY(hipMemsetAsync(c->S->d_touched.p, 0, nq * 16, stream));
-    HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));
-    const int64_t *d_ip = sg.dev(r_ip), *d_ep = sg.dev(r_ep), *d_cp = sg.dev(r_cp);
+    const int64_t *d_ep = sg.dev(r_ep), *d_cp = sg.dev(r_cp);
     const int32_t *d_sl = sg.dev(r_sl), *d_nl = sg.dev(r_nl);
     const PhraseBoolDev* d_pb = sg.dev(r_pb);
-    const SegView sv = seg_view(seg);
-    const bool legacy = seg->version < 1;
-    {
-      TimedLaunch tl(c, stream, "k_search_and(phrase-bool candidates)", 0);
-      const int xcd_chunk = and_xcd_chunk(seg);
-      const unsigned grid = wg_count(and_grid((items + AND_WG_WAVES - 1) / AND_WG_WAVES, xcd_chunk));
-      auto go = [&](auto kern) {
-        RGPU_LAUNCH(kern, dim3(grid), dim3(AND_WG_THREADS), 0, stream, sv, (const DevQuery*)sg.dev(r_cq), (const DevTerm*)sg.dev(r_cdt), d_ip, (int)n_queries, items,
-                    blocks_per_item, k_emit, c->S->d_partial_keys.p, c->S->d_partial_counts.p, c->S->d_tau.p, c->S->d_touched.p, d_ep, c->phrase_count.p,
-                    (void*)c->phrase_docs.p, (const unsigned long long*)nullptr, (const int32_t*)nullptr,
-                    clause_bitmaps.empty() ? (const TermBitmap*)nullptr : sg.dev(r_bm), xcd_chunk);
-      };
-      if (any_not) { if (legacy) go(k_search_and<true, false, true, false>); else go(k_search_and<false, false, true, false>); }
-      else { if (legacy) go(k_search_and<true, false, false, false>); else go(k_search_and<false, false, false, false>); }
+    const bool chunked = phrase_collect_chunked(k, collect_items);
+    int64_t redo_cap = 0;  // (sized from the slots of ALL planes: any of them may hand candidates on)
+    // (the conjunctions: one per query, plane 0; slots and counts: every plane's - k_phrase_bool_fanout fills the others)
+    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{"k_search_and(phrase-bool candidates)", sg.dev(r_cq), sg.dev(r_cdt), sg.dev(r_ip), d_ep,
+                                                      clause_bitmaps.empty() ? nullptr : sg.dev(r_bm), n_queries, nv, items, slots, blocks_per_item, std::min<int>(k, 64),
+                                                      any_not, chunked ? (size_t)collect_items * (size_t)k : 0, chunked ? (size_t)collect_items : 0, &redo_cap, true}));
+    const unsigned ggrid = wg_count((groups0 + WG_WAVES - 1) / WG_WAVES);
+    if (groups0 > 0 && max_planes > 1) {
+      TimedLaunch tl(c, stream, "k_phrase_bool_fanout", 0);
+      RGPU_LAUNCH(k_phrase_bool_fanout, dim3(ggrid), dim3(WG_THREADS), 0, stream, d_pb, d_ep, c->phrase_count.p, c->phrase_docs.p, (int)n_queries, groups0);
     }
+    RGPU_TRY(phrase_match_stage(seg, stream, PhraseMatchStage{sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ppt), d_ep, d_sl, sg.dev(r_gr), (int32_t)nv, slots, redo_cap, true,
+                                                              false, false, false, nullptr, nullptr, nullptr, 0}));
     if (groups0 > 0) {
-      const unsigned ggrid = wg_count((groups0 + WG_WAVES - 1) / WG_WAVES);
-      if (max_planes > 1) {
-        TimedLaunch tl(c, stream, "k_phrase_bool_fanout", 0);
-        RGPU_LAUNCH(k_phrase_bool_fanout, dim3(ggrid), dim3(WG_THREADS), 0, stream, d_pb, d_ep, c->phrase_count.p, c->phrase_docs.p, (int)n_queries, groups0);
-      }
-      PhraseMatchStage ms{sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ppt), d_ep, d_sl, sg.dev(r_gr), (int32_t)nv, slots, redo_cap, true, false, false, false,
-                          nullptr, nullptr, nullptr, 0};
-      RGPU_TRY(phrase_match_stage(seg, stream, ms));
-      {
-        TimedLaunch tl(c, stream, "k_phrase_bool_score", 0);
-        auto go = [&](auto kern) {
-          RGPU_LAUNCH(kern, dim3(ggrid), dim3(WG_THREADS), 0, stream, sv, d_pb, (const int32_t*)sg.dev(r_or), (const DevTerm*)sg.dev(r_sdt), d_ep,
-                      (const unsigned long long*)c->phrase_count.p, (int)n_queries, groups0, c->phrase_keys.p, c->d_err);
-        };
-        if (legacy) go(k_phrase_bool_score<true>); else go(k_phrase_bool_score<false>);
-      }
+      const SegView sv = seg_view(seg);
+      TimedLaunch tl(c, stream, "k_phrase_bool_score", 0);
+      auto go = [&](auto kern) {
+        RGPU_LAUNCH(kern, dim3(ggrid), dim3(WG_THREADS), 0, stream, sv, d_pb, (const int32_t*)sg.dev(r_or), (const DevTerm*)sg.dev(r_sdt), d_ep,
+                    (const unsigned long long*)c->phrase_count.p, (int)n_queries, groups0, c->phrase_keys.p, c->d_err);
+      };
+      if (seg->version < 1) go(k_phrase_bool_score<true>); else go(k_phrase_bool_score<false>);
     }
-    if (chunked) {
-      {
-        TimedLaunch tl(c, stream, "k_phrase_collect", 0);
-        const unsigned grid = wg_count((collect_items + WG_WAVES - 1) / WG_WAVES);
-        if (k > 64)
-          RGPU_LAUNCH(k_phrase_collect_items<true>, dim3(grid), dim3(WG_THREADS), 0, stream, d_cp, d_ep, c->phrase_count.p, c->phrase_keys.p,
-                      (const int32_t*)sg.dev(r_ab), (int)n_queries, collect_items, (int)k, c->S->d_partial_keys.p, c->S->d_partial_counts.p);
-        else
-          RGPU_LAUNCH(k_phrase_collect_items<false>, dim3(grid), dim3(WG_THREADS), 0, stream, d_cp, d_ep, c->phrase_count.p, c->phrase_keys.p,
-                      (const int32_t*)sg.dev(r_ab), (int)n_queries, collect_items, (int)k, c->S->d_partial_keys.p, c->S->d_partial_counts.p);
-      }
-      if (k > 64) launch_merge<true>(c, stream, n_queries, k, d_cp, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
-      else launch_merge<false>(c, stream, n_queries, k, d_cp, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
-    } else {
-      TimedLaunch tl(c, stream, "k_phrase_collect", 0);
-      const unsigned grid = wg_count((n_queries + WG_WAVES - 1) / WG_WAVES);
-      if (k > 64)
-        RGPU_LAUNCH(k_phrase_collect<true>, dim3(grid), dim3(WG_THREADS), 0, stream, d_ep, c->phrase_count.p, c->phrase_keys.p,
-                    (const int32_t*)c->phrase_docs.p, d_sl, d_nl, (int)n_queries, (int)k, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
-      else
-        RGPU_LAUNCH(k_phrase_collect<false>, dim3(grid), dim3(WG_THREADS), 0, stream, d_ep, c->phrase_count.p, c->phrase_keys.p,
-                    (const int32_t*)c->phrase_docs.p, d_sl, d_nl, (int)n_queries, (int)k, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
-    }
+    // (no sloppy clause, no next_limit: no scorer here is two-phase, nothing is abandoned)
+    phrase_collect_stage(seg, stream, PhraseCollectStage{d_ep, d_cp, d_sl, d_nl, n_queries, k, collect_items, false, sg.dev(r_ab), nullptr});
     HIP_TRY(launch_status());
     // a refused call writes nothing: the match stage's verdict first, the rows after it
-    HIP_TRY(hipMemcpyAsync(&err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    RGPU_TRY(phrase_match_status(err, "a doc holds one of an exact phrase's terms more than 1024 times", "internal: a conjunction match was not found again"));
+    RGPU_TRY(phrase_match_verdict(c, stream, "a doc holds one of an exact phrase's terms more than 1024 times", "internal: a conjunction match was not found again"));
   }
-  hipError_t e1 = hipMemcpyAsync(hits_out, c->host_api_hits.p, nq * (size_t)k * sizeof(HitOut), hipMemcpyDeviceToHost, stream);
-  hipError_t e2 = hipMemcpyAsync(total_hits_out, c->host_api_totals.p, nq * 8, hipMemcpyDeviceToHost, stream);
-  hipError_t e3 = hipStreamSynchronize(stream);
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(RGPU_ERR_RUNTIME, "device to host copy failed");
-  return RGPU_OK;
+  return api_rows_read_back(c, stream, n_queries, k, hits_out, total_hits_out);
 }
 
 // ---- BooleanQuery of SHOULD / MUST_NOT clauses with exact PhraseQuery clauses among the SHOULD ones: "a b" "c d" e -f -------------
 // (include/rucene_gpu.h rgpu_search_phrase_or_batch; the plan: host/phrase_or_plan.hpp; the run-building kernels:
 // kernels/search_phrase_or.hpp.) Launch sequence, all on the call's stream:
-//   1. k_search_and in emit mode, one "virtual query" per (query, phrase that exists in the leaf) -> that phrase's candidate docs
-//      (the conjunction of its terms, as rgpu_search_phrase_batch finds them);
+//   1. and_emit_stage (with phrase_match_setup among its memsets in front of the launch: keys zeroed, the redo list sized, d_err
+//      zeroed): k_search_and in emit mode, one "virtual query" per (query, phrase that exists in the leaf) -> that phrase's
+//      candidate docs (the conjunction of its terms, as rgpu_search_phrase_batch finds them);
 //   2. phrase_match_stage over the virtual queries — exact kernels only: one make_key(BM25(phrase freq, norm), doc) or 0 per slot.
-//      Once per call; its verdict (a doc that holds a phrase term more than 1024 times ...) is looked at before anything else runs;
-//   3. search_or_group over a Group of op OR: clauses in query order, a pseudo DevTerm (df = capacity) at every phrase position,
+//      Once per call; its verdict (phrase_match_verdict: a doc that holds a phrase term more than 1024 times ...) is looked at
+//      before anything else runs;
+//   3. api_rows_default, then search_or_group over a Group of op OR: clauses in query order, a pseudo DevTerm (df = capacity) at every phrase position,
 //      MUST_NOT terms behind them (DevQuery::pad), min_should_match in op bits 8... Its hook fills the phrase clauses' runs between
 //      k_score_terms and k_or_windows: k_phrase_run_fill, _count, _scan, _scatter, _sort;
 //   4. k > RGPU_PASS_K: step 3 once per pass of 128 hits, as search_impl runs its passes (rgpu_ctx::Pass, ceiling slots). The keys of
@@ -5046,46 +5098,32 @@ extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phr
   std::vector<const rgpu_term_state*> ptrs;
   std::vector<rgpu_host::PhraseOrPlan> plans(nq);
   std::vector<int32_t> first_virtual(nq + 1, 0);  // virtual query (query q, phrase j) = first_virtual[q] + j
+  const PhraseClauseArrays arrays{phrases, n_phrases_total, phrase_terms, n_phrase_terms_total, terms, n_terms_total};
   for (int32_t q = 0; q < n_queries; ++q) {
     const rgpu_phrase_or_query& Q = queries[q];
-    if (Q.n_phrases < 1 || Q.n_phrases > RGPU_MAX_BOOL_PHRASES) return fail(RGPU_ERR_UNSUPPORTED, "a disjunction over phrases holds 1..RGPU_MAX_BOOL_PHRASES phrases");
-    if (Q.first_phrase < 0 || (int64_t)Q.first_phrase + Q.n_phrases > (int64_t)n_phrases_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "phrase range outside phrases[]");
-    if (Q.n_terms < 0 || Q.n_must_not < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "negative clause count");
-    if (Q.n_terms + (int64_t)Q.n_must_not > 0 && (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms + Q.n_must_not > (int64_t)n_terms_total))
-      return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "clause range outside terms[]");
-    for (int i = 0; i < Q.n_phrases; ++i) {
-      const rgpu_phrase_query& P = phrases[Q.first_phrase + i];
-      RGPU_TRY(check_phrase_query(c, P, n_phrase_terms_total, false));
-      RGPU_TRY(check_phrase_terms(seg, P, phrase_terms, &ptrs));
-    }
-    for (int64_t i = 0; i < (int64_t)Q.n_terms + Q.n_must_not; ++i) {
-      const rgpu_query_term& t = terms[Q.first_term + i];
-      if (i < Q.n_terms && (t.sim_table < 0 || t.sim_table >= c->n_sim_tables)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
-      if (t.state.doc_freq > 0) ptrs.push_back(&t.state);
-    }
+    RGPU_TRY(check_phrases_query(seg, Q, "a disjunction over phrases", arrays, &ptrs));
     plans[(size_t)q] = rgpu_host::plan_phrase_or(Q, phrases, phrase_terms, terms);
     if (plans[(size_t)q].status != RGPU_OK) return fail(plans[(size_t)q].status, plans[(size_t)q].why);
     first_virtual[(size_t)q + 1] = first_virtual[(size_t)q] + Q.n_phrases;
   }
   RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
   // the candidate conjunctions answer a dense clause from its doc bitmap, as a phrase search's do
-  const int64_t bitmap_df = (c->cfg.and_bitmaps >= 0 && c->n_sim_tables > 0) ? bitmap_min_df_and(seg) : INT64_MAX;
-  if (bitmap_df != INT64_MAX) {
-    std::vector<const rgpu_term_state*> dense;
-    std::vector<int32_t> dense_sim;
+  int64_t bitmap_df = INT64_MAX;
+  {
+    std::vector<const rgpu_term_state*> clauses;
+    std::vector<int32_t> clause_sim;
+    clauses.reserve(ptrs.size());  // (every clause of a conjunction is a live term: ptrs holds them all)
+    clause_sim.reserve(ptrs.size());
     for (int32_t q = 0; q < n_queries; ++q) {
       const rgpu_host::PhraseOrPlan& P = plans[(size_t)q];
       if (P.dead) continue;
       for (int j = 0; j < queries[q].n_phrases; ++j) {
         if (P.capacity[(size_t)j] <= 0) continue;
         const rgpu_phrase_query& ph = phrases[queries[q].first_phrase + j];
-        for (int i = 0; i < ph.n_terms; ++i) {
-          const rgpu_term_state& st = phrase_terms[ph.first_term + i].state;
-          if (st.doc_freq >= bitmap_df && !seg->bitmaps.find(st.doc_start_fp)) { dense.push_back(&st); dense_sim.push_back(ph.sim_table); }
-        }
+        for (int i = 0; i < ph.n_terms; ++i) { clauses.push_back(&phrase_terms[ph.first_term + i].state); clause_sim.push_back(ph.sim_table); }
       }
     }
-    if (!dense.empty()) RGPU_TRY(ensure_bitmaps_locked(seg, dense.data(), dense_sim.data(), dense.size()));
+    RGPU_TRY(ensure_and_bitmaps_locked(seg, clauses, clause_sim, &bitmap_df));
   }
   // ---- the match stage's arrays (one virtual query per phrase) and the disjunction's Group
   const size_t nv = (size_t)first_virtual[nq];
@@ -5117,8 +5155,8 @@ extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phr
       vq[v].n_terms = ph.n_terms;
       const DevTerm& lead = pdt[(size_t)vq[v].first_term];
       if (lead.df != P.capacity[(size_t)j]) return fail(RGPU_ERR_ILLEGAL_STATE, "internal: a phrase's lead term is not its rarest");
-      items += lead.nblocks == 0 ? 1 : (lead.nblocks + blocks_per_item - 1) / blocks_per_item;
-      slots += ((int64_t)lead.df + 63) & ~(int64_t)63;  // (the 64 slots of a wavefront belong to one virtual query)
+      items += lead_items(lead, blocks_per_item);
+      slots += lead_slots(lead);
     }
     // DisjunctionSumScorer's children in query order, pseudo terms at the phrase positions; the MUST_NOT terms behind them
     DevQuery dq{RGPU_OP_OR | (P.min_should_match > 1 ? P.min_should_match << 8 : 0), 0, (int32_t)G0.terms.size(), 0};
@@ -5154,10 +5192,6 @@ extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phr
   }
   item_prefix[nv] = items;
   emit_prefix[nv] = slots;
-  HIP_TRY(c->host_api_hits.reserve(nq * (size_t)k, 0, stream));
-  HIP_TRY(c->host_api_totals.reserve(nq, 0, stream));
-  HitOut* hits_dev = c->host_api_hits.p;
-  int64_t* totals_dev = c->host_api_totals.p;
   const int n_buckets = (int)(((int64_t)seg->max_doc + PHRASE_OR_BUCKET - 1) / PHRASE_OR_BUCKET);
   const size_t n_cells = nv * (size_t)std::max(1, n_buckets);
   if (items > 0) {
@@ -5170,22 +5204,7 @@ extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phr
     const auto r_ip = st.add<int64_t>(nv + 1), r_ep = st.add<int64_t>(nv + 1);
     const auto r_sl = st.add<int32_t>(nv);  // slop 0 throughout
     const auto r_gr = st.add<SloppyGroups>(nv);
-    std::vector<TermBitmap> clause_bitmaps;  // parallel to pdt: the clauses behind a phrase's lead that have a doc bitmap
-    if (bitmap_df != INT64_MAX && seg->bitmaps.size() > 0) {
-      bool any = false;
-      clause_bitmaps.assign(pdt.size(), TermBitmap{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0});
-      for (const DevQuery& q0 : vq) {
-        for (int i = 1; i < q0.n_terms; ++i) {
-          const DevTerm& t = pdt[(size_t)(q0.first_term + i)];
-          if (t.df < bitmap_df) continue;
-          const BitmapInfo* bm = seg->bitmaps.find((int64_t)t.start_fp);
-          if (!bm || !bm->usable || bm->df != t.df) continue;
-          clause_bitmaps[(size_t)(q0.first_term + i)] = TermBitmap{bm->words, bm->ranks, bm->freqs, bm->ovf, bm->nib, bm->memb, bm->n_ovf, 0};
-          any = true;
-        }
-      }
-      if (!any) clause_bitmaps.clear();
-    }
+    const std::vector<TermBitmap> clause_bitmaps = clause_bitmap_table(seg, vq, pdt, bitmap_df);
     const auto r_bm = st.add_if<TermBitmap>(!clause_bitmaps.empty(), clause_bitmaps.size());
     STAGE_SIZED(sg, st);
     sg.put(r_vq, vq);
@@ -5197,44 +5216,16 @@ extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phr
     sg.fill(r_gr, 0xff);
     sg.put(r_bm, clause_bitmaps);
     RGPU_TRY(sg.upload(stream));
-    HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
-    HIP_TRY(c->phrase_keys.reserve((size_t)slots + 64, 0, stream));
-    const int64_t redo_cap = phrase_redo_cap(slots);
-    HIP_TRY(c->phrase_redo.reserve((size_t)redo_cap + 64, 0, stream));
-    HIP_TRY(c->phrase_count.reserve(nv, 0, stream));
-    HIP_TRY(hipMemsetAsync(c->phrase_count.p, 0, nv * 8, stream));
-    HIP_TRY(hipMemsetAsync(c->phrase_keys.p, 0, (size_t)slots * 8, stream));  // (a 64-candidate group past a query's count is never written)
-    const int k_emit = std::min<int>(k, 64);  // the conjunction only emits candidates: its (empty) top-k lists are the narrow kind
-    HIP_TRY(c->S->d_partial_keys.reserve((size_t)items * (size_t)k_emit, 0, stream));
-    HIP_TRY(c->S->d_partial_counts.reserve((size_t)items, 0, stream));
-    HIP_TRY(c->S->d_tau.reserve(nv, 0, stream));
-    HIP_TRY(c->S->d_touched.reserve(nv * 2, 0, stream));
-    HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, nv * 8, stream));
-    HIP_TRY(hipMemsetAsync(c->S->d_touched.p, 0, nv * 16, stream));
-    HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));
-    const SegView sv = seg_view(seg);
-    const bool legacy = seg->version < 1;
-    {
-      TimedLaunch tl(c, stream, "k_search_and(phrase-or candidates)", 0);
-      const int xcd_chunk = and_xcd_chunk(seg);
-      const unsigned grid = wg_count(and_grid((items + AND_WG_WAVES - 1) / AND_WG_WAVES, xcd_chunk));
-      auto go = [&](auto kern) {
-        RGPU_LAUNCH(kern, dim3(grid), dim3(AND_WG_THREADS), 0, stream, sv, (const DevQuery*)sg.dev(r_vq), (const DevTerm*)sg.dev(r_pdt), (const int64_t*)sg.dev(r_ip),
-                    (int)nv, items, blocks_per_item, k_emit, c->S->d_partial_keys.p, c->S->d_partial_counts.p, c->S->d_tau.p, c->S->d_touched.p,
-                    (const int64_t*)sg.dev(r_ep), c->phrase_count.p, (void*)c->phrase_docs.p, (const unsigned long long*)nullptr, (const int32_t*)nullptr,
-                    clause_bitmaps.empty() ? (const TermBitmap*)nullptr : sg.dev(r_bm), xcd_chunk);
-      };
-      if (legacy) go(k_search_and<true, false, false, false>); else go(k_search_and<false, false, false, false>);
-    }
-    PhraseMatchStage ms{sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ppt), sg.dev(r_ep), sg.dev(r_sl), sg.dev(r_gr), (int32_t)nv, slots, redo_cap, true, false, false, false,
-                        nullptr, nullptr, nullptr, 0};
-    RGPU_TRY(phrase_match_stage(seg, stream, ms));
+    int64_t redo_cap = 0;
+    // (one conjunction per virtual query; the MUST_NOT clauses belong to the disjunction, step 3; nothing is collected here)
+    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{"k_search_and(phrase-or candidates)", sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ip), sg.dev(r_ep),
+                                                      clause_bitmaps.empty() ? nullptr : sg.dev(r_bm), (int32_t)nv, nv, items, slots, blocks_per_item,
+                                                      std::min<int>(k, 64), false, 0, 0, &redo_cap, true}));
+    RGPU_TRY(phrase_match_stage(seg, stream, PhraseMatchStage{sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ppt), sg.dev(r_ep), sg.dev(r_sl), sg.dev(r_gr), (int32_t)nv, slots,
+                                                              redo_cap, true, false, false, false, nullptr, nullptr, nullptr, 0}));
     HIP_TRY(launch_status());
     // a refused call writes nothing: the match stage's verdict before the disjunction runs (the sync also frees the slot's stage)
-    int err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    RGPU_TRY(phrase_match_status(err, "a doc holds one of an exact phrase's terms more than 1024 times", "internal: a conjunction match was not found again"));
+    RGPU_TRY(phrase_match_verdict(c, stream, "a doc holds one of an exact phrase's terms more than 1024 times", "internal: a conjunction match was not found again"));
     // what the run-building kernels read in every pass
     HIP_TRY(c->phrase_or_prefix.reserve(nv + 1, 0, stream));
     HIP_TRY(c->phrase_or_runs.reserve(nv, 0, stream));
@@ -5281,12 +5272,11 @@ extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phr
   };
   // one pass: defaults for every row (a leaf that holds no clause of any query merges nothing), then the group
   auto one_pass = [&](int32_t k_pass) -> int32_t {
-    HIP_TRY(hipMemsetAsync(totals_dev, 0, nq * 8, stream));
-    RGPU_LAUNCH(k_init_hits, dim3(wg_count((nq * (size_t)k_pass + 255) / 256)), dim3(256), 0, stream, hits_dev, (int64_t)n_queries, (int)k_pass,
-                c->pass.stride > 0 ? c->pass.stride : (int)k_pass, c->pass.col0);
+    const RowColumns cols{k_pass, c->pass.stride > 0 ? c->pass.stride : k_pass, c->pass.col0};
+    RGPU_TRY(api_rows_default(c, stream, n_queries, k, &cols));
     if (c->pass.ceil_out) HIP_TRY(hipMemsetAsync(c->pass.ceil_out, 0, nq * 8, stream));
     Group G = G0;  // (search_or_group marks dense clauses in the group it is given)
-    return search_or_group(seg, G, k_pass, hits_dev, totals_dev, stream, &hook);
+    return search_or_group(seg, G, k_pass, c->host_api_hits.p, c->host_api_totals.p, stream, &hook);
   };
   c->pass = rgpu_ctx::Pass{};
   int32_t rc = RGPU_OK;
@@ -5309,11 +5299,7 @@ extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phr
   }
   if (rc != RGPU_OK) { (void)hipStreamSynchronize(stream); return rc; }
   HIP_TRY(launch_status());
-  hipError_t e1 = hipMemcpyAsync(hits_out, hits_dev, nq * (size_t)k * sizeof(HitOut), hipMemcpyDeviceToHost, stream);
-  hipError_t e2 = hipMemcpyAsync(total_hits_out, totals_dev, nq * 8, hipMemcpyDeviceToHost, stream);
-  hipError_t e3 = hipStreamSynchronize(stream);
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(RGPU_ERR_RUNTIME, "device to host copy failed");
-  return RGPU_OK;
+  return api_rows_read_back(c, stream, n_queries, k, hits_out, total_hits_out);
 }
 
 // ---- QueryRescorer ------------------------------------------------------------------------------------------------------------
@@ -5439,7 +5425,7 @@ extern "C" int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phras
   }
   RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
   // ---- plan: row q owns the candidate slots [q * S, q * S + S)
-  const int S = (k + 63) & ~63;
+  const int S = (int)rgpu_host::pb_round_up_64(k);
   const int64_t slots = (int64_t)n_queries * S;
   std::vector<DevQuery> dq((size_t)n_queries);
   std::vector<DevTerm> dt;
@@ -5484,15 +5470,11 @@ extern "C" int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phras
   const size_t n_hits = (size_t)n_queries * (size_t)k;
   HIP_TRY(c->host_api_hits.reserve(n_hits, 0, stream));
   HIP_TRY(hipMemcpyAsync(c->host_api_hits.p, hits_inout, n_hits * sizeof(HitOut), hipMemcpyHostToDevice, stream));
-  HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
-  HIP_TRY(c->phrase_keys.reserve((size_t)slots + 64, 0, stream));
-  const int64_t redo_cap = phrase_redo_cap(slots);
-  HIP_TRY(c->phrase_redo.reserve((size_t)redo_cap + 64, 0, stream));
+  int64_t redo_cap = 0;
+  // (zero_keys: k_rescore_phrase_combine reads the slots behind a row's window, and a batch of absent-term rows launches no match kernel)
+  RGPU_TRY(phrase_match_setup(c, stream, slots, true, &redo_cap));
   HIP_TRY(c->phrase_count.reserve((size_t)n_queries, 0, stream));
   HIP_TRY(hipMemcpyAsync(c->phrase_count.p, sg.dev(r_ec), (size_t)n_queries * 8, hipMemcpyDeviceToDevice, stream));
-  // (a 64-candidate kernel leaves the slots behind a row's window unwritten, and a batch of absent-term rows launches none)
-  HIP_TRY(hipMemsetAsync(c->phrase_keys.p, 0, (size_t)slots * 8, stream));
-  HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));
   const DevQuery* d_q = sg.dev(r_q);
   const DevTerm* d_t = sg.dev(r_t);
   RescoreParams* d_r = sg.dev(r_r);
@@ -5503,22 +5485,16 @@ extern "C" int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phras
     if (seg->version < 1) RGPU_LAUNCH(k_rescore_phrase_candidates<true>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_r, (int)n_queries, (int)k, S, c->host_api_hits.p, c->phrase_docs.p);
     else RGPU_LAUNCH(k_rescore_phrase_candidates<false>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_r, (int)n_queries, (int)k, S, c->host_api_hits.p, c->phrase_docs.p);
   }
-  if (any_exact || any_sloppy) {
-    PhraseMatchStage ms{d_q, d_t, sg.dev(r_pt), sg.dev(r_ep), sg.dev(r_sl), sg.dev(r_gr), n_queries, slots, redo_cap, any_exact, any_sloppy, false, false,
-                        nullptr, nullptr, nullptr, 0};
-    RGPU_TRY(phrase_match_stage(seg, stream, ms));
-  }
+  RGPU_TRY(phrase_match_stage(seg, stream, PhraseMatchStage{d_q, d_t, sg.dev(r_pt), sg.dev(r_ep), sg.dev(r_sl), sg.dev(r_gr), n_queries, slots, redo_cap, any_exact,
+                                                            any_sloppy, false, false, nullptr, nullptr, nullptr, 0}));
   {
     TimedLaunch tl(c, stream, "k_rescore_phrase_combine", 0);
     RGPU_LAUNCH(k_rescore_phrase_combine, dim3(wg_count((n_hits + 255) / 256)), dim3(256), 0, stream, sv, d_r, (int)n_queries, (int)k, S, c->phrase_keys.p, c->host_api_hits.p, finish ? 1 : 0);
   }
   if (finish) launch_rescore_sort(c, stream, d_r, n_queries, k);
   HIP_TRY(launch_status());
-  int err = 0;
-  HIP_TRY(hipMemcpyAsync(&err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
   // (a refusal here too leaves hits_inout as it came)
-  RGPU_TRY(phrase_match_status(err, "a hit doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)",
+  RGPU_TRY(phrase_match_verdict(c, stream, "a hit doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)",
                                "internal: a candidate doc was not found again"));
   HIP_TRY(hipMemcpyAsync(hits_inout, c->host_api_hits.p, n_hits * sizeof(HitOut), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
