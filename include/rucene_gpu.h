@@ -846,6 +846,34 @@ int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phrase_or_quer
                                     const rgpu_query_term* terms, int32_t n_terms_total,
                                     int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out);
 
+/* The three exact-phrase calls above restricted to a doc set (rgpu_docset_*, above): "a b" #F -X, +"a b" +c #F -X, "a b" c -X with
+ * the filters combined into `set`. Bit for bit the rows and totals the unmasked call returns on a segment uploaded with live_docs =
+ * live AND set: no scorer of an exact phrase is two-phase, so a doc outside the mask is a deleted doc and nothing else. The rules
+ * are rgpu_search_batch_masked's: the set belongs to `seg` (RGPU_ERR_ILLEGAL_ARGUMENT otherwise), live AND set is formed once and
+ * kept, closures pending from deferred batches are settled before the mask is installed, rgpu_docset_free waits for the call.
+ * A query or clause with slop > 0 -> RGPU_ERR_UNSUPPORTED, nothing launched, nothing written: SloppyPhraseScorer's next_limit counts
+ * deleted docs but not docs outside a filter, so the equivalence does not hold. A refused match verdict writes nothing, as without a
+ * mask. rgpu_search_phrase_or_batch_masked runs every pass of a k > 128 call under the mask. There are no masked rescore, planner or
+ * sharded forms.
+ * The candidate conjunction of a masked call drops the candidates that are outside the mask where it finds them (its own
+ * instantiation of the conjunction kernel; kernel statistics "k_search_and(masked phrase candidates)", "...(masked phrase-bool
+ * candidates)", "...(masked phrase-or candidates)"), so the match kernels see the survivors only. RGPU_PHRASE_MASK_COMPACT=0 in the
+ * environment when the context is created: the unmasked calls' instantiation, which keeps them marked ("k_search_and(masked phrase,
+ * marked)", "...(masked phrase-bool, marked)", "...(masked phrase-or, marked)"); rows are identical either way. */
+int32_t rgpu_search_phrase_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_query* queries, int32_t n_queries,
+                                        const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
+                                        int64_t* total_hits_out);
+int32_t rgpu_search_phrase_bool_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_bool_query* queries, int32_t n_queries,
+                                             const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                             const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                             const rgpu_query_term* terms, int32_t n_terms_total,
+                                             int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out);
+int32_t rgpu_search_phrase_or_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_or_query* queries, int32_t n_queries,
+                                           const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                           const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                           const rgpu_query_term* terms, int32_t n_terms_total,
+                                           int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out);
+
 /* ---- second-pass scoring (QueryRescorer)------------------------------------------------------------------------------ */
 /* search/scorer/rescorer.rs: QueryRescorer re-ranks the top `window_size` hits of a first pass with a second query —
  * per hit the second query's scorer is advanced to the doc and the two scores are combined (combine_score :337-352:

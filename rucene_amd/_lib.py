@@ -78,6 +78,7 @@ EXPORTS = [
     "rgpu_planner_create", "rgpu_planner_create_flat", "rgpu_planner_destroy", "rgpu_planner_sim_table", "rgpu_planner_set_sim_table", "rgpu_plan_uniform_ids",
     "rgpu_docset_from_words", "rgpu_docset_from_docs", "rgpu_docset_collect_batch", "rgpu_docset_combine", "rgpu_docset_cardinality", "rgpu_docset_words",
     "rgpu_docset_bytes", "rgpu_docset_free", "rgpu_search_batch_masked", "rgpu_search_batch_device_masked",
+    "rgpu_search_phrase_batch_masked", "rgpu_search_phrase_bool_batch_masked", "rgpu_search_phrase_or_batch_masked",
     "rgpu_points_attach", "rgpu_points_get_info", "rgpu_points_free", "rgpu_docset_from_point_ranges",
     "rgpu_plan_uniform_bytes", "rgpu_plan_batch_ids", "rgpu_plan_batch_bytes", "rgpu_planner_search_uniform_ids_device", "rgpu_planner_search_uniform_ids_sharded",
 ]
@@ -193,6 +194,9 @@ def lib():
         "rgpu_points_free": (None, [vp]),
         "rgpu_docset_from_point_ranges": (i32, [vp, vp, i32, i32, vp]),
         "rgpu_search_batch_masked": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp]),
+        "rgpu_search_phrase_batch_masked": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp]),
+        "rgpu_search_phrase_bool_batch_masked": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
+        "rgpu_search_phrase_or_batch_masked": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_batch_device_masked": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp]),
         "rgpu_bm25_compute_weight": (i32, [f32, f32, i64, i64, i64, vp, i32, f32, vp, vp, vp]),
         "rgpu_bm25_encode_norm": (C.c_uint8, [f32, i32]),
@@ -831,6 +835,41 @@ class Segment:
         totals = np.zeros(q.size, dtype=np.int64)
         _check(lib().rgpu_search_phrase_or_batch(self._h, q.ctypes.data, q.size, p.ctypes.data, p.size, pt.ctypes.data, pt.size,
                                                  t.ctypes.data if t.size else None, t.size, k, hits.ctypes.data, totals.ctypes.data))
+        return hits, totals
+
+    def search_phrase_batch_masked(self, docset, queries, terms, k):
+        """rgpu_search_phrase_batch_masked: search_phrase_batch restricted to `docset` (a DocSet of this segment); exact phrases only.
+        A refusal raises and returns nothing."""
+        q = np.ascontiguousarray(queries, dtype=PHRASE_QUERY_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=PHRASE_TERM_DTYPE)
+        hits = np.zeros((q.size, k), dtype=HIT_DTYPE)
+        totals = np.zeros(q.size, dtype=np.int64)
+        _check(lib().rgpu_search_phrase_batch_masked(self._h, docset._h, q.ctypes.data, q.size, t.ctypes.data, t.size, k, hits.ctypes.data,
+                                                     totals.ctypes.data))
+        return hits, totals
+
+    def search_phrase_bool_batch_masked(self, docset, queries, phrases, phrase_terms, terms, k):
+        """rgpu_search_phrase_bool_batch_masked: search_phrase_bool_batch restricted to `docset` (a DocSet of this segment)"""
+        q = np.ascontiguousarray(queries, dtype=PHRASE_BOOL_QUERY_DTYPE)
+        p = np.ascontiguousarray(phrases, dtype=PHRASE_QUERY_DTYPE)
+        pt = np.ascontiguousarray(phrase_terms, dtype=PHRASE_TERM_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=QUERY_TERM_DTYPE)
+        hits = np.zeros((q.size, k), dtype=HIT_DTYPE)
+        totals = np.zeros(q.size, dtype=np.int64)
+        _check(lib().rgpu_search_phrase_bool_batch_masked(self._h, docset._h, q.ctypes.data, q.size, p.ctypes.data, p.size, pt.ctypes.data, pt.size,
+                                                          t.ctypes.data if t.size else None, t.size, k, hits.ctypes.data, totals.ctypes.data))
+        return hits, totals
+
+    def search_phrase_or_batch_masked(self, docset, queries, phrases, phrase_terms, terms, k):
+        """rgpu_search_phrase_or_batch_masked: search_phrase_or_batch restricted to `docset` (a DocSet of this segment)"""
+        q = np.ascontiguousarray(queries, dtype=PHRASE_OR_QUERY_DTYPE)
+        p = np.ascontiguousarray(phrases, dtype=PHRASE_QUERY_DTYPE)
+        pt = np.ascontiguousarray(phrase_terms, dtype=PHRASE_TERM_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=QUERY_TERM_DTYPE)
+        hits = np.zeros((q.size, k), dtype=HIT_DTYPE)
+        totals = np.zeros(q.size, dtype=np.int64)
+        _check(lib().rgpu_search_phrase_or_batch_masked(self._h, docset._h, q.ctypes.data, q.size, p.ctypes.data, p.size, pt.ctypes.data, pt.size,
+                                                        t.ctypes.data if t.size else None, t.size, k, hits.ctypes.data, totals.ctypes.data))
         return hits, totals
 
     def rescore_batch(self, queries, terms, requests, hits, finish=True):

@@ -440,8 +440,12 @@ struct CachedFilter {
 //   FilteredQuery::clauses(Q, {F ...}, {X ...})      the BooleanQuery "Q's clauses, #F, -X": the rows are the reference's when Q brings a
 //                                                    MUST or FILTER clause of its own ("b c #F" is ReqOptScorer(F, b | c) there and matches
 //                                                    ALL of F) and, for -X, min_should_match <= 1 (boolean_query.rs:235-251)
-// Anything else — a phrase underneath included: a sloppy phrase's next_limit counts deleted docs, not docs outside a filter, and the
-// phrase entry points have no masked form — is UnsupportedOperation, i.e. cpu_fallback. `query` is not owned.
+// Anything else — a phrase underneath included — is UnsupportedOperation, i.e. cpu_fallback. `query` is not owned.
+// GpuIndexSearcher::filtered_phrases = true (off by default) serves EXACT phrases underneath through the masked phrase calls
+// (rgpu_search_phrase_batch_masked, _phrase_bool_batch_masked, _phrase_or_batch_masked): a PhraseQuery or PhraseBooleanQuery under either
+// spelling, a PhraseDisjunctionQuery under filter_query or under clauses(Q, {}, {X ...}) with min_should_match <= 1. Still refused with it
+// on: any sloppy phrase (its next_limit counts deleted docs, not docs outside a filter), clauses(PhraseDisjunctionQuery, {F ...}) — "a b"
+// c #F, the doc set is the only required clause —, -X beside min_should_match >= 2, what the phrase queries' own check_served refuses.
 struct FilteredQuery : Query {
   const Query* query = nullptr;
   std::vector<CachedFilter> filters, excludes;
@@ -460,13 +464,25 @@ struct FilteredQuery : Query {
     out.excludes = std::move(x);
     return out;
   }
-  void check_served() const;  // (below PhraseBooleanQuery / PhraseDisjunctionQuery's definitions)
+  void check_served(bool filtered_phrases = false) const;  // (below PhraseBooleanQuery / PhraseDisjunctionQuery's definitions)
 };
-inline void FilteredQuery::check_served() const {
+inline void FilteredQuery::check_served(bool filtered_phrases) const {
   if (!query || (filters.empty() && excludes.empty()) || (as_filter_query && (filters.empty() || !excludes.empty())))
     throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "a filtered query takes a query and at least one cached filter");
-  if (dynamic_cast<const PhraseQuery*>(query) || dynamic_cast<const PhraseBooleanQuery*>(query) || dynamic_cast<const PhraseDisjunctionQuery*>(query))
-    throw Error(RGPU_ERR_UNSUPPORTED, "a filtered phrase is not served by the GPU path");
+  const PhraseQuery* phrase = dynamic_cast<const PhraseQuery*>(query);
+  const PhraseBooleanQuery* phrase_bool = dynamic_cast<const PhraseBooleanQuery*>(query);
+  const PhraseDisjunctionQuery* phrase_or = dynamic_cast<const PhraseDisjunctionQuery*>(query);
+  if (phrase || phrase_bool || phrase_or) {
+    if (!filtered_phrases || (phrase && phrase->slop > 0)) throw Error(RGPU_ERR_UNSUPPORTED, "a filtered phrase is not served by the GPU path");
+    if (phrase_bool) phrase_bool->check_served();
+    if (phrase_or) {
+      phrase_or->check_served();
+      if (as_filter_query) return;
+      if (!filters.empty()) throw Error(RGPU_ERR_UNSUPPORTED, "a doc set as the only required clause is not served by the GPU path (the reference matches all of it)");
+      if (phrase_or->min_should_match > 1) throw Error(RGPU_ERR_UNSUPPORTED, "a MUST_NOT doc set beside min_should_match >= 2 is not served by the GPU path");
+    }
+    return;
+  }
   if (dynamic_cast<const FilteredQuery*>(query) || dynamic_cast<const NestedBooleanQuery*>(query))
     throw Error(RGPU_ERR_UNSUPPORTED, "a filtered query over a nested or another filtered query is not served by the GPU path");
   if (as_filter_query) return;
@@ -480,7 +496,8 @@ inline void FilteredQuery::check_served() const {
 // byte order of the sortable bytes. ONE dimension (4 or 8 bytes per bound). It does not score — ConstantScoreScorer(0.0) under MUST and
 // FILTER alike, PointRangeWeight::new :482 — so it is served as a doc set: GpuIndexSearcher::range_filter builds the CachedFilter on
 // the GPU from attached points and range_clauses spells "Q's clauses, +/#ranges, -ranges" as a FilteredQuery. Alone, under SHOULD, as
-// the only required clause or beside a phrase it is UnsupportedOperation (cpu_fallback), as the same shapes with a CachedFilter are.
+// the only required clause or beside a phrase (unless filtered_phrases is on, and the phrase exact) it is UnsupportedOperation
+// (cpu_fallback), as the same shapes with a CachedFilter are.
 struct PointRangeQuery : Query {
   std::string field;
   std::vector<uint8_t> lower, upper;
@@ -775,6 +792,9 @@ class GpuIndexSearcher {
   // Trees the GPU path does not serve: fold one level of nesting (same docs, scores within 1e-5 — NestedBooleanQuery), and / or
   // hand the query to the host's CPU searcher — where rust/gpu/searcher.rs calls DefaultIndexSearcher::search
   bool flatten_nested = false;
+  // FilteredQuery over EXACT phrases (PhraseQuery, PhraseBooleanQuery, PhraseDisjunctionQuery) goes through the masked phrase calls
+  // instead of being UnsupportedOperation (FilteredQuery's comment says what stays refused)
+  bool filtered_phrases = false;
   std::function<void(const Query&, TopDocsCollector&)> cpu_fallback;
 
   // ---- cached filters: doc sets in HBM as FILTER / MUST_NOT masks (include/rucene_gpu.h rgpu_docset_*) ---------------------------
@@ -1007,7 +1027,8 @@ class GpuIndexSearcher {
 
   // IndexSearcher::search(PhraseQuery, TopDocsCollector(k)) for a batch of exact phrases. PhraseQuery::create_weight
   // (phrase_query.rs:136-186): ONE BM25 weight from the statistics of all the phrase's terms.
-  std::vector<TopDocs> search_phrases(const std::vector<const PhraseQuery*>& queries, size_t k) {
+  // `masks` (one doc set per leaf, or null): the search restricted to them — rgpu_search_phrase_batch_masked; exact phrases only.
+  std::vector<TopDocs> search_phrases(const std::vector<const PhraseQuery*>& queries, size_t k, const std::vector<rgpu_docset*>* masks = nullptr) {
     const int32_t nq = static_cast<int32_t>(queries.size());
     std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
     std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
@@ -1019,15 +1040,20 @@ class GpuIndexSearcher {
       pack_phrases(queries, leaf, &qs, &ts);
       leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
       leaf_totals[li].assign(static_cast<size_t>(nq), 0);
-      check(rgpu_search_phrase_batch(leaf.segment, qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
-                                     leaf_hits[li].data(), leaf_totals[li].data()));
+      if (masks)
+        check(rgpu_search_phrase_batch_masked(leaf.segment, (*masks)[li], qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
+                                              leaf_hits[li].data(), leaf_totals[li].data()));
+      else
+        check(rgpu_search_phrase_batch(leaf.segment, qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
+                                       leaf_hits[li].data(), leaf_totals[li].data()));
     }
     return merge_leaves(leaf_hits, leaf_totals, nq, k);
   }
 
   // IndexSearcher::search(BooleanQuery over phrases and terms, TopDocsCollector(k)) for a batch: rgpu_search_phrase_bool_batch per leaf.
   // A FILTER clause rides with weight 0 (needs_scores = false); phrase_slot[i] = the phrase's index in `required`.
-  std::vector<TopDocs> search_phrase_bools(const std::vector<const PhraseBooleanQuery*>& queries, size_t k) {
+  // `masks` as for search_phrases: rgpu_search_phrase_bool_batch_masked.
+  std::vector<TopDocs> search_phrase_bools(const std::vector<const PhraseBooleanQuery*>& queries, size_t k, const std::vector<rgpu_docset*>* masks = nullptr) {
     const int32_t nq = static_cast<int32_t>(queries.size());
     for (const PhraseBooleanQuery* q : queries) q->check_served();
     std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
@@ -1072,16 +1098,22 @@ class GpuIndexSearcher {
       for (size_t i = 0; i < ps.size(); ++i) { if (filtered[i]) ps[i].weight = 0.0f; ps[i].next_limit = 0; }
       leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
       leaf_totals[li].assign(static_cast<size_t>(nq), 0);
-      check(rgpu_search_phrase_bool_batch(leaf.segment, qs.data(), nq, ps.data(), static_cast<int32_t>(ps.size()), pts.data(), static_cast<int32_t>(pts.size()),
-                                          ts.empty() ? nullptr : ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
-                                          leaf_hits[li].data(), leaf_totals[li].data()));
+      if (masks)
+        check(rgpu_search_phrase_bool_batch_masked(leaf.segment, (*masks)[li], qs.data(), nq, ps.data(), static_cast<int32_t>(ps.size()), pts.data(),
+                                                   static_cast<int32_t>(pts.size()), ts.empty() ? nullptr : ts.data(), static_cast<int32_t>(ts.size()),
+                                                   static_cast<int32_t>(k), leaf_hits[li].data(), leaf_totals[li].data()));
+      else
+        check(rgpu_search_phrase_bool_batch(leaf.segment, qs.data(), nq, ps.data(), static_cast<int32_t>(ps.size()), pts.data(), static_cast<int32_t>(pts.size()),
+                                            ts.empty() ? nullptr : ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
+                                            leaf_hits[li].data(), leaf_totals[li].data()));
     }
     return merge_leaves(leaf_hits, leaf_totals, nq, k);
   }
 
   // IndexSearcher::search(BooleanQuery of SHOULD phrases and terms, TopDocsCollector(k)) for a batch: rgpu_search_phrase_or_batch per
   // leaf. phrase_slot[i] = the phrase's index in `should_queries`.
-  std::vector<TopDocs> search_phrase_ors(const std::vector<const PhraseDisjunctionQuery*>& queries, size_t k) {
+  // `masks` as for search_phrases: rgpu_search_phrase_or_batch_masked.
+  std::vector<TopDocs> search_phrase_ors(const std::vector<const PhraseDisjunctionQuery*>& queries, size_t k, const std::vector<rgpu_docset*>* masks = nullptr) {
     const int32_t nq = static_cast<int32_t>(queries.size());
     for (const PhraseDisjunctionQuery* q : queries) q->check_served();
     std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
@@ -1125,9 +1157,14 @@ class GpuIndexSearcher {
       for (rgpu_phrase_query& p : ps) p.next_limit = 0;
       leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
       leaf_totals[li].assign(static_cast<size_t>(nq), 0);
-      check(rgpu_search_phrase_or_batch(leaf.segment, qs.data(), nq, ps.data(), static_cast<int32_t>(ps.size()), pts.data(), static_cast<int32_t>(pts.size()),
-                                        ts.empty() ? nullptr : ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
-                                        leaf_hits[li].data(), leaf_totals[li].data()));
+      if (masks)
+        check(rgpu_search_phrase_or_batch_masked(leaf.segment, (*masks)[li], qs.data(), nq, ps.data(), static_cast<int32_t>(ps.size()), pts.data(),
+                                                 static_cast<int32_t>(pts.size()), ts.empty() ? nullptr : ts.data(), static_cast<int32_t>(ts.size()),
+                                                 static_cast<int32_t>(k), leaf_hits[li].data(), leaf_totals[li].data()));
+      else
+        check(rgpu_search_phrase_or_batch(leaf.segment, qs.data(), nq, ps.data(), static_cast<int32_t>(ps.size()), pts.data(), static_cast<int32_t>(pts.size()),
+                                          ts.empty() ? nullptr : ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
+                                          leaf_hits[li].data(), leaf_totals[li].data()));
     }
     return merge_leaves(leaf_hits, leaf_totals, nq, k);
   }
@@ -1272,7 +1309,7 @@ class GpuIndexSearcher {
     for (size_t i = 0; i < queries.size(); ++i) {   // refused before any leaf is touched
       inner[i] = queries[i];
       if (const FilteredQuery* f = dynamic_cast<const FilteredQuery*>(queries[i])) {
-        f->check_served();
+        f->check_served(filtered_phrases);
         std::vector<uint64_t> fs, xs;
         for (CachedFilter c : f->filters) { sets_of(c); fs.push_back(c.id); }
         for (CachedFilter c : f->excludes) { sets_of(c); xs.push_back(c.id); }
@@ -1289,19 +1326,48 @@ class GpuIndexSearcher {
         got = search_many(part, k);
       } else {
         const std::vector<rgpu_docset*>& masks = masks_of(grp.key);
-        const int32_t nq = static_cast<int32_t>(part.size());
-        std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
-        std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
-        for (size_t li = 0; li < leaves_.size(); ++li) {
-          std::vector<rgpu_query> qs;
-          std::vector<rgpu_query_term> ts;
-          plan(part, li, &qs, &ts);
-          leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
-          leaf_totals[li].assign(static_cast<size_t>(nq), 0);
-          check(rgpu_search_batch_masked(leaves_[li].segment, masks[li], qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
-                                         leaf_hits[li].data(), leaf_totals[li].data()));
+        // (filtered_phrases: the group's phrase rows, by kind, through the masked phrase calls; the other rows as they went)
+        std::vector<size_t> plain_at, phrase_at, bool_at, or_at;
+        for (size_t i = 0; i < part.size(); ++i) {
+          if (dynamic_cast<const PhraseQuery*>(part[i])) phrase_at.push_back(i);
+          else if (dynamic_cast<const PhraseBooleanQuery*>(part[i])) bool_at.push_back(i);
+          else if (dynamic_cast<const PhraseDisjunctionQuery*>(part[i])) or_at.push_back(i);
+          else plain_at.push_back(i);
         }
-        got = merge_leaves(leaf_hits, leaf_totals, nq, k);
+        got.resize(part.size());
+        auto place = [&](const std::vector<size_t>& at, std::vector<TopDocs> rows) { for (size_t i = 0; i < at.size(); ++i) got[at[i]] = std::move(rows[i]); };
+        if (!plain_at.empty()) {
+          std::vector<const Query*> plain;
+          for (size_t i : plain_at) plain.push_back(part[i]);
+          const int32_t nq = static_cast<int32_t>(plain.size());
+          std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
+          std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
+          for (size_t li = 0; li < leaves_.size(); ++li) {
+            std::vector<rgpu_query> qs;
+            std::vector<rgpu_query_term> ts;
+            plan(plain, li, &qs, &ts);
+            leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
+            leaf_totals[li].assign(static_cast<size_t>(nq), 0);
+            check(rgpu_search_batch_masked(leaves_[li].segment, masks[li], qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
+                                           leaf_hits[li].data(), leaf_totals[li].data()));
+          }
+          place(plain_at, merge_leaves(leaf_hits, leaf_totals, nq, k));
+        }
+        if (!phrase_at.empty()) {
+          std::vector<const PhraseQuery*> rows;
+          for (size_t i : phrase_at) rows.push_back(static_cast<const PhraseQuery*>(part[i]));
+          place(phrase_at, search_phrases(rows, k, &masks));
+        }
+        if (!bool_at.empty()) {
+          std::vector<const PhraseBooleanQuery*> rows;
+          for (size_t i : bool_at) rows.push_back(static_cast<const PhraseBooleanQuery*>(part[i]));
+          place(bool_at, search_phrase_bools(rows, k, &masks));
+        }
+        if (!or_at.empty()) {
+          std::vector<const PhraseDisjunctionQuery*> rows;
+          for (size_t i : or_at) rows.push_back(static_cast<const PhraseDisjunctionQuery*>(part[i]));
+          place(or_at, search_phrase_ors(rows, k, &masks));
+        }
       }
       for (size_t i = 0; i < grp.rows.size(); ++i) out[static_cast<size_t>(grp.rows[i])] = std::move(got[i]);
     }

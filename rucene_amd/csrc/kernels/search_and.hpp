@@ -175,7 +175,12 @@ struct SeqRec {
 // scorer/boosting_scorer.rs:40-81). DevQuery::pad = n_not | n_dem << 8, device clause order [MUST][MUST_NOT x n_not][demoting x n_dem]:
 // a candidate found in a demoting clause stays, counts, and has its finished f32 sum multiplied once by negative_boost (the first
 // demoting clause's DevTerm::weight) before its key is formed. The instantiations without HAS_DEM are the code they were.
-template <bool LEGACY, bool WIDE, bool HAS_NOT, bool HAS_OPT, bool HAS_DEM = false>
+// LIVE_ONLY (emit mode without HAS_OPT: the masked exact-phrase calls, whose seg.live is `live AND doc set`): a candidate that is not
+// live is dropped - before the first clause is asked about it - instead of travelling on with its sign bit set, so the survivors
+// sit compactly at the atomic cursor. An exact phrase has no next_limit: nothing downstream counts a dead candidate. Under a
+// selective doc set nearly every lead posting is dead; it then costs no probe here, no slot behind emit_count[q] and no lane of
+// the match kernels. The instantiations without LIVE_ONLY are the code they were.
+template <bool LEGACY, bool WIDE, bool HAS_NOT, bool HAS_OPT, bool HAS_DEM = false, bool LIVE_ONLY = false>
 __global__ __launch_bounds__(AND_WG_THREADS, AND_WAVES_PER_SIMD) void k_search_and(SegView seg, const DevQuery* __restrict__ queries,
                                                            const DevTerm* __restrict__ terms,
                                                            const int64_t* __restrict__ item_prefix, int n_queries,
@@ -201,6 +206,7 @@ __global__ __launch_bounds__(AND_WG_THREADS, AND_WAVES_PER_SIMD) void k_search_a
   // at emit_prefix[q] in any order, emit_count[q] the cursor. With HAS_OPT (the exact ReqOptScorer rule): one SeqRec per
   // lead posting at emit_prefix[q] + the posting's ordinal — doc order, no cursor.
   static_assert(!HAS_DEM || (HAS_NOT && !HAS_OPT), "demoting clauses sit behind the MUST_NOT clauses of a tree without optional clauses");
+  static_assert(!LIVE_ONLY || (!HAS_OPT && !HAS_DEM && !WIDE), "LIVE_ONLY is an emitting conjunction of required and prohibited clauses");
   int32_t* const emit_docs = HAS_OPT ? nullptr : static_cast<int32_t*>(emit_out);
   SeqRec* const seq_out = HAS_OPT ? static_cast<SeqRec*>(emit_out) : nullptr;
   __shared__ __attribute__((aligned(16))) uint8_t slabs[AND_WG_WAVES][2 * SLAB_STREAM];  // FullBlock staging only: tails arrive decoded
@@ -267,7 +273,8 @@ __global__ __launch_bounds__(AND_WG_THREADS, AND_WAVES_PER_SIMD) void k_search_a
                        uint32_t c1f1) {  // nn = norm byte 0 | norm byte 1 << 8; ord0 = ordinal of the wave's first lead posting
     // (phrase candidates keep their deleted docs — marked when they are emitted: the two-phase loop of bulk_scorer.rs counts
     // every approximation towards next_limit, live or not; the branch is scalar)
-    const uint64_t* const live_here = (!HAS_OPT && emit_out != nullptr) ? nullptr : seg.live;
+    // (LIVE_ONLY: exact phrases under a mask - no next_limit, so a dead candidate ends here)
+    const uint64_t* const live_here = (!LIVE_ONLY && !HAS_OPT && emit_out != nullptr) ? nullptr : seg.live;
     a0 = a0 && doc_in_segment(seg, d0) && doc_is_live(live_here, d0);
     a1 = a1 && doc_in_segment(seg, d1) && doc_is_live(live_here, d1);
     use_table(L.sim_table);
@@ -547,8 +554,9 @@ __global__ __launch_bounds__(AND_WG_THREADS, AND_WAVES_PER_SIMD) void k_search_a
         if (lane == 0) at = atomicAdd(emit_count + q, (unsigned long long)nc);
         const int64_t base_at = emit_prefix[q] + (int64_t)readlane64(at, 0);
         // a deleted doc travels with its sign bit set (search_phrase.hpp PHRASE_DEAD): no position check, but it counts as an approximation
-        if (a0) emit_docs[base_at + mbcnt(m0)] = doc_is_live(seg.live, d0) ? d0 : (d0 | (int32_t)0x80000000);
-        if (a1) emit_docs[base_at + n0c + mbcnt(m1)] = doc_is_live(seg.live, d1) ? d1 : (d1 | (int32_t)0x80000000);
+        // (LIVE_ONLY: every candidate that got here is live)
+        if (a0) emit_docs[base_at + mbcnt(m0)] = (LIVE_ONLY || doc_is_live(seg.live, d0)) ? d0 : (d0 | (int32_t)0x80000000);
+        if (a1) emit_docs[base_at + n0c + mbcnt(m1)] = (LIVE_ONLY || doc_is_live(seg.live, d1)) ? d1 : (d1 | (int32_t)0x80000000);
       }
       return;
     }

@@ -249,6 +249,7 @@ struct rgpu_ctx {
   int term_min_item_blocks = 64;  // ... and none of its items shorter than this (RGPU_TERM_MIN_ITEM_BLOCKS)
   int term_target_items = 3000;  // single-term launches: items of the launch's size, at most about this many (RGPU_TERM_TARGET_ITEMS in the environment)
   int term_split = 8;         // single-term queries: at least this many items per query, of 64 blocks or more each (RGPU_TERM_SPLIT in the environment; 1: off)
+  bool phrase_mask_compact = true;  // masked exact-phrase calls drop non-live candidates at emission (RGPU_PHRASE_MASK_COMPACT=0: they mark them, as the unmasked calls do; A/B, tests)
   bool memb_only_on = true;   // membership-only bits for sparse first clauses of conjunctions (RGPU_AND_MEMB_ONLY=0 in the environment: off; A/B, tests)
   bool term_sketches = true;  // block-max sketches for single-term queries (search_term.hpp); RGPU_TERM_SKETCH=0 in the environment turns them off (A/B, tests)
   DevVec<uint32_t> pos_counts;             // rgpu_decode_positions: positions per directory slot -> their exclusive prefix sums
@@ -1270,6 +1271,7 @@ extern "C" int32_t rgpu_init(int32_t device_ordinal, const rgpu_config* cfg, rgp
   if (const char* e = std::getenv("RGPU_TERM_SKETCH")) c->term_sketches = std::atoi(e) != 0;
   if (const char* e = std::getenv("RGPU_UPLOAD_ASIDE")) c->upload_aside = std::atoi(e) != 0;
   if (const char* e = std::getenv("RGPU_AND_MEMB_ONLY")) c->memb_only_on = std::atoi(e) != 0;
+  if (const char* e = std::getenv("RGPU_PHRASE_MASK_COMPACT")) c->phrase_mask_compact = std::atoi(e) != 0;
   if (const char* e = std::getenv("RGPU_TERM_TARGET_ITEMS")) c->term_target_items = std::max(256, std::atoi(e));
   if (const char* e = std::getenv("RGPU_HOST_TIME")) c->host_time = std::atoi(e) != 0;
   if (const char* e = std::getenv("RGPU_STAGE_COPY")) c->stage_by_kernel = std::strcmp(e, "dma") != 0;
@@ -3639,6 +3641,9 @@ struct AndEmitStage {
   // of it inside a kernel (the phrase-bool launch sequence).
   int64_t* redo_cap = nullptr;
   bool zero_keys = false;
+  // the masked exact-phrase calls (seg's live docs are `live AND set`): the LIVE_ONLY instantiation - a candidate that is not live is
+  // dropped, not marked; the slots behind the survivors stay unwritten, as the slots behind any query's count do
+  bool live_only = false;
 };
 static int32_t and_emit_stage(rgpu_segment* seg, hipStream_t stream, const AndEmitStage& a) {
   rgpu_ctx* c = seg->ctx;
@@ -3663,6 +3668,11 @@ static int32_t and_emit_stage(rgpu_segment* seg, hipStream_t stream, const AndEm
                 (const unsigned long long*)nullptr, (const int32_t*)nullptr, a.d_bm, xcd_chunk);
   };
   const bool legacy = seg->version < 1;
+  if (a.live_only) {
+    if (a.any_not) { if (legacy) go(k_search_and<true, false, true, false, false, true>); else go(k_search_and<false, false, true, false, false, true>); }
+    else { if (legacy) go(k_search_and<true, false, false, false, false, true>); else go(k_search_and<false, false, false, false, false, true>); }
+    return RGPU_OK;
+  }
   if (a.any_not) { if (legacy) go(k_search_and<true, false, true, false>); else go(k_search_and<false, false, true, false>); }
   else { if (legacy) go(k_search_and<true, false, false, false>); else go(k_search_and<false, false, false, false>); }
   return RGPU_OK;
@@ -4247,6 +4257,38 @@ static void docset_mark_in_flight(rgpu_docset* set, hipStream_t s) {
   else { (void)hipEventDestroy(ev); (void)hipStreamSynchronize(s); }
 }
 
+// The masked exact-phrase calls (rgpu_search_phrase_batch_masked, _phrase_bool_batch_masked, _phrase_or_batch_masked): what each does
+// under the context's mutex before its first launch - closures pending from earlier calls settled, `live AND set` formed (once, kept)
+// and installed for the rest of the call. `set` null: the unmasked call, nothing happens. The caller has refused sloppy phrases
+// already: an exact phrase under a mask is the phrase on a leaf whose live docs are the mask, a sloppy one is not (next_limit counts
+// deleted docs, not docs outside the filter).
+struct PhraseMask {
+  rgpu_segment* seg = nullptr;
+  rgpu_docset* set = nullptr;
+  ~PhraseMask() { if (seg) { seg->call_mask = nullptr; docset_mark_in_flight(set, seg->ctx->stream); } }
+  int32_t install(rgpu_segment* s, rgpu_docset* d) {
+    if (!d) return RGPU_OK;
+    rgpu_ctx* c = s->ctx;
+    RGPU_TRY(settle_pending(c));
+    const uint64_t* mask = nullptr;
+    RGPU_TRY(docset_mask_locked(s, d, &mask));
+    c->defer_or = false;  // a masked call never defers
+    s->call_mask = mask;
+    seg = s;
+    set = d;
+    return RGPU_OK;
+  }
+  bool on() const { return seg != nullptr; }
+};
+// the launch names of the candidate stage under a mask: the compacting instantiation's own, the marking one's own (RGPU_PHRASE_MASK_COMPACT=0);
+// rgpu_kernel_stat::name holds 47 characters
+static const char* masked_stage_name(const rgpu_ctx* c, const char* compact, const char* marked) { return c->phrase_mask_compact ? compact : marked; }
+static int32_t refuse_sloppy_masked(const rgpu_phrase_query* phrases, int32_t n) {
+  for (int32_t i = 0; i < n; ++i)
+    if (phrases[i].slop > 0) return fail(RGPU_ERR_UNSUPPORTED, "a sloppy phrase under a doc set is not served: next_limit counts deleted docs, not docs outside the filter");
+  return RGPU_OK;
+}
+
 extern "C" int32_t rgpu_search_batch_device_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_query* queries, int32_t n_queries,
                                                    const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, void* hits_dev,
                                                    void* totals_dev, void* hip_stream) {
@@ -4758,11 +4800,12 @@ static int32_t check_phrases_query(const rgpu_segment* seg, const BoolQuery& Q, 
   return RGPU_OK;
 }
 
-extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
-                                            const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
-                                            int64_t* total_hits_out) {
+static int32_t search_phrase_batch_impl(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_query* queries, int32_t n_queries,
+                                        const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
+                                        int64_t* total_hits_out) {
   if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !hits_out || !total_hits_out)
     return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  if (set) { RGPU_TRY(docset_check(seg, set)); RGPU_TRY(refuse_sloppy_masked(queries, n_queries)); }
   if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "phrase search: k must be in 1..RGPU_MAX_K");
   if (!seg->has_positions || !seg->d_pos) return fail(RGPU_ERR_ILLEGAL_STATE, "phrase search needs a positions field with its .pos file attached");
   rgpu_ctx* c = seg->ctx;
@@ -4775,6 +4818,8 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
     RGPU_TRY(check_phrase_query(c, queries[q], n_terms_total, true));
     RGPU_TRY(check_phrase_terms(seg, queries[q], terms, &ptrs));
   }
+  PhraseMask masked;
+  RGPU_TRY(masked.install(seg, set));
   RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
   // the conjunction that finds a phrase's candidates answers a dense clause from its doc bitmap, as a BooleanQuery's does
   int64_t bitmap_df = INT64_MAX;
@@ -4868,10 +4913,13 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
     const bool chunked = phrase_collect_chunked(k, collect_items);
     int64_t redo_cap = 0;
     // (k_emit: the conjunction only emits candidates, its (empty) top-k lists are the narrow kind)
-    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{"k_search_and(phrase candidates)", d_q, d_t, sg.dev(r_ip), d_ep, clause_bitmaps.empty() ? nullptr : sg.dev(r_bm),
+    const char* stage_name = masked.on() ? masked_stage_name(c, "k_search_and(masked phrase candidates)", "k_search_and(masked phrase, marked)")
+                                         : "k_search_and(phrase candidates)";
+    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{stage_name, d_q, d_t, sg.dev(r_ip), d_ep, clause_bitmaps.empty() ? nullptr : sg.dev(r_bm),
                                                       n_queries, nq, items, slots, blocks_per_item, std::min<int>(k, 64), false,
                                                       chunked ? (size_t)collect_items * (size_t)k : 0, chunked ? (size_t)collect_items : 0,
-                                                      &redo_cap, false /* the collectors read a query's first emit_count slots only */}));
+                                                      &redo_cap, false /* the collectors read a query's first emit_count slots only */,
+                                                      masked.on() && c->phrase_mask_compact}));
     RGPU_TRY(phrase_match_stage(seg, stream, PhraseMatchStage{d_q, d_t, sg.dev(r_pt), d_ep, d_sl, sg.dev(r_gr), n_queries, slots, redo_cap, any_exact, any_sloppy,
                                                               sloppy_rpts, true, d_cut, d_cp, d_nl, collect_items}));
     phrase_collect_stage(seg, stream, PhraseCollectStage{d_ep, d_cp, d_sl, d_nl, n_queries, k, collect_items, any_cutoff, sg.dev(r_ab), d_cut});
@@ -4882,6 +4930,17 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
   RGPU_TRY(api_rows_read_back(c, stream, n_queries, k, hits_out, total_hits_out, items > 0 ? &err : nullptr));
   return phrase_match_status(err, "a doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)",
                              "internal: a conjunction match was not found again");
+}
+extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
+                                            const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
+                                            int64_t* total_hits_out) {
+  return search_phrase_batch_impl(seg, nullptr, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out);
+}
+extern "C" int32_t rgpu_search_phrase_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_query* queries, int32_t n_queries,
+                                                   const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
+                                                   int64_t* total_hits_out) {
+  if (!set) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  return search_phrase_batch_impl(seg, set, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out);
 }
 
 // ---- BooleanQuery with exact PhraseQuery clauses among its required clauses: +"a b" +c -d #e ------------------------------------
@@ -4899,14 +4958,15 @@ extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase
 // Unsupported shapes (see the header): sloppy clauses, phrases under SHOULD / MUST_NOT, SHOULD clauses or nested BooleanQuery clauses
 // beside a phrase, more than RGPU_MAX_BOOL_PHRASES phrases.
 static_assert(PHRASE_BOOL_MAX_PLANES == RGPU_MAX_BOOL_PHRASES, "k_phrase_bool_score keeps one key per plane in registers");
-extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_phrase_bool_query* queries, int32_t n_queries,
-                                                 const rgpu_phrase_query* phrases, int32_t n_phrases_total,
-                                                 const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
-                                                 const rgpu_query_term* terms, int32_t n_terms_total,
-                                                 int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
+static int32_t search_phrase_bool_batch_impl(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_bool_query* queries, int32_t n_queries,
+                                             const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                             const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                             const rgpu_query_term* terms, int32_t n_terms_total,
+                                             int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
   if (!seg || !queries || n_queries <= 0 || !phrases || n_phrases_total <= 0 || !phrase_terms || n_phrase_terms_total <= 0 || n_terms_total < 0 ||
       (n_terms_total > 0 && !terms) || !hits_out || !total_hits_out)
     return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  if (set) RGPU_TRY(docset_check(seg, set));
   if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "boolean query over phrases: k must be in 1..RGPU_MAX_K");
   if (!seg->has_positions || !seg->d_pos) return fail(RGPU_ERR_ILLEGAL_STATE, "a boolean query over phrases needs a positions field with its .pos file attached");
   rgpu_ctx* c = seg->ctx;
@@ -4928,6 +4988,8 @@ extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_p
     if (P.status != RGPU_OK) return fail(P.status, P.why);
     if (!P.dead) { max_planes = std::max(max_planes, (int)Q.n_phrases); any_not = any_not || !P.must_not.empty(); }
   }
+  PhraseMask masked;
+  RGPU_TRY(masked.install(seg, set));
   RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
   // the candidate conjunction answers a dense clause from its doc bitmap, as a phrase search's does
   int64_t bitmap_df = INT64_MAX;
@@ -5036,9 +5098,12 @@ extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_p
     const bool chunked = phrase_collect_chunked(k, collect_items);
     int64_t redo_cap = 0;  // (sized from the slots of ALL planes: any of them may hand candidates on)
     // (the conjunctions: one per query, plane 0; slots and counts: every plane's - k_phrase_bool_fanout fills the others)
-    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{"k_search_and(phrase-bool candidates)", sg.dev(r_cq), sg.dev(r_cdt), sg.dev(r_ip), d_ep,
+    const char* stage_name = masked.on() ? masked_stage_name(c, "k_search_and(masked phrase-bool candidates)", "k_search_and(masked phrase-bool, marked)")
+                                         : "k_search_and(phrase-bool candidates)";
+    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{stage_name, sg.dev(r_cq), sg.dev(r_cdt), sg.dev(r_ip), d_ep,
                                                       clause_bitmaps.empty() ? nullptr : sg.dev(r_bm), n_queries, nv, items, slots, blocks_per_item, std::min<int>(k, 64),
-                                                      any_not, chunked ? (size_t)collect_items * (size_t)k : 0, chunked ? (size_t)collect_items : 0, &redo_cap, true}));
+                                                      any_not, chunked ? (size_t)collect_items * (size_t)k : 0, chunked ? (size_t)collect_items : 0, &redo_cap, true,
+                                                      masked.on() && c->phrase_mask_compact}));
     const unsigned ggrid = wg_count((groups0 + WG_WAVES - 1) / WG_WAVES);
     if (groups0 > 0 && max_planes > 1) {
       TimedLaunch tl(c, stream, "k_phrase_bool_fanout", 0);
@@ -5063,6 +5128,23 @@ extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_p
   }
   return api_rows_read_back(c, stream, n_queries, k, hits_out, total_hits_out);
 }
+extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_phrase_bool_query* queries, int32_t n_queries,
+                                                 const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                                 const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                                 const rgpu_query_term* terms, int32_t n_terms_total,
+                                                 int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
+  return search_phrase_bool_batch_impl(seg, nullptr, queries, n_queries, phrases, n_phrases_total, phrase_terms, n_phrase_terms_total, terms, n_terms_total, k,
+                                       hits_out, total_hits_out);
+}
+extern "C" int32_t rgpu_search_phrase_bool_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_bool_query* queries, int32_t n_queries,
+                                                        const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                                        const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                                        const rgpu_query_term* terms, int32_t n_terms_total,
+                                                        int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
+  if (!set) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  return search_phrase_bool_batch_impl(seg, set, queries, n_queries, phrases, n_phrases_total, phrase_terms, n_phrase_terms_total, terms, n_terms_total, k,
+                                       hits_out, total_hits_out);
+}
 
 // ---- BooleanQuery of SHOULD / MUST_NOT clauses with exact PhraseQuery clauses among the SHOULD ones: "a b" "c d" e -f -------------
 // (include/rucene_gpu.h rgpu_search_phrase_or_batch; the plan: host/phrase_or_plan.hpp; the run-building kernels:
@@ -5079,14 +5161,15 @@ extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_p
 //   4. k > RGPU_PASS_K: step 3 once per pass of 128 hits, as search_impl runs its passes (rgpu_ctx::Pass, ceiling slots). The keys of
 //      step 2 stay in c->phrase_keys; what the run-building kernels read besides lives in buffers of the context's, not in the scratch
 //      slot that staged steps 1-2 (four passes later that slot is somebody else's).
-extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phrase_or_query* queries, int32_t n_queries,
-                                               const rgpu_phrase_query* phrases, int32_t n_phrases_total,
-                                               const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
-                                               const rgpu_query_term* terms, int32_t n_terms_total,
-                                               int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
+static int32_t search_phrase_or_batch_impl(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_or_query* queries, int32_t n_queries,
+                                           const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                           const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                           const rgpu_query_term* terms, int32_t n_terms_total,
+                                           int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
   if (!seg || !queries || n_queries <= 0 || !phrases || n_phrases_total <= 0 || !phrase_terms || n_phrase_terms_total <= 0 || n_terms_total < 0 ||
       (n_terms_total > 0 && !terms) || !hits_out || !total_hits_out)
     return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  if (set) RGPU_TRY(docset_check(seg, set));
   if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "disjunction over phrases: k must be in 1..RGPU_MAX_K");
   if (!seg->has_positions || !seg->d_pos) return fail(RGPU_ERR_ILLEGAL_STATE, "a disjunction over phrases needs a positions field with its .pos file attached");
   rgpu_ctx* c = seg->ctx;
@@ -5106,6 +5189,8 @@ extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phr
     if (plans[(size_t)q].status != RGPU_OK) return fail(plans[(size_t)q].status, plans[(size_t)q].why);
     first_virtual[(size_t)q + 1] = first_virtual[(size_t)q] + Q.n_phrases;
   }
+  PhraseMask masked;  // (installed for the whole call: every pass of k > RGPU_PASS_K runs under it)
+  RGPU_TRY(masked.install(seg, set));
   RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
   // the candidate conjunctions answer a dense clause from its doc bitmap, as a phrase search's do
   int64_t bitmap_df = INT64_MAX;
@@ -5218,9 +5303,11 @@ extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phr
     RGPU_TRY(sg.upload(stream));
     int64_t redo_cap = 0;
     // (one conjunction per virtual query; the MUST_NOT clauses belong to the disjunction, step 3; nothing is collected here)
-    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{"k_search_and(phrase-or candidates)", sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ip), sg.dev(r_ep),
+    const char* stage_name = masked.on() ? masked_stage_name(c, "k_search_and(masked phrase-or candidates)", "k_search_and(masked phrase-or, marked)")
+                                         : "k_search_and(phrase-or candidates)";
+    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{stage_name, sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ip), sg.dev(r_ep),
                                                       clause_bitmaps.empty() ? nullptr : sg.dev(r_bm), (int32_t)nv, nv, items, slots, blocks_per_item,
-                                                      std::min<int>(k, 64), false, 0, 0, &redo_cap, true}));
+                                                      std::min<int>(k, 64), false, 0, 0, &redo_cap, true, masked.on() && c->phrase_mask_compact}));
     RGPU_TRY(phrase_match_stage(seg, stream, PhraseMatchStage{sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ppt), sg.dev(r_ep), sg.dev(r_sl), sg.dev(r_gr), (int32_t)nv, slots,
                                                               redo_cap, true, false, false, false, nullptr, nullptr, nullptr, 0}));
     HIP_TRY(launch_status());
@@ -5300,6 +5387,23 @@ extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phr
   if (rc != RGPU_OK) { (void)hipStreamSynchronize(stream); return rc; }
   HIP_TRY(launch_status());
   return api_rows_read_back(c, stream, n_queries, k, hits_out, total_hits_out);
+}
+extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phrase_or_query* queries, int32_t n_queries,
+                                               const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                               const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                               const rgpu_query_term* terms, int32_t n_terms_total,
+                                               int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
+  return search_phrase_or_batch_impl(seg, nullptr, queries, n_queries, phrases, n_phrases_total, phrase_terms, n_phrase_terms_total, terms, n_terms_total, k,
+                                     hits_out, total_hits_out);
+}
+extern "C" int32_t rgpu_search_phrase_or_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_or_query* queries, int32_t n_queries,
+                                                      const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                                      const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                                      const rgpu_query_term* terms, int32_t n_terms_total,
+                                                      int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
+  if (!set) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
+  return search_phrase_or_batch_impl(seg, set, queries, n_queries, phrases, n_phrases_total, phrase_terms, n_phrase_terms_total, terms, n_terms_total, k,
+                                     hits_out, total_hits_out);
 }
 
 // ---- QueryRescorer ------------------------------------------------------------------------------------------------------------

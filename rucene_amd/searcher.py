@@ -259,7 +259,8 @@ class PointRangeQuery:
     bytes; IntPoint / LongPoint / FloatPoint / DoublePoint below build them); a query built with num_dims > 1 is
     UnsupportedOperation (what it matches depends on the BKD cell layout: include/rucene_gpu.h). It does not score: ConstantScoreScorer(0.0) under
     MUST and FILTER alike (PointRangeWeight::new :482 — nothing normalises the weight), so GpuIndexSearcher turns the clause into
-    a doc set (range_filter) and searches masked; under SHOULD, alone, or beside a phrase it is UnsupportedOperation."""
+    a doc set (range_filter) and searches masked; under SHOULD, alone, or beside a phrase (unless the searcher was made with
+    filtered_phrases=True and the phrase is exact) it is UnsupportedOperation."""
 
     def __init__(self, field, lower_bytes, upper_bytes, num_dims=1):
         self.field, self.lower, self.upper, self.num_dims = str(field), bytes(lower_bytes), bytes(upper_bytes), int(num_dims)
@@ -347,7 +348,8 @@ class CachedFilter:
 class FilterQuery:
     """query/filter_query.rs:155-233: `query`'s docs and scores, restricted to the docs every one of `filters` (CachedFilter)
     holds. Served by the GPU path when `query` is a term / boolean / dismax / boosting query (rgpu_search_batch_masked); a phrase
-    underneath is UnsupportedOperation, i.e. the caller's CPU path."""
+    underneath is UnsupportedOperation, i.e. the caller's CPU path, unless the searcher was made with filtered_phrases=True (exact
+    phrases and the boolean queries over them then go through the masked phrase calls)."""
 
     def __init__(self, query, filters):
         self.query, self.filters = query, list(filters)
@@ -647,12 +649,18 @@ class GpuIndexSearcher:
 
     range_filter_capacity = 256   # memoised range filters kept from one search_batch to the next (range_filter); set per searcher
 
-    def __init__(self, leaves, ctx=None, similarity=None, next_limit=None, flatten_nested=False, cpu_fallback=None):
-        """flatten_nested: fold one level of nested BooleanQuery clauses (BooleanQuery.flattened: same docs and counts, scores
+    def __init__(self, leaves, ctx=None, similarity=None, next_limit=None, flatten_nested=False, cpu_fallback=None, filtered_phrases=False):
+        """filtered_phrases: serve EXACT phrases beside doc-set clauses - FilterQuery("a b", F), +"a b" #F -X, +"a b" +c #F -X,
+        "a b" c -X with min_should_match <= 1, point ranges in those positions - through rgpu_search_phrase_batch_masked,
+        _phrase_bool_batch_masked and _phrase_or_batch_masked (off by default: such rows are UnsupportedOperation, as they have been).
+        Still refused with it on: any sloppy phrase under a mask, "a b" c #F (the doc set is the only required clause), -X beside
+        min_should_match >= 2, and whatever phrase_bool_parts / phrase_or_parts refuse.
+        flatten_nested: fold one level of nested BooleanQuery clauses (BooleanQuery.flattened: same docs and counts, scores
         within 1e-5 of the reference's — off by default because it is not bit-exact). cpu_fallback(query, collector): what
         SURVEY 8(f)1 calls "everything else to the CPU path" — search() hands every tree the GPU path does not serve
         (UnsupportedOperation) to it, as the Rust shim hands them to DefaultIndexSearcher (rust/gpu/searcher.rs); None: raise."""
         self.flatten_nested = bool(flatten_nested)
+        self.filtered_phrases = bool(filtered_phrases)
         self.cpu_fallback = cpu_fallback
         self.leaves = list(leaves)
         # DefaultIndexSearcher::new(reader, next_limit: Option<usize>) (searcher.rs:291-296, :361): how many approximations of a
@@ -1181,13 +1189,24 @@ class GpuIndexSearcher:
             for key in [k for k in self._masks if id(gone) in k[0] or id(gone) in k[1]]:
                 del self._masks[key]
 
+    def _filtered_phrase(self, rest):
+        """A phrase, or a BooleanQuery over phrases, left under a mask: served when the searcher opted in (filtered_phrases) and every
+        phrase is exact - on a leaf whose live docs are live AND filters AND NOT excludes an exact phrase collects the reference's docs,
+        counts and scores, a sloppy one does not (next_limit counts deleted docs, not docs outside a filter)."""
+        if not getattr(self, "filtered_phrases", False) or (isinstance(rest, PhraseQuery) and rest.slop > 0):
+            raise RgpuError(-5, "a filtered phrase is not served by the GPU path")
+        if isinstance(rest, BooleanQuery):   # (their refusals: sloppy clauses, nested clauses, SHOULD beside a required phrase ...)
+            (self.phrase_bool_parts if (rest.must_queries or rest.filter_queries) else self.phrase_or_parts)(rest)
+
     def _peel(self, query, build=True):
         """query -> (the query without its doc-set clauses, (FILTER CachedFilters, MUST_NOT CachedFilters)). The rest, searched on
         live docs AND filters AND NOT excludes, collects the reference's docs, counts and f32 scores when (1) it contributes a MUST
         or FILTER clause of its own — "b c #F" is ReqOptScorer(F, b | c) in the reference and matches ALL of F, a lone #F likewise —
         and (2) for -X, min_should_match <= 1 (boolean_query.rs:235-251 reuses it for the MUST_NOT union). FilterQuery(Q, F) asks
-        only that Q has a scorer of its own. Phrases are not served under a mask (a sloppy phrase's next_limit counts deleted docs,
-        not docs outside a filter; the phrase entry points have no masked form). Anything else: UnsupportedOperation.
+        only that Q has a scorer of its own. Phrases are not served under a mask unless the searcher opted in (filtered_phrases), and
+        then exact ones only (a sloppy phrase's next_limit counts deleted docs, not docs outside a filter); with the opt-in
+        "a b" c -X (min_should_match <= 1) is served too: ReqNotScorer over the disjunction, whose phrase clause is a scorer of its own.
+        Anything else: UnsupportedOperation.
         A PointRangeQuery under MUST / FILTER / MUST_NOT is checked first (dimensions, field, width), the rules above are applied, and
         only then is its doc set built; build=False stops short of that (the sets are then the queries themselves) — search_batch
         runs it over the whole batch first, so a refused row launches nothing. min_should_match stays the query's own: "+range #a b"
@@ -1195,7 +1214,7 @@ class GpuIndexSearcher:
         if isinstance(query, FilterQuery):
             inner, (f, x) = self._peel(query.query, build)
             if isinstance(inner, PhraseQuery) or (isinstance(inner, BooleanQuery) and inner.has_phrases()):
-                raise RgpuError(-5, "a filtered phrase is not served by the GPU path")
+                self._filtered_phrase(inner)
             return inner, (f + list(query.filters), x)
         if isinstance(query, PointRangeQuery):
             raise RgpuError(-5, "a lone point range is not served by the GPU path (the reference matches all of it)")
@@ -1210,7 +1229,8 @@ class GpuIndexSearcher:
         musts = [q for q in query.must_queries if not isinstance(q, sets)]
         filters = [q for q in query.filter_queries if not isinstance(q, sets)]
         must_nots = [q for q in query.must_not_queries if not isinstance(q, sets)]
-        if not (musts or filters):
+        phrase_or = getattr(self, "filtered_phrases", False) and not f and any(isinstance(q, PhraseQuery) for q in query.should_queries)
+        if not (musts or filters) and not phrase_or:
             raise RgpuError(-5, "a doc set as the only required clause is not served by the GPU path (the reference matches all of it)")
         if x and query.min_should_match > 1:
             raise RgpuError(-5, "a MUST_NOT doc set beside min_should_match >= 2 is not served by the GPU path")
@@ -1220,7 +1240,7 @@ class GpuIndexSearcher:
             # (the peeled clauses were the only MUST ones: build() has derived the default of a query without MUST clauses)
             rest = BooleanQuery(musts, list(query.should_queries), query.min_should_match, must_nots, filters)
         if isinstance(rest, PhraseQuery) or (isinstance(rest, BooleanQuery) and rest.has_phrases()):
-            raise RgpuError(-5, "a filtered phrase is not served by the GPU path")
+            self._filtered_phrase(rest)
         if build:
             made = iter(self._range_filters_for([q for q in f + x if isinstance(q, PointRangeQuery)]))
             f = [next(made) if isinstance(q, PointRangeQuery) else q for q in f]
@@ -1249,7 +1269,7 @@ class GpuIndexSearcher:
         required clauses (rgpu_search_phrase_bool_batch) and BooleanQuery rows of SHOULD / MUST_NOT clauses with phrases among the
         SHOULD ones (rgpu_search_phrase_or_batch): one call per kind and leaf, rows keep their order. Rows with doc-set clauses
         (CachedFilter under FILTER / MUST_NOT, FilterQuery) are grouped by their combination of sets and searched masked
-        (rgpu_search_batch_masked), one call per group and leaf."""
+        (rgpu_search_batch_masked; with filtered_phrases the phrase kinds through their masked calls), one call per group, kind and leaf."""
         for q in queries:   # refused before any leaf is touched and before any range's set is built
             self._peel(q, build=False)
         if getattr(self, "_range_filters", None):   # (a batch on a searcher that never built a range filter goes the way it went)
@@ -1286,7 +1306,7 @@ class GpuIndexSearcher:
                 qs, ts = self.pack(queries, leaf)
                 per_leaf.append(leaf.segment.search_batch(qs, ts, k) if masks is None else leaf.segment.search_batch_masked(masks[i], qs, ts, k))
         else:
-            if masks is not None:
+            if masks is not None and (not getattr(self, "filtered_phrases", False) or any(q.slop > 0 for q in queries if isinstance(q, PhraseQuery))):
                 raise RgpuError(-5, "a filtered phrase is not served by the GPU path")
             rows = [np.flatnonzero(np.array(kinds) == kd) for kd in (0, 1, 2, 3)]
             groups = [[queries[i] for i in r] for r in rows]
@@ -1295,18 +1315,23 @@ class GpuIndexSearcher:
             for q in groups[3]:
                 self.phrase_or_parts(q)
             per_leaf = []
-            for leaf in self.leaves:
+            for i, leaf in enumerate(self.leaves):
                 hits, totals = np.zeros((len(queries), k), dtype=_lib.HIT_DTYPE), np.zeros(len(queries), dtype=np.int64)
+                seg = leaf.segment
                 if groups[0]:
                     qs, ts = self.pack(groups[0], leaf)
-                    hits[rows[0]], totals[rows[0]] = leaf.segment.search_batch(qs, ts, k)
+                    hits[rows[0]], totals[rows[0]] = seg.search_batch(qs, ts, k) if masks is None else seg.search_batch_masked(masks[i], qs, ts, k)
                 if groups[1]:
                     qs, ts = self.pack_phrases(groups[1], leaf)
-                    hits[rows[1]], totals[rows[1]] = leaf.segment.search_phrase_batch(qs, ts, k)
+                    hits[rows[1]], totals[rows[1]] = seg.search_phrase_batch(qs, ts, k) if masks is None else seg.search_phrase_batch_masked(masks[i], qs, ts, k)
                 if groups[2]:
-                    hits[rows[2]], totals[rows[2]] = leaf.segment.search_phrase_bool_batch(*self.pack_phrase_bool(groups[2], leaf), k)
+                    packed = self.pack_phrase_bool(groups[2], leaf)
+                    hits[rows[2]], totals[rows[2]] = (seg.search_phrase_bool_batch(*packed, k) if masks is None
+                                                      else seg.search_phrase_bool_batch_masked(masks[i], *packed, k))
                 if groups[3]:
-                    hits[rows[3]], totals[rows[3]] = leaf.segment.search_phrase_or_batch(*self.pack_phrase_or(groups[3], leaf), k)
+                    packed = self.pack_phrase_or(groups[3], leaf)
+                    hits[rows[3]], totals[rows[3]] = (seg.search_phrase_or_batch(*packed, k) if masks is None
+                                                      else seg.search_phrase_or_batch_masked(masks[i], *packed, k))
                 per_leaf.append((hits, totals))
         return per_leaf
 

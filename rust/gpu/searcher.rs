@@ -138,6 +138,12 @@ pub struct GpuIndexSearcher<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: De
     /// Fold ONE level of nested BooleanQuery into its parent (see flatten). Off by default, as in the C++ and Python mirrors
     /// (flatten_nested = false): the folded f32 sum is within 1e-5 of the CPU's, not bit-equal.
     allow_flatten: bool,
+    /// try_filtered serves EXACT phrases — a PhraseQuery, a BooleanQuery over phrases — through rgpu_search_phrase_batch_masked,
+    /// rgpu_search_phrase_bool_batch_masked and rgpu_search_phrase_or_batch_masked instead of leaving them to the CPU searcher. Off by
+    /// default, as `filtered_phrases` of the Python and C++ mirrors. Still the CPU's with it on: any sloppy phrase under a mask (its
+    /// next_limit counts deleted docs, not docs outside a filter), "\"a b\" c #F" (the doc set is the only required clause), a MUST_NOT
+    /// set beside min_should_match >= 2, and whatever try_phrase_bool / try_phrase_or leave to it.
+    pub filtered_phrases: bool,
 }
 
 unsafe impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: SimilarityProducer<C>> Send for GpuIndexSearcher<C, R, IR, SP> {}
@@ -171,7 +177,7 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             leaves.push(GpuLeaf { seg, has_positions: pos.is_some() });
         }
         let next_limit = match next_limit { None => 0, Some(0) => RGPU_NEXT_LIMIT_ZERO, Some(n) => n.min(i32::max_value() as usize) as i32 };
-        Ok(GpuIndexSearcher { cpu, ctx, field: field.to_string(), leaves, sim_tables: Mutex::new(HashMap::new()), next_limit, allow_flatten })
+        Ok(GpuIndexSearcher { cpu, ctx, field: field.to_string(), leaves, sim_tables: Mutex::new(HashMap::new()), next_limit, allow_flatten, filtered_phrases: false })
     }
 
     /// BooleanQuery trees the C ABI serves, flattened to one clause list (query/boolean_query.rs:195-279 is what the CPU builds
@@ -393,13 +399,13 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
 
     fn try_gpu(&self, query: &dyn Query<C>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
         if k == 0 || k > RGPU_MAX_K as usize { return Ok(false); }
-        if let Some(p) = query.as_any().downcast_ref::<PhraseQuery>() { return self.try_phrase(p, top, k); }
+        if let Some(p) = query.as_any().downcast_ref::<PhraseQuery>() { return self.try_phrase(p, None, top, k); }
         if let Some(b) = query.as_any().downcast_ref::<BooleanQuery<C>>() {
             let (must, should, filter, must_not, _) = b.clauses();
             if must.iter().chain(should).chain(filter).chain(must_not).any(|q| q.as_any().downcast_ref::<PhraseQuery>().is_some()) {
                 // no MUST and no FILTER clause: one DisjunctionSumScorer over the SHOULD clauses; else the conjunction's rules decide
-                if must.is_empty() && filter.is_empty() { return self.try_phrase_or(b, top, k); }
-                return self.try_phrase_bool(b, top, k);
+                if must.is_empty() && filter.is_empty() { return self.try_phrase_or(b, None, top, k); }
+                return self.try_phrase_bool(b, None, top, k);
             }
         }
         let flat = match self.flatten(query) { Some(f) => f, None => return Ok(false) };
@@ -474,10 +480,11 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
     /// weight = summed idf x boost as PhraseQuery::create_weight (phrase_query.rs:136-186; its boost is 1.0). Per leaf as
     /// PhraseWeight::create_scorer (:268-333): a term absent from the leaf -> no scorer for that leaf (doc_freq = 0 tells the
     /// library the same); slop 0 -> ExactPhraseScorer, slop > 0 -> SloppyPhraseScorer under the searcher's next_limit.
-    fn try_phrase(&self, p: &PhraseQuery, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
+    /// `masks` (try_filtered: one doc set per leaf, by LeafReaderContext::ord): the search restricted to them, exact phrases only.
+    fn try_phrase(&self, p: &PhraseQuery, masks: Option<&[*mut RgpuDocset]>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
         let (field, terms, positions, slop) = p.parts();
         if field != self.field || terms.len() < 2 || terms.len() > RGPU_MAX_PHRASE_TERMS as usize || terms.len() != positions.len()
-            || self.leaves.iter().any(|l| !l.has_positions) {
+            || self.leaves.iter().any(|l| !l.has_positions) || (masks.is_some() && slop != 0) {
             return Ok(false);
         }
         let term_refs: Vec<&Term> = terms.iter().collect();
@@ -487,8 +494,13 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             let q = RgpuPhraseQuery { n_terms: pterms.len() as i32, first_term: 0, weight, sim_table, slop, next_limit: self.next_limit };
             let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
             let mut total: i64 = 0;
-            check(unsafe { rgpu_search_phrase_batch(self.leaves[leaf.ord].seg, &q, 1, pterms.as_ptr(), pterms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total) },
-                  self.ctx)?;
+            let seg = self.leaves[leaf.ord].seg;
+            check(unsafe {
+                match masks {
+                    Some(m) => rgpu_search_phrase_batch_masked(seg, m[leaf.ord], &q, 1, pterms.as_ptr(), pterms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total),
+                    None => rgpu_search_phrase_batch(seg, &q, 1, pterms.as_ptr(), pterms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total),
+                }
+            }, self.ctx)?;
             Self::hand_over(top, &hits, total);
         }
         Ok(true)
@@ -502,7 +514,8 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
     /// phrase of the wrong size) and for every shape the library does not serve: a sloppy phrase clause (inside a conjunction the CPU
     /// matches it on its approximation and scores a stale sloppy_freq), a phrase under SHOULD or MUST_NOT, a SHOULD clause or a
     /// nested BooleanQuery beside a phrase, more than RGPU_MAX_BOOL_PHRASES phrases, more than RGPU_MAX_QUERY_TERMS clause terms.
-    fn try_phrase_bool(&self, b: &BooleanQuery<C>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
+    /// `masks` as for try_phrase: rgpu_search_phrase_bool_batch_masked.
+    fn try_phrase_bool(&self, b: &BooleanQuery<C>, masks: Option<&[*mut RgpuDocset]>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
         let (must, should, filter, must_not, _) = b.clauses();
         if !should.is_empty() || self.leaves.iter().any(|l| !l.has_positions) { return Ok(false); }
         let term_of = |q: &Box<dyn Query<C>>| q.as_any().downcast_ref::<TermQuery>().filter(|t| t.term.field == self.field);
@@ -562,9 +575,16 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             }
             let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
             let mut total: i64 = 0;
-            check(unsafe { rgpu_search_phrase_bool_batch(self.leaves[leaf.ord].seg, &bq, 1, pqs.as_ptr(), pqs.len() as i32, pterms.as_ptr(), pterms.len() as i32,
-                                                         if terms.is_empty() { std::ptr::null() } else { terms.as_ptr() }, terms.len() as i32, k as i32,
-                                                         hits.as_mut_ptr(), &mut total) }, self.ctx)?;
+            let seg = self.leaves[leaf.ord].seg;
+            let terms_ptr = if terms.is_empty() { std::ptr::null() } else { terms.as_ptr() };
+            check(unsafe {
+                match masks {
+                    Some(m) => rgpu_search_phrase_bool_batch_masked(seg, m[leaf.ord], &bq, 1, pqs.as_ptr(), pqs.len() as i32, pterms.as_ptr(), pterms.len() as i32,
+                                                                    terms_ptr, terms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total),
+                    None => rgpu_search_phrase_bool_batch(seg, &bq, 1, pqs.as_ptr(), pqs.len() as i32, pterms.as_ptr(), pterms.len() as i32,
+                                                          terms_ptr, terms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total),
+                }
+            }, self.ctx)?;
             Self::hand_over(top, &hits, total);
         }
         Ok(true)
@@ -578,7 +598,8 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
     /// a leaf without positions, a phrase of the wrong size) and for every shape the library does not serve: a sloppy phrase clause
     /// (two-phase), ten or more SHOULD clauses (the heap-order arm), a phrase under MUST_NOT, a nested BooleanQuery, more than
     /// RGPU_MAX_BOOL_PHRASES phrases, more than RGPU_MAX_QUERY_TERMS clause terms.
-    fn try_phrase_or(&self, b: &BooleanQuery<C>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
+    /// `masks` as for try_phrase: rgpu_search_phrase_or_batch_masked.
+    fn try_phrase_or(&self, b: &BooleanQuery<C>, masks: Option<&[*mut RgpuDocset]>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
         let (must, should, filter, must_not, min_should_match) = b.clauses();
         if !must.is_empty() || !filter.is_empty() || should.is_empty() || should.len() > 9 || min_should_match < 0 || min_should_match > 255
             || self.leaves.iter().any(|l| !l.has_positions) {
@@ -636,9 +657,16 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             }
             let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
             let mut total: i64 = 0;
-            check(unsafe { rgpu_search_phrase_or_batch(self.leaves[leaf.ord].seg, &oq, 1, pqs.as_ptr(), pqs.len() as i32, pterms.as_ptr(), pterms.len() as i32,
-                                                       if terms.is_empty() { std::ptr::null() } else { terms.as_ptr() }, terms.len() as i32, k as i32,
-                                                       hits.as_mut_ptr(), &mut total) }, self.ctx)?;
+            let seg = self.leaves[leaf.ord].seg;
+            let terms_ptr = if terms.is_empty() { std::ptr::null() } else { terms.as_ptr() };
+            check(unsafe {
+                match masks {
+                    Some(m) => rgpu_search_phrase_or_batch_masked(seg, m[leaf.ord], &oq, 1, pqs.as_ptr(), pqs.len() as i32, pterms.as_ptr(), pterms.len() as i32,
+                                                                  terms_ptr, terms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total),
+                    None => rgpu_search_phrase_or_batch(seg, &oq, 1, pqs.as_ptr(), pqs.len() as i32, pterms.as_ptr(), pterms.len() as i32,
+                                                        terms_ptr, terms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total),
+                }
+            }, self.ctx)?;
             Self::hand_over(top, &hits, total);
         }
         Ok(true)
@@ -743,12 +771,16 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
     /// has a scorer of its own; otherwise the sets are FILTER / MUST_NOT clauses of the BooleanQuery `query` was taken out of, and the
     /// rows are the reference's only when (1) what is left contributes a MUST or FILTER clause — "b c #F" is ReqOptScorer(F, b | c) in
     /// the reference and matches ALL of F — and (2) for a MUST_NOT set, min_should_match <= 1 (boolean_query.rs:235-251 reuses it for
-    /// the MUST_NOT union). Ok(false): not served here — the CPU searcher takes the whole query (phrases have no masked entry point:
-    /// a sloppy phrase's next_limit counts deleted docs, not docs outside a filter).
+    /// the MUST_NOT union). Ok(false): not served here — the CPU searcher takes the whole query. A phrase, or a tree over phrases, is
+    /// the CPU's unless `filtered_phrases` is set (try_filtered_phrase; never a sloppy one: its next_limit counts deleted docs, not
+    /// docs outside a filter).
     pub fn try_filtered(&self, query: &dyn Query<C>, filters: &[&GpuCachedFilter], excludes: &[&GpuCachedFilter], as_filter_query: bool,
                         top: &mut TopDocsCollector, k: usize) -> Result<bool> {
         if k == 0 || k > RGPU_MAX_K as usize || (filters.is_empty() && excludes.is_empty()) { return Ok(false); }
         if filters.iter().chain(excludes.iter()).any(|f| f.sets.len() != self.leaves.len()) { bail!(ErrorKind::IllegalArgument("a cached filter of another searcher".into())); }
+        if self.filtered_phrases {
+            if let Some(served) = self.try_filtered_phrase(query, filters, excludes, as_filter_query, top, k)? { return Ok(served); }
+        }
         let flat = match self.flatten(query) { Some(f) => f, None => return Ok(false) }; // (a PhraseQuery, a tree over phrases: not flat)
         let base = flat.op & 0xff;
         let msm = (flat.op >> 8) & 0xff;
@@ -783,6 +815,49 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             Self::hand_over(top, &hits, total);
         }
         Ok(true)
+    }
+
+    /// try_filtered for a PhraseQuery or a BooleanQuery with PhraseQuery clauses (`filtered_phrases`): None — `query` is neither;
+    /// Some(false) — the CPU searcher; Some(true) — collected through the masked phrase calls, one per leaf. The rules: a required
+    /// phrase (alone, or among MUST / FILTER clauses) under either spelling; a disjunction over phrases under FilterQuery, or beside
+    /// MUST_NOT sets only with min_should_match <= 1 ("\"a b\" c #F": the set is the only required clause and the reference matches
+    /// all of it).
+    fn try_filtered_phrase(&self, query: &dyn Query<C>, filters: &[&GpuCachedFilter], excludes: &[&GpuCachedFilter], as_filter_query: bool,
+                           top: &mut TopDocsCollector, k: usize) -> Result<Option<bool>> {
+        let phrase = query.as_any().downcast_ref::<PhraseQuery>();
+        let tree = query.as_any().downcast_ref::<BooleanQuery<C>>().filter(|b| {
+            let (must, should, filter, must_not, _) = b.clauses();
+            must.iter().chain(should).chain(filter).chain(must_not).any(|q| q.as_any().downcast_ref::<PhraseQuery>().is_some())
+        });
+        if phrase.is_none() && tree.is_none() { return Ok(None); }
+        let disjunction = tree.map_or(false, |b| { let (must, _, filter, _, _) = b.clauses(); must.is_empty() && filter.is_empty() });
+        if disjunction && !as_filter_query {
+            let msm = tree.map_or(0, |b| b.clauses().4);
+            if !filters.is_empty() || msm > 1 { return Ok(Some(false)); }
+        }
+        // one set per leaf: the single filter itself, or the AND of the filters minus the excludes, freed behind the calls
+        let mut masks: Vec<*mut RgpuDocset> = Vec::with_capacity(self.leaves.len());
+        let mut combined: Vec<*mut RgpuDocset> = Vec::new();
+        let mut rc = 0;
+        for (ord, leaf) in self.leaves.iter().enumerate() {
+            if filters.len() == 1 && excludes.is_empty() { masks.push(filters[0].sets[ord]); continue; }
+            let all: Vec<*mut RgpuDocset> = filters.iter().map(|f| f.sets[ord]).collect();
+            let none: Vec<*mut RgpuDocset> = excludes.iter().map(|f| f.sets[ord]).collect();
+            let mut made: *mut RgpuDocset = std::ptr::null_mut();
+            rc = unsafe { rgpu_docset_combine(leaf.seg, all.as_ptr(), all.len() as i32, none.as_ptr(), none.len() as i32, &mut made) };
+            if rc != 0 { break; }
+            masks.push(made);
+            combined.push(made);
+        }
+        let served = if rc != 0 { check(rc, self.ctx).map(|_| false) } else if let Some(p) = phrase {
+            self.try_phrase(p, Some(&masks), top, k)
+        } else if disjunction {
+            self.try_phrase_or(tree.unwrap(), Some(&masks), top, k)
+        } else {
+            self.try_phrase_bool(tree.unwrap(), Some(&masks), top, k)
+        };
+        for set in combined { unsafe { rgpu_docset_free(set) }; }
+        served.map(Some)
     }
 
     pub fn search_many(&self, queries: &[&dyn Query<C>], collectors: &mut [TopDocsCollector]) -> Result<()> {
