@@ -367,10 +367,12 @@ int32_t rgpu_search_batch_device(rgpu_segment* seg, const rgpu_query* queries, i
  * same f32 scores as Q alone on a leaf whose live docs are L AND F AND NOT X — provided Q contributes a MUST or FILTER clause of
  * its own and, for -X, min_should_match <= 1 (boolean_query.rs:235-251 reuses the outer min_should_match for the MUST_NOT union).
  * The filter scorer adds + 0.0 somewhere in ConjunctionScorer::score (conjunction_scorer.rs:87-95): x + 0.0 == x bit for bit for
- * every x but -0.0 (which becomes +0.0 in the reference: the one deviation). NOT equivalent, and refused by the mirrors: SHOULD
- * clauses whose only required clause is a doc set ("b c #F": the reference matches all of F), a lone #F, and sloppy phrases
- * (next_limit counts deleted docs but not docs outside a conjoined filter). Only rgpu_search_batch and rgpu_search_batch_device
- * have masked forms: the phrase, phrase-bool, phrase-or, rescore, planner and sharded / record entry points do not.
+ * every x but -0.0 (which becomes +0.0 in the reference: the one deviation). NOT equivalent under the masked calls: SHOULD
+ * clauses whose only required clause is a doc set ("b c #F": the reference matches all of F), a lone #F or a lone range, "b c -X",
+ * "-X" and MatchAllDocsQuery — these are served by rgpu_search_batch_required_set (below), which collects every doc of the set.
+ * Sloppy phrases under a doc set stay refused (next_limit counts deleted docs but not docs outside a conjoined filter). Only
+ * rgpu_search_batch and rgpu_search_batch_device have masked and required-set forms: the rescore, planner and sharded / record
+ * entry points do not (the exact-phrase calls have masked forms of their own, below, and no required-set form).
  *
  * Ownership: a doc set belongs to the segment it was made for (using it with another one: RGPU_ERR_ILLEGAL_ARGUMENT) and is
  * freed before it. rgpu_docset_free waits for the masked searches in flight that read the set. Every constructor returns a
@@ -407,6 +409,42 @@ int32_t rgpu_search_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu
 int32_t rgpu_search_batch_device_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_query* queries, int32_t n_queries,
                                         const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, void* hits_dev,
                                         void* total_hits_dev, void* hip_stream);
+
+/* A doc set as the ONLY required clause: "b c #F", a lone #F, a lone range, "+range b c", "b c -X", "-X", MatchAllDocsQuery (for
+ * which BooleanQuery::build inserts a MatchAllDocsQuery MUST clause, boolean_query.rs:76-79). The reference builds
+ * ReqOptScorer(F, DisjunctionSumScorer(b, c)) (boolean_query.rs:253-262). The required side is ConstantScoreScorer(0.0)
+ * (query_cache.rs:434-452, PointRangeWeight, MatchAllDocsWeight; nothing normalises a weight, searcher.rs:709-722), so
+ * ReqOptScorer::score (req_opt_scorer.rs:42-65) starts from 0.0, its skipping rule 2.0 * score < scores_sum / scores_num is 0 < 0
+ * and never fires, and min_should_match has no effect (only advance() reaches the optional scorer). With M = live AND set and
+ * O = the docs of M that a SHOULD clause present in the leaf holds: every doc of M is collected, total_hits = |M|, score(d) = the
+ * disjunction's own sum S(d) for d in O and +0.0 for d in M \ O. Ranked score desc, doc asc: the best rows of O, then the lowest
+ * doc ids of M \ O at score 0.
+ *
+ * The head of a set: |live AND set| and its first n docs (ascending), built on the device in one pass over the words per
+ * RGPU_DOCSET_HEAD_CHUNK_WORDS-word chunk, kept with the set (4 n bytes, counted in rgpu_docset_bytes, freed with it) and rebuilt
+ * only when a larger n is asked for. rgpu_docset_head returns it: docs_out holds n slots, *n_out = min(n, |live AND set|) of them
+ * are written as leaf-local ids; 0 <= n <= RGPU_MAX_K (n < 0: RGPU_ERR_ILLEGAL_ARGUMENT, above: RGPU_ERR_UNSUPPORTED). */
+#define RGPU_DOCSET_HEAD_CHUNK_WORDS 2048
+int32_t rgpu_docset_head(rgpu_segment* seg, rgpu_docset* set, int32_t n, int32_t* docs_out, int32_t* n_out, int64_t* live_cardinality_out);
+/* `set` is M without the live docs (the library applies them, as the masked calls do); a set of another segment:
+ * RGPU_ERR_ILLEGAL_ARGUMENT. The rows are the SHOULD side: RGPU_OP_TERM, a flat RGPU_OP_OR of 1..RGPU_MAX_QUERY_TERMS clauses (an msm
+ * byte is accepted and ignored, as under RGPU_OP_WITH_SHOULD), or {RGPU_OP_OR, n_terms 0, n_must_not 0}: no optional side, the row
+ * is the first k docs of M at score 0 (a batch of such rows alone may pass terms = NULL, n_terms_total = 0). RGPU_ERR_UNSUPPORTED,
+ * nothing launched: n_must_not != 0 (MUST_NOT term clauses are folded into the set by the caller: rgpu_docset_collect_batch,
+ * rgpu_docset_combine), a demote byte, RGPU_OP_AND, RGPU_OP_DISMAX, RGPU_OP_WITH_SHOULD, RGPU_OP_SHOULD_REQUIRED / RGPU_OP_NESTED_MUST,
+ * and a SHOULD clause whose weight is not finite and > 0. The last because the result is exact only while every scored doc's score
+ * is > 0: the scored rows come from rgpu_search_batch_device_masked's machinery over M and a row it fills with k docs stands; a
+ * row of fewer holds all of O and is completed from the head with the lowest docs of M \ O — a score-0 doc of O would tie with
+ * those, and a full row could hide zero-score docs with lower ids.
+ * Scores: below ten present SHOULD clauses bit-exact; with ten or more the clause-order f32 sums of the masked call (the
+ * reference's heap-order band, 1e-5 relative, as for every masked disjunction). Any k up to RGPU_MAX_K. The _device form blocks
+ * where rgpu_search_batch_device_masked does, and the first use of a set (or of a larger k) builds its head and ends synchronised;
+ * the fill is enqueued behind the search on the same stream, and rgpu_docset_free waits for the call. */
+int32_t rgpu_search_batch_required_set(rgpu_segment* seg, rgpu_docset* set, const rgpu_query* queries, int32_t n_queries,
+                                       const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out);
+int32_t rgpu_search_batch_device_required_set(rgpu_segment* seg, rgpu_docset* set, const rgpu_query* queries, int32_t n_queries,
+                                              const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, void* hits_dev,
+                                              void* total_hits_dev, void* hip_stream);
 
 /* ---- point ranges: numeric range filters built as doc sets -------------------------------------------------------------- */
 /* PointRangeQuery (search/query/point_range_query.rs): create_scorer (:503-561) collects the docs that hold a point inside the

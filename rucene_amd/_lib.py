@@ -78,6 +78,7 @@ EXPORTS = [
     "rgpu_planner_create", "rgpu_planner_create_flat", "rgpu_planner_destroy", "rgpu_planner_sim_table", "rgpu_planner_set_sim_table", "rgpu_plan_uniform_ids",
     "rgpu_docset_from_words", "rgpu_docset_from_docs", "rgpu_docset_collect_batch", "rgpu_docset_combine", "rgpu_docset_cardinality", "rgpu_docset_words",
     "rgpu_docset_bytes", "rgpu_docset_free", "rgpu_search_batch_masked", "rgpu_search_batch_device_masked",
+    "rgpu_docset_head", "rgpu_search_batch_required_set", "rgpu_search_batch_device_required_set",
     "rgpu_search_phrase_batch_masked", "rgpu_search_phrase_bool_batch_masked", "rgpu_search_phrase_or_batch_masked",
     "rgpu_points_attach", "rgpu_points_get_info", "rgpu_points_free", "rgpu_docset_from_point_ranges",
     "rgpu_plan_uniform_bytes", "rgpu_plan_batch_ids", "rgpu_plan_batch_bytes", "rgpu_planner_search_uniform_ids_device", "rgpu_planner_search_uniform_ids_sharded",
@@ -109,6 +110,7 @@ POINTS_INFO_DTYPE = np.dtype([("n_points", "<i8"), ("doc_count", "<i8"), ("hbm_b
 POINT_RANGE_DTYPE = np.dtype([("lower", "u1", (8,)), ("upper", "u1", (8,))], align=True)
 assert POINTS_INFO_DTYPE.itemsize == 48 and POINT_RANGE_DTYPE.itemsize == 16
 POINTS_PATH_AUTO, POINTS_PATH_SCATTER, POINTS_PATH_SCAN = 0, 1, 2   # rgpu_docset_from_point_ranges' path
+DOCSET_HEAD_CHUNK_WORDS = 2048   # RGPU_DOCSET_HEAD_CHUNK_WORDS: u64 words per chunk of a doc set's head build
 
 
 class _KernelStat(C.Structure):
@@ -198,6 +200,9 @@ def lib():
         "rgpu_search_phrase_bool_batch_masked": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_phrase_or_batch_masked": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_batch_device_masked": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp]),
+        "rgpu_docset_head": (i32, [vp, vp, i32, vp, C.POINTER(i32), C.POINTER(i64)]),
+        "rgpu_search_batch_required_set": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp]),
+        "rgpu_search_batch_device_required_set": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp]),
         "rgpu_bm25_compute_weight": (i32, [f32, f32, i64, i64, i64, vp, i32, f32, vp, vp, vp]),
         "rgpu_bm25_encode_norm": (C.c_uint8, [f32, i32]),
         "rgpu_bm25_term_weights": (i32, [i64, i64, vp, i64, f32, vp]),
@@ -985,6 +990,30 @@ class Segment:
         t = np.ascontiguousarray(terms, dtype=QUERY_TERM_DTYPE)
         _check(lib().rgpu_search_batch_device_masked(self._h, docset._h, q.ctypes.data, q.size, t.ctypes.data, t.size, k, hits_ptr, totals_ptr,
                                                      stream or None))
+
+    def docset_head(self, docset, n):
+        """rgpu_docset_head: (the first min(n, |live AND set|) docs of `live AND set`, ascending leaf-local ids; |live AND set|)"""
+        docs = np.zeros(max(n, 1), dtype=np.int32)
+        m, card = C.c_int32(), C.c_int64()
+        _check(lib().rgpu_docset_head(self._h, docset._h, n, docs.ctypes.data, C.byref(m), C.byref(card)))
+        return docs[:m.value].copy(), int(card.value)
+
+    def search_batch_required_set(self, docset, queries, terms, k):
+        """rgpu_search_batch_required_set: `docset` as the only required clause, the rows as its SHOULD side — every doc of
+        live AND set is collected, the docs no SHOULD clause holds at score 0"""
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=QUERY_TERM_DTYPE)
+        hits = np.zeros((q.size, max(k, 1)), dtype=HIT_DTYPE)
+        totals = np.zeros(q.size, dtype=np.int64)
+        _check(lib().rgpu_search_batch_required_set(self._h, docset._h, q.ctypes.data, q.size, t.ctypes.data if t.size else None, t.size, k,
+                                                    hits.ctypes.data, totals.ctypes.data))
+        return hits, totals
+
+    def search_batch_device_required_set(self, docset, queries, terms, k, hits_ptr, totals_ptr, stream=0):
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=QUERY_TERM_DTYPE)
+        _check(lib().rgpu_search_batch_device_required_set(self._h, docset._h, q.ctypes.data, q.size, t.ctypes.data if t.size else None, t.size, k,
+                                                           hits_ptr, totals_ptr, stream or None))
 
     def search_batch_record_device(self, queries, terms, k, record_ptr, stream=0):
         """This shard's record ([hits][counts][status], record_bytes(n_queries, k) bytes of device memory); enqueue-only."""

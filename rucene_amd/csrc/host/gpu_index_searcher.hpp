@@ -85,6 +85,10 @@ struct TermQuery : Query {
   explicit TermQuery(std::string bytes, float b = 1.0f) : text(std::move(bytes)), boost(b) {}
   bool by_text() const { return term < 0; }
 };
+// search/query/match_all_query.rs: every doc, ConstantScoreScorer with the weight's default of 0.0. Served by a searcher whose
+// required_sets is on: alone, and as the `query` of a FilteredQuery — clauses(MatchAllDocsQuery, {F}, {X}) is "#F -X", which is
+// "+*:* #F -X" (boolean_query.rs:76-79 gives a query of MUST_NOT clauses alone the MUST clause).
+struct MatchAllDocsQuery : Query {};
 struct BooleanQuery : Query {
   std::vector<TermQuery> must_queries, should_queries, must_not_queries;
   int32_t min_should_match = 0;
@@ -464,9 +468,20 @@ struct FilteredQuery : Query {
     out.excludes = std::move(x);
     return out;
   }
-  void check_served(bool filtered_phrases = false) const;  // (below PhraseBooleanQuery / PhraseDisjunctionQuery's definitions)
+  // -> the doc sets are the query's ONLY required clauses (GpuIndexSearcher::required_sets: rgpu_search_batch_required_set collects
+  // every doc of them, the query's SHOULD clauses score): clauses(should-only BooleanQuery, {F ...}, {X ...}) — "b c #F -X" — and
+  // MatchAllDocsQuery under either spelling — a lone "#F", "-X". With required_sets on clauses(should-only, {}, {X}) is served too,
+  // masked: "b c -X" gets no MatchAllDocsQuery, it is ReqNotScorer over the disjunction. Refused there: an exclusion beside
+  // min_should_match >= 2, a SHOULD clause of boost <= 0, MUST_NOT term clauses beside the sets (the Python mirror folds those into an
+  // excluded set; this mirror does not).
+  bool check_served(bool filtered_phrases = false, bool required_sets = false) const;  // (below PhraseBooleanQuery / PhraseDisjunctionQuery's definitions)
 };
-inline void FilteredQuery::check_served(bool filtered_phrases) const {
+inline bool FilteredQuery::check_served(bool filtered_phrases, bool required_sets) const {
+  if (query && dynamic_cast<const MatchAllDocsQuery*>(query)) {
+    if (filters.empty() && excludes.empty()) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "a filtered query takes a query and at least one cached filter");
+    if (!required_sets) throw Error(RGPU_ERR_UNSUPPORTED, "a doc set as the only required clause is not served by the GPU path (the reference matches all of it)");
+    return true;
+  }
   if (!query || (filters.empty() && excludes.empty()) || (as_filter_query && (filters.empty() || !excludes.empty())))
     throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "a filtered query takes a query and at least one cached filter");
   const PhraseQuery* phrase = dynamic_cast<const PhraseQuery*>(query);
@@ -477,19 +492,29 @@ inline void FilteredQuery::check_served(bool filtered_phrases) const {
     if (phrase_bool) phrase_bool->check_served();
     if (phrase_or) {
       phrase_or->check_served();
-      if (as_filter_query) return;
+      if (as_filter_query) return false;
       if (!filters.empty()) throw Error(RGPU_ERR_UNSUPPORTED, "a doc set as the only required clause is not served by the GPU path (the reference matches all of it)");
       if (phrase_or->min_should_match > 1) throw Error(RGPU_ERR_UNSUPPORTED, "a MUST_NOT doc set beside min_should_match >= 2 is not served by the GPU path");
     }
-    return;
+    return false;
   }
   if (dynamic_cast<const FilteredQuery*>(query) || dynamic_cast<const NestedBooleanQuery*>(query))
     throw Error(RGPU_ERR_UNSUPPORTED, "a filtered query over a nested or another filtered query is not served by the GPU path");
-  if (as_filter_query) return;
+  if (as_filter_query) return false;
   if (const BooleanQuery* b = dynamic_cast<const BooleanQuery*>(query)) {
-    if (b->must_queries.empty()) throw Error(RGPU_ERR_UNSUPPORTED, "a doc set as the only required clause is not served by the GPU path (the reference matches all of it)");
+    if (b->must_queries.empty()) {
+      if (!required_sets) throw Error(RGPU_ERR_UNSUPPORTED, "a doc set as the only required clause is not served by the GPU path (the reference matches all of it)");
+      if (!excludes.empty() && b->min_should_match > 1) throw Error(RGPU_ERR_UNSUPPORTED, "a MUST_NOT doc set beside min_should_match >= 2 is not served by the GPU path");
+      if (filters.empty()) return false;  // "b c -X": the masked disjunction
+      if (!b->must_not_queries.empty()) throw Error(RGPU_ERR_UNSUPPORTED, "MUST_NOT term clauses beside a doc set as the only required clause are not folded into the set by this mirror");
+      if (b->should_required || b->nested_must) throw Error(RGPU_ERR_UNSUPPORTED, "beside a doc set as the only required clause the SHOULD clauses are term queries");
+      for (const TermQuery& t : b->should_queries)
+        if (!(t.boost > 0.0f)) throw Error(RGPU_ERR_UNSUPPORTED, "beside a doc set as the only required clause a SHOULD clause has a boost > 0");
+      return true;
+    }
     if (!excludes.empty() && b->min_should_match > 1) throw Error(RGPU_ERR_UNSUPPORTED, "a MUST_NOT doc set beside min_should_match >= 2 is not served by the GPU path");
   }
+  return false;
 }
 
 // search/query/point_range_query.rs: the docs holding a point of `field` with lower <= value <= upper, both ends inclusive, in unsigned
@@ -795,6 +820,10 @@ class GpuIndexSearcher {
   // FilteredQuery over EXACT phrases (PhraseQuery, PhraseBooleanQuery, PhraseDisjunctionQuery) goes through the masked phrase calls
   // instead of being UnsupportedOperation (FilteredQuery's comment says what stays refused)
   bool filtered_phrases = false;
+  // Doc sets as the ONLY required clauses — "b c #F", a lone "#F", "-X", MatchAllDocsQuery — go through
+  // rgpu_search_batch_required_set (every doc of live AND sets is collected, the docs no SHOULD clause holds at score 0) instead of
+  // being UnsupportedOperation; "b c -X" is then searched masked (FilteredQuery::check_served says what stays refused)
+  bool required_sets = false;
   std::function<void(const Query&, TopDocsCollector&)> cpu_fallback;
 
   // ---- cached filters: doc sets in HBM as FILTER / MUST_NOT masks (include/rucene_gpu.h rgpu_docset_*) ---------------------------
@@ -846,6 +875,18 @@ class GpuIndexSearcher {
       throw;
     }
     return keep(std::move(sets));
+  }
+  // MatchAllDocsQuery as a required clause: every doc of every leaf (rgpu_docset_combine of no operands), made once
+  CachedFilter every_doc() {
+    if (every_doc_.id != 0 && filters_.count(every_doc_.id)) return every_doc_;
+    std::vector<rgpu_docset*> sets(leaves_.size(), nullptr);
+    try {
+      for (size_t li = 0; li < leaves_.size(); ++li) check(rgpu_docset_combine(leaves_[li].segment, nullptr, 0, nullptr, 0, &sets[li]));
+    } catch (...) {
+      for (rgpu_docset* d : sets) rgpu_docset_free(d);
+      throw;
+    }
+    return every_doc_ = keep(std::move(sets));
   }
   int64_t filter_cardinality(CachedFilter f) const {
     int64_t n = 0;
@@ -981,7 +1022,7 @@ class GpuIndexSearcher {
     for (const Query* q : queries)
       if (dynamic_cast<const PointRangeQuery*>(q)) throw Error(RGPU_ERR_UNSUPPORTED, "a lone point range is not served by the GPU path (the reference matches all of it)");
     for (const Query* q : queries)
-      if (dynamic_cast<const FilteredQuery*>(q)) return search_filtered(queries, k);
+      if (dynamic_cast<const FilteredQuery*>(q) || dynamic_cast<const MatchAllDocsQuery*>(q)) return search_filtered(queries, k);
     std::vector<size_t> phrase_rows, bool_rows, or_rows, plain_rows;
     for (size_t i = 0; i < queries.size(); ++i) {
       if (dynamic_cast<const PhraseQuery*>(queries[i])) phrase_rows.push_back(i);
@@ -1306,19 +1347,42 @@ class GpuIndexSearcher {
   std::vector<TopDocs> search_filtered(const std::vector<const Query*>& queries, size_t k) {
     std::vector<rgpu_host::DocsetKey> keys(queries.size());
     std::vector<const Query*> inner(queries.size());
+    std::vector<char> required(queries.size(), 0);   // the doc sets are the row's only required clauses (required_sets)
     for (size_t i = 0; i < queries.size(); ++i) {   // refused before any leaf is touched
       inner[i] = queries[i];
       if (const FilteredQuery* f = dynamic_cast<const FilteredQuery*>(queries[i])) {
-        f->check_served(filtered_phrases);
+        required[i] = f->check_served(filtered_phrases, required_sets) ? 1 : 0;
         std::vector<uint64_t> fs, xs;
         for (CachedFilter c : f->filters) { sets_of(c); fs.push_back(c.id); }
         for (CachedFilter c : f->excludes) { sets_of(c); xs.push_back(c.id); }
+        if (required[i] && fs.empty()) fs.push_back(every_doc().id);   // "-X" is "+*:* -X"
         keys[i] = rgpu_host::docset_key(std::move(fs), std::move(xs));
         inner[i] = f->query;
+      } else if (dynamic_cast<const MatchAllDocsQuery*>(queries[i])) {
+        if (!required_sets) throw Error(RGPU_ERR_UNSUPPORTED, "MatchAllDocsQuery is not served by the GPU path (required_sets)");
+        required[i] = 1;
+        keys[i] = rgpu_host::docset_key({every_doc().id}, {});
       }
     }
     std::vector<TopDocs> out(queries.size());
-    for (const rgpu_host::DocsetGroup& grp : rgpu_host::group_by_docset_key(keys)) {
+    // rows whose only required clauses are the sets: groups, and calls, of their own
+    std::vector<rgpu_host::DocsetKey> required_keys;
+    std::vector<size_t> required_at;
+    for (size_t i = 0; i < queries.size(); ++i)
+      if (required[i]) { required_keys.push_back(keys[i]); required_at.push_back(i); }
+    for (const rgpu_host::DocsetGroup& grp : rgpu_host::group_by_docset_key(required_keys)) {
+      std::vector<const BooleanQuery*> part;   // null: no optional side (MatchAllDocsQuery)
+      for (int32_t r : grp.rows) part.push_back(dynamic_cast<const BooleanQuery*>(inner[required_at[static_cast<size_t>(r)]]));
+      std::vector<TopDocs> got = search_required_sets(part, masks_of(grp.key), k);
+      for (size_t i = 0; i < grp.rows.size(); ++i) out[required_at[static_cast<size_t>(grp.rows[i])]] = std::move(got[i]);
+    }
+    std::vector<rgpu_host::DocsetKey> other_keys;
+    std::vector<size_t> other_at;
+    for (size_t i = 0; i < queries.size(); ++i)
+      if (!required[i]) { other_keys.push_back(keys[i]); other_at.push_back(i); }
+    for (const rgpu_host::DocsetGroup& grp0 : rgpu_host::group_by_docset_key(other_keys)) {
+      rgpu_host::DocsetGroup grp = grp0;
+      for (int32_t& r : grp.rows) r = static_cast<int32_t>(other_at[static_cast<size_t>(r)]);   // rows of the caller's batch again
       std::vector<const Query*> part;
       for (int32_t r : grp.rows) part.push_back(inner[static_cast<size_t>(r)]);
       std::vector<TopDocs> got;
@@ -1372,6 +1436,29 @@ class GpuIndexSearcher {
       for (size_t i = 0; i < grp.rows.size(); ++i) out[static_cast<size_t>(grp.rows[i])] = std::move(got[i]);
     }
     return out;
+  }
+
+  // Rows whose only required clauses are the doc sets behind `masks` (rgpu_search_batch_required_set): the rows' SHOULD sides as
+  // OR queries, {OR, no clause} for a row without one (null). Zero-score rows of earlier leaves carry lower global ids: merge_leaves'
+  // order is the reference's.
+  std::vector<TopDocs> search_required_sets(const std::vector<const BooleanQuery*>& rows, const std::vector<rgpu_docset*>& masks, size_t k) {
+    const int32_t nq = static_cast<int32_t>(rows.size());
+    std::vector<const Query*> scored;
+    for (const BooleanQuery* b : rows) if (b) scored.push_back(b);
+    std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
+    std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
+    for (size_t li = 0; li < leaves_.size(); ++li) {
+      std::vector<rgpu_query> some, qs(rows.size(), rgpu_query{RGPU_OP_OR, 0, 0, 0});
+      std::vector<rgpu_query_term> ts;
+      if (!scored.empty()) plan(scored, li, &some, &ts);
+      size_t at = 0;
+      for (size_t i = 0; i < rows.size(); ++i) if (rows[i]) qs[i] = some[at++];
+      leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
+      leaf_totals[li].assign(static_cast<size_t>(nq), 0);
+      check(rgpu_search_batch_required_set(leaves_[li].segment, masks[li], qs.data(), nq, ts.empty() ? nullptr : ts.data(), static_cast<int32_t>(ts.size()),
+                                           static_cast<int32_t>(k), leaf_hits[li].data(), leaf_totals[li].data()));
+    }
+    return merge_leaves(leaf_hits, leaf_totals, nq, k);
   }
 
   // TopDocsCollector::finish_parallel (top_docs.rs:157-172) over a handful of leaves: canonical order
@@ -1566,6 +1653,7 @@ class GpuIndexSearcher {
   std::map<std::tuple<std::string, std::vector<uint8_t>, std::vector<uint8_t>>, CachedFilter> range_filters_;  // the memo of range_filter
   std::map<std::pair<std::vector<uint64_t>, std::vector<uint64_t>>, std::vector<rgpu_docset*>> masks_;  // (filters, excludes) -> combined sets per leaf
   uint64_t next_filter_id_ = 0;
+  CachedFilter every_doc_;
 };
 
 }  // namespace rucene

@@ -6,10 +6,13 @@
 //   k_docset_lists<CLEAR>  (set row, term) jobs: the term's prepared list decoded block by block, bits set — or cleared (MUST_NOT)
 //   k_docset_from_emitted  the candidate lists k_search_and leaves in emit mode -> bits (conjunctions)
 //   k_docset_combine       AND of sets, minus sets, inside [0, max_doc), optionally AND live docs; counts the result
+//   k_docset_chunk_counts, k_docset_head_scan, k_docset_select_head   the head of a set: its cardinality and first n docs (at the end)
+//   k_required_set_fill    rows of "SHOULD clauses beside a required doc set" completed from the head at score 0 (at the end)
 // The kernels view the words as u32 (little endian: bit doc & 31 of u32 word doc >> 5 is the same bit).
 #pragma once
 #include "decode.hpp"
 #include "decode_terms.hpp"
+#include "search.hpp"
 #include "types.hpp"
 
 namespace rgpu {
@@ -195,6 +198,134 @@ __global__ __launch_bounds__(DOCSET_THREADS) void k_docset_combine(DocsetCombine
     for (int i = 0; i < DOCSET_WAVES; ++i) total += wave_counts[i];
     if (total != 0) atomicAdd(cardinality, (unsigned long long)total);
   }
+}
+
+// ---- a doc set as the only required clause (rgpu_docset_head, rgpu_search_batch_required_set) -------------------------------------
+// The head of M = live AND set: |M| and its first n docs, ascending. Three launches over the mask's words, no atomics:
+//   k_docset_chunk_counts  popcount per chunk of DOCSET_HEAD_CHUNK_WORDS u64 words, one workgroup per chunk
+//   k_docset_head_scan     exclusive prefix of the chunk counts and their total; one wavefront (a 2^31-doc leaf has 16384 chunks)
+//   k_docset_select_head   every chunk whose prefix is below n writes its docs of rank < n to head[rank]
+// The mask's allocation ends on a 16-byte boundary and its padding word is zero (docset_new / docset_mask_locked), so a pair
+// load of the last word of an odd count stays inside it.
+constexpr int DOCSET_HEAD_CHUNK_WORDS = 2048;  // = RGPU_DOCSET_HEAD_CHUNK_WORDS (include/rucene_gpu.h): 131072 docs per chunk
+
+__global__ __launch_bounds__(DOCSET_THREADS) void k_docset_chunk_counts(const uint64_t* __restrict__ words, int64_t n_words,
+                                                                         int* __restrict__ counts) {
+  __shared__ int wave_counts[DOCSET_WAVES];
+  const int64_t c0 = (int64_t)blockIdx.x * DOCSET_HEAD_CHUNK_WORDS;
+  const int64_t c1 = c0 + DOCSET_HEAD_CHUNK_WORDS < n_words ? c0 + DOCSET_HEAD_CHUNK_WORDS : n_words;
+  int count = 0;
+  for (int64_t w = c0 + 2 * (int64_t)threadIdx.x; w < c1; w += 2 * DOCSET_THREADS) {  // (c0 is even: w + 1 is the pair's second word or the padding)
+    const uint4 t = *reinterpret_cast<const uint4*>(words + w);
+    count += __popc(t.x) + __popc(t.y) + __popc(t.z) + __popc(t.w);
+  }
+  const int wsum = wave_reduce_add(count);
+  if (lane_id() == 0) wave_counts[wave_id()] = wsum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int total = 0;
+#pragma unroll
+    for (int i = 0; i < DOCSET_WAVES; ++i) total += wave_counts[i];
+    counts[blockIdx.x] = total;
+  }
+}
+
+// prefix[c] = docs of M in the chunks before c; *total = |M|. Launched as ONE wavefront.
+__global__ __launch_bounds__(64) void k_docset_head_scan(const int* __restrict__ counts, int n_chunks, long long* __restrict__ prefix,
+                                                         long long* __restrict__ total) {
+  const int lane = lane_id();
+  long long carry = 0;
+  for (int base = 0; base < n_chunks; base += 64) {
+    const int c = base + lane;
+    const int v = c < n_chunks ? counts[c] : 0;
+    const int incl = wave_incl_scan(v);  // (64 chunks hold at most 2^23 docs)
+    if (c < n_chunks) prefix[c] = carry + (long long)(incl - v);
+    carry += (long long)readlane(incl, 63);
+  }
+  if (lane == 0) *total = carry;
+}
+
+// One workgroup per chunk; a chunk at or past rank n has nothing to write. A step takes DOCSET_THREADS words, one per lane: the
+// word's popcount, an inclusive scan inside the wavefront, the wavefronts' totals through LDS — the rank of the lane's first doc —
+// and the lane peels its word's bits while rank < n. head holds n slots.
+__global__ __launch_bounds__(DOCSET_THREADS) void k_docset_select_head(const uint64_t* __restrict__ words, int64_t n_words,
+                                                                        const long long* __restrict__ prefix, int n,
+                                                                        int32_t* __restrict__ head) {
+  __shared__ int wave_totals[2][DOCSET_WAVES];
+  long long rank_base = prefix[blockIdx.x];
+  if (rank_base >= (long long)n) return;  // (uniform in the workgroup)
+  const int lane = lane_id(), wave = wave_id();
+  const int64_t c0 = (int64_t)blockIdx.x * DOCSET_HEAD_CHUNK_WORDS;
+  const int64_t c1 = c0 + DOCSET_HEAD_CHUNK_WORDS < n_words ? c0 + DOCSET_HEAD_CHUNK_WORDS : n_words;
+  int buf = 0;
+  for (int64_t w0 = c0; w0 < c1 && rank_base < (long long)n; w0 += DOCSET_THREADS, buf ^= 1) {
+    const int64_t w = w0 + threadIdx.x;
+    uint64_t x = w < c1 ? words[w] : 0ull;
+    const int cnt = __popcll(x);
+    const int incl = wave_incl_scan(cnt);
+    if (lane == 63) wave_totals[buf][wave] = incl;
+    __syncthreads();  // (two buffers: a wavefront a step ahead writes the other one)
+    int before = 0, all = 0;
+#pragma unroll
+    for (int i = 0; i < DOCSET_WAVES; ++i) { const int t = wave_totals[buf][i]; all += t; if (i < wave) before += t; }
+    long long rank = rank_base + (long long)(before + incl - cnt);
+    while (x != 0ull && rank < (long long)n) {
+      head[rank] = (int32_t)((w << 6) + __builtin_ctzll(x));
+      x &= x - 1ull;
+      ++rank;
+    }
+    rank_base += (long long)all;
+  }
+}
+
+// Rows of "SHOULD clauses beside a required doc set": the masked disjunction has left query q's scored docs (the docs of O, best
+// first, {-1, 0} behind them) in its row; every doc of M matches, the unscored ones at +0.0 in doc order. One wavefront per query.
+// A full row stands (every scored doc's score is > 0: the host refuses other weights). Otherwise all n_q docs of O are in the row
+// and the first k docs of M hold at least k - n_q docs outside O: the scored docs are looked up in the ascending head (binary
+// search) and flagged in LDS, the unflagged head docs are appended in order from slot n_q on. total_hits = |M| for every row.
+constexpr int REQUIRED_SET_FILL_WAVES = 4;
+constexpr int REQUIRED_SET_MAX_HEAD = 1024;  // = RGPU_MAX_K
+
+__global__ __launch_bounds__(64 * REQUIRED_SET_FILL_WAVES) void k_required_set_fill(HitOut* __restrict__ hits, int64_t* __restrict__ totals,
+                                                                                     int n_queries, int k, const int32_t* __restrict__ head,
+                                                                                     int head_len, int64_t cardinality, int32_t doc_base) {
+  __shared__ uint32_t flags[REQUIRED_SET_FILL_WAVES][REQUIRED_SET_MAX_HEAD / 32];
+  const int lane = lane_id(), wave = wave_id();
+  const int q = (int)blockIdx.x * REQUIRED_SET_FILL_WAVES + wave;
+  if (q >= n_queries) return;
+  if (lane == 0) totals[q] = cardinality;
+  HitOut* row = hits + (int64_t)q * k;
+  if (row[k - 1].doc >= 0) return;  // k scored docs: the row stands
+  const int hn = head_len < k ? head_len : k;  // (head_len <= REQUIRED_SET_MAX_HEAD)
+  uint32_t* fl = flags[wave];
+  if (lane < REQUIRED_SET_MAX_HEAD / 32) fl[lane] = 0u;
+  wave_sync();
+  int n_q = 0;
+  for (int base = 0; base < k; base += 64) {
+    const int i = base + lane;
+    const int32_t doc = i < k ? row[i].doc : -1;
+    const bool valid = doc >= 0;
+    if (valid) {
+      const int32_t d = doc - doc_base;
+      int lo = 0, hi = hn;  // first slot whose doc is >= d
+      while (lo < hi) { const int mid = (lo + hi) >> 1; if (head[mid] < d) lo = mid + 1; else hi = mid; }
+      if (lo < hn && head[lo] == d) atomicOr(&fl[lo >> 5], 1u << (lo & 31));
+    }
+    const uint64_t m = __ballot(valid);
+    n_q += __popcll(m);
+    if (m != ~0ull) break;  // (scored docs are a prefix of the row)
+  }
+  wave_sync();
+  int out = n_q;
+  for (int base = 0; base < hn && out < k; base += 64) {
+    const int p = base + lane;
+    const bool keep = p < hn && ((fl[p >> 5] >> (p & 31)) & 1u) == 0u;
+    const uint64_t m = __ballot(keep);
+    const int slot = out + mbcnt(m);
+    if (keep && slot < k) row[slot] = HitOut{head[p] + doc_base, 0.0f};
+    out += __popcll(m);
+  }
+  for (int i = (out < k ? out : k) + lane; i < k; i += 64) row[i] = HitOut{-1, 0.0f};
 }
 
 }  // namespace rgpu

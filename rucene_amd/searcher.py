@@ -278,6 +278,26 @@ class PointRangeQuery:
         return "PointRangeQuery(field: %s, lower: %s, upper: %s)" % (self.field, self.lower.hex(), self.upper.hex())
 
 
+class MatchAllDocsQuery:
+    """search/query/match_all_query.rs: every doc, ConstantScoreScorer with the weight's default of 0.0 (nothing normalises it).
+    BooleanQuery::build gives a query of MUST_NOT clauses alone one as its MUST clause (boolean_query.rs:76-79). Served by a
+    searcher made with required_sets=True, alone and under `musts=`: as a required clause it is the every-doc set."""
+
+    def extract_terms(self):
+        return []
+
+    def __str__(self):
+        return "MatchAllDocsQuery()"
+
+
+class _RequiredSet:
+    """What _peel leaves of a query whose only required clauses are doc sets: its SHOULD side, TermQuery clauses of boost > 0
+    (none: every doc of the sets at score 0). Searched through rgpu_search_batch_required_set."""
+
+    def __init__(self, shoulds):
+        self.shoulds = list(shoulds)
+
+
 class _Point:
     """One-dimensional point types: encode = encode_dimension (the sortable bytes), new_range_query / new_exact_query as in the
     reference (point_range_query.rs:83-310)."""
@@ -398,7 +418,9 @@ class BooleanQuery:
         # (so does a PhraseQuery clause: GpuIndexSearcher.phrase_bool_parts says which trees over phrases the GPU path serves)
         # (a CachedFilter under FILTER / MUST_NOT is a doc-set clause: GpuIndexSearcher.search_batch peels it off and masks the search)
         # (a PointRangeQuery under MUST / FILTER / MUST_NOT likewise: GpuIndexSearcher.range_filter makes its doc set)
-        if any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, PointRangeQuery)) for q in list(musts)) or \
+        # (a MatchAllDocsQuery under MUST is the every-doc set: GpuIndexSearcher(required_sets=True). A query of MUST_NOT clauses alone
+        # gets one from the reference's build(); here the searcher supplies it when it peels such a query, the tree stays as given)
+        if any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, PointRangeQuery, MatchAllDocsQuery)) for q in list(musts)) or \
                 any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery)) for q in list(shoulds)) or \
                 any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, CachedFilter, PointRangeQuery)) for q in list(must_nots) + list(filters)):
             raise RgpuError(-5, "only term, phrase and boolean clauses are known to this mirror")
@@ -649,8 +671,15 @@ class GpuIndexSearcher:
 
     range_filter_capacity = 256   # memoised range filters kept from one search_batch to the next (range_filter); set per searcher
 
-    def __init__(self, leaves, ctx=None, similarity=None, next_limit=None, flatten_nested=False, cpu_fallback=None, filtered_phrases=False):
-        """filtered_phrases: serve EXACT phrases beside doc-set clauses - FilterQuery("a b", F), +"a b" #F -X, +"a b" +c #F -X,
+    def __init__(self, leaves, ctx=None, similarity=None, next_limit=None, flatten_nested=False, cpu_fallback=None, filtered_phrases=False,
+                 required_sets=False):
+        """required_sets: serve queries whose ONLY required clauses are doc sets - "b c #F", a lone #F, a lone PointRangeQuery,
+        "+range b c", "-X", "-t", MatchAllDocsQuery alone and under MUST - through rgpu_search_batch_required_set: every doc of
+        live AND sets is collected, the docs no SHOULD clause holds at score 0 (off by default: such rows are UnsupportedOperation,
+        as they have been). With it on "b c -X" (min_should_match <= 1) is served too, masked: ReqNotScorer over the disjunction,
+        which has a scorer of its own. Still refused: an exclusion beside min_should_match >= 2, and on the SHOULD side of such a
+        row phrases, nested clauses and a clause of boost <= 0.
+        filtered_phrases: serve EXACT phrases beside doc-set clauses - FilterQuery("a b", F), +"a b" #F -X, +"a b" +c #F -X,
         "a b" c -X with min_should_match <= 1, point ranges in those positions - through rgpu_search_phrase_batch_masked,
         _phrase_bool_batch_masked and _phrase_or_batch_masked (off by default: such rows are UnsupportedOperation, as they have been).
         Still refused with it on: any sloppy phrase under a mask, "a b" c #F (the doc set is the only required clause), -X beside
@@ -661,6 +690,7 @@ class GpuIndexSearcher:
         (UnsupportedOperation) to it, as the Rust shim hands them to DefaultIndexSearcher (rust/gpu/searcher.rs); None: raise."""
         self.flatten_nested = bool(flatten_nested)
         self.filtered_phrases = bool(filtered_phrases)
+        self.required_sets = bool(required_sets)
         self.cpu_fallback = cpu_fallback
         self.leaves = list(leaves)
         # DefaultIndexSearcher::new(reader, next_limit: Option<usize>) (searcher.rs:291-296, :361): how many approximations of a
@@ -691,6 +721,8 @@ class GpuIndexSearcher:
         self._masks = {}          # (filter sets, exclude sets) key -> (the CachedFilters, one combined DocSet per leaf)
         self._points = {}         # field -> (bytes per value, one _lib.Points per leaf or None)
         self._range_filters = {}  # (field, lower, upper) -> CachedFilter, least recently used first
+        self._every_doc = None    # required_sets: MatchAllDocsQuery as a CachedFilter (rgpu_docset_combine of nothing, once per leaf)
+        self._not_filters = {}    # required_sets: MUST_NOT term clauses as an excluded CachedFilter, by clause tuple; least recently used first
 
     def max_doc(self):
         return sum(leaf.max_doc for leaf in self.leaves)
@@ -1206,7 +1238,9 @@ class GpuIndexSearcher:
         only that Q has a scorer of its own. Phrases are not served under a mask unless the searcher opted in (filtered_phrases), and
         then exact ones only (a sloppy phrase's next_limit counts deleted docs, not docs outside a filter); with the opt-in
         "a b" c -X (min_should_match <= 1) is served too: ReqNotScorer over the disjunction, whose phrase clause is a scorer of its own.
-        Anything else: UnsupportedOperation.
+        Anything else: UnsupportedOperation — unless the searcher opted in to required_sets: a query whose only required clauses are doc
+        sets (MatchAllDocsQuery among them, which a query of MUST_NOT clauses alone gets from build()) then comes back as a
+        _RequiredSet holding its SHOULD clauses (_peel_required), and "b c -X" as the masked disjunction it is.
         A PointRangeQuery under MUST / FILTER / MUST_NOT is checked first (dimensions, field, width), the rules above are applied, and
         only then is its doc set built; build=False stops short of that (the sets are then the queries themselves) — search_batch
         runs it over the whole batch first, so a refused row launches nothing. min_should_match stays the query's own: "+range #a b"
@@ -1216,22 +1250,39 @@ class GpuIndexSearcher:
             if isinstance(inner, PhraseQuery) or (isinstance(inner, BooleanQuery) and inner.has_phrases()):
                 self._filtered_phrase(inner)
             return inner, (f + list(query.filters), x)
+        required_sets = getattr(self, "required_sets", False)
         if isinstance(query, PointRangeQuery):
-            raise RgpuError(-5, "a lone point range is not served by the GPU path (the reference matches all of it)")
+            if not required_sets:
+                raise RgpuError(-5, "a lone point range is not served by the GPU path (the reference matches all of it)")
+            self._check_ranges([query])
+            return _RequiredSet([]), (self._sets_of([query]) if build else [query], [])
+        if isinstance(query, MatchAllDocsQuery):
+            if not required_sets:
+                raise RgpuError(-5, "MatchAllDocsQuery is not served by the GPU path (required_sets)")
+            return _RequiredSet([]), (self._sets_of([query]) if build else [query], [])
         if not isinstance(query, BooleanQuery):
             return query, ([], [])
-        sets = (CachedFilter, PointRangeQuery)
+        sets = (CachedFilter, PointRangeQuery, MatchAllDocsQuery)
         f = [q for q in list(query.must_queries) + list(query.filter_queries) if isinstance(q, sets)]   # a range under MUST adds + 0.0 as under FILTER
         x = [q for q in query.must_not_queries if isinstance(q, sets)]
-        if not f and not x:
+        # "-t": BooleanQuery::build gives a query of MUST_NOT clauses alone a MatchAllDocsQuery MUST clause (boolean_query.rs:76-79)
+        only_nots = required_sets and bool(query.must_not_queries) and not (query.must_queries or query.filter_queries or query.should_queries)
+        if not f and not x and not only_nots:
             return query, ([], [])
+        if not required_sets and any(isinstance(q, MatchAllDocsQuery) for q in f + x):
+            raise RgpuError(-5, "MatchAllDocsQuery is not served by the GPU path (required_sets)")
         self._check_ranges([q for q in f + x if isinstance(q, PointRangeQuery)])
         musts = [q for q in query.must_queries if not isinstance(q, sets)]
         filters = [q for q in query.filter_queries if not isinstance(q, sets)]
         must_nots = [q for q in query.must_not_queries if not isinstance(q, sets)]
         phrase_or = getattr(self, "filtered_phrases", False) and not f and any(isinstance(q, PhraseQuery) for q in query.should_queries)
         if not (musts or filters) and not phrase_or:
-            raise RgpuError(-5, "a doc set as the only required clause is not served by the GPU path (the reference matches all of it)")
+            if not required_sets:
+                raise RgpuError(-5, "a doc set as the only required clause is not served by the GPU path (the reference matches all of it)")
+            if f or not query.should_queries:
+                return self._peel_required(query, f, x, must_nots, build)
+            # "b c -X": no MatchAllDocsQuery is inserted beside SHOULD clauses; ReqNotScorer(DisjunctionSumScorer(b, c), X) collects
+            # the disjunction's docs outside X — the disjunction has a scorer of its own, so the masked search below is that query
         if x and query.min_should_match > 1:
             raise RgpuError(-5, "a MUST_NOT doc set beside min_should_match >= 2 is not served by the GPU path")
         rest = BooleanQuery.build(musts, list(query.should_queries), filters=filters, must_nots=must_nots,
@@ -1242,10 +1293,66 @@ class GpuIndexSearcher:
         if isinstance(rest, PhraseQuery) or (isinstance(rest, BooleanQuery) and rest.has_phrases()):
             self._filtered_phrase(rest)
         if build:
-            made = iter(self._range_filters_for([q for q in f + x if isinstance(q, PointRangeQuery)]))
-            f = [next(made) if isinstance(q, PointRangeQuery) else q for q in f]
-            x = [next(made) if isinstance(q, PointRangeQuery) else q for q in x]
+            made = self._sets_of(f + x)
+            f, x = made[:len(f)], made[len(f):]
         return rest, (f, x)
+
+    def _sets_of(self, clauses):
+        """doc-set clauses as CachedFilters: a PointRangeQuery's memoised range filter (the missing ones built in one call per leaf),
+        MatchAllDocsQuery's every-doc set, a CachedFilter itself"""
+        made = iter(self._range_filters_for([q for q in clauses if isinstance(q, PointRangeQuery)]))
+        out = []
+        for q in clauses:
+            if isinstance(q, PointRangeQuery):
+                out.append(next(made))
+            elif isinstance(q, MatchAllDocsQuery):
+                if self._every_doc is None:   # rgpu_docset_combine of no operands: every doc of the leaf, once per leaf
+                    self._every_doc = self._cached([leaf.segment.docset_combine() for leaf in self.leaves])
+                out.append(self._every_doc)
+            else:
+                out.append(q)
+        return out
+
+    def _not_filter(self, must_nots):
+        """MUST_NOT term clauses of a row whose required clauses are doc sets, as one excluded CachedFilter: the union of their docs,
+        collected per leaf by one rgpu_docset_collect_batch OR row, memoised per clause tuple and bounded like the range filters"""
+        key = tuple(c.term for c in must_nots)
+        if key in self._not_filters:
+            self._not_filters[key] = self._not_filters.pop(key)   # most recently used last
+        else:
+            union = TermQuery(key[0]) if len(key) == 1 else BooleanQuery([], [TermQuery(t) for t in key], 1)
+            self._not_filters[key] = self._cached([leaf.segment.docset_collect_batch(*self.pack([union], leaf))[0] for leaf in self.leaves])
+            while len(self._not_filters) > max(1, int(self.range_filter_capacity)):
+                gone = self._not_filters.pop(next(iter(self._not_filters)))
+                for mk in [m for m in self._masks if id(gone) in m[0] or id(gone) in m[1]]:
+                    del self._masks[mk]
+        return self._not_filters[key]
+
+    def _peel_required(self, query, f, x, must_nots, build):
+        """The required-set route of _peel: doc sets f (none: build()'s MatchAllDocsQuery) are the only required clauses. ->
+        (_RequiredSet(the SHOULD clauses), (filters, excludes)) with the MUST_NOT term clauses among the excludes. The reference
+        builds ReqOptScorer(sets, DisjunctionSumScorer(shoulds)), in a ReqNotScorer when there are exclusions; min_should_match
+        reaches the MUST_NOT union only (boolean_query.rs:235-251), hence the existing rule for exclusions."""
+        if (x or must_nots) and query.min_should_match > 1:
+            raise RgpuError(-5, "an exclusion beside min_should_match >= 2 is not served by the GPU path")
+        for q in query.should_queries:
+            if not isinstance(q, TermQuery):
+                raise RgpuError(-5, "beside a doc set as the only required clause the SHOULD clauses are term queries")
+            if not q.boost > 0.0:
+                raise RgpuError(-5, "beside a doc set as the only required clause a SHOULD clause has a boost > 0")
+        if any(not isinstance(q, TermQuery) for q in must_nots):
+            raise RgpuError(-5, "beside a doc set as the only required clause the MUST_NOT clauses are terms and doc sets")
+        if len(query.should_queries) > _lib.MAX_QUERY_TERMS or len(must_nots) > _lib.MAX_QUERY_TERMS:
+            raise RgpuError(-5, "more than %d clauses" % _lib.MAX_QUERY_TERMS)
+        f = list(f) or [MatchAllDocsQuery()]
+        if build:
+            made = self._sets_of(f + x)
+            f, x = made[:len(f)], made[len(f):]
+            if must_nots:
+                x = x + [self._not_filter(must_nots)]
+        else:
+            x = x + list(must_nots)
+        return _RequiredSet(query.should_queries), (f, x)
 
     def _mask(self, filters, excludes):
         """One DocSet per leaf for a (filters, excludes) combination: combined once per combination and leaf
@@ -1279,8 +1386,10 @@ class GpuIndexSearcher:
             per_leaf = self._rows_per_leaf(queries, k, None)
         else:
             groups = {}   # key -> (masks per leaf or None, caller rows): first appearance first, caller order inside a group
-            for i, (_, (f, x)) in enumerate(peeled):
+            for i, (rest, (f, x)) in enumerate(peeled):
                 key, masks = self._mask(f, x) if (f or x) else (None, None)
+                if isinstance(rest, _RequiredSet):   # the same sets as the ONLY required clauses: a group, and a call, of its own
+                    key = (key, "required")
                 groups.setdefault(key, (masks, []))[1].append(i)
             per_leaf = [(np.zeros((len(queries), k), dtype=_lib.HIT_DTYPE), np.zeros(len(queries), dtype=np.int64)) for _ in self.leaves]
             for masks, rows in groups.values():
@@ -1299,6 +1408,8 @@ class GpuIndexSearcher:
             if isinstance(q, BooleanQuery) and q.has_phrases():   # no MUST, no FILTER: the disjunction route; else phrase_bool_parts decides
                 return 2 if (q.must_queries or q.filter_queries) else 3
             return 0
+        if queries and isinstance(queries[0], _RequiredSet):   # (a group holds such rows alone: search_batch)
+            return self._required_rows_per_leaf(queries, k, masks)
         kinds = [kind(q) for q in queries]
         if not any(kinds):
             per_leaf = []
@@ -1333,6 +1444,21 @@ class GpuIndexSearcher:
                     hits[rows[3]], totals[rows[3]] = (seg.search_phrase_or_batch(*packed, k) if masks is None
                                                       else seg.search_phrase_or_batch_masked(masks[i], *packed, k))
                 per_leaf.append((hits, totals))
+        return per_leaf
+
+    def _required_rows_per_leaf(self, rests, k, masks):
+        """[(hits, totals)] per leaf for rows whose only required clauses are the doc sets behind `masks`
+        (rgpu_search_batch_required_set): the rows' SHOULD sides as TERM / OR queries, {OR, no clause} where there is none"""
+        some = [i for i, r in enumerate(rests) if r.shoulds]
+        scored = [rests[i].shoulds[0] if len(rests[i].shoulds) == 1 else BooleanQuery([], list(rests[i].shoulds), 1) for i in some]
+        per_leaf = []
+        for i, leaf in enumerate(self.leaves):
+            qs = np.zeros(len(rests), dtype=QUERY_DTYPE)
+            qs["op"] = OP_OR
+            ts = np.zeros(0, dtype=QUERY_TERM_DTYPE)
+            if scored:
+                qs[some], ts = self.pack(scored, leaf)
+            per_leaf.append(leaf.segment.search_batch_required_set(masks[i], qs, ts, k))
         return per_leaf
 
     def _merge_leaves(self, per_leaf, n_queries, k):

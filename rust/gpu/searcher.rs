@@ -144,6 +144,12 @@ pub struct GpuIndexSearcher<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: De
     /// next_limit counts deleted docs, not docs outside a filter), "\"a b\" c #F" (the doc set is the only required clause), a MUST_NOT
     /// set beside min_should_match >= 2, and whatever try_phrase_bool / try_phrase_or leave to it.
     pub filtered_phrases: bool,
+    /// try_filtered serves queries whose ONLY required clauses are doc sets — "b c #F", a lone "#F" or range, "-X" — through
+    /// rgpu_search_batch_required_set (try_required_set: every doc of live AND sets is collected, the docs no SHOULD clause holds at
+    /// score 0, as the reference's ReqOptScorer(F, b | c) does), and "b c -X" masked. Off by default, as `required_sets` of the
+    /// Python and C++ mirrors. Still the CPU's with it on: an exclusion beside min_should_match >= 2, MUST_NOT term clauses beside
+    /// the sets, a SHOULD clause of boost <= 0, phrases and nested clauses on the SHOULD side.
+    pub required_sets: bool,
 }
 
 unsafe impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: SimilarityProducer<C>> Send for GpuIndexSearcher<C, R, IR, SP> {}
@@ -177,7 +183,7 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             leaves.push(GpuLeaf { seg, has_positions: pos.is_some() });
         }
         let next_limit = match next_limit { None => 0, Some(0) => RGPU_NEXT_LIMIT_ZERO, Some(n) => n.min(i32::max_value() as usize) as i32 };
-        Ok(GpuIndexSearcher { cpu, ctx, field: field.to_string(), leaves, sim_tables: Mutex::new(HashMap::new()), next_limit, allow_flatten, filtered_phrases: false })
+        Ok(GpuIndexSearcher { cpu, ctx, field: field.to_string(), leaves, sim_tables: Mutex::new(HashMap::new()), next_limit, allow_flatten, filtered_phrases: false, required_sets: false })
     }
 
     /// BooleanQuery trees the C ABI serves, flattened to one clause list (query/boolean_query.rs:195-279 is what the CPU builds
@@ -785,8 +791,13 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
         let base = flat.op & 0xff;
         let msm = (flat.op >> 8) & 0xff;
         if !as_filter_query {
-            if !(base == RGPU_OP_TERM || base == RGPU_OP_AND) { return Ok(false); }   // no required clause of its own
             if !excludes.is_empty() && msm > 1 { return Ok(false); }
+            if !(base == RGPU_OP_TERM || base == RGPU_OP_AND) {   // no required clause of its own
+                if !self.required_sets || base != RGPU_OP_OR { return Ok(false); }
+                // "b c #F": the sets are the only required clauses. "b c -X" gets no MatchAllDocsQuery (boolean_query.rs:76-79 adds one
+                // only when there is no MUST, SHOULD or FILTER clause): ReqNotScorer over the disjunction, the masked search below.
+                if !filters.is_empty() { return self.try_required_set(Some(&flat), filters, excludes, top, k); }
+            }
         }
         let n = flat.n_clauses();
         if n > RGPU_MAX_QUERY_TERMS as usize { return Ok(false); }
@@ -810,6 +821,55 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
             let mut total: i64 = 0;
             let rc = unsafe { rgpu_search_batch_masked(seg, mask, &q, 1, terms.as_ptr(), n as i32, k as i32, hits.as_mut_ptr(), &mut total) };
+            if !combined.is_null() { unsafe { rgpu_docset_free(combined) }; }
+            check(rc, self.ctx)?;
+            Self::hand_over(top, &hits, total);
+        }
+        Ok(true)
+    }
+
+    /// A lone "#F" / range, or "-X" (which BooleanQuery::build turns into "+*:* -X"): `filters` as the only required clauses, no SHOULD
+    /// side. With no filter at all the every-doc set stands in for MatchAllDocsQuery. Ok(false): `required_sets` is off.
+    pub fn try_filter_alone(&self, filters: &[&GpuCachedFilter], excludes: &[&GpuCachedFilter], top: &mut TopDocsCollector, k: usize) -> Result<bool> {
+        if !self.required_sets || k == 0 || k > RGPU_MAX_K as usize || (filters.is_empty() && excludes.is_empty()) { return Ok(false); }
+        if filters.iter().chain(excludes.iter()).any(|f| f.sets.len() != self.leaves.len()) { bail!(ErrorKind::IllegalArgument("a cached filter of another searcher".into())); }
+        self.try_required_set(None, filters, excludes, top, k)
+    }
+
+    /// The sets are the query's ONLY required clauses: ReqOptScorer(sets, DisjunctionSumScorer(SHOULD clauses)) in the reference, whose
+    /// required side scores 0.0 and whose skipping rule therefore never fires — every doc of live AND filters AND NOT excludes is
+    /// collected, scored by the disjunction where it matches and 0.0 elsewhere (rgpu_search_batch_required_set, one call per leaf;
+    /// min_should_match has no effect there and is dropped). `flat`: the SHOULD side, an RGPU_OP_OR query; None: no optional side.
+    /// Ok(false) — the CPU searcher: MUST_NOT term clauses beside the sets (not folded into a set here), a boost <= 0.
+    fn try_required_set(&self, flat: Option<&FlatQuery<'_>>, filters: &[&GpuCachedFilter], excludes: &[&GpuCachedFilter], top: &mut TopDocsCollector,
+                        k: usize) -> Result<bool> {
+        let n = flat.map_or(0, |f| f.positive.len());
+        if let Some(f) = flat {
+            if !f.must_not.is_empty() || !f.optional.is_empty() || n == 0 || n > RGPU_MAX_QUERY_TERMS as usize { return Ok(false); }
+            if f.positive.iter().any(|(_, boost)| !(*boost > 0.0)) { return Ok(false); }
+        }
+        let weights = match flat { Some(f) => self.clause_weights(f)?, None => Vec::new() };
+        for leaf in self.cpu.reader().leaves() {
+            let seg = self.leaves[leaf.ord].seg;
+            let all: Vec<*mut RgpuDocset> = filters.iter().map(|f| f.sets[leaf.ord]).collect();
+            let none: Vec<*mut RgpuDocset> = excludes.iter().map(|f| f.sets[leaf.ord]).collect();
+            let mut combined: *mut RgpuDocset = std::ptr::null_mut();
+            // (no filter: rgpu_docset_combine starts from every doc of the leaf — MatchAllDocsQuery as a set)
+            let mask = if all.len() == 1 && none.is_empty() { all[0] } else {
+                check(unsafe { rgpu_docset_combine(seg, all.as_ptr(), all.len() as i32, none.as_ptr(), none.len() as i32, &mut combined) }, self.ctx)?;
+                combined
+            };
+            let mut terms = Vec::with_capacity(n);
+            if let Some(f) = flat {
+                for (i, (t, _)) in f.positive.iter().enumerate() {
+                    terms.push(RgpuQueryTerm { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: weights[i].0, sim_table: weights[i].1 });
+                }
+            }
+            let q = RgpuQuery { op: RGPU_OP_OR, n_terms: n as i32, first_term: 0, n_must_not: 0 };
+            let terms_ptr = if terms.is_empty() { std::ptr::null() } else { terms.as_ptr() };
+            let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
+            let mut total: i64 = 0;
+            let rc = unsafe { rgpu_search_batch_required_set(seg, mask, &q, 1, terms_ptr, n as i32, k as i32, hits.as_mut_ptr(), &mut total) };
             if !combined.is_null() { unsafe { rgpu_docset_free(combined) }; }
             check(rc, self.ctx)?;
             Self::hand_over(top, &hits, total);
