@@ -187,33 +187,90 @@ class BatchPlanner {
     for (int64_t i = 0; i < n; ++i) {
       const int64_t id = ids[i];
       if (id < 0 || id >= n_leaf) { use(i, static_cast<const Rec*>(nullptr), (int32_t)-1); continue; }
-      const size_t at = (size_t)(((uint64_t)id * 0x9E3779B97F4A7C15ull) >> (64 - FLAT_MEMO_BITS));
-      FlatMemoSlot& e = flat_memo_[at];
-      FlatMemoPlace& p = flat_memo_place_[at];
-      Rec* rec = reinterpret_cast<Rec*>(e.rec);
-      if (e.id != id || e.gen != gen || (e.held && (p.id != id || p.memo_gen != gen || p.arena_gen != arena_gen))) {
-        const rgpu_term_state& st = leaf_states_[(size_t)id];
-        int32_t held = 0;
-        p = FlatMemoPlace{};
-        if (st.doc_freq > 0) {
-          int32_t df = 0;
-          if (id < n_stats) df = own_stats_ ? stats_df_[(size_t)id] : st.doc_freq;
-          held = make(st, idf_of(df > 0 ? df : 0), rec);
-          if (held < 0) { e.gen = 0; return false; }
-          if (held) {
-            const int64_t where = place(static_cast<const Rec*>(rec));
-            if (where < 0) { e.gen = 0; return false; }
-            p = FlatMemoPlace{id, gen, (uint32_t)where, arena_gen};
-          }
-        }
-        e.id = id;
-        e.gen = gen;
-        e.held = held;
-      }
-      use(i, e.held ? rec : static_cast<const Rec*>(nullptr), e.held ? (int32_t)p.index : (int32_t)-1);
+      const Rec* rec = nullptr;
+      int32_t index = -1;
+      if (!flat_memo_placed_one<Rec>(id, gen, arena_gen, n_stats, make, place, &rec, &index)) return false;
+      use(i, rec, index);
     }
     return true;
   }
+
+  // for_each_flat_memo_placed for a caller that needs, per id, only the record's arena index and a few bytes of what the record says
+  // (the fused single-term step: df, nblocks and the launch bucket — 16 bytes of answer for which the memo reads an 80-byte slot that
+  // straddles cache lines, a 24-byte place and the 64-byte record). In front of the memo stands a direct-mapped table of 32-byte,
+  // naturally aligned entries {id, stamp, index, digest}: an id whose entry carries the current stamp is answered from that one cache
+  // line and touches neither memo array. A stamp is issued for a triple — (key, record size), memo generation, arena generation —
+  // and any change of the triple issues a new one, which makes every entry a miss at once; a stamp that wraps clears the table.
+  // A miss runs for_each_flat_memo_placed's per-id body (the memo entry is made and placed if need be), then fills the hot entry.
+  // Why a hit may skip the memo: within an arena generation a record is written once and never again, a memo eviction only
+  // orphans it, and what it says is a function of the key — so (index, digest) stay right for as long as the triple holds. A pass
+  // that gives up after placing records has the caller turn the arena's generation over (the stamp goes with it); one that gives up
+  // with nothing placed has filled hot entries from valid memo entries only.
+  // digest_of(rec) -> Digest (plain, at most HOT_DIGEST bytes); use(i, index, digest) in id order: index -1 and a zero digest for an id
+  // outside the table or a term the leaf does not hold (absent terms are cached too). make / place and the lock as above.
+  template <class Rec, class Digest, class Make, class Place, class DigestOf, class Use>
+  bool for_each_flat_memo_hot(const int64_t* ids, int64_t n, const MemoKey& key, uint32_t arena_gen, Make&& make, Place&& place, DigestOf&& digest_of,
+                              Use&& use) {
+    static_assert(std::is_trivially_copyable<Rec>::value && sizeof(Rec) <= FLAT_MEMO_REC, "a plain record of at most FLAT_MEMO_REC bytes");
+    static_assert(std::is_trivially_copyable<Digest>::value && sizeof(Digest) <= HOT_DIGEST, "a plain digest of at most HOT_DIGEST bytes");
+    std::lock_guard<std::mutex> g(mu_);
+    if (flat_memo_.empty() || !(flat_memo_key_ == key) || flat_memo_rec_ != sizeof(Rec)) {
+      if (flat_memo_.empty() || ++flat_memo_gen_ == 0) {
+        flat_memo_.assign(FLAT_MEMO_SLOTS, FlatMemoSlot{});
+        flat_memo_gen_ = 1;
+      }
+      flat_memo_key_ = key;
+      flat_memo_rec_ = sizeof(Rec);
+    }
+    if (flat_memo_place_.empty()) flat_memo_place_.assign(FLAT_MEMO_SLOTS, FlatMemoPlace{});
+    const uint32_t gen = flat_memo_gen_;
+    if (hot_.empty() || hot_stamp_ == 0 || !(hot_key_ == key) || hot_rec_ != sizeof(Rec) || hot_memo_gen_ != gen || hot_arena_gen_ != arena_gen) {
+      if (hot_.empty() || ++hot_stamp_ == 0) {
+        hot_.assign(HOT_SLOTS, HotEntry{});  // (stamp 0 everywhere)
+        hot_stamp_ = 1;
+      }
+      hot_key_ = key;
+      hot_rec_ = sizeof(Rec);
+      hot_memo_gen_ = gen;
+      hot_arena_gen_ = arena_gen;
+    }
+    const uint32_t stamp = hot_stamp_;
+    const int64_t n_leaf = (int64_t)leaf_states_.size();
+    const int64_t n_stats = own_stats_ ? (int64_t)stats_df_.size() : n_leaf;
+    HotEntry* const hot = hot_.data();
+    const Digest none{};
+    for (int64_t i = 0; i < n; ++i) {
+      if (i + HOT_AHEAD < n) __builtin_prefetch(&hot[hot_slot(ids[i + HOT_AHEAD])]);
+      const int64_t id = ids[i];
+      if (id < 0 || id >= n_leaf) { use(i, (int32_t)-1, none); continue; }
+      HotEntry& h = hot[hot_slot(id)];
+      if (h.id != id || h.stamp != stamp) {
+        const Rec* rec = nullptr;
+        int32_t index = -1;
+        if (!flat_memo_placed_one<Rec>(id, gen, arena_gen, n_stats, make, place, &rec, &index)) return false;
+        h.id = id;
+        h.stamp = stamp;
+        h.index = index;
+        std::memset(h.digest, 0, sizeof h.digest);
+        if (rec) {
+          const Digest d = digest_of(*rec);
+          std::memcpy(h.digest, &d, sizeof d);
+        }
+      }
+      Digest d;
+      std::memcpy(&d, h.digest, sizeof d);
+      use(i, h.index, d);
+    }
+    return true;
+  }
+  // the hot table's slot of an id (ids 2^HOT_BITS apart share one; the memo's slots follow another hash, so the two tables' collisions differ)
+  static constexpr int HOT_BITS = 16;
+  static constexpr size_t HOT_SLOTS = (size_t)1 << HOT_BITS;
+  static constexpr size_t HOT_DIGEST = 16;
+  static size_t hot_slot(int64_t id) { return (size_t)((uint64_t)id & (HOT_SLOTS - 1)); }
+  // (tests) the stamp in use becomes `v`: the next change of the triple issues v + 1, and a wrap past 2^32 - 1 clears the table
+  // (only forwards: no entry may carry a stamp above `v` already)
+  void hot_stamp_set(uint32_t v) { std::lock_guard<std::mutex> g(mu_); if (!hot_.empty()) { hot_stamp_ = v; hot_rec_ = 0; } }
 
   // The flat-table planner's per-clause work WITHOUT the arrays in between (the fused plan + search entry points write device
   // descriptors straight from it): f(i, state, weight) for every id, boost 1, under the planner's lock. An id outside the
@@ -263,6 +320,47 @@ class BatchPlanner {
   // for_each_flat_memo has rewritten since is not taken for placed
   struct FlatMemoPlace { int64_t id = -1; uint32_t memo_gen = 0; uint32_t index = 0; uint32_t arena_gen = 0; };
   std::vector<FlatMemoPlace> flat_memo_place_;  // (empty until the first for_each_flat_memo_placed)
+  // one id (inside the table) of for_each_flat_memo_placed and for_each_flat_memo_hot, under the lock: the memo entry is made and placed
+  // unless it is both already. *rec: the record, null for a term the leaf does not hold; *index: its place in the arena, or -1.
+  // false: make() or place() gave up (the entry is dropped).
+  template <class Rec, class Make, class Place>
+  bool flat_memo_placed_one(int64_t id, uint32_t gen, uint32_t arena_gen, int64_t n_stats, Make& make, Place& place, const Rec** rec_out, int32_t* index) {
+    const size_t at = (size_t)(((uint64_t)id * 0x9E3779B97F4A7C15ull) >> (64 - FLAT_MEMO_BITS));
+    FlatMemoSlot& e = flat_memo_[at];
+    FlatMemoPlace& p = flat_memo_place_[at];
+    Rec* rec = reinterpret_cast<Rec*>(e.rec);
+    if (e.id != id || e.gen != gen || (e.held && (p.id != id || p.memo_gen != gen || p.arena_gen != arena_gen))) {
+      const rgpu_term_state& st = leaf_states_[(size_t)id];
+      int32_t held = 0;
+      p = FlatMemoPlace{};
+      if (st.doc_freq > 0) {
+        int32_t df = 0;
+        if (id < n_stats) df = own_stats_ ? stats_df_[(size_t)id] : st.doc_freq;
+        held = make(st, idf_of(df > 0 ? df : 0), rec);
+        if (held < 0) { e.gen = 0; return false; }
+        if (held) {
+          const int64_t where = place(static_cast<const Rec*>(rec));
+          if (where < 0) { e.gen = 0; return false; }
+          p = FlatMemoPlace{id, gen, (uint32_t)where, arena_gen};
+        }
+      }
+      e.id = id;
+      e.gen = gen;
+      e.held = held;
+    }
+    *rec_out = e.held ? rec : static_cast<const Rec*>(nullptr);
+    *index = e.held ? (int32_t)p.index : (int32_t)-1;
+    return true;
+  }
+  // for_each_flat_memo_hot's table, in front of the memo: one naturally aligned 32-byte entry per slot (never across two cache lines)
+  struct alignas(32) HotEntry { int64_t id = -1; uint32_t stamp = 0; int32_t index = -1; unsigned char digest[HOT_DIGEST] = {}; };
+  static_assert(sizeof(HotEntry) == 32, "one hot entry is half a cache line");
+  static constexpr int64_t HOT_AHEAD = 8;  // entries prefetched ahead of the one being read
+  std::vector<HotEntry> hot_;  // (empty until the first for_each_flat_memo_hot: 2 MB)
+  uint32_t hot_stamp_ = 0;     // the stamp of the triple below (0: none issued)
+  MemoKey hot_key_{{0, 0, 0, 0}};
+  size_t hot_rec_ = 0;
+  uint32_t hot_memo_gen_ = 0, hot_arena_gen_ = 0;
   uint32_t flat_memo_gen_ = 0;  // the generation the current key's records carry (0: no slot is valid)
   std::vector<FlatMemoSlot> flat_memo_;  // (empty until the first for_each_flat_memo: 5 MB)
   MemoKey flat_memo_key_{{0, 0, 0, 0}};

@@ -2,6 +2,7 @@
 // gfx950 kernels in kernels/*.hpp. HIP runtime only — no torch types, no CPU fallback: every entry point
 // either runs on the GPU or fails with a negative rgpu_status.
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -80,6 +81,14 @@ static inline unsigned wg_count(unsigned long long n) { return n > 0xffffffffull
     const dim3 g_ = (grid), b_ = (block);                                                                  \
     if ((unsigned long long)g_.x * (unsigned long long)b_.x > 0xffffffffull) g_refused_launch = #kern;     \
     else hipLaunchKernelGGL(kern, g_, b_, shmem, stream, __VA_ARGS__);                                     \
+  } while (0)
+// ... with `stop_event` bound to the kernel as its stop event (hipExtLaunchKernelGGL): the event completes when the kernel does, as
+// one recorded right behind the launch would, without a call and a stream packet of its own
+#define RGPU_LAUNCH_WITH_STOP(kern, grid, block, shmem, stream, stop_event, ...)                            \
+  do {                                                                                                     \
+    const dim3 g_ = (grid), b_ = (block);                                                                  \
+    if ((unsigned long long)g_.x * (unsigned long long)b_.x > 0xffffffffull) g_refused_launch = #kern;     \
+    else hipExtLaunchKernelGGL(kern, g_, b_, shmem, stream, nullptr, stop_event, 0, __VA_ARGS__);          \
   } while (0)
 #define HIP_TRY(expr)                                                                                      \
   do {                                                                                                     \
@@ -243,6 +252,12 @@ struct rgpu_ctx {
   // ... and reads its plan as one TermLaunch per query from the pinned stage, the term descriptors staying on the device in `arena`
   // (term_batch_resident); RGPU_TERM_PLAN=staged in the environment: the whole plan is staged every step, as before (A/B)
   bool term_plan_resident = true;
+  // ... and takes what its memo pass needs of a term from the planner's hot entries (BatchPlanner::for_each_flat_memo_hot);
+  // RGPU_TERM_HOT=0 in the environment: from the memo's records (for_each_flat_memo_placed), as before (A/B)
+  bool term_hot = true;
+  // ... and binds its slot's `done` event to the search kernel as the launch's stop event; RGPU_SLOT_EVENT=record in the environment:
+  // hipEventRecord behind the launch (scratch_mark), as every other path does (A/B)
+  bool term_slot_event_bound = true;
   rucene::TermArena arena;             // the descriptor arena's bookkeeping (host/term_arena.hpp); RGPU_TERM_ARENA_RECORDS sizes it
   std::vector<void*> arena_spares;     // buffers of retired generations, kept for the next turnover (at most ARENA_SPARES_MAX)
   int term_query_waves = 4;       // 2, 4 or 8 (RGPU_TERM_QUERY_WAVES)
@@ -287,6 +302,8 @@ struct rgpu_ctx {
   int64_t last_counted_or_bytes = 0;     // k_or_lazy: encoded bytes + norms of the walked clauses + the lazy clauses' bitmap words
   // profiling
   std::vector<StatSlot> stats;
+  // term_batch_resident's three stat names, resolved once (stat_slot_once; -1: not yet, or the stats were reset since)
+  int stat_k_search_term = -1, stat_term_query_launches = -1, stat_fused_term_batches = -1;
   std::vector<PendingEvent> pending;
   std::vector<hipEvent_t> free_events;
   char name[128] = {0};
@@ -355,6 +372,12 @@ static int stat_slot(rgpu_ctx* c, const char* name) {
   c->stats.push_back(StatSlot{name, 0, 0.0, 0, {}});
   return (int)c->stats.size() - 1;
 }
+// ... for a call path that names the same stat every call: the index is looked up once per context and kept in *cached (a slot keeps
+// its index until rgpu_kernel_stats_reset, which forgets the cached ones too; first use registers the name, in the same order as before)
+static inline int stat_slot_once(rgpu_ctx* c, int* cached, const char* name) {
+  if (*cached < 0) *cached = stat_slot(c, name);
+  return *cached;
+}
 static hipEvent_t take_event(rgpu_ctx* c) {
   if (!c->free_events.empty()) { hipEvent_t e = c->free_events.back(); c->free_events.pop_back(); return e; }
   hipEvent_t e;
@@ -367,8 +390,9 @@ struct TimedLaunch {
   int slot;
   hipEvent_t stop = nullptr;
   bool on;
-  TimedLaunch(rgpu_ctx* c_, hipStream_t s_, const char* name, int64_t postings) : c(c_), s(s_), on(c_->cfg.profile_kernels != 0) {
-    slot = stat_slot(c, name);
+  TimedLaunch(rgpu_ctx* c_, hipStream_t s_, const char* name, int64_t postings) : TimedLaunch(c_, s_, stat_slot(c_, name), postings) {}
+  // ... under a stat slot the caller has resolved already (stat_slot_once)
+  TimedLaunch(rgpu_ctx* c_, hipStream_t s_, int slot_, int64_t postings) : c(c_), s(s_), slot(slot_), on(c_->cfg.profile_kernels != 0) {
     c->stats[(size_t)slot].launches++;
     c->stats[(size_t)slot].postings += postings;
     if (on) {
@@ -1278,6 +1302,8 @@ extern "C" int32_t rgpu_init(int32_t device_ordinal, const rgpu_config* cfg, rgp
   if (const char* e = std::getenv("RGPU_TERM_FOLD")) c->term_fold = std::atoi(e) != 0;
   if (const char* e = std::getenv("RGPU_TERM_KERNEL")) c->term_query_kernel = std::strcmp(e, "items") != 0;
   if (const char* e = std::getenv("RGPU_TERM_PLAN")) c->term_plan_resident = std::strcmp(e, "staged") != 0;
+  if (const char* e = std::getenv("RGPU_TERM_HOT")) c->term_hot = std::atoi(e) != 0;
+  if (const char* e = std::getenv("RGPU_SLOT_EVENT")) c->term_slot_event_bound = std::strcmp(e, "record") != 0;
   if (const char* e = std::getenv("RGPU_TERM_ARENA_RECORDS")) c->arena = rucene::TermArena((uint32_t)std::max(1, std::min(1 << 24, std::atoi(e))));
   if (const char* e = std::getenv("RGPU_TERM_QUERY_WAVES")) { const int w = std::atoi(e); c->term_query_waves = w <= 2 ? 2 : w >= 8 ? 8 : 4; }
   if (const char* e = std::getenv("RGPU_TERM_MIN_ITEM_BLOCKS")) c->term_min_item_blocks = std::max(8, std::min(4096, std::atoi(e)));
@@ -1410,6 +1436,7 @@ extern "C" void rgpu_kernel_stats_reset(rgpu_ctx* c) {
   (void)hipSetDevice(c->device);
   drain_events(c);
   c->stats.clear();
+  c->stat_k_search_term = c->stat_term_query_launches = c->stat_fused_term_batches = -1;
 }
 
 // ---- similarity tables ---------------------------------------------------------------------------------------
@@ -6575,6 +6602,9 @@ struct HostLaps {
     *this = HostLaps{};
   }
 };
+// what term_batch_resident's memo pass needs of a DevTerm besides its arena index: the digest of the planner's hot entry
+// (host/batch_planner.hpp for_each_flat_memo_hot). bucket: clz(nblocks), 32 for a list without FullBlocks
+struct TermHot { int32_t df, nblocks, bucket; };
 // The fused single-term step with the term descriptors RESIDENT on the device (the default; RGPU_TERM_PLAN=staged: the staged plan
 // below). What a step sends is 8 bytes per query — TermLaunch{record, row} in launch order, which k_search_term_query reads straight
 // from the pinned stage — and nothing is copied: no stage kernel, no DevQuery / DevTerm / order / qmap arrays. The descriptors live in
@@ -6628,14 +6658,32 @@ static int32_t term_batch_resident(rgpu_segment* seg, rucene::BatchPlanner* P, i
     lo = 0xffffffffu;
     hi = 0u;
     bool full = false;
-    // the memo pass counts the launch order's buckets (0: the longest lists; floor(log2(nblocks))) on the way
-    const bool ok = P->for_each_flat_memo_placed<DevTerm>(ids, nq, memo_key, A.generation(), make_term, [&](const DevTerm* t) -> int64_t {
+    auto place = [&](const DevTerm* t) -> int64_t {
       const int64_t at = A.append();
       if (at < 0) { full = true; return -1; }
       if (first_up < 0) first_up = at;  // (appends of one pass are consecutive: the context's lock is held)
       hup[n_up++] = *t;
       return at;
-    }, [&](int64_t q, const DevTerm* t, int32_t rec) {
+    };
+    // the memo pass counts the launch order's buckets (0: the longest lists; floor(log2(nblocks))) on the way. What it needs of a term —
+    // its record's index, df, nblocks, the bucket — comes from the planner's hot entry (one cache line per query; RGPU_TERM_HOT=0: from
+    // the memo's record, as before)
+    const bool ok = c->term_hot ? P->for_each_flat_memo_hot<DevTerm, TermHot>(ids, nq, memo_key, A.generation(), make_term, place, [](const DevTerm& t) {
+      return TermHot{t.df, t.nblocks, t.nblocks > 0 ? __builtin_clz((uint32_t)t.nblocks) : 32};
+    }, [&](int64_t q, int32_t rec, const TermHot& t) {
+      int b = 32;
+      if (rec >= 0) {
+        postings += t.df;
+        total_blocks += t.nblocks;
+        loose += t.df == 1 ? 1 : t.df % 128;  // (make_term's tail_n)
+        b = t.bucket;
+        lo = std::min(lo, (uint32_t)rec);
+        hi = std::max(hi, (uint32_t)rec);
+      }
+      recs[(size_t)q] = rec;
+      buckets[(size_t)q] = (uint8_t)b;
+      ++start[b + 1];
+    }) : P->for_each_flat_memo_placed<DevTerm>(ids, nq, memo_key, A.generation(), make_term, place, [&](int64_t q, const DevTerm* t, int32_t rec) {
       int b = 32;
       if (t) {
         postings += t->df;
@@ -6703,12 +6751,18 @@ static int32_t term_batch_resident(rgpu_segment* seg, rucene::BatchPlanner* P, i
   c->last_counted_loose = loose;
   const bool wide = k > 64;
   const bool legacy = seg->version < 1;
+  // the slot's mark travels with the step's only launch: `done` is the kernel's stop event, and no hipEventRecord follows it
+  const bool bound = c->term_slot_event_bound;
+  if (bound && !c->S->done) HIP_TRY(hipEventCreateWithFlags(&c->S->done, hipEventDisableTiming));
   {
-    TimedLaunch tl(c, stream, "k_search_term", postings);  // (under the TERM search's name, like the staged plan's launch below)
+    TimedLaunch tl(c, stream, stat_slot_once(c, &c->stat_k_search_term, "k_search_term"), postings);  // (under the TERM search's name, like the staged plan's launch below)
     const SegView sv = seg_view(seg);
     auto go = [&](auto kern, int waves) -> hipError_t {
-      RGPU_LAUNCH(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, sv, (const DevQuery*)nullptr, d_arena, (const int32_t*)nullptr, nq, (int)k, d_work,
-                  (const int32_t*)nullptr, hits_dev, totals_dev, seg->doc_base, (const TermLaunch*)hl);
+      // (hipExtLaunchKernelGGL passes the arguments as they are typed here: each one has its parameter's type exactly)
+      if (bound) RGPU_LAUNCH_WITH_STOP(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, c->S->done, sv, (const DevQuery*)nullptr, d_arena, (const int32_t*)nullptr,
+                                       (int)nq, (int)k, d_work, (const int32_t*)nullptr, hits_dev, totals_dev, (int32_t)seg->doc_base, (const TermLaunch*)hl);
+      else RGPU_LAUNCH(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, sv, (const DevQuery*)nullptr, d_arena, (const int32_t*)nullptr, nq, (int)k, d_work,
+                       (const int32_t*)nullptr, hits_dev, totals_dev, seg->doc_base, (const TermLaunch*)hl);
       return hipSuccess;
     };
     auto pick = [&](auto legacy_c, auto wide_c) -> hipError_t {
@@ -6721,13 +6775,14 @@ static int32_t term_batch_resident(rgpu_segment* seg, rucene::BatchPlanner* P, i
     if (legacy) e = wide ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{});
     else e = wide ? pick(std::false_type{}, std::true_type{}) : pick(std::false_type{}, std::false_type{});
     HIP_TRY(e);
-    c->stats[(size_t)stat_slot(c, "term_query_launches")].launches += 1;
+    c->stats[(size_t)stat_slot_once(c, &c->stat_term_query_launches, "term_query_launches")].launches += 1;
   }
   if (laps) laps->lap(5);
-  HIP_TRY(launch_status());
-  HIP_TRY(scratch_mark(c, stream));
+  HIP_TRY(launch_status());  // (a refused launch: the slot stays unmarked, `busy` false)
+  if (bound) c->S->busy = true;
+  else HIP_TRY(scratch_mark(c, stream));
   A.slot_marked((int)(c->S - c->scr), (uint64_t)(uintptr_t)stream);
-  c->stats[(size_t)stat_slot(c, "fused_term_batches")].launches += 1;
+  c->stats[(size_t)stat_slot_once(c, &c->stat_fused_term_batches, "fused_term_batches")].launches += 1;
   if (laps) { laps->lap(6); laps->done(); }
   *taken = true;
   return RGPU_OK;
