@@ -804,6 +804,31 @@ int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* que
                                  const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
                                  int64_t* total_hits_out);
 
+/* One leaf of IndexSearcher::search(SpanNearQuery(in_order = true) over SpanTermQuery clauses, TopDocsCollector(k)).
+ * The reference (search/query/spans/): SpanNearQuery::new and span_near_weight (span_near.rs:101-124, :143-160); NearSpansOrdered
+ * (:725-852) takes every position p0 of clause 0 in ascending order and stretches the other clauses to order (:759-776): clause
+ * i >= 1 moves forward to its first start >= end(i - 1) (span.rs:214-219), match_width sums start(i) - end(i - 1), the span counts
+ * iff match_width <= slop, and a clause that runs out of positions ends the doc. A SpanTermQuery's span is [position, position + 1)
+ * (span_term.rs:170-200); every clause has its own iterator, so a term may be named by several clauses. SpanScorer
+ * (span.rs:458-527) sums 1 / (width + 1) (bm25_similarity.rs:65-67) over the spans, in the order they come out, in f32 from 0.0;
+ * the score is BM25(that frequency, norm) (bm25_similarity.rs:99-113, :151-177). A doc is a hit when it has a span, whatever its
+ * score: the sloppy phrase scorer's "> f32::EPSILON" rule does not exist here. Spans of different p0 may share later positions
+ * (a@1, a@3, b@5 with slop 3: two spans), and transposed terms never match - neither is what a sloppy PhraseQuery does.
+ * `queries` / `terms` are rgpu_search_phrase_batch's structs: n_terms = 2..RGPU_MAX_PHRASE_TERMS clauses in the query's clause
+ * order; terms[i].position must be i and .reserved 0; slop >= 0 = the allowed slop; weight = idf summed over every clause's term -
+ * a term named by two clauses counts twice (build_sim_weight over extract_term_keys, span.rs:574-602) - x boost; sim_table as for
+ * rgpu_query_term. next_limit as for a sloppy phrase, AT EVERY SLOP, 0 included: spans are always two-phase (span.rs:1033-1091,
+ * bulk_scorer.rs:97-113, :132-150). in_order must be non-zero. The segment needs rgpu_segment_attach_positions. Outputs as
+ * rgpu_search_phrase_batch; scores are bit-exact with the CPU scorer. A leaf that lacks a clause's term matches nothing.
+ * Refused like rgpu_search_phrase_batch refuses the same faults (clause count, slop < 0, sim_table, k: its codes; position /
+ * reserved: RGPU_ERR_ILLEGAL_ARGUMENT); in_order == 0 and a doc holding one clause's term more than 1024 times -> RGPU_ERR_UNSUPPORTED.
+ * NOT served (the caller keeps these on its CPU path): unordered near - NearSpansUnordered pops a BinaryHeap whose order among cells
+ * at equal (start, end) is the heap array's (span_near.rs:681-696); SpanGapQuery clauses; SpanOrQuery; nested span clauses; a span
+ * query as a BooleanQuery clause or under a doc-set mask; the planner, rescore and sharded forms. */
+int32_t rgpu_search_span_near_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
+                                    const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t in_order, int32_t k,
+                                    rgpu_hit* hits_out, int64_t* total_hits_out);
+
 /* BooleanQuery with exact PhraseQuery clauses among its required clauses: +"a b" +c -d #e. BooleanWeight::create_scorer
  * (boolean_query.rs:196-279) builds a ConjunctionScorer over must_weights — the MUST weights in query order, then the FILTER weights
  * (needs_scores = false: they score 0.0) — sorted stably by cost (conjunction_scorer.rs:27-42: a term's cost is its doc_freq in

@@ -362,6 +362,36 @@ struct PhraseQuery : Query {
   }
 };
 
+// SpanTermQuery (query/spans/span_term.rs): the spans [position, position + 1) of one term; served as a clause of an ordered SpanNearQuery.
+struct SpanTermQuery : Query {
+  TermQuery term;
+  explicit SpanTermQuery(TermQuery t) : term(std::move(t)) {}
+};
+// SpanNearQuery::new (query/spans/span_near.rs:101-124): the clauses within `slop` positions of each other, in the clauses' order when
+// in_order. The GPU path serves a top-level query with in_order = true whose clauses are all SpanTermQuery (rgpu_search_span_near_batch):
+// NearSpansOrdered + SpanScorer, next_limit applied at every slop (spans are always two-phase). The weight sums the idf of every clause's
+// term, a term named twice counted twice (build_sim_weight, span.rs:574-602). Unordered near (NearSpansUnordered's heap order among equal
+// cells is the heap array's, span_near.rs:681-696), nested span clauses (add_nested), a span query under a FilteredQuery or in a rescore
+// request are UnsupportedOperation when the query is searched - the caller's CPU path. No boolean query of this mirror can hold one.
+struct SpanNearQuery : Query {
+  std::vector<SpanTermQuery> clauses;
+  int32_t nested = 0;  // clauses that are themselves SpanNearQuerys (add_nested): kept as a count, the query is refused when searched
+  int32_t slop;
+  bool in_order;
+  float boost;
+  explicit SpanNearQuery(std::vector<SpanTermQuery> c, int32_t slop_ = 0, bool in_order_ = true, float b = 1.0f)
+      : clauses(std::move(c)), slop(slop_), in_order(in_order_), boost(b) {
+    if (clauses.size() < 2) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "clauses length must not be smaller than 2!");
+  }
+  SpanNearQuery& add_nested(const SpanNearQuery&) { ++nested; return *this; }
+  void check_served() const {
+    if (!in_order) throw Error(RGPU_ERR_UNSUPPORTED, "an unordered SpanNearQuery is not served by the GPU path");
+    if (nested > 0) throw Error(RGPU_ERR_UNSUPPORTED, "a SpanNearQuery with nested span clauses is not served by the GPU path");
+    if (clauses.size() > RGPU_MAX_PHRASE_TERMS) throw Error(RGPU_ERR_UNSUPPORTED, "a SpanNearQuery of more than RGPU_MAX_PHRASE_TERMS clauses is not served by the GPU path");
+    if (slop < 0) throw Error(RGPU_ERR_UNSUPPORTED, "a SpanNearQuery with a negative slop is not served by the GPU path");
+  }
+};
+
 // BooleanQuery with exact PhraseQuery clauses among its required clauses: +"a b" +c -d #e (rgpu_search_phrase_bool_batch).
 // `required`: BooleanWeight::must_weights — the MUST clauses in query order (must()), then the FILTER clauses (filter(): they
 // score 0); a clause is a phrase or a term. Only the shapes the GPU path serves can be written here: no SHOULD clause, no phrase
@@ -498,6 +528,8 @@ inline bool FilteredQuery::check_served(bool filtered_phrases, bool required_set
     }
     return false;
   }
+  if (dynamic_cast<const SpanNearQuery*>(query) || dynamic_cast<const SpanTermQuery*>(query))
+    throw Error(RGPU_ERR_UNSUPPORTED, "a filtered span query is not served by the GPU path");
   if (dynamic_cast<const FilteredQuery*>(query) || dynamic_cast<const NestedBooleanQuery*>(query))
     throw Error(RGPU_ERR_UNSUPPORTED, "a filtered query over a nested or another filtered query is not served by the GPU path");
   if (as_filter_query) return false;
@@ -1021,16 +1053,21 @@ class GpuIndexSearcher {
   std::vector<TopDocs> search_many(const std::vector<const Query*>& queries, size_t k) {
     for (const Query* q : queries)
       if (dynamic_cast<const PointRangeQuery*>(q)) throw Error(RGPU_ERR_UNSUPPORTED, "a lone point range is not served by the GPU path (the reference matches all of it)");
+    for (const Query* q : queries) {  // refused before any leaf is touched
+      if (const SpanNearQuery* near = dynamic_cast<const SpanNearQuery*>(q)) near->check_served();
+      if (dynamic_cast<const SpanTermQuery*>(q)) throw Error(RGPU_ERR_UNSUPPORTED, "a span query is served by the GPU path as a top-level ordered SpanNearQuery only");
+    }
     for (const Query* q : queries)
       if (dynamic_cast<const FilteredQuery*>(q) || dynamic_cast<const MatchAllDocsQuery*>(q)) return search_filtered(queries, k);
-    std::vector<size_t> phrase_rows, bool_rows, or_rows, plain_rows;
+    std::vector<size_t> phrase_rows, bool_rows, or_rows, span_rows, plain_rows;
     for (size_t i = 0; i < queries.size(); ++i) {
-      if (dynamic_cast<const PhraseQuery*>(queries[i])) phrase_rows.push_back(i);
+      if (dynamic_cast<const SpanNearQuery*>(queries[i])) span_rows.push_back(i);
+      else if (dynamic_cast<const PhraseQuery*>(queries[i])) phrase_rows.push_back(i);
       else if (dynamic_cast<const PhraseBooleanQuery*>(queries[i])) bool_rows.push_back(i);
       else if (dynamic_cast<const PhraseDisjunctionQuery*>(queries[i])) or_rows.push_back(i);
       else plain_rows.push_back(i);
     }
-    if (!phrase_rows.empty() || !bool_rows.empty() || !or_rows.empty()) {
+    if (!phrase_rows.empty() || !bool_rows.empty() || !or_rows.empty() || !span_rows.empty()) {
       std::vector<TopDocs> out(queries.size());
       auto place = [&](const std::vector<size_t>& rows, std::vector<TopDocs> got) { for (size_t i = 0; i < rows.size(); ++i) out[rows[i]] = std::move(got[i]); };
       std::vector<const PhraseBooleanQuery*> bools;
@@ -1049,6 +1086,11 @@ class GpuIndexSearcher {
       }
       if (!bools.empty()) place(bool_rows, search_phrase_bools(bools, k));
       if (!ors.empty()) place(or_rows, search_phrase_ors(ors, k));
+      if (!span_rows.empty()) {
+        std::vector<const SpanNearQuery*> nears;
+        for (size_t i : span_rows) nears.push_back(static_cast<const SpanNearQuery*>(queries[i]));
+        place(span_rows, search_span_nears(nears, k));
+      }
       return out;
     }
     const int32_t nq = static_cast<int32_t>(queries.size());
@@ -1087,6 +1129,35 @@ class GpuIndexSearcher {
       else
         check(rgpu_search_phrase_batch(leaf.segment, qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
                                        leaf_hits[li].data(), leaf_totals[li].data()));
+    }
+    return merge_leaves(leaf_hits, leaf_totals, nq, k);
+  }
+
+  // IndexSearcher::search(SpanNearQuery, TopDocsCollector(k)) for a batch of ordered near queries over SpanTermQuery clauses:
+  // rgpu_search_span_near_batch per leaf, the rows packed as phrases (clause i at position i, `slop` the allowed slop).
+  std::vector<TopDocs> search_span_nears(const std::vector<const SpanNearQuery*>& queries, size_t k) {
+    const int32_t nq = static_cast<int32_t>(queries.size());
+    std::vector<PhraseQuery> as_phrases;
+    std::vector<const PhraseQuery*> rows;
+    for (const SpanNearQuery* q : queries) {
+      q->check_served();
+      std::vector<TermQuery> terms;
+      for (const SpanTermQuery& c : q->clauses) terms.push_back(c.term);
+      as_phrases.emplace_back(std::move(terms), std::vector<int32_t>{}, q->boost, q->slop);
+    }
+    for (const PhraseQuery& p : as_phrases) rows.push_back(&p);
+    std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
+    std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
+    for (size_t li = 0; li < leaves_.size(); ++li) {
+      const LeafReader& leaf = leaves_[li];
+      if (!leaf.pos_bytes) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "span search needs a positions field (LeafReader::pos_bytes)");
+      std::vector<rgpu_phrase_query> qs;
+      std::vector<rgpu_phrase_term> ts;
+      pack_phrases(rows, leaf, &qs, &ts);
+      leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
+      leaf_totals[li].assign(static_cast<size_t>(nq), 0);
+      check(rgpu_search_span_near_batch(leaf.segment, qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), 1, static_cast<int32_t>(k),
+                                        leaf_hits[li].data(), leaf_totals[li].data()));
     }
     return merge_leaves(leaf_hits, leaf_totals, nq, k);
   }
@@ -1230,6 +1301,8 @@ class GpuIndexSearcher {
     std::vector<const PhraseQuery*> phrases;
     for (size_t q = 0; q < requests.size(); ++q) {
       if (!requests[q].query) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "a rescore request needs a query");
+      if (dynamic_cast<const SpanNearQuery*>(requests[q].query) || dynamic_cast<const SpanTermQuery*>(requests[q].query))
+        throw Error(RGPU_ERR_UNSUPPORTED, "rescoring with a span query is not served by the GPU path");
       if (const PhraseQuery* pq = dynamic_cast<const PhraseQuery*>(requests[q].query)) {
         // refused before any leaf is touched (a leaf that lacks the term would serve the row, the next one not)
         for (size_t i = 1; pq->slop > 0 && i < pq->terms.size(); ++i)

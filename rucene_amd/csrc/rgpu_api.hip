@@ -36,6 +36,7 @@
 #include "host/stage_layout.hpp"
 #include "host/term_arena.hpp"
 #include "kernels/search_phrase.hpp"
+#include "kernels/search_span.hpp"
 #include "kernels/search_phrase_bool.hpp"
 #include "host/phrase_bool_plan.hpp"
 #include "kernels/search_phrase_or.hpp"
@@ -4768,10 +4769,13 @@ struct PhraseMatchStage {
   const int64_t* d_cp0;
   const int32_t* d_nl0;
   int64_t collect_items;
+  // rgpu_search_span_near_batch: every live query of the call is an ordered SpanNearQuery (d_sl: its true slops) - the span
+  // kernels run instead of the phrase kernels (any_exact and any_sloppy are false then)
+  bool any_span = false;
 };
 static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const PhraseMatchStage& a) {
   rgpu_ctx* c = seg->ctx;
-  if (a.slots == 0 || !(a.any_exact || a.any_sloppy)) return RGPU_OK;  // no slot, or no live phrase to look at one: d_err stays "fine"
+  if (a.slots == 0 || !(a.any_exact || a.any_sloppy || a.any_span)) return RGPU_OK;  // no slot, or no live phrase to look at one: d_err stays "fine"
   const SegView sv = seg_view(seg);
   const bool legacy = seg->version < 1;
   // One wavefront per candidate slot, first with the small position lists / pools (seven wavefronts per SIMD). A doc that holds
@@ -4844,6 +4848,16 @@ static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const P
       }
     }
   }
+  if (a.any_span) {  // ordered span-near queries: as the exact phrases' ladder, with the span walk (kernels/search_span.hpp)
+    if (legacy) {
+      TimedLaunch tl(c, stream, "k_span_near", 0);
+      exact(k_span_near<true, PHRASE_SMALL_CAP, false>, all_slots, a.slots);
+    } else {
+      TimedLaunch tl(c, stream, "k_span_near_lanes", 0);
+      RGPU_LAUNCH(k_span_near_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl,
+                  (int)a.n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)a.redo_cap, c->d_err + 2);
+    }
+  }
   // ---- which candidates wait for another pass (bits PHRASE_REDO_*): one look per stage that can raise one
   int listed = 0, redo = 0;  // d_err[2]: slots on the list, d_err[3]: the bits
   auto redo_bits = [&]() -> int32_t {
@@ -4859,7 +4873,7 @@ static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const P
   const bool by_list = !legacy && (int64_t)listed <= a.redo_cap;
   const int64_t* const left = by_list ? (const int64_t*)c->phrase_redo.p : all_slots;
   const int64_t n_left = by_list ? (int64_t)listed : a.slots;
-  if (HostClock::on() && (redo & (PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES)))
+  if (HostClock::on() && (redo & (PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES | PHRASE_REDO_SPAN_LANES)))
     std::fprintf(stderr, "[phrase] %d of %lld candidate slots left for the one-candidate kernels\n", listed, (long long)a.slots);
   if (redo & PHRASE_REDO_LANES) {
     TimedLaunch tl(c, stream, "k_phrase_match(left by the 64-candidate kernel)", 0);
@@ -4869,10 +4883,18 @@ static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const P
     TimedLaunch tl(c, stream, "k_sloppy_match(left by the 64-candidate kernel)", 0);  // (the groups are there: computed in front of the 64-candidate kernels)
     sloppy(k_sloppy_match<false, SLOPPY_SMALL_POOL, true>, left, n_left);
   }
-  if (redo & (PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES)) RGPU_TRY(redo_bits());
+  if (redo & PHRASE_REDO_SPAN_LANES) {
+    TimedLaunch tl(c, stream, "k_span_near(left by the 64-candidate kernel)", 0);
+    exact(k_span_near<false, PHRASE_SMALL_CAP, true>, left, n_left);
+  }
+  if (redo & (PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES | PHRASE_REDO_SPAN_LANES)) RGPU_TRY(redo_bits());
   if (redo & PHRASE_REDO_WIDE) {
     TimedLaunch tl(c, stream, "k_phrase_match(wide lists)", 0);
     if (legacy) exact(k_phrase_match<true, PHRASE_LIST_CAP, true>, left, n_left); else exact(k_phrase_match<false, PHRASE_LIST_CAP, true>, left, n_left);
+  }
+  if (redo & PHRASE_REDO_SPAN_WIDE) {
+    TimedLaunch tl(c, stream, "k_span_near(wide lists)", 0);
+    if (legacy) exact(k_span_near<true, PHRASE_LIST_CAP, true>, left, n_left); else exact(k_span_near<false, PHRASE_LIST_CAP, true>, left, n_left);
   }
   if (redo & PHRASE_REDO_SLOPPY) {
     TimedLaunch tl(c, stream, "k_sloppy_match(wide pool)", 0);
@@ -5024,9 +5046,22 @@ static int32_t check_phrases_query(const rgpu_segment* seg, const BoolQuery& Q, 
   return RGPU_OK;
 }
 
+// rgpu_search_span_near_batch: clause i of a span-near query is rgpu_phrase_term i with position = i, reserved = 0
+static int32_t check_span_clauses(const rgpu_phrase_query& Q, const rgpu_phrase_term* terms) {
+  for (int i = 0; i < Q.n_terms; ++i) {
+    const rgpu_phrase_term& t = terms[Q.first_term + i];
+    if (t.position != i) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "span near: rgpu_phrase_term.position must be the clause's index");
+    if (t.reserved != 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "span near: rgpu_phrase_term.reserved must be 0");
+  }
+  return RGPU_OK;
+}
+
 static int32_t search_phrase_batch_impl(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_query* queries, int32_t n_queries,
                                         const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
-                                        int64_t* total_hits_out) {
+                                        int64_t* total_hits_out, bool span = false) {
+  // span: rgpu_search_span_near_batch - the queries are ordered SpanNearQuerys over SpanTermQuery clauses. The plan, the candidate
+  // stage and the collectors are the phrases'; the match stage runs the span kernels, and the collectors are handed a marker in
+  // place of the slops: SpanScorer is two-phase whatever the slop (span.rs:1033-1091), so next_limit applies at slop 0 too.
   if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !hits_out || !total_hits_out)
     return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
   if (set) { RGPU_TRY(docset_check(seg, set)); RGPU_TRY(refuse_sloppy_masked(queries, n_queries)); }
@@ -5041,6 +5076,7 @@ static int32_t search_phrase_batch_impl(rgpu_segment* seg, rgpu_docset* set, con
   for (int32_t q = 0; q < n_queries; ++q) {
     RGPU_TRY(check_phrase_query(c, queries[q], n_terms_total, true));
     RGPU_TRY(check_phrase_terms(seg, queries[q], terms, &ptrs));
+    if (span) RGPU_TRY(check_span_clauses(queries[q], terms));
   }
   PhraseMask masked;
   RGPU_TRY(masked.install(seg, set));
@@ -5061,6 +5097,9 @@ static int32_t search_phrase_batch_impl(rgpu_segment* seg, rgpu_docset* set, con
   std::vector<PosTerm> pt;
   std::vector<int64_t> item_prefix((size_t)n_queries + 1), emit_prefix((size_t)n_queries + 1), collect_prefix((size_t)n_queries + 1);
   std::vector<int32_t> slops((size_t)n_queries, 0), limits((size_t)n_queries, -1);
+  std::vector<int32_t> two_phase;  // span: what the collectors read in place of the slops - 1 for every live query
+  if (span) two_phase.assign((size_t)n_queries, 0);
+  bool any_span = false;
   int64_t collect_items = 0;
   bool any_cutoff = false;
   bool any_sloppy = false, any_exact = false;
@@ -5085,14 +5124,21 @@ static int32_t search_phrase_batch_impl(rgpu_segment* seg, rgpu_docset* set, con
     slops[(size_t)q] = Q.slop;
     limits[(size_t)q] = Q.next_limit == 0 ? 500000 /* searcher.rs:47 DEFAULT_DISMATCH_NEXT_LIMIT */
                                           : (Q.next_limit == RGPU_NEXT_LIMIT_ZERO ? 0 /* DefaultIndexSearcher::new(reader, Some(0)) */ : Q.next_limit);
-    (Q.slop > 0 ? any_sloppy : any_exact) = true;
-    if (Q.slop > 0) for (size_t i = pt.size() - (size_t)Q.n_terms; i < pt.size(); ++i) sloppy_rpts = sloppy_rpts || pt[i].same_as != pt[i].query_ord;
+    if (span) {
+      // the loaders hand out position - phrase_pos: a span clause's positions are the term's own
+      for (size_t i = pt.size() - (size_t)Q.n_terms; i < pt.size(); ++i) pt[i].phrase_pos = 0;
+      two_phase[(size_t)q] = 1;
+      any_span = true;
+    } else {
+      (Q.slop > 0 ? any_sloppy : any_exact) = true;
+    }
+    if (!span && Q.slop > 0) for (size_t i = pt.size() - (size_t)Q.n_terms; i < pt.size(); ++i) sloppy_rpts = sloppy_rpts || pt[i].same_as != pt[i].query_ord;
     dq[(size_t)q].n_terms = Q.n_terms;
     const DevTerm& lead = dt[(size_t)dq[(size_t)q].first_term];
     items += lead_items(lead, blocks_per_item);
     slots += lead_slots(lead);
     collect_items += lead_collect_chunks(lead);
-    any_cutoff = any_cutoff || (Q.slop > 0 && limits[(size_t)q] >= 0);
+    any_cutoff = any_cutoff || ((span || Q.slop > 0) && limits[(size_t)q] >= 0);
   }
   item_prefix[(size_t)n_queries] = items;
   emit_prefix[(size_t)n_queries] = slots;
@@ -5107,6 +5153,7 @@ static int32_t search_phrase_batch_impl(rgpu_segment* seg, rgpu_docset* set, con
     const auto r_pt = st.add<PosTerm>(pt.size());
     const auto r_ip = st.add<int64_t>(nq + 1), r_ep = st.add<int64_t>(nq + 1);
     const auto r_sl = st.add<int32_t>(nq), r_nl = st.add<int32_t>(nq);
+    const auto r_tp = st.add_if<int32_t>(span, nq);
     const auto r_gr = st.add<SloppyGroups>(nq);  // written by k_sloppy_groups
     const auto r_cp = st.add<int64_t>(nq + 1);   // the chunked collector's items
     const auto r_ab = st.add<int32_t>(nq);       // k_phrase_cutoff's flags (zeroed by the copy)
@@ -5118,6 +5165,7 @@ static int32_t search_phrase_batch_impl(rgpu_segment* seg, rgpu_docset* set, con
     sg.put(r_t, dt);
     sg.put(r_pt, pt);
     sg.put(r_sl, slops);
+    sg.put(r_tp, two_phase);
     sg.put(r_nl, limits);
     sg.put(r_ip, item_prefix);
     sg.put(r_ep, emit_prefix);
@@ -5138,22 +5186,32 @@ static int32_t search_phrase_batch_impl(rgpu_segment* seg, rgpu_docset* set, con
     int64_t redo_cap = 0;
     // (k_emit: the conjunction only emits candidates, its (empty) top-k lists are the narrow kind)
     const char* stage_name = masked.on() ? masked_stage_name(c, "k_search_and(masked phrase candidates)", "k_search_and(masked phrase, marked)")
-                                         : "k_search_and(phrase candidates)";
+                                         : (span ? "k_search_and(span candidates)" : "k_search_and(phrase candidates)");
+    const int32_t* d_collect_sl = span ? sg.dev(r_tp) : d_sl;  // "two-phase" to the collectors: slop > 0, or a span query
     RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{stage_name, d_q, d_t, sg.dev(r_ip), d_ep, clause_bitmaps.empty() ? nullptr : sg.dev(r_bm),
                                                       n_queries, nq, items, slots, blocks_per_item, std::min<int>(k, 64), false,
                                                       chunked ? (size_t)collect_items * (size_t)k : 0, chunked ? (size_t)collect_items : 0,
                                                       &redo_cap, false /* the collectors read a query's first emit_count slots only */,
                                                       masked.on() && c->phrase_mask_compact}));
     RGPU_TRY(phrase_match_stage(seg, stream, PhraseMatchStage{d_q, d_t, sg.dev(r_pt), d_ep, d_sl, sg.dev(r_gr), n_queries, slots, redo_cap, any_exact, any_sloppy,
-                                                              sloppy_rpts, true, d_cut, d_cp, d_nl, collect_items}));
-    phrase_collect_stage(seg, stream, PhraseCollectStage{d_ep, d_cp, d_sl, d_nl, n_queries, k, collect_items, any_cutoff, sg.dev(r_ab), d_cut});
+                                                              sloppy_rpts, true, d_cut, d_cp, d_nl, collect_items, any_span}));
+    phrase_collect_stage(seg, stream, PhraseCollectStage{d_ep, d_cp, d_collect_sl, d_nl, n_queries, k, collect_items, any_cutoff, sg.dev(r_ab), d_cut});
     HIP_TRY(launch_status());
   }
   // the verdict in the same round as the rows (nothing launched: nothing to ask, and d_err may hold another call's)
   int err = 0;
   RGPU_TRY(api_rows_read_back(c, stream, n_queries, k, hits_out, total_hits_out, items > 0 ? &err : nullptr));
-  return phrase_match_status(err, "a doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)",
+  return phrase_match_status(err, span ? "a doc holds the term of a span clause more than 1024 times"
+                                       : "a doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)",
                              "internal: a conjunction match was not found again");
+}
+// (include/rucene_gpu.h rgpu_search_span_near_batch; the match kernels: kernels/search_span.hpp)
+extern "C" int32_t rgpu_search_span_near_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
+                                               const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t in_order, int32_t k,
+                                               rgpu_hit* hits_out, int64_t* total_hits_out) {
+  // NearSpansUnordered pops a BinaryHeap whose order among cells at equal (start, end) is the heap array's (span_near.rs:681-696)
+  if (in_order == 0) return fail(RGPU_ERR_UNSUPPORTED, "span near: only in_order = true is served");
+  return search_phrase_batch_impl(seg, nullptr, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out, true);
 }
 extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
                                             const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,

@@ -253,6 +253,89 @@ class PhraseQuery:
             raise RgpuError(-2, "Must have as many terms as positions")
 
 
+class SpanTermQuery:
+    """query/spans/span_term.rs: the spans [position, position + 1) of one term. Served as a clause of an ordered SpanNearQuery
+    (whose weight takes the near query's boost alone: a clause's `boost` only travels with extract_terms)."""
+
+    def __init__(self, term, boost=1.0):
+        self.term = bytes(term) if isinstance(term, (bytes, bytearray, memoryview)) else int(term)
+        self.boost = float(boost)
+
+    def extract_terms(self):
+        return [TermQuery(self.term, self.boost)]
+
+    def __str__(self):
+        return "SpanTermQuery(field: body, term: %r)" % (self.term,)
+
+
+class SpanNearQuery:
+    """SpanNearQuery::new (query/spans/span_near.rs:101-124): `clauses` within `slop` positions of each other, in the clauses' order
+    when in_order. The GPU path serves a top-level query with in_order=True whose clauses are all SpanTermQuery
+    (rgpu_search_span_near_batch); unordered near and nested span clauses are UnsupportedOperation when the query is searched, i.e.
+    the caller's CPU path, and so is a span query inside BooleanQuery, FilterQuery, DisjunctionMaxQuery, BoostingQuery or a rescoring.
+    The weight sums the idf of every clause's term, a term named twice counted twice (build_sim_weight, span.rs:574-602)."""
+
+    def __init__(self, clauses, slop=0, in_order=True, boost=1.0):
+        self.clauses = list(clauses)
+        self.slop, self.in_order, self.boost = int(slop), bool(in_order), float(boost)
+        if len(self.clauses) < 2:
+            raise RgpuError(-2, "clauses length must not be smaller than 2!")
+        if not all(isinstance(c, (SpanTermQuery, SpanNearQuery)) for c in self.clauses):
+            raise RgpuError(-2, "SpanNearQuery takes span queries as clauses")
+
+    def served_by_gpu(self):
+        """None, or why the GPU path leaves this query to the CPU searcher"""
+        if not self.in_order:
+            return "an unordered SpanNearQuery is not served by the GPU path"
+        if not all(isinstance(c, SpanTermQuery) for c in self.clauses):
+            return "a SpanNearQuery with nested span clauses is not served by the GPU path"
+        if len(self.clauses) > _lib.MAX_PHRASE_TERMS:
+            return "a SpanNearQuery of more than %d clauses is not served by the GPU path" % _lib.MAX_PHRASE_TERMS
+        if self.slop < 0:   # (NearSpansOrdered would match nothing: match_width >= 0)
+            return "a SpanNearQuery with a negative slop is not served by the GPU path"
+        return None
+
+    # the phrase packer's view of the query (GpuIndexSearcher.pack_phrases): clause i's term at "position" i
+    @property
+    def terms(self):
+        return [c.term for c in self.clauses]
+
+    @property
+    def positions(self):
+        return list(range(len(self.clauses)))
+
+    def extract_terms(self):
+        return [t for c in self.clauses for t in c.extract_terms()]
+
+    def __str__(self):
+        return "SpanNearQuery(clauses: [%s], slop: %d, in_order: %s)" % (", ".join(str(c) for c in self.clauses), self.slop, str(self.in_order).lower())
+
+
+def _holds_span(query):
+    """a span query anywhere inside `query`"""
+    if isinstance(query, (SpanTermQuery, SpanNearQuery)):
+        return True
+    if isinstance(query, BooleanQuery):
+        return any(_holds_span(q) for q in list(query.must_queries) + list(query.should_queries) + list(query.must_not_queries) + list(query.filter_queries))
+    if isinstance(query, FilterQuery):
+        return _holds_span(query.query)
+    if isinstance(query, DisjunctionMaxQuery):
+        return any(_holds_span(q) for q in query.disjuncts)
+    if isinstance(query, BoostingQuery):
+        return _holds_span(query.positive) or _holds_span(query.negative)
+    return False
+
+
+def _refuse_unserved_spans(query):
+    """UnsupportedOperation for every span query but a top-level ordered SpanNearQuery over SpanTermQuery clauses"""
+    if isinstance(query, SpanNearQuery):
+        why = query.served_by_gpu()
+        if why:
+            raise RgpuError(-5, why)
+    elif _holds_span(query):
+        raise RgpuError(-5, "a span query is served by the GPU path as a top-level ordered SpanNearQuery only")
+
+
 class PointRangeQuery:
     """search/query/point_range_query.rs: the docs that hold a point of `field` with lower <= value <= upper, both ends inclusive,
     in unsigned byte order of the sortable bytes. ONE dimension: `lower_bytes` / `upper_bytes` are one encoded value each (4 or 8
@@ -420,9 +503,11 @@ class BooleanQuery:
         # (a PointRangeQuery under MUST / FILTER / MUST_NOT likewise: GpuIndexSearcher.range_filter makes its doc set)
         # (a MatchAllDocsQuery under MUST is the every-doc set: GpuIndexSearcher(required_sets=True). A query of MUST_NOT clauses alone
         # gets one from the reference's build(); here the searcher supplies it when it peels such a query, the tree stays as given)
-        if any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, PointRangeQuery, MatchAllDocsQuery)) for q in list(musts)) or \
-                any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery)) for q in list(shoulds)) or \
-                any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, CachedFilter, PointRangeQuery)) for q in list(must_nots) + list(filters)):
+        # (a span clause builds too; no tree with one is served: GpuIndexSearcher.search_batch refuses it as UnsupportedOperation)
+        spans = (SpanTermQuery, SpanNearQuery)
+        if any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, PointRangeQuery, MatchAllDocsQuery) + spans) for q in list(musts)) or \
+                any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery) + spans) for q in list(shoulds)) or \
+                any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, CachedFilter, PointRangeQuery) + spans) for q in list(must_nots) + list(filters)):
             raise RgpuError(-5, "only term, phrase and boolean clauses are known to this mirror")
         return BooleanQuery(list(musts), list(shoulds), msm, list(must_nots), list(filters))
 
@@ -983,6 +1068,8 @@ class GpuIndexSearcher:
         req["query_weight"], req["rescore_weight"], req["mode"] = query_weight, rescore_weight, mode
         req["window_size"] = k if window_size is None else window_size
         is_phrase = np.array([isinstance(q, PhraseQuery) for q in rescore_queries], dtype=bool)
+        if any(_holds_span(q) for q in rescore_queries):
+            raise RgpuError(-5, "rescoring with a span query is not served by the GPU path")
         for q in rescore_queries:   # refused before any leaf is touched (a leaf that lacks the term would serve the row, the next one not)
             if isinstance(q, PhraseQuery) and q.slop > 0 and len(set(q.terms)) < len(q.terms):
                 raise RgpuError(-5, "phrase rescoring: a sloppy phrase that names a term twice is not served")
@@ -1374,10 +1461,12 @@ class GpuIndexSearcher:
         """-> (hits[n][k] structured {doc, score}, total_hits[n]) merged over all leaves. A batch may mix term / boolean / dismax /
         boosting queries (rgpu_search_batch), PhraseQuery rows (rgpu_search_phrase_batch), BooleanQuery rows with phrases among their
         required clauses (rgpu_search_phrase_bool_batch) and BooleanQuery rows of SHOULD / MUST_NOT clauses with phrases among the
-        SHOULD ones (rgpu_search_phrase_or_batch): one call per kind and leaf, rows keep their order. Rows with doc-set clauses
+        SHOULD ones (rgpu_search_phrase_or_batch) and top-level ordered SpanNearQuery rows over SpanTermQuery clauses
+        (rgpu_search_span_near_batch; any other span query is UnsupportedOperation): one call per kind and leaf, rows keep their order. Rows with doc-set clauses
         (CachedFilter under FILTER / MUST_NOT, FilterQuery) are grouped by their combination of sets and searched masked
         (rgpu_search_batch_masked; with filtered_phrases the phrase kinds through their masked calls), one call per group, kind and leaf."""
         for q in queries:   # refused before any leaf is touched and before any range's set is built
+            _refuse_unserved_spans(q)
             self._peel(q, build=False)
         if getattr(self, "_range_filters", None):   # (a batch on a searcher that never built a range filter goes the way it went)
             self.drop_range_filters(keep=self.range_filter_capacity)
@@ -1405,6 +1494,8 @@ class GpuIndexSearcher:
         def kind(q):
             if isinstance(q, PhraseQuery):
                 return 1
+            if isinstance(q, SpanNearQuery):
+                return 4
             if isinstance(q, BooleanQuery) and q.has_phrases():   # no MUST, no FILTER: the disjunction route; else phrase_bool_parts decides
                 return 2 if (q.must_queries or q.filter_queries) else 3
             return 0
@@ -1419,7 +1510,9 @@ class GpuIndexSearcher:
         else:
             if masks is not None and (not getattr(self, "filtered_phrases", False) or any(q.slop > 0 for q in queries if isinstance(q, PhraseQuery))):
                 raise RgpuError(-5, "a filtered phrase is not served by the GPU path")
-            rows = [np.flatnonzero(np.array(kinds) == kd) for kd in (0, 1, 2, 3)]
+            if masks is not None and 4 in kinds:
+                raise RgpuError(-5, "a filtered span query is not served by the GPU path")
+            rows = [np.flatnonzero(np.array(kinds) == kd) for kd in (0, 1, 2, 3, 4)]
             groups = [[queries[i] for i in r] for r in rows]
             for q in groups[2]:   # refused before any leaf is touched
                 self.phrase_bool_parts(q)
@@ -1443,6 +1536,9 @@ class GpuIndexSearcher:
                     packed = self.pack_phrase_or(groups[3], leaf)
                     hits[rows[3]], totals[rows[3]] = (seg.search_phrase_or_batch(*packed, k) if masks is None
                                                       else seg.search_phrase_or_batch_masked(masks[i], *packed, k))
+                if groups[4]:   # ordered SpanNearQuery rows: packed as phrases, clause i at position i
+                    qs, ts = self.pack_phrases(groups[4], leaf)
+                    hits[rows[4]], totals[rows[4]] = seg.search_span_near_batch(qs, ts, k)
                 per_leaf.append((hits, totals))
         return per_leaf
 
