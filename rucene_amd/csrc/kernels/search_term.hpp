@@ -99,20 +99,130 @@ __device__ __forceinline__ uint64_t group_kth(const GroupList& g, int k) {
   const uint64_t v = __hip_atomic_load(g.keys + (k - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   return ((uint64_t)(uint32_t)readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)readfirstlane((int)(uint32_t)v);
 }
+#ifndef RGPU_TERM_RANK_MERGE  // 1: 3 .. RGPU_TERM_RANK_MERGE_MAX entering keys are ranked and scattered (variant builds, scripts/ab.sh)
+#define RGPU_TERM_RANK_MERGE 0
+#endif
+#ifndef RGPU_TERM_RANK_MERGE_MAX
+#define RGPU_TERM_RANK_MERGE_MAX 16  // more entering keys than this keep the insertions
+#endif
+#ifndef RGPU_TERM_LEVEL_CUT  // 0: every candidate of a block reaches the lock (variant builds)
+#define RGPU_TERM_LEVEL_CUT 1
+#endif
+#ifndef RGPU_TERM_LEVEL_CUT_MIN
+#define RGPU_TERM_LEVEL_CUT_MIN 16  // candidates (against the caller's threshold) from which a block is cut to its best score levels before the lock
+#endif
+#ifdef RGPU_TERM_TRACE  // k_search_term_query's timeline: shader cycles spent waiting for the lock / holding it, offers, keys entered
+#define TERM_LK_PARAM , uint32_t (&lk)[4]
+#define TERM_LK_NOW(v) const uint64_t v = (uint64_t)clock64()
+#define TERM_LK_ADD(i, since) lk[i] += (uint32_t)((uint64_t)clock64() - (since))
+#define TERM_LK_COUNT(i, n) lk[i] += (uint32_t)(n)
+#define TERM_LK_DECL uint32_t lk[4] = {0, 0, 0, 0}
+#define TERM_LK_PASS , lk
+#else
+#define TERM_LK_PARAM
+#define TERM_LK_DECL do {} while (0)
+#define TERM_LK_PASS
+#define TERM_LK_NOW(v) do {} while (0)
+#define TERM_LK_ADD(i, since) do {} while (0)
+#define TERM_LK_COUNT(i, n) do {} while (0)
+#endif
 // Offer two keys per lane (0 == none) to the group's list; `tau` returns the entry threshold afterwards.
+// What the query kernel's timeline shows (scripts/term_query_timeline.py on a -DRGPU_TERM_TRACE build): the launch's
+// longest workgroups are the lists of 1-15 blocks. They have no sketch, so their waves meet an EMPTY list with 128 candidates
+// each: the first to get the lock pays ~35 insertions (a key enters whenever it beats the k best of the keys in front of it, in doc
+// order) while the others wait — lock wait + lock hold were 39 % of those workgroups' wave-cycles.
+// The level cut, in front of the lock: a block with more than max(k, RGPU_TERM_LEVEL_CUT_MIN) candidates against the caller's
+// threshold (a lower bound of the list's, which only rises) is cut to its best SCORE LEVELS — one wave maximum and two ballots per
+// level, from the top, until the levels cover k keys. A key below the last level has k keys of its own block above it and cannot
+// be in the top-k whatever the list holds; the keys of the last level tie, doc ascending decides, and the insertions take the
+// first of them and skip the rest at one ballot each. A term's scores take few values (freq x norm rank), so k keys are
+// covered after a few levels, and an empty list then costs min(k, n) insertions instead of ~k (1 + ln(n / k)).
+// The rank merge (RGPU_TERM_RANK_MERGE=1, variant builds): for 3 <= n <= RGPU_TERM_RANK_MERGE_MAX keys entering under the lock, the
+// list and the candidates are RANKED against each other instead of one insertion per key. The candidates are compacted to lanes
+// 0 .. n-1 of one register (ballot + mbcnt through the wave's own staging slab, which is free once the block's doc deltas are in
+// registers: no new LDS, and key0 / key1 are dead from there on). Candidate i is then read as a scalar x; two ballots give its
+// place in the merged order — popc(L > x) list keys and popc(c > x) candidates above it — and lane i stores it there; every lane
+// counts the candidates above its own list key L (its shift). Then L goes to keys[lane + shift]. Keys are unique, so the targets
+// are a permutation of 0 .. 63 + n, and every lane has L in a register before any lane writes; what lands at 64 or beyond is
+// dropped. The list stays sorted as a whole. Ranks below k hold exactly what the insertions leave: a key the insertions skip
+// because the threshold rose inside the block lands at a rank >= k, which nobody reads (group_kth, the list's writers: as after
+// topk_merge_sorted). keys[k - 1] is written once, as by the insertions' write-back. MEASURED and left off: an iteration is a
+// chain of readlane -> compare -> popcount -> store through the scalar unit and costs about what an insertion does (lock hold per
+// offer 2551 against 2435 cycles in the longest workgroups), and the drain loop of k_search_term_query<false, false, 4> takes 65
+// VGPRs with it instead of 63.
+// WIDE lists (k > 64, two registers per lane) take neither.
+static_assert(RGPU_TERM_RANK_MERGE_MAX >= 3 && RGPU_TERM_RANK_MERGE_MAX <= 64 && 8 * RGPU_TERM_RANK_MERGE_MAX <= TERM_BLOCK_SLAB,
+              "the candidates of a rank merge fit one register and the staging slab");
 template <bool WIDE>
 __device__ __forceinline__ void group_offer2(const GroupList& g, uint64_t key0, uint64_t key1, uint64_t& tau, int k, int lane,
-                                             uint64_t floor) {
+                                             uint64_t floor, uint8_t* slab TERM_LK_PARAM) {
+  // slab: this wave's staging slab, its contents no longer needed; tau: a threshold the list has reached (or 0)
+#if RGPU_TERM_LEVEL_CUT
+  if (!WIDE && __popcll(__ballot(key0 > tau)) + __popcll(__ballot(key1 > tau)) > (k > RGPU_TERM_LEVEL_CUT_MIN ? k : RGPU_TERM_LEVEL_CUT_MIN)) {
+    // score levels from the top (a key's high word: the score's order bits; 0 = no key) until k keys are covered
+    uint32_t level = 0xffffffffu;
+    for (int have = 0; have < k;) {
+      const uint32_t h0 = (uint32_t)(key0 >> 32), h1 = (uint32_t)(key1 >> 32);
+      const uint32_t b0 = h0 < level ? h0 : 0u, b1 = h1 < level ? h1 : 0u;
+      const uint32_t t = wave_reduce_max_u32(b0 > b1 ? b0 : b1);
+      if (t == 0u) { level = 0u; break; }  // fewer than k keys in all
+      have += __popcll(__ballot(h0 == t)) + __popcll(__ballot(h1 == t));
+      level = t;
+    }
+    key0 = (uint32_t)(key0 >> 32) >= level ? key0 : 0ull;
+    key1 = (uint32_t)(key1 >> 32) >= level ? key1 : 0ull;
+  }
+#endif
+  TERM_LK_NOW(lk_t0);
+  TERM_LK_COUNT(2, 1);
   group_lock(g.lock, lane);
+  TERM_LK_ADD(0, lk_t0);
+  TERM_LK_NOW(lk_t1);
   WaveTopK top;
   top.a = g.keys[lane];
   if (WIDE) top.b = g.keys[64 + lane];
   const uint64_t kth = topk_threshold<WIDE>(top, k);
   tau = kth > floor ? kth : floor;
+#if RGPU_TERM_RANK_MERGE
+  const uint64_t m0 = __ballot(key0 > tau), m1 = __ballot(key1 > tau);
+  const int n0 = __popcll(m0), n = n0 + __popcll(m1);
+  TERM_LK_COUNT(3, n);
+  if (!WIDE && n > 2 && n <= RGPU_TERM_RANK_MERGE_MAX) {
+    uint64_t* stage = reinterpret_cast<uint64_t*>(slab);
+    // (the lane index made opaque: the addresses below are then computed here, on the rare path, instead of being hoisted out of
+    // the caller's block loop into registers of their own — 65-66 VGPRs in k_search_term_query<false, false, 4> instead of 63)
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    if ((m0 >> ln) & 1ull) stage[mbcnt(m0)] = key0;
+    if ((m1 >> ln) & 1ull) stage[n0 + mbcnt(m1)] = key1;
+    wave_sync();
+    const uint64_t c = ln < n ? stage[ln] : 0ull;
+    wave_sync();  // (the slab is the caller's again)
+    const uint64_t L = top.a;
+    int shift = 0;
+    for (int i = 0; i < n; ++i) {
+      const uint64_t x = readlane64(c, i);
+      const bool above = L > x;
+      const int at = __popcll(__ballot(above)) + __popcll(__ballot(c > x));
+      shift += above ? 0 : 1;  // (L != x: the list's keys and the block's are different docs; an empty slot is below everything)
+      if (ln == i && at < 64) g.keys[at] = c;
+    }
+    if (ln + shift < 64) g.keys[ln + shift] = L;
+    wave_sync();
+    const uint64_t now = group_kth<WIDE>(g, k);
+    tau = now > floor ? now : floor;
+    TERM_LK_ADD(1, lk_t1);
+    group_unlock(g.lock, lane);
+    return;
+  }
+#else
+  TERM_LK_COUNT(3, __popcll(__ballot(key0 > tau)) + __popcll(__ballot(key1 > tau)));
+#endif
   topk_offer<WIDE>(top, key0, tau, k, lane, floor);
   topk_offer<WIDE>(top, key1, tau, k, lane, floor);
   g.keys[lane] = top.a;
   if (WIDE) g.keys[64 + lane] = top.b;
+  TERM_LK_ADD(1, lk_t1);
   group_unlock(g.lock, lane);
 }
 
@@ -147,6 +257,7 @@ __device__ __forceinline__ void term_blocks_fast(const SegView& seg, const DevTe
                                                  SharedTau& shared, uint64_t& floor, int k, int& count, bool prune, uint32_t& looked,
                                                  uint32_t& touched, uint64_t ceil, bool exchange, bool head TERM_PH_PARAM) {
   constexpr int DEPTH = PREFETCH_DEPTH;
+  TERM_LK_DECL;
   TERM_PH_NOW(ph_enter);
   const uint8_t* term_rows = seg.bstore + T.bs_base;
   const uint8_t* pn = seg.pnorm + T.pn_base;
@@ -344,7 +455,7 @@ __device__ __forceinline__ void term_blocks_fast(const SegView& seg, const DevTe
         TERM_PH_ADD(4, ph_s2);
         TERM_PH_NOW(ph_s3);
         if (__ballot((key0 > key1 ? key0 : key1) > tau)) {
-          group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor);
+          group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor, slab TERM_LK_PASS);
 #ifdef RGPU_TERM_TRACE
           ph[7] += 1u;
 #endif
@@ -643,6 +754,7 @@ __global__ __launch_bounds__(TERM_THREADS, (LEGACY || WIDE) ? RGPU_TERM_OTHER_WA
     // one look at what earlier workgroups of this query already achieved (per-block exchanges through HBM cost
     // far more in same-address atomics than they save in insertions), one publication when the group is done
     uint64_t floor = 0, tau = 0;
+    TERM_LK_DECL;
     const uint64_t seen = shared.peek();
     float k1;
     load_sim_table(seg, T.sim_table, cache, lane, k1);
@@ -676,7 +788,7 @@ __global__ __launch_bounds__(TERM_THREADS, (LEGACY || WIDE) ? RGPU_TERM_OTHER_WA
       count += __popcll(__ballot(v0)) + __popcll(__ballot(v1));
       const uint64_t key0 = v0 ? below(make_key(s0, d0), ceil) : 0ull, key1 = v1 ? below(make_key(s1, d1), ceil) : 0ull;
       // `tau` may lag behind the group's list: a stale threshold only lets more keys through to the locked offer
-      if (__ballot((key0 > key1 ? key0 : key1) > tau)) group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor);
+      if (__ballot((key0 > key1 ? key0 : key1) > tau)) group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor, slab TERM_LK_PASS);
     };
 
     const int b0 = chunk * blocks_per_item;

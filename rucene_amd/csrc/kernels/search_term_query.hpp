@@ -32,6 +32,9 @@ constexpr int TQ_CHUNK_UNROLL = 4;      // chunk frontier words per thread per g
 #define RGPU_TERMQ_STEP_CHUNKS 2
 #endif
 constexpr int TQ_STEP_CHUNKS = RGPU_TERMQ_STEP_CHUNKS;  // surviving chunks per wave per gather step
+#ifndef RGPU_TERMQ_FAST_WAVES
+#define RGPU_TERMQ_FAST_WAVES RGPU_TERM_FAST_WAVES
+#endif
 static_assert(TQ_CAP >= 64 && TQ_CAP <= 65536, "queue positions are u16 and a chunk must fit an empty queue");
 
 // the entry test of term_blocks_fast on raw score bits: a block whose postings' best score is `bound` can enter iff
@@ -55,9 +58,27 @@ __device__ __forceinline__ uint32_t term_bound_of(const float* cache, uint64_t w
   return fmax > (uint32_t)SCORE_TABLE_FREQS ? 0xffffffffu : bb;
 }
 
+#ifdef RGPU_TERM_TRACE  // developer instrumentation (variant builds only): one record per WORKGROUP of k_search_term_query in g_term_trace
+// (three of k_search_term's records each; read back by rgpu_debug_trace, printed by scripts/term_query_timeline.py).
+// d[]: 10 ns ticks from t0 to: descriptor in registers, table built, sketch folded, end of the first gather, end of the first sort,
+// end of the drain (every wave past its last block), end of the tail. cyc[w]: wave w's shader-clock cycles {waiting for the list's
+// lock, holding it, the rest of step()} up to the end of the drain; wave0_cycles: wave 0's shader clock over the same ticks as d[5].
+struct TermQueryTraceRec {
+  unsigned long long t0, t1;
+  int32_t q, nblocks, rounds, entries, unpacked, offers, entered;
+  unsigned int d[7];
+  unsigned int waves, wave0_cycles;
+  unsigned int cyc[8][3];
+  unsigned int pad[16];
+};
+static_assert(sizeof(TermQueryTraceRec) == 3 * sizeof(TermTraceRec), "a workgroup's record takes three slots of g_term_trace");
+#define TQ_TR(slot, dep) do { asm volatile("" :: "v"(dep)); tq_d[slot] = (unsigned int)((unsigned long long)wall_clock64() - tq_t0); } while (0)
+#else
+#define TQ_TR(slot, dep) do {} while (0)
+#endif
 
 template <bool LEGACY, bool WIDE, int W>
-__global__ __launch_bounds__(64 * W, (LEGACY || WIDE) ? RGPU_TERM_OTHER_WAVES : RGPU_TERM_FAST_WAVES)
+__global__ __launch_bounds__(64 * W, (LEGACY || WIDE) ? RGPU_TERM_OTHER_WAVES : RGPU_TERMQ_FAST_WAVES)
 void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, const DevTerm* __restrict__ terms,
                          const int32_t* __restrict__ order, int n_queries, int k, unsigned long long* __restrict__ work_slots,
                          const int32_t* __restrict__ qmap, HitOut* __restrict__ hits, int64_t* __restrict__ totals, int32_t doc_base,
@@ -85,6 +106,15 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
   const int lane = lane_id();
   const int wave = wave_id();
   const int tid = (int)threadIdx.x;
+#ifdef RGPU_TERM_TRACE
+  __shared__ uint32_t tq_w[8][5];  // per wave: lock wait, lock hold, step() in all, offers, keys entered
+  const unsigned long long tq_t0 = (unsigned long long)wall_clock64();
+  const uint64_t tq_c0 = (uint64_t)clock64();
+  unsigned int tq_d[7] = {0, 0, 0, 0, 0, 0, 0};
+  uint32_t tq_step = 0;
+  int tq_rounds = 0, tq_entries = 0;
+#endif
+  TERM_LK_DECL;
   int q, row, rec;
   if (launch != nullptr) {
     if ((int)blockIdx.x >= n_queries) return;
@@ -111,6 +141,7 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
     return;
   }
   const DevTerm T = terms[rec];
+  TQ_TR(0, T.df);
   const bool has_norms = seg.norms != nullptr;
   const bool tabled = has_norms && seg.n_norm_ranks > 0;
   const bool fast = tabled && seg.live == nullptr && T.weight >= 0.0f && RGPU_TERM_PRUNE && (T.flags & TERM_FLAG_MONOTONE) != 0u;
@@ -129,6 +160,7 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
     float k1_;
     load_sim_table(seg, T.sim_table, cache, lane, k1_);
     if (tabled) build_score_table(cache, wk, lane);
+    TQ_TR(1, cache[lane]);
     // the term's block-max sketch: k real postings of k blocks, scored with this query's table — a threshold to start from
     if (fast && T.sketch != 0u && seg.sketch != nullptr && k <= TERM_SKETCH_K) {
       const uint64_t f = sketch_floor<WIDE>(seg.sketch + (size_t)(T.sketch - 1u) * TERM_SKETCH_K, cache, k, lane);
@@ -143,6 +175,7 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
     return kth > floor ? kth : floor;
   };
   uint64_t tau = floor;
+  TQ_TR(2, (uint32_t)floor);
 
   if (fast) {
     count = wave == 0 ? 128 * T.nblocks : 0;  // no deleted docs on this path: every posting is a hit
@@ -211,10 +244,12 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
             touched += 18u * (uint32_t)nb;
           }
           uint64_t pm[TQ_STEP_CHUNKS];
+          uint32_t bd[TQ_STEP_CHUNKS];  // the block's bound: ten table reads, kept for the queue entry
 #pragma unroll
           for (int s = 0; s < TQ_STEP_CHUNKS; ++s) {
             const int nb = ch[s] < 0 ? 0 : min(64, T.nblocks - 64 * ch[s]);
-            pm[s] = __ballot(lane < nb && term_bound_of(cache, bm[s]) >= term_thr_of(tau, lo[s]));
+            bd[s] = term_bound_of(cache, bm[s]);
+            pm[s] = __ballot(lane < nb && bd[s] >= term_thr_of(tau, lo[s]));
             if (lane == 0) cnt[wave * TQ_STEP_CHUNKS + s] = (uint32_t)__popcll(pm[s]);
           }
           __syncthreads();
@@ -231,7 +266,7 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
               e_row[at] = rw[s];
               e_hdr[at] = (uint16_t)hd[s];
               e_lo[at] = lo[s];
-              e_bound[at] = term_bound_of(cache, bm[s]);
+              e_bound[at] = bd[s];
             }
           }
           nq += cut > 0 ? readlane(incl, cut - 1) : 0;
@@ -243,6 +278,11 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
         cnext = window_end;
         if (full) break;
       }
+#ifdef RGPU_TERM_TRACE
+      if (tq_rounds == 0) TQ_TR(3, nq);
+      tq_rounds += 1;
+      tq_entries += nq;
+#endif
       if (nq == 0) continue;
       // ---- sort: queue position -> entry, (bound desc, entry asc); entries are in block order ----
       for (int i = tid; i < nq; i += NT) {
@@ -256,6 +296,9 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
       }
       if (tid == 0) cursor = 0u;
       __syncthreads();
+#ifdef RGPU_TERM_TRACE
+      if (tq_rounds == 1) TQ_TR(4, e_order[0]);
+#endif
       // ---- drain ----
       // An entry is re-tested against the list's k-th best of the moment when it is popped. The threshold only rises, and an entry
       // behind a failed one has a bound at most as large and, at an equal bound, a later block (its doc in front is at least as
@@ -314,7 +357,7 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
           deltas_to_docs(e0, e1, lo < 0 ? 0 : lo, d0, d1);
           const uint64_t key0 = make_key(s0, d0), key1 = make_key(s1, d1);
           tau = tau_now();
-          if (__ballot((key0 > key1 ? key0 : key1) > tau)) group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor);
+          if (__ballot((key0 > key1 ? key0 : key1) > tau)) group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor, slab TERM_LK_PASS);
         }
         wave_sync();  // slab is free for the next block
       };
@@ -340,7 +383,11 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
           ring[j] = block_rows_load(block_rows_at(term_rows, e_row[pj]), e_hdr[pj], lane);
           nring[j] = norms_of(pj);
           if (i >= 0) {
+            TERM_LK_NOW(tq_s0);
             step(i, rows, nn);
+#ifdef RGPU_TERM_TRACE
+            tq_step += (uint32_t)((uint64_t)clock64() - tq_s0);
+#endif
           }
         }
       }
@@ -369,7 +416,7 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
       }
       count += __popcll(__ballot(v0)) + __popcll(__ballot(v1));
       const uint64_t key0 = v0 ? make_key(s0, d0) : 0ull, key1 = v1 ? make_key(s1, d1) : 0ull;
-      if (__ballot((key0 > key1 ? key0 : key1) > tau)) group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor);
+      if (__ballot((key0 > key1 ? key0 : key1) > tau)) group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor, slab TERM_LK_PASS);
     };
     for (int c = wave; c < n_chunks; c += W) {
       const int b0 = 64 * c, b1 = min(T.nblocks, b0 + 64);
@@ -385,9 +432,16 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
     atomicAdd(&sums[0], (uint32_t)count);
     atomicAdd(&sums[1], looked);
     atomicAdd(&sums[2], touched);
+#ifdef RGPU_TERM_TRACE
+    if (wave < 8) { tq_w[wave][0] = lk[0]; tq_w[wave][1] = lk[1]; tq_w[wave][2] = tq_step; tq_w[wave][3] = lk[2]; tq_w[wave][4] = lk[3]; }
+#endif
   }
   __syncthreads();
   if (wave != 0) return;
+#ifdef RGPU_TERM_TRACE
+  TQ_TR(5, sums[0]);
+  const unsigned int tq_wave0 = (unsigned int)((uint64_t)clock64() - tq_c0);
+#endif
   // the tail and the singleton (postings outside FullBlocks), then the caller's row
   {
     const bool has_live = seg.live != nullptr;
@@ -409,7 +463,7 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
       tcount += __popcll(__ballot(v0)) + __popcll(__ballot(v1));
       const uint64_t key0 = v0 ? make_key(s0, d0) : 0ull, key1 = v1 ? make_key(s1, d1) : 0ull;
       tau = tau_now();
-      if (__ballot((key0 > key1 ? key0 : key1) > tau)) group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor);
+      if (__ballot((key0 > key1 ? key0 : key1) > tau)) group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor, slabs[0] TERM_LK_PASS);
     };
     if (T.df == 1) {
       const bool v0 = lane == 0;
@@ -435,6 +489,23 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
         work_slots[n_queries + q] = (unsigned long long)sums[1];
       }
     }
+#ifdef RGPU_TERM_TRACE
+    TQ_TR(6, a);
+    if (lane == 0 && 3 * (int)blockIdx.x + 2 < TERM_TRACE_CAP) {
+      TermQueryTraceRec r{};
+      r.t0 = tq_t0; r.t1 = (unsigned long long)wall_clock64();
+      r.q = q; r.nblocks = T.nblocks; r.rounds = tq_rounds; r.entries = tq_entries; r.unpacked = (int32_t)sums[1];
+      for (int i = 0; i < 7; ++i) r.d[i] = tq_d[i];
+      r.waves = (unsigned int)W; r.wave0_cycles = tq_wave0;
+      int offers = 0, entered = 0;
+      for (int w = 0; w < (W < 8 ? W : 8); ++w) {
+        r.cyc[w][0] = tq_w[w][0]; r.cyc[w][1] = tq_w[w][1]; r.cyc[w][2] = tq_w[w][2] - tq_w[w][0] - tq_w[w][1];
+        offers += (int)tq_w[w][3]; entered += (int)tq_w[w][4];
+      }
+      r.offers = offers + (int)(lk[2] - tq_w[0][3]); r.entered = entered + (int)(lk[3] - tq_w[0][4]);  // (+ the tail's, wave 0)
+      reinterpret_cast<TermQueryTraceRec*>(g_term_trace)[blockIdx.x] = r;
+    }
+#endif
   }
 }
 
