@@ -410,6 +410,27 @@ int32_t rgpu_search_batch_device_masked(rgpu_segment* seg, rgpu_docset* set, con
                                         const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, void* hits_dev,
                                         void* total_hits_dev, void* hip_stream);
 
+/* IndexSearcher::count (search/searcher.rs:632-654): hit counts without scoring - what a TotalHitCountCollector collects
+ * (search/collector/mod.rs TotalHitCountCollector: needs_scores() is false; its TotalHitsCountLeafCollector adds one per live doc
+ * the leaf's scorer stops at). counts_out[q] is exactly the total_hits_out[q] rgpu_search_batch reports for the same queries / terms,
+ * with a set the total_hits_out[q] of rgpu_search_batch_masked: the docs of live AND set that query q matches in this leaf. No score
+ * is computed - `weight` and `sim_table` of the clauses are ignored - no freq or norm is read and no list of hits is kept; the call
+ * returns synchronised. `set_or_null`: a doc set of `seg` (of another segment: RGPU_ERR_ILLEGAL_ARGUMENT), or NULL.
+ * Served: RGPU_OP_TERM; flat RGPU_OP_AND; RGPU_OP_OR with min_should_match 0..255 (it counts clauses: a term named twice counts
+ * twice); each with or without MUST_NOT term clauses - every MUST_NOT clause present in the leaf excludes its docs: two or more are a
+ * DisjunctionSumScorer(.., false, min_should_match) (query/boolean_query.rs:235-252) that ReqNotScorer only advance()s, and advance()
+ * does not look at min_should_match (scorer/disjunction_scorer.rs:75-89), exactly as in rgpu_search_batch; RGPU_OP_DISMAX (the docs of the OR; n_must_not is the tie-breaker's bits); RGPU_OP_WITH_SHOULD(op, n)
+ * (the n optional clauses are skipped: ReqOptScorer never changes which docs match); a demote byte in n_must_not (a leaf where no
+ * demoting term has a posting counts 0, query/boosting_query.rs:102-118; otherwise the demoting clauses are ignored). A MUST clause
+ * absent from the leaf: 0; a SHOULD or MUST_NOT clause absent from the leaf drops out, min_should_match stays
+ * (query/boolean_query.rs:196-275). A lone present term without a present MUST_NOT clause, on a segment without deletions and without
+ * a set, is answered with its doc_freq on the host (searcher.rs:640-648): a batch of such rows and of rows that count 0 launches nothing.
+ * Refused, nothing launched and counts_out untouched: RGPU_OP_SHOULD_REQUIRED / RGPU_OP_NESTED_MUST (RGPU_ERR_UNSUPPORTED); malformed
+ * rows, by rgpu_search_batch's checks (RGPU_ERR_ILLEGAL_ARGUMENT); a conjunction of two or more distinct terms on a context without a
+ * similarity table (RGPU_ERR_ILLEGAL_STATE: it runs the search's conjunction kernel, as rgpu_docset_collect_batch does). */
+int32_t rgpu_count_batch(rgpu_segment* seg, rgpu_docset* set_or_null, const rgpu_query* queries, int32_t n_queries,
+                         const rgpu_query_term* terms, int32_t n_terms_total, int64_t* counts_out);
+
 /* A doc set as the ONLY required clause: "b c #F", a lone #F, a lone range, "+range b c", "b c -X", "-X", MatchAllDocsQuery (for
  * which BooleanQuery::build inserts a MatchAllDocsQuery MUST clause, boolean_query.rs:76-79). The reference builds
  * ReqOptScorer(F, DisjunctionSumScorer(b, c)) (boolean_query.rs:253-262). The required side is ConstantScoreScorer(0.0)

@@ -77,7 +77,7 @@ EXPORTS = [
     "rgpu_search_batch_record_device", "rgpu_merge_records_device", "rgpu_last_search_counters",
     "rgpu_planner_create", "rgpu_planner_create_flat", "rgpu_planner_destroy", "rgpu_planner_sim_table", "rgpu_planner_set_sim_table", "rgpu_plan_uniform_ids",
     "rgpu_docset_from_words", "rgpu_docset_from_docs", "rgpu_docset_collect_batch", "rgpu_docset_combine", "rgpu_docset_cardinality", "rgpu_docset_words",
-    "rgpu_docset_bytes", "rgpu_docset_free", "rgpu_search_batch_masked", "rgpu_search_batch_device_masked",
+    "rgpu_docset_bytes", "rgpu_docset_free", "rgpu_search_batch_masked", "rgpu_search_batch_device_masked", "rgpu_count_batch",
     "rgpu_docset_head", "rgpu_search_batch_required_set", "rgpu_search_batch_device_required_set",
     "rgpu_search_phrase_batch_masked", "rgpu_search_phrase_bool_batch_masked", "rgpu_search_phrase_or_batch_masked",
     "rgpu_search_span_near_batch",
@@ -198,6 +198,7 @@ def lib():
         "rgpu_points_free": (None, [vp]),
         "rgpu_docset_from_point_ranges": (i32, [vp, vp, i32, i32, vp]),
         "rgpu_search_batch_masked": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp]),
+        "rgpu_count_batch": (i32, [vp, vp, vp, i32, vp, i32, vp]),
         "rgpu_search_phrase_batch_masked": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_phrase_bool_batch_masked": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_phrase_or_batch_masked": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
@@ -1004,6 +1005,14 @@ class Segment:
         t = np.ascontiguousarray(terms, dtype=QUERY_TERM_DTYPE)
         _check(lib().rgpu_search_batch_device_masked(self._h, docset._h, q.ctypes.data, q.size, t.ctypes.data, t.size, k, hits_ptr, totals_ptr,
                                                      stream or None))
+
+    def count_batch(self, queries, terms, docset=None):
+        """rgpu_count_batch (IndexSearcher::count per leaf): the docs of live AND `docset` each query matches, nothing scored -> int64[n]"""
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=QUERY_TERM_DTYPE)
+        counts = np.zeros(q.size, dtype=np.int64)
+        _check(lib().rgpu_count_batch(self._h, docset._h if docset is not None else None, q.ctypes.data, q.size, t.ctypes.data, t.size, counts.ctypes.data))
+        return counts
 
     def docset_head(self, docset, n):
         """rgpu_docset_head: (the first min(n, |live AND set|) docs of `live AND set`, ascending leaf-local ids; |live AND set|)"""

@@ -1108,6 +1108,53 @@ class GpuIndexSearcher {
     return merge_leaves(leaf_hits, leaf_totals, nq, k);
   }
 
+  // ---- IndexSearcher::count (search/searcher.rs:632-654): hit counts without scoring ---------------------------------------------
+  // where count() hands what the GPU path refuses (UnsupportedOperation: phrases, spans, nested trees, doc-set clauses); empty: rethrow
+  std::function<int64_t(const Query&)> cpu_count_fallback;
+
+  // MatchAllDocsQuery: num_docs from the leaves' live docs, no GPU call (searcher.rs:636-638); a TermQuery on leaves without deletions:
+  // the sum of doc_freq, no GPU call (:640-648); anything else through count_many.
+  int64_t count(const Query& query) {
+    if (dynamic_cast<const MatchAllDocsQuery*>(&query)) {
+      int64_t n = 0;
+      for (const LeafReader& leaf : leaves_) n += leaf_num_docs(leaf);
+      return n;
+    }
+    bool deletions = false;
+    for (const LeafReader& leaf : leaves_) deletions = deletions || leaf.live_docs != nullptr;
+    if (const TermQuery* t = dynamic_cast<const TermQuery*>(&query); t && !deletions) {
+      int64_t n = 0;
+      rgpu_term_state st;
+      for (const LeafReader& leaf : leaves_) if (leaf.term_state(*t, &st)) n += st.doc_freq;
+      return n;
+    }
+    try {
+      return count_many({&query})[0];
+    } catch (const Error& e) {
+      if (e.kind != RGPU_ERR_UNSUPPORTED || !cpu_count_fallback) throw;  // ErrorKind::UnsupportedOperation -> the CPU path
+      return cpu_count_fallback(query);
+    }
+  }
+
+  // the live docs each query matches, summed over the leaves: one rgpu_count_batch per leaf, nothing scored. Term, boolean, dismax and
+  // boosting queries; anything else (phrases, spans, FilteredQuery / doc-set rows, nested trees) is UnsupportedOperation.
+  std::vector<int64_t> count_many(const std::vector<const Query*>& queries) {
+    for (const Query* q : queries)  // refused before any leaf is touched
+      if (!dynamic_cast<const TermQuery*>(q) && !dynamic_cast<const BooleanQuery*>(q) && !dynamic_cast<const DisjunctionMaxQuery*>(q) && !dynamic_cast<const BoostingQuery*>(q))
+        throw Error(RGPU_ERR_UNSUPPORTED, "a count is served by the GPU path for term, boolean, dismax and boosting queries");
+    const int32_t nq = static_cast<int32_t>(queries.size());
+    std::vector<int64_t> counts(queries.size(), 0), leaf_counts(queries.size(), 0);
+    if (nq == 0) return counts;
+    for (size_t li = 0; li < leaves_.size(); ++li) {
+      std::vector<rgpu_query> qs;
+      std::vector<rgpu_query_term> ts;
+      plan(queries, li, &qs, &ts);
+      check(rgpu_count_batch(leaves_[li].segment, nullptr, qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), leaf_counts.data()));
+      for (size_t i = 0; i < counts.size(); ++i) counts[i] += leaf_counts[i];
+    }
+    return counts;
+  }
+
   // IndexSearcher::search(PhraseQuery, TopDocsCollector(k)) for a batch of exact phrases. PhraseQuery::create_weight
   // (phrase_query.rs:136-186): ONE BM25 weight from the statistics of all the phrase's terms.
   // `masks` (one doc set per leaf, or null): the search restricted to them — rgpu_search_phrase_batch_masked; exact phrases only.
@@ -1708,6 +1755,13 @@ class GpuIndexSearcher {
     }
     if (bo) demote_fields(*bo, &rq, ts);
     qs->push_back(rq);
+  }
+
+  static int64_t leaf_num_docs(const LeafReader& leaf) {
+    if (!leaf.live_docs) return leaf.max_doc;
+    int64_t n = 0;
+    for (int32_t d = 0; d < leaf.max_doc; ++d) n += static_cast<int64_t>((leaf.live_docs[d >> 6] >> (d & 63)) & 1u);
+    return n;
   }
 
   std::vector<LeafReader> leaves_;

@@ -1583,3 +1583,60 @@ class GpuIndexSearcher:
         row = hits[0]
         docs = [(int(d), float(s)) for d, s in zip(row["doc"], row["score"]) if d >= 0]
         collector._result = TopDocs(int(totals[0]), docs)
+
+    # ---- IndexSearcher::count (search/searcher.rs:632-654): hit counts without scoring ------------------------------------------
+    cpu_count_fallback = None   # cpu_count_fallback(query) -> int: where count() hands what the GPU path refuses (UnsupportedOperation); None: raise
+
+    def _leaf_num_docs(self, leaf):
+        if leaf.live_docs is None:
+            return int(leaf.max_doc)
+        words = np.ascontiguousarray(leaf.live_docs, dtype=np.uint64)
+        return int(np.unpackbits(words.view(np.uint8), bitorder="little")[:leaf.max_doc].sum())
+
+    def count(self, query):
+        """IndexSearcher::count. MatchAllDocsQuery: num_docs from the leaves' live docs, no GPU call (searcher.rs:636-638); a TermQuery on
+        leaves without deletions: the sum of doc_freq, no GPU call (:640-648); anything else through count_batch. What the GPU path
+        refuses (UnsupportedOperation: phrases, spans, nested trees) goes to cpu_count_fallback(query) when that is set."""
+        if isinstance(query, MatchAllDocsQuery):
+            return sum(self._leaf_num_docs(leaf) for leaf in self.leaves)
+        if isinstance(query, TermQuery) and all(leaf.live_docs is None for leaf in self.leaves):
+            states = [leaf.term_state(query.term) for leaf in self.leaves]
+            return sum(int(st["doc_freq"]) for st in states if st is not None)
+        try:
+            return int(self.count_batch([query])[0])
+        except RgpuError as e:
+            if e.status == -5 and self.cpu_count_fallback is not None:
+                return int(self.cpu_count_fallback(query))
+            raise
+
+    def count_batch(self, queries):
+        """-> int64[n]: the live docs each query matches, summed over the leaves (rgpu_count_batch per leaf; nothing is scored). Rows
+        with doc-set clauses are grouped by their combination of sets exactly as search_batch groups them and counted under the group's
+        mask; a row whose only required clauses are doc sets (required_sets=True) matches all of live AND sets whatever its SHOULD
+        clauses say: the live cardinality of its mask (rgpu_docset_head with n = 0). Whatever search_batch refuses, and phrases and
+        spans in any position, are UnsupportedOperation."""
+        for q in queries:   # refused before any leaf is touched and before any range's set is built
+            if _holds_span(q) or isinstance(q, (PhraseQuery, SpanNearQuery)) or (isinstance(q, BooleanQuery) and q.has_phrases()):
+                raise RgpuError(-5, "a count is served by the GPU path for term, boolean, dismax and boosting queries")
+            rest, _ = self._peel(q, build=False)
+            if isinstance(rest, PhraseQuery) or (isinstance(rest, BooleanQuery) and rest.has_phrases()):
+                raise RgpuError(-5, "a count is served by the GPU path for term, boolean, dismax and boosting queries")
+        if getattr(self, "_range_filters", None):
+            self.drop_range_filters(keep=self.range_filter_capacity)
+        peeled = [self._peel(q) for q in queries]
+        counts = np.zeros(len(queries), dtype=np.int64)
+        groups = {}   # key -> (masks per leaf or None, caller rows): first appearance first, caller order inside a group
+        for i, (rest, (f, x)) in enumerate(peeled):
+            key, masks = self._mask(f, x) if (f or x) else (None, None)
+            if isinstance(rest, _RequiredSet):
+                key = (key, "required")
+            groups.setdefault(key, (masks, []))[1].append(i)
+        for masks, rows in groups.values():
+            rests = [peeled[i][0] for i in rows]
+            for li, leaf in enumerate(self.leaves):
+                if isinstance(rests[0], _RequiredSet):   # (a group holds such rows alone)
+                    counts[rows] += leaf.segment.docset_head(masks[li], 0)[1]
+                    continue
+                qs, ts = self.pack(rests, leaf)
+                counts[rows] += leaf.segment.count_batch(qs, ts, None if masks is None else masks[li])
+        return counts

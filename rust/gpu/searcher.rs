@@ -432,6 +432,28 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
         Ok(true)
     }
 
+    /// The live docs `query` matches, summed over the leaves (TotalHitCountCollector, searcher.rs:650-653); None: not a tree of term
+    /// clauses `flatten` accepts. The clause weights are computed as for a search - the library ignores them, but a conjunction runs
+    /// the search's conjunction kernel, which wants the similarity table uploaded.
+    fn try_count(&self, query: &dyn Query<C>) -> Result<Option<i32>> {
+        let flat = match self.flatten(query) { Some(f) => f, None => return Ok(None) };
+        let n = flat.n_clauses();
+        if n > RGPU_MAX_QUERY_TERMS as usize { return Ok(None); }
+        let weights = self.clause_weights(&flat)?;
+        let mut sum: i64 = 0;
+        for leaf in self.cpu.reader().leaves() {
+            let mut terms = Vec::with_capacity(n);
+            for (i, t) in flat.clauses().enumerate() {
+                terms.push(RgpuQueryTerm { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: weights[i].0, sim_table: weights[i].1 });
+            }
+            let q = RgpuQuery { op: flat.op, n_terms: flat.positive.len() as i32, first_term: 0, n_must_not: flat.must_not.len() as i32 };
+            let mut count: i64 = 0;
+            check(unsafe { rgpu_count_batch(self.leaves[leaf.ord].seg, std::ptr::null_mut(), &q, 1, terms.as_ptr(), n as i32, &mut count) }, self.ctx)?;
+            sum += count;
+        }
+        Ok(Some(sum as i32))
+    }
+
     /// The phrase's terms in one leaf, in the query's order: postings + position-stream pointers (a term absent from the leaf:
     /// doc_freq = 0, which tells the library what PhraseWeight::create_scorer -> None tells the reference)
     fn phrase_terms(&self, leaf: &LeafReaderContext<'_, C>, terms: &[Term], positions: &[i32]) -> Result<Vec<RgpuPhraseTerm>> {
@@ -989,7 +1011,15 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
         self.cpu.search(query, collector)
     }
     fn search_parallel<S: SearchCollector>(&self, query: &dyn Query<C>, collector: &mut S) -> Result<()> { self.search(query, collector) }
-    fn count(&self, query: &dyn Query<C>) -> Result<i32> { self.cpu.count(query) }
+    /// IndexSearcher::count (searcher.rs:632-654): what `flatten` accepts is counted on the GPU (rgpu_count_batch per leaf, nothing
+    /// scored); every other query - and any RGPU_ERR_UNSUPPORTED the library answers with - takes the CPU path unchanged.
+    fn count(&self, query: &dyn Query<C>) -> Result<i32> {
+        match self.try_count(query) {
+            Ok(Some(n)) => Ok(n),
+            Ok(None) | Err(Error(ErrorKind::UnsupportedOperation(_), _)) => self.cpu.count(query),
+            Err(e) => Err(e),
+        }
+    }
     fn explain(&self, query: &dyn Query<C>, doc: DocId) -> Result<core::search::explanation::Explanation> { self.cpu.explain(query, doc) }
 }
 
