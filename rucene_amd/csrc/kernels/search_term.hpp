@@ -153,10 +153,10 @@ __device__ __forceinline__ uint64_t group_kth(const GroupList& g, int k) {
 // WIDE lists (k > 64, two registers per lane) take neither.
 static_assert(RGPU_TERM_RANK_MERGE_MAX >= 3 && RGPU_TERM_RANK_MERGE_MAX <= 64 && 8 * RGPU_TERM_RANK_MERGE_MAX <= TERM_BLOCK_SLAB,
               "the candidates of a rank merge fit one register and the staging slab");
+// The level cut on its own (see above): key0 / key1 keep only the block's best score levels once they hold more candidates against
+// `tau` than max(k, RGPU_TERM_LEVEL_CUT_MIN). Shared by group_offer2 and the query kernel's private lists (wave_offer2).
 template <bool WIDE>
-__device__ __forceinline__ void group_offer2(const GroupList& g, uint64_t key0, uint64_t key1, uint64_t& tau, int k, int lane,
-                                             uint64_t floor, uint8_t* slab TERM_LK_PARAM) {
-  // slab: this wave's staging slab, its contents no longer needed; tau: a threshold the list has reached (or 0)
+__device__ __forceinline__ void term_level_cut(uint64_t& key0, uint64_t& key1, uint64_t tau, int k) {
 #if RGPU_TERM_LEVEL_CUT
   if (!WIDE && __popcll(__ballot(key0 > tau)) + __popcll(__ballot(key1 > tau)) > (k > RGPU_TERM_LEVEL_CUT_MIN ? k : RGPU_TERM_LEVEL_CUT_MIN)) {
     // score levels from the top (a key's high word: the score's order bits; 0 = no key) until k keys are covered
@@ -173,6 +173,27 @@ __device__ __forceinline__ void group_offer2(const GroupList& g, uint64_t key0, 
     key1 = (uint32_t)(key1 >> 32) >= level ? key1 : 0ull;
   }
 #endif
+}
+// Offer two keys per lane to a list that ONE wave owns (keys: LDS, 64 or 128 keys at rest like GroupList's; no lock): the level cut,
+// then the insertions. tau = max(the list's k-th best, floor) on entry and on return. Every lane reads and writes its own slots only.
+template <bool WIDE>
+__device__ __forceinline__ void wave_offer2(uint64_t* keys, uint64_t key0, uint64_t key1, uint64_t& tau, int k, int lane, uint64_t floor TERM_LK_PARAM) {
+  term_level_cut<WIDE>(key0, key1, tau, k);
+  TERM_LK_COUNT(2, 1);
+  TERM_LK_COUNT(3, __popcll(__ballot(key0 > tau)) + __popcll(__ballot(key1 > tau)));
+  WaveTopK top;
+  top.a = keys[lane];
+  if (WIDE) top.b = keys[64 + lane];
+  topk_offer<WIDE>(top, key0, tau, k, lane, floor);
+  topk_offer<WIDE>(top, key1, tau, k, lane, floor);
+  keys[lane] = top.a;
+  if (WIDE) keys[64 + lane] = top.b;
+}
+template <bool WIDE>
+__device__ __forceinline__ void group_offer2(const GroupList& g, uint64_t key0, uint64_t key1, uint64_t& tau, int k, int lane,
+                                             uint64_t floor, uint8_t* slab TERM_LK_PARAM) {
+  // slab: this wave's staging slab, its contents no longer needed; tau: a threshold the list has reached (or 0)
+  term_level_cut<WIDE>(key0, key1, tau, k);
   TERM_LK_NOW(lk_t0);
   TERM_LK_COUNT(2, 1);
   group_lock(g.lock, lane);

@@ -18,6 +18,21 @@
 // no partial lists, no per-query counters in memory, no exchange between XCDs.
 // Queries off the table path (raw norms, deleted docs, a negative weight, a sim table without TERM_FLAG_MONOTONE) run in the same
 // launch: the waves stride over the list's chunks with stream_blocks and offer into the same list.
+// One-chunk path (table-path lists of at most `short_blocks` <= 64 FullBlocks; RGPU_TERM_SHORT_BLOCKS, 0: off): such
+// a list is one lane per block, so it has no chunk frontier to test, no queue to fill, sort and pop, and — its waves being the only
+// writers — needs no shared list:
+//   loads     the chunk's directory entries (dir_bmax, dir_row, dir_hdr, dir_last) are requested from the descriptor alone, by waves
+//             1 .. W - 1 while wave 0 builds the table (wave 0: behind its build); wave W - 1 also loads the tail (row -> cells ->
+//             norms -> the similarity's cache entries) and scores it ahead of the barrier, without the table;
+//   deal      behind the barrier every wave computes every block's bound and the same ballot of survivors against the floor; wave w
+//             owns the survivors of rank w, w + W, ... and parks their directory entries in the (unused) queue arrays;
+//   unpack    the general path's per-block body through a PREFETCH_DEPTH-deep ring, a block re-tested against the WAVE's threshold
+//             just before it is unpacked; offers go to a list of the wave's own (LDS over `cq`, checked out per offer, level cut in
+//             front: wave_offer2) with tau = max(its k-th best, floor). No lock;
+//   merge     one barrier, then wave 0 folds the W sorted lists (topk_merge_sorted) and writes the row, the total and the counters.
+// Exact: a subset's k-th best key is a lower bound of the list's, so a block skipped against a private threshold holds no winner;
+// keys are unique, so the k best of the union of the private lists are the list's k best.
+// On the general path a gather round past the list's last chunk and a block-step slot without a chunk issue no loads and no bound.
 #pragma once
 #include "search_term.hpp"
 
@@ -32,8 +47,14 @@ constexpr int TQ_CHUNK_UNROLL = 4;      // chunk frontier words per thread per g
 #define RGPU_TERMQ_STEP_CHUNKS 2
 #endif
 constexpr int TQ_STEP_CHUNKS = RGPU_TERMQ_STEP_CHUNKS;  // surviving chunks per wave per gather step
+// The bound asks for 7 waves per SIMD. With the one-chunk path in the kernel, a bound of 6 (k_search_term's) lets the scheduler spread
+// the general path's drain over 73 VGPRs (six waves); at 7 the headline instantiation takes 71, no scratch, and keeps its seven.
+// (W = 2 keeps k_search_term's bound: two-wave workgroups ran at six before, and do not fit seven.)
 #ifndef RGPU_TERMQ_FAST_WAVES
-#define RGPU_TERMQ_FAST_WAVES RGPU_TERM_FAST_WAVES
+#define RGPU_TERMQ_FAST_WAVES 7
+#endif
+#ifndef RGPU_TERMQ_ONE  // 0: variant builds without the one-chunk path
+#define RGPU_TERMQ_ONE 1
 #endif
 static_assert(TQ_CAP >= 64 && TQ_CAP <= 65536, "queue positions are u16 and a chunk must fit an empty queue");
 
@@ -77,16 +98,33 @@ static_assert(sizeof(TermQueryTraceRec) == 3 * sizeof(TermTraceRec), "a workgrou
 #define TQ_TR(slot, dep) do {} while (0)
 #endif
 
+// a one-chunk list's directory, one lane per block: frontier word, store row, header, the doc in front of the block (-1: none)
+struct OneChunkDir {
+  uint64_t bm = 0ull;
+  uint32_t rw = 0u, hd = 0u;
+  int32_t lo = -1;
+  __device__ __forceinline__ void load(const SegView& seg, const DevTerm& T, int lane) {
+    if (lane < T.nblocks) {
+      const uint32_t b = T.dir_base + (uint32_t)lane;
+      bm = seg.dir_bmax[b];
+      rw = seg.dir_row[b];
+      hd = (uint32_t)seg.dir_hdr[b];
+      if (lane > 0) lo = seg.dir_last[b - 1u];
+    }
+  }
+};
+
 template <bool LEGACY, bool WIDE, int W>
-__global__ __launch_bounds__(64 * W, (LEGACY || WIDE) ? RGPU_TERM_OTHER_WAVES : RGPU_TERMQ_FAST_WAVES)
+__global__ __launch_bounds__(64 * W, (LEGACY || WIDE) ? RGPU_TERM_OTHER_WAVES : W == 2 ? RGPU_TERM_FAST_WAVES : RGPU_TERMQ_FAST_WAVES)
 void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, const DevTerm* __restrict__ terms,
                          const int32_t* __restrict__ order, int n_queries, int k, unsigned long long* __restrict__ work_slots,
                          const int32_t* __restrict__ qmap, HitOut* __restrict__ hits, int64_t* __restrict__ totals, int32_t doc_base,
-                         const TermLaunch* __restrict__ launch) {
+                         const TermLaunch* __restrict__ launch, int short_blocks) {
   // order[i]: the query of workgroup i (heaviest first); work_slots (nullable): [q] = bytes requested for query q, [n_queries + q] =
   // FullBlocks unpacked (rgpu_last_search_counters).
   // launch (nullable; pinned host memory): workgroup i's whole plan is launch[i] — `terms` is then the context's descriptor arena and
   // `queries`, `order` and `qmap` are not read: one read over the bus and one of device memory instead of order -> query -> term
+  // short_blocks (0..64, the same in every workgroup): table-path lists of at most this many FullBlocks take the one-chunk path; 0: none
   constexpr int LIST_N = WIDE ? 128 : 64;
   constexpr int NT = 64 * W;
   constexpr int DEPTH = PREFETCH_DEPTH;
@@ -97,7 +135,9 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
   __shared__ uint32_t e_blk[TQ_CAP], e_row[TQ_CAP], e_bound[TQ_CAP];  // the queue, in block order
   __shared__ int32_t e_lo[TQ_CAP];
   __shared__ uint16_t e_hdr[TQ_CAP], e_order[TQ_CAP];                 // e_order: queue positions, best bound first
-  __shared__ uint32_t cq[TQ_CHUNK_UNROLL * NT];                       // surviving chunks of the current gather window
+  // cq: surviving chunks of the current gather window; on the one-chunk path (no window, no queue) the waves' private lists
+  __shared__ __attribute__((aligned(16))) uint32_t cq[TQ_CHUNK_UNROLL * NT];
+  static_assert(sizeof(uint32_t) * TQ_CHUNK_UNROLL * NT >= sizeof(uint64_t) * W * LIST_N, "W private lists of LIST_N keys alias cq");
   __shared__ uint32_t cnt[TQ_CHUNK_UNROLL * NT / 64 > W * TQ_STEP_CHUNKS ? TQ_CHUNK_UNROLL * NT / 64 : W * TQ_STEP_CHUNKS];
   __shared__ uint32_t cursor;
   __shared__ uint32_t sums[3];  // hits, blocks unpacked, bytes requested
@@ -152,6 +192,14 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
   const int n_chunks = (T.nblocks + 63) >> 6;
   const uint32_t sum_base = (T.dir_base + 63u) >> 6;
 
+  // One-chunk path: a table-path list of at most short_blocks (<= 64) FullBlocks is one lane per block in every wave. Its directory
+  // entries depend on the descriptor alone, so every wave requests them here (the same lines in every wave: L2 hits) and they fly
+  // while wave 0 builds the table; wave W - 1 also requests the tail (or the singleton's norm): tail row -> cells -> norms.
+  // (workgroup-uniform, and said so: a branch the compiler takes for divergent is laid out as both sides under masks, and what one
+  // side keeps in registers then stays live across the other)
+  const bool one = readfirstlane((int)(RGPU_TERMQ_ONE && fast && short_blocks > 0 && T.nblocks <= short_blocks)) != 0;
+  OneChunkDir oc;
+  uint64_t oc_k0 = 0ull, oc_k1 = 0ull;  // wave W - 1: the tail's (or the singleton's) keys
   for (int i = tid; i < LIST_N; i += NT) list[i] = 0ull;
   if (tid == 0) { lock_word = 0u; sums[0] = sums[1] = sums[2] = 0u; floor_s = 0ull; cursor = 0u; }
   uint32_t looked = 0, touched = 0;  // per wave (scalar)
@@ -160,12 +208,38 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
     float k1_;
     load_sim_table(seg, T.sim_table, cache, lane, k1_);
     if (tabled) build_score_table(cache, wk, lane);
+    if (one) oc.load(seg, T, lane);
     TQ_TR(1, cache[lane]);
     // the term's block-max sketch: k real postings of k blocks, scored with this query's table — a threshold to start from
     if (fast && T.sketch != 0u && seg.sketch != nullptr && k <= TERM_SKETCH_K) {
       const uint64_t f = sketch_floor<WIDE>(seg.sketch + (size_t)(T.sketch - 1u) * TERM_SKETCH_K, cache, k, lane);
       if (lane == 0) floor_s = f;
       touched += 2u * (uint32_t)k;
+    }
+  } else if (one) {
+    // (an else of wave 0's branch, not a block in front of it: what is loaded here is then not live across the table build, whose
+    // eleven divisions in flight want the registers; wave 0 requests its directory entries behind the build)
+    oc.load(seg, T, lane);
+    if (wave == W - 1 && (T.df == 1 || T.tail_n > 0)) {
+      // scored here, without the table: table_score(rank, freq) IS bm25_score(wk, freq, the rank's cache entry), the expression below
+      // on the same operands, so the bits are the table's; two keys cross the barrier instead of docs, freqs and norms
+      int32_t d0 = T.singleton_doc, d1 = 0;
+      uint32_t f0 = (uint32_t)T.singleton_freq, f1 = 1u, n0, n1 = 0u;
+      bool v0 = lane == 0, v1 = false;
+      if (T.df == 1) {
+        n0 = v0 ? norm_at(seg, T.singleton_doc) : 0u;
+      } else {
+        tail_load(term_rows, seg.dir_row[T.dir_base + T.nblocks], lane, d0, d1, f0, f1);  // decoded and validated at prepare time
+        v0 = 2 * lane < T.tail_n;
+        v1 = 2 * lane + 1 < T.tail_n;
+        n0 = v0 ? seg.norms[d0] : 0u;
+        n1 = v1 ? seg.norms[d1] : 0u;
+      }
+      const float* sim = seg.sim_tables + (size_t)T.sim_table * 257;
+      const float c0 = sim[seg.rank_to_norm[n0]], c1 = sim[seg.rank_to_norm[n1]];
+      const float s0 = bm25_score(wk, (float)(int32_t)f0, c0), s1 = bm25_score(wk, (float)(int32_t)f1, c1);
+      oc_k0 = v0 ? make_key(s0, d0) : 0ull;
+      oc_k1 = v1 ? make_key(s1, d1) : 0ull;
     }
   }
   __syncthreads();
@@ -177,7 +251,129 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
   uint64_t tau = floor;
   TQ_TR(2, (uint32_t)floor);
 
-  if (fast) {
+  if (one) {
+    // ---- one chunk: no chunk frontier, no queue, no sort, no lock ----
+    // A ballot is the queue: every wave computes every block's bound and the same survivor mask pm against the floor; wave w takes
+    // the survivors of rank w, w + W, ... in pm and keeps a list of its own in registers (tau = max(its k-th best, floor)). A
+    // subset's k-th best key is a lower bound of the list's final one, so a block skipped against a private threshold holds no
+    // winner, and keys are unique: the merge of the W private top-k lists at the end is the top-k of their union.
+    const uint8_t* pn = seg.pnorm + T.pn_base;
+    uint8_t* slab = slabs[wave];
+    // this wave's private list: LDS over cq, which this path never uses, checked out into registers for an offer (no lock: one owner)
+    uint64_t* mine = reinterpret_cast<uint64_t*>(cq) + wave * LIST_N;
+    mine[lane] = 0ull;
+    if (WIDE) mine[64 + lane] = 0ull;
+    if (wave == 0) {
+      count = 128 * T.nblocks;  // no deleted docs on this path: every posting is a hit
+      touched += 18u * (uint32_t)T.nblocks;
+    }
+    // the tail or the singleton, beside the other waves' blocks: its loads were requested with the directory's
+    if (wave == W - 1) {
+      count += T.df == 1 ? 1 : T.tail_n;
+      if (__ballot((oc_k0 > oc_k1 ? oc_k0 : oc_k1) > tau)) wave_offer2<WIDE>(mine, oc_k0, oc_k1, tau, k, lane, floor TERM_LK_PASS);
+    }
+    const uint32_t bd = term_bound_of(cache, oc.bm);
+    const uint64_t pm = __ballot(lane < T.nblocks && bd >= term_thr_of(floor, oc.lo));
+    // (wave W - 1 has the tail behind it: its threshold may already be above the floor)
+    uint64_t todo = __ballot(((pm >> lane) & 1ull) != 0ull && (mbcnt(pm) & (W - 1)) == wave && bd >= term_thr_of(tau, oc.lo));
+    const int first = todo ? (int)__builtin_ctzll(todo) : 0;
+    // the owner of a block parks its directory entry in the (unused) queue arrays, indexed by block: four registers less across the
+    // ring, which then costs what the general path's drain does
+    if ((todo >> lane) & 1ull) { e_row[lane] = oc.rw; e_hdr[lane] = (uint16_t)oc.hd; e_lo[lane] = oc.lo; e_bound[lane] = bd; }
+    wave_sync();
+#ifdef RGPU_TERM_TRACE
+    tq_entries = __popcll(pm);
+    TQ_TR(3, bd);
+    tq_d[4] = tq_d[3];
+#endif
+    auto take = [&]() -> int {
+      if (!todo) return -1;
+      const int i = (int)__builtin_ctzll(todo);
+      todo &= todo - 1ull;
+      return i;
+    };
+    auto rows_of = [&](int i) -> uint4 { return block_rows_load(block_rows_at(term_rows, e_row[i]), e_hdr[i], lane); };
+    auto norms_of = [&](int i) -> uint32_t {
+      return *reinterpret_cast<const uint16_t*>(pn + (128u * (uint32_t)i + 2u * (uint32_t)lane));
+    };
+    // the wave's share, up to DEPTH rows in flight (at most 15 blocks over 4 waves: one ring fill); slots without a block reload the
+    // wave's first block instead of being guarded, and a wave without a block requests nothing
+    int slot[DEPTH];
+    uint4 ring[DEPTH];
+    uint32_t nring[DEPTH];
+#pragma unroll
+    for (int j = 0; j < DEPTH; ++j) { slot[j] = -1; ring[j] = uint4{0u, 0u, 0u, 0u}; nring[j] = 0u; }
+    if (todo != 0ull) {
+#pragma unroll
+      for (int j = 0; j < DEPTH; ++j) {
+        slot[j] = take();
+        const int pj = slot[j] < 0 ? first : slot[j];
+        ring[j] = rows_of(pj);
+        nring[j] = norms_of(pj);
+      }
+    }
+    auto step = [&](int i, const uint4& rows, uint32_t nn) {
+      const uint32_t hdr = (uint32_t)e_hdr[i];
+      const int32_t lo = e_lo[i];
+      touched += encoded_block_bytes(hdr) + 128u;  // both streams' rows + the posting-order norms were requested
+      // against the wave's threshold of the moment, just before the block is unpacked
+      if (e_bound[i] < term_thr_of(tau, lo)) return;
+      const int bf = hdr_bfreq(hdr);
+      stage_rows(rows, slab, lane);
+      wave_sync();
+      uint32_t f0, f1;
+      bool in_table = true;  // wave-uniform: every freq of the block has a table column
+      if (bf) {
+        extract_pair<LEGACY>(slab + SLAB_STREAM, bf, lane, f0, f1);
+        if (bf > 3) in_table = !__ballot((f0 > f1 ? f0 : f1) > (uint32_t)SCORE_TABLE_FREQS);
+      } else {
+        const uint32_t f = (uint32_t)readlane((int)rows.x, 32);  // all-equal stream: its value
+        f0 = f1 = f;
+        in_table = f <= (uint32_t)SCORE_TABLE_FREQS;
+      }
+      const uint32_t nb0 = nn & 0xffu, nb1 = nn >> 8;
+      float s0, s1;
+      if (in_table) {
+        s0 = table_score(cache, nb0, f0);
+        s1 = table_score(cache, nb1, f1);
+      } else {
+        s0 = bm25_score(wk, (float)(int32_t)f0, cache[nb0]);
+        s1 = bm25_score(wk, (float)(int32_t)f1, cache[nb1]);
+      }
+      looked += 1u;
+      const uint32_t thr = term_thr_of(tau, lo);
+      const uint32_t r0 = __float_as_uint(s0), r1 = __float_as_uint(s1);
+      if (__ballot((r0 > r1 ? r0 : r1) >= thr)) {  // the doc deltas only when some posting can still enter
+        uint32_t e0, e1;
+        staged_doc_deltas<LEGACY>(slab, rows, hdr, lane, e0, e1);
+        int32_t d0, d1;
+        deltas_to_docs(e0, e1, lo < 0 ? 0 : lo, d0, d1);
+        const uint64_t key0 = make_key(s0, d0), key1 = make_key(s1, d1);
+        if (__ballot((key0 > key1 ? key0 : key1) > tau)) wave_offer2<WIDE>(mine, key0, key1, tau, k, lane, floor TERM_LK_PASS);
+      }
+      wave_sync();  // slab is free for the next block
+    };
+    while (slot[0] >= 0) {  // slots fill in order, so an empty slot 0 means an empty ring
+#pragma unroll
+      for (int j = 0; j < DEPTH; ++j) {
+        const uint4 rows = ring[j];
+        const uint32_t nn = nring[j];
+        const int i = slot[j];
+        slot[j] = i >= 0 ? take() : -1;
+        const int pj = slot[j] < 0 ? first : slot[j];
+        ring[j] = rows_of(pj);
+        nring[j] = norms_of(pj);
+        if (i >= 0) {
+          TERM_LK_NOW(tq_s0);
+          step(i, rows, nn);
+#ifdef RGPU_TERM_TRACE
+          tq_step += (uint32_t)((uint64_t)clock64() - tq_s0);
+#endif
+        }
+      }
+    }
+    // (the private lists are in LDS, sorted, 0 = empty: wave 0 folds them behind the barrier below)
+  } else if (fast) {
     count = wave == 0 ? 128 * T.nblocks : 0;  // no deleted docs on this path: every posting is a hit
     const uint8_t* pn = seg.pnorm + T.pn_base;
     uint8_t* slab = slabs[wave];
@@ -193,6 +389,8 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
         uint32_t tb = 0u;
 #pragma unroll
         for (int u = 0; u < TQ_CHUNK_UNROLL; ++u) {
+          // (a wave whose 64 chunks of this round all lie past the list's end — every wave of a round past it — has nothing to test)
+          if (cnext + u * NT + 64 * wave >= n_chunks) { pass_m[u] = 0ull; continue; }
           const int c = cnext + u * NT + tid;
           const bool in = c < n_chunks;
           const bool whole = in && 64 * c + 64 <= T.nblocks;
@@ -234,9 +432,10 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
           for (int s = 0; s < TQ_STEP_CHUNKS; ++s) {
             const int ci = pos + wave * TQ_STEP_CHUNKS + s;
             ch[s] = ci < n_cq ? (int)cq[ci] : -1;
-            const int nb = ch[s] < 0 ? 0 : min(64, T.nblocks - 64 * ch[s]);
+            if (ch[s] < 0) { bm[s] = 0ull; rw[s] = 0u; hd[s] = 0u; lo[s] = -1; continue; }  // an empty slot requests nothing
+            const int nb = min(64, T.nblocks - 64 * ch[s]);
             const bool ok = lane < nb;
-            const uint32_t b = T.dir_base + 64u * (uint32_t)(ch[s] < 0 ? 0 : ch[s]) + (uint32_t)lane;
+            const uint32_t b = T.dir_base + 64u * (uint32_t)ch[s] + (uint32_t)lane;
             bm[s] = ok ? seg.dir_bmax[b] : 0ull;
             rw[s] = ok ? seg.dir_row[b] : 0u;
             hd[s] = ok ? (uint32_t)seg.dir_hdr[b] : 0u;
@@ -247,9 +446,14 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
           uint32_t bd[TQ_STEP_CHUNKS];  // the block's bound: ten table reads, kept for the queue entry
 #pragma unroll
           for (int s = 0; s < TQ_STEP_CHUNKS; ++s) {
-            const int nb = ch[s] < 0 ? 0 : min(64, T.nblocks - 64 * ch[s]);
-            bd[s] = term_bound_of(cache, bm[s]);
-            pm[s] = __ballot(lane < nb && bd[s] >= term_thr_of(tau, lo[s]));
+            if (ch[s] < 0) {  // (wave-uniform) an empty slot: no bound, no candidates
+              bd[s] = 0u;
+              pm[s] = 0ull;
+            } else {
+              const int nb = min(64, T.nblocks - 64 * ch[s]);
+              bd[s] = term_bound_of(cache, bm[s]);
+              pm[s] = __ballot(lane < nb && bd[s] >= term_thr_of(tau, lo[s]));
+            }
             if (lane == 0) cnt[wave * TQ_STEP_CHUNKS + s] = (uint32_t)__popcll(pm[s]);
           }
           __syncthreads();
@@ -465,7 +669,15 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
       tau = tau_now();
       if (__ballot((key0 > key1 ? key0 : key1) > tau)) group_offer2<WIDE>(group, key0, key1, tau, k, lane, floor, slabs[0] TERM_LK_PASS);
     };
-    if (T.df == 1) {
+    WaveTopK merged;
+    if (one) {
+      // every wave's list is in LDS (the barrier above), the tail is in wave W - 1's: one bitonic merge per list
+      const uint64_t* wl = reinterpret_cast<const uint64_t*>(cq);
+      merged.a = wl[lane];
+      if (WIDE) merged.b = wl[64 + lane];
+#pragma unroll
+      for (int w = 1; w < W; ++w) topk_merge_sorted<WIDE>(merged, wl[w * LIST_N + lane], WIDE ? wl[w * LIST_N + 64 + lane] : 0ull, lane);
+    } else if (T.df == 1) {
       const bool v0 = lane == 0;
       const uint32_t nb0 = (has_norms && v0) ? norm_at(seg, T.singleton_doc) : 0u;
       collect(T.singleton_doc, 0, (uint32_t)T.singleton_freq, 1u, nb0, 0u, v0, false);
@@ -478,8 +690,8 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
       collect(d0, d1, f0, f1, nb0, nb1, v0, v1);
     }
     wave_sync();
-    const uint64_t a = list[lane];
-    const uint64_t b = WIDE ? list[64 + lane] : 0ull;
+    const uint64_t a = one ? merged.a : list[lane];
+    const uint64_t b = !WIDE ? 0ull : one ? merged.b : list[64 + lane];
     if (lane < k) out[lane] = a ? HitOut{key_doc(a) + doc_base, key_score(a)} : HitOut{-1, 0.f};
     if (WIDE && lane + 64 < k) out[lane + 64] = b ? HitOut{key_doc(b) + doc_base, key_score(b)} : HitOut{-1, 0.f};
     if (lane == 0) {
@@ -497,6 +709,7 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
       r.q = q; r.nblocks = T.nblocks; r.rounds = tq_rounds; r.entries = tq_entries; r.unpacked = (int32_t)sums[1];
       for (int i = 0; i < 7; ++i) r.d[i] = tq_d[i];
       r.waves = (unsigned int)W; r.wave0_cycles = tq_wave0;
+      r.pad[0] = one ? 1u : 0u;  // the workgroup took the one-chunk path (rounds 0, entries = the survivors of its ballot)
       int offers = 0, entered = 0;
       for (int w = 0; w < (W < 8 ? W : 8); ++w) {
         r.cyc[w][0] = tq_w[w][0]; r.cyc[w][1] = tq_w[w][1]; r.cyc[w][2] = tq_w[w][2] - tq_w[w][0] - tq_w[w][1];

@@ -264,6 +264,7 @@ struct rgpu_ctx {
   rucene::TermArena arena;             // the descriptor arena's bookkeeping (host/term_arena.hpp); RGPU_TERM_ARENA_RECORDS sizes it
   std::vector<void*> arena_spares;     // buffers of retired generations, kept for the next turnover (at most ARENA_SPARES_MAX)
   int term_query_waves = 4;       // 2, 4 or 8 (RGPU_TERM_QUERY_WAVES)
+  int term_short_blocks = 64;     // ... table-path lists of at most this many FullBlocks take its one-chunk path (RGPU_TERM_SHORT_BLOCKS, 0..64; 0: off)
   int term_min_item_blocks = 64;  // ... and none of its items shorter than this (RGPU_TERM_MIN_ITEM_BLOCKS)
   int term_target_items = 3000;  // single-term launches: items of the launch's size, at most about this many (RGPU_TERM_TARGET_ITEMS in the environment)
   int term_split = 8;         // single-term queries: at least this many items per query, of 64 blocks or more each (RGPU_TERM_SPLIT in the environment; 1: off)
@@ -1311,6 +1312,7 @@ extern "C" int32_t rgpu_init(int32_t device_ordinal, const rgpu_config* cfg, rgp
   if (const char* e = std::getenv("RGPU_SLOT_EVENT")) c->term_slot_event_bound = std::strcmp(e, "record") != 0;
   if (const char* e = std::getenv("RGPU_TERM_ARENA_RECORDS")) c->arena = rucene::TermArena((uint32_t)std::max(1, std::min(1 << 24, std::atoi(e))));
   if (const char* e = std::getenv("RGPU_TERM_QUERY_WAVES")) { const int w = std::atoi(e); c->term_query_waves = w <= 2 ? 2 : w >= 8 ? 8 : 4; }
+  if (const char* e = std::getenv("RGPU_TERM_SHORT_BLOCKS")) c->term_short_blocks = std::max(0, std::min(64, std::atoi(e)));
   if (const char* e = std::getenv("RGPU_TERM_MIN_ITEM_BLOCKS")) c->term_min_item_blocks = std::max(8, std::min(4096, std::atoi(e)));
   if (const char* e = std::getenv("RGPU_TERM_SPLIT")) c->term_split = std::max(1, std::min(64, std::atoi(e)));
   if (const char* e = std::getenv("RGPU_COUNT_WINDOWS_PER_ITEM")) c->count_windows_per_item = std::max(0, std::min(1 << 20, std::atoi(e)));
@@ -7041,9 +7043,10 @@ static int32_t term_batch_resident(rgpu_segment* seg, rucene::BatchPlanner* P, i
     auto go = [&](auto kern, int waves) -> hipError_t {
       // (hipExtLaunchKernelGGL passes the arguments as they are typed here: each one has its parameter's type exactly)
       if (bound) RGPU_LAUNCH_WITH_STOP(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, c->S->done, sv, (const DevQuery*)nullptr, d_arena, (const int32_t*)nullptr,
-                                       (int)nq, (int)k, d_work, (const int32_t*)nullptr, hits_dev, totals_dev, (int32_t)seg->doc_base, (const TermLaunch*)hl);
+                                       (int)nq, (int)k, d_work, (const int32_t*)nullptr, hits_dev, totals_dev, (int32_t)seg->doc_base, (const TermLaunch*)hl,
+                                       (int)c->term_short_blocks);
       else RGPU_LAUNCH(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, sv, (const DevQuery*)nullptr, d_arena, (const int32_t*)nullptr, nq, (int)k, d_work,
-                       (const int32_t*)nullptr, hits_dev, totals_dev, seg->doc_base, (const TermLaunch*)hl);
+                       (const int32_t*)nullptr, hits_dev, totals_dev, seg->doc_base, (const TermLaunch*)hl, c->term_short_blocks);
       return hipSuccess;
     };
     auto pick = [&](auto legacy_c, auto wide_c) -> hipError_t {
@@ -7263,7 +7266,7 @@ static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32
     const int32_t* dord = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_ord);
     auto go = [&](auto kern, int waves) -> hipError_t {
       RGPU_LAUNCH(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, sv, dq, dt, dord, nq, (int)k, d_work, dm, hits_dev, totals_dev, seg->doc_base,
-                  (const TermLaunch*)nullptr);
+                  (const TermLaunch*)nullptr, c->term_short_blocks);
       return hipSuccess;
     };
     auto pick = [&](auto legacy_c, auto wide_c) -> hipError_t {

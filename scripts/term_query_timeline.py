@@ -49,6 +49,9 @@ end = (rec["t1"] - t0) / 100.0
 dur = end - start
 W = int(rec["waves"][0])
 print("%d workgroups of %d waves traced; launch span %.1f us" % (rec.size, W, end.max()))
+one = rec["pad"][:, 0] == 1  # (the kernel marks a workgroup that took the one-chunk path)
+print("%d workgroups took the one-chunk path (lists of at most RGPU_TERM_SHORT_BLOCKS blocks): mean %.1f us, max %.1f us" % (
+    one.sum(), dur[one].mean() if one.any() else 0.0, dur[one].max() if one.any() else 0.0))
 print("workgroup duration us: mean %.1f  p50 %.1f  p90 %.1f  p99 %.1f  max %.1f" % (dur.mean(), *np.percentile(dur, [50, 90, 99]), dur.max()))
 print("workgroup start us: p50 %.1f  p90 %.1f  max %.1f;  sum of durations %.0f us = %.1f x the span" % (
     *np.percentile(start, [50, 90]), start.max(), dur.sum(), dur.sum() / end.max()))
