@@ -47,12 +47,22 @@ constexpr int TQ_CHUNK_UNROLL = 4;      // chunk frontier words per thread per g
 #define RGPU_TERMQ_STEP_CHUNKS 2
 #endif
 constexpr int TQ_STEP_CHUNKS = RGPU_TERMQ_STEP_CHUNKS;  // surviving chunks per wave per gather step
-// The bound asks for 7 waves per SIMD. With the one-chunk path in the kernel, a bound of 6 (k_search_term's) lets the scheduler spread
-// the general path's drain over 73 VGPRs (six waves); at 7 the headline instantiation takes 71, no scratch, and keeps its seven.
-// (W = 2 keeps k_search_term's bound: two-wave workgroups ran at six before, and do not fit seven.)
+// The bound asks for 6 waves per SIMD (k_search_term's): the scheduler spreads the general path's drain over 73 VGPRs and spills 22
+// SGPRs. A bound of 7 holds the headline instantiation to 71 VGPRs and seven waves, pays for it with 44 spilled SGPRs in the general
+// path, and its one-stream step measures 5 % slower in every run: -DRGPU_TERMQ_FAST_WAVES=7 builds it. (W = 2 always takes
+// k_search_term's bound: two-wave workgroups do not fit seven.)
 #ifndef RGPU_TERMQ_FAST_WAVES
-#define RGPU_TERMQ_FAST_WAVES 7
+#define RGPU_TERMQ_FAST_WAVES 6
 #endif
+// 1: variant builds whose block gather deals a window's surviving chunks to the waves without a barrier, the queue entries reserved
+// from an LDS counter (modelled by tests/test_term_gather_model_cpu.py). 1-1.5 % faster, not separated from noise.
+#ifndef RGPU_TERMQ_DEAL
+#define RGPU_TERMQ_DEAL 0
+#endif
+#ifndef RGPU_TERMQ_DEAL_CHUNKS
+#define RGPU_TERMQ_DEAL_CHUNKS 4
+#endif
+constexpr int TQ_DEAL_CHUNKS = RGPU_TERMQ_DEAL_CHUNKS;  // chunks a wave has in flight in the dealt gather (one round trip for them all)
 #ifndef RGPU_TERMQ_ONE  // 0: variant builds without the one-chunk path
 #define RGPU_TERMQ_ONE 1
 #endif
@@ -140,6 +150,10 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
   static_assert(sizeof(uint32_t) * TQ_CHUNK_UNROLL * NT >= sizeof(uint64_t) * W * LIST_N, "W private lists of LIST_N keys alias cq");
   __shared__ uint32_t cnt[TQ_CHUNK_UNROLL * NT / 64 > W * TQ_STEP_CHUNKS ? TQ_CHUNK_UNROLL * NT / 64 : W * TQ_STEP_CHUNKS];
   __shared__ uint32_t cursor;
+#if RGPU_TERMQ_DEAL
+  __shared__ uint32_t q_count, q_end;                       // entries reserved this round; where the first reservation that did not fit starts
+  __shared__ uint32_t done_map[TQ_CHUNK_UNROLL * NT / 32];  // one bit per chunk of the gather window: its blocks are queued
+#endif
   __shared__ uint32_t sums[3];  // hits, blocks unpacked, bytes requested
   __shared__ uint64_t floor_s;
 
@@ -378,13 +392,22 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
     const uint8_t* pn = seg.pnorm + T.pn_base;
     uint8_t* slab = slabs[wave];
     int cnext = 0;  // workgroup-uniform: the first chunk not gathered yet
+#if RGPU_TERMQ_DEAL
+    bool redo = false;  // workgroup-uniform: the window at cnext filled a round and is repeated (done_map holds what it queued)
+#endif
     while (cnext < n_chunks) {  // rounds
       int nq = 0;  // entries in the queue (workgroup-uniform)
+#if RGPU_TERMQ_DEAL
+      if (tid == 0) { q_count = 0u; q_end = 0xffffffffu; }  // (the window's barriers lie between this and the first reservation)
+#endif
       // ---- gather ----
       while (cnext < n_chunks) {
         // a window of TQ_CHUNK_UNROLL * NT chunks from cnext: one thread per chunk against its frontier word, strict where the doc in
         // front of the chunk is at or past the threshold's doc (the list is the same in every wave: nothing is offered while gathering)
         tau = tau_now();
+#if RGPU_TERMQ_DEAL
+        if (!redo && tid < TQ_CHUNK_UNROLL * NT / 32) done_map[tid] = 0u;  // a new window (its chunks are marked two barriers on)
+#endif
         uint64_t pass_m[TQ_CHUNK_UNROLL];
         uint32_t tb = 0u;
 #pragma unroll
@@ -392,7 +415,16 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
           // (a wave whose 64 chunks of this round all lie past the list's end — every wave of a round past it — has nothing to test)
           if (cnext + u * NT + 64 * wave >= n_chunks) { pass_m[u] = 0ull; continue; }
           const int c = cnext + u * NT + tid;
+#if RGPU_TERMQ_DEAL  // a repeated window: the chunks an earlier round of it queued are out (this wave's 64 bits of the map, uniform)
+          uint64_t dm = 0ull;
+          if (redo) {
+            const int wd = 2 * (u * W + wave);
+            dm = ((uint64_t)(uint32_t)readfirstlane((int)done_map[wd + 1]) << 32) | (uint32_t)readfirstlane((int)done_map[wd]);
+          }
+          const bool in = c < n_chunks && ((dm >> lane) & 1ull) == 0ull;
+#else
           const bool in = c < n_chunks;
+#endif
           const bool whole = in && 64 * c + 64 <= T.nblocks;
           const bool worded = whole && seg.dir_sum != nullptr;
           const uint64_t w = worded ? seg.dir_sum[sum_base + (uint32_t)c] : 15ull;
@@ -418,6 +450,75 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
         const int n_cq = (int)readfirstlane(wave_reduce_add(lane < TQ_CHUNK_UNROLL * W ? (int)cnt[lane] : 0));
         const int window_end = min(n_chunks, cnext + TQ_CHUNK_UNROLL * NT);
         __syncthreads();
+#if RGPU_TERMQ_DEAL
+        // the surviving chunks, dealt to the waves (wave w: cq[w], cq[w + W], ...), no barrier inside: every block's frontier word,
+        // store row, header and the doc in front of it, one lane per block, TQ_DEAL_CHUNKS chunks of the wave requested at a time.
+        // The blocks that may still enter take queue entries reserved from q_count (consecutive intervals of a counter that only
+        // grows): a reservation that fits is written and its chunk marked done; the first that does not fit starts at q_end, every
+        // earlier one ends at or below it and every later one starts past TQ_CAP — [0, min(q_count, q_end)) is what was written.
+        bool full = false;
+        if (n_cq > 0) {
+          bool stop = false;  // (wave-uniform) this wave met a full queue
+          for (int base = wave; base < n_cq && !stop; base += W * TQ_DEAL_CHUNKS) {
+            uint64_t bm[TQ_DEAL_CHUNKS];
+            uint32_t rw[TQ_DEAL_CHUNKS], hd[TQ_DEAL_CHUNKS];
+            int32_t lo[TQ_DEAL_CHUNKS];
+            int ch[TQ_DEAL_CHUNKS];
+#pragma unroll
+            for (int g = 0; g < TQ_DEAL_CHUNKS; ++g) {
+              const int ci = base + g * W;
+              ch[g] = ci < n_cq ? (int)cq[ci] : -1;
+              if (ch[g] < 0) { bm[g] = 0ull; rw[g] = 0u; hd[g] = 0u; lo[g] = -1; continue; }  // an empty slot requests nothing
+              const int nb = min(64, T.nblocks - 64 * ch[g]);
+              const bool ok = lane < nb;
+              const uint32_t b = T.dir_base + 64u * (uint32_t)ch[g] + (uint32_t)lane;
+              bm[g] = ok ? seg.dir_bmax[b] : 0ull;
+              rw[g] = ok ? seg.dir_row[b] : 0u;
+              hd[g] = ok ? (uint32_t)seg.dir_hdr[b] : 0u;
+              lo[g] = (ok && b > T.dir_base) ? seg.dir_last[b - 1u] : -1;
+              touched += 18u * (uint32_t)nb;
+            }
+#pragma unroll
+            for (int g = 0; g < TQ_DEAL_CHUNKS; ++g) {
+              if (ch[g] < 0 || stop) continue;
+              const int nb = min(64, T.nblocks - 64 * ch[g]);
+              const uint32_t bd = term_bound_of(cache, bm[g]);
+              const uint64_t pm = __ballot(lane < nb && bd >= term_thr_of(tau, lo[g]));
+              const int n = __popcll(pm);
+              const int wi = ch[g] - cnext;  // the chunk's bit in the window's done map
+              uint32_t at = 0u;
+              if (n > 0) {  // (a chunk with nothing to queue is done without a reservation)
+                if (lane == 0) at = atomicAdd(&q_count, (uint32_t)n);
+                at = (uint32_t)readfirstlane((int)at);
+                if (at + (uint32_t)n > (uint32_t)TQ_CAP) {  // the round is full; the chunk stays undone and this wave takes no more
+                  if (lane == 0) atomicMin(&q_end, at);
+                  stop = true;
+                  continue;
+                }
+                if ((pm >> lane) & 1ull) {
+                  const uint32_t e = at + (uint32_t)mbcnt(pm);
+                  e_blk[e] = (uint32_t)(64 * ch[g] + lane);
+                  e_row[e] = rw[g];
+                  e_hdr[e] = (uint16_t)hd[g];
+                  e_lo[e] = lo[g];
+                  e_bound[e] = bd;
+                }
+              }
+              if (lane == 0) atomicOr(&done_map[wi >> 5], 1u << (wi & 31));
+            }
+          }
+          __syncthreads();
+          const uint32_t qc = q_count, qe = q_end;
+          nq = (int)(qc < qe ? qc : qe);
+          full = qe != 0xffffffffu;
+        }
+        // a full round drains, then repeats this window from its start with the threshold the drain reached: the window test skips
+        // the chunks marked done, so no block is queued twice
+        redo = full;
+        if (full) break;
+        cnext = window_end;
+      }
+#else
         // the surviving chunks, TQ_STEP_CHUNKS per wave per step: every block's frontier word, store row, header and the doc in front
         // of it, one lane per block; the blocks that may still enter are appended to the queue in block order. A step whose blocks
         // do not all fit ends the round at the first chunk that does not fit.
@@ -482,12 +583,25 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
         cnext = window_end;
         if (full) break;
       }
+#endif
 #ifdef RGPU_TERM_TRACE
       if (tq_rounds == 0) TQ_TR(3, nq);
       tq_rounds += 1;
       tq_entries += nq;
 #endif
       if (nq == 0) continue;
+#if RGPU_TERMQ_DEAL
+      // ---- sort: queue position -> entry, (bound desc, block asc) as one key; the entries lie in the order the waves reserved them ----
+      for (int i = tid; i < nq; i += NT) {
+        const uint64_t ki = ((uint64_t)e_bound[i] << 32) | (uint64_t)(0xffffffffu - e_blk[i]);
+        int r = 0;
+        for (int j = 0; j < nq; ++j) {
+          const uint64_t kj = ((uint64_t)e_bound[j] << 32) | (uint64_t)(0xffffffffu - e_blk[j]);
+          r += kj > ki ? 1 : 0;
+        }
+        e_order[r] = (uint16_t)i;
+      }
+#else
       // ---- sort: queue position -> entry, (bound desc, entry asc); entries are in block order ----
       for (int i = tid; i < nq; i += NT) {
         const uint32_t bi = e_bound[i];
@@ -498,6 +612,7 @@ void k_search_term_query(SegView seg, const DevQuery* __restrict__ queries, cons
         }
         e_order[r] = (uint16_t)i;
       }
+#endif
       if (tid == 0) cursor = 0u;
       __syncthreads();
 #ifdef RGPU_TERM_TRACE
