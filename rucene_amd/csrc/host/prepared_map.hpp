@@ -34,7 +34,7 @@ struct PreparedMap {
   std::vector<uint8_t> moved;                      // bulk[i] lives in `map` now
   size_t bulk_live = 0;
   // bumped by everything that adds, replaces or removes a term's TermInfo (a term moving from `bulk` into `map` keeps its value and
-  // does not count): what a memo of finished descriptors checks (rgpu_api.hip term_batch_fast)
+  // does not count): what a memo of finished descriptors checks (api/fused.hpp term_batch_fast)
   uint64_t epoch = 1;
   static TermInfo expand(const PreparedEntry& e, uint64_t bs_base, bool no_norms) {
     return TermInfo{e.dir_base, e.df / 128, e.df, 0, bs_base, no_norms};

@@ -1,4 +1,4 @@
-// The bookkeeping of a context's device-resident term descriptors (rgpu_api.hip term_batch_resident). Host-only: no HIP calls, the
+// The bookkeeping of a context's device-resident term descriptors (api/fused.hpp term_batch_resident). Host-only: no HIP calls, the
 // device buffers and events are opaque pointers the owner allocates, frees and records.
 //
 // A fused single-term step names the same terms call after call, and a term's descriptor depends only on things that stay put between

@@ -124,7 +124,7 @@ struct TermBitmap {
   int32_t pad;
 };
 
-// One workgroup of k_search_term_query when the term descriptors live on the device (rgpu_api.hip term_batch_resident): the whole
+// One workgroup of k_search_term_query when the term descriptors live on the device (api/fused.hpp term_batch_resident): the whole
 // per-step plan of a query, in launch order, read straight from pinned host memory.
 struct TermLaunch {
   int32_t rec;  // the term's DevTerm in the descriptor arena; -1: the leaf does not hold the term

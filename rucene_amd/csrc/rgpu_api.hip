@@ -6112,1341 +6112,12 @@ extern "C" int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phras
   return RGPU_OK;
 }
 
-// ---- segment-sharded search: RCCL all-gather of per-shard top-k + device merge -------------------------------------------
-constexpr int N_COMM_SLOTS = 4;
-struct CommSlot {
-  // One record (record_bytes: hits, counts, status word) per rank. The all-gather is IN PLACE: this rank's search writes its
-  // record straight into its own region, recv + rank * record (ncclAllGather with sendbuff == recvbuff + rank * count moves
-  // nothing locally: no send buffer, no device copy of the rank's own record).
-  DevVec<uint8_t> recv;
-  size_t record = 0;           // the record size the status words below were prepared for
-  bool status_zero = false;    // this rank's status word already reads RGPU_OK (zeroed with the buffer, never dirtied since): a
-                               // successful search then needs no extra launch to say so
-  hipEvent_t done = nullptr;
-  bool busy = false;
-};
-struct rgpu_comm {
-  rgpu_ctx* ctx = nullptr;
-  ncclComm_t nccl = nullptr;
-  int n_ranks = 1, rank = 0;
-  CommSlot slots[N_COMM_SLOTS];
-  int next = 0;
-  // collectives of one communicator must not run side by side: when consecutive calls come on different streams, the
-  // later all-gather waits for the earlier one (an event), while the searches in front of them still overlap
-  hipStream_t last_stream = nullptr;
-  hipEvent_t last_collective = nullptr;
-  bool have_last = false;
-  CommSlot* last_slot = nullptr;  // the most recent batch's records (rgpu_comm_status)
-  int32_t last_queries = 0, last_k = 0;
-  int64_t gathers_issued = 0;     // ncclAllGather calls enqueued on this communicator (rgpu_comm_gathers_issued)
-};
-#define NCCL_TRY(expr)                                                                                          \
-  do {                                                                                                          \
-    ncclResult_t _r = (expr);                                                                                   \
-    if (_r != ncclSuccess) return fail(RGPU_ERR_RUNTIME, std::string(#expr) + ": " + ncclGetErrorString(_r)); \
-  } while (0)
-static_assert(RGPU_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "rgpu_comm ids are ncclUniqueIds");
-
-extern "C" int32_t rgpu_comm_unique_id(uint8_t* id_out) {
-  if (!id_out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "id_out is null");
-  ncclUniqueId id;
-  NCCL_TRY(ncclGetUniqueId(&id));
-  std::memcpy(id_out, id.internal, RGPU_COMM_ID_BYTES);
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_comm_init(rgpu_ctx* c, int32_t n_ranks, int32_t rank, const uint8_t* id_bytes, rgpu_comm** out) {
-  if (!out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "out_comm is null");
-  *out = nullptr;
-  if (!c || !id_bytes) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
-  if (n_ranks < 1 || rank < 0 || rank >= n_ranks) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "rank outside [0, n_ranks)");
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  ncclUniqueId id;
-  std::memcpy(id.internal, id_bytes, RGPU_COMM_ID_BYTES);
-  auto comm = std::make_unique<rgpu_comm>();
-  comm->ctx = c;
-  comm->n_ranks = n_ranks;
-  comm->rank = rank;
-  NCCL_TRY(ncclCommInitRank(&comm->nccl, n_ranks, id, rank));
-  *out = comm.release();
-  return RGPU_OK;
-}
-
-// One process, one thread, n contexts (Rucene itself is one process: search_parallel hands leaves to threads,
-// searcher.rs:527-630): ncclCommInitRank blocks until every rank of the id has joined, so n of them issued one after the
-// other from one thread would never return — they have to sit inside one ncclGroupStart / ncclGroupEnd.
-extern "C" int32_t rgpu_comm_init_all(rgpu_ctx* const* ctxs, int32_t n, rgpu_comm** out_comms) {
-  if (!ctxs || !out_comms || n < 1) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  for (int32_t r = 0; r < n; ++r) {
-    out_comms[r] = nullptr;
-    if (!ctxs[r]) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null context");
-    for (int32_t j = 0; j < r; ++j)
-      if (ctxs[j] == ctxs[r] || ctxs[j]->device == ctxs[r]->device) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "every rank needs its own context on its own device");
-  }
-  ncclUniqueId id;
-  NCCL_TRY(ncclGetUniqueId(&id));
-  std::vector<std::unique_ptr<rgpu_comm>> comms;
-  for (int32_t r = 0; r < n; ++r) {
-    comms.emplace_back(new rgpu_comm());
-    comms.back()->ctx = ctxs[r];
-    comms.back()->n_ranks = n;
-    comms.back()->rank = r;
-  }
-  ncclResult_t res = ncclGroupStart();
-  for (int32_t r = 0; r < n && res == ncclSuccess; ++r) {
-    if (hipSetDevice(ctxs[r]->device) != hipSuccess) { res = ncclUnhandledCudaError; break; }
-    res = ncclCommInitRank(&comms[(size_t)r]->nccl, n, id, r);
-  }
-  const ncclResult_t end = ncclGroupEnd();
-  if (res == ncclSuccess) res = end;
-  if (res != ncclSuccess) {
-    for (auto& cm : comms) if (cm->nccl) (void)ncclCommAbort(cm->nccl);
-    return fail(RGPU_ERR_RUNTIME, std::string("ncclCommInitRank (grouped): ") + ncclGetErrorString(res));
-  }
-  for (int32_t r = 0; r < n; ++r) out_comms[r] = comms[(size_t)r].release();
-  return RGPU_OK;
-}
-
-extern "C" void rgpu_comm_destroy(rgpu_comm* comm) {
-  if (!comm) return;
-  (void)hipSetDevice(comm->ctx->device);
-  for (auto& sl : comm->slots) {
-    if (sl.busy) (void)hipEventSynchronize(sl.done);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-    sl.recv.release();
-  }
-  if (comm->last_collective) (void)hipEventDestroy(comm->last_collective);
-  if (comm->nccl) (void)ncclCommDestroy(comm->nccl);
-  delete comm;
-}
-
-// ---- a shard's record: what one rank contributes to the all-gather ---------------------------------------------------------
-// [n_queries x k rgpu_hit][n_queries x int64 hit count][int64 status] — the status word is the rank's rgpu_status for the
-// batch: a rank whose local search failed still takes part in the collective (with empty rows), so that the other ranks
-// neither hang in the all-gather nor silently merge a stale record; every rank can read everybody's status afterwards.
-static size_t record_hits_bytes(int32_t n_queries, int32_t k) { return (size_t)n_queries * (size_t)k * sizeof(HitOut); }
-static size_t record_bytes(int32_t n_queries, int32_t k) { return record_hits_bytes(n_queries, k) + (size_t)n_queries * 8 + 8; }
-extern "C" int64_t rgpu_record_bytes(int32_t n_queries, int32_t k) {
-  if (n_queries <= 0 || k <= 0) return 0;
-  return (int64_t)record_bytes(n_queries, k);
-}
-
-__global__ void k_set_i64(int64_t* p, int64_t v) { *p = v; }
-
-// local search of one shard straight into a record (device memory, record_bytes long); enqueue-only. The call's own status
-// is returned AND left in the record's status word; on failure the record holds empty rows.
-// `status_zero` (in / out, may be null): the record's status word is known to hold RGPU_OK already — a successful search then
-// leaves it alone (one launch less per batch on the serving path); a failure writes it and clears the flag.
-// `defer`: >= 10-clause disjunctions leave their hand-back flags for settle_pending (the caller runs it before the record is
-// read by anybody: before the collective) — the one-process form enqueues every shard's search before it waits for any.
-// A uniform batch that is still to be planned (the fused plan + search entry points): n_queries x n_clauses flat-table ids
-struct UniformBatch {
-  rgpu_planner* planner;
-  int32_t op, n_clauses;
-  const int64_t* ids;
-};
-static int32_t search_uniform_locked(rgpu_segment* seg, const UniformBatch& ub, int32_t n_queries, int32_t k, HitOut* hits_dev, int64_t* totals_dev,
-                                     hipStream_t stream);
-static int32_t search_into_record(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
-                                  int32_t n_terms_total, int32_t k, uint8_t* record, hipStream_t s, bool* status_zero = nullptr, bool defer = false,
-                                  const UniformBatch* uniform = nullptr) {
-  const size_t hits_bytes = record_hits_bytes(n_queries, k);
-  seg->ctx->defer_or = defer;
-  int32_t rc = uniform ? search_uniform_locked(seg, *uniform, n_queries, k, (HitOut*)record, (int64_t*)(record + hits_bytes), s)
-                       : search_impl(seg, queries, n_queries, terms, n_terms_total, k, (HitOut*)record, (int64_t*)(record + hits_bytes), s);
-  seg->ctx->defer_or = false;
-  std::string why = rc == RGPU_OK ? std::string() : g_last_error;
-  // No early return below: the status word is written whatever else fails (a peer that merged a record without one would
-  // take stale rows for this shard's answer), and the first error is the one reported.
-  auto note = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && rc == RGPU_OK) { rc = RGPU_ERR_RUNTIME; why = std::string(what) + ": " + hipGetErrorString(e); }
-  };
-  if (rc != RGPU_OK) {  // whatever was enqueued before the failure is overwritten behind it on the same stream
-    note(hipMemsetAsync(record + hits_bytes, 0, (size_t)n_queries * 8, s), "hipMemsetAsync(record counts)");
-    RGPU_LAUNCH(k_init_hits, dim3(wg_count(((size_t)n_queries * k + 255) / 256)), dim3(256), 0, s, (HitOut*)record, (int64_t)n_queries, (int)k, (int)k, 0);
-    note(launch_status(), "k_init_hits");
-  }
-  if (rc == RGPU_OK && status_zero != nullptr && *status_zero) return RGPU_OK;  // the word says RGPU_OK already
-  if (status_zero != nullptr) *status_zero = false;  // (set again by the caller once it has zeroed the word)
-  RGPU_LAUNCH(k_set_i64, dim3(1), dim3(1), 0, s, (int64_t*)(record + hits_bytes + (size_t)n_queries * 8), (int64_t)rc);
-  const hipError_t e_status = launch_status();
-  if (e_status != hipSuccess) {  // the launch itself was refused: put the word there with a copy from the host instead
-    const int64_t word = rc != RGPU_OK ? (int64_t)rc : (int64_t)RGPU_ERR_RUNTIME;
-    (void)hipMemcpyAsync(record + hits_bytes + (size_t)n_queries * 8, &word, 8, hipMemcpyHostToDevice, s);
-    (void)hipStreamSynchronize(s);  // (`word` lives on this frame)
-    note(e_status, "k_set_i64");
-  }
-  if (rc != RGPU_OK) return fail(rc, why);
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_search_batch_record_device(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries,
-                                                   const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, void* record_dev,
-                                                   void* hip_stream) {
-  if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !record_dev) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
-  std::lock_guard<std::mutex> g(seg->ctx->mu);
-  HIP_TRY(hipSetDevice(seg->ctx->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : seg->ctx->stream;
-  return search_into_record(seg, queries, n_queries, terms, n_terms_total, k, (uint8_t*)record_dev, s);
-}
-
-// the canonical k-way merge over `n_ranks` gathered records (k_merge_lists reading them in place, with the record stride)
-static int32_t merge_records(rgpu_ctx* c, const uint8_t* records, int32_t n_ranks, int32_t n_queries, int32_t k, HitOut* hits_dev,
-                             int64_t* totals_dev, hipStream_t s) {
-  const size_t hits_bytes = record_hits_bytes(n_queries, k), record = record_bytes(n_queries, k);
-  {
-    TimedLaunch tl(c, s, "k_merge_lists", 0);
-    const unsigned grid = wg_count((n_queries + WG_WAVES - 1) / WG_WAVES);
-    auto go = [&](auto kern) {
-      RGPU_LAUNCH(kern, dim3(grid), dim3(WG_THREADS), 0, s, (const HitOut*)records, (const int64_t*)(records + hits_bytes),
-                         (int64_t)(record / sizeof(HitOut)), (int64_t)(record / 8), n_ranks, n_queries, (int)k, hits_dev, totals_dev);
-    };
-    if (k > 64) go(k_merge_lists<true>); else go(k_merge_lists<false>);
-  }
-  HIP_TRY(launch_status());
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_merge_records_device(rgpu_ctx* c, const void* records_dev, int32_t n_ranks, int32_t n_queries, int32_t k,
-                                             void* hits_out_dev, void* totals_out_dev, void* hip_stream) {
-  if (!c || !records_dev || !hits_out_dev || !totals_out_dev || n_ranks <= 0 || n_queries <= 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  return merge_records(c, (const uint8_t*)records_dev, n_ranks, n_queries, k, (HitOut*)hits_out_dev, (int64_t*)totals_out_dev,
-                       hip_stream ? (hipStream_t)hip_stream : c->stream);
-}
-
-// ---- the three phases of a sharded batch (context mutex held by the caller) -------------------------------------------------
-struct ShardedCall {
-  CommSlot* sl = nullptr;
-  size_t record = 0;
-  int32_t local_rc = RGPU_OK;
-  std::string local_why;
-  int32_t pre_rc = RGPU_OK;  // a failure in front of the collective that did not keep this rank from joining it
-  std::string pre_why;
-};
-// phase 0: the slot and its buffers. The ONE thing that can fail here and leave the communicator out of step with its peers
-// is the allocation of the record buffer itself (nowhere to gather into): rgpu_comm_reserve does it at start-up, so a serving
-// host never allocates on the data path. Everything else that goes wrong (a wait on the slot's previous batch, the status
-// word's memset) is remembered in call->pre_rc and reported AFTER the collective has been joined.
-static int32_t sharded_reserve(rgpu_comm* comm, int32_t n_queries, int32_t k, hipStream_t s, ShardedCall* call) {
-  CommSlot& sl = comm->slots[comm->next];
-  auto note = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && call->pre_rc == RGPU_OK) { call->pre_rc = RGPU_ERR_RUNTIME; call->pre_why = std::string(what) + ": " + hipGetErrorString(e); }
-  };
-  if (sl.busy) { note(hipEventSynchronize(sl.done), "hipEventSynchronize(slot)"); sl.busy = false; }
-  const size_t record = record_bytes(n_queries, k);
-  const uint8_t* before = sl.recv.p;
-  HIP_TRY(sl.recv.reserve(record * (size_t)comm->n_ranks, 0, s));
-  if (sl.recv.p != before || sl.record != record || !sl.status_zero) {
-    // this rank's status word, zeroed once per (buffer, record size): a batch that succeeds never touches it again
-    const hipError_t e = hipMemsetAsync(sl.recv.p + (size_t)comm->rank * record + record - 8, 0, 8, s);
-    sl.record = record;
-    sl.status_zero = e == hipSuccess;  // not zeroed: search_into_record writes the word with a launch instead
-  }
-  call->sl = &sl;
-  call->record = record;
-  return RGPU_OK;
-}
-// phase 1: from here on this rank WILL enqueue the collective, whatever its local search does (search_into_record leaves the
-// status in the record)
-static void sharded_local(rgpu_comm* comm, rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
-                          int32_t n_terms_total, int32_t k, hipStream_t s, ShardedCall* call, bool defer = false, const UniformBatch* uniform = nullptr) {
-  comm->next = (comm->next + 1) % N_COMM_SLOTS;
-  call->local_rc = search_into_record(seg, queries, n_queries, terms, n_terms_total, k, call->sl->recv.p + (size_t)comm->rank * call->record, s,
-                                      &call->sl->status_zero, defer, uniform);
-  if (call->local_rc != RGPU_OK) call->local_why = g_last_error;
-}
-// phase 1b (after a deferred sharded_local): whatever the shard's disjunctions still have to run again runs now, before the
-// record is gathered; a failure becomes the shard's status like a failure of the search itself
-static void sharded_settle(rgpu_comm* comm, int32_t n_queries, int32_t k, hipStream_t s, ShardedCall* call) {
-  const int32_t rc = settle_pending(comm->ctx);
-  if (rc == RGPU_OK || call->local_rc != RGPU_OK) return;
-  call->local_rc = rc;
-  call->local_why = g_last_error;
-  uint8_t* record = call->sl->recv.p + (size_t)comm->rank * call->record;
-  const size_t hits_bytes = record_hits_bytes(n_queries, k);
-  call->sl->status_zero = false;
-  (void)hipMemsetAsync(record + hits_bytes, 0, (size_t)n_queries * 8, s);
-  RGPU_LAUNCH(k_init_hits, dim3(wg_count(((size_t)n_queries * k + 255) / 256)), dim3(256), 0, s, (HitOut*)record, (int64_t)n_queries, (int)k, (int)k, 0);
-  RGPU_LAUNCH(k_set_i64, dim3(1), dim3(1), 0, s, (int64_t*)(record + hits_bytes + (size_t)n_queries * 8), (int64_t)rc);
-  (void)launch_status();
-}
-static int32_t sharded_gather(rgpu_comm* comm, hipStream_t s, ShardedCall& call) {
-  // A communicator of one rank has nothing to gather: its record is already where the merge reads it. (Before round 5 this
-  // path cost a device copy of the record, a one-thread launch for the status word and an event wait between consecutive
-  // batches on different streams: 0.157 ms per 1024-query TERM step against 0.093 for the local search.)
-  // rgpu_config.comm_force_gather issues the in-place all-gather all the same: the N > 1 path on a one-GPU box.
-  if (comm->n_ranks == 1 && comm->ctx->cfg.comm_force_gather == 0) return RGPU_OK;
-  auto note = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && call.pre_rc == RGPU_OK) { call.pre_rc = RGPU_ERR_RUNTIME; call.pre_why = std::string(what) + ": " + hipGetErrorString(e); }
-    return e;
-  };
-  // collectives of one communicator run one after the other; when the stream changed, the later one waits for the earlier
-  // one's event. If that wait cannot be enqueued the host waits instead — this rank still joins the collective (its peers
-  // are in it already): nothing between sharded_reserve and ncclAllGather returns
-  if (comm->have_last && comm->last_stream != s)
-    if (note(hipStreamWaitEvent(s, comm->last_collective, 0), "hipStreamWaitEvent(last collective)") != hipSuccess)
-      (void)hipEventSynchronize(comm->last_collective);
-  uint8_t* const mine = call.sl->recv.p + (size_t)comm->rank * call.record;  // in place: sendbuff == recvbuff + rank * count
-  NCCL_TRY(ncclAllGather(mine, call.sl->recv.p, call.record, ncclInt8, comm->nccl, s));
-  comm->gathers_issued++;
-  if (!comm->last_collective) (void)note(hipEventCreateWithFlags(&comm->last_collective, hipEventDisableTiming), "hipEventCreate(last collective)");
-  if (comm->last_collective && note(hipEventRecord(comm->last_collective, s), "hipEventRecord(last collective)") == hipSuccess) {
-    comm->last_stream = s;
-    comm->have_last = true;
-  } else {  // no event to order the next collective behind this one: the host waits for this one now
-    (void)hipStreamSynchronize(s);
-    comm->have_last = false;
-  }
-  return RGPU_OK;
-}
-static int32_t sharded_merge(rgpu_comm* comm, int32_t n_queries, int32_t k, void* hits_dev, void* totals_dev, hipStream_t s, const ShardedCall& call) {
-  int32_t rc = merge_records(comm->ctx, call.sl->recv.p, comm->n_ranks, n_queries, k, (HitOut*)hits_dev, (int64_t*)totals_dev, s);
-  if (rc != RGPU_OK) return rc;
-  if (!call.sl->done) HIP_TRY(hipEventCreateWithFlags(&call.sl->done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(call.sl->done, s));
-  call.sl->busy = true;
-  comm->last_slot = call.sl;
-  comm->last_queries = n_queries;
-  comm->last_k = k;
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_search_batch_sharded(rgpu_comm* comm, rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries,
-                                             const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, void* hits_dev,
-                                             void* totals_dev, void* hip_stream) {
-  if (!comm || !seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !hits_dev || !totals_dev)
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (seg->ctx != comm->ctx) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "segment and communicator belong to different contexts");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
-  rgpu_ctx* c = comm->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  ShardedCall call;
-  int32_t rc = sharded_reserve(comm, n_queries, k, s, &call);
-  if (rc != RGPU_OK) return rc;
-  sharded_local(comm, seg, queries, n_queries, terms, n_terms_total, k, s, &call);
-  rc = sharded_gather(comm, s, call);
-  if (rc != RGPU_OK) return rc;
-  rc = sharded_merge(comm, n_queries, k, hits_dev, totals_dev, s, call);
-  if (rc != RGPU_OK) return rc;
-  // the collective has been honoured; now this rank's own failure, if any, is reported (its peers see it in the status words)
-  if (call.local_rc != RGPU_OK) return fail(call.local_rc, call.local_why);
-  if (call.pre_rc != RGPU_OK) return fail(call.pre_rc, call.pre_why);
-  return RGPU_OK;
-}
-
-// Start-up sizing: every slot's gather buffer for batches of up to n_queries x k, allocated now — the data path then never
-// allocates, and the one failure that would leave a rank out of a collective (no buffer to gather into) cannot happen there.
-// Not a collective; every rank calls it with the shapes it will serve.
-extern "C" int32_t rgpu_comm_reserve(rgpu_comm* comm, int32_t n_queries, int32_t k) {
-  if (!comm || n_queries <= 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
-  rgpu_ctx* c = comm->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t bytes = record_bytes(n_queries, k) * (size_t)comm->n_ranks;
-  for (auto& sl : comm->slots) {
-    if (sl.busy) { HIP_TRY(hipEventSynchronize(sl.done)); sl.busy = false; }
-    const uint8_t* before = sl.recv.p;
-    HIP_TRY(sl.recv.reserve(bytes, 0, c->stream));
-    if (sl.recv.p != before) sl.status_zero = false;
-    if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-  }
-  if (!comm->last_collective) HIP_TRY(hipEventCreateWithFlags(&comm->last_collective, hipEventDisableTiming));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return RGPU_OK;
-}
-
-// ncclAllGather calls this communicator has enqueued so far (a communicator of one rank issues none unless
-// rgpu_config.comm_force_gather is set): tests and bench.py assert that the collective really ran.
-extern "C" int64_t rgpu_comm_gathers_issued(rgpu_comm* comm) {
-  if (!comm) return -1;
-  std::lock_guard<std::mutex> g(comm->ctx->mu);
-  return comm->gathers_issued;
-}
-
-// The one-process form: rank r = comms[r] / segs[r] (from rgpu_comm_init_all), one thread issues the whole batch. The n
-// all-gathers sit in one NCCL group (issued one by one from one thread the first would wait for peers that this very
-// thread has not reached yet).
-extern "C" int32_t rgpu_search_batch_sharded_all(rgpu_comm* const* comms, rgpu_segment* const* segs, int32_t n, const rgpu_query* queries,
-                                                 int32_t n_queries, const rgpu_query_term* const* terms_per_rank, int32_t n_terms_total,
-                                                 int32_t k, void* const* hits_dev, void* const* totals_dev, void* const* hip_streams) {
-  if (!comms || !segs || n < 1 || !queries || n_queries <= 0 || !terms_per_rank || n_terms_total <= 0 || !hits_dev || !totals_dev)
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
-  for (int32_t r = 0; r < n; ++r) {
-    if (!comms[r] || !segs[r] || !terms_per_rank[r] || !hits_dev[r] || !totals_dev[r]) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null per-rank argument");
-    if (segs[r]->ctx != comms[r]->ctx || comms[r]->rank != r || comms[r]->n_ranks != n)
-      return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "comms[r] / segs[r] must be rank r of an n-rank rgpu_comm_init_all group");
-  }
-  std::vector<ShardedCall> calls((size_t)n);
-  std::vector<hipStream_t> ss((size_t)n);
-  for (int32_t r = 0; r < n; ++r) {  // phase 0 for every rank: a failure here returns before ANY rank has moved on
-    rgpu_ctx* c = comms[r]->ctx;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    ss[(size_t)r] = (hip_streams && hip_streams[r]) ? (hipStream_t)hip_streams[r] : c->stream;
-    int32_t rc = sharded_reserve(comms[r], n_queries, k, ss[(size_t)r], &calls[(size_t)r]);
-    if (rc != RGPU_OK) return rc;
-  }
-  // From here to ncclGroupEnd nothing returns: every rank advances its slot, searches (a failing shard leaves its status in
-  // its record) and issues its all-gather — a rank left out would leave the others hanging in theirs.
-  int32_t first_rc = RGPU_OK;
-  std::string first_why;
-  auto note = [&](int32_t rc, const std::string& why) { if (rc != RGPU_OK && first_rc == RGPU_OK) { first_rc = rc; first_why = why; } };
-  for (int32_t r = 0; r < n; ++r) {  // every shard's search is enqueued before any collective: the GPUs work side by side
-    rgpu_ctx* c = comms[r]->ctx;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (hipSetDevice(c->device) != hipSuccess) {  // the search cannot run: an empty record with a status would need the device too
-      comms[r]->next = (comms[r]->next + 1) % N_COMM_SLOTS;
-      calls[(size_t)r].local_rc = RGPU_ERR_RUNTIME;
-      calls[(size_t)r].local_why = "hipSetDevice";
-      continue;
-    }
-    sharded_local(comms[r], segs[r], queries, n_queries, terms_per_rank[r], n_terms_total, k, ss[(size_t)r], &calls[(size_t)r], true);
-  }
-  // (round 5: every shard's kernels are enqueued by now — disjunctions included, whose groups used to end in a stream sync and so
-  // ran shard after shard; only here does the thread wait, shard by shard, for flags that are back by then as a rule)
-  for (int32_t r = 0; r < n; ++r) {
-    rgpu_ctx* c = comms[r]->ctx;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (hipSetDevice(c->device) != hipSuccess) continue;
-    sharded_settle(comms[r], n_queries, k, ss[(size_t)r], &calls[(size_t)r]);
-  }
-  {
-    const ncclResult_t gs = ncclGroupStart();
-    if (gs != ncclSuccess) note(RGPU_ERR_RUNTIME, std::string("ncclGroupStart: ") + ncclGetErrorString(gs));
-    for (int32_t r = 0; r < n; ++r) {
-      rgpu_ctx* c = comms[r]->ctx;
-      std::lock_guard<std::mutex> g(c->mu);
-      if (hipSetDevice(c->device) != hipSuccess) { note(RGPU_ERR_RUNTIME, "hipSetDevice"); continue; }
-      const int32_t rc = sharded_gather(comms[r], ss[(size_t)r], calls[(size_t)r]);
-      if (rc != RGPU_OK) note(rc, "rank " + std::to_string(r) + ": " + g_last_error);
-    }
-    const ncclResult_t ge = ncclGroupEnd();
-    if (ge != ncclSuccess) note(RGPU_ERR_RUNTIME, std::string("ncclGroupEnd: ") + ncclGetErrorString(ge));
-  }
-  if (first_rc != RGPU_OK) return fail(first_rc, first_why);  // a collective that could not be issued: rgpu_comm_destroy / a new communicator
-  for (int32_t r = 0; r < n; ++r) {
-    rgpu_ctx* c = comms[r]->ctx;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (hipSetDevice(c->device) != hipSuccess) { note(RGPU_ERR_RUNTIME, "hipSetDevice"); continue; }
-    const int32_t rc = sharded_merge(comms[r], n_queries, k, hits_dev[r], totals_dev[r], ss[(size_t)r], calls[(size_t)r]);
-    if (rc != RGPU_OK) note(rc, "rank " + std::to_string(r) + ": " + g_last_error);
-    if (calls[(size_t)r].local_rc != RGPU_OK) note(calls[(size_t)r].local_rc, "rank " + std::to_string(r) + ": " + calls[(size_t)r].local_why);
-    if (calls[(size_t)r].pre_rc != RGPU_OK) note(calls[(size_t)r].pre_rc, "rank " + std::to_string(r) + ": " + calls[(size_t)r].pre_why);
-  }
-  if (first_rc != RGPU_OK) return fail(first_rc, first_why);
-  return RGPU_OK;
-}
-
-// Every rank's status word of the most recent sharded batch on this communicator (waits for that batch): 0, or the
-// rgpu_status its local search failed with — the merged rows then lack that shard's hits.
-extern "C" int32_t rgpu_comm_status(rgpu_comm* comm, int32_t* status_out) {
-  if (!comm || !status_out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
-  rgpu_ctx* c = comm->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  for (int r = 0; r < comm->n_ranks; ++r) status_out[r] = RGPU_OK;
-  if (!comm->last_slot) return RGPU_OK;
-  if (comm->last_slot->busy) { HIP_TRY(hipEventSynchronize(comm->last_slot->done)); comm->last_slot->busy = false; }
-  const size_t record = record_bytes(comm->last_queries, comm->last_k);
-  for (int r = 0; r < comm->n_ranks; ++r) {
-    int64_t v = 0;
-    HIP_TRY(hipMemcpy(&v, comm->last_slot->recv.p + (size_t)r * record + record - 8, 8, hipMemcpyDeviceToHost));
-    status_out[r] = (int32_t)v;
-  }
-  return RGPU_OK;
-}
-
-// ---- host helpers: BM25Similarity (no GPU involved) ------------------------------------------------------------
-#include "host/bm25_similarity.hpp"
-
-extern "C" int32_t rgpu_bm25_compute_weight(float k1, float b, int64_t max_doc, int64_t doc_count, int64_t sum_total_term_freq,
-                                            const int64_t* doc_freqs, int32_t n_terms, float boost, float* weight_out,
-                                            float* idf_out, float* cache_out) {
-  if (!doc_freqs || n_terms <= 0 || n_terms > 64) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  rucene::CollectionStatistics cs;
-  cs.max_doc = max_doc;
-  cs.doc_count = doc_count;
-  cs.sum_total_term_freq = sum_total_term_freq;
-  rucene::TermStatistics ts[64];
-  for (int i = 0; i < n_terms; ++i) ts[i].doc_freq = doc_freqs[i];
-  rucene::BM25SimWeight w = rucene::BM25Similarity(k1, b).compute_weight(cs, ts, (size_t)n_terms, boost);
-  if (weight_out) *weight_out = w.weight;
-  if (idf_out) *idf_out = w.idf;
-  if (cache_out) std::memcpy(cache_out, w.cache.data(), 256 * sizeof(float));
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_bm25_term_weights(int64_t max_doc, int64_t doc_count, const int64_t* doc_freqs, int64_t n, float boost,
-                                          float* weights_out) {
-  if (!doc_freqs || !weights_out || n < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  rucene::CollectionStatistics cs;
-  cs.max_doc = max_doc;
-  cs.doc_count = doc_count;
-  for (int64_t i = 0; i < n; ++i) {
-    rucene::TermStatistics ts;
-    ts.doc_freq = doc_freqs[i];
-    weights_out[i] = rucene::BM25Similarity::idf(&ts, 1, cs) * boost;  // BM25SimWeight::weight = idf * boost
-  }
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_norms_from_lucene53(const uint8_t* nvm, size_t nvm_len, const uint8_t* nvd, size_t nvd_len,
-                                            int32_t field_number, int32_t max_doc, uint8_t* norms_out) {
-  std::string why;
-  const int rc = rucene::read_lucene53_norms(nvm, nvm_len, nvd, nvd_len, field_number, max_doc, norms_out, &why);
-  return rc == 0 ? RGPU_OK : fail(rc, why);
-}
-
-extern "C" int32_t rgpu_live_docs_from_lucene50(const uint8_t* liv, size_t liv_len, int32_t max_doc, int32_t del_count,
-                                                uint64_t* words_out) {
-  std::string why;
-  const int rc = rucene::read_lucene50_live_docs(liv, liv_len, max_doc, del_count, words_out, &why);
-  return rc == 0 ? RGPU_OK : fail(rc, why);
-}
-
-// ---- term dictionary (host) --------------------------------------------------------------------------------------------
-struct rgpu_terms {
-  std::unique_ptr<rucene::TermDictionary> dict;
-};
-static_assert(sizeof(rucene::TermState) == sizeof(rgpu_term_state) && offsetof(rucene::TermState, doc_freq) == offsetof(rgpu_term_state, doc_freq) &&
-                  offsetof(rucene::TermState, skip_offset) == offsetof(rgpu_term_state, skip_offset),
-              "rucene::TermState must mirror rgpu_term_state");
-static_assert(sizeof(rucene::TermFieldStats) == sizeof(rgpu_field_stats), "rucene::TermFieldStats must mirror rgpu_field_stats");
-
-extern "C" int32_t rgpu_terms_open(const uint8_t* tim, size_t tim_len, const uint8_t* tip, size_t tip_len, const rgpu_field_info* infos,
-                                   int32_t n_infos, int32_t max_doc, rgpu_terms** out_terms) {
-  if (!out_terms) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "out_terms is null");
-  *out_terms = nullptr;
-  if (n_infos < 0 || (n_infos > 0 && !infos)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad field infos");
-  std::vector<rucene::TermFieldInfo> fi((size_t)n_infos);
-  for (int32_t i = 0; i < n_infos; ++i) fi[i] = rucene::TermFieldInfo{infos[i].number, infos[i].index_options, infos[i].has_payloads};  // .flags is informational
-  std::string why;
-  auto h = std::make_unique<rgpu_terms>();
-  int rc;
-  try {
-    rc = rucene::TermDictionary::open(tim, tim_len, tip, tip_len, fi.data(), n_infos, max_doc, &h->dict, &why);
-  } catch (const std::bad_alloc&) {
-    return fail(RGPU_ERR_RUNTIME, "out of host memory while building the term dictionary");
-  }
-  if (rc != 0) return fail(rc, why);
-  *out_terms = h.release();
-  return RGPU_OK;
-}
-
-extern "C" void rgpu_terms_close(rgpu_terms* terms) { delete terms; }
-
-extern "C" int32_t rgpu_segment_info_from_lucene62(const uint8_t* si, size_t si_len, const uint8_t* expected_id16_or_null, rgpu_segment_info* out) {
-  if (!out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "out is null");
-  rucene::SegmentInfoEntry e;
-  std::string why;
-  const int rc = rucene::read_lucene62_segment_info(si, si_len, expected_id16_or_null, &e, &why);
-  if (rc != 0) return fail(rc, why);
-  *out = rgpu_segment_info{};
-  out->max_doc = e.max_doc;
-  out->is_compound_file = e.is_compound_file ? 1 : 0;
-  for (int i = 0; i < 3; ++i) out->version[i] = e.version[i];
-  out->n_files = e.n_files;
-  out->n_sort_fields = e.n_sort_fields;
-  std::memcpy(out->id, e.id, 16);
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_commit_from_segments_file(const uint8_t* data, size_t len, int64_t generation, rgpu_commit_segment* out, int32_t cap) {
-  std::vector<rucene::CommitSegmentEntry> segs;
-  std::string why;
-  const int rc = rucene::read_segments_file(data, len, generation, &segs, &why);
-  if (rc != 0) return fail(rc, why);
-  for (size_t i = 0; i < segs.size() && out && (int64_t)i < cap; ++i) {
-    const rucene::CommitSegmentEntry& s = segs[i];
-    if (s.name.size() >= sizeof(out[i].name) || s.codec.size() >= sizeof(out[i].codec)) return fail(RGPU_ERR_UNSUPPORTED, "segment or codec name too long");
-    out[i] = rgpu_commit_segment{};
-    std::memcpy(out[i].name, s.name.c_str(), s.name.size());
-    std::memcpy(out[i].codec, s.codec.c_str(), s.codec.size());
-    std::memcpy(out[i].id, s.id, 16);
-    out[i].del_gen = s.del_gen;
-    out[i].field_infos_gen = s.field_infos_gen;
-    out[i].dv_gen = s.dv_gen;
-    out[i].del_count = s.del_count;
-  }
-  return (int32_t)segs.size();
-}
-
-extern "C" int32_t rgpu_compound_entries_from_lucene50(const uint8_t* cfe, size_t cfe_len, const uint8_t* cfs_or_null, size_t cfs_len,
-                                                       const uint8_t* expected_id16_or_null, rgpu_compound_entry* out, int32_t cap) {
-  std::vector<rucene::CompoundEntry> entries;
-  std::string why;
-  const int rc = rucene::read_lucene50_compound_entries(cfe, cfe_len, cfs_or_null, cfs_len, expected_id16_or_null, &entries, &why);
-  if (rc != 0) return fail(rc, why);
-  for (size_t i = 0; i < entries.size() && out && (int64_t)i < cap; ++i) {
-    if (entries[i].id.size() >= sizeof(out[i].id)) return fail(RGPU_ERR_UNSUPPORTED, "compound entry name too long");
-    out[i] = rgpu_compound_entry{};
-    std::memcpy(out[i].id, entries[i].id.c_str(), entries[i].id.size());
-    out[i].offset = entries[i].offset;
-    out[i].length = entries[i].length;
-  }
-  return (int32_t)entries.size();
-}
-
-extern "C" int32_t rgpu_field_infos_from_lucene60(const uint8_t* fnm, size_t fnm_len, rgpu_field_info* infos_out, int32_t cap, char* names_out,
-                                                  size_t names_cap, size_t* names_len_out) {
-  std::vector<rucene::FieldInfoEntry> infos;
-  std::string why;
-  const int rc = rucene::read_lucene60_field_infos(fnm, fnm_len, &infos, &why);
-  if (rc != 0) return fail(rc, why);
-  size_t names_len = 0;
-  for (size_t i = 0; i < infos.size(); ++i) {
-    const rucene::FieldInfoEntry& fi = infos[i];
-    if (infos_out && (int64_t)i < cap)
-      infos_out[i] = rgpu_field_info{fi.number, fi.index_options, fi.store_payloads ? 1 : 0,
-                                     (fi.omit_norms ? 1 : 0) | (fi.store_term_vector ? 2 : 0) | (fi.doc_values_type << 8)};
-    if (names_out && names_len + fi.name.size() + 1 <= names_cap) std::memcpy(names_out + names_len, fi.name.c_str(), fi.name.size() + 1);
-    names_len += fi.name.size() + 1;
-  }
-  if (names_len_out) *names_len_out = names_len;
-  return (int32_t)infos.size();
-}
-
-extern "C" int32_t rgpu_terms_field_stats(const rgpu_terms* terms, int32_t field_number, rgpu_field_stats* out) {
-  if (!terms || !out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
-  const rucene::TermFieldStats* st = terms->dict->field_stats(field_number);
-  if (!st) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "no such indexed field in this segment");
-  std::memcpy(out, st, sizeof(*out));
-  return RGPU_OK;
-}
-
-static int32_t terms_lookup_impl(const rgpu_terms* terms, int32_t field_number, const uint8_t* term_bytes, const int64_t* term_offsets,
-                                 int32_t n_terms, rgpu_term_state* states_out, rgpu_term_positions* positions_out, uint8_t* found_out) {
-  if (!terms || n_terms < 0 || (n_terms > 0 && (!term_offsets || !states_out))) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
-  for (int32_t i = 0; i < n_terms; ++i)
-    if (term_offsets[i] < 0 || term_offsets[i + 1] < term_offsets[i]) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "term_offsets must be non-decreasing");
-  static const uint8_t kEmpty = 0;
-  if (n_terms > 0 && term_offsets[n_terms] > term_offsets[0] && !term_bytes) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "term_bytes is null");
-  static_assert(sizeof(rucene::TermState) == sizeof(rgpu_term_state), "layout");
-  static_assert(sizeof(rucene::TermPositions) == sizeof(rgpu_term_positions), "layout");
-  terms->dict->lookup_batch(field_number, term_bytes ? term_bytes : &kEmpty, term_offsets, n_terms,
-                            reinterpret_cast<rucene::TermState*>(states_out), found_out,
-                            reinterpret_cast<rucene::TermPositions*>(positions_out));
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_terms_lookup(const rgpu_terms* terms, int32_t field_number, const uint8_t* term_bytes, const int64_t* term_offsets,
-                                     int32_t n_terms, rgpu_term_state* states_out, uint8_t* found_out) {
-  return terms_lookup_impl(terms, field_number, term_bytes, term_offsets, n_terms, states_out, nullptr, found_out);
-}
-
-extern "C" int32_t rgpu_terms_lookup_positions(const rgpu_terms* terms, int32_t field_number, const uint8_t* term_bytes,
-                                               const int64_t* term_offsets, int32_t n_terms, rgpu_term_state* states_out,
-                                               rgpu_term_positions* positions_out, uint8_t* found_out) {
-  if (n_terms > 0 && !positions_out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "positions_out is null");
-  return terms_lookup_impl(terms, field_number, term_bytes, term_offsets, n_terms, states_out, positions_out, found_out);
-}
-
-// ---- batch planner (host) -----------------------------------------------------------------------------------------------
-#include "host/batch_planner.hpp"
-struct rgpu_planner {
-  std::unique_ptr<rucene::BatchPlanner> p;
-};
-static int32_t planner_sim_table(rgpu_ctx* c, const rgpu_plan_stats* ps, int32_t* table_out) {
-  if (!ps) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
-  if (!(ps->k1 >= 0.0f) || !(ps->b >= 0.0f && ps->b <= 1.0f)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "illegal k1 / b value");  // BM25Similarity::new
-  if (!c) { *table_out = -1; return RGPU_OK; }  // the host uploads the field's norm cache itself: rgpu_planner_set_sim_table
-  rucene::CollectionStatistics cs;
-  cs.max_doc = ps->max_doc;
-  cs.doc_count = ps->doc_count;
-  cs.sum_total_term_freq = ps->sum_total_term_freq;
-  rucene::TermStatistics ts;
-  const rucene::BM25SimWeight w = rucene::BM25Similarity(ps->k1, ps->b).compute_weight(cs, &ts, 1, 1.0f);  // the cache depends on the collection alone
-  const int32_t t = rgpu_sim_table_upload(c, w.cache.data(), ps->k1);
-  if (t < 0) return t;
-  *table_out = t;
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_planner_create_flat(rgpu_ctx* c, const rgpu_plan_stats* ps, const rgpu_term_state* leaf_states, int64_t n_leaf,
-                                            const rgpu_term_state* stats_states_or_null, int64_t n_stats, rgpu_planner** out) {
-  if (!out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "out is null");
-  *out = nullptr;
-  if (n_leaf < 0 || (n_leaf > 0 && !leaf_states) || n_stats < 0 || (n_stats > 0 && !stats_states_or_null)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad term tables");
-  int32_t table = -1;
-  const int32_t rc = planner_sim_table(c, ps, &table);
-  if (rc != RGPU_OK) return rc;
-  try {
-    auto h = std::make_unique<rgpu_planner>();
-    h->p.reset(new rucene::BatchPlanner(*ps, table, leaf_states, n_leaf, stats_states_or_null, n_stats));
-    *out = h.release();
-  } catch (const std::bad_alloc&) { return fail(RGPU_ERR_RUNTIME, "out of host memory"); }
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_planner_create(rgpu_ctx* c, const rgpu_plan_stats* ps, const rgpu_terms* leaf_terms, const rgpu_terms* stats_terms_or_null,
-                                       int32_t field_number, rgpu_planner** out) {
-  if (!out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "out is null");
-  *out = nullptr;
-  if (!leaf_terms) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "leaf_terms is null");
-  if (!leaf_terms->dict->field_stats(field_number)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "no such indexed field in this segment");
-  int32_t table = -1;
-  const int32_t rc = planner_sim_table(c, ps, &table);
-  if (rc != RGPU_OK) return rc;
-  auto h = std::make_unique<rgpu_planner>();
-  h->p.reset(new rucene::BatchPlanner(*ps, table, leaf_terms->dict.get(), stats_terms_or_null ? stats_terms_or_null->dict.get() : nullptr, field_number));
-  *out = h.release();
-  return RGPU_OK;
-}
-
-extern "C" void rgpu_planner_destroy(rgpu_planner* p) { delete p; }
-extern "C" int32_t rgpu_planner_sim_table(const rgpu_planner* p) { return p ? p->p->sim_table() : RGPU_ERR_ILLEGAL_ARGUMENT; }
-extern "C" int32_t rgpu_planner_set_sim_table(rgpu_planner* p, int32_t sim_table) {
-  if (!p || sim_table < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  p->p->set_sim_table(sim_table);
-  return RGPU_OK;
-}
-
-static int32_t plan_checked(rgpu_planner* p, int32_t n_queries, const int32_t* ops, const int32_t* n_terms, const int32_t* n_must_not,
-                            const int64_t* ids, const uint8_t* bytes, const int64_t* offsets, const float* boosts, rgpu_query* queries_out,
-                            rgpu_query_term* terms_out, int64_t terms_cap) {
-  if (!p || n_queries <= 0 || !ops || !n_terms || !queries_out || !terms_out || terms_cap < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  std::string why;
-  const int rc = p->p->plan(n_queries, ops, n_terms, n_must_not, ids, bytes, offsets, boosts, queries_out, terms_out, terms_cap, &why);
-  return rc == RGPU_OK ? RGPU_OK : fail(rc, why);
-}
-
-extern "C" int32_t rgpu_plan_batch_ids(rgpu_planner* p, int32_t n_queries, const int32_t* ops, const int32_t* n_terms, const int32_t* n_must_not_or_null,
-                                       const int64_t* term_ids, const float* boosts_or_null, rgpu_query* queries_out, rgpu_query_term* terms_out,
-                                       int64_t terms_cap) {
-  if (!term_ids) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "term_ids is null");
-  return plan_checked(p, n_queries, ops, n_terms, n_must_not_or_null, term_ids, nullptr, nullptr, boosts_or_null, queries_out, terms_out, terms_cap);
-}
-
-extern "C" int32_t rgpu_plan_batch_bytes(rgpu_planner* p, int32_t n_queries, const int32_t* ops, const int32_t* n_terms, const int32_t* n_must_not_or_null,
-                                         const uint8_t* term_bytes, const int64_t* term_offsets, const float* boosts_or_null, rgpu_query* queries_out,
-                                         rgpu_query_term* terms_out, int64_t terms_cap) {
-  if (!term_offsets) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "term_offsets is null");
-  static const uint8_t kEmpty = 0;
-  return plan_checked(p, n_queries, ops, n_terms, n_must_not_or_null, nullptr, term_bytes ? term_bytes : &kEmpty, term_offsets, boosts_or_null, queries_out,
-                      terms_out, terms_cap);
-}
-
-// every query the same shape: `op` (RGPU_OP_TERM / AND / OR, OR optionally RGPU_OP_OR_MSM) over n_clauses terms, boost 1
-static int32_t plan_uniform(rgpu_planner* p, int32_t op, int32_t n_queries, int32_t n_clauses, const int64_t* ids, const uint8_t* bytes,
-                            const int64_t* offsets, rgpu_query* queries_out, rgpu_query_term* terms_out) {
-  if (n_queries <= 0 || n_clauses <= 0 || n_clauses > RGPU_MAX_QUERY_TERMS) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad batch shape");
-  if ((op >> 16) != 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a uniform batch has no optional clauses");
-  thread_local std::vector<int32_t> ops, counts;
-  ops.assign((size_t)n_queries, op);
-  counts.assign((size_t)n_queries, n_clauses);
-  return plan_checked(p, n_queries, ops.data(), counts.data(), nullptr, ids, bytes, offsets, nullptr, queries_out, terms_out,
-                      (int64_t)n_queries * n_clauses);
-}
-extern "C" int32_t rgpu_plan_uniform_ids(rgpu_planner* p, int32_t op, int32_t n_queries, int32_t n_clauses, const int64_t* term_ids,
-                                         rgpu_query* queries_out, rgpu_query_term* terms_out) {
-  if (!term_ids) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "term_ids is null");
-  return plan_uniform(p, op, n_queries, n_clauses, term_ids, nullptr, nullptr, queries_out, terms_out);
-}
-extern "C" int32_t rgpu_plan_uniform_bytes(rgpu_planner* p, int32_t op, int32_t n_queries, int32_t n_clauses, const uint8_t* term_bytes,
-                                           const int64_t* term_offsets, rgpu_query* queries_out, rgpu_query_term* terms_out) {
-  if (!term_offsets) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "term_offsets is null");
-  static const uint8_t kEmpty = 0;
-  return plan_uniform(p, op, n_queries, n_clauses, nullptr, term_bytes ? term_bytes : &kEmpty, term_offsets, queries_out, terms_out);
-}
-
-// ---- plan + search in ONE call ------------------------------------------------------------------------------------------------
-// A serving host's steady state is "a batch of term ids arrives -> rows": rgpu_plan_uniform_ids writes rgpu_query[] /
-// rgpu_query_term[] (40 B a clause), rgpu_search_batch_device reads them back, validates them as foreign input, looks every
-// clause's prepared structures up, sorts the queries into groups and only then builds the device descriptors — 63 us of one
-// host thread per 1024-query TERM batch against 47 us of GPU time (round 5). The fused form keeps the ids inside the library:
-// for single-term batches the planner's per-clause result (term state, idf) and the prepared-term table entry go straight
-// into the staged DevQuery / DevTerm arrays — one pass, no intermediate arrays, nothing to validate (the planner's own
-// tables are trusted; an id outside them is an absent term) — and the zeroed per-query counters travel with the same staged
-// copy (three enqueues per batch: copy, k_search_term, k_merge_items). Anything the fast pass does not handle — another op,
-// a term that is not prepared yet or lacks its block-max sketch, k > 128, a prepared-term budget, a dictionary planner — goes
-// through plan() + search_impl() inside the same call: same rows either way (tests/test_gpu_parity.py).
-// RGPU_HOST_TIME=1 in the environment: where the calling thread's time goes inside term_batch_fast, averaged over 256 calls (stderr)
-struct HostLaps {
-  static constexpr int N = 7;
-  long long ns[N] = {0, 0, 0, 0, 0, 0, 0};
-  int calls = 0;
-  std::chrono::steady_clock::time_point last;
-  void start() { last = std::chrono::steady_clock::now(); }
-  void lap(int i) { const auto t = std::chrono::steady_clock::now(); ns[i] += std::chrono::duration_cast<std::chrono::nanoseconds>(t - last).count(); last = t; }
-  void done() {
-    if (++calls < 256) return;
-    std::fprintf(stderr, "[term_batch_fast host, us per call] slot + stage room %.2f | term states -> descriptors %.2f | items %.2f | item descriptors + zeroes %.2f | "
-                         "stage copy enqueue %.2f | reserve + kernel enqueue %.2f | status + mark %.2f\n",
-                 ns[0] / 256e3, ns[1] / 256e3, ns[2] / 256e3, ns[3] / 256e3, ns[4] / 256e3, ns[5] / 256e3, ns[6] / 256e3);
-    *this = HostLaps{};
-  }
-};
-// what term_batch_resident's memo pass needs of a DevTerm besides its arena index: the digest of the planner's hot entry
-// (host/batch_planner.hpp for_each_flat_memo_hot). bucket: clz(nblocks), 32 for a list without FullBlocks
-struct TermHot { int32_t df, nblocks, bucket; };
-// The fused single-term step with the term descriptors RESIDENT on the device (the default; RGPU_TERM_PLAN=staged: the staged plan
-// below). What a step sends is 8 bytes per query — TermLaunch{record, row} in launch order, which k_search_term_query reads straight
-// from the pinned stage — and nothing is copied: no stage kernel, no DevQuery / DevTerm / order / qmap arrays. The descriptors live in
-// the context's arena (host/term_arena.hpp has the ownership rules), written once each:
-//   * a memo miss appends the record to the current generation and to this call's stage; the call then runs k_stage_term_plan — the
-//     stage copy, with the arena as its destination — on ITS stream ahead of its search kernel, and records an event behind it;
-//   * a call on another stream that names records of an upload not known complete makes its stream wait for that event
-//     (hipStreamWaitEvent) before its search kernel. Uploads become known complete when a slot marked behind them on their stream
-//     is waited for, which scratch_take does anyway: a steady state makes no event call for the arena;
-//   * nothing in a generation is ever overwritten, and a generation's buffer is handed back only when no busy scratch slot carries
-//     its number — so a launch in flight on either stream reads what its plan named, whatever the memo does meanwhile.
-// *staged: the call is not for this path after all (more distinct terms than the arena holds): the caller stages the plan.
-template <class Make>
-static int32_t term_batch_resident(rgpu_segment* seg, rucene::BatchPlanner* P, int32_t nq, const int64_t* ids, int32_t k, HitOut* hits_dev,
-                                   int64_t* totals_dev, hipStream_t stream, const rucene::BatchPlanner::MemoKey& memo_key, Make& make_term,
-                                   HostLaps* laps, bool* taken, bool* staged) {
-  rgpu_ctx* c = seg->ctx;
-  rucene::TermArena& A = c->arena;
-  *staged = false;
-  if (A.begin(rucene::TermArena::Key{{memo_key.w[0], memo_key.w[1], memo_key.w[2], memo_key.w[3]}})) HIP_TRY(arena_new_buffer(c));
-  Stager st(c);
-  const size_t o_l = st.add((size_t)nq * sizeof(TermLaunch));
-  const size_t o_up = st.add((size_t)nq * sizeof(DevTerm));  // records this call places (at most one per query)
-  HIP_TRY(c->S->h_stage.reserve(st.used));
-  HIP_TRY(c->S->d_stage.reserve((size_t)nq * 16, 0, stream));  // the launch's counters: the kernel stores every one of them
-  if (laps) laps->lap(0);
-  TermLaunch* hl = reinterpret_cast<TermLaunch*>(c->S->h_stage.p + o_l);
-  DevTerm* hup = reinterpret_cast<DevTerm*>(c->S->h_stage.p + o_up);
-  static thread_local std::vector<int32_t> recs;
-  static thread_local std::vector<uint8_t> buckets;
-  recs.resize((size_t)nq);
-  buckets.resize((size_t)nq);
-  int64_t postings = 0, total_blocks = 0, loose = 0;
-  int32_t start[34];
-  int32_t n_up = 0;
-  int64_t first_up = -1;
-  uint32_t lo = 0xffffffffu, hi = 0u;
-  // records placed by a pass whose upload is never enqueued (a term the fast pass does not take, a failed call) must not be named by
-  // a later call: the generation ends with them
-  struct Unplace {
-    rucene::TermArena& A;
-    const int32_t& n_up;
-    bool armed = true;
-    ~Unplace() { if (armed && n_up > 0) A.turn_over(); }
-  } unplace{A, n_up};
-  for (int attempt = 0;; ++attempt) {
-    postings = total_blocks = loose = 0;
-    std::memset(start, 0, sizeof start);
-    n_up = 0;
-    first_up = -1;
-    lo = 0xffffffffu;
-    hi = 0u;
-    bool full = false;
-    auto place = [&](const DevTerm* t) -> int64_t {
-      const int64_t at = A.append();
-      if (at < 0) { full = true; return -1; }
-      if (first_up < 0) first_up = at;  // (appends of one pass are consecutive: the context's lock is held)
-      hup[n_up++] = *t;
-      return at;
-    };
-    // the memo pass counts the launch order's buckets (0: the longest lists; floor(log2(nblocks))) on the way. What it needs of a term —
-    // its record's index, df, nblocks, the bucket — comes from the planner's hot entry (one cache line per query; RGPU_TERM_HOT=0: from
-    // the memo's record, as before)
-    const bool ok = c->term_hot ? P->for_each_flat_memo_hot<DevTerm, TermHot>(ids, nq, memo_key, A.generation(), make_term, place, [](const DevTerm& t) {
-      return TermHot{t.df, t.nblocks, t.nblocks > 0 ? __builtin_clz((uint32_t)t.nblocks) : 32};
-    }, [&](int64_t q, int32_t rec, const TermHot& t) {
-      int b = 32;
-      if (rec >= 0) {
-        postings += t.df;
-        total_blocks += t.nblocks;
-        loose += t.df == 1 ? 1 : t.df % 128;  // (make_term's tail_n)
-        b = t.bucket;
-        lo = std::min(lo, (uint32_t)rec);
-        hi = std::max(hi, (uint32_t)rec);
-      }
-      recs[(size_t)q] = rec;
-      buckets[(size_t)q] = (uint8_t)b;
-      ++start[b + 1];
-    }) : P->for_each_flat_memo_placed<DevTerm>(ids, nq, memo_key, A.generation(), make_term, place, [&](int64_t q, const DevTerm* t, int32_t rec) {
-      int b = 32;
-      if (t) {
-        postings += t->df;
-        total_blocks += t->nblocks;
-        loose += t->df == 1 ? 1 : t->tail_n;
-        if (t->nblocks > 0) b = __builtin_clz((uint32_t)t->nblocks);
-        lo = std::min(lo, (uint32_t)rec);
-        hi = std::max(hi, (uint32_t)rec);
-      }
-      recs[(size_t)q] = rec;
-      buckets[(size_t)q] = (uint8_t)b;
-      ++start[b + 1];
-    });
-    if (ok) break;
-    if (!full) return RGPU_OK;  // (the full path takes the call; the slot was taken and not marked: it is simply free again)
-    // the generation is full: a fresh one, and the pass again (every entry misses). A batch that does not fit an empty arena is staged.
-    n_up = 0;
-    A.turn_over();
-    if (attempt == 1) { *staged = true; return RGPU_OK; }
-    HIP_TRY(arena_new_buffer(c));
-  }
-  if (laps) laps->lap(1);
-  for (int b = 0; b < 33; ++b) start[b + 1] += start[b];
-  for (int q = 0; q < nq; ++q) hl[start[buckets[(size_t)q]]++] = TermLaunch{recs[(size_t)q], q};
-  if (laps) { laps->lap(2); laps->lap(3); }
-  const DevTerm* d_arena = static_cast<const DevTerm*>(A.buffer());
-  if (n_up > 0) {
-    {
-      // k_stage_term_plan's second job: the new records, from the stage to their place in the arena (no zero range, no item descriptors)
-      TimedLaunch tl(c, stream, "k_stage_term_plan", 0);
-      const size_t n16 = (size_t)n_up * (sizeof(DevTerm) / 16);
-      const TermPlanLayout L{0u, 0u, 0u, 0u, 0u, 0u, 0};
-      const unsigned grid = (unsigned)std::min<size_t>(1024, (n16 + 255) / 256);
-      RGPU_LAUNCH(k_stage_term_plan, dim3(grid), dim3(256), 0, stream, c->S->h_stage.p + o_up,
-                  reinterpret_cast<uint8_t*>(const_cast<DevTerm*>(d_arena + first_up)), n16, L);
-    }
-    HIP_TRY(launch_status());
-    void* ev = A.take_spare_event();
-    if (!ev) {
-      hipEvent_t e = nullptr;
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      ev = e;
-    }
-    const hipError_t er = hipEventRecord((hipEvent_t)ev, stream);
-    if (er != hipSuccess) { A.give_spare_event(ev); HIP_TRY(er); }
-    A.note_upload((uint32_t)first_up, (uint32_t)(first_up + n_up), (uint64_t)(uintptr_t)stream, ev);
-  }
-  unplace.armed = false;  // (what this pass placed is on its way)
-  if (A.pending_uploads() != 0 && lo <= hi) {
-    hipError_t ew = hipSuccess;
-    A.for_each_wait((uint64_t)(uintptr_t)stream, lo, hi, [&](void* ev) {
-      const hipError_t e = hipStreamWaitEvent(stream, (hipEvent_t)ev, 0);
-      if (ew == hipSuccess) ew = e;
-    });
-    HIP_TRY(ew);
-  }
-  if (laps) laps->lap(4);
-  unsigned long long* d_work = reinterpret_cast<unsigned long long*>(c->S->d_stage.p);
-  c->last_counted = c->S;
-  c->last_counted_words = d_work;
-  c->last_counted_op = RGPU_OP_TERM;
-  c->last_counted_queries = nq;
-  c->last_counted_postings = postings;
-  c->last_counted_dir_blocks = total_blocks;
-  c->last_counted_loose = loose;
-  const bool wide = k > 64;
-  const bool legacy = seg->version < 1;
-  // the slot's mark travels with the step's only launch: `done` is the kernel's stop event, and no hipEventRecord follows it
-  const bool bound = c->term_slot_event_bound;
-  if (bound && !c->S->done) HIP_TRY(hipEventCreateWithFlags(&c->S->done, hipEventDisableTiming));
-  {
-    TimedLaunch tl(c, stream, stat_slot_once(c, &c->stat_k_search_term, "k_search_term"), postings);  // (under the TERM search's name, like the staged plan's launch below)
-    const SegView sv = seg_view(seg);
-    auto go = [&](auto kern, int waves) -> hipError_t {
-      // (hipExtLaunchKernelGGL passes the arguments as they are typed here: each one has its parameter's type exactly)
-      if (bound) RGPU_LAUNCH_WITH_STOP(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, c->S->done, sv, (const DevQuery*)nullptr, d_arena, (const int32_t*)nullptr,
-                                       (int)nq, (int)k, d_work, (const int32_t*)nullptr, hits_dev, totals_dev, (int32_t)seg->doc_base, (const TermLaunch*)hl,
-                                       (int)c->term_short_blocks);
-      else RGPU_LAUNCH(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, sv, (const DevQuery*)nullptr, d_arena, (const int32_t*)nullptr, nq, (int)k, d_work,
-                       (const int32_t*)nullptr, hits_dev, totals_dev, seg->doc_base, (const TermLaunch*)hl, c->term_short_blocks);
-      return hipSuccess;
-    };
-    auto pick = [&](auto legacy_c, auto wide_c) -> hipError_t {
-      constexpr bool LG = decltype(legacy_c)::value, WD = decltype(wide_c)::value;
-      if (c->term_query_waves == 2) return go(k_search_term_query<LG, WD, 2>, 2);
-      if (c->term_query_waves == 8) return go(k_search_term_query<LG, WD, 8>, 8);
-      return go(k_search_term_query<LG, WD, 4>, 4);
-    };
-    hipError_t e;
-    if (legacy) e = wide ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{});
-    else e = wide ? pick(std::false_type{}, std::true_type{}) : pick(std::false_type{}, std::false_type{});
-    HIP_TRY(e);
-    c->stats[(size_t)stat_slot_once(c, &c->stat_term_query_launches, "term_query_launches")].launches += 1;
-  }
-  if (laps) laps->lap(5);
-  HIP_TRY(launch_status());  // (a refused launch: the slot stays unmarked, `busy` false)
-  if (bound) c->S->busy = true;
-  else HIP_TRY(scratch_mark(c, stream));
-  A.slot_marked((int)(c->S - c->scr), (uint64_t)(uintptr_t)stream);
-  c->stats[(size_t)stat_slot_once(c, &c->stat_fused_term_batches, "fused_term_batches")].launches += 1;
-  if (laps) { laps->lap(6); laps->done(); }
-  *taken = true;
-  return RGPU_OK;
-}
-static int32_t term_batch_fast(rgpu_segment* seg, rucene::BatchPlanner* P, int32_t nq, const int64_t* ids, int32_t k, HitOut* hits_dev,
-                               int64_t* totals_dev, hipStream_t stream, bool* taken) {
-  rgpu_ctx* c = seg->ctx;
-  *taken = false;
-  static thread_local HostLaps laps;
-  const bool timed = c->host_time;
-  if (timed) laps.start();
-  const int32_t sim_table = P->sim_table();
-  if (!P->flat() || k > RGPU_PASS_K || c->prepared_budget != 0 || sim_table < 0 || sim_table >= c->n_sim_tables || seg->dir_used == 0) return RGPU_OK;
-  const bool want_sketch = c->term_sketches && seg->d_norms && seg->n_norm_ranks > 0 && !live_words(seg);
-  const bool need_norms = seg->d_norms != nullptr;
-  const uint32_t flags = c->sim_monotone[(size_t)sim_table] ? TERM_FLAG_MONOTONE : 0u;
-  c->pass = rgpu_ctx::Pass{};
-  SCRATCH_TAKE(c);
-  const int32_t max_doc = seg->max_doc;
-  const bool has_freqs = seg->has_freqs;
-  // term id -> finished descriptor through the planner's memo (host/batch_planner.hpp for_each_flat_memo): a descriptor is a function
-  // of the planner's tables (immutable), the segment and what its prepared store holds (uid, epoch), and the flags below
-  const rucene::BatchPlanner::MemoKey memo_key{{seg->uid, seg->prepared.epoch, (uint64_t)(uint32_t)sim_table | ((uint64_t)flags << 32),
-                                                (uint64_t)want_sketch | ((uint64_t)need_norms << 1) | ((uint64_t)has_freqs << 2) | ((uint64_t)(uint32_t)max_doc << 8)}};
-  auto make_term = [&](const rgpu_term_state& s0, float idf, DevTerm* out) -> int32_t {
-    DevTerm t;
-    t.start_fp = (uint64_t)std::max<int64_t>(0, s0.doc_start_fp);
-    t.pn_base = 0;
-    t.bs_base = 0;
-    t.dir_base = 0;
-    t.nblocks = 0;
-    t.df = s0.doc_freq;
-    t.tail_n = s0.doc_freq > 1 ? s0.doc_freq % 128 : 0;
-    t.singleton_doc = s0.singleton_doc_id;
-    t.singleton_freq = has_freqs ? (int32_t)s0.total_term_freq : 1;
-    t.weight = idf;
-    t.sim_table = sim_table;
-    t.flags = flags;
-    t.sketch = 0;
-    if (s0.doc_freq == 1) {
-      if (s0.singleton_doc_id < 0 || s0.singleton_doc_id >= max_doc) return -1;  // (the full path names the error)
-    } else {
-      const TermInfo* info = seg->prepared.find(s0.doc_start_fp);
-      if (!info || info->df != s0.doc_freq || (need_norms && !info->norms) ||
-          (want_sketch && info->sketch == 0 && info->nblocks >= TERM_SKETCH_MIN_BLOCKS)) return -1;  // (the full path prepares it: another epoch)
-      t.dir_base = info->dir_base;
-      t.nblocks = info->nblocks;
-      t.pn_base = info->pn_base;
-      t.bs_base = info->bs_base;
-      t.sketch = info->sketch;
-    }
-    *out = t;
-    return 1;
-  };
-  // k_search_term_query: one workgroup per query, no work items
-  const bool per_query = c->term_query_kernel && c->blocks_per_item_auto && c->term_fold;
-  if (per_query && c->term_plan_resident && c->stage_by_kernel && !c->upload_aside) {
-    bool staged_after_all = false;
-    const int32_t rc = term_batch_resident(seg, P, nq, ids, k, hits_dev, totals_dev, stream, memo_key, make_term, timed ? &laps : nullptr, taken, &staged_after_all);
-    if (!staged_after_all) return rc;
-  }
-  Stager st(c);
-  const size_t o_q = st.add((size_t)nq * sizeof(DevQuery));
-  const size_t o_t = st.add((size_t)nq * sizeof(DevTerm));
-  const size_t o_p = st.add((size_t)(nq + 1) * 8);
-  const size_t o_m = st.add((size_t)nq * 4);
-  const size_t o_sh = st.add((size_t)nq);            // log2 of every query's own item size (0: the launch's)
-  const size_t o_ord = st.add((size_t)nq * 4);       // k_search_term_query: the query of every workgroup, heaviest first
-  const size_t o_tau = st.add((size_t)nq * 8);       // per-query shared thresholds ...
-  const size_t o_w = st.add((size_t)nq * 16);        // ... and the launch's counters: zeroed by the copy that brings the plan
-  const size_t o_done = st.add((size_t)nq * 4);      // ... and the per-query counts of finished items (TermMerge::done)
-  const size_t o_zero_end = st.add(0);               // (the three above are one range: [o_tau, o_zero_end))
-  // ... and the item descriptors, LAST: their number is known only once the terms have been read (at most 262144 + nq, the item
-  // loop's cap), the stage has room for the worst case and the copy takes what is used
-  const size_t o_id = st.add(((size_t)262144 + (size_t)nq) * sizeof(int4));
-  HIP_TRY(c->S->h_stage.reserve(st.used));
-  HIP_TRY(c->S->d_stage.reserve(st.used, 0, stream));
-  if (timed) laps.lap(0);
-  DevQuery* hq = reinterpret_cast<DevQuery*>(c->S->h_stage.p + o_q);
-  DevTerm* ht = reinterpret_cast<DevTerm*>(c->S->h_stage.p + o_t);
-  int64_t* hp = reinterpret_cast<int64_t*>(c->S->h_stage.p + o_p);
-  int32_t* hm = reinterpret_cast<int32_t*>(c->S->h_stage.p + o_m);
-  int32_t nt = 0;
-  int64_t postings = 0, total_blocks = 0, loose = 0;
-  bool bail = false;
-  bail = !P->for_each_flat_memo<DevTerm>(ids, nq, memo_key, make_term, [&](int64_t q, const DevTerm* t) {
-    hm[q] = (int32_t)q;
-    if (!t) { hq[q] = DevQuery{RGPU_OP_TERM, 0, nt, 0}; return; }  // TermWeight::create_scorer -> None for this leaf
-    hq[q] = DevQuery{RGPU_OP_TERM, 1, nt, 0};
-    ht[nt++] = *t;
-    postings += t->df;
-    total_blocks += t->nblocks;
-    loose += t->df == 1 ? 1 : t->tail_n;
-  });
-  if (bail) return RGPU_OK;  // (the slot was taken and not marked: it is simply free again)
-  if (timed) laps.lap(1);
-  // k_search_term_query — the plan is the queries, their terms and a launch order, longest lists first (a counting sort on
-  // floor(log2(nblocks)))
-  if (per_query) {
-    int32_t* ho = reinterpret_cast<int32_t*>(c->S->h_stage.p + o_ord);
-    int32_t start[34] = {0};
-    auto bucket = [&](int q) -> int {  // 0: the longest lists
-      const int32_t nb = hq[q].n_terms >= 1 ? ht[hq[q].first_term].nblocks : 0;
-      return nb <= 0 ? 32 : __builtin_clz((uint32_t)nb);
-    };
-    for (int q = 0; q < nq; ++q) ++start[bucket(q) + 1];
-    for (int b = 0; b < 33; ++b) start[b + 1] += start[b];
-    for (int q = 0; q < nq; ++q) ho[start[bucket(q)]++] = q;
-  }
-  // items: chunks of a term's blocks; every query's first chunk is scheduled first (search_pass's rule, to the letter)
-  int blocks_per_item = c->cfg.blocks_per_item;
-  int term_split = 1;
-  if (c->blocks_per_item_auto) {
-    blocks_per_item = term_item_blocks(total_blocks, c->term_target_items);
-    term_split = c->term_split;
-  }
-  int64_t items = 0;
-  uint8_t* hsh = c->S->h_stage.p + o_sh;
-  while (!per_query) {
-    items = 0;
-    const int base_sh = term_item_shift(blocks_per_item);  // 0: not a power of two (a caller's own size) — no per-query sizes then
-    const int floor_sh = std::max(1, term_item_shift(c->term_min_item_blocks));
-    for (int q = 0; q < nq; ++q) {
-      hp[q] = items;
-      hsh[q] = 0;
-      if (hq[q].n_terms >= 1) {
-        const int32_t nb = ht[hq[q].first_term].nblocks;
-        if (base_sh > 0) {  // term_query_item_blocks in shifts: halve while the query has fewer than `split` items
-          int sh = base_sh;
-          if (term_split > 1) while (sh > floor_sh && ((nb + (1 << sh) - 1) >> sh) < term_split) --sh;
-          hsh[q] = (uint8_t)sh;
-          items += (nb == 0 ? 1 : (nb + (1 << sh) - 1) >> sh) - 1;
-        } else {
-          items += (nb == 0 ? 1 : (nb + blocks_per_item - 1) / blocks_per_item) - 1;
-        }
-      }
-    }
-    hp[nq] = items;
-    if (items <= 262144 || blocks_per_item >= (1 << 17)) break;
-    blocks_per_item *= 2;
-  }
-  if (!per_query) items += nq;
-  if (timed) laps.lap(2);
-  if (items > 262144 + (int64_t)nq) return RGPU_OK;  // (blocks_per_item hit its ceiling on an absurd batch: the full path takes it)
-  const bool plan_on_device = c->stage_by_kernel && !c->upload_aside && o_id + (size_t)items * sizeof(int4) <= 0xffffffffull;
-  if (plan_on_device) {
-    // zeroes and item descriptors are the copy kernel's work (k_stage_term_plan)
-    if (timed) laps.lap(3);
-    const size_t n16 = (o_id + 15) / 16;  // (o_id is 256-aligned: everything in front of the descriptors)
-    const TermPlanLayout L{(uint32_t)o_q, (uint32_t)o_p, (uint32_t)o_sh, (uint32_t)o_id, (uint32_t)o_tau, (uint32_t)o_zero_end, per_query ? 0 : nq};
-    TimedLaunch tl(c, stream, "k_stage_term_plan", 0);
-    const unsigned grid = (unsigned)std::min<size_t>(1024, std::max<size_t>((n16 + 255) / 256, per_query ? 0 : ((size_t)nq + 255) / 256));
-    RGPU_LAUNCH(k_stage_term_plan, dim3(grid), dim3(256), 0, stream, c->S->h_stage.p, c->S->d_stage.p, n16, L);
-  } else {
-    std::memset(c->S->h_stage.p + o_tau, 0, o_zero_end - o_tau);
-    int4* hd = reinterpret_cast<int4*>(c->S->h_stage.p + o_id);
-    for (int q = 0; q < (per_query ? 0 : nq); ++q) {  // fill_term_item_desc with the sizes the item loop chose
-      const int n_mine = 1 + (int)(hp[q + 1] - hp[q]);
-      const int ft = hq[q].n_terms >= 1 ? hq[q].first_term : -1;
-      const int w = n_mine | ((int)hsh[q] << 24);
-      hd[q] = make_int4(q, 0, ft, w);
-      int4* rest = hd + nq + hp[q];
-      for (int ch = 1; ch < n_mine; ++ch) rest[ch - 1] = make_int4(q, ch, ft, w);
-    }
-    const size_t staged = o_id + (size_t)items * sizeof(int4);
-    if (timed) laps.lap(3);
-    HIP_TRY(stage_h2d(c, staged, stream));
-  }
-  if (timed) laps.lap(4);
-  if (!per_query) {
-    HIP_TRY(c->S->d_partial_keys.reserve((size_t)items * (size_t)k, 0, stream));
-    HIP_TRY(c->S->d_partial_counts.reserve((size_t)items, 0, stream));
-  }
-  unsigned long long* d_tau = reinterpret_cast<unsigned long long*>(c->S->d_stage.p + o_tau);
-  unsigned long long* d_work = reinterpret_cast<unsigned long long*>(c->S->d_stage.p + o_w);
-  const DevQuery* dq = reinterpret_cast<const DevQuery*>(c->S->d_stage.p + o_q);
-  const DevTerm* dt = reinterpret_cast<const DevTerm*>(c->S->d_stage.p + o_t);
-  const int64_t* dp = reinterpret_cast<const int64_t*>(c->S->d_stage.p + o_p);
-  const int32_t* dm = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_m);
-  c->last_counted = c->S;
-  c->last_counted_words = d_work;
-  c->last_counted_op = RGPU_OP_TERM;
-  c->last_counted_queries = nq;
-  c->last_counted_postings = postings;
-  c->last_counted_dir_blocks = total_blocks;
-  c->last_counted_loose = loose;
-  const bool wide = k > 64;
-  const bool legacy = seg->version < 1;
-  // the fold of every query's item lists happens inside k_search_term (TermMerge), unless RGPU_TERM_FOLD=0 asks for k_merge_items
-  const TermMerge fold = c->term_fold ? TermMerge{reinterpret_cast<unsigned int*>(c->S->d_stage.p + o_done), dp, hits_dev, totals_dev, nullptr, seg->doc_base, 0, 0}
-                                      : TermMerge{};
-  if (per_query) {
-    // (timed under the TERM search's name: what reads the stats — bench.py's roofline among them — asks for "k_search_term"; the
-    // term_query_launches stat below tells the two kernels apart)
-    TimedLaunch tl(c, stream, "k_search_term", postings);
-    const SegView sv = seg_view(seg);
-    const int32_t* dord = reinterpret_cast<const int32_t*>(c->S->d_stage.p + o_ord);
-    auto go = [&](auto kern, int waves) -> hipError_t {
-      RGPU_LAUNCH(kern, dim3((unsigned)nq), dim3(64 * waves), 0, stream, sv, dq, dt, dord, nq, (int)k, d_work, dm, hits_dev, totals_dev, seg->doc_base,
-                  (const TermLaunch*)nullptr, c->term_short_blocks);
-      return hipSuccess;
-    };
-    auto pick = [&](auto legacy_c, auto wide_c) -> hipError_t {
-      constexpr bool LG = decltype(legacy_c)::value, WD = decltype(wide_c)::value;
-      if (c->term_query_waves == 2) return go(k_search_term_query<LG, WD, 2>, 2);
-      if (c->term_query_waves == 8) return go(k_search_term_query<LG, WD, 8>, 8);
-      return go(k_search_term_query<LG, WD, 4>, 4);
-    };
-    hipError_t e;
-    if (legacy) e = wide ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{});
-    else e = wide ? pick(std::false_type{}, std::true_type{}) : pick(std::false_type{}, std::false_type{});
-    HIP_TRY(e);
-    c->stats[(size_t)stat_slot(c, "term_query_launches")].launches += 1;
-  } else {
-    TimedLaunch tl(c, stream, "k_search_term", postings);
-    const unsigned grid = wg_count((items + TERM_WAVES - 1) / TERM_WAVES);
-    const size_t lds = term_lds_bytes(wide);
-    const SegView sv = seg_view(seg);
-    auto go = [&](auto kern) -> hipError_t {
-      hipError_t e = set_dynamic_lds_once(c, reinterpret_cast<const void*>(kern), lds);
-      if (e != hipSuccess) return e;
-      RGPU_LAUNCH(kern, dim3(grid), dim3(TERM_THREADS), lds, stream, sv, dq, dt, reinterpret_cast<const int4*>(c->S->d_stage.p + o_id), nq, items,
-                         blocks_per_item, (int)k, c->S->d_partial_keys.p, c->S->d_partial_counts.p, d_tau, d_work, (const unsigned long long*)nullptr, dm, fold);
-      return hipSuccess;
-    };
-    hipError_t e;
-    if (legacy) e = wide ? go(k_search_term<true, true>) : go(k_search_term<true, false>);
-    else e = wide ? go(k_search_term<false, true>) : go(k_search_term<false, false>);
-    HIP_TRY(e);
-  }
-  if (!per_query && !c->term_fold) {
-    if (wide) launch_merge<true>(c, stream, nq, k, dp, seg->doc_base, hits_dev, totals_dev, nq, nullptr, nullptr, dm);
-    else launch_merge<false>(c, stream, nq, k, dp, seg->doc_base, hits_dev, totals_dev, nq, nullptr, nullptr, dm);
-  }
-  if (timed) laps.lap(5);
-  HIP_TRY(launch_status());
-  HIP_TRY(scratch_mark(c, stream));
-  c->stats[(size_t)stat_slot(c, "fused_term_batches")].launches += 1;  // (tests ask whether this path ran: rgpu_kernel_stats)
-  if (timed) { laps.lap(6); laps.done(); }
-  *taken = true;
-  return RGPU_OK;
-}
-
-// context mutex held by the caller; c->defer_or as the caller set it
-static int32_t search_uniform_locked(rgpu_segment* seg, const UniformBatch& ub, int32_t n_queries, int32_t k, HitOut* hits_dev, int64_t* totals_dev,
-                                     hipStream_t stream) {
-  const int32_t op = ub.op & 0xff;
-  // BooleanQuery::build: a lone clause IS that clause (boolean_query.rs:56-68) — as plan() rewrites it
-  if (ub.n_clauses == 1 && (ub.op >> 8) == 0 && op >= RGPU_OP_TERM && op <= RGPU_OP_OR) {
-    bool taken = false;
-    const int32_t rc = term_batch_fast(seg, ub.planner->p.get(), n_queries, ub.ids, k, hits_dev, totals_dev, stream, &taken);
-    if (rc != RGPU_OK || taken) return rc;
-  }
-  thread_local std::vector<rgpu_query> queries;
-  thread_local std::vector<rgpu_query_term> terms;
-  queries.resize((size_t)n_queries);
-  terms.resize((size_t)n_queries * (size_t)ub.n_clauses);
-  const int32_t rc = plan_uniform(ub.planner, ub.op, n_queries, ub.n_clauses, ub.ids, nullptr, nullptr, queries.data(), terms.data());
-  if (rc != RGPU_OK) return rc;
-  return search_impl(seg, queries.data(), n_queries, terms.data(), (int32_t)terms.size(), k, hits_dev, totals_dev, stream);
-}
-
-static int32_t uniform_args_ok(rgpu_planner* p, rgpu_segment* seg, int32_t op, int32_t n_queries, int32_t n_clauses, const int64_t* ids, int32_t k,
-                               const void* hits_dev, const void* totals_dev) {
-  if (!p || !seg || !ids || !hits_dev || !totals_dev) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
-  if (n_queries <= 0 || n_clauses <= 0 || n_clauses > RGPU_MAX_QUERY_TERMS || (int64_t)n_queries * n_clauses > 0x7fffffff) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad batch shape");
-  if ((op & 0xff) == RGPU_OP_DISMAX) return fail(RGPU_ERR_UNSUPPORTED, "the planner does not plan RGPU_OP_DISMAX: pack rgpu_query / rgpu_query_term and call rgpu_search_batch*");
-  if ((op >> 16) != 0 || (op & 0xff) < RGPU_OP_TERM || (op & 0xff) > RGPU_OP_OR || ((op & 0xff) == RGPU_OP_TERM && n_clauses != 1))
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a uniform batch is TERM (one clause), AND or OR (optionally RGPU_OP_OR_MSM)");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
-  if (!p->p->flat()) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "this planner names terms by their bytes (rgpu_planner_create): plan with rgpu_plan_uniform_bytes, then rgpu_search_batch_device");
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_planner_search_uniform_ids_device(rgpu_planner* p, rgpu_segment* seg, int32_t op, int32_t n_queries, int32_t n_clauses,
-                                                          const int64_t* term_ids, int32_t k, void* hits_dev, void* totals_dev, void* hip_stream) {
-  const int32_t ok = uniform_args_ok(p, seg, op, n_queries, n_clauses, term_ids, k, hits_dev, totals_dev);
-  if (ok != RGPU_OK) return ok;
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  const UniformBatch ub{p, op, n_clauses, term_ids};
-  c->defer_or = c->cfg.or_deferred != 0;
-  const int32_t rc = search_uniform_locked(seg, ub, n_queries, k, (HitOut*)hits_dev, (int64_t*)totals_dev, s);
-  c->defer_or = false;
-  return rc;
-}
-
-// ... and its sharded form: rgpu_search_batch_sharded with the batch named by ids (local plan + search -> all-gather -> merge)
-extern "C" int32_t rgpu_planner_search_uniform_ids_sharded(rgpu_comm* comm, rgpu_planner* p, rgpu_segment* seg, int32_t op, int32_t n_queries,
-                                                           int32_t n_clauses, const int64_t* term_ids, int32_t k, void* hits_dev, void* totals_dev,
-                                                           void* hip_stream) {
-  if (!comm) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
-  const int32_t ok = uniform_args_ok(p, seg, op, n_queries, n_clauses, term_ids, k, hits_dev, totals_dev);
-  if (ok != RGPU_OK) return ok;
-  if (seg->ctx != comm->ctx) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "segment and communicator belong to different contexts");
-  rgpu_ctx* c = comm->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  const UniformBatch ub{p, op, n_clauses, term_ids};
-  ShardedCall call;
-  int32_t rc = sharded_reserve(comm, n_queries, k, s, &call);
-  if (rc != RGPU_OK) return rc;
-  sharded_local(comm, seg, nullptr, n_queries, nullptr, 0, k, s, &call, false, &ub);
-  rc = sharded_gather(comm, s, call);
-  if (rc != RGPU_OK) return rc;
-  rc = sharded_merge(comm, n_queries, k, hits_dev, totals_dev, s, call);
-  if (rc != RGPU_OK) return rc;
-  if (call.local_rc != RGPU_OK) return fail(call.local_rc, call.local_why);
-  if (call.pre_rc != RGPU_OK) return fail(call.pre_rc, call.pre_why);
-  return RGPU_OK;
-}
-
-extern "C" uint8_t rgpu_bm25_encode_norm(float boost, int32_t field_length) {
-  return rucene::BM25Similarity::encode_norm_value(boost, field_length);
-}
-
-#ifdef RGPU_ORX_TIME
-extern "C" int32_t rgpu_debug_counters(unsigned long long* out8, int32_t reset) {  // k_or_wide wave-cycles per phase (search_or_wide.hpp)
-  if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_orx_dbg), 64) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_orx_dbg), z, 64) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
-#ifdef RGPU_LZ_TIME
-extern "C" int32_t rgpu_debug_counters(unsigned long long* out8, int32_t reset) {  // k_or_lazy wave-cycles per phase (search_or_lazy.hpp)
-  if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_lz_dbg), 64) != hipSuccess) return -1;
-  unsigned long long more[8];
-  if (hipMemcpyFromSymbol(more, HIP_SYMBOL(g_lz_dbg), 64, 64) != hipSuccess) return -1;
-  std::fprintf(stderr, "[lz steps] lazy-only test on in %llu of %llu steps; a doc in enough lists in %llu; bound iterations %llu; mean need %.2f, need_hi %.2f\n", more[0], more[3],
-               more[1], more[2], more[0] ? (double)more[4] / (double)more[0] : 0.0, more[0] ? (double)more[5] / (double)more[0] : 0.0);
-  if (reset) {
-    unsigned long long z[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_lz_dbg), z, 128) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
-#ifdef RGPU_AND_TIME
-extern "C" int32_t rgpu_debug_counters(unsigned long long* out8, int32_t reset) {  // k_search_and wave-cycles per phase (search_and.hpp)
-  unsigned long long all[16];
-  if (hipMemcpyFromSymbol(all, HIP_SYMBOL(g_and_time), 128) != hipSuccess) return -1;
-  std::memcpy(out8, all, 64);
-  std::fprintf(stderr, "[and time] cycles: set-up %llu, first probe %llu, loop(queued) %llu, loop(block by block) %llu, epilogue %llu | items %llu, pops %llu, block vectors %llu, "
-               "queued survivors %llu, walked decodes: after a pop %llu, block by block %llu\n", all[0], all[1], all[2], all[3], all[4], all[5], all[6], all[7], all[8], all[9], all[10]);
-  if (reset) {
-    unsigned long long z[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_and_time), z, 128) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
-#ifdef RGPU_TERM_TRACE
-extern "C" int32_t rgpu_debug_trace(void* out, int32_t n) {  // the most recent k_search_term launch's item timeline
-  if (n > TERM_TRACE_CAP) n = TERM_TRACE_CAP;
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_term_trace), (size_t)n * sizeof(TermTraceRec)) == hipSuccess ? n : -1;
-}
-#endif
-#ifdef RGPU_AND_TRACE
-// the most recent k_search_and launch's item timeline: n records of {t0, t1 (100 MHz wall clock), q, chunk, lead blocks, survivors popped}
-extern "C" int32_t rgpu_debug_trace(void* out, int32_t n) {
-  if (n > AND_TRACE_CAP) n = AND_TRACE_CAP;
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_and_trace), (size_t)n * sizeof(AndTraceRec)) == hipSuccess ? n : -1;
-}
-#endif
-#ifdef RGPU_EXP_COUNT
-extern "C" int32_t rgpu_debug_counters(unsigned long long* out8, int32_t reset) {  // [0..3] TERM, [4..7] AND
-  if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_term_dbg), 32) != hipSuccess) return -1;
-  if (hipMemcpyFromSymbol(out8 + 4, HIP_SYMBOL(g_and_dbg), 32) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[4] = {0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_term_dbg), z, 32) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(g_and_dbg), z, 32) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
+// ---- the tail of this translation unit, cut by concern ------------------------------------------------------------------
+// The first step of splitting this file: what followed here stands in the parts below, moved verbatim. A part is not a header of
+// its own: it relies on everything above and on the parts in front of it (each says on what), so the order is part of the program.
+// Each part is included once, here and nowhere else (tests/test_api_parts.py); nothing else is defined from here on.
+#include "api/sharded.hpp"       // rgpu_comm_*, records, rgpu_search_batch_record_device, rgpu_merge_records_device, rgpu_search_batch_sharded*
+#include "api/host_formats.hpp"  // rgpu_bm25_*, norms, live docs, rgpu_terms_*, segment / commit / compound / field infos
+#include "api/planner.hpp"       // rgpu_planner_create* / destroy / sim_table, rgpu_plan_batch_*, rgpu_plan_uniform_*
+#include "api/fused.hpp"         // term_batch_resident, term_batch_fast, search_uniform_locked, rgpu_planner_search_uniform_ids_device / _sharded
+#include "api/debug.hpp"         // rgpu_bm25_encode_norm; rgpu_debug_counters / rgpu_debug_trace of the variant builds

@@ -1,4 +1,4 @@
-// csrc/host/batch_planner.hpp for_each_flat_memo_hot (the 32-byte hot entries in front of the planner's memo; rgpu_api.hip
+// csrc/host/batch_planner.hpp for_each_flat_memo_hot (the 32-byte hot entries in front of the planner's memo; csrc/api/fused.hpp
 // term_batch_resident) against for_each_flat_memo_placed on a second planner over the same table, and against for_each_flat: for every
 // id the same held / absent verdict, the same record behind the returned index, the same digest — over a hot set asked again and again,
 // ids that share a hot slot, ids that share a memo slot, ids outside the table and absent terms, new arena generations, new keys,

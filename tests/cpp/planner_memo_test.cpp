@@ -1,4 +1,4 @@
-// csrc/host/batch_planner.hpp for_each_flat_memo (term id -> the caller's finished record, rgpu_api.hip term_batch_fast) against
+// csrc/host/batch_planner.hpp for_each_flat_memo (term id -> the caller's finished record, csrc/api/fused.hpp term_batch_fast) against
 // for_each_flat: the same (state, idf) reach `make` as for_each_flat hands out, once per id per key; ids that share a slot evict each
 // other and stay right; absent ids and ids outside the table arrive as null; a refusal keeps nothing and stops at once; another key
 // empties the table. And csrc/host/prepared_map.hpp: `epoch` moves with every change of a term's TermInfo, not with look-ups.

@@ -1,4 +1,4 @@
-"""The fused single-term call with its term descriptors resident on the device (`-m gpu`; rgpu_api.hip term_batch_resident,
+"""The fused single-term call with its term descriptors resident on the device (`-m gpu`; csrc/api/fused.hpp term_batch_resident,
 host/term_arena.hpp): a steady state launches no stage kernel; memo entries that evict each other, first touches on the other stream,
 a released prepared store and an arena that turns over every few calls — all with launches in flight on two streams — return the
 oracle's rows, bit for bit; RGPU_TERM_PLAN=staged and RGPU_TERM_KERNEL=items return the same rows and counters.

@@ -1,5 +1,5 @@
 """The fused single-term step reading the planner's hot entries instead of its memo (`-m gpu`; host/batch_planner.hpp
-for_each_flat_memo_hot, rgpu_api.hip term_batch_resident), and the slot's event bound to the search kernel: every row equals the
+for_each_flat_memo_hot, csrc/api/fused.hpp term_batch_resident), and the slot's event bound to the search kernel: every row equals the
 oracle's and the rows of a context opened with RGPU_TERM_HOT=0, bit for bit, and `postings_covered` is the sum of the dfs — for
 duplicate / absent / outside ids, ids that share a hot slot alternating on two streams, an arena that turns over every other call,
 a released prepared store, and 200 enqueue-only calls on two streams under either slot event.

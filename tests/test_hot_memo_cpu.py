@@ -1,5 +1,5 @@
 """csrc/host/batch_planner.hpp for_each_flat_memo_hot, the hot entries in front of the planner's memo that the fused single-term step
-reads (rgpu_api.hip term_batch_resident): tests/cpp/hot_memo_test.cpp, a stand-alone program, built plain and under
+reads (csrc/api/fused.hpp term_batch_resident): tests/cpp/hot_memo_test.cpp, a stand-alone program, built plain and under
 -fsanitize=address,undefined. No GPU, nothing loaded into Python."""
 import os
 import subprocess
