@@ -843,12 +843,40 @@ int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* que
  * rgpu_search_phrase_batch; scores are bit-exact with the CPU scorer. A leaf that lacks a clause's term matches nothing.
  * Refused like rgpu_search_phrase_batch refuses the same faults (clause count, slop < 0, sim_table, k: its codes; position /
  * reserved: RGPU_ERR_ILLEGAL_ARGUMENT); in_order == 0 and a doc holding one clause's term more than 1024 times -> RGPU_ERR_UNSUPPORTED.
- * NOT served (the caller keeps these on its CPU path): unordered near - NearSpansUnordered pops a BinaryHeap whose order among cells
- * at equal (start, end) is the heap array's (span_near.rs:681-696); SpanGapQuery clauses; SpanOrQuery; nested span clauses; a span
+ * NOT served by this call: unordered near - that is rgpu_search_span_unordered_batch (in_order == 0 here stays RGPU_ERR_UNSUPPORTED).
+ * NOT served at all (the caller keeps these on its CPU path): SpanGapQuery clauses; SpanOrQuery; nested span clauses; a span
  * query as a BooleanQuery clause or under a doc-set mask; the planner, rescore and sharded forms. */
 int32_t rgpu_search_span_near_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
                                     const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t in_order, int32_t k,
                                     rgpu_hit* hits_out, int64_t* total_hits_out);
+
+/* One leaf of IndexSearcher::search(SpanNearQuery(in_order = false) over SpanTermQuery clauses, TopDocsCollector(k)): "these
+ * terms within slop positions of each other, in any order".
+ * The reference: NearSpansUnordered (span_near.rs:333-528). On a doc that holds every clause's term the cells 0 .. n - 1, one per
+ * clause in clause order, move to their first position and are pushed on a std BinaryHeap (sub_span_cells_to_positions_queue,
+ * :393-404; push = data.push + sift_up, util/external/binary_heap.rs:131-163 is a copy of that std). Then, repeatedly: at_match
+ * (:406-412) - end(max cell) - start(heap top) - total_span_length <= slop, i.e. with term spans [p, p + 1) (span_term.rs:170-200)
+ * width = start(max cell) - start(heap top) <= slop + n - 1 - yields a span of that width (:512-515); the heap's top cell moves to
+ * its next position through peek_mut, whose drop runs sift_down_range(0, len) (binary_heap.rs:29-35, :167-190); a cell without a
+ * further position ends the doc there (:443-445, :475-480). SpansCellElement::cmp (:681-696) orders by (start, end) only, so among
+ * cells at one start - two clauses naming one term, or distinct terms stacked at one position - the cell that moves first is
+ * whichever the heap ARRAY holds on top, and with distinct stacked terms that changes the spans. The kernels therefore keep the array
+ * and run push, sift_up and sift_down_range operation by operation. adjust_max (:568-577) keeps the running maximum of the ends; the
+ * index it carries over from the previous doc is harmless (TermSpans stand at -1 on a fresh doc, span_term.rs:188-196).
+ * SpanScorer (span.rs:489-519) sums 1 / (width + 1) over the spans in the order they come out, in f32 from 0.0; the score is
+ * BM25(that frequency, norm); a doc is a hit iff it has a span. Transposed terms DO match (a@1, a@3, b@5 at slop 3: widths 4, 2,
+ * in either clause order).
+ * `queries` / `terms`, the checks, next_limit (AT EVERY SLOP: spans are always two-phase, and every approximation counts, deleted
+ * docs included), the weight (idf summed over every clause's term, span.rs:574-602) and the outputs are
+ * rgpu_search_span_near_batch's: terms[i].position must be i and .reserved 0, n_terms = 2..RGPU_MAX_PHRASE_TERMS, slop >= 0. The
+ * segment needs rgpu_segment_attach_positions. Scores are bit-exact with the CPU scorer.
+ * Refused: what rgpu_search_span_near_batch refuses, with its codes; a doc whose clauses' terms hold more than 2048 positions in all
+ * (the sloppy phrases' rule) -> RGPU_ERR_UNSUPPORTED.
+ * NOT served (the caller keeps these on its CPU path): nested span clauses; SpanOrQuery; SpanGapQuery clauses; a span query inside a
+ * boolean, filtered, dismax, boosting or rescoring query; the planner, masked and sharded forms. */
+int32_t rgpu_search_span_unordered_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
+                                         const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
+                                         int64_t* total_hits_out);
 
 /* BooleanQuery with exact PhraseQuery clauses among its required clauses: +"a b" +c -d #e. BooleanWeight::create_scorer
  * (boolean_query.rs:196-279) builds a ConjunctionScorer over must_weights — the MUST weights in query order, then the FILTER weights

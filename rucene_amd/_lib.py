@@ -81,6 +81,7 @@ EXPORTS = [
     "rgpu_docset_head", "rgpu_search_batch_required_set", "rgpu_search_batch_device_required_set",
     "rgpu_search_phrase_batch_masked", "rgpu_search_phrase_bool_batch_masked", "rgpu_search_phrase_or_batch_masked",
     "rgpu_search_span_near_batch",
+    "rgpu_search_span_unordered_batch",
     "rgpu_points_attach", "rgpu_points_get_info", "rgpu_points_free", "rgpu_docset_from_point_ranges",
     "rgpu_plan_uniform_bytes", "rgpu_plan_batch_ids", "rgpu_plan_batch_bytes", "rgpu_planner_search_uniform_ids_device", "rgpu_planner_search_uniform_ids_sharded",
 ]
@@ -174,6 +175,7 @@ def lib():
         "rgpu_decode_positions_device": (i32, [vp, vp, vp, C.c_int64, vp, vp]),
         "rgpu_search_phrase_batch": (i32, [vp, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_span_near_batch": (i32, [vp, vp, i32, vp, i32, i32, i32, vp, vp]),
+        "rgpu_search_span_unordered_batch": (i32, [vp, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_phrase_bool_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_phrase_or_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_rescore_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32]),
@@ -820,13 +822,23 @@ class Segment:
     def search_span_near_batch(self, queries, terms, k, in_order=True):
         """rgpu_search_span_near_batch: ordered SpanNearQuery rows over SpanTermQuery clauses, packed as for search_phrase_batch
         (a row's terms are its clauses in query order, `position` = the clause's index; `slop` = the allowed slop; next_limit applies
-        at every slop). in_order=False is UnsupportedOperation. A refusal raises and returns nothing."""
+        at every slop). in_order=False is UnsupportedOperation here (search_span_unordered_batch serves it). A refusal raises and returns nothing."""
         q = np.ascontiguousarray(queries, dtype=PHRASE_QUERY_DTYPE)
         t = np.ascontiguousarray(terms, dtype=PHRASE_TERM_DTYPE)
         hits = np.zeros((q.size, k), dtype=HIT_DTYPE)
         totals = np.zeros(q.size, dtype=np.int64)
         _check(lib().rgpu_search_span_near_batch(self._h, q.ctypes.data, q.size, t.ctypes.data, t.size, 1 if in_order else 0, k, hits.ctypes.data,
                                                  totals.ctypes.data))
+        return hits, totals
+
+    def search_span_unordered_batch(self, queries, terms, k):
+        """rgpu_search_span_unordered_batch: SpanNearQuery(in_order=False) rows over SpanTermQuery clauses (NearSpansUnordered), packed
+        exactly as for search_span_near_batch. A refusal raises and returns nothing."""
+        q = np.ascontiguousarray(queries, dtype=PHRASE_QUERY_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=PHRASE_TERM_DTYPE)
+        hits = np.zeros((q.size, k), dtype=HIT_DTYPE)
+        totals = np.zeros(q.size, dtype=np.int64)
+        _check(lib().rgpu_search_span_unordered_batch(self._h, q.ctypes.data, q.size, t.ctypes.data, t.size, k, hits.ctypes.data, totals.ctypes.data))
         return hits, totals
 
     def search_phrase_bool_batch(self, queries, phrases, phrase_terms, terms, k):

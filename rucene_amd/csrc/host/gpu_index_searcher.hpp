@@ -362,7 +362,7 @@ struct PhraseQuery : Query {
   }
 };
 
-// SpanTermQuery (query/spans/span_term.rs): the spans [position, position + 1) of one term; served as a clause of an ordered SpanNearQuery.
+// SpanTermQuery (query/spans/span_term.rs): the spans [position, position + 1) of one term; served as a clause of a SpanNearQuery.
 struct SpanTermQuery : Query {
   TermQuery term;
   explicit SpanTermQuery(TermQuery t) : term(std::move(t)) {}
@@ -370,9 +370,12 @@ struct SpanTermQuery : Query {
 // SpanNearQuery::new (query/spans/span_near.rs:101-124): the clauses within `slop` positions of each other, in the clauses' order when
 // in_order. The GPU path serves a top-level query with in_order = true whose clauses are all SpanTermQuery (rgpu_search_span_near_batch):
 // NearSpansOrdered + SpanScorer, next_limit applied at every slop (spans are always two-phase). The weight sums the idf of every clause's
-// term, a term named twice counted twice (build_sim_weight, span.rs:574-602). Unordered near (NearSpansUnordered's heap order among equal
-// cells is the heap array's, span_near.rs:681-696), nested span clauses (add_nested), a span query under a FilteredQuery or in a rescore
-// request are UnsupportedOperation when the query is searched - the caller's CPU path. No boolean query of this mirror can hold one.
+// term, a term named twice counted twice (build_sim_weight, span.rs:574-602). Unordered near (NearSpansUnordered, span_near.rs:333-528: the
+// order among equal cells is its heap's array order, which the kernels keep) is served through rgpu_search_span_unordered_batch by a
+// searcher with GpuIndexSearcher::unordered_spans = true; check_served() keeps refusing it, as it does for every caller that has not
+// opted in, and the searcher routes opted-in rows around it (check_shape). Nested span clauses (add_nested), a span query under a
+// FilteredQuery or in a rescore request are UnsupportedOperation when the query is searched - the caller's CPU path. No boolean query
+// of this mirror can hold one.
 struct SpanNearQuery : Query {
   std::vector<SpanTermQuery> clauses;
   int32_t nested = 0;  // clauses that are themselves SpanNearQuerys (add_nested): kept as a count, the query is refused when searched
@@ -386,6 +389,9 @@ struct SpanNearQuery : Query {
   SpanNearQuery& add_nested(const SpanNearQuery&) { ++nested; return *this; }
   void check_served() const {
     if (!in_order) throw Error(RGPU_ERR_UNSUPPORTED, "an unordered SpanNearQuery is not served by the GPU path");
+    check_shape();
+  }
+  void check_shape() const {  // what is refused whatever the order
     if (nested > 0) throw Error(RGPU_ERR_UNSUPPORTED, "a SpanNearQuery with nested span clauses is not served by the GPU path");
     if (clauses.size() > RGPU_MAX_PHRASE_TERMS) throw Error(RGPU_ERR_UNSUPPORTED, "a SpanNearQuery of more than RGPU_MAX_PHRASE_TERMS clauses is not served by the GPU path");
     if (slop < 0) throw Error(RGPU_ERR_UNSUPPORTED, "a SpanNearQuery with a negative slop is not served by the GPU path");
@@ -856,6 +862,10 @@ class GpuIndexSearcher {
   // rgpu_search_batch_required_set (every doc of live AND sets is collected, the docs no SHOULD clause holds at score 0) instead of
   // being UnsupportedOperation; "b c -X" is then searched masked (FilteredQuery::check_served says what stays refused)
   bool required_sets = false;
+  // A top-level SpanNearQuery(in_order = false) over SpanTermQuery clauses goes through rgpu_search_span_unordered_batch
+  // (NearSpansUnordered, the heap's array order kept) instead of being UnsupportedOperation. Refused either way: nested span clauses,
+  // a span query under a FilteredQuery or in a rescore request.
+  bool unordered_spans = false;
   std::function<void(const Query&, TopDocsCollector&)> cpu_fallback;
 
   // ---- cached filters: doc sets in HBM as FILTER / MUST_NOT masks (include/rucene_gpu.h rgpu_docset_*) ---------------------------
@@ -1054,8 +1064,8 @@ class GpuIndexSearcher {
     for (const Query* q : queries)
       if (dynamic_cast<const PointRangeQuery*>(q)) throw Error(RGPU_ERR_UNSUPPORTED, "a lone point range is not served by the GPU path (the reference matches all of it)");
     for (const Query* q : queries) {  // refused before any leaf is touched
-      if (const SpanNearQuery* near = dynamic_cast<const SpanNearQuery*>(q)) near->check_served();
-      if (dynamic_cast<const SpanTermQuery*>(q)) throw Error(RGPU_ERR_UNSUPPORTED, "a span query is served by the GPU path as a top-level ordered SpanNearQuery only");
+      if (const SpanNearQuery* near = dynamic_cast<const SpanNearQuery*>(q)) check_span(*near);
+      if (dynamic_cast<const SpanTermQuery*>(q)) throw Error(RGPU_ERR_UNSUPPORTED, "a span query is served by the GPU path as a top-level SpanNearQuery only");
     }
     for (const Query* q : queries)
       if (dynamic_cast<const FilteredQuery*>(q) || dynamic_cast<const MatchAllDocsQuery*>(q)) return search_filtered(queries, k);
@@ -1086,10 +1096,14 @@ class GpuIndexSearcher {
       }
       if (!bools.empty()) place(bool_rows, search_phrase_bools(bools, k));
       if (!ors.empty()) place(or_rows, search_phrase_ors(ors, k));
-      if (!span_rows.empty()) {
-        std::vector<const SpanNearQuery*> nears;
-        for (size_t i : span_rows) nears.push_back(static_cast<const SpanNearQuery*>(queries[i]));
-        place(span_rows, search_span_nears(nears, k));
+      if (!span_rows.empty()) {  // ordered rows: rgpu_search_span_near_batch; unordered ones (unordered_spans): rgpu_search_span_unordered_batch
+        for (const bool in_order : {true, false}) {
+          std::vector<size_t> rows;
+          std::vector<const SpanNearQuery*> nears;
+          for (size_t i : span_rows)
+            if (static_cast<const SpanNearQuery*>(queries[i])->in_order == in_order) { rows.push_back(i); nears.push_back(static_cast<const SpanNearQuery*>(queries[i])); }
+          if (!rows.empty()) place(rows, search_span_nears(nears, k, in_order));
+        }
       }
       return out;
     }
@@ -1180,14 +1194,22 @@ class GpuIndexSearcher {
     return merge_leaves(leaf_hits, leaf_totals, nq, k);
   }
 
-  // IndexSearcher::search(SpanNearQuery, TopDocsCollector(k)) for a batch of ordered near queries over SpanTermQuery clauses:
-  // rgpu_search_span_near_batch per leaf, the rows packed as phrases (clause i at position i, `slop` the allowed slop).
-  std::vector<TopDocs> search_span_nears(const std::vector<const SpanNearQuery*>& queries, size_t k) {
+  // a SpanNearQuery row: unordered near passes only on a searcher that opted in (unordered_spans), and then around
+  // SpanNearQuery::check_served, which keeps refusing it
+  void check_span(const SpanNearQuery& near) const {
+    if (!near.in_order && unordered_spans) near.check_shape(); else near.check_served();
+  }
+
+  // IndexSearcher::search(SpanNearQuery, TopDocsCollector(k)) for a batch of near queries over SpanTermQuery clauses, all ordered
+  // (rgpu_search_span_near_batch per leaf) or all unordered (rgpu_search_span_unordered_batch per leaf; unordered_spans). The rows are
+  // packed as phrases either way (clause i at position i, `slop` the allowed slop) and merged over the leaves with their doc bases.
+  std::vector<TopDocs> search_span_nears(const std::vector<const SpanNearQuery*>& queries, size_t k, bool in_order = true) {
     const int32_t nq = static_cast<int32_t>(queries.size());
     std::vector<PhraseQuery> as_phrases;
     std::vector<const PhraseQuery*> rows;
     for (const SpanNearQuery* q : queries) {
-      q->check_served();
+      if (q->in_order != in_order) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "search_span_nears: a batch is all ordered or all unordered");
+      check_span(*q);
       std::vector<TermQuery> terms;
       for (const SpanTermQuery& c : q->clauses) terms.push_back(c.term);
       as_phrases.emplace_back(std::move(terms), std::vector<int32_t>{}, q->boost, q->slop);
@@ -1203,8 +1225,12 @@ class GpuIndexSearcher {
       pack_phrases(rows, leaf, &qs, &ts);
       leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
       leaf_totals[li].assign(static_cast<size_t>(nq), 0);
-      check(rgpu_search_span_near_batch(leaf.segment, qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), 1, static_cast<int32_t>(k),
-                                        leaf_hits[li].data(), leaf_totals[li].data()));
+      if (in_order)
+        check(rgpu_search_span_near_batch(leaf.segment, qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), 1, static_cast<int32_t>(k),
+                                          leaf_hits[li].data(), leaf_totals[li].data()));
+      else
+        check(rgpu_search_span_unordered_batch(leaf.segment, qs.data(), nq, ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
+                                               leaf_hits[li].data(), leaf_totals[li].data()));
     }
     return merge_leaves(leaf_hits, leaf_totals, nq, k);
   }

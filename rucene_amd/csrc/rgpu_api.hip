@@ -37,6 +37,7 @@
 #include "host/term_arena.hpp"
 #include "kernels/search_phrase.hpp"
 #include "kernels/search_span.hpp"
+#include "kernels/search_span_unordered.hpp"
 #include "kernels/search_phrase_bool.hpp"
 #include "host/phrase_bool_plan.hpp"
 #include "kernels/search_phrase_or.hpp"
@@ -4997,6 +4998,9 @@ struct PhraseMatchStage {
   // rgpu_search_span_near_batch: every live query of the call is an ordered SpanNearQuery (d_sl: its true slops) - the span
   // kernels run instead of the phrase kernels (any_exact and any_sloppy are false then)
   bool any_span = false;
+  // rgpu_search_span_unordered_batch: the span queries are unordered (NearSpansUnordered) - kernels/search_span_unordered.hpp runs
+  // in place of kernels/search_span.hpp, on the same ladder. No other caller sets it.
+  bool unordered_span = false;
 };
 static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const PhraseMatchStage& a) {
   rgpu_ctx* c = seg->ctx;
@@ -5073,7 +5077,16 @@ static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const P
       }
     }
   }
-  if (a.any_span) {  // ordered span-near queries: as the exact phrases' ladder, with the span walk (kernels/search_span.hpp)
+  if (a.any_span && a.unordered_span) {  // unordered span-near queries: the sloppy phrases' ladder (one pool), NearSpansUnordered's walk
+    if (legacy) {
+      TimedLaunch tl(c, stream, "k_span_unordered", 0);
+      exact(k_span_unordered<true, SLOPPY_SMALL_POOL, false>, all_slots, a.slots);
+    } else {
+      TimedLaunch tl(c, stream, "k_span_unordered_lanes", 0);
+      RGPU_LAUNCH(k_span_unordered_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl,
+                  (int)a.n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)a.redo_cap, c->d_err + 2);
+    }
+  } else if (a.any_span) {  // ordered span-near queries: as the exact phrases' ladder, with the span walk (kernels/search_span.hpp)
     if (legacy) {
       TimedLaunch tl(c, stream, "k_span_near", 0);
       exact(k_span_near<true, PHRASE_SMALL_CAP, false>, all_slots, a.slots);
@@ -5098,7 +5111,8 @@ static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const P
   const bool by_list = !legacy && (int64_t)listed <= a.redo_cap;
   const int64_t* const left = by_list ? (const int64_t*)c->phrase_redo.p : all_slots;
   const int64_t n_left = by_list ? (int64_t)listed : a.slots;
-  if (HostClock::on() && (redo & (PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES | PHRASE_REDO_SPAN_LANES)))
+  constexpr int REDO_FROM_LANES = PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES | PHRASE_REDO_SPAN_LANES | PHRASE_REDO_SPAN_UNORD_LANES;
+  if (HostClock::on() && (redo & REDO_FROM_LANES))
     std::fprintf(stderr, "[phrase] %d of %lld candidate slots left for the one-candidate kernels\n", listed, (long long)a.slots);
   if (redo & PHRASE_REDO_LANES) {
     TimedLaunch tl(c, stream, "k_phrase_match(left by the 64-candidate kernel)", 0);
@@ -5112,7 +5126,12 @@ static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const P
     TimedLaunch tl(c, stream, "k_span_near(left by the 64-candidate kernel)", 0);
     exact(k_span_near<false, PHRASE_SMALL_CAP, true>, left, n_left);
   }
-  if (redo & (PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES | PHRASE_REDO_SPAN_LANES)) RGPU_TRY(redo_bits());
+  if (redo & PHRASE_REDO_SPAN_UNORD_LANES) {
+    // ("unord": rgpu_kernel_stat.name holds 47 characters)
+    TimedLaunch tl(c, stream, "k_span_unord(left by the 64-candidate kernel)", 0);
+    exact(k_span_unordered<false, SLOPPY_SMALL_POOL, true>, left, n_left);
+  }
+  if (redo & REDO_FROM_LANES) RGPU_TRY(redo_bits());
   if (redo & PHRASE_REDO_WIDE) {
     TimedLaunch tl(c, stream, "k_phrase_match(wide lists)", 0);
     if (legacy) exact(k_phrase_match<true, PHRASE_LIST_CAP, true>, left, n_left); else exact(k_phrase_match<false, PHRASE_LIST_CAP, true>, left, n_left);
@@ -5120,6 +5139,10 @@ static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const P
   if (redo & PHRASE_REDO_SPAN_WIDE) {
     TimedLaunch tl(c, stream, "k_span_near(wide lists)", 0);
     if (legacy) exact(k_span_near<true, PHRASE_LIST_CAP, true>, left, n_left); else exact(k_span_near<false, PHRASE_LIST_CAP, true>, left, n_left);
+  }
+  if (redo & PHRASE_REDO_SPAN_UNORD_WIDE) {
+    TimedLaunch tl(c, stream, "k_span_unordered(wide pool)", 0);
+    if (legacy) exact(k_span_unordered<true, SLOPPY_POOL, true>, left, n_left); else exact(k_span_unordered<false, SLOPPY_POOL, true>, left, n_left);
   }
   if (redo & PHRASE_REDO_SLOPPY) {
     TimedLaunch tl(c, stream, "k_sloppy_match(wide pool)", 0);
@@ -5283,7 +5306,9 @@ static int32_t check_span_clauses(const rgpu_phrase_query& Q, const rgpu_phrase_
 
 static int32_t search_phrase_batch_impl(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_query* queries, int32_t n_queries,
                                         const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
-                                        int64_t* total_hits_out, bool span = false) {
+                                        int64_t* total_hits_out, bool span = false, bool unordered = false) {
+  // unordered (with span): rgpu_search_span_unordered_batch - the same plan, checks and collectors; the match stage runs
+  // NearSpansUnordered's kernels (kernels/search_span_unordered.hpp).
   // span: rgpu_search_span_near_batch - the queries are ordered SpanNearQuerys over SpanTermQuery clauses. The plan, the candidate
   // stage and the collectors are the phrases'; the match stage runs the span kernels, and the collectors are handed a marker in
   // place of the slops: SpanScorer is two-phase whatever the slop (span.rs:1033-1091), so next_limit applies at slop 0 too.
@@ -5419,14 +5444,15 @@ static int32_t search_phrase_batch_impl(rgpu_segment* seg, rgpu_docset* set, con
                                                       &redo_cap, false /* the collectors read a query's first emit_count slots only */,
                                                       masked.on() && c->phrase_mask_compact}));
     RGPU_TRY(phrase_match_stage(seg, stream, PhraseMatchStage{d_q, d_t, sg.dev(r_pt), d_ep, d_sl, sg.dev(r_gr), n_queries, slots, redo_cap, any_exact, any_sloppy,
-                                                              sloppy_rpts, true, d_cut, d_cp, d_nl, collect_items, any_span}));
+                                                              sloppy_rpts, true, d_cut, d_cp, d_nl, collect_items, any_span, span && unordered}));
     phrase_collect_stage(seg, stream, PhraseCollectStage{d_ep, d_cp, d_collect_sl, d_nl, n_queries, k, collect_items, any_cutoff, sg.dev(r_ab), d_cut});
     HIP_TRY(launch_status());
   }
   // the verdict in the same round as the rows (nothing launched: nothing to ask, and d_err may hold another call's)
   int err = 0;
   RGPU_TRY(api_rows_read_back(c, stream, n_queries, k, hits_out, total_hits_out, items > 0 ? &err : nullptr));
-  return phrase_match_status(err, span ? "a doc holds the term of a span clause more than 1024 times"
+  return phrase_match_status(err, span ? (unordered ? "a doc holds the terms of an unordered span query's clauses more than 2048 times in all"
+                                                   : "a doc holds the term of a span clause more than 1024 times")
                                        : "a doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)",
                              "internal: a conjunction match was not found again");
 }
@@ -5434,9 +5460,15 @@ static int32_t search_phrase_batch_impl(rgpu_segment* seg, rgpu_docset* set, con
 extern "C" int32_t rgpu_search_span_near_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
                                                const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t in_order, int32_t k,
                                                rgpu_hit* hits_out, int64_t* total_hits_out) {
-  // NearSpansUnordered pops a BinaryHeap whose order among cells at equal (start, end) is the heap array's (span_near.rs:681-696)
-  if (in_order == 0) return fail(RGPU_ERR_UNSUPPORTED, "span near: only in_order = true is served");
+  // NearSpansUnordered is another walk and another call: rgpu_search_span_unordered_batch
+  if (in_order == 0) return fail(RGPU_ERR_UNSUPPORTED, "span near: only in_order = true is served (unordered near: rgpu_search_span_unordered_batch)");
   return search_phrase_batch_impl(seg, nullptr, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out, true);
+}
+// (include/rucene_gpu.h rgpu_search_span_unordered_batch; the match kernels: kernels/search_span_unordered.hpp)
+extern "C" int32_t rgpu_search_span_unordered_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
+                                                    const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
+                                                    int64_t* total_hits_out) {
+  return search_phrase_batch_impl(seg, nullptr, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out, true, true);
 }
 extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
                                             const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,

@@ -254,7 +254,7 @@ class PhraseQuery:
 
 
 class SpanTermQuery:
-    """query/spans/span_term.rs: the spans [position, position + 1) of one term. Served as a clause of an ordered SpanNearQuery
+    """query/spans/span_term.rs: the spans [position, position + 1) of one term. Served as a clause of a SpanNearQuery
     (whose weight takes the near query's boost alone: a clause's `boost` only travels with extract_terms)."""
 
     def __init__(self, term, boost=1.0):
@@ -271,8 +271,10 @@ class SpanTermQuery:
 class SpanNearQuery:
     """SpanNearQuery::new (query/spans/span_near.rs:101-124): `clauses` within `slop` positions of each other, in the clauses' order
     when in_order. The GPU path serves a top-level query with in_order=True whose clauses are all SpanTermQuery
-    (rgpu_search_span_near_batch); unordered near and nested span clauses are UnsupportedOperation when the query is searched, i.e.
-    the caller's CPU path, and so is a span query inside BooleanQuery, FilterQuery, DisjunctionMaxQuery, BoostingQuery or a rescoring.
+    (rgpu_search_span_near_batch), and the same shape with in_order=False (NearSpansUnordered, rgpu_search_span_unordered_batch) on a
+    searcher made with unordered_spans=True. Unordered near on any other searcher and nested span clauses are UnsupportedOperation
+    when the query is searched, i.e. the caller's CPU path, and so is a span query inside BooleanQuery, FilterQuery,
+    DisjunctionMaxQuery, BoostingQuery or a rescoring.
     The weight sums the idf of every clause's term, a term named twice counted twice (build_sim_weight, span.rs:574-602)."""
 
     def __init__(self, clauses, slop=0, in_order=True, boost=1.0):
@@ -283,15 +285,16 @@ class SpanNearQuery:
         if not all(isinstance(c, (SpanTermQuery, SpanNearQuery)) for c in self.clauses):
             raise RgpuError(-2, "SpanNearQuery takes span queries as clauses")
 
-    def served_by_gpu(self):
-        """None, or why the GPU path leaves this query to the CPU searcher"""
-        if not self.in_order:
+    def served_by_gpu(self, unordered_spans=False):
+        """None, or why the GPU path leaves this query to the CPU searcher. unordered_spans: the searcher's opt-in - without it
+        unordered near is refused, as it is for every caller that has not opted in."""
+        if not self.in_order and not unordered_spans:
             return "an unordered SpanNearQuery is not served by the GPU path"
         if not all(isinstance(c, SpanTermQuery) for c in self.clauses):
             return "a SpanNearQuery with nested span clauses is not served by the GPU path"
         if len(self.clauses) > _lib.MAX_PHRASE_TERMS:
             return "a SpanNearQuery of more than %d clauses is not served by the GPU path" % _lib.MAX_PHRASE_TERMS
-        if self.slop < 0:   # (NearSpansOrdered would match nothing: match_width >= 0)
+        if self.slop < 0:   # (NearSpansOrdered would match nothing: match_width >= 0; NearSpansUnordered could, the call refuses it)
             return "a SpanNearQuery with a negative slop is not served by the GPU path"
         return None
 
@@ -326,14 +329,15 @@ def _holds_span(query):
     return False
 
 
-def _refuse_unserved_spans(query):
-    """UnsupportedOperation for every span query but a top-level ordered SpanNearQuery over SpanTermQuery clauses"""
+def _refuse_unserved_spans(query, unordered_spans=False):
+    """UnsupportedOperation for every span query but a top-level SpanNearQuery over SpanTermQuery clauses - ordered, or, on a
+    searcher that opted in (unordered_spans), unordered"""
     if isinstance(query, SpanNearQuery):
-        why = query.served_by_gpu()
+        why = query.served_by_gpu(unordered_spans)
         if why:
             raise RgpuError(-5, why)
     elif _holds_span(query):
-        raise RgpuError(-5, "a span query is served by the GPU path as a top-level ordered SpanNearQuery only")
+        raise RgpuError(-5, "a span query is served by the GPU path as a top-level SpanNearQuery only")
 
 
 class PointRangeQuery:
@@ -757,8 +761,12 @@ class GpuIndexSearcher:
     range_filter_capacity = 256   # memoised range filters kept from one search_batch to the next (range_filter); set per searcher
 
     def __init__(self, leaves, ctx=None, similarity=None, next_limit=None, flatten_nested=False, cpu_fallback=None, filtered_phrases=False,
-                 required_sets=False):
-        """required_sets: serve queries whose ONLY required clauses are doc sets - "b c #F", a lone #F, a lone PointRangeQuery,
+                 required_sets=False, unordered_spans=False):
+        """unordered_spans: serve a top-level SpanNearQuery(in_order=False) over SpanTermQuery clauses through
+        rgpu_search_span_unordered_batch (NearSpansUnordered, the heap's array order kept; off by default: such rows are
+        UnsupportedOperation, as they have been). Still refused with it on: nested span clauses, a span query inside a boolean,
+        filtered, dismax, boosting or rescoring query.
+        required_sets: serve queries whose ONLY required clauses are doc sets - "b c #F", a lone #F, a lone PointRangeQuery,
         "+range b c", "-X", "-t", MatchAllDocsQuery alone and under MUST - through rgpu_search_batch_required_set: every doc of
         live AND sets is collected, the docs no SHOULD clause holds at score 0 (off by default: such rows are UnsupportedOperation,
         as they have been). With it on "b c -X" (min_should_match <= 1) is served too, masked: ReqNotScorer over the disjunction,
@@ -776,6 +784,7 @@ class GpuIndexSearcher:
         self.flatten_nested = bool(flatten_nested)
         self.filtered_phrases = bool(filtered_phrases)
         self.required_sets = bool(required_sets)
+        self.unordered_spans = bool(unordered_spans)
         self.cpu_fallback = cpu_fallback
         self.leaves = list(leaves)
         # DefaultIndexSearcher::new(reader, next_limit: Option<usize>) (searcher.rs:291-296, :361): how many approximations of a
@@ -1462,11 +1471,12 @@ class GpuIndexSearcher:
         boosting queries (rgpu_search_batch), PhraseQuery rows (rgpu_search_phrase_batch), BooleanQuery rows with phrases among their
         required clauses (rgpu_search_phrase_bool_batch) and BooleanQuery rows of SHOULD / MUST_NOT clauses with phrases among the
         SHOULD ones (rgpu_search_phrase_or_batch) and top-level ordered SpanNearQuery rows over SpanTermQuery clauses
-        (rgpu_search_span_near_batch; any other span query is UnsupportedOperation): one call per kind and leaf, rows keep their order. Rows with doc-set clauses
+        (rgpu_search_span_near_batch; with unordered_spans the unordered ones through rgpu_search_span_unordered_batch; any other span
+        query is UnsupportedOperation): one call per kind and leaf, rows keep their order. Rows with doc-set clauses
         (CachedFilter under FILTER / MUST_NOT, FilterQuery) are grouped by their combination of sets and searched masked
         (rgpu_search_batch_masked; with filtered_phrases the phrase kinds through their masked calls), one call per group, kind and leaf."""
         for q in queries:   # refused before any leaf is touched and before any range's set is built
-            _refuse_unserved_spans(q)
+            _refuse_unserved_spans(q, getattr(self, "unordered_spans", False))
             self._peel(q, build=False)
         if getattr(self, "_range_filters", None):   # (a batch on a searcher that never built a range filter goes the way it went)
             self.drop_range_filters(keep=self.range_filter_capacity)
@@ -1495,7 +1505,7 @@ class GpuIndexSearcher:
             if isinstance(q, PhraseQuery):
                 return 1
             if isinstance(q, SpanNearQuery):
-                return 4
+                return 4 if q.in_order else 5
             if isinstance(q, BooleanQuery) and q.has_phrases():   # no MUST, no FILTER: the disjunction route; else phrase_bool_parts decides
                 return 2 if (q.must_queries or q.filter_queries) else 3
             return 0
@@ -1510,9 +1520,11 @@ class GpuIndexSearcher:
         else:
             if masks is not None and (not getattr(self, "filtered_phrases", False) or any(q.slop > 0 for q in queries if isinstance(q, PhraseQuery))):
                 raise RgpuError(-5, "a filtered phrase is not served by the GPU path")
-            if masks is not None and 4 in kinds:
+            if masks is not None and (4 in kinds or 5 in kinds):
                 raise RgpuError(-5, "a filtered span query is not served by the GPU path")
-            rows = [np.flatnonzero(np.array(kinds) == kd) for kd in (0, 1, 2, 3, 4)]
+            if 5 in kinds and not getattr(self, "unordered_spans", False):   # (search_batch has refused it already)
+                raise RgpuError(-5, "an unordered SpanNearQuery is not served by the GPU path")
+            rows = [np.flatnonzero(np.array(kinds) == kd) for kd in (0, 1, 2, 3, 4, 5)]
             groups = [[queries[i] for i in r] for r in rows]
             for q in groups[2]:   # refused before any leaf is touched
                 self.phrase_bool_parts(q)
@@ -1539,6 +1551,9 @@ class GpuIndexSearcher:
                 if groups[4]:   # ordered SpanNearQuery rows: packed as phrases, clause i at position i
                     qs, ts = self.pack_phrases(groups[4], leaf)
                     hits[rows[4]], totals[rows[4]] = seg.search_span_near_batch(qs, ts, k)
+                if groups[5]:   # unordered SpanNearQuery rows (unordered_spans): packed exactly as the ordered ones
+                    qs, ts = self.pack_phrases(groups[5], leaf)
+                    hits[rows[5]], totals[rows[5]] = seg.search_span_unordered_batch(qs, ts, k)
                 per_leaf.append((hits, totals))
         return per_leaf
 

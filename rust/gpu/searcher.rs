@@ -16,6 +16,8 @@
 //   * search/collector/top_docs.rs    pub(crate) fn estimated_hits(&self) -> usize
 //                                     pub(crate) fn add_leaf_result(&mut self, hits: &[(DocId, f32)], total_hits: usize)
 //       = what finish_parallel does with one LeafTopDocs (top_docs.rs:157-172): total_hits += n; add_doc(doc, score) per hit.
+// and, for `unordered_spans` (rust/rucene_span_accessor.patch, a file of its own):
+//   * search/query/spans/span_near.rs pub(crate) fn parts(&self) -> (&str, &[SpanQueryEnum], i32, bool)
 use std::collections::HashMap;
 use std::ops::Deref;
 use std::sync::Mutex;
@@ -26,6 +28,7 @@ use core::codec::{Codec, TermIterator, Terms};
 use core::doc::Term;
 use core::index::reader::{IndexReader, LeafReader, LeafReaderContext};
 use core::search::collector::{SearchCollector, TopDocsCollector};
+use core::search::query::spans::{SpanNearQuery, SpanQueryEnum};
 use core::search::query::{BooleanQuery, PhraseQuery, Query, TermQuery};
 use core::search::searcher::{DefaultIndexSearcher, IndexSearcher, SearchPlanBuilder};
 use core::search::similarity::SimilarityProducer;
@@ -150,6 +153,12 @@ pub struct GpuIndexSearcher<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: De
     /// Python and C++ mirrors. Still the CPU's with it on: an exclusion beside min_should_match >= 2, MUST_NOT term clauses beside
     /// the sets, a SHOULD clause of boost <= 0, phrases and nested clauses on the SHOULD side.
     pub required_sets: bool,
+    /// try_gpu serves a top-level SpanNearQuery(in_order = false) whose clauses are all SpanTermQuery through
+    /// rgpu_search_span_unordered_batch (try_span_unordered: NearSpansUnordered with the heap's array order kept, bit-exact) instead of
+    /// leaving it to the CPU searcher. Off by default, as `unordered_spans` of the Python and C++ mirrors. The CPU's either way:
+    /// nested span clauses, SpanOrQuery and SpanGapQuery clauses, a span query inside a boolean, filtered, dismax, boosting or
+    /// rescoring query (no tree this shim flattens holds one), and - in this shim - the ordered SpanNearQuery.
+    pub unordered_spans: bool,
 }
 
 unsafe impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: SimilarityProducer<C>> Send for GpuIndexSearcher<C, R, IR, SP> {}
@@ -183,7 +192,7 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             leaves.push(GpuLeaf { seg, has_positions: pos.is_some() });
         }
         let next_limit = match next_limit { None => 0, Some(0) => RGPU_NEXT_LIMIT_ZERO, Some(n) => n.min(i32::max_value() as usize) as i32 };
-        Ok(GpuIndexSearcher { cpu, ctx, field: field.to_string(), leaves, sim_tables: Mutex::new(HashMap::new()), next_limit, allow_flatten, filtered_phrases: false, required_sets: false })
+        Ok(GpuIndexSearcher { cpu, ctx, field: field.to_string(), leaves, sim_tables: Mutex::new(HashMap::new()), next_limit, allow_flatten, filtered_phrases: false, required_sets: false, unordered_spans: false })
     }
 
     /// BooleanQuery trees the C ABI serves, flattened to one clause list (query/boolean_query.rs:195-279 is what the CPU builds
@@ -406,6 +415,9 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
     fn try_gpu(&self, query: &dyn Query<C>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
         if k == 0 || k > RGPU_MAX_K as usize { return Ok(false); }
         if let Some(p) = query.as_any().downcast_ref::<PhraseQuery>() { return self.try_phrase(p, None, top, k); }
+        if let Some(n) = query.as_any().downcast_ref::<SpanNearQuery>() {
+            return if self.unordered_spans { self.try_span_unordered(n, top, k) } else { Ok(false) };
+        }
         if let Some(b) = query.as_any().downcast_ref::<BooleanQuery<C>>() {
             let (must, should, filter, must_not, _) = b.clauses();
             if must.iter().chain(should).chain(filter).chain(must_not).any(|q| q.as_any().downcast_ref::<PhraseQuery>().is_some()) {
@@ -528,6 +540,44 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
                     Some(m) => rgpu_search_phrase_batch_masked(seg, m[leaf.ord], &q, 1, pterms.as_ptr(), pterms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total),
                     None => rgpu_search_phrase_batch(seg, &q, 1, pterms.as_ptr(), pterms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total),
                 }
+            }, self.ctx)?;
+            Self::hand_over(top, &hits, total);
+        }
+        Ok(true)
+    }
+
+    /// SpanNearQuery { in_order: false } over SpanTermQuery clauses (`unordered_spans`): NearSpansUnordered (span_near.rs:333-528) +
+    /// SpanScorer (span.rs:489-519) -> rgpu_search_span_unordered_batch per leaf. The row is packed exactly as an ordered one: clause
+    /// i is phrase term i at position i, `slop` the allowed slop; weight = idf summed over every clause's term, a term named by two
+    /// clauses counted twice (build_sim_weight over extract_term_keys, span.rs:574-602), boost 1.0. Per leaf as
+    /// SpanNearWeight::get_spans: a clause whose term the leaf lacks -> no spans for that leaf (doc_freq = 0 tells the library the
+    /// same). The searcher's next_limit applies at every slop: spans are always two-phase. Ok(false) - the CPU searcher - for an
+    /// ordered query, another field, a clause that is not a SpanTermQuery (nested near, SpanOrQuery, SpanGapQuery, SpanBoostQuery),
+    /// more than RGPU_MAX_PHRASE_TERMS clauses, a negative slop, a clause that carries a KeyedContext (its idf is not the
+    /// statistics'), a leaf without positions.
+    fn try_span_unordered(&self, n: &SpanNearQuery, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
+        let (field, clauses, slop, in_order) = n.parts();
+        if in_order || field != self.field || clauses.len() < 2 || clauses.len() > RGPU_MAX_PHRASE_TERMS as usize || slop < 0
+            || self.leaves.iter().any(|l| !l.has_positions) {
+            return Ok(false);
+        }
+        let mut terms: Vec<Term> = Vec::with_capacity(clauses.len());
+        for c in clauses {
+            match c {
+                SpanQueryEnum::Term(t) if t.ctx.is_none() => terms.push(t.term.clone()),
+                _ => return Ok(false),
+            }
+        }
+        let positions: Vec<i32> = (0..terms.len() as i32).collect();
+        let term_refs: Vec<&Term> = terms.iter().collect();
+        let (weight, sim_table) = self.weight_of(&term_refs, 1.0)?;
+        for leaf in self.cpu.reader().leaves() {
+            let pterms = self.phrase_terms(&leaf, &terms, &positions)?;
+            let q = RgpuPhraseQuery { n_terms: pterms.len() as i32, first_term: 0, weight, sim_table, slop, next_limit: self.next_limit };
+            let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
+            let mut total: i64 = 0;
+            check(unsafe {
+                rgpu_search_span_unordered_batch(self.leaves[leaf.ord].seg, &q, 1, pterms.as_ptr(), pterms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total)
             }, self.ctx)?;
             Self::hand_over(top, &hits, total);
         }
