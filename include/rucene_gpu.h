@@ -1025,6 +1025,99 @@ int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* qu
                                   const rgpu_phrase_term* terms, int32_t n_terms_total,
                                   const rgpu_rescore_request* requests, int32_t k, rgpu_hit* hits_inout, int32_t finish);
 
+/* ---- further fields of a segment; term and dismax clauses over fields -------------------------------------- */
+/* A Lucene segment keeps the postings of ALL its indexed fields in one .doc file and shares max_doc and the live docs between
+ * them; what differs per field is the norms (norms_producer.rs:146-154: one entry per field number), the IndexOptions and with
+ * them the width of a skip entry (skip_writer.rs:261-289). Field 0 is the field the segment was uploaded with; this declares a
+ * further one, over the same .doc bytes and live docs: its own norm bytes in HBM (NULL: the field omits norms), held as ranks
+ * with a rank_to_norm of its own when at most 64 distinct bytes occur (and rgpu_config.raw_norms is 0), raw otherwise - the
+ * rule rgpu_segment_upload_field applies - and its own index_options, the values rgpu_segment_upload_field takes (1..4,
+ * | RGPU_FIELD_STORES_PAYLOADS). *field_out = the slot, 1 .. RGPU_MAX_FIELDS - 1, in the order of the calls; a ninth field is
+ * RGPU_ERR_UNSUPPORTED. Positions of an attached field are never read: no entry point takes a phrase over it.
+ * Every other entry point keeps meaning field 0 and is unchanged by attached fields. */
+#define RGPU_MAX_FIELDS 8
+int32_t rgpu_segment_attach_field(rgpu_segment* seg, const uint8_t* norms_or_null, int32_t index_options, int32_t* field_out);
+/* rgpu_segment_prepare_terms for terms of field `field` (0: the same call): both stages run against that field's norms, freq
+ * layout and skip-entry width. A term belongs to exactly one field: a doc_start_fp that was prepared under another field is
+ * RGPU_ERR_ILLEGAL_ARGUMENT - in both directions: once fields are attached, rgpu_segment_prepare_terms and every field-0 entry point
+ * answer the same for a term state whose postings a field-N call prepared (on a segment without attached fields nothing changes). No doc bitmaps and no block-max sketches are built for fields other than 0. Dropping the store
+ * (rgpu_segment_release_prepared_terms, rgpu_config.prepared_budget_mib) drops every field's terms; they are prepared again
+ * when they are next named. */
+int32_t rgpu_segment_prepare_field_terms(rgpu_segment* seg, int32_t field, const rgpu_term_state* terms, int64_t n_terms);
+typedef struct rgpu_segment_field_info {
+  int64_t norms_bytes;    /* HBM bytes of the field's norms: max_doc, or 0 for a field without norms */
+  int32_t norm_mode;      /* 0 none, 1 ranks (+ a 64-byte rank_to_norm), 2 raw bytes */
+  int32_t n_norm_ranks;   /* distinct norm bytes in rank mode, else 0 */
+  int32_t index_options;  /* as given at upload / attach, RGPU_FIELD_STORES_PAYLOADS included */
+  int32_t skip_values;    /* values per level-0 skip entry of this field's terms: 2, 4, 5 or 6 */
+} rgpu_segment_field_info;
+int32_t rgpu_segment_get_field_info(rgpu_segment* seg, int32_t field, rgpu_segment_field_info* out);
+
+/* One scored (or prohibited) TermQuery clause of a cross-field query: rgpu_query_term plus the field slot its term lives in.
+ * `weight` and `sim_table` are that FIELD's: idf and the norm cache come from the field's own CollectionStatistics
+ * (term_query.rs:58-95, bm25_similarity.rs:151-177). */
+typedef struct rgpu_field_clause {
+  rgpu_term_state state;
+  float weight;
+  int32_t sim_table;
+  int32_t field;     /* 0 .. RGPU_MAX_FIELDS - 1, attached */
+  int32_t reserved;  /* 0 */
+} rgpu_field_clause;
+#define RGPU_GROUP_TERM 0    /* one TermQuery: n_terms = 1 */
+#define RGPU_GROUP_DISMAX 1  /* DisjunctionMaxQuery of 1..RGPU_MAX_GROUP_DISJUNCTS TermQuery disjuncts, in any fields */
+#define RGPU_MAX_FIELD_GROUPS 9     /* ten or more children of a DisjunctionSumScorer / DisjunctionMaxScorer are summed in heap */
+#define RGPU_MAX_GROUP_DISJUNCTS 9  /* order (disjunction_scorer.rs:41-45, 264-283): refused */
+#define RGPU_MAX_FIELDS_QUERY_CLAUSES 128 /* clauses of one query, MUST_NOT ones included (two cursors per lane of a wavefront) */
+typedef struct rgpu_field_group {
+  int32_t first_term;  /* index of the group's first clause in `clauses` */
+  int32_t n_terms;
+  uint32_t tie_bits;   /* RGPU_GROUP_DISMAX: bit pattern of the f32 tie_breaker_multiplier (finite); else ignored */
+  int32_t kind;        /* RGPU_GROUP_TERM / RGPU_GROUP_DISMAX */
+} rgpu_field_group;
+#define RGPU_OCCUR_SHOULD 1  /* rgpu_fields_query.occur: which kinds of positive clauses the BooleanQuery holds, or-ed together */
+#define RGPU_OCCUR_MUST 2
+#define RGPU_OCCUR_FILTER 4
+typedef struct rgpu_fields_query {
+  int32_t occur;             /* RGPU_OCCUR_SHOULD or RGPU_OCCUR_MUST; any other combination is refused (below) */
+  int32_t first_group;       /* index of the query's first group in `groups` */
+  int32_t n_groups;
+  int32_t min_should_match;  /* BooleanQuery::min_should_match; 0 and 1 alike */
+  int32_t first_must_not;    /* MUST_NOT TermQuery clauses of any field: a range of `clauses` (weight / sim_table unused) */
+  int32_t n_must_not;
+} rgpu_fields_query;
+/* BooleanQuery over TermQuery and DisjunctionMaxQuery clauses whose terms live in different fields of one segment -
+ * "title:gpu | body:gpu", "(title:a | body:a) (title:b | body:b)" - per leaf, by BooleanWeight::create_scorer
+ * (query/boolean_query.rs:200-273):
+ *   presence  a disjunct with doc_freq 0 has no scorer and drops out (query/disjunction_max_query.rs:142-161); a group with no
+ *             disjunct left has none; with ONE left it is that TermScorer (:154). A clause's score on a doc is TermScorer's
+ *             BM25 (term_scorer.rs:43-67) with the norm byte of THE CLAUSE'S FIELD and the clause's sim table. A dismax group
+ *             with two or more present disjuncts: sum and max over those that hold the doc, in disjunct order, from 0.0f / -inf,
+ *             then max + (sum - max) * tie as three f32 operations (scorer/disjunction_scorer.rs:246-262).
+ *   SHOULD    1..RGPU_MAX_FIELD_GROUPS groups, DisjunctionSumScorer over a SimpleQueue (boolean_query.rs:217-234): a doc any
+ *             present group holds is a hit, its score 0.0f + g1 + g2 .. over the groups on the doc in clause order
+ *             (disjunction_scorer.rs:213-225); min_should_match >= 2 counts GROUPS on the doc (:317-329; two disjuncts of one
+ *             group count once). A group absent from the leaf drops, min_should_match stays.
+ *   MUST      ConjunctionScorer over the groups (boolean_query.rs:200-216; one group: that scorer): every group must hold the
+ *             doc, a group absent from the leaf = the query matches nothing there. The score takes the first addend as it is
+ *             and adds the others one by one in the leaf's STABLE cost order - a term's cost is its doc_freq, a dismax group's
+ *             the sum of its present disjuncts' (disjunction_scorer.rs:126; conjunction_scorer.rs:30, 87-95); the library sorts
+ *             per leaf. min_should_match has no effect.
+ *   MUST_NOT  ReqNotScorer over the union of the present clauses (boolean_query.rs:235-273, req_not_scorer.rs:47-63).
+ * Live docs apply; total_hits_out[q] counts every collected live doc; rows are score desc, doc asc, {-1, 0} padded; doc ids
+ * carry the segment's doc_base. 1 <= k <= 128. Terms are prepared implicitly, each under its clause's field. Blocking; rows are
+ * bit-equal to the reference.
+ * Refused with RGPU_ERR_UNSUPPORTED, nothing launched and nothing written: more than RGPU_MAX_FIELD_GROUPS groups or
+ * RGPU_MAX_GROUP_DISJUNCTS disjuncts; occur = MUST | SHOULD (ReqOptScorer); RGPU_OCCUR_FILTER in occur; MUST_NOT clauses beside
+ * min_should_match >= 2 under SHOULD; more than RGPU_MAX_FIELDS_QUERY_CLAUSES clauses in a query; k > 128.
+ * RGPU_ERR_ILLEGAL_ARGUMENT, likewise: a field slot that is not attached, a non-finite tie, zero groups, one doc_start_fp (of a
+ * term of doc_freq >= 2) named under two fields or under another field than the one it was prepared under - checked before anything
+ * is prepared, so that nothing is filed under a wrong slot -, a TERM group of other
+ * than one clause, a dismax group without a disjunct, ranges outside the arrays, a negative count, a sim_table that was never
+ * uploaded. There are no masked, sharded, planner, rescore or count forms. */
+int32_t rgpu_search_fields_batch(rgpu_segment* seg, const rgpu_fields_query* queries, int32_t n_queries, const rgpu_field_group* groups,
+                                 int32_t n_groups_total, const rgpu_field_clause* clauses, int32_t n_clauses_total, int32_t k,
+                                 rgpu_hit* hits_out, int64_t* total_hits_out);
+
 /* ---- measurement ------------------------------------------------------------------------------------------ */
 typedef struct rgpu_kernel_stat {
   char name[48];

@@ -46,6 +46,21 @@ PHRASE_OR_QUERY_DTYPE = np.dtype([("n_phrases", "<i4"), ("first_phrase", "<i4"),
 assert PHRASE_OR_QUERY_DTYPE.itemsize == 48
 PHRASE_OR_MAX_SHOULD = 9   # ten or more SHOULD clauses sum in heap order (disjunction_scorer.rs:41-45)
 FIELD_INFO_DTYPE = np.dtype([("number", "<i4"), ("index_options", "<i4"), ("has_payloads", "<i4"), ("flags", "<i4")], align=True)
+# rgpu_search_fields_batch: clauses that say which field of the segment their term lives in, groups of them, queries of groups
+MAX_FIELDS = 8                    # RGPU_MAX_FIELDS: field 0 (the upload's) + attached slots 1..7
+MAX_FIELD_GROUPS = 9              # RGPU_MAX_FIELD_GROUPS
+MAX_GROUP_DISJUNCTS = 9           # RGPU_MAX_GROUP_DISJUNCTS
+MAX_FIELDS_QUERY_CLAUSES = 128    # RGPU_MAX_FIELDS_QUERY_CLAUSES
+GROUP_TERM, GROUP_DISMAX = 0, 1   # rgpu_field_group.kind
+OCCUR_SHOULD, OCCUR_MUST, OCCUR_FILTER = 1, 2, 4   # rgpu_fields_query.occur (SHOULD or MUST alone are served)
+FIELD_CLAUSE_DTYPE = np.dtype([("state", TERM_STATE_DTYPE), ("weight", "<f4"), ("sim_table", "<i4"), ("field", "<i4"), ("reserved", "<i4")], align=True)
+FIELD_GROUP_DTYPE = np.dtype([("first_term", "<i4"), ("n_terms", "<i4"), ("tie_bits", "<u4"), ("kind", "<i4")], align=True)
+FIELDS_QUERY_DTYPE = np.dtype([("occur", "<i4"), ("first_group", "<i4"), ("n_groups", "<i4"), ("min_should_match", "<i4"), ("first_must_not", "<i4"),
+                               ("n_must_not", "<i4")], align=True)
+SEGMENT_FIELD_INFO_DTYPE = np.dtype([("norms_bytes", "<i8"), ("norm_mode", "<i4"), ("n_norm_ranks", "<i4"), ("index_options", "<i4"), ("skip_values", "<i4")],
+                                    align=True)
+assert FIELD_CLAUSE_DTYPE.itemsize == 48 and FIELD_GROUP_DTYPE.itemsize == 16 and FIELDS_QUERY_DTYPE.itemsize == 24 and SEGMENT_FIELD_INFO_DTYPE.itemsize == 24
+NORM_MODE_NONE, NORM_MODE_RANK, NORM_MODE_RAW = 0, 1, 2   # rgpu_segment_field_info.norm_mode
 FIELD_STATS_DTYPE = np.dtype([("num_terms", "<i8"), ("sum_total_term_freq", "<i8"), ("sum_doc_freq", "<i8"), ("doc_count", "<i4"),
                               ("longs_size", "<i4")], align=True)
 INDEX_OPTIONS_DOCS, INDEX_OPTIONS_DOCS_AND_FREQS, INDEX_OPTIONS_POSITIONS, INDEX_OPTIONS_OFFSETS = 1, 2, 3, 4
@@ -82,6 +97,7 @@ EXPORTS = [
     "rgpu_search_phrase_batch_masked", "rgpu_search_phrase_bool_batch_masked", "rgpu_search_phrase_or_batch_masked",
     "rgpu_search_span_near_batch",
     "rgpu_search_span_unordered_batch",
+    "rgpu_segment_attach_field", "rgpu_segment_prepare_field_terms", "rgpu_segment_get_field_info", "rgpu_search_fields_batch",
     "rgpu_points_attach", "rgpu_points_get_info", "rgpu_points_free", "rgpu_docset_from_point_ranges",
     "rgpu_plan_uniform_bytes", "rgpu_plan_batch_ids", "rgpu_plan_batch_bytes", "rgpu_planner_search_uniform_ids_device", "rgpu_planner_search_uniform_ids_sharded",
 ]
@@ -185,6 +201,10 @@ def lib():
         "rgpu_advance_batch": (i32, [vp, vp, vp, i64, vp, vp]),
         "rgpu_sim_table_upload": (i32, [vp, vp, f32]),
         "rgpu_search_batch": (i32, [vp, vp, i32, vp, i32, i32, vp, vp]),
+        "rgpu_segment_attach_field": (i32, [vp, vp, i32, C.POINTER(i32)]),
+        "rgpu_segment_prepare_field_terms": (i32, [vp, i32, vp, i64]),
+        "rgpu_segment_get_field_info": (i32, [vp, i32, vp]),
+        "rgpu_search_fields_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_batch_device": (i32, [vp, vp, i32, vp, i32, i32, vp, vp, vp]),
         "rgpu_merge_topk_device": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "rgpu_docset_from_words": (i32, [vp, vp, C.POINTER(vp)]),
@@ -922,6 +942,37 @@ class Segment:
         h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).copy()
         _check(lib().rgpu_rescore_phrase_batch(self._h, q.ctypes.data, q.size, t.ctypes.data, t.size, r.ctypes.data, h.shape[1], h.ctypes.data, int(finish)))
         return h
+
+    def attach_field(self, norms, index_options=INDEX_OPTIONS_DOCS_AND_FREQS):
+        """rgpu_segment_attach_field: a further indexed field of the same Lucene segment (same .doc bytes, live docs, max_doc) -> its slot"""
+        nb = None if norms is None else np.ascontiguousarray(norms, dtype=np.uint8)
+        if nb is not None and nb.size != self.max_doc:
+            raise RgpuError(-2, "a field's norms hold one byte per doc: %d for max_doc %d" % (nb.size, self.max_doc))
+        slot = C.c_int32(-1)
+        _check(lib().rgpu_segment_attach_field(self._h, None if nb is None else nb.ctypes.data, int(index_options), C.byref(slot)))
+        return int(slot.value)
+
+    def prepare_field_terms(self, field, states):
+        st = np.ascontiguousarray(np.atleast_1d(states), dtype=TERM_STATE_DTYPE)
+        _check(lib().rgpu_segment_prepare_field_terms(self._h, int(field), st.ctypes.data, st.size))
+
+    def field_info(self, field):
+        """rgpu_segment_get_field_info: norms bytes, norm mode (NORM_MODE_*), n_norm_ranks, index options and skip-entry width of a field slot"""
+        out = np.zeros(1, dtype=SEGMENT_FIELD_INFO_DTYPE)
+        _check(lib().rgpu_segment_get_field_info(self._h, int(field), out.ctypes.data))
+        return {k: int(out[0][k]) for k in SEGMENT_FIELD_INFO_DTYPE.names}
+
+    def search_fields_batch(self, queries, groups, clauses, k, hits=None, totals=None):
+        """rgpu_search_fields_batch: BooleanQuery rows over TermQuery / DisjunctionMaxQuery groups whose clauses name their field.
+        `hits` / `totals`: arrays to write into (tests: a refusal leaves them untouched)."""
+        q = np.ascontiguousarray(queries, dtype=FIELDS_QUERY_DTYPE)
+        g = np.ascontiguousarray(groups, dtype=FIELD_GROUP_DTYPE)
+        t = np.ascontiguousarray(clauses, dtype=FIELD_CLAUSE_DTYPE)
+        hits = np.zeros((q.size, max(k, 1)), dtype=HIT_DTYPE) if hits is None else hits
+        totals = np.zeros(q.size, dtype=np.int64) if totals is None else totals
+        _check(lib().rgpu_search_fields_batch(self._h, q.ctypes.data if q.size else None, q.size, g.ctypes.data if g.size else None, g.size,
+                                              t.ctypes.data if t.size else None, t.size, k, hits.ctypes.data, totals.ctypes.data))
+        return hits, totals
 
     def release_prepared_terms(self):
         _check(lib().rgpu_segment_release_prepared_terms(self._h))

@@ -17,6 +17,7 @@
 #include <dirent.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <fstream>
@@ -84,6 +85,11 @@ struct TermQuery : Query {
   explicit TermQuery(int64_t t, float b = 1.0f) : term(t), boost(b) {}
   explicit TermQuery(std::string bytes, float b = 1.0f) : text(std::move(bytes)), boost(b) {}
   bool by_text() const { return term < 0; }
+  // The indexed field the term lives in; empty = the leaves' primary field (LeafReader::field). Another field must be one of the
+  // leaves' extra_fields: GpuIndexSearcher::search / search_many route such trees to rgpu_search_fields_batch, every other path
+  // (count, rescoring, cached filters) answers UnsupportedOperation for them.
+  std::string field;
+  TermQuery in(std::string f) const { TermQuery t(*this); t.field = std::move(f); return t; }
 };
 // search/query/match_all_query.rs: every doc, ConstantScoreScorer with the weight's default of 0.0. Served by a searcher whose
 // required_sets is on: alone, and as the `query` of a FilteredQuery — clauses(MatchAllDocsQuery, {F}, {X}) is "#F -X", which is
@@ -148,6 +154,44 @@ struct DisjunctionMaxQuery : Query {
     return bits;
   }
   std::vector<TermQuery> extract_terms() const { return disjuncts; }  // :91-97
+};
+
+// BooleanQuery over TermQuery and DisjunctionMaxQuery-of-TermQuery clauses whose terms may live in different fields - the multi-field
+// query "(title:a | body:a) (title:b | body:b)" every query parser emits (rgpu_search_fields_batch in include/rucene_gpu.h): all
+// SHOULD (min_should_match counts groups) or all MUST, with MUST_NOT TermQuery clauses of any field. A BooleanQuery / DisjunctionMaxQuery
+// / TermQuery that names a further field is served the same way (GpuIndexSearcher::cross_spec). Ten or more groups or disjuncts are
+// UnsupportedOperation when searched: the reference sums those in heap order.
+struct MultiFieldQuery : Query {
+  struct Group {
+    bool dismax = false;
+    float tie_breaker_multiplier = 0.0f;
+    std::vector<TermQuery> terms;  // one TermQuery, or the disjuncts
+  };
+  std::vector<Group> groups;
+  bool must = false;  // the groups are MUST clauses (else SHOULD)
+  int32_t min_should_match = 0;
+  std::vector<TermQuery> must_not_queries;
+  static Group term(TermQuery t) { Group g; g.terms.push_back(std::move(t)); return g; }
+  static Group dismax(std::vector<TermQuery> disjuncts, float tie) {
+    if (disjuncts.empty()) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "DisjunctionMaxQuery: sub query should not be empty!");
+    Group g;
+    g.dismax = true;
+    g.tie_breaker_multiplier = tie;
+    g.terms = std::move(disjuncts);
+    return g;
+  }
+  static std::unique_ptr<MultiFieldQuery> should(std::vector<Group> groups, int32_t min_should_match = 0, std::vector<TermQuery> must_nots = {}) {
+    std::unique_ptr<MultiFieldQuery> q(new MultiFieldQuery());
+    q->groups = std::move(groups);
+    q->min_should_match = min_should_match;
+    q->must_not_queries = std::move(must_nots);
+    return q;
+  }
+  static std::unique_ptr<MultiFieldQuery> all_must(std::vector<Group> groups, std::vector<TermQuery> must_nots = {}) {
+    std::unique_ptr<MultiFieldQuery> q = should(std::move(groups), 0, std::move(must_nots));
+    q->must = true;
+    return q;
+  }
 };
 
 // query/boosting_query.rs:29-118, scorer/boosting_scorer.rs:40-81: the positive query's docs, counts and scores, a doc's score
@@ -632,7 +676,38 @@ struct RescoreRequest {
 
 // One segment: postings file, norms, live docs, FieldReader statistics, and the terms: a block-tree dictionary
 // (rgpu_terms_open over the segment's .tim/.tip) and/or a flat term table.
+// A further indexed field of a leaf's segment (LeafReader::extra_fields): its postings live in the leaf's one .doc file
+struct ExtraField {
+  std::string name;
+  int32_t field_number = 0;
+  int32_t index_options = 2;  // as for rgpu_segment_attach_field, RGPU_FIELD_STORES_PAYLOADS included
+  const uint8_t* norms = nullptr;  // null: the field omits norms
+  int64_t doc_count = 0, sum_total_term_freq = 0, sum_doc_freq = -1;
+  const rgpu_term_state* terms = nullptr;  // a flat table indexed by term id, or ...
+  int64_t n_terms = 0;
+  const rgpu_terms* dictionary = nullptr;  // ... the segment's block-tree dictionary, asked under field_number (not owned)
+  int32_t slot = -1;                       // rgpu_segment_attach_field's, filled by the searcher
+  bool term_state(const TermQuery& q, rgpu_term_state* out) const {
+    if (q.by_text()) {
+      if (!dictionary) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "this field has no term dictionary: query it by term id");
+      const int64_t offs[2] = {0, static_cast<int64_t>(q.text.size())};
+      uint8_t found = 0;
+      check(rgpu_terms_lookup(dictionary, field_number, reinterpret_cast<const uint8_t*>(q.text.data()), offs, 1, out, &found));
+      return found != 0;
+    }
+    if (q.term >= n_terms || terms[q.term].doc_freq <= 0) return false;
+    *out = terms[q.term];
+    return true;
+  }
+};
+
 struct LeafReader {
+  std::string field = "body";  // the primary field's name: a TermQuery without a field, or with this one, means it
+  std::vector<ExtraField> extra_fields;  // the segment's further indexed fields a query may name (TermQuery::field)
+  const ExtraField* extra(const std::string& name) const {
+    for (const ExtraField& x : extra_fields) if (x.name == name) return &x;
+    return nullptr;
+  }
   int32_t index_options = 2;  // doc::IndexOptions ordinal of the searched field: 1 Docs, 2 DocsAndFreqs
   const uint8_t* doc_bytes = nullptr;
   size_t doc_len = 0;
@@ -814,6 +889,7 @@ class GpuIndexSearcher {
     for (auto& l : leaves_) {
       check(rgpu_segment_upload_field(ctx_, l.doc_bytes, l.doc_len, l.norms, l.max_doc, l.doc_base, l.live_docs, l.index_options, &l.segment));
       if (l.pos_bytes) check(rgpu_segment_attach_positions(l.segment, l.pos_bytes, l.pos_len));
+      for (ExtraField& x : l.extra_fields) check(rgpu_segment_attach_field(l.segment, x.norms, x.index_options, &x.slot));  // slots 1.. in the order given
     }
     // searcher.rs:306-363: the first leaf with the largest max_doc provides the collection statistics
     for (size_t i = 1; i < leaves_.size(); ++i)
@@ -1034,6 +1110,7 @@ class GpuIndexSearcher {
     try {
       std::unique_ptr<Query> folded;
       const Query* q = &query;
+      if (dynamic_cast<const NestedBooleanQuery*>(&query)) refuse_other_fields(query);  // (before a fold hides where its clauses stood)
       if (auto* nested = dynamic_cast<const NestedBooleanQuery*>(&query)) {
         std::unique_ptr<BooleanQuery> req = nested->required_disjunction();
         // (the library sorts a conjunction's children by cost per leaf and adds a nested child's sum where ConjunctionScorer::score
@@ -1061,6 +1138,27 @@ class GpuIndexSearcher {
   // FilteredQuery rows are grouped by their combination of doc sets (host/docset_plan.hpp: caller order kept inside a group) and searched
   // masked, one rgpu_search_batch_masked per group and leaf; every other row goes the way it went.
   std::vector<TopDocs> search_many(const std::vector<const Query*>& queries, size_t k) {
+    {  // rows that name a further field of the leaves go to rgpu_search_fields_batch; a batch without one goes where it went.
+       // That call serves k <= 128: a batch that holds such a row is UnsupportedOperation as a whole for k > 128, its primary-field
+       // rows included (they are served up to k = 1024 in a batch of their own) - refused before any leaf is touched
+      std::vector<size_t> cross_rows, rest_rows;
+      for (size_t i = 0; i < queries.size(); ++i) (names_other_field(*queries[i]) ? cross_rows : rest_rows).push_back(i);
+      if (!cross_rows.empty()) {
+        std::vector<MultiFieldQuery> specs;
+        for (size_t i : cross_rows) specs.push_back(cross_spec(*queries[i]));  // refused before any leaf is touched
+        if (k > 128) throw Error(RGPU_ERR_UNSUPPORTED, "a cross-field query is served for k <= 128");
+        std::vector<TopDocs> out(queries.size());
+        if (!rest_rows.empty()) {
+          std::vector<const Query*> rest;
+          for (size_t i : rest_rows) rest.push_back(queries[i]);
+          std::vector<TopDocs> got = search_many(rest, k);
+          for (size_t i = 0; i < rest_rows.size(); ++i) out[rest_rows[i]] = std::move(got[i]);
+        }
+        std::vector<TopDocs> got = search_fields(specs, k);
+        for (size_t i = 0; i < cross_rows.size(); ++i) out[cross_rows[i]] = std::move(got[i]);
+        return out;
+      }
+    }
     for (const Query* q : queries)
       if (dynamic_cast<const PointRangeQuery*>(q)) throw Error(RGPU_ERR_UNSUPPORTED, "a lone point range is not served by the GPU path (the reference matches all of it)");
     for (const Query* q : queries) {  // refused before any leaf is touched
@@ -1136,7 +1234,7 @@ class GpuIndexSearcher {
     }
     bool deletions = false;
     for (const LeafReader& leaf : leaves_) deletions = deletions || leaf.live_docs != nullptr;
-    if (const TermQuery* t = dynamic_cast<const TermQuery*>(&query); t && !deletions) {
+    if (const TermQuery* t = dynamic_cast<const TermQuery*>(&query); t && !deletions && primary(*t)) {
       int64_t n = 0;
       rgpu_term_state st;
       for (const LeafReader& leaf : leaves_) if (leaf.term_state(*t, &st)) n += st.doc_freq;
@@ -1173,6 +1271,7 @@ class GpuIndexSearcher {
   // (phrase_query.rs:136-186): ONE BM25 weight from the statistics of all the phrase's terms.
   // `masks` (one doc set per leaf, or null): the search restricted to them — rgpu_search_phrase_batch_masked; exact phrases only.
   std::vector<TopDocs> search_phrases(const std::vector<const PhraseQuery*>& queries, size_t k, const std::vector<rgpu_docset*>* masks = nullptr) {
+    for (const auto* q : queries) refuse_other_fields(*q);  // (these paths read the primary field's postings, idf and sim table)
     const int32_t nq = static_cast<int32_t>(queries.size());
     std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
     std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
@@ -1204,6 +1303,7 @@ class GpuIndexSearcher {
   // (rgpu_search_span_near_batch per leaf) or all unordered (rgpu_search_span_unordered_batch per leaf; unordered_spans). The rows are
   // packed as phrases either way (clause i at position i, `slop` the allowed slop) and merged over the leaves with their doc bases.
   std::vector<TopDocs> search_span_nears(const std::vector<const SpanNearQuery*>& queries, size_t k, bool in_order = true) {
+    for (const auto* q : queries) refuse_other_fields(*q);  // (these paths read the primary field's postings, idf and sim table)
     const int32_t nq = static_cast<int32_t>(queries.size());
     std::vector<PhraseQuery> as_phrases;
     std::vector<const PhraseQuery*> rows;
@@ -1239,6 +1339,7 @@ class GpuIndexSearcher {
   // A FILTER clause rides with weight 0 (needs_scores = false); phrase_slot[i] = the phrase's index in `required`.
   // `masks` as for search_phrases: rgpu_search_phrase_bool_batch_masked.
   std::vector<TopDocs> search_phrase_bools(const std::vector<const PhraseBooleanQuery*>& queries, size_t k, const std::vector<rgpu_docset*>* masks = nullptr) {
+    for (const auto* q : queries) refuse_other_fields(*q);  // (these paths read the primary field's postings, idf and sim table)
     const int32_t nq = static_cast<int32_t>(queries.size());
     for (const PhraseBooleanQuery* q : queries) q->check_served();
     std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
@@ -1299,6 +1400,7 @@ class GpuIndexSearcher {
   // leaf. phrase_slot[i] = the phrase's index in `should_queries`.
   // `masks` as for search_phrases: rgpu_search_phrase_or_batch_masked.
   std::vector<TopDocs> search_phrase_ors(const std::vector<const PhraseDisjunctionQuery*>& queries, size_t k, const std::vector<rgpu_docset*>* masks = nullptr) {
+    for (const auto* q : queries) refuse_other_fields(*q);  // (these paths read the primary field's postings, idf and sim table)
     const int32_t nq = static_cast<int32_t>(queries.size());
     for (const PhraseDisjunctionQuery* q : queries) q->check_served();
     std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
@@ -1374,6 +1476,7 @@ class GpuIndexSearcher {
     std::vector<const PhraseQuery*> phrases;
     for (size_t q = 0; q < requests.size(); ++q) {
       if (!requests[q].query) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "a rescore request needs a query");
+      refuse_other_fields(*requests[q].query);
       if (dynamic_cast<const SpanNearQuery*>(requests[q].query) || dynamic_cast<const SpanTermQuery*>(requests[q].query))
         throw Error(RGPU_ERR_UNSUPPORTED, "rescoring with a span query is not served by the GPU path");
       if (const PhraseQuery* pq = dynamic_cast<const PhraseQuery*>(requests[q].query)) {
@@ -1630,6 +1733,151 @@ class GpuIndexSearcher {
     return out;
   }
 
+  // ---- cross-field queries (rgpu_search_fields_batch) -----------------------------------------------------------------------------
+  bool primary(const TermQuery& t) const { return t.field.empty() || t.field == leaves_[0].field; }
+  bool any_other_field(const std::vector<TermQuery>& ts) const {
+    for (const TermQuery& t : ts) if (!primary(t)) return true;
+    return false;
+  }
+  // does some TermQuery of the tree name a field other than the leaves' primary one?
+  bool names_other_field(const Query& q) const {
+    if (dynamic_cast<const MultiFieldQuery*>(&q)) return true;  // (served by the cross-field call whatever its fields)
+    if (auto* t = dynamic_cast<const TermQuery*>(&q)) return !primary(*t);
+    if (auto* b = dynamic_cast<const BooleanQuery*>(&q)) return any_other_field(b->must_queries) || any_other_field(b->should_queries) || any_other_field(b->must_not_queries);
+    if (auto* d = dynamic_cast<const DisjunctionMaxQuery*>(&q)) return any_other_field(d->disjuncts);
+    if (auto* bo = dynamic_cast<const BoostingQuery*>(&q)) return (bo->served_positive() && names_other_field(*bo->served_positive())) || any_other_field(bo->demoting_terms());
+    // every other type that holds TermQuery members: none of them is served across fields (cross_spec refuses them), and none may
+    // answer for the primary field's postings under another field's name
+    if (auto* p = dynamic_cast<const PhraseQuery*>(&q)) return any_other_field(p->terms);
+    if (auto* st = dynamic_cast<const SpanTermQuery*>(&q)) return !primary(st->term);
+    if (auto* sn = dynamic_cast<const SpanNearQuery*>(&q)) {
+      for (const SpanTermQuery& c : sn->clauses) if (!primary(c.term)) return true;
+      return false;
+    }
+    if (auto* pb = dynamic_cast<const PhraseBooleanQuery*>(&q)) {
+      for (const PhraseBooleanQuery::Required& r : pb->required)
+        if (r.phrase ? any_other_field(r.phrase->terms) : !primary(r.term)) return true;
+      return any_other_field(pb->must_not_queries);
+    }
+    if (auto* pd = dynamic_cast<const PhraseDisjunctionQuery*>(&q)) {
+      for (const PhraseDisjunctionQuery::Should& c : pd->should_queries)
+        if (c.phrase ? any_other_field(c.phrase->terms) : !primary(c.term)) return true;
+      return any_other_field(pd->must_not_queries);
+    }
+    if (auto* fq = dynamic_cast<const FilteredQuery*>(&q)) return fq->query && names_other_field(*fq->query);
+    if (auto* nb = dynamic_cast<const NestedBooleanQuery*>(&q)) {
+      for (const auto* list : {&nb->must_queries, &nb->should_queries, &nb->must_not_nested, &nb->filter_nested})
+        for (const std::unique_ptr<Query>& c : *list) if (c && names_other_field(*c)) return true;
+      return any_other_field(nb->must_not_queries);
+    }
+    return false;
+  }
+  // every path but search / search_many reads the primary field alone: such a tree is the caller's CPU path there
+  void refuse_other_fields(const Query& q) const {
+    if (names_other_field(q)) throw Error(RGPU_ERR_UNSUPPORTED, "a query that names a further field is served by search / search_many only");
+  }
+  // a flat tree over TermQuery / DisjunctionMaxQuery clauses as the call's groups; what the call cannot express is UnsupportedOperation
+  MultiFieldQuery cross_spec(const Query& q) const {
+    MultiFieldQuery m;
+    if (auto* mf = dynamic_cast<const MultiFieldQuery*>(&q)) m = *mf;
+    else if (auto* t = dynamic_cast<const TermQuery*>(&q)) m.groups.push_back(MultiFieldQuery::term(*t));
+    else if (auto* d = dynamic_cast<const DisjunctionMaxQuery*>(&q)) m.groups.push_back(MultiFieldQuery::dismax(d->disjuncts, d->tie_breaker_multiplier));
+    else if (auto* b = dynamic_cast<const BooleanQuery*>(&q)) {
+      if (b->should_required || b->nested_must) throw Error(RGPU_ERR_UNSUPPORTED, "nested boolean clauses are not served across fields by the GPU path");
+      if (!b->must_queries.empty() && !b->should_queries.empty())
+        throw Error(RGPU_ERR_UNSUPPORTED, "MUST and SHOULD clauses in one cross-field query (ReqOptScorer) are not served by the GPU path");
+      m.must = !b->must_queries.empty();
+      for (const TermQuery& t : m.must ? b->must_queries : b->should_queries) m.groups.push_back(MultiFieldQuery::term(t));
+      m.min_should_match = m.must ? 0 : b->min_should_match;
+      m.must_not_queries = b->must_not_queries;
+    } else {
+      throw Error(RGPU_ERR_UNSUPPORTED, "query type not served across fields by the GPU path");
+    }
+    if (m.groups.empty()) throw Error(RGPU_ERR_UNSUPPORTED, "a query of MUST_NOT clauses alone is not served across fields by the GPU path");
+    if (m.groups.size() > static_cast<size_t>(RGPU_MAX_FIELD_GROUPS)) throw Error(RGPU_ERR_UNSUPPORTED, "ten or more clauses are summed in heap order by the reference");
+    if (!m.must && m.min_should_match >= 2 && !m.must_not_queries.empty())
+      throw Error(RGPU_ERR_UNSUPPORTED, "MUST_NOT clauses beside min_should_match >= 2 are not served across fields by the GPU path");
+    auto known = [&](const TermQuery& t) {
+      if (primary(t)) return;
+      for (const LeafReader& l : leaves_) if (!l.extra(t.field)) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "no field '" + t.field + "' among the leaves' extra_fields");
+    };
+    for (const MultiFieldQuery::Group& g : m.groups) {
+      if (g.terms.size() > static_cast<size_t>(RGPU_MAX_GROUP_DISJUNCTS)) throw Error(RGPU_ERR_UNSUPPORTED, "ten or more disjuncts are summed in heap order by the reference");
+      if (g.dismax && !std::isfinite(g.tie_breaker_multiplier)) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "tie_breaker_multiplier is not finite");
+      for (const TermQuery& t : g.terms) known(t);
+    }
+    for (const TermQuery& t : m.must_not_queries) known(t);
+    return m;
+  }
+  // (weight, sim table) of a clause from ITS field's statistics in the statistics leaf (searcher.rs:306-363, 732-767): one cache per field
+  std::pair<float, int32_t> field_weight_of(const TermQuery& tq) {
+    if (primary(tq)) return weight_of(tq);
+    const ExtraField& x = *leaves_[stats_leaf_].extra(tq.field);
+    rgpu_term_state st;
+    TermStatistics ts;
+    const bool have = x.term_state(tq, &st);
+    ts.doc_freq = have ? st.doc_freq : 0;
+    ts.total_term_freq = have ? st.total_term_freq : 0;
+    CollectionStatistics cs = stats_;
+    cs.doc_count = x.doc_count;
+    cs.sum_total_term_freq = x.sum_total_term_freq;
+    cs.sum_doc_freq = x.sum_doc_freq;
+    const BM25SimWeight w = sim_.compute_weight(cs, &ts, 1, tq.boost);
+    auto at = field_sim_tables_.find(tq.field);
+    if (at == field_sim_tables_.end()) {
+      int32_t table = -1;
+      check(table = rgpu_sim_table_upload(ctx_, w.cache.data(), w.k1));
+      at = field_sim_tables_.emplace(tq.field, table).first;
+    }
+    return {w.weight, at->second};
+  }
+  std::vector<TopDocs> search_fields(const std::vector<MultiFieldQuery>& specs, size_t k) {
+    if (k > 128) throw Error(RGPU_ERR_UNSUPPORTED, "a cross-field query is served for k <= 128");
+    const int32_t nq = static_cast<int32_t>(specs.size());
+    std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
+    std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
+    for (size_t li = 0; li < leaves_.size(); ++li) {
+      const LeafReader& leaf = leaves_[li];
+      std::vector<rgpu_fields_query> qs;
+      std::vector<rgpu_field_group> gs;
+      std::vector<rgpu_field_clause> cs;
+      auto clause = [&](const TermQuery& t, bool scored) {
+        rgpu_field_clause c{};
+        const ExtraField* x = primary(t) ? nullptr : leaf.extra(t.field);
+        const bool have = x ? x->term_state(t, &c.state) : leaf.term_state(t, &c.state);
+        if (!have) { c.state = rgpu_term_state{}; c.state.skip_offset = -1; c.state.singleton_doc_id = -1; }
+        if (scored) { auto w = field_weight_of(t); c.weight = w.first; c.sim_table = w.second; }
+        c.field = x ? x->slot : 0;
+        cs.push_back(c);
+      };
+      for (const MultiFieldQuery& m : specs) {
+        rgpu_fields_query fq{};
+        fq.occur = m.must ? RGPU_OCCUR_MUST : RGPU_OCCUR_SHOULD;
+        fq.first_group = static_cast<int32_t>(gs.size());
+        fq.n_groups = static_cast<int32_t>(m.groups.size());
+        fq.min_should_match = m.must ? 0 : m.min_should_match;
+        for (const MultiFieldQuery::Group& g : m.groups) {
+          rgpu_field_group fg{};
+          fg.first_term = static_cast<int32_t>(cs.size());
+          fg.n_terms = static_cast<int32_t>(g.terms.size());
+          fg.kind = g.dismax ? RGPU_GROUP_DISMAX : RGPU_GROUP_TERM;
+          std::memcpy(&fg.tie_bits, &g.tie_breaker_multiplier, sizeof fg.tie_bits);
+          for (const TermQuery& t : g.terms) clause(t, true);
+          gs.push_back(fg);
+        }
+        fq.first_must_not = static_cast<int32_t>(cs.size());
+        fq.n_must_not = static_cast<int32_t>(m.must_not_queries.size());
+        for (const TermQuery& t : m.must_not_queries) clause(t, false);
+        qs.push_back(fq);
+      }
+      leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
+      leaf_totals[li].assign(static_cast<size_t>(nq), 0);
+      check(rgpu_search_fields_batch(leaf.segment, qs.data(), nq, gs.data(), static_cast<int32_t>(gs.size()), cs.data(), static_cast<int32_t>(cs.size()),
+                                     static_cast<int32_t>(k), leaf_hits[li].data(), leaf_totals[li].data()));
+    }
+    return merge_leaves(leaf_hits, leaf_totals, nq, k);
+  }
+
   std::pair<float, int32_t> weight_of(const TermQuery& tq) {
     // TermQuery::create_weight (term_query.rs:58-95) -> BM25Similarity::compute_weight
     const TermStatistics ts = term_statistics(tq);
@@ -1642,6 +1890,7 @@ class GpuIndexSearcher {
   // — one call per leaf instead of one dictionary lookup and one f64 log per clause. A batch that mixes id-named and
   // byte-named terms (or names terms the leaf cannot resolve that way) goes clause by clause through pack().
   void plan(const std::vector<const Query*>& queries, size_t li, std::vector<rgpu_query>* qs, std::vector<rgpu_query_term>* ts) {
+    for (const Query* q : queries) refuse_other_fields(*q);  // (search_many has routed those rows away; every other caller refuses them)
     const LeafReader& leaf = leaves_[li];
     std::vector<int32_t> ops, n_terms, n_not;
     std::vector<int64_t> ids, offs{0};
@@ -1737,6 +1986,7 @@ class GpuIndexSearcher {
     }
   }
   void pack(const Query& q0, const LeafReader& leaf, std::vector<rgpu_query>* qs, std::vector<rgpu_query_term>* ts) {
+    refuse_other_fields(q0);
     const BoostingQuery* bo = dynamic_cast<const BoostingQuery*>(&q0);
     const Query& q = bo ? *bo->served_positive() : q0;
     const std::vector<TermQuery>* clauses = nullptr;
@@ -1796,6 +2046,7 @@ class GpuIndexSearcher {
   size_t stats_leaf_ = 0;
   CollectionStatistics stats_;
   int32_t sim_table_ = -1;
+  std::map<std::string, int32_t> field_sim_tables_;  // a further field's norm cache: one table per field
   std::vector<rgpu_planner*> planners_;  // per leaf and naming scheme (2 * leaf + by-bytes), created on first use
   std::map<uint64_t, std::vector<rgpu_docset*>> filters_;  // CachedFilter::id -> one doc set per leaf
   struct FieldPoints {

@@ -13,8 +13,10 @@ namespace rucene {
 
 struct TermInfo {
   uint32_t dir_base; int32_t nblocks; int32_t df; uint64_t pn_base; uint64_t bs_base; bool norms;
+  uint8_t field = 0;    // the field slot the term was prepared under (rgpu_segment_attach_field); a bulk entry is of field 0
   uint32_t sketch = 0;  // 1 + index of the term's block-max sketch (kernels/search_term.hpp), 0: none
 };
+static_assert(sizeof(TermInfo) == 40, "the field slot sits in the padding behind `norms`: a table entry keeps its size");
 
 // doc_start_fp -> TermInfo of the prepared terms (host/flat_fp_map.hpp: two look-ups per clause per batch).
 // A bulk first touch (every term of a segment's dictionary: 152 k at 100 M docs) used to end with 152 k insertions into a table

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -50,6 +51,8 @@
 #include "kernels/count.hpp"
 #include "host/count_plan.hpp"
 #include "host/points_plan.hpp"
+#include "kernels/search_fields.hpp"
+#include "host/fields_plan.hpp"
 
 using namespace rgpu;
 
@@ -279,6 +282,7 @@ struct rgpu_ctx {
   DevVec<int64_t> phrase_redo;             // ... and the slots the 64-candidate kernel left for the one-candidate kernel (PHRASE_REDO_LIST_CAP)
   DevVec<unsigned long long> phrase_count;  // ... how many each query's conjunction produced
   DevVec<unsigned long long> count_rows;    // rgpu_count_batch: one counter per row
+  int fields_windows_per_item = 0;          // k_fields_windows: windows per work item; 0: sized per call (RGPU_FIELDS_WINDOWS_PER_ITEM in the environment: tests)
   int count_windows_per_item = 0;           // k_count_windows: windows per work item; 0: sized per call (RGPU_COUNT_WINDOWS_PER_ITEM in the environment: tests)
   // rgpu_search_phrase_or_batch: what the run-building kernels read in every pass of a call (the slot that staged the match stage's
   // plan may come round again before the last pass): the virtual queries' slot prefix, their PhraseRunDev, the bucket counts / offsets
@@ -371,7 +375,32 @@ struct rgpu_segment {
   DevVec<uint16_t> sketch;       // block-max sketches of long terms (SegView::sketch), TERM_SKETCH_K entries each
   size_t sketch_used = 0;        // sketches in use (TermInfo::sketch = 1 + index); dropped with the prepared terms
   DevVec<SketchJob> sketch_jobs;
+  // rgpu_segment_attach_field: the further indexed fields of the same Lucene segment (slot f = fields[f - 1]): what differs per
+  // field — norms and their mode, the freq layout, the width of a skip entry. The members above describe ONE field at a time:
+  // field 0, except inside a FieldScope (api/fields.hpp), which swaps a slot's values in under ctx->mu for the length of a
+  // preparation or of a k_score_terms launch, so that seg_view() and the prepare path read the field they work for.
+  struct Field {
+    uint8_t* d_norms = nullptr;
+    uint8_t* d_rank_to_norm = nullptr;
+    int32_t n_norm_ranks = 0;
+    int32_t index_options = 2;  // as given, RGPU_FIELD_STORES_PAYLOADS included
+    bool has_freqs = true, has_positions = false, has_offsets = false, has_payloads = false;
+    int skip_vals = 2;
+  };
+  std::vector<Field> fields;
+  int cur_field = 0;           // whose values the members above hold right now
+  bool any_positions = false;  // some field's skip entries carry position pointers: dir_pos keeps a cell per directory slot
+  int32_t index_options0 = 2;  // field 0's, as given at upload
 };
+// dir_pos grows with the other directory arrays when ANY field writes it (a field with positions passes it to the skip kernels, the
+// others pass null), so that the array always covers dir_used slots
+static inline bool keeps_dir_pos(const rgpu_segment* s) { return s->has_positions || s->any_positions; }
+// What every entry point but the cross-field ones relies on, made checkable: under the context's mutex and outside a FieldScope
+// (api/fields.hpp) the segment's members describe field 0. Asked where the field-0 paths meet: the implicit / explicit term
+// preparation (prepare_terms_locked) and the search proper (search_impl).
+static inline int32_t field0_view(const rgpu_segment* s) {
+  return s->cur_field == 0 ? RGPU_OK : fail(RGPU_ERR_ILLEGAL_STATE, "internal: a field view was left installed on the segment");
+}
 
 // ---- profiling helpers -----------------------------------------------------------------------------------------
 static int stat_slot(rgpu_ctx* c, const char* name) {
@@ -739,7 +768,7 @@ static int32_t prepare_norms_locked(rgpu_segment* seg, const rgpu_term_state* co
 // bytes of HBM the prepared-term store of a segment holds (what rgpu_segment_get_footprint reports as directory + block store +
 // posting-order norms)
 static size_t prepared_store_bytes(const rgpu_segment* seg) {
-  const size_t per_slot = 4 + 4 + 4 + 2 + 8 + (seg->has_positions ? 8 : 0);  // dir_last, dir_off, dir_row, dir_hdr, dir_bmax (, dir_pos)
+  const size_t per_slot = 4 + 4 + 4 + 2 + 8 + (keeps_dir_pos(seg) ? 8 : 0);  // dir_last, dir_off, dir_row, dir_hdr, dir_bmax (, dir_pos)
   return seg->dir_used * per_slot + seg->bstore_used + seg->pnorm_used + seg->sketch_used * (size_t)TERM_SKETCH_K * 2 + (seg->dir_used ? (seg->dir_used / 64 + 2) * 8 : 0);
 }
 // rgpu_config.prepared_budget_mib: a store over its ceiling is dropped as a whole BEFORE the arriving batch is planned — the
@@ -762,6 +791,7 @@ static int32_t enforce_prepared_budget(rgpu_segment* seg) {
 }
 static int32_t prepare_terms_locked(rgpu_segment* seg, const rgpu_term_state* const* sts, size_t n, bool with_norms = true,
                                     const DecodeSink* sink = nullptr) {
+  RGPU_TRY(field0_view(seg));
   int32_t rc = enforce_prepared_budget(seg);
   if (rc != RGPU_OK) return rc;
   rc = prepare_terms_attempt(seg, sts, n, false, sink);
@@ -864,7 +894,7 @@ static int32_t prepare_terms_attempt(rgpu_segment* seg, const rgpu_term_state* c
     HIP_TRY(seg->dir_hdr.reserve(need_slots, seg->dir_used, c->stream));
     HIP_TRY(seg->dir_bmax.reserve(need_slots, seg->dir_used, c->stream));
     HIP_TRY(seg->dir_sum.reserve(need_slots / 64 + 2, seg->dir_used / 64 + 2, c->stream));
-    if (seg->has_positions) HIP_TRY(seg->dir_pos.reserve(need_slots, seg->dir_used, c->stream));
+    if (keeps_dir_pos(seg)) HIP_TRY(seg->dir_pos.reserve(need_slots, seg->dir_used, c->stream));
     t_reserve = hc.lap();
     n_slots = need_slots - seg->dir_used;
     n_tiles = (int64_t)((n_slots + SCAN_TILE - 1) / SCAN_TILE);
@@ -878,7 +908,7 @@ static int32_t prepare_terms_attempt(rgpu_segment* seg, const rgpu_term_state* c
   };
 
   const int n_parts = rucene::host_threads();
-  bool bulk = none_prepared && n >= BULK_PLAN_MIN && n_parts > 1;
+  bool bulk = none_prepared && n >= BULK_PLAN_MIN && n_parts > 1 && seg->cur_field == 0;  // (a bulk entry does not say which field it is of)
   if (bulk) {
     std::vector<BulkPart> parts((size_t)n_parts), base((size_t)n_parts);  // a range's sums; what precedes a range
     PrepTerm* h_work = nullptr;
@@ -987,6 +1017,7 @@ static int32_t prepare_terms_attempt(rgpu_segment* seg, const rgpu_term_state* c
       if (!none_prepared) {
         if (const TermInfo* known = seg->prepared.find(st.doc_start_fp)) {
           if (known->df != st.doc_freq) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "term state changed doc_freq for a known doc_start_fp");
+          if (known->field != (uint8_t)seg->cur_field) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a term's doc_start_fp was prepared under another field of the segment");
           continue;
         }
       }
@@ -1113,7 +1144,7 @@ static int32_t prepare_terms_attempt(rgpu_segment* seg, const rgpu_term_state* c
   // The terms are filed as prepared WHILE the kernels run (the context's mutex is held: nobody looks before this call returns):
   // 152 k insertions into a table that is grown and first touched here — 2 to 6 ms of host time that used to follow the
   // 1.3 ms of kernels instead of hiding behind them. A failing call takes them back (remove_keys: a rebuild, the rare path).
-  const bool as_bulk = ascending && added.size() >= 4096;  // file order, no repeats: the array itself is the index (PreparedMap)
+  const bool as_bulk = ascending && added.size() >= 4096 && seg->cur_field == 0;  // file order, no repeats: the array itself is the index (PreparedMap)
   std::vector<int64_t> added_keys;
   if (as_bulk) {
     seg->prepared.adopt_sorted(std::move(added), (uint64_t)batch_bs, seg->d_norms == nullptr);
@@ -1122,7 +1153,9 @@ static int32_t prepare_terms_attempt(rgpu_segment* seg, const rgpu_term_state* c
     seg->prepared.reserve_more(added.size());
     for (size_t i = 0; i < added.size(); ++i) {
       if (i + AHEAD < added.size()) seg->prepared.prefetch(added[i + AHEAD].first);
-      seg->prepared.put(added[i].first, PreparedMap::expand(added[i], (uint64_t)batch_bs, seg->d_norms == nullptr));
+      TermInfo fresh = PreparedMap::expand(added[i], (uint64_t)batch_bs, seg->d_norms == nullptr);
+      fresh.field = (uint8_t)seg->cur_field;
+      seg->prepared.put(added[i].first, fresh);
       added_keys[i] = added[i].first;
     }
   }
@@ -1317,6 +1350,7 @@ extern "C" int32_t rgpu_init(int32_t device_ordinal, const rgpu_config* cfg, rgp
   if (const char* e = std::getenv("RGPU_TERM_MIN_ITEM_BLOCKS")) c->term_min_item_blocks = std::max(8, std::min(4096, std::atoi(e)));
   if (const char* e = std::getenv("RGPU_TERM_SPLIT")) c->term_split = std::max(1, std::min(64, std::atoi(e)));
   if (const char* e = std::getenv("RGPU_COUNT_WINDOWS_PER_ITEM")) c->count_windows_per_item = std::max(0, std::min(1 << 20, std::atoi(e)));
+  if (const char* e = std::getenv("RGPU_FIELDS_WINDOWS_PER_ITEM")) c->fields_windows_per_item = std::max(0, std::min(1 << 20, std::atoi(e)));
   if (const char* e = std::getenv("RGPU_COMM_FORCE_GATHER")) { if (std::atoi(e) != 0) c->cfg.comm_force_gather = 1; }
   std::snprintf(c->name, sizeof c->name, "%s (%s)", prop.name, prop.gcnArchName);
   // (the upload stream only exists when it is asked for: HIP multiplexes streams onto four hardware queues, and a fifth stream in the
@@ -1510,6 +1544,8 @@ extern "C" int32_t rgpu_segment_upload_field(rgpu_ctx* c, const uint8_t* doc_fil
   s->has_offsets = index_options >= 4;
   s->has_payloads = payloads;
   s->skip_vals = !s->has_positions ? 2 : payloads ? 6 : s->has_offsets ? 5 : 4;  // skip_writer.rs:261-289
+  s->any_positions = s->has_positions;
+  s->index_options0 = index_options | (payloads ? RGPU_FIELD_STORES_PAYLOADS : 0);
   const size_t pad = 8192;  // speculative row / tail loads may run past the last posting byte
   auto bail = [&](hipError_t e, const char* what) { rgpu_segment_free(s); return fail(RGPU_ERR_RUNTIME, std::string(what) + ": " + hipGetErrorString(e)); };
   hipError_t e;
@@ -1572,6 +1608,7 @@ extern "C" void rgpu_segment_free(rgpu_segment* s) {
   if (s->d_rank_to_norm) (void)hipFree(s->d_rank_to_norm);
   if (s->d_live) (void)hipFree(s->d_live);
   if (s->d_pos) (void)hipFree(s->d_pos);
+  for (auto& f : s->fields) { if (f.d_norms) (void)hipFree(f.d_norms); if (f.d_rank_to_norm) (void)hipFree(f.d_rank_to_norm); }
   s->dir_last.release(); s->dir_off.release(); s->dir_row.release(); s->dir_hdr.release(); s->dir_bmax.release(); s->dir_sum.release(); s->dir_pos.release(); s->pnorm.release(); s->bstore.release(); s->prep_scratch.release(); s->sketch.release(); s->sketch_jobs.release();
   for (void* b : s->bitmap_allocs) (void)hipFree(b);
   s->ctx->bitmap_bytes -= std::min(s->ctx->bitmap_bytes, s->bitmap_bytes);
@@ -2855,6 +2892,7 @@ static int32_t search_pass(rgpu_segment* seg, const rgpu_query* queries, int32_t
 static int32_t search_impl(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
                            int32_t n_terms_total, int32_t k, HitOut* hits_dev, int64_t* totals_dev, hipStream_t stream) {
   rgpu_ctx* c = seg->ctx;
+  RGPU_TRY(field0_view(seg));
   if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
   c->pass = rgpu_ctx::Pass{};
   if (k <= RGPU_PASS_K) return search_pass(seg, queries, n_queries, terms, n_terms_total, k, k, hits_dev, totals_dev, stream);
@@ -6152,4 +6190,5 @@ extern "C" int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phras
 #include "api/host_formats.hpp"  // rgpu_bm25_*, norms, live docs, rgpu_terms_*, segment / commit / compound / field infos
 #include "api/planner.hpp"       // rgpu_planner_create* / destroy / sim_table, rgpu_plan_batch_*, rgpu_plan_uniform_*
 #include "api/fused.hpp"         // term_batch_resident, term_batch_fast, search_uniform_locked, rgpu_planner_search_uniform_ids_device / _sharded
+#include "api/fields.hpp"        // rgpu_segment_attach_field / _prepare_field_terms / _get_field_info, rgpu_search_fields_batch
 #include "api/debug.hpp"         // rgpu_bm25_encode_norm; rgpu_debug_counters / rgpu_debug_trace of the variant builds

@@ -52,6 +52,37 @@ class BM25Similarity:
         return "BM25Similarity(k1: %s, b: %s)" % (self.k1, self.b)
 
 
+class ExtraField:
+    """A further indexed field of a leaf's segment (LeafReader.extra_fields): its number, norms, FieldReader statistics, index
+    options and term lookup - a flat table of term states indexed by term id, or the leaf's block-tree dictionary under the
+    field's number. `slot`: the field slot of the uploaded segment (rgpu_segment_attach_field), set by the searcher."""
+
+    def __init__(self, name, field_number, norms, doc_count, sum_total_term_freq, index_options=_lib.INDEX_OPTIONS_DOCS_AND_FREQS,
+                 has_payloads=False, terms=None, term_dictionary=None, sum_doc_freq=-1):
+        self.name, self.field_number, self.norms = str(name), int(field_number), norms
+        self.doc_count, self.sum_total_term_freq, self.sum_doc_freq = int(doc_count), int(sum_total_term_freq), int(sum_doc_freq)
+        self.index_options, self.has_payloads = int(index_options), bool(has_payloads)
+        self.terms = None if terms is None else np.ascontiguousarray(terms, dtype=TERM_STATE_DTYPE)
+        self.term_dictionary = term_dictionary
+        self._resolved = {}
+        self.slot = None
+
+    def term_state(self, term):
+        """None when the term is absent from this field of the leaf"""
+        if isinstance(term, bytes):
+            if term not in self._resolved:
+                if self.term_dictionary is None:
+                    raise RgpuError(-2, "field %r of this leaf has no term dictionary: query it by term id" % self.name)
+                states, found = self.term_dictionary.lookup(self.field_number, [term])
+                if len(self._resolved) >= LeafReader.RESOLVED_CACHE_TERMS:
+                    self._resolved.clear()
+                self._resolved[term] = states[0].copy() if found[0] else None
+            return self._resolved[term]
+        if self.terms is None or term < 0 or term >= self.terms.size or self.terms[term]["doc_freq"] <= 0:
+            return None
+        return self.terms[term]
+
+
 class LeafReader:
     """One segment as the searcher sees it (index/reader/leaf_reader.rs:62-182, reduced to what BM25 term and
     boolean queries read): postings file, norms, live docs, FieldReader statistics, and the term dictionary — either a
@@ -76,6 +107,15 @@ class LeafReader:
         self.term_positions = None  # per flat term id: TERM_POSITIONS_DTYPE records (synthetic segments)
         self._resolved = {}  # term bytes -> state or None
         self.segment = None  # rgpu_segment, created by the searcher
+        self.extra_fields = {}  # name -> ExtraField: the segment's further indexed fields a query may name (TermQuery(field=...))
+
+    def add_field(self, name, norms, terms, doc_count=None, sum_total_term_freq=0, index_options=_lib.INDEX_OPTIONS_DOCS_AND_FREQS,
+                  field_number=None):
+        """Declare a further field of a synthetic leaf: `terms` are the term states of ITS terms in the leaf's one .doc file."""
+        number = len(self.extra_fields) + 1 + self.field_number if field_number is None else field_number
+        self.extra_fields[name] = ExtraField(name, number, norms, self.max_doc if doc_count is None else doc_count, sum_total_term_freq,
+                                             index_options, terms=terms)
+        return self.extra_fields[name]
 
     @classmethod
     def from_synthetic(cls, seg, doc_base=None):
@@ -112,13 +152,17 @@ class LeafReader:
 
     @classmethod
     def from_index_files(cls, doc, tim, tip, nvm, nvd, max_doc, field_number=0, index_options=2, liv=None, del_count=-1,
-                         doc_base=0, field="body", other_fields=(), fnm=None, has_payloads=False):
+                         doc_base=0, field="body", other_fields=(), fnm=None, has_payloads=False, extra_fields=()):
         """A segment as Rucene wrote it (SegmentReader::open -> the per-format producers): `.doc` postings, `.tim`/`.tip`
         block-tree term dictionary, `.nvm`/`.nvd` norms, optional `.liv` live docs. With `fnm` (the segment's field infos
         file) the searched field is found by its name `field` and every other indexed field is declared from the file;
         otherwise pass `field_number`/`index_options` and `other_fields`: (number, index_options[, has_payloads]) of the
         segment's other indexed fields (the `.tim` summary lists them all).
-        Any indexed field can be searched; for phrases set `pos_bytes` (and, for a field with payloads / offsets, `pay_bytes`)."""
+        Any indexed field can be searched; for phrases set `pos_bytes` (and, for a field with payloads / offsets, `pay_bytes`).
+        extra_fields: names of further indexed fields (needs `fnm`) that queries may name beside `field`: each gets its norms from
+        `.nvm` / `.nvd` (none when the field omits them), its statistics from `.tim` and its term lookup from the same dictionary."""
+        if extra_fields and fnm is None:
+            raise RgpuError(-2, "extra_fields are found by name: pass the segment's .fnm")
         if fnm is not None:
             infos = _lib.field_infos_from_lucene60(fnm)
             mine = [fi for fi in infos if fi["name"] == field]
@@ -135,8 +179,20 @@ class LeafReader:
             raise RgpuError(-2, "field %d has no postings in this segment" % field_number)
         norms = _lib.norms_from_lucene53(nvm, nvd, field_number, max_doc)
         live = _lib.live_docs_from_lucene50(liv, max_doc, del_count) if liv is not None else None
-        return cls(doc, norms, max_doc, None, doc_base, live, stats["doc_count"], stats["sum_total_term_freq"],
+        leaf = cls(doc, norms, max_doc, None, doc_base, live, stats["doc_count"], stats["sum_total_term_freq"],
                    stats["sum_doc_freq"], field, td, field_number, index_options, has_payloads)
+        for name in extra_fields:
+            fi = [x for x in infos if x["name"] == name and x["index_options"] != 0]
+            if not fi or name == field:
+                raise RgpuError(-2, "no further indexed field named %r in this segment" % name)
+            fi = fi[0]
+            fstats = td.field_stats(fi["number"])
+            if fstats is None:   # the field has no postings in this segment: every term of it is absent here
+                fstats = dict(doc_count=0, sum_total_term_freq=0, sum_doc_freq=0)
+            fnorms = None if fi.get("omit_norms") else _lib.norms_from_lucene53(nvm, nvd, fi["number"], max_doc)
+            leaf.extra_fields[name] = ExtraField(name, fi["number"], fnorms, fstats["doc_count"], fstats["sum_total_term_freq"], fi["index_options"],
+                                                 bool(fi["has_payloads"]), term_dictionary=td, sum_doc_freq=fstats["sum_doc_freq"])
+        return leaf
 
     def resolve(self, terms):
         """One batched dictionary lookup for the byte terms not seen before (seek_exact + term_state each)."""
@@ -171,12 +227,12 @@ def _base36(v):
             return out
 
 
-def open_directory(path, field="body"):
+def open_directory(path, field="body", extra_fields=()):
     """StandardDirectoryReader::open for the slice this path needs: the newest commit point `segments_N` names the
     segments; per segment `.si` gives max_doc, `.fnm` the field's number and index options, `_Lucene50_0.{doc,tim,tip}` the
     postings and term dictionary, `.nvm/.nvd` the norms, `_<delgen>.liv` the live docs (index/reader/directory_reader.rs:
     90-140; segment_reader.rs open; file names per codec/segment_infos/mod.rs:60-114). Returns the LeafReaders with
-    cumulative doc bases, ready for GpuIndexSearcher. A compound segment's files are taken out of its `.cfs` through the
+    cumulative doc bases, ready for GpuIndexSearcher; extra_fields: further indexed fields by name (LeafReader.extra_fields). A compound segment's files are taken out of its `.cfs` through the
     `.cfe` entry table (codec/compound.rs); its `.si` and `.liv` stay outside, as Rucene writes them."""
     import os
     gens = [int(f[len("segments_"):], 36) for f in os.listdir(path) if f.startswith("segments_")]
@@ -211,7 +267,7 @@ def open_directory(path, field="body"):
         leaf = LeafReader.from_index_files(np.frombuffer(part("_Lucene50_0.doc"), dtype=np.uint8), part("_Lucene50_0.tim"),
                                            part("_Lucene50_0.tip"), part(".nvm"), part(".nvd"), info["max_doc"],
                                            liv=liv, del_count=seg["del_count"] if liv is not None else -1, doc_base=doc_base,
-                                           field=field, fnm=fnm)
+                                           field=field, fnm=fnm, extra_fields=extra_fields)
         leaves.append(leaf)
         doc_base += info["max_doc"]
     return leaves
@@ -225,15 +281,18 @@ def _i32(op):
 class TermQuery:
     """term: bytes (resolved through each leaf's term dictionary) or an int term id (synthetic flat term table)."""
 
-    def __init__(self, term, boost=1.0):
+    def __init__(self, term, boost=1.0, field=None):
+        """field: the name of the indexed field the term lives in; None = the leaf's primary field (LeafReader.field). Another
+        field must be one of the leaves' extra_fields: such clauses are served by rgpu_search_fields_batch."""
         self.term = bytes(term) if isinstance(term, (bytes, bytearray, memoryview)) else int(term)
         self.boost = float(boost)
+        self.field = None if field is None else str(field)
 
     def extract_terms(self):
         return [self]
 
     def __str__(self):
-        return "TermQuery(field: body, term: %r, boost: %s)" % (self.term, self.boost)
+        return "TermQuery(field: %s, term: %r, boost: %s)" % (self.field or "body", self.term, self.boost)
 
 
 class PhraseQuery:
@@ -509,8 +568,11 @@ class BooleanQuery:
         # gets one from the reference's build(); here the searcher supplies it when it peels such a query, the tree stays as given)
         # (a span clause builds too; no tree with one is served: GpuIndexSearcher.search_batch refuses it as UnsupportedOperation)
         spans = (SpanTermQuery, SpanNearQuery)
-        if any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, PointRangeQuery, MatchAllDocsQuery) + spans) for q in list(musts)) or \
-                any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery) + spans) for q in list(shoulds)) or \
+        # (a DisjunctionMaxQuery clause builds: the multi-field query "(title:a | body:a) (title:b | body:b)"; it is served when its
+        # terms name a further field of the leaves - GpuIndexSearcher routes such trees to rgpu_search_fields_batch - and is
+        # UnsupportedOperation when searched otherwise)
+        if any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, PointRangeQuery, MatchAllDocsQuery, DisjunctionMaxQuery) + spans) for q in list(musts)) or \
+                any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, DisjunctionMaxQuery) + spans) for q in list(shoulds)) or \
                 any(not isinstance(q, (TermQuery, BooleanQuery, PhraseQuery, CachedFilter, PointRangeQuery) + spans) for q in list(must_nots) + list(filters)):
             raise RgpuError(-5, "only term, phrase and boolean clauses are known to this mirror")
         return BooleanQuery(list(musts), list(shoulds), msm, list(must_nots), list(filters))
@@ -568,7 +630,7 @@ class BooleanQuery:
                 if isinstance(q, TermQuery):
                     out.append(q)
                     continue
-                if not q.is_flat() or q.must_not_queries or q.filter_queries:
+                if not isinstance(q, BooleanQuery) or not q.is_flat() or q.must_not_queries or q.filter_queries:
                     return None
                 if want_must and q.must_queries and not q.should_queries:
                     out.extend(q.must_queries)
@@ -602,7 +664,7 @@ class BooleanQuery:
         if len(nested) != 1:
             return None
         d = nested[0]
-        if (not d.is_flat() or d.must_queries or d.must_not_queries or d.filter_queries or d.min_should_match > 1
+        if (not isinstance(d, BooleanQuery) or not d.is_flat() or d.must_queries or d.must_not_queries or d.filter_queries or d.min_should_match > 1
                 or not 1 <= len(d.should_queries) <= 9):
             return None
         return d
@@ -622,7 +684,8 @@ class BooleanQuery:
         if len(nested) != 1 or nested[0] > 1:
             return None
         d = self.should_queries[nested[0]]
-        if not d.is_flat() or d.must_queries or d.must_not_queries or d.filter_queries or d.min_should_match > 1 or not d.should_queries:
+        if (not isinstance(d, BooleanQuery) or not d.is_flat() or d.must_queries or d.must_not_queries or d.filter_queries or d.min_should_match > 1
+                or not d.should_queries):
             return None
         rest = [q for q in self.should_queries if q is not d]
         if len(d.should_queries) + len(rest) >= 10:
@@ -640,7 +703,7 @@ class BooleanQuery:
         if len(nested) != 1:
             return None
         c = nested[0]
-        if not c.is_flat() or c.should_queries or c.must_not_queries or c.filter_queries or len(c.must_queries) < 2:
+        if not isinstance(c, BooleanQuery) or not c.is_flat() or c.should_queries or c.must_not_queries or c.filter_queries or len(c.must_queries) < 2:
             return None
         return c
 
@@ -801,6 +864,9 @@ class GpuIndexSearcher:
                                             leaf.index_options | (_lib.FIELD_STORES_PAYLOADS if getattr(leaf, "has_payloads", False) else 0))
                 if getattr(leaf, "pay_bytes", None) is not None:
                     leaf.segment.attach_payloads(leaf.pay_bytes)   # Lucene50PostingsReader::open checks the third file too
+            for xf in getattr(leaf, "extra_fields", {}).values():   # the segment's further fields: slots 1.. in the order given
+                if xf.slot is None:
+                    xf.slot = leaf.segment.attach_field(xf.norms, xf.index_options | (_lib.FIELD_STORES_PAYLOADS if xf.has_payloads else 0))
         # searcher.rs:306-363: statistics of the first leaf with the largest max_doc stand in for the index
         self._stats_leaf = 0
         for i, leaf in enumerate(self.leaves):
@@ -810,6 +876,7 @@ class GpuIndexSearcher:
         self.collection_statistics = CollectionStatistics(sl.field, sl.doc_base, self.max_doc(), sl.doc_count,
                                                           sl.sum_total_term_freq, sl.sum_doc_freq)
         self._weights = {}
+        self._field_weights = {}  # (field name, term, boost) -> (weight, sim table): a further field's own statistics
         self._planners = {}       # per leaf: the native batch planner
         self._stats_terms = None  # override_statistics: another leaf's term table / dictionary
         self._masks = {}          # (filter sets, exclude sets) key -> (the CachedFilters, one combined DocSet per leaf)
@@ -841,9 +908,131 @@ class GpuIndexSearcher:
             self._weights[key] = (w, self.ctx.sim_table(cache, self.similarity.k1))
         return self._weights[key]
 
+    # ---- cross-field queries (rgpu_search_fields_batch) ---------------------------------------------------------------------------
+    def _primary(self, tq):
+        return tq.field is None or tq.field == self.leaves[0].field
+
+    def _names_other_field(self, query):
+        """Does some TermQuery of the tree name a field other than the leaves' primary one?"""
+        if isinstance(query, TermQuery):
+            return not self._primary(query)
+        if isinstance(query, DisjunctionMaxQuery):
+            return any(self._names_other_field(q) for q in query.disjuncts)
+        if isinstance(query, BooleanQuery):
+            return any(self._names_other_field(q) for q in list(query.must_queries) + list(query.should_queries) + list(query.must_not_queries) +
+                       list(query.filter_queries) if not isinstance(q, CachedFilter))
+        if isinstance(query, BoostingQuery):
+            return self._names_other_field(query.positive) or self._names_other_field(query.negative)
+        if isinstance(query, FilterQuery):
+            return self._names_other_field(query.query)
+        return False
+
+    def _refuse_other_fields(self, query):
+        """Only search_batch / search route a tree that names a further field (to rgpu_search_fields_batch). Every other path -
+        count, count_batch, rescore_batch, cache_filter, the packers - reads the primary field alone and hands such a tree to the
+        caller's CPU path instead of answering for the wrong field."""
+        if self._names_other_field(query):
+            raise RgpuError(-5, "a query that names a further field is served by search_batch / search only")
+
+    def _field_weight(self, tq):
+        """(weight, sim table) of a clause from ITS field's statistics: idf from the term's doc_freq in that field of the statistics
+        leaf, the norm cache from that field's doc_count and sum_total_term_freq there (searcher.rs:306-363, 732-767)"""
+        if self._primary(tq):
+            return self._weight(tq.term, tq.boost)
+        key = (tq.field, tq.term, tq.boost)
+        if key not in self._field_weights:
+            if len(self._field_weights) >= (1 << 20):
+                self._field_weights.clear()
+            sl = self.leaves[self._stats_leaf]
+            if tq.field not in sl.extra_fields:
+                raise RgpuError(-2, "no field %r among the leaves' extra_fields" % tq.field)
+            xf = sl.extra_fields[tq.field]
+            st = xf.term_state(tq.term)
+            stats = CollectionStatistics(tq.field, sl.doc_base, self.max_doc(), xf.doc_count, xf.sum_total_term_freq, xf.sum_doc_freq)
+            w, cache = self.similarity.compute_weight(stats, [0 if st is None else int(st["doc_freq"])], tq.boost)
+            self._field_weights[key] = (w, self.ctx.sim_table(cache, self.similarity.k1))
+        return self._field_weights[key]
+
+    def _cross_spec(self, query):
+        """A flat tree over TermQuery / DisjunctionMaxQuery-of-TermQuery clauses -> (occur, [(kind, tie bits, [TermQuery])], msm,
+        [MUST_NOT TermQuery]); anything rgpu_search_fields_batch cannot express is UnsupportedOperation (the caller's CPU path)"""
+        def group(q):
+            if isinstance(q, TermQuery):
+                return (_lib.GROUP_TERM, 0, [q])
+            if isinstance(q, DisjunctionMaxQuery) and all(isinstance(d, TermQuery) for d in q.disjuncts):
+                if not np.isfinite(np.float32(q.tie_breaker_multiplier)):
+                    raise RgpuError(-2, "tie_breaker_multiplier is not finite")
+                if len(q.disjuncts) > _lib.MAX_GROUP_DISJUNCTS:
+                    raise RgpuError(-5, "ten or more disjuncts are summed in heap order by the reference")
+                return (_lib.GROUP_DISMAX, int(np.float32(q.tie_breaker_multiplier).view(np.uint32)), list(q.disjuncts))
+            raise RgpuError(-5, "a cross-field query is served over TermQuery and DisjunctionMaxQuery-of-TermQuery clauses")
+        def known(spec):
+            for tq in [t for g in spec[1] for t in g[2]] + spec[3]:
+                if not self._primary(tq) and any(tq.field not in leaf.extra_fields for leaf in self.leaves):
+                    raise RgpuError(-2, "no field %r among the leaves' extra_fields" % tq.field)
+            return spec
+        if isinstance(query, (TermQuery, DisjunctionMaxQuery)):
+            return known((_lib.OCCUR_SHOULD, [group(query)], 0, []))
+        if not isinstance(query, BooleanQuery):
+            raise RgpuError(-5, "query type not served across fields by the GPU path: %r" % (query,))
+        if query.filter_queries:
+            raise RgpuError(-5, "FILTER clauses are not served across fields by the GPU path")
+        if query.must_queries and query.should_queries:
+            raise RgpuError(-5, "MUST and SHOULD clauses in one cross-field query (ReqOptScorer) are not served by the GPU path")
+        if not all(isinstance(q, TermQuery) for q in query.must_not_queries):
+            raise RgpuError(-5, "a cross-field query's MUST_NOT clauses are TermQuerys")
+        positive = list(query.must_queries) or list(query.should_queries)
+        if not positive:
+            raise RgpuError(-5, "a query of MUST_NOT clauses alone is not served across fields by the GPU path")
+        if len(positive) > _lib.MAX_FIELD_GROUPS:
+            raise RgpuError(-5, "ten or more clauses are summed in heap order by the reference")
+        occur = _lib.OCCUR_MUST if query.must_queries else _lib.OCCUR_SHOULD
+        msm = 0 if query.must_queries else int(query.min_should_match)
+        if occur == _lib.OCCUR_SHOULD and msm >= 2 and query.must_not_queries:
+            raise RgpuError(-5, "MUST_NOT clauses beside min_should_match >= 2 are not served across fields by the GPU path")
+        groups = [group(q) for q in positive]
+        if sum(len(g[2]) for g in groups) + len(query.must_not_queries) > _lib.MAX_FIELDS_QUERY_CLAUSES:
+            raise RgpuError(-5, "too many clauses in one cross-field query")
+        return known((occur, groups, msm, list(query.must_not_queries)))
+
+    def pack_fields(self, specs, leaf):
+        """_cross_spec rows -> (rgpu_fields_query[], rgpu_field_group[], rgpu_field_clause[]) for one leaf"""
+        Q, G, C = [], [], []
+
+        def clause(tq, scored=True):
+            row = np.zeros(1, _lib.FIELD_CLAUSE_DTYPE)[0]
+            xf = None if self._primary(tq) else leaf.extra_fields[tq.field]
+            st = leaf.term_state(tq.term) if xf is None else xf.term_state(tq.term)
+            if st is not None:
+                row["state"] = st
+            if scored:
+                row["weight"], row["sim_table"] = self._field_weight(tq)
+            row["field"] = 0 if xf is None else xf.slot
+            C.append(row)
+        for occur, groups, msm, nots in specs:
+            g0 = len(G)
+            for kind, tie_bits, tqs in groups:
+                c0 = len(C)
+                for tq in tqs:
+                    clause(tq)
+                G.append((c0, len(tqs), tie_bits, kind))
+            n0 = len(C)
+            for tq in nots:
+                clause(tq, scored=False)
+            Q.append((occur, g0, len(G) - g0, msm, n0, len(nots)))
+        return np.array(Q, _lib.FIELDS_QUERY_DTYPE), np.array(G, _lib.FIELD_GROUP_DTYPE), np.array(C, _lib.FIELD_CLAUSE_DTYPE)
+
+    def _cross_rows(self, specs, k):
+        """(hits, totals) of _cross_spec rows (rows that name a further field), merged over the leaves"""
+        if k > 128:
+            raise RgpuError(-5, "a cross-field query is served for k <= 128")
+        per_leaf = [leaf.segment.search_fields_batch(*self.pack_fields(specs, leaf), k) for leaf in self.leaves]
+        return per_leaf[0] if len(per_leaf) == 1 else self._merge_leaves(per_leaf, len(specs), k)
+
     def _flatten(self, query):
         """-> (op, required / scored clauses, optional SHOULD clauses beside MUST ones, MUST_NOT clauses — a BoostingQuery's demoting
         clauses behind them: _boosting_fields)"""
+        self._refuse_other_fields(query)
         if isinstance(query, TermQuery):
             return OP_TERM, [query], [], []
         if isinstance(query, PointRangeQuery) or (isinstance(query, BooleanQuery) and any(
@@ -869,6 +1058,9 @@ class GpuIndexSearcher:
                 raise RgpuError(-5, "a DisjunctionMaxQuery is served by the GPU path when every disjunct is a TermQuery")
             return OP_DISMAX, list(query.disjuncts), [], []   # (the tie-breaker rides in n_must_not: _dismax_fields)
         if isinstance(query, BooleanQuery):
+            if any(isinstance(q, DisjunctionMaxQuery) for q in list(query.must_queries) + list(query.should_queries) + list(query.must_not_queries) +
+                   list(query.filter_queries)):
+                raise RgpuError(-5, "a DisjunctionMaxQuery clause inside a BooleanQuery is served across fields only (TermQuery(field=...))")
             query = query.normalized()
             if not query.is_flat():
                 first = query.nested_disjunction_first()
@@ -1080,6 +1272,7 @@ class GpuIndexSearcher:
         if any(_holds_span(q) for q in rescore_queries):
             raise RgpuError(-5, "rescoring with a span query is not served by the GPU path")
         for q in rescore_queries:   # refused before any leaf is touched (a leaf that lacks the term would serve the row, the next one not)
+            self._refuse_other_fields(q)
             if isinstance(q, PhraseQuery) and q.slop > 0 and len(set(q.terms)) < len(q.terms):
                 raise RgpuError(-5, "phrase rescoring: a sloppy phrase that names a term twice is not served")
         out = np.ascontiguousarray(hits, dtype=_lib.HIT_DTYPE).copy()
@@ -1341,6 +1534,7 @@ class GpuIndexSearcher:
         only then is its doc set built; build=False stops short of that (the sets are then the queries themselves) — search_batch
         runs it over the whole batch first, so a refused row launches nothing. min_should_match stays the query's own: "+range #a b"
         has 0 (it had a MUST clause), where build() would give the rest "#a b" 1."""
+        self._refuse_other_fields(query)
         if isinstance(query, FilterQuery):
             inner, (f, x) = self._peel(query.query, build)
             if isinstance(inner, PhraseQuery) or (isinstance(inner, BooleanQuery) and inner.has_phrases()):
@@ -1474,7 +1668,24 @@ class GpuIndexSearcher:
         (rgpu_search_span_near_batch; with unordered_spans the unordered ones through rgpu_search_span_unordered_batch; any other span
         query is UnsupportedOperation): one call per kind and leaf, rows keep their order. Rows with doc-set clauses
         (CachedFilter under FILTER / MUST_NOT, FilterQuery) are grouped by their combination of sets and searched masked
-        (rgpu_search_batch_masked; with filtered_phrases the phrase kinds through their masked calls), one call per group, kind and leaf."""
+        (rgpu_search_batch_masked; with filtered_phrases the phrase kinds through their masked calls), one call per group, kind and leaf.
+        Rows that name a further field of the leaves (TermQuery(field=...)) go to rgpu_search_fields_batch, which serves k <= 128: a
+        batch that holds such a row is UnsupportedOperation as a whole for k > 128, its primary-field rows included (they are served
+        up to k = 1024 in a batch of their own) - a batch has one k, and a refused batch launches nothing."""
+        # rows that name a further field of the leaves (TermQuery(field=...)) go to rgpu_search_fields_batch; a batch without one
+        # goes exactly where it went
+        cross = [i for i, q in enumerate(queries) if self._names_other_field(q)]
+        if cross:
+            crossed = set(cross)
+            rest = [i for i in range(len(queries)) if i not in crossed]
+            specs = [self._cross_spec(queries[i]) for i in cross]   # refused before any leaf is touched
+            if k > 128:
+                raise RgpuError(-5, "a cross-field query is served for k <= 128")
+            hits, totals = np.zeros((len(queries), k), dtype=_lib.HIT_DTYPE), np.zeros(len(queries), dtype=np.int64)
+            if rest:
+                hits[rest], totals[rest] = self.search_batch([queries[i] for i in rest], k)
+            hits[cross], totals[cross] = self._cross_rows(specs, k)
+            return hits, totals
         for q in queries:   # refused before any leaf is touched and before any range's set is built
             _refuse_unserved_spans(q, getattr(self, "unordered_spans", False))
             self._peel(q, build=False)
@@ -1614,7 +1825,7 @@ class GpuIndexSearcher:
         refuses (UnsupportedOperation: phrases, spans, nested trees) goes to cpu_count_fallback(query) when that is set."""
         if isinstance(query, MatchAllDocsQuery):
             return sum(self._leaf_num_docs(leaf) for leaf in self.leaves)
-        if isinstance(query, TermQuery) and all(leaf.live_docs is None for leaf in self.leaves):
+        if isinstance(query, TermQuery) and self._primary(query) and all(leaf.live_docs is None for leaf in self.leaves):
             states = [leaf.term_state(query.term) for leaf in self.leaves]
             return sum(int(st["doc_freq"]) for st in states if st is not None)
         try:
@@ -1631,6 +1842,7 @@ class GpuIndexSearcher:
         clauses say: the live cardinality of its mask (rgpu_docset_head with n = 0). Whatever search_batch refuses, and phrases and
         spans in any position, are UnsupportedOperation."""
         for q in queries:   # refused before any leaf is touched and before any range's set is built
+            self._refuse_other_fields(q)
             if _holds_span(q) or isinstance(q, (PhraseQuery, SpanNearQuery)) or (isinstance(q, BooleanQuery) and q.has_phrases()):
                 raise RgpuError(-5, "a count is served by the GPU path for term, boolean, dismax and boosting queries")
             rest, _ = self._peel(q, build=False)

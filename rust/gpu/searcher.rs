@@ -29,7 +29,7 @@ use core::doc::Term;
 use core::index::reader::{IndexReader, LeafReader, LeafReaderContext};
 use core::search::collector::{SearchCollector, TopDocsCollector};
 use core::search::query::spans::{SpanNearQuery, SpanQueryEnum};
-use core::search::query::{BooleanQuery, PhraseQuery, Query, TermQuery};
+use core::search::query::{BooleanQuery, DisjunctionMaxQuery, PhraseQuery, Query, TermQuery};
 use core::search::searcher::{DefaultIndexSearcher, IndexSearcher, SearchPlanBuilder};
 use core::search::similarity::SimilarityProducer;
 use core::search::statistics::{CollectionStatistics, TermStatistics};
@@ -131,11 +131,26 @@ impl<'q> FlatQuery<'q> {
     }
 }
 
+/// One group of a cross-field query (rgpu_field_group): a TermQuery, or a DisjunctionMaxQuery of TermQuery disjuncts in any fields
+struct CrossGroup<'q> {
+    dismax: bool,
+    tie: f32,
+    terms: Vec<&'q TermQuery>,
+}
+/// A BooleanQuery of all-SHOULD or all-MUST groups whose terms live in the uploaded field or in attached ones (rgpu_fields_query)
+struct CrossQuery<'q> {
+    must: bool,
+    msm: i32,
+    groups: Vec<CrossGroup<'q>>,
+    must_not: Vec<&'q TermQuery>,
+}
+
 pub struct GpuIndexSearcher<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: SimilarityProducer<C>> {
     cpu: DefaultIndexSearcher<C, R, IR, SP>, // statistics (searcher.rs:306-363, :732-767) and the fallback for everything else
     ctx: *mut RgpuCtx,
-    field: String,                            // the uploaded field (one rgpu_segment per (leaf, field); more fields: a map)
+    field: String,                            // the uploaded field: field 0 of every rgpu_segment (further fields: extra_fields)
     leaves: Vec<GpuLeaf>,                     // by LeafReaderContext::ord
+    extra_fields: Vec<(String, Vec<i32>)>,    // attach_field: further fields of the same segments -> their slot per leaf (by ord)
     sim_tables: Mutex<HashMap<u32, i32>>,     // avgdl bits -> rgpu_sim_table_upload handle (k1, b fixed above)
     next_limit: i32,                          // DefaultIndexSearcher::next_limit (searcher.rs:285): None -> 0, Some(0) -> RGPU_NEXT_LIMIT_ZERO
     /// Fold ONE level of nested BooleanQuery into its parent (see flatten). Off by default, as in the C++ and Python mirrors
@@ -192,7 +207,127 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             leaves.push(GpuLeaf { seg, has_positions: pos.is_some() });
         }
         let next_limit = match next_limit { None => 0, Some(0) => RGPU_NEXT_LIMIT_ZERO, Some(n) => n.min(i32::max_value() as usize) as i32 };
-        Ok(GpuIndexSearcher { cpu, ctx, field: field.to_string(), leaves, sim_tables: Mutex::new(HashMap::new()), next_limit, allow_flatten, filtered_phrases: false, required_sets: false, unordered_spans: false })
+        Ok(GpuIndexSearcher { cpu, ctx, field: field.to_string(), leaves, extra_fields: Vec::new(), sim_tables: Mutex::new(HashMap::new()), next_limit, allow_flatten, filtered_phrases: false, required_sets: false, unordered_spans: false })
+    }
+
+    /// A further indexed field of the same segments (rgpu_segment_attach_field): `norms(leaf)` hands over the field's norms as one
+    /// byte per doc (None: the field omits them); `index_options` as for open(). Queries that name it - "title:gpu | body:gpu",
+    /// "(title:a | body:a) (title:b | body:b)" - are then served by try_fields; every other path of this shim keeps reading the
+    /// uploaded field alone (flatten's term_of drops any other field: those trees stay the CPU searcher's).
+    pub fn attach_field<F>(&mut self, field: &str, index_options: i32, norms: F) -> Result<()>
+    where
+        F: Fn(&LeafReaderContext<'_, C>) -> Result<Option<&[u8]>>,
+    {
+        let mut slots = vec![0i32; self.leaves.len()];
+        for leaf in self.cpu.reader().leaves() {
+            let bytes = norms(&leaf)?;
+            let mut slot: i32 = -1;
+            check(unsafe { rgpu_segment_attach_field(self.leaves[leaf.ord].seg, bytes.map_or(std::ptr::null(), |n| n.as_ptr()), index_options, &mut slot) }, self.ctx)?;
+            slots[leaf.ord] = slot;
+        }
+        self.extra_fields.push((field.to_string(), slots));
+        Ok(())
+    }
+
+    /// The field slot of `field` in leaf `ord`: 0 for the uploaded field, an attached field's slot, None for any other field
+    fn slot_of(&self, field: &str, ord: usize) -> Option<i32> {
+        if field == self.field { return Some(0); }
+        self.extra_fields.iter().find(|(name, _)| name == field).map(|(_, slots)| slots[ord])
+    }
+
+    /// Trees rgpu_search_fields_batch serves, when they name an attached field: a TermQuery, a DisjunctionMaxQuery of 1..=9 TermQuery
+    /// disjuncts, a BooleanQuery of 1..=9 such clauses that are all MUST or all SHOULD, with MUST_NOT TermQuery clauses. None = not
+    /// this call's: a tree over the uploaded field alone goes the way it went (flatten), FILTER clauses, MUST beside SHOULD
+    /// (ReqOptScorer), ten or more groups or disjuncts (the heap-order arm), MUST_NOT beside min_should_match >= 2 and a field that
+    /// is not attached stay the CPU searcher's.
+    fn cross_spec<'q>(&self, query: &'q dyn Query<C>) -> Option<CrossQuery<'q>> {
+        let known = |t: &TermQuery| self.slot_of(&t.term.field, 0).is_some();
+        let group = |q: &'q dyn Query<C>| -> Option<CrossGroup<'q>> {
+            if let Some(t) = q.as_any().downcast_ref::<TermQuery>() {
+                return if known(t) { Some(CrossGroup { dismax: false, tie: 0.0, terms: vec![t] }) } else { None };
+            }
+            let d = q.as_any().downcast_ref::<DisjunctionMaxQuery<C>>()?;
+            if d.disjuncts.is_empty() || d.disjuncts.len() > RGPU_MAX_GROUP_DISJUNCTS as usize || !d.tie_breaker_multiplier.is_finite() { return None; }
+            let mut terms = Vec::with_capacity(d.disjuncts.len());
+            for c in &d.disjuncts {
+                let t = c.as_any().downcast_ref::<TermQuery>()?;
+                if !known(t) { return None; }
+                terms.push(t);
+            }
+            Some(CrossGroup { dismax: true, tie: d.tie_breaker_multiplier, terms })
+        };
+        let spec = if let Some(b) = query.as_any().downcast_ref::<BooleanQuery<C>>() {
+            let (must, should, filter, must_not, msm) = b.clauses();
+            if !filter.is_empty() || (!must.is_empty() && !should.is_empty()) || (must.is_empty() && should.is_empty()) { return None; }
+            let positive = if must.is_empty() { should } else { must };
+            if positive.len() > RGPU_MAX_FIELD_GROUPS as usize { return None; }
+            let mut groups = Vec::with_capacity(positive.len());
+            for q in positive { groups.push(group(q.as_ref())?); }
+            let mut prohibited = Vec::with_capacity(must_not.len());
+            for q in must_not {
+                let t = q.as_any().downcast_ref::<TermQuery>()?;
+                if !known(t) { return None; }
+                prohibited.push(t);
+            }
+            if must.is_empty() && msm >= 2 && !prohibited.is_empty() { return None; }
+            CrossQuery { must: !must.is_empty(), msm: if must.is_empty() { msm } else { 0 }, groups, must_not: prohibited }
+        } else {
+            CrossQuery { must: false, msm: 0, groups: vec![group(query)?], must_not: vec![] }
+        };
+        let n: usize = spec.groups.iter().map(|g| g.terms.len()).sum::<usize>() + spec.must_not.len();
+        if n > RGPU_MAX_FIELDS_QUERY_CLAUSES as usize { return None; }
+        // a tree over the uploaded field alone is flatten's, as it has been
+        let other = spec.groups.iter().flat_map(|g| g.terms.iter()).chain(spec.must_not.iter()).any(|t| t.term.field != self.field);
+        if other { Some(spec) } else { None }
+    }
+
+    /// weight = idf x boost of a clause and the norm cache of ITS field: collections_statistics(term.field), the searcher's
+    /// term_statistics (df of the largest leaf), BM25Similarity::compute_weight - weight_of with the field taken from the term
+    fn field_weight_of(&self, term: &Term, boost: f32) -> Result<(f32, i32)> {
+        let coll: &CollectionStatistics = self.cpu.collections_statistics(&term.field).ok_or_else(|| Error::from(ErrorKind::IllegalState("no statistics".into())))?;
+        let s: TermStatistics = self.cpu.term_statistics(term)?;
+        let dfs = [s.doc_freq];
+        let mut w = 0f32;
+        check(unsafe { rgpu_bm25_compute_weight(BM25_K1, BM25_B, coll.max_doc, coll.doc_count, coll.sum_total_term_freq, dfs.as_ptr(), 1, boost,
+                                                &mut w, std::ptr::null_mut(), std::ptr::null_mut()) }, self.ctx)?;
+        Ok((w, self.sim_table(coll)?))
+    }
+
+    /// A cross-field tree through rgpu_search_fields_batch, one call per leaf: each clause carries its field's slot in that leaf,
+    /// its own field's weight and norm cache; the library sums in the reference's order (clause order under SHOULD, the leaf's stable
+    /// cost order under MUST) - bit-equal rows. k above 128 stays the CPU searcher's.
+    fn try_fields(&self, spec: &CrossQuery<'_>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
+        if k > 128 { return Ok(false); }
+        let mut weights = Vec::new();
+        for g in &spec.groups { for t in &g.terms { weights.push(self.field_weight_of(&t.term, t.boost)?); } }
+        for leaf in self.cpu.reader().leaves() {
+            let mut clauses: Vec<RgpuFieldClause> = Vec::with_capacity(weights.len() + spec.must_not.len());
+            let mut groups: Vec<RgpuFieldGroup> = Vec::with_capacity(spec.groups.len());
+            let mut at = 0usize;
+            for g in &spec.groups {
+                groups.push(RgpuFieldGroup { first_term: clauses.len() as i32, n_terms: g.terms.len() as i32, tie_bits: g.tie.to_bits(),
+                                             kind: if g.dismax { RGPU_GROUP_DISMAX } else { RGPU_GROUP_TERM } });
+                for t in &g.terms {
+                    let slot = self.slot_of(&t.term.field, leaf.ord).unwrap_or(0);
+                    clauses.push(RgpuFieldClause { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: weights[at].0, sim_table: weights[at].1,
+                                                   field: slot, reserved: 0 });
+                    at += 1;
+                }
+            }
+            let first_must_not = clauses.len() as i32;
+            for t in &spec.must_not {
+                let slot = self.slot_of(&t.term.field, leaf.ord).unwrap_or(0);
+                clauses.push(RgpuFieldClause { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: 0.0, sim_table: 0, field: slot, reserved: 0 });
+            }
+            let q = RgpuFieldsQuery { occur: if spec.must { RGPU_OCCUR_MUST } else { RGPU_OCCUR_SHOULD }, first_group: 0, n_groups: groups.len() as i32,
+                                      min_should_match: spec.msm, first_must_not, n_must_not: spec.must_not.len() as i32 };
+            let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
+            let mut total: i64 = 0;
+            check(unsafe { rgpu_search_fields_batch(self.leaves[leaf.ord].seg, &q, 1, groups.as_ptr(), groups.len() as i32, clauses.as_ptr(), clauses.len() as i32,
+                                                    k as i32, hits.as_mut_ptr(), &mut total) }, self.ctx)?;
+            Self::hand_over(top, &hits, total);
+        }
+        Ok(true)
     }
 
     /// BooleanQuery trees the C ABI serves, flattened to one clause list (query/boolean_query.rs:195-279 is what the CPU builds
@@ -425,6 +560,9 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
                 if must.is_empty() && filter.is_empty() { return self.try_phrase_or(b, None, top, k); }
                 return self.try_phrase_bool(b, None, top, k);
             }
+        }
+        if !self.extra_fields.is_empty() {   // a tree that names an attached field: rgpu_search_fields_batch
+            if let Some(spec) = self.cross_spec(query) { return self.try_fields(&spec, top, k); }
         }
         let flat = match self.flatten(query) { Some(f) => f, None => return Ok(false) };
         let n = flat.n_clauses();
