@@ -1,7 +1,7 @@
 // Further fields of a segment and the cross-field search. FieldScope, field_norms_upload, prepare_field_terms_locked, search_fields_locked.
 // Entry points: rgpu_segment_attach_field, rgpu_segment_prepare_field_terms, rgpu_segment_get_field_info, rgpu_search_fields_batch.
-// Uses: rgpu_api.hip itself (rgpu_ctx, rgpu_segment, fail, the prepare path, make_dev_term, Stager / Staged, launch_merge,
-// api_rows_read_back), kernels/search_fields.hpp, host/fields_plan.hpp.
+// Uses: rgpu_api.hip itself (rgpu_ctx, rgpu_segment, fail, the prepare path, make_dev_term, Stager / Staged, launch_merge),
+// rows.hpp (api_rows_read_back), kernels/search_fields.hpp, host/fields_plan.hpp.
 // Not a stand-alone header: part of the one translation unit rgpu_api.hip, included there once and in this order.
 
 static_assert(sizeof(FieldsGroupDev) == sizeof(rgpu_host::FieldsPlanGroup) && sizeof(FieldsQueryDev) == sizeof(rgpu_host::FieldsPlanQuery),

@@ -3583,2612 +3583,27 @@ extern "C" int32_t rgpu_search_batch_device(rgpu_segment* seg, const rgpu_query*
   return rc;
 }
 
-// ---- the device-side rows of a blocking call: c->host_api_hits ([n_queries][k]) and c->host_api_totals, grow-only ---------------
-// Every row's defaults - total 0 and "no hit" in every column: what a query that launches nothing, or a leaf that holds none of
-// its clauses, returns. `pass`: one pass of a k > RGPU_PASS_K call, which fills `width` columns from `col0` on of rows `stride`
-// wide; null: the whole rows of k columns.
-struct RowColumns { int32_t width, stride, col0; };
-static int32_t api_rows_default(rgpu_ctx* c, hipStream_t stream, int32_t n_queries, int32_t k, const RowColumns* pass = nullptr) {
-  const size_t nq = (size_t)n_queries;
-  const RowColumns cols = pass ? *pass : RowColumns{k, k, 0};
-  HIP_TRY(c->host_api_hits.reserve(nq * (size_t)k, 0, stream));
-  HIP_TRY(c->host_api_totals.reserve(nq, 0, stream));
-  HIP_TRY(hipMemsetAsync(c->host_api_totals.p, 0, nq * 8, stream));
-  RGPU_LAUNCH(k_init_hits, dim3(wg_count((nq * (size_t)cols.width + 255) / 256)), dim3(256), 0, stream, c->host_api_hits.p, (int64_t)n_queries, (int)cols.width,
-              (int)cols.stride, (int)cols.col0);
-  return RGPU_OK;
-}
-// ... and the rows out to the caller's arrays; ends synchronised. `verdict`: also fetch the phrase match stage's verdict
-// (c->d_err[0]) in the same round - one synchronise less for a call that is content to have written its rows when it refuses
-// (rgpu_search_phrase_batch; include/rucene_gpu.h says per call what a refusal leaves).
-static int32_t api_rows_read_back(rgpu_ctx* c, hipStream_t stream, int32_t n_queries, int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out, int* verdict = nullptr) {
-  hipError_t e0 = verdict ? hipMemcpyAsync(verdict, c->d_err, sizeof(int), hipMemcpyDeviceToHost, stream) : hipSuccess;
-  hipError_t e1 = hipMemcpyAsync(hits_out, c->host_api_hits.p, (size_t)n_queries * (size_t)k * sizeof(HitOut), hipMemcpyDeviceToHost, stream);
-  hipError_t e2 = hipMemcpyAsync(total_hits_out, c->host_api_totals.p, (size_t)n_queries * 8, hipMemcpyDeviceToHost, stream);
-  hipError_t e3 = hipStreamSynchronize(stream);
-  if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(RGPU_ERR_RUNTIME, "device to host copy failed");
-  return RGPU_OK;
-}
-
-// rgpu_search_batch behind its argument checks (ctx mutex held, device set): shared with rgpu_search_batch_masked
-static int32_t search_batch_host_locked(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
-                                        int32_t n_terms_total, int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
-  rgpu_ctx* c = seg->ctx;
-  // device-side result rows of the blocking variant live in the context (grow-only): the call ends with a stream
-  // sync, so they are free again when it returns
-  // IndexSearcher::search is ONE query per call (search/searcher.rs:487-525): a batch of one is a launch-latency exercise — 66 us
-  // of wall time around 23 us of kernels (round 6's latency leg), two of its six stream operations being the device-to-host
-  // copies of 88 bytes. Rows of up to 256 KiB are therefore written by the kernels straight into pinned host memory
-  // (hipHostMalloc: device-visible, coherent) and copied to the caller's arrays by the CPU after the one stream sync.
-  const size_t hits_bytes = (size_t)n_queries * (size_t)k * sizeof(HitOut), tot_bytes = (size_t)n_queries * 8;
-  if (hits_bytes + tot_bytes <= ((size_t)256 << 10)) {
-    HIP_TRY(c->host_api_rows.reserve(hits_bytes + tot_bytes));
-    HitOut* p_hits = reinterpret_cast<HitOut*>(c->host_api_rows.p);
-    int64_t* p_tot = reinterpret_cast<int64_t*>(c->host_api_rows.p + hits_bytes);
-    int32_t rc = search_impl(seg, queries, n_queries, terms, n_terms_total, k, p_hits, p_tot, c->stream);
-    if (rc != RGPU_OK) return rc;
-    rc = settle_pending(c);  // (nothing is deferred on this path; a closure left by an earlier deferred batch may own the stream's tail)
-    if (rc != RGPU_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    std::memcpy(hits_out, p_hits, hits_bytes);
-    std::memcpy(total_hits_out, p_tot, tot_bytes);
-    return RGPU_OK;
-  }
-  HIP_TRY(c->host_api_hits.reserve((size_t)n_queries * (size_t)k, 0, c->stream));
-  HIP_TRY(c->host_api_totals.reserve((size_t)n_queries, 0, c->stream));
-  RGPU_TRY(search_impl(seg, queries, n_queries, terms, n_terms_total, k, c->host_api_hits.p, c->host_api_totals.p, c->stream));
-  return api_rows_read_back(c, c->stream, n_queries, k, hits_out, total_hits_out);
-}
-
-extern "C" int32_t rgpu_search_batch(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
-                                     int32_t n_terms_total, int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
-  if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !hits_out || !total_hits_out)
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  return search_batch_host_locked(seg, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out);
-}
-
-static int64_t phrase_redo_cap(int64_t slots) {
-  // (developer knob: RGPU_PHRASE_REDO_CAP=<n> shrinks the list of left-over candidates, so that a test reaches the pass that runs without it)
-  int64_t redo_cap = PHRASE_REDO_LIST_CAP;
-  if (const char* e = std::getenv("RGPU_PHRASE_REDO_CAP")) redo_cap = std::max<int64_t>(0, std::min<int64_t>(redo_cap, std::atoll(e)));
-  return std::min<int64_t>(slots, redo_cap);
-}
-// ---- the set-up of phrase_match_stage (below, with the exact phrases), in front of the launch that fills the slots - and_emit_stage
-// runs it among its own memsets, a rescoring by itself - and whether or not the stage will have a slot to look at:
-// the callers read d_err afterwards.
-// `zero_keys`: zero c->phrase_keys. The match kernels write a key (or 0) to every slot below a query's count and to none above it:
-// a 64-candidate group past a query's count is never written. rgpu_rescore_phrase_batch needs the zeroes: k_rescore_phrase_combine
-// reads a row's slots by position, a 64-candidate kernel leaves the slots behind a row's window unwritten, and a batch of
-// absent-term rows launches no match kernel at all. rgpu_search_phrase_bool_batch and _phrase_or_batch ask for them too:
-// k_phrase_bool_score and k_phrase_run_place walk the slots by 64-slot group (both also look at the count; the zeroes are kept as
-// the second line they have been). rgpu_search_phrase_batch does without the memset: its collectors read emit_count[q] slots of
-// query q and nothing behind them.
-static int32_t phrase_match_setup(rgpu_ctx* c, hipStream_t stream, int64_t slots, bool zero_keys, int64_t* redo_cap) {
-  HIP_TRY(c->phrase_docs.reserve((size_t)slots + 64, 0, stream));
-  HIP_TRY(c->phrase_keys.reserve((size_t)slots + 64, 0, stream));
-  *redo_cap = phrase_redo_cap(slots);
-  HIP_TRY(c->phrase_redo.reserve((size_t)*redo_cap + 64, 0, stream));
-  if (zero_keys) HIP_TRY(hipMemsetAsync(c->phrase_keys.p, 0, (size_t)slots * 8, stream));
-  HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));  // [0]: error code, [2]: slots on the redo list, [3]: "a candidate needs the wide lists"
-  return RGPU_OK;
-}
-
-// ---- the candidate stage: k_search_and in emit mode ------------------------------------------------------------------------------
-// A conjunction that collects nothing: the docs that hold every required clause of (virtual) query q (and none of its MUST_NOT
-// clauses, DevQuery::pad) go to c->phrase_docs from slot emit_prefix[q] on, their number to c->phrase_count[q]. What reads the
-// slots afterwards is the caller's business: phrase_match_stage (rgpu_search_phrase_batch, _phrase_bool_batch, _phrase_or_batch)
-// or k_docset_from_emitted (rgpu_docset_collect_batch).
-// A query's share of the launch, from the conjunction's lead (its first, rarest, clause): work items of `blocks_per_item` lead
-// blocks ...
-static inline int64_t lead_items(const DevTerm& lead, int blocks_per_item) { return lead.nblocks == 0 ? 1 : (lead.nblocks + blocks_per_item - 1) / blocks_per_item; }
-// ... candidate slots: the lead's doc_freq bounds the matches; whole groups of 64 (the 64 slots of a k_phrase_match_lanes wavefront
-// belong to one query) ...
-static inline int64_t lead_slots(const DevTerm& lead) { return rgpu_host::pb_round_up_64((int64_t)lead.df); }
-// ... and items of the chunked collector (k_phrase_collect_items)
-static inline int64_t lead_collect_chunks(const DevTerm& lead) { return ((int64_t)lead.df + PHRASE_COLLECT_CHUNK - 1) / PHRASE_COLLECT_CHUNK; }
-struct AndEmitStage {
-  const char* name;  // of the launch in the kernel statistics
-  const DevQuery* d_q;
-  const DevTerm* d_t;
-  const int64_t* d_ip;     // items in front of each query's
-  const int64_t* d_ep;     // slots in front of each query's
-  const TermBitmap* d_bm;  // clause_bitmap_table, or null
-  int32_t n_queries;       // the conjunctions (virtual queries where a query runs several)
-  // entries of c->phrase_count to reserve and zero: n_queries, or more where later stages count slots of their own behind the
-  // conjunctions' (rgpu_search_phrase_bool_batch: one plane per phrase, k_phrase_bool_fanout fills planes 1..)
-  size_t n_counts;
-  int64_t items, slots;
-  int blocks_per_item;
-  int k_emit;    // width of the (empty) top-k lists the kernel keeps all the same: the narrowest kind the caller's k allows
-  bool any_not;  // some query has MUST_NOT clauses: the HAS_NOT instantiation
-  // least sizes of c->S->d_partial_keys / d_partial_counts: the kernel's own lists need items * k_emit and items; the chunked phrase
-  // collector reuses both buffers behind it and needs them larger (0: no such need)
-  size_t partial_keys, partial_counts;
-  // phrase_match_stage comes behind (the phrase callers): the stage runs phrase_match_setup, zeroing the keys or not, between its
-  // memset of the counts and those of the thresholds, and hands the set-up's *redo_cap on. Every memset of the call then stands in
-  // front of the conjunction, the large one (the keys) second as it always has: with the set-up called by the callers in front of
-  // this stage - the same memsets, the keys first - rgpu_search_phrase_bool_batch took 0.05 - 0.07 ms of 2.15 longer per call, none
-  // of it inside a kernel (the phrase-bool launch sequence).
-  int64_t* redo_cap = nullptr;
-  bool zero_keys = false;
-  // the masked exact-phrase calls (seg's live docs are `live AND set`): the LIVE_ONLY instantiation - a candidate that is not live is
-  // dropped, not marked; the slots behind the survivors stay unwritten, as the slots behind any query's count do
-  bool live_only = false;
-};
-static int32_t and_emit_stage(rgpu_segment* seg, hipStream_t stream, const AndEmitStage& a) {
-  rgpu_ctx* c = seg->ctx;
-  const size_t nq = (size_t)a.n_queries;
-  HIP_TRY(c->phrase_docs.reserve((size_t)a.slots + 64, 0, stream));  // (phrase_match_setup reserves it too: a doc-set call runs no set-up, a rescoring not this stage)
-  HIP_TRY(c->phrase_count.reserve(a.n_counts, 0, stream));
-  HIP_TRY(c->S->d_partial_keys.reserve(std::max((size_t)a.items * (size_t)a.k_emit, a.partial_keys), 0, stream));
-  HIP_TRY(c->S->d_partial_counts.reserve(std::max((size_t)a.items, a.partial_counts), 0, stream));
-  HIP_TRY(c->S->d_tau.reserve(nq, 0, stream));  // (thresholds and counted words: per conjunction)
-  HIP_TRY(c->S->d_touched.reserve(nq * 2, 0, stream));
-  HIP_TRY(hipMemsetAsync(c->phrase_count.p, 0, a.n_counts * 8, stream));
-  if (a.redo_cap) RGPU_TRY(phrase_match_setup(c, stream, a.slots, a.zero_keys, a.redo_cap));
-  HIP_TRY(hipMemsetAsync(c->S->d_tau.p, 0, nq * 8, stream));
-  HIP_TRY(hipMemsetAsync(c->S->d_touched.p, 0, nq * 16, stream));
-  TimedLaunch tl(c, stream, a.name, 0);
-  const SegView sv = seg_view(seg);
-  const int xcd_chunk = and_xcd_chunk(seg);
-  const unsigned grid = wg_count(and_grid((a.items + AND_WG_WAVES - 1) / AND_WG_WAVES, xcd_chunk));
-  auto go = [&](auto kern) {
-    RGPU_LAUNCH(kern, dim3(grid), dim3(AND_WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_ip, (int)a.n_queries, a.items, a.blocks_per_item, a.k_emit,
-                c->S->d_partial_keys.p, c->S->d_partial_counts.p, c->S->d_tau.p, c->S->d_touched.p, a.d_ep, c->phrase_count.p, (void*)c->phrase_docs.p,
-                (const unsigned long long*)nullptr, (const int32_t*)nullptr, a.d_bm, xcd_chunk);
-  };
-  const bool legacy = seg->version < 1;
-  if (a.live_only) {
-    if (a.any_not) { if (legacy) go(k_search_and<true, false, true, false, false, true>); else go(k_search_and<false, false, true, false, false, true>); }
-    else { if (legacy) go(k_search_and<true, false, false, false, false, true>); else go(k_search_and<false, false, false, false, false, true>); }
-    return RGPU_OK;
-  }
-  if (a.any_not) { if (legacy) go(k_search_and<true, false, true, false>); else go(k_search_and<false, false, true, false>); }
-  else { if (legacy) go(k_search_and<true, false, false, false>); else go(k_search_and<false, false, false, false>); }
-  return RGPU_OK;
-}
-
-// ---- doc sets: cached filters as FILTER / MUST_NOT masks (include/rucene_gpu.h rgpu_docset_*; the plan: host/docset_plan.hpp; the
-// kernels: kernels/docset.hpp) -----------------------------------------------------------------------------------------------------
-// Every constructor ends synchronised on the context's stream, so a finished set can be read from any stream without an event. A
-// masked search installs `live AND set` as the segment's live docs for the duration of the call (MaskScope, under ctx->mu): the
-// kernels take SegView by value, and every host decision asks live_words(). Launch sequences:
-//   from_words        copy, k_docset_combine (the count)
-//   from_docs         copy, k_docset_from_docs, k_docset_combine (the count)
-//   collect_batch     term preparation as a search; k_docset_lists<set>, k_docset_lists<clear> for TERM / OR rows; k_search_and in
-//                     emit mode (MUST_NOT clauses through its HAS_NOT instantiation) and k_docset_from_emitted for AND rows; one
-//                     k_docset_combine per row (the count)
-//   combine           k_docset_combine, once per DOCSET_MAX_OPERANDS operands of a side
-//   masked search     first use of a set on a segment with deletions: k_docset_combine (live AND set), kept; then the search
-struct rgpu_docset {
-  rgpu_ctx* ctx = nullptr;
-  uint64_t seg_uid = 0;
-  int32_t max_doc = 0;
-  size_t n_words = 0;
-  uint64_t* d_words = nullptr;           // n_words u64 (the allocation is never empty)
-  uint64_t* d_mask = nullptr;            // live AND set: formed by the first masked search when the segment has deletions
-  unsigned long long* d_count = nullptr; // [0]: cardinality (k_docset_combine), [1]: ids out of range (k_docset_from_docs) / a count nobody reads; 4 words
-  int64_t cardinality = 0;
-  // the head of `live AND set` (rgpu_docset_head, rgpu_search_batch_required_set): its first min(head_n, live_cardinality) docs,
-  // built for the largest n asked for so far; sets and live docs are immutable, so nothing ever invalidates it
-  int32_t* d_head = nullptr;
-  int32_t head_n = -1;                   // -1: never built
-  int64_t live_cardinality = 0;          // |live AND set|, known once a head is built
-  std::vector<hipEvent_t> in_flight;     // one per masked search enqueued and not yet seen finished
-};
-
-static size_t docset_head_alloc_bytes(int32_t n) { return std::max<size_t>(256, (size_t)std::max<int32_t>(n, 0) * 4); }
-static size_t docset_alloc_bytes(size_t n_words) { return std::max<size_t>(16, (n_words * 8 + 15) & ~size_t(15)); }
-
-static int32_t docset_new(rgpu_segment* seg, rgpu_docset** out, bool zeroed = true) {  // !zeroed: every word gets written by its builder
-  rgpu_docset* d = new rgpu_docset();
-  d->ctx = seg->ctx;
-  d->seg_uid = seg->uid;
-  d->max_doc = seg->max_doc;
-  d->n_words = (size_t)rgpu_host::docset_word_count(seg->max_doc);
-  hipError_t e = hipMalloc(&d->d_words, docset_alloc_bytes(d->n_words));
-  if (e == hipSuccess) e = hipMalloc(&d->d_count, 32);
-  // (!zeroed: the builder writes the n_words words; the padding of an odd count is zeroed all the same — no byte of a set is ever undefined)
-  if (e == hipSuccess) {
-    const size_t from = zeroed ? 0 : d->n_words * 8, bytes = docset_alloc_bytes(d->n_words);
-    if (from < bytes) e = hipMemsetAsync(reinterpret_cast<uint8_t*>(d->d_words) + from, 0, bytes - from, seg->ctx->stream);
-  }
-  if (e != hipSuccess) {
-    if (d->d_words) (void)hipFree(d->d_words);
-    if (d->d_count) (void)hipFree(d->d_count);
-    delete d;
-    return fail(RGPU_ERR_RUNTIME, std::string("doc set allocation: ") + hipGetErrorString(e));
-  }
-  *out = d;
-  return RGPU_OK;
-}
-static void docset_delete(rgpu_docset* d) {
-  if (!d) return;
-  for (hipEvent_t ev : d->in_flight) { (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
-  if (d->d_words) (void)hipFree(d->d_words);
-  if (d->d_mask) (void)hipFree(d->d_mask);
-  if (d->d_head) (void)hipFree(d->d_head);
-  if (d->d_count) (void)hipFree(d->d_count);
-  delete d;
-}
-
-// out = AND all_of, minus every none_of, inside [0, max_doc) [AND live]; *d_count += its cardinality. Enqueue-only.
-static int32_t docset_combine_launch(rgpu_ctx* c, hipStream_t stream, int32_t max_doc, const uint64_t* const* all_of, int32_t n_all,
-                                     const uint64_t* const* none_of, int32_t n_none, const uint64_t* live, uint64_t* out,
-                                     unsigned long long* d_count) {
-  HIP_TRY(hipMemsetAsync(d_count, 0, 8, stream));
-  const int64_t n_words = rgpu_host::docset_word_count(max_doc);
-  if (n_words == 0) return RGPU_OK;
-  const unsigned grid = wg_count(((unsigned long long)(n_words + 1) / 2 + DOCSET_THREADS - 1) / DOCSET_THREADS);
-  int32_t a = 0, x = 0;
-  bool first = true;
-  while (first || a < n_all || x < n_none) {  // rounds of DOCSET_MAX_OPERANDS per side; later rounds start from what the earlier ones left
-    DocsetCombineArgs args;
-    std::memset(&args, 0, sizeof args);
-    args.max_doc = max_doc;
-    if (!first) args.all_of[args.n_all++] = out;
-    while (a < n_all && args.n_all < DOCSET_MAX_OPERANDS) args.all_of[args.n_all++] = all_of[a++];
-    while (x < n_none && args.n_none < DOCSET_MAX_OPERANDS) args.none_of[args.n_none++] = none_of[x++];
-    const bool last = a >= n_all && x >= n_none;
-    args.live = last ? live : nullptr;
-    if (!last) HIP_TRY(hipMemsetAsync(d_count, 0, 8, stream));
-    TimedLaunch tl(c, stream, "k_docset_combine", 0);
-    RGPU_LAUNCH(k_docset_combine, dim3(grid), dim3(DOCSET_THREADS), 0, stream, args, out, last ? d_count : d_count + 1);
-    first = false;
-  }
-  HIP_TRY(launch_status());
-  return RGPU_OK;
-}
-// the bits past max_doc cleared (there are none unless a caller's words had some: refused before), the set counted; ends synchronised
-static int32_t docset_finish(rgpu_docset* d, hipStream_t stream) {
-  const uint64_t* self[1] = {d->d_words};
-  RGPU_TRY(docset_combine_launch(d->ctx, stream, d->max_doc, self, 1, nullptr, 0, nullptr, d->d_words, d->d_count));
-  unsigned long long n = 0;
-  HIP_TRY(hipMemcpyAsync(&n, d->d_count, 8, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  d->cardinality = (int64_t)n;
-  return RGPU_OK;
-}
-static int32_t docset_check(const rgpu_segment* seg, const rgpu_docset* set) {
-  if (set->seg_uid != seg->uid || set->ctx != seg->ctx) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "the doc set belongs to another segment");
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_docset_from_words(rgpu_segment* seg, const uint64_t* words, rgpu_docset** out_set) {
-  if (!seg || !out_set || (!words && seg->max_doc > 0)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  *out_set = nullptr;
-  if (!rgpu_host::docset_words_valid(words, seg->max_doc)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a bit at or past max_doc is set");
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  rgpu_docset* d = nullptr;
-  RGPU_TRY(docset_new(seg, &d));
-  int32_t rc = RGPU_OK;
-  if (d->n_words > 0 && hipMemcpyAsync(d->d_words, words, d->n_words * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-    rc = fail(RGPU_ERR_RUNTIME, "copy of the doc set's words failed");
-  if (rc == RGPU_OK) rc = docset_finish(d, c->stream);
-  if (rc != RGPU_OK) { (void)hipStreamSynchronize(c->stream); docset_delete(d); return rc; }
-  *out_set = d;
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_docset_from_docs(rgpu_segment* seg, const int32_t* docs, int64_t n_docs, rgpu_docset** out_set) {
-  if (!seg || !out_set || n_docs < 0 || (!docs && n_docs > 0)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  *out_set = nullptr;
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  rgpu_docset* d = nullptr;
-  RGPU_TRY(docset_new(seg, &d));
-  int32_t* d_docs = nullptr;
-  auto run = [&]() -> int32_t {
-    if (n_docs > 0) {
-      HIP_TRY(hipMalloc(&d_docs, (size_t)n_docs * 4));
-      HIP_TRY(hipMemcpyAsync(d_docs, docs, (size_t)n_docs * 4, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(hipMemsetAsync(d->d_count + 1, 0, 8, c->stream));
-      {
-        TimedLaunch tl(c, c->stream, "k_docset_from_docs", n_docs);
-        RGPU_LAUNCH(k_docset_from_docs, dim3(wg_count(((unsigned long long)n_docs + DOCSET_THREADS - 1) / DOCSET_THREADS)), dim3(DOCSET_THREADS), 0, c->stream,
-                    d_docs, n_docs, seg->max_doc, reinterpret_cast<uint32_t*>(d->d_words), reinterpret_cast<unsigned int*>(d->d_count + 1));
-      }
-      HIP_TRY(launch_status());
-      unsigned int bad = 0;
-      HIP_TRY(hipMemcpyAsync(&bad, d->d_count + 1, 4, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (bad != 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a doc id outside [0, max_doc)");
-    }
-    return docset_finish(d, c->stream);
-  };
-  const int32_t rc = run();
-  if (rc != RGPU_OK) (void)hipStreamSynchronize(c->stream);
-  if (d_docs) (void)hipFree(d_docs);
-  if (rc != RGPU_OK) { docset_delete(d); return rc; }
-  *out_set = d;
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_docset_combine(rgpu_segment* seg, rgpu_docset* const* all_of, int32_t n_all, rgpu_docset* const* none_of, int32_t n_none,
-                                       rgpu_docset** out_set) {
-  if (!seg || !out_set || n_all < 0 || n_none < 0 || (n_all > 0 && !all_of) || (n_none > 0 && !none_of)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  *out_set = nullptr;
-  std::vector<const uint64_t*> a, x;
-  for (int32_t i = 0; i < n_all; ++i) { if (!all_of[i]) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null doc set"); RGPU_TRY(docset_check(seg, all_of[i])); a.push_back(all_of[i]->d_words); }
-  for (int32_t i = 0; i < n_none; ++i) { if (!none_of[i]) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null doc set"); RGPU_TRY(docset_check(seg, none_of[i])); x.push_back(none_of[i]->d_words); }
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  rgpu_docset* d = nullptr;
-  RGPU_TRY(docset_new(seg, &d));
-  int32_t rc = docset_combine_launch(c, c->stream, d->max_doc, a.data(), n_all, x.data(), n_none, nullptr, d->d_words, d->d_count);
-  unsigned long long n = 0;
-  if (rc == RGPU_OK && (hipMemcpyAsync(&n, d->d_count, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess))
-    rc = fail(RGPU_ERR_RUNTIME, "doc set combine failed");
-  if (rc != RGPU_OK) { (void)hipStreamSynchronize(c->stream); docset_delete(d); return rc; }
-  d->cardinality = (int64_t)n;
-  *out_set = d;
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_docset_cardinality(const rgpu_docset* set, int64_t* n_out) {
-  if (!set || !n_out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
-  *n_out = set->cardinality;
-  return RGPU_OK;
-}
-extern "C" int64_t rgpu_docset_bytes(const rgpu_docset* set) {
-  if (!set) return 0;
-  return (int64_t)docset_alloc_bytes(set->n_words) * (set->d_mask ? 2 : 1) + 32 + (set->d_head ? (int64_t)docset_head_alloc_bytes(set->head_n) : 0);
-}
-extern "C" int32_t rgpu_docset_words(rgpu_docset* set, uint64_t* words_out) {
-  if (!set || (!words_out && set->n_words > 0)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
-  if (set->n_words == 0) return RGPU_OK;
-  std::lock_guard<std::mutex> g(set->ctx->mu);
-  HIP_TRY(hipSetDevice(set->ctx->device));
-  HIP_TRY(hipMemcpy(words_out, set->d_words, set->n_words * 8, hipMemcpyDeviceToHost));
-  return RGPU_OK;
-}
-extern "C" void rgpu_docset_free(rgpu_docset* set) {
-  if (!set) return;
-  (void)hipSetDevice(set->ctx->device);
-  std::lock_guard<std::mutex> g(set->ctx->mu);  // (a masked call in another thread finishes enqueueing first)
-  docset_delete(set);  // waits for every masked search in flight that reads the set
-}
-
-// ---- point ranges: numeric range filters built as doc sets (include/rucene_gpu.h rgpu_points_*; the plan: host/points_plan.hpp;
-// the kernels: kernels/points.hpp) --------------------------------------------------------------------------------------------------
-// Launch sequences of rgpu_docset_from_point_ranges, per range as the plan answers it:
-//   nothing        memset of the set (its construction), k_docset_combine (the count)
-//   every doc      k_docset_combine with no operands (all ones inside [0, max_doc), counted)
-//   scatter        memset, k_docset_from_docs over docs_by_value[i0, i1), k_docset_combine (the count)
-//   scan           dense: k_points_scan<K, true> (no memset: every word has one writer); else memset, k_points_scan<K, false>;
-//                  ONE launch per POINTS_SCAN_RANGES scanned ranges of the call; k_docset_combine per set (the count)
-// and one synchronisation at the end of the call.
-struct rgpu_points {
-  rgpu_segment* seg = nullptr;
-  rgpu_ctx* ctx = nullptr;
-  uint64_t seg_uid = 0;
-  rgpu_host::PointsColumns cols;    // keys_sorted stays; the other columns are released after the upload
-  void* d_keys_by_doc = nullptr;    // u32 / u64 keys in doc order, whole chunks, zero-filled behind n_points
-  int32_t* d_docs_by_doc = nullptr; // not dense only; whole chunks
-  int32_t* d_docs_by_value = nullptr;
-  int64_t hbm_bytes = 0;
-};
-
-static void points_delete(rgpu_points* p) {
-  if (!p) return;
-  if (p->d_keys_by_doc) (void)hipFree(p->d_keys_by_doc);
-  if (p->d_docs_by_doc) (void)hipFree(p->d_docs_by_doc);
-  if (p->d_docs_by_value) (void)hipFree(p->d_docs_by_value);
-  delete p;
-}
-
-extern "C" int32_t rgpu_points_attach(rgpu_segment* seg, int32_t bytes_per_dim, const int32_t* docs, const uint8_t* values, int64_t n_points,
-                                      rgpu_points** out_points) {
-  if (!seg || !out_points) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  *out_points = nullptr;
-  if (bytes_per_dim != 4 && bytes_per_dim != 8) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "points: one dimension of 4 or 8 bytes");
-  if (n_points < 0 || n_points >= ((int64_t)1 << 31) || (n_points > 0 && (!docs || !values))) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));   // (before anything is allocated: an early return owns nothing)
-  rgpu_points* p = new rgpu_points();
-  if (rgpu_host::points_build(seg->max_doc, bytes_per_dim, docs, values, n_points, p->cols) != RGPU_OK) {
-    delete p;
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "points: a doc id outside [0, max_doc)");
-  }
-  p->seg = seg;
-  p->ctx = seg->ctx;
-  p->seg_uid = seg->uid;
-  rgpu_host::PointsColumns& C = p->cols;
-  const size_t padded = (size_t)rgpu_host::points_padded_count(n_points, seg->max_doc, bytes_per_dim, C.dense);
-  const size_t n = (size_t)n_points;
-  auto run = [&]() -> int32_t {
-    HIP_TRY(hipMalloc(&p->d_keys_by_doc, padded * (size_t)bytes_per_dim));
-    HIP_TRY(hipMemsetAsync(p->d_keys_by_doc, 0, padded * (size_t)bytes_per_dim, c->stream));
-    p->hbm_bytes += (int64_t)(padded * (size_t)bytes_per_dim);
-    std::vector<uint32_t> k32;
-    if (bytes_per_dim == 4) {
-      k32.resize(n);
-      for (size_t i = 0; i < n; ++i) k32[i] = (uint32_t)C.keys_by_doc[i];
-    }
-    if (n > 0) HIP_TRY(hipMemcpyAsync(p->d_keys_by_doc, bytes_per_dim == 4 ? (const void*)k32.data() : (const void*)C.keys_by_doc.data(), n * (size_t)bytes_per_dim,
-                                      hipMemcpyHostToDevice, c->stream));
-    if (!C.dense) {
-      HIP_TRY(hipMalloc(&p->d_docs_by_doc, padded * 4));
-      HIP_TRY(hipMemsetAsync(p->d_docs_by_doc, 0, padded * 4, c->stream));
-      if (n > 0) HIP_TRY(hipMemcpyAsync(p->d_docs_by_doc, C.docs_by_doc.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-      p->hbm_bytes += (int64_t)(padded * 4);
-    }
-    HIP_TRY(hipMalloc(&p->d_docs_by_value, std::max<size_t>(n, 1) * 4));
-    if (n > 0) HIP_TRY(hipMemcpyAsync(p->d_docs_by_value, C.docs_by_value.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-    p->hbm_bytes += (int64_t)(std::max<size_t>(n, 1) * 4);
-    HIP_TRY(hipStreamSynchronize(c->stream));   // (the host vectors the copies read go away below)
-    return RGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc != RGPU_OK) { (void)hipStreamSynchronize(c->stream); points_delete(p); return rc; }
-  std::vector<uint64_t>().swap(C.keys_by_doc);
-  std::vector<int32_t>().swap(C.docs_by_doc);
-  std::vector<int32_t>().swap(C.docs_by_value);
-  *out_points = p;
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_points_get_info(const rgpu_points* points, rgpu_points_info* out) {
-  if (!points || !out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "null argument");
-  std::memset(out, 0, sizeof *out);
-  out->n_points = points->cols.n_points;
-  out->doc_count = points->cols.doc_count;
-  out->hbm_bytes = points->hbm_bytes;
-  out->bytes_per_dim = points->cols.bytes_per_dim;
-  out->dense = points->cols.dense ? 1 : 0;
-  if (points->cols.n_points > 0) {
-    rgpu_host::points_key_bytes(points->cols.min_key, points->cols.bytes_per_dim, out->min_value);
-    rgpu_host::points_key_bytes(points->cols.max_key, points->cols.bytes_per_dim, out->max_value);
-  }
-  return RGPU_OK;
-}
-
-extern "C" void rgpu_points_free(rgpu_points* points) {
-  if (!points) return;
-  (void)hipSetDevice(points->ctx->device);
-  std::lock_guard<std::mutex> g(points->ctx->mu);  // a build in another thread ends synchronised under this lock
-  points_delete(points);
-}
-
-template <typename K, bool DENSE>
-static int32_t points_scan_launch(rgpu_points* p, const std::vector<rgpu_host::PointsRangePlan>& plans, const std::vector<int32_t>& pass,
-                                  const std::vector<rgpu_docset*>& sets, hipStream_t stream) {
-  PointsScanArgs<K> a;
-  std::memset(&a, 0, sizeof a);
-  a.n_ranges = (int32_t)pass.size();
-  a.max_doc = p->cols.max_doc;
-  a.n_points = p->cols.n_points;
-  for (size_t i = 0; i < pass.size(); ++i) {
-    const rgpu_host::PointsRangePlan& P = plans[(size_t)pass[i]];
-    a.lower[i] = (K)P.lower;
-    a.span[i] = (K)(P.upper - P.lower);
-    a.rows[i] = reinterpret_cast<uint32_t*>(sets[(size_t)pass[i]]->d_words);
-  }
-  constexpr int64_t chunk = 64 * (16 / (int64_t)sizeof(K));
-  const int64_t padded = rgpu_host::points_padded_count(p->cols.n_points, p->cols.max_doc, (int32_t)sizeof(K), DENSE);
-  const int64_t n_chunks = padded / chunk;
-  const unsigned grid = (unsigned)std::min<int64_t>(POINTS_SCAN_MAX_BLOCKS, (n_chunks + DOCSET_WAVES - 1) / DOCSET_WAVES);
-  {
-    TimedLaunch tl(p->ctx, stream, "k_points_scan", p->cols.n_points);
-    RGPU_LAUNCH((k_points_scan<K, DENSE>), dim3(grid), dim3(DOCSET_THREADS), 0, stream, static_cast<const K*>(p->d_keys_by_doc), p->d_docs_by_doc, a);
-  }
-  HIP_TRY(launch_status());
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_docset_from_point_ranges(rgpu_points* points, const rgpu_point_range* ranges, int32_t n_ranges, int32_t path,
-                                                 rgpu_docset** out_sets) {
-  if (!points || !ranges || n_ranges <= 0 || !out_sets || path < 0 || path > 2) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  for (int32_t r = 0; r < n_ranges; ++r) out_sets[r] = nullptr;
-  rgpu_ctx* c = points->ctx;
-  rgpu_segment* seg = points->seg;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t stream = c->stream;
-  const rgpu_host::PointsColumns& C = points->cols;
-  const std::vector<rgpu_host::PointsRangePlan> plans = rgpu_host::plan_point_ranges(C, ranges, n_ranges, path);
-  const std::vector<std::vector<int32_t>> passes = rgpu_host::points_scan_passes(plans);
-  std::vector<rgpu_docset*> sets((size_t)n_ranges, nullptr);
-  std::vector<unsigned long long> counts((size_t)n_ranges, 0ull);
-  auto run = [&]() -> int32_t {
-    for (int32_t r = 0; r < n_ranges; ++r) {
-      const rgpu_host::PointsAnswer ans = plans[(size_t)r].answer;
-      const bool written_whole = ans == rgpu_host::POINTS_EVERY_DOC || (ans == rgpu_host::POINTS_SCAN && C.dense);
-      RGPU_TRY(docset_new(seg, &sets[(size_t)r], !written_whole));
-    }
-    for (int32_t r = 0; r < n_ranges; ++r) {
-      const rgpu_host::PointsRangePlan& P = plans[(size_t)r];
-      if (P.answer != rgpu_host::POINTS_SCATTER) continue;
-      rgpu_docset* d = sets[(size_t)r];
-      const int64_t m = P.i1 - P.i0;
-      HIP_TRY(hipMemsetAsync(d->d_count + 1, 0, 8, stream));
-      {
-        TimedLaunch tl(c, stream, "k_docset_from_docs", m);
-        RGPU_LAUNCH(k_docset_from_docs, dim3(wg_count(((unsigned long long)m + DOCSET_THREADS - 1) / DOCSET_THREADS)), dim3(DOCSET_THREADS), 0, stream,
-                    points->d_docs_by_value + P.i0, m, seg->max_doc, reinterpret_cast<uint32_t*>(d->d_words), reinterpret_cast<unsigned int*>(d->d_count + 1));
-      }
-      HIP_TRY(launch_status());
-    }
-    for (const std::vector<int32_t>& pass : passes) {
-      if (C.bytes_per_dim == 4) RGPU_TRY(C.dense ? (points_scan_launch<uint32_t, true>(points, plans, pass, sets, stream)) : (points_scan_launch<uint32_t, false>(points, plans, pass, sets, stream)));
-      else RGPU_TRY(C.dense ? (points_scan_launch<uint64_t, true>(points, plans, pass, sets, stream)) : (points_scan_launch<uint64_t, false>(points, plans, pass, sets, stream)));
-    }
-    // the count of every set (an every-doc set is formed by the same launch); one synchronisation for the call
-    for (int32_t r = 0; r < n_ranges; ++r) {
-      rgpu_docset* d = sets[(size_t)r];
-      const uint64_t* self[1] = {d->d_words};
-      const bool all = plans[(size_t)r].answer == rgpu_host::POINTS_EVERY_DOC;
-      RGPU_TRY(docset_combine_launch(c, stream, d->max_doc, self, all ? 0 : 1, nullptr, 0, nullptr, d->d_words, d->d_count));
-      HIP_TRY(hipMemcpyAsync(&counts[(size_t)r], d->d_count, 8, hipMemcpyDeviceToHost, stream));
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    return RGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc != RGPU_OK) {
-    (void)hipStreamSynchronize(stream);
-    for (rgpu_docset* d : sets) docset_delete(d);
-    return rc;
-  }
-  for (int32_t r = 0; r < n_ranges; ++r) { sets[(size_t)r]->cardinality = (int64_t)counts[(size_t)r]; out_sets[r] = sets[(size_t)r]; }
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_docset_collect_batch(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
-                                             int32_t n_terms_total, rgpu_docset** out_sets) {
-  if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !out_sets) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  for (int32_t q = 0; q < n_queries; ++q) out_sets[q] = nullptr;
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t stream = c->stream;
-  // ---- plan: refusals come before anything is allocated
-  std::vector<rgpu_host::DocsetQueryPlan> plans((size_t)n_queries);
-  std::vector<const rgpu_term_state*> ptrs;
-  bool any_conj = false;
-  for (int32_t q = 0; q < n_queries; ++q) {
-    plans[(size_t)q] = rgpu_host::plan_docset_query(queries[q], terms, n_terms_total);
-    const rgpu_host::DocsetQueryPlan& P = plans[(size_t)q];
-    if (P.status != RGPU_OK) return fail(P.status, P.why);
-    for (const std::vector<const rgpu_term_state*>* side : {&P.positive, &P.negative})
-      for (const rgpu_term_state* st : *side) {
-        RGPU_TRY(validate_state(seg, *st));
-        if (st->doc_freq == 1 && (st->singleton_doc_id < 0 || st->singleton_doc_id >= seg->max_doc)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "singleton_doc_id out of range");
-        ptrs.push_back(st);
-      }
-    any_conj = any_conj || P.conjunction;
-  }
-  if (any_conj && c->n_sim_tables <= 0)
-    return fail(RGPU_ERR_ILLEGAL_STATE, "collecting a conjunction runs the search's conjunction kernel: upload a similarity table first (rgpu_sim_table_upload)");
-  // (a conjunction's lead is walked with its posting-order norms, as in a search; the list kernel needs the blocks alone)
-  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size(), any_conj));
-  std::vector<rgpu_docset*> sets((size_t)n_queries, nullptr);
-  auto drop = [&](int32_t rc) { (void)hipStreamSynchronize(stream); for (rgpu_docset* d : sets) docset_delete(d); return rc; };
-  for (int32_t q = 0; q < n_queries; ++q) { const int32_t rc = docset_new(seg, &sets[(size_t)q]); if (rc != RGPU_OK) return drop(rc); }
-  std::vector<uint32_t*> rows((size_t)n_queries);
-  for (int32_t q = 0; q < n_queries; ++q) rows[(size_t)q] = reinterpret_cast<uint32_t*>(sets[(size_t)q]->d_words);
-  const SegView sv = seg_view(seg);
-  const bool legacy = seg->version < 1;
-  auto lists = [&]() -> int32_t {  // ---- TERM / OR rows: bits set list by list, then the MUST_NOT lists cleared
-    const rgpu_host::DocsetJobs J = rgpu_host::plan_docset_jobs(plans, DOCSET_BLOCKS_PER_ITEM);
-    if (J.set.empty()) return RGPU_OK;
-    std::vector<DevTerm> dt;
-    std::vector<DocsetJob> js, jc;
-    std::vector<int64_t> ps, pc;
-    int64_t postings = 0;
-    for (const std::vector<rgpu_host::DocsetListJob>* side : {&J.set, &J.clear})
-      for (const rgpu_host::DocsetListJob& j : *side) {
-        dt.emplace_back();
-        RGPU_TRY(make_dev_term(seg, *j.term, 0.0f, 0, &dt.back(), false));
-        // (the plan sized the job from doc_freq; the prepared term must agree, or items would run past its blocks)
-        if (rgpu_host::docset_term_items(dt.back().df, DOCSET_BLOCKS_PER_ITEM) != j.n_items || (dt.back().df >= 2 && dt.back().nblocks != dt.back().df / 128))
-          return fail(RGPU_ERR_ILLEGAL_STATE, "internal: a prepared term disagrees with its doc_freq");
-        (side == &J.set ? js : jc).push_back(DocsetJob{(uint32_t)(dt.size() - 1), (uint32_t)j.row});
-        (side == &J.set ? ps : pc).push_back(j.first_item);
-        postings += j.term->doc_freq;
-      }
-    ps.push_back(J.set_items);
-    pc.push_back(J.clear_items);
-    SCRATCH_TAKE(c);
-    Stager st(c);
-    const auto r_t = st.add<DevTerm>(dt.size());
-    const auto r_js = st.add<DocsetJob>(js.size()), r_jc = st.add<DocsetJob>(std::max<size_t>(1, jc.size()));
-    const auto r_ps = st.add<int64_t>(ps.size()), r_pc = st.add<int64_t>(pc.size());
-    const auto r_rows = st.add<uint32_t*>(rows.size());
-    STAGE_SIZED(sg, st);
-    sg.put(r_t, dt);
-    sg.put(r_js, js);
-    sg.put(r_jc, jc);
-    sg.put(r_ps, ps);
-    sg.put(r_pc, pc);
-    sg.put(r_rows, rows);
-    RGPU_TRY(sg.upload(stream));
-    {
-      TimedLaunch tl(c, stream, "k_docset_lists", postings);
-      const unsigned grid = wg_count(((unsigned long long)J.set_items + DOCSET_WAVES - 1) / DOCSET_WAVES);
-      if (legacy) RGPU_LAUNCH((k_docset_lists<true, false>), dim3(grid), dim3(DOCSET_THREADS), 0, stream, sv, (const DevTerm*)sg.dev(r_t), (const DocsetJob*)sg.dev(r_js),
-                              (const int64_t*)sg.dev(r_ps), (int)js.size(), J.set_items, (uint32_t* const*)sg.dev(r_rows));
-      else RGPU_LAUNCH((k_docset_lists<false, false>), dim3(grid), dim3(DOCSET_THREADS), 0, stream, sv, (const DevTerm*)sg.dev(r_t), (const DocsetJob*)sg.dev(r_js),
-                       (const int64_t*)sg.dev(r_ps), (int)js.size(), J.set_items, (uint32_t* const*)sg.dev(r_rows));
-    }
-    if (!jc.empty()) {
-      TimedLaunch tl(c, stream, "k_docset_lists", 0);
-      const unsigned grid = wg_count(((unsigned long long)J.clear_items + DOCSET_WAVES - 1) / DOCSET_WAVES);
-      if (legacy) RGPU_LAUNCH((k_docset_lists<true, true>), dim3(grid), dim3(DOCSET_THREADS), 0, stream, sv, (const DevTerm*)sg.dev(r_t), (const DocsetJob*)sg.dev(r_jc),
-                              (const int64_t*)sg.dev(r_pc), (int)jc.size(), J.clear_items, (uint32_t* const*)sg.dev(r_rows));
-      else RGPU_LAUNCH((k_docset_lists<false, true>), dim3(grid), dim3(DOCSET_THREADS), 0, stream, sv, (const DevTerm*)sg.dev(r_t), (const DocsetJob*)sg.dev(r_jc),
-                       (const int64_t*)sg.dev(r_pc), (int)jc.size(), J.clear_items, (uint32_t* const*)sg.dev(r_rows));
-    }
-    HIP_TRY(launch_status());
-    HIP_TRY(scratch_mark(c, stream));
-    return RGPU_OK;
-  };
-  auto conjunctions = [&]() -> int32_t {  // ---- AND rows: k_search_and emits the matches (deleted docs included, marked), scattered into bits
-    if (!any_conj) return RGPU_OK;
-    const size_t nq = (size_t)n_queries;
-    std::vector<DevQuery> dq(nq, DevQuery{RGPU_OP_AND, 0, 0, 0});
-    std::vector<DevTerm> dt;
-    std::vector<int64_t> item_prefix(nq + 1), emit_prefix(nq + 1);
-    int64_t lead_blocks = 0;
-    for (const rgpu_host::DocsetQueryPlan& P : plans) if (P.conjunction) lead_blocks += P.positive[0]->doc_freq / 128;
-    const int blocks_per_item = and_item_blocks(c, lead_blocks);
-    int64_t items = 0, slots = 0;
-    bool any_not = false;
-    for (size_t q = 0; q < nq; ++q) {
-      const rgpu_host::DocsetQueryPlan& P = plans[q];
-      item_prefix[q] = items;
-      emit_prefix[q] = slots;
-      dq[q].first_term = (int32_t)dt.size();
-      if (!P.conjunction) continue;
-      int32_t sim = terms[queries[q].first_term].sim_table;  // (an emitting conjunction loads its lead's table and scores nothing)
-      if (sim < 0 || sim >= c->n_sim_tables) sim = 0;
-      dq[q] = DevQuery{RGPU_OP_AND, (int32_t)P.positive.size(), (int32_t)dt.size(), (int32_t)P.negative.size()};
-      for (const rgpu_term_state* st : P.positive) { dt.emplace_back(); RGPU_TRY(make_dev_term(seg, *st, 0.0f, sim, &dt.back())); }
-      for (const rgpu_term_state* st : P.negative) { dt.emplace_back(); RGPU_TRY(make_dev_term(seg, *st, 0.0f, sim, &dt.back())); }
-      any_not = any_not || !P.negative.empty();
-      const DevTerm& lead = dt[(size_t)dq[q].first_term];
-      items += lead_items(lead, blocks_per_item);
-      slots += lead_slots(lead);
-    }
-    item_prefix[nq] = items;
-    emit_prefix[nq] = slots;
-    if (items == 0) return RGPU_OK;
-    SCRATCH_TAKE(c);
-    Stager st(c);
-    const auto r_q = st.add<DevQuery>(nq);
-    const auto r_t = st.add<DevTerm>(dt.size());
-    const auto r_ip = st.add<int64_t>(nq + 1), r_ep = st.add<int64_t>(nq + 1);
-    const auto r_rows = st.add<uint32_t*>(rows.size());
-    STAGE_SIZED(sg, st);
-    sg.put(r_q, dq);
-    sg.put(r_t, dt);
-    sg.put(r_ip, item_prefix);
-    sg.put(r_ep, emit_prefix);
-    sg.put(r_rows, rows);
-    RGPU_TRY(sg.upload(stream));
-    // (no clause bitmaps: every clause is walked; nothing is collected: k_emit 1, the narrowest kind of list)
-    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{"k_search_and(doc set candidates)", sg.dev(r_q), sg.dev(r_t), sg.dev(r_ip), sg.dev(r_ep), nullptr, n_queries, nq,
-                                                      items, slots, blocks_per_item, 1, any_not, 0, 0}));
-    if (slots > 0) {
-      TimedLaunch tl(c, stream, "k_docset_from_emitted", 0);
-      RGPU_LAUNCH(k_docset_from_emitted, dim3(wg_count(((unsigned long long)slots + DOCSET_THREADS - 1) / DOCSET_THREADS)), dim3(DOCSET_THREADS), 0, stream,
-                  (const int32_t*)c->phrase_docs.p, (const int64_t*)sg.dev(r_ep), (const unsigned long long*)c->phrase_count.p, (int)n_queries, slots, seg->max_doc,
-                  (uint32_t* const*)sg.dev(r_rows));
-    }
-    HIP_TRY(launch_status());
-    HIP_TRY(scratch_mark(c, stream));
-    return RGPU_OK;
-  };
-  int32_t rc = lists();
-  if (rc == RGPU_OK) rc = conjunctions();
-  for (int32_t q = 0; q < n_queries && rc == RGPU_OK; ++q) rc = docset_finish(sets[(size_t)q], stream);
-  if (rc != RGPU_OK) return drop(rc);
-  for (int32_t q = 0; q < n_queries; ++q) out_sets[q] = sets[(size_t)q];
-  return RGPU_OK;
-}
-
-// ---- masked search -----------------------------------------------------------------------------------------------------------------
-// The mask of a masked call: the set itself when the segment has no deletions, else `live AND set`, formed by k_docset_combine the
-// first time the set is used and kept (segments are immutable). Ends synchronised when it forms one, so that any stream may read it.
-static int32_t docset_mask_locked(rgpu_segment* seg, rgpu_docset* set, const uint64_t** mask_out) {
-  if (!seg->d_live) { *mask_out = set->d_words; return RGPU_OK; }
-  if (!set->d_mask) {
-    rgpu_ctx* c = seg->ctx;
-    uint64_t* m = nullptr;
-    HIP_TRY(hipMalloc(&m, docset_alloc_bytes(set->n_words)));
-    const uint64_t* self[1] = {set->d_words};
-    int32_t rc = hipMemsetAsync(m, 0, docset_alloc_bytes(set->n_words), c->stream) == hipSuccess ? RGPU_OK : fail(RGPU_ERR_RUNTIME, "memset of a doc set's mask failed");
-    if (rc == RGPU_OK) rc = docset_combine_launch(c, c->stream, set->max_doc, self, 1, nullptr, 0, seg->d_live, m, set->d_count + 1);
-    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == RGPU_OK) rc = fail(RGPU_ERR_RUNTIME, "forming a doc set's mask failed");
-    if (rc != RGPU_OK) { (void)hipFree(m); return rc; }
-    set->d_mask = m;
-  }
-  *mask_out = set->d_mask;
-  return RGPU_OK;
-}
-// installs the mask for the rest of the scope. Before it: closures pending from earlier (unmasked, or differently masked) calls are
-// settled — a redo they launch reads the segment's live docs as they were when the batch was enqueued. Inside it nothing is deferred
-// (the entry points leave defer_or false), so no closure of a masked call ever runs outside its scope.
-struct MaskScope {
-  rgpu_segment* seg;
-  MaskScope(rgpu_segment* s, const uint64_t* mask) : seg(s) { seg->call_mask = mask; }
-  ~MaskScope() { seg->call_mask = nullptr; }
-};
-// one event per masked call behind its work on `s`: rgpu_docset_free waits for them (events seen finished are recycled here)
-static void docset_mark_in_flight(rgpu_docset* set, hipStream_t s) {
-  size_t kept = 0;
-  hipEvent_t ev = nullptr;
-  for (hipEvent_t e : set->in_flight) {
-    if (hipEventQuery(e) == hipSuccess) { if (!ev) ev = e; else (void)hipEventDestroy(e); }
-    else set->in_flight[kept++] = e;
-  }
-  (void)hipGetLastError();  // (hipErrorNotReady of the queries is not an error)
-  set->in_flight.resize(kept);
-  if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipStreamSynchronize(s); return; }
-  if (hipEventRecord(ev, s) == hipSuccess) set->in_flight.push_back(ev);
-  else { (void)hipEventDestroy(ev); (void)hipStreamSynchronize(s); }
-}
-
-// The masked exact-phrase calls (rgpu_search_phrase_batch_masked, _phrase_bool_batch_masked, _phrase_or_batch_masked): what each does
-// under the context's mutex before its first launch - closures pending from earlier calls settled, `live AND set` formed (once, kept)
-// and installed for the rest of the call. `set` null: the unmasked call, nothing happens. The caller has refused sloppy phrases
-// already: an exact phrase under a mask is the phrase on a leaf whose live docs are the mask, a sloppy one is not (next_limit counts
-// deleted docs, not docs outside the filter).
-struct PhraseMask {
-  rgpu_segment* seg = nullptr;
-  rgpu_docset* set = nullptr;
-  ~PhraseMask() { if (seg) { seg->call_mask = nullptr; docset_mark_in_flight(set, seg->ctx->stream); } }
-  int32_t install(rgpu_segment* s, rgpu_docset* d) {
-    if (!d) return RGPU_OK;
-    rgpu_ctx* c = s->ctx;
-    RGPU_TRY(settle_pending(c));
-    const uint64_t* mask = nullptr;
-    RGPU_TRY(docset_mask_locked(s, d, &mask));
-    c->defer_or = false;  // a masked call never defers
-    s->call_mask = mask;
-    seg = s;
-    set = d;
-    return RGPU_OK;
-  }
-  bool on() const { return seg != nullptr; }
-};
-// the launch names of the candidate stage under a mask: the compacting instantiation's own, the marking one's own (RGPU_PHRASE_MASK_COMPACT=0);
-// rgpu_kernel_stat::name holds 47 characters
-static const char* masked_stage_name(const rgpu_ctx* c, const char* compact, const char* marked) { return c->phrase_mask_compact ? compact : marked; }
-static int32_t refuse_sloppy_masked(const rgpu_phrase_query* phrases, int32_t n) {
-  for (int32_t i = 0; i < n; ++i)
-    if (phrases[i].slop > 0) return fail(RGPU_ERR_UNSUPPORTED, "a sloppy phrase under a doc set is not served: next_limit counts deleted docs, not docs outside the filter");
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_search_batch_device_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_query* queries, int32_t n_queries,
-                                                   const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, void* hits_dev,
-                                                   void* totals_dev, void* hip_stream) {
-  if (!seg || !set || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !hits_dev || !totals_dev)
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  RGPU_TRY(docset_check(seg, set));
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  RGPU_TRY(settle_pending(c));
-  const uint64_t* mask = nullptr;
-  RGPU_TRY(docset_mask_locked(seg, set, &mask));
-  c->defer_or = false;  // a masked call never defers: its redo would run later, outside the scope
-  int32_t rc;
-  {
-    MaskScope scope(seg, mask);
-    rc = search_impl(seg, queries, n_queries, terms, n_terms_total, k, (HitOut*)hits_dev, (int64_t*)totals_dev, s);
-  }
-  docset_mark_in_flight(set, s);
-  return rc;
-}
-
-extern "C" int32_t rgpu_search_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_query* queries, int32_t n_queries,
-                                            const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
-                                            int64_t* total_hits_out) {
-  if (!seg || !set || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !hits_out || !total_hits_out)
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
-  RGPU_TRY(docset_check(seg, set));
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  RGPU_TRY(settle_pending(c));
-  const uint64_t* mask = nullptr;
-  RGPU_TRY(docset_mask_locked(seg, set, &mask));
-  c->defer_or = false;
-  MaskScope scope(seg, mask);
-  return search_batch_host_locked(seg, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out);
-}
-
-// ---- hit counts without scoring (include/rucene_gpu.h rgpu_count_batch; the plan: host/count_plan.hpp; the kernels:
-// kernels/count.hpp) -----------------------------------------------------------------------------------------------------------------
-// IndexSearcher::count (search/searcher.rs:632-654): counts[q] = the docs of `live AND set` row q matches in this leaf. Launch sequence:
-//   term preparation as a search (only what is not prepared yet); a memset of the row counters;
-//   k_count_lists     when some row is a LIST row
-//   k_count_windows   when some row is a WINDOWS row (one launch: the bit or the counter form is a row's own)
-//   k_search_and in emit mode (and_emit_stage, "k_search_and(count candidates)") + k_count_emitted   when some row is a CONJ row
-//   one copy of the counters back; the call returns synchronised. A batch of ZERO and DOC_FREQ rows alone launches nothing.
-extern "C" int32_t rgpu_count_batch(rgpu_segment* seg, rgpu_docset* set_or_null, const rgpu_query* queries, int32_t n_queries,
-                                    const rgpu_query_term* terms, int32_t n_terms_total, int64_t* counts_out) {
-  if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !counts_out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (set_or_null) RGPU_TRY(docset_check(seg, set_or_null));
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t stream = c->stream;
-  // ---- plan: every refusal comes before anything is launched or written
-  rgpu_host::CountMask cm;
-  cm.deletions = seg->d_live != nullptr;
-  cm.set = set_or_null != nullptr;
-  cm.empty_set = set_or_null != nullptr && set_or_null->cardinality == 0;
-  const size_t nq = (size_t)n_queries;
-  std::vector<rgpu_host::CountRowPlan> plans(nq);
-  std::vector<const rgpu_term_state*> ptrs;
-  bool any_list = false, any_conj = false, any_windows = false;
-  for (size_t q = 0; q < nq; ++q) {
-    plans[q] = rgpu_host::plan_count_query(queries[q], terms, n_terms_total, cm);
-    const rgpu_host::CountRowPlan& P = plans[q];
-    if (P.status != RGPU_OK) return fail(P.status, P.why);
-    for (const std::vector<rgpu_host::CountClause>* side : {&P.positive, &P.negative})
-      for (const rgpu_host::CountClause& cl : *side) {
-        RGPU_TRY(validate_state(seg, *cl.term));
-        if (cl.term->doc_freq == 1 && (cl.term->singleton_doc_id < 0 || cl.term->singleton_doc_id >= seg->max_doc)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "singleton_doc_id out of range");
-        ptrs.push_back(cl.term);
-      }
-    any_list = any_list || P.kind == rgpu_host::COUNT_LIST;
-    any_conj = any_conj || P.kind == rgpu_host::COUNT_CONJ;
-    any_windows = any_windows || P.kind == rgpu_host::COUNT_WINDOWS;
-  }
-  if (any_conj && c->n_sim_tables <= 0)
-    return fail(RGPU_ERR_ILLEGAL_STATE, "counting a conjunction runs the search's conjunction kernel: upload a similarity table first (rgpu_sim_table_upload)");
-  if (!any_list && !any_conj && !any_windows) {  // ZERO and DOC_FREQ rows alone: the host knows
-    for (size_t q = 0; q < nq; ++q) counts_out[q] = plans[q].kind == rgpu_host::COUNT_DOC_FREQ ? plans[q].doc_freq : 0;
-    return RGPU_OK;
-  }
-  RGPU_TRY(settle_pending(c));  // (a deferred batch's redo reads scratch this call is about to take)
-  const uint64_t* mask64 = seg->d_live;
-  if (set_or_null) RGPU_TRY(docset_mask_locked(seg, set_or_null, &mask64));
-  const uint32_t* mask = reinterpret_cast<const uint32_t*>(mask64);
-  // (a conjunction's lead is walked with its posting-order norms, as in a search; the other kernels need the blocks alone)
-  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size(), any_conj));
-  HIP_TRY(c->count_rows.reserve(nq, 0, stream));
-  HIP_TRY(hipMemsetAsync(c->count_rows.p, 0, nq * 8, stream));
-  unsigned long long* const d_counts = c->count_rows.p;
-  const SegView sv = seg_view(seg);
-  const bool legacy = seg->version < 1;
-  auto dev_term = [&](const rgpu_term_state& st, std::vector<DevTerm>& dt) -> int32_t {
-    dt.emplace_back();
-    RGPU_TRY(make_dev_term(seg, st, 0.0f, 0, &dt.back(), false));
-    // (the items are sized from doc_freq; the prepared term must agree, or a wavefront would run past its blocks)
-    if (dt.back().df >= 2 && dt.back().nblocks != dt.back().df / 128) return fail(RGPU_ERR_ILLEGAL_STATE, "internal: a prepared term disagrees with its doc_freq");
-    return RGPU_OK;
-  };
-  auto lists = [&]() -> int32_t {  // ---- LIST rows
-    if (!any_list) return RGPU_OK;
-    std::vector<DevTerm> dt;
-    std::vector<CountJob> jobs;
-    std::vector<int64_t> prefix;
-    int64_t items = 0, postings = 0;
-    for (size_t q = 0; q < nq; ++q) {
-      if (plans[q].kind != rgpu_host::COUNT_LIST) continue;
-      const rgpu_term_state& st = *plans[q].positive[0].term;
-      RGPU_TRY(dev_term(st, dt));
-      jobs.push_back(CountJob{(uint32_t)(dt.size() - 1), (uint32_t)q});
-      prefix.push_back(items);
-      items += rgpu_host::docset_term_items(st.doc_freq, DOCSET_BLOCKS_PER_ITEM);
-      postings += st.doc_freq;
-    }
-    prefix.push_back(items);
-    SCRATCH_TAKE(c);
-    Stager st(c);
-    const auto r_t = st.add<DevTerm>(dt.size());
-    const auto r_j = st.add<CountJob>(jobs.size());
-    const auto r_p = st.add<int64_t>(prefix.size());
-    STAGE_SIZED(sg, st);
-    sg.put(r_t, dt);
-    sg.put(r_j, jobs);
-    sg.put(r_p, prefix);
-    RGPU_TRY(sg.upload(stream));
-    {
-      TimedLaunch tl(c, stream, "k_count_lists", postings);
-      const unsigned grid = wg_count(((unsigned long long)items + COUNT_WAVES - 1) / COUNT_WAVES);
-      if (legacy) RGPU_LAUNCH(k_count_lists<true>, dim3(grid), dim3(COUNT_THREADS), 0, stream, sv, (const DevTerm*)sg.dev(r_t), (const CountJob*)sg.dev(r_j),
-                              (const int64_t*)sg.dev(r_p), (int)jobs.size(), items, mask, d_counts);
-      else RGPU_LAUNCH(k_count_lists<false>, dim3(grid), dim3(COUNT_THREADS), 0, stream, sv, (const DevTerm*)sg.dev(r_t), (const CountJob*)sg.dev(r_j),
-                       (const int64_t*)sg.dev(r_p), (int)jobs.size(), items, mask, d_counts);
-    }
-    HIP_TRY(launch_status());
-    HIP_TRY(scratch_mark(c, stream));
-    return RGPU_OK;
-  };
-  auto windows = [&]() -> int32_t {  // ---- WINDOWS rows
-    if (!any_windows) return RGPU_OK;
-    std::vector<DevTerm> dt;
-    std::vector<CountRow> rows;
-    std::vector<CountClauseDev> cls;
-    int64_t postings = 0;
-    for (size_t q = 0; q < nq; ++q) {
-      const rgpu_host::CountRowPlan& P = plans[q];
-      if (P.kind != rgpu_host::COUNT_WINDOWS) continue;
-      rows.push_back(CountRow{(int32_t)cls.size(), (int32_t)P.positive.size(), (int32_t)P.negative.size(), P.need, P.need_not, (int32_t)q});
-      for (const std::vector<rgpu_host::CountClause>* side : {&P.positive, &P.negative})
-        for (const rgpu_host::CountClause& cl : *side) {
-          RGPU_TRY(dev_term(*cl.term, dt));
-          // a doc bitmap some search has built already is read in the bit form; this call builds none (that takes a similarity table)
-          const TermBitmap bm = P.bit_form() ? bitmap_of(seg, dt.back()) : NO_BITMAP;
-          cls.push_back(CountClauseDev{(uint32_t)(dt.size() - 1), (uint32_t)cl.mult, bm.words != nullptr ? bm.memb : nullptr});
-          postings += cl.term->doc_freq;
-        }
-    }
-    const int32_t per_item = rgpu_host::count_windows_per_item(seg->max_doc, COUNT_WINDOW_DOCS, (int64_t)rows.size(), 8192, c->count_windows_per_item);
-    const int64_t items_per_row = rgpu_host::count_window_items(seg->max_doc, COUNT_WINDOW_DOCS, per_item);
-    if (items_per_row <= 0) return RGPU_OK;  // (a segment without docs)
-    if (items_per_row > 0x7fffffff) return fail(RGPU_ERR_ILLEGAL_STATE, "internal: window items per row");
-    SCRATCH_TAKE(c);
-    Stager st(c);
-    const auto r_t = st.add<DevTerm>(dt.size());
-    const auto r_r = st.add<CountRow>(rows.size());
-    const auto r_c = st.add<CountClauseDev>(cls.size());
-    STAGE_SIZED(sg, st);
-    sg.put(r_t, dt);
-    sg.put(r_r, rows);
-    sg.put(r_c, cls);
-    RGPU_TRY(sg.upload(stream));
-    {
-      TimedLaunch tl(c, stream, "k_count_windows", postings);
-      const int64_t items = (int64_t)rows.size() * items_per_row;
-      const unsigned grid = wg_count(((unsigned long long)items + COUNT_WAVES - 1) / COUNT_WAVES);
-      if (legacy) RGPU_LAUNCH(k_count_windows<true>, dim3(grid), dim3(COUNT_THREADS), 0, stream, sv, (const DevTerm*)sg.dev(r_t), (const CountRow*)sg.dev(r_r),
-                              (const CountClauseDev*)sg.dev(r_c), (int)rows.size(), (int)items_per_row, (int)per_item, mask, d_counts);
-      else RGPU_LAUNCH(k_count_windows<false>, dim3(grid), dim3(COUNT_THREADS), 0, stream, sv, (const DevTerm*)sg.dev(r_t), (const CountRow*)sg.dev(r_r),
-                       (const CountClauseDev*)sg.dev(r_c), (int)rows.size(), (int)items_per_row, (int)per_item, mask, d_counts);
-    }
-    HIP_TRY(launch_status());
-    HIP_TRY(scratch_mark(c, stream));
-    return RGPU_OK;
-  };
-  auto conjunctions = [&]() -> int32_t {  // ---- CONJ rows: k_search_and emits the matches (deleted docs marked), counted against the mask
-    if (!any_conj) return RGPU_OK;
-    std::vector<DevQuery> dq(nq, DevQuery{RGPU_OP_AND, 0, 0, 0});
-    std::vector<DevTerm> dt;
-    std::vector<int64_t> item_prefix(nq + 1), emit_prefix(nq + 1);
-    int64_t lead_blocks = 0;
-    for (const rgpu_host::CountRowPlan& P : plans) if (P.kind == rgpu_host::COUNT_CONJ) lead_blocks += P.positive[0].term->doc_freq / 128;
-    const int blocks_per_item = and_item_blocks(c, lead_blocks);
-    int64_t items = 0, slots = 0;
-    bool any_not = false;
-    for (size_t q = 0; q < nq; ++q) {
-      const rgpu_host::CountRowPlan& P = plans[q];
-      item_prefix[q] = items;
-      emit_prefix[q] = slots;
-      dq[q].first_term = (int32_t)dt.size();
-      if (P.kind != rgpu_host::COUNT_CONJ) continue;
-      int32_t sim = terms[queries[q].first_term].sim_table;  // (an emitting conjunction loads its lead's table and scores nothing)
-      if (sim < 0 || sim >= c->n_sim_tables) sim = 0;
-      dq[q] = DevQuery{RGPU_OP_AND, (int32_t)P.positive.size(), (int32_t)dt.size(), (int32_t)P.negative.size()};
-      for (const std::vector<rgpu_host::CountClause>* side : {&P.positive, &P.negative})
-        for (const rgpu_host::CountClause& cl : *side) { dt.emplace_back(); RGPU_TRY(make_dev_term(seg, *cl.term, 0.0f, sim, &dt.back())); }
-      any_not = any_not || !P.negative.empty();
-      const DevTerm& lead = dt[(size_t)dq[q].first_term];
-      items += lead_items(lead, blocks_per_item);
-      slots += lead_slots(lead);
-    }
-    item_prefix[nq] = items;
-    emit_prefix[nq] = slots;
-    if (items == 0 || slots == 0) return RGPU_OK;
-    SCRATCH_TAKE(c);
-    Stager st(c);
-    const auto r_q = st.add<DevQuery>(nq);
-    const auto r_t = st.add<DevTerm>(dt.size());
-    const auto r_ip = st.add<int64_t>(nq + 1), r_ep = st.add<int64_t>(nq + 1);
-    STAGE_SIZED(sg, st);
-    sg.put(r_q, dq);
-    sg.put(r_t, dt);
-    sg.put(r_ip, item_prefix);
-    sg.put(r_ep, emit_prefix);
-    RGPU_TRY(sg.upload(stream));
-    // (no clause bitmaps: every clause is walked; nothing is collected: k_emit 1, the narrowest kind of list)
-    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{"k_search_and(count candidates)", sg.dev(r_q), sg.dev(r_t), sg.dev(r_ip), sg.dev(r_ep), nullptr, n_queries, nq,
-                                                      items, slots, blocks_per_item, 1, any_not, 0, 0}));
-    {
-      TimedLaunch tl(c, stream, "k_count_emitted", 0);
-      RGPU_LAUNCH(k_count_emitted, dim3(wg_count(((unsigned long long)slots + COUNT_THREADS - 1) / COUNT_THREADS)), dim3(COUNT_THREADS), 0, stream,
-                  (const int32_t*)c->phrase_docs.p, (const int64_t*)sg.dev(r_ep), (const unsigned long long*)c->phrase_count.p, (int)n_queries, slots, seg->max_doc,
-                  mask, d_counts);
-    }
-    HIP_TRY(launch_status());
-    HIP_TRY(scratch_mark(c, stream));
-    return RGPU_OK;
-  };
-  std::vector<unsigned long long> got(nq, 0ull);
-  auto run = [&]() -> int32_t {
-    RGPU_TRY(lists());
-    RGPU_TRY(windows());
-    RGPU_TRY(conjunctions());
-    HIP_TRY(hipMemcpyAsync(got.data(), d_counts, nq * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return RGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc != RGPU_OK) { (void)hipStreamSynchronize(stream); return rc; }
-  for (size_t q = 0; q < nq; ++q) {
-    const rgpu_host::CountRowPlan& P = plans[q];
-    counts_out[q] = P.kind == rgpu_host::COUNT_ZERO ? 0 : P.kind == rgpu_host::COUNT_DOC_FREQ ? P.doc_freq : (int64_t)got[q];
-  }
-  return RGPU_OK;
-}
-
-// ---- a doc set as the only required clause: "b c #F", a lone #F, *:* (include/rucene_gpu.h rgpu_docset_head,
-// rgpu_search_batch_required_set; the kernels: kernels/docset.hpp) -------------------------------------------------------------------
-// Launch sequences:
-//   head (first use of a set, or a larger n than before)   [k_docset_combine: live AND set, as a masked search] k_docset_chunk_counts,
-//                                                          k_docset_head_scan, k_docset_select_head (n > 0 and M not empty)
-//   rgpu_search_batch[_device]_required_set                [head] the masked search of the rows that have SHOULD clauses (k_init_hits
-//                                                          alone when none has), k_required_set_fill
-// The head of M = live AND set for at least n docs: |M| and the first min(n, |M|) docs, kept with the set. Ends synchronised when it
-// builds (any stream may read the head afterwards); a head that is replaced waits for the searches in flight that read the old one.
-static int32_t docset_head_locked(rgpu_segment* seg, rgpu_docset* set, int32_t n, const uint64_t* mask) {
-  if (set->head_n >= 0 && ((int64_t)set->head_n >= (int64_t)n || (int64_t)set->head_n >= set->live_cardinality)) return RGPU_OK;
-  rgpu_ctx* c = seg->ctx;
-  hipStream_t stream = c->stream;
-  const int64_t n_words = (int64_t)set->n_words;
-  const int64_t n_chunks = (n_words + DOCSET_HEAD_CHUNK_WORDS - 1) / DOCSET_HEAD_CHUNK_WORDS;
-  int32_t* head = nullptr;
-  uint8_t* work = nullptr;  // [n_chunks] i64 prefix, i64 total, [n_chunks] i32 counts
-  const size_t o_total = (size_t)n_chunks * 8, o_counts = o_total + 8, work_bytes = o_counts + (size_t)n_chunks * 4;
-  long long total = 0;
-  auto run = [&]() -> int32_t {
-    HIP_TRY(hipMalloc(&head, docset_head_alloc_bytes(n)));
-    if (n_chunks == 0) return RGPU_OK;
-    HIP_TRY(hipMalloc(&work, work_bytes));
-    long long* d_prefix = reinterpret_cast<long long*>(work);
-    long long* d_total = reinterpret_cast<long long*>(work + o_total);
-    int* d_counts = reinterpret_cast<int*>(work + o_counts);
-    {
-      TimedLaunch tl(c, stream, "k_docset_chunk_counts", 0);
-      RGPU_LAUNCH(k_docset_chunk_counts, dim3((unsigned)n_chunks), dim3(DOCSET_THREADS), 0, stream, mask, n_words, d_counts);
-    }
-    {
-      TimedLaunch tl(c, stream, "k_docset_head_scan", 0);
-      RGPU_LAUNCH(k_docset_head_scan, dim3(1), dim3(64), 0, stream, (const int*)d_counts, (int)n_chunks, d_prefix, d_total);
-    }
-    if (n > 0) {  // (a chunk whose prefix is at or past n, an empty M among them, returns at once)
-      TimedLaunch tl(c, stream, "k_docset_select_head", 0);
-      RGPU_LAUNCH(k_docset_select_head, dim3((unsigned)n_chunks), dim3(DOCSET_THREADS), 0, stream, mask, n_words, (const long long*)d_prefix, (int)n, head);
-    }
-    HIP_TRY(launch_status());
-    HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return RGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc != RGPU_OK) (void)hipStreamSynchronize(stream);
-  if (work) (void)hipFree(work);
-  if (rc != RGPU_OK) { if (head) (void)hipFree(head); return rc; }
-  if (set->d_head) {  // searches enqueued on other streams may still read the old head
-    for (hipEvent_t ev : set->in_flight) (void)hipEventSynchronize(ev);
-    (void)hipFree(set->d_head);
-  }
-  set->d_head = head;
-  set->head_n = n;
-  set->live_cardinality = (int64_t)total;
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_docset_head(rgpu_segment* seg, rgpu_docset* set, int32_t n, int32_t* docs_out, int32_t* n_out, int64_t* live_cardinality_out) {
-  if (!seg || !set || !n_out || !live_cardinality_out || n < 0 || (n > 0 && !docs_out)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (n > RGPU_MAX_K) return fail(RGPU_ERR_UNSUPPORTED, "a doc set's head holds at most RGPU_MAX_K docs");
-  RGPU_TRY(docset_check(seg, set));
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  const uint64_t* mask = nullptr;
-  RGPU_TRY(docset_mask_locked(seg, set, &mask));
-  RGPU_TRY(docset_head_locked(seg, set, n, mask));
-  const int32_t m = (int32_t)std::min<int64_t>(n, set->live_cardinality);
-  if (m > 0) HIP_TRY(hipMemcpy(docs_out, set->d_head, (size_t)m * 4, hipMemcpyDeviceToHost));
-  *n_out = m;
-  *live_cardinality_out = set->live_cardinality;
-  return RGPU_OK;
-}
-
-// The rows rgpu_search_batch_required_set accepts, as the masked search takes them: msm bytes cleared (ReqOptScorer only advance()s
-// the optional scorer), a row without an optional side as a TERM query of an absent term (appended to the clauses), which launches
-// nothing and leaves the row's defaults. `scored`: rows that have SHOULD clauses.
-struct RequiredSetRows {
-  std::vector<rgpu_query> queries;
-  std::vector<rgpu_query_term> terms;
-  int32_t scored = 0;
-};
-static int32_t required_set_rows(const rgpu_ctx* c, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms, int32_t n_terms_total,
-                                 RequiredSetRows* out) {
-  out->queries.assign(queries, queries + n_queries);
-  bool any_empty = false;
-  for (int32_t q = 0; q < n_queries; ++q) {
-    rgpu_query& Q = out->queries[(size_t)q];
-    const int qop = Q.op & 0xff;
-    if (qop < RGPU_OP_TERM || qop > RGPU_OP_DISMAX) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown query op");
-    if (qop != RGPU_OP_TERM && qop != RGPU_OP_OR) return fail(RGPU_ERR_UNSUPPORTED, "beside a required doc set: RGPU_OP_TERM or a flat RGPU_OP_OR (the SHOULD clauses)");
-    if ((Q.op & ~0xffff) != 0) return fail(RGPU_ERR_UNSUPPORTED, "beside a required doc set: no RGPU_OP_WITH_SHOULD, nested or required-SHOULD flags");
-    if (Q.n_must_not != 0) return fail(RGPU_ERR_UNSUPPORTED, "beside a required doc set: no MUST_NOT or demoting clauses (fold MUST_NOT terms into the set)");
-    Q.op = qop;  // the msm byte has no effect
-    if (Q.n_terms < 0 || Q.n_terms > RGPU_MAX_QUERY_TERMS || (qop == RGPU_OP_TERM && Q.n_terms != 1)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad clause count");
-    if (Q.n_terms == 0) { any_empty = true; continue; }
-    if (!terms || Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms > (int64_t)n_terms_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "clause range outside terms[]");
-    for (int i = 0; i < Q.n_terms; ++i) {
-      const float w = terms[Q.first_term + i].weight;
-      // a score of 0 in O would tie with the fill: a full row could hide zero-score docs with lower ids
-      if (!(std::isfinite(w) && w > 0.0f)) return fail(RGPU_ERR_UNSUPPORTED, "beside a required doc set a SHOULD clause's weight is finite and > 0");
-    }
-    ++out->scored;
-  }
-  if (out->scored > 0 && any_empty) {
-    if (c->n_sim_tables <= 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
-    out->terms.assign(terms, terms + n_terms_total);
-    rgpu_query_term absent;
-    std::memset(&absent, 0, sizeof absent);
-    absent.state.skip_offset = -1;
-    absent.state.singleton_doc_id = -1;
-    out->terms.push_back(absent);
-    for (rgpu_query& Q : out->queries)
-      if (Q.n_terms == 0) Q = rgpu_query{RGPU_OP_TERM, 1, n_terms_total, 0};
-  }
-  return RGPU_OK;
-}
-// mask installed by the caller's scope; rows to device memory, the fill enqueued behind the search on `s`
-static int32_t required_set_search_locked(rgpu_segment* seg, rgpu_docset* set, const RequiredSetRows& R, const rgpu_query_term* terms, int32_t n_terms_total,
-                                          int32_t k, HitOut* hits_dev, int64_t* totals_dev, hipStream_t s) {
-  rgpu_ctx* c = seg->ctx;
-  const int32_t n_queries = (int32_t)R.queries.size();
-  if (R.scored > 0) {
-    const bool own = !R.terms.empty();
-    RGPU_TRY(search_impl(seg, R.queries.data(), n_queries, own ? R.terms.data() : terms, own ? (int32_t)R.terms.size() : n_terms_total, k, hits_dev, totals_dev, s));
-  } else {
-    RGPU_LAUNCH(k_init_hits, dim3(wg_count(((size_t)n_queries * k + 255) / 256)), dim3(256), 0, s, hits_dev, (int64_t)n_queries, (int)k, (int)k, 0);
-  }
-  {
-    TimedLaunch tl(c, s, "k_required_set_fill", 0);
-    RGPU_LAUNCH(k_required_set_fill, dim3(wg_count(((unsigned long long)n_queries + REQUIRED_SET_FILL_WAVES - 1) / REQUIRED_SET_FILL_WAVES)),
-                dim3(64 * REQUIRED_SET_FILL_WAVES), 0, s, hits_dev, totals_dev, (int)n_queries, (int)k, (const int32_t*)set->d_head,
-                (int)std::min<int64_t>(std::min<int64_t>(set->head_n, set->live_cardinality), k), set->live_cardinality, seg->doc_base);
-  }
-  HIP_TRY(launch_status());
-  return RGPU_OK;
-}
-static_assert(REQUIRED_SET_MAX_HEAD == RGPU_MAX_K && DOCSET_HEAD_CHUNK_WORDS == RGPU_DOCSET_HEAD_CHUNK_WORDS, "kernels/docset.hpp follows include/rucene_gpu.h");
-
-extern "C" int32_t rgpu_search_batch_device_required_set(rgpu_segment* seg, rgpu_docset* set, const rgpu_query* queries, int32_t n_queries,
-                                                         const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, void* hits_dev,
-                                                         void* totals_dev, void* hip_stream) {
-  if (!seg || !set || !queries || n_queries <= 0 || n_terms_total < 0 || !hits_dev || !totals_dev) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
-  RGPU_TRY(docset_check(seg, set));
-  rgpu_ctx* c = seg->ctx;
-  RequiredSetRows R;
-  RGPU_TRY(required_set_rows(c, queries, n_queries, terms, n_terms_total, &R));
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  RGPU_TRY(settle_pending(c));
-  const uint64_t* mask = nullptr;
-  RGPU_TRY(docset_mask_locked(seg, set, &mask));
-  RGPU_TRY(docset_head_locked(seg, set, k, mask));
-  c->defer_or = false;  // never defers, as a masked call
-  int32_t rc;
-  {
-    MaskScope scope(seg, mask);
-    rc = required_set_search_locked(seg, set, R, terms, n_terms_total, k, (HitOut*)hits_dev, (int64_t*)totals_dev, s);
-  }
-  docset_mark_in_flight(set, s);
-  return rc;
-}
-
-extern "C" int32_t rgpu_search_batch_required_set(rgpu_segment* seg, rgpu_docset* set, const rgpu_query* queries, int32_t n_queries,
-                                                  const rgpu_query_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
-                                                  int64_t* total_hits_out) {
-  if (!seg || !set || !queries || n_queries <= 0 || n_terms_total < 0 || !hits_out || !total_hits_out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
-  RGPU_TRY(docset_check(seg, set));
-  rgpu_ctx* c = seg->ctx;
-  RequiredSetRows R;
-  RGPU_TRY(required_set_rows(c, queries, n_queries, terms, n_terms_total, &R));
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  RGPU_TRY(settle_pending(c));
-  const uint64_t* mask = nullptr;
-  RGPU_TRY(docset_mask_locked(seg, set, &mask));
-  RGPU_TRY(docset_head_locked(seg, set, k, mask));
-  c->defer_or = false;
-  HIP_TRY(c->host_api_hits.reserve((size_t)n_queries * (size_t)k, 0, c->stream));
-  HIP_TRY(c->host_api_totals.reserve((size_t)n_queries, 0, c->stream));
-  {
-    MaskScope scope(seg, mask);
-    RGPU_TRY(required_set_search_locked(seg, set, R, terms, n_terms_total, k, c->host_api_hits.p, c->host_api_totals.p, c->stream));
-  }
-  return api_rows_read_back(c, c->stream, n_queries, k, hits_out, total_hits_out);
-}
-
-extern "C" int32_t rgpu_merge_topk_device(rgpu_ctx* c, const void* hits_dev, const void* totals_dev, int32_t n_lists, int32_t n_queries,
-                                          int32_t k, void* hits_out_dev, void* totals_out_dev, void* hip_stream) {
-  if (!c || !hits_dev || !totals_dev || !hits_out_dev || !totals_out_dev || n_lists <= 0 || n_queries <= 0)
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "k must be in 1..RGPU_MAX_K");
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  {
-    TimedLaunch tl(c, s, "k_merge_lists", 0);
-    const unsigned grid = wg_count((n_queries + WG_WAVES - 1) / WG_WAVES);
-    if (k > 64)
-      RGPU_LAUNCH(k_merge_lists<true>, dim3(grid), dim3(WG_THREADS), 0, s, (const HitOut*)hits_dev, (const int64_t*)totals_dev,
-                         (int64_t)n_queries * k, (int64_t)n_queries, n_lists, n_queries, k, (HitOut*)hits_out_dev, (int64_t*)totals_out_dev);
-    else
-      RGPU_LAUNCH(k_merge_lists<false>, dim3(grid), dim3(WG_THREADS), 0, s, (const HitOut*)hits_dev, (const int64_t*)totals_dev,
-                         (int64_t)n_queries * k, (int64_t)n_queries, n_lists, n_queries, k, (HitOut*)hits_out_dev, (int64_t*)totals_out_dev);
-  }
-  HIP_TRY(launch_status());
-  return RGPU_OK;  // enqueue only, like rgpu_search_batch_device
-}
-
-// ---- exact phrases -----------------------------------------------------------------------------------------------------------
-extern "C" int32_t rgpu_segment_attach_positions(rgpu_segment* seg, const uint8_t* pos_file, size_t pos_len) {
-  if (!seg || !pos_file) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (!seg->has_positions) return fail(RGPU_ERR_ILLEGAL_STATE, "the segment was not uploaded as a positions field (index_options >= 3)");
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  std::vector<uint8_t> head(128);
-  const size_t head_n = std::min(seg->doc_len, head.size());
-  HIP_TRY(hipMemcpy(head.data(), seg->d_doc, head_n, hipMemcpyDeviceToHost));  // the .doc header: id + suffix to compare with
-  int64_t start = 0;
-  std::string why;
-  const int rc = rucene::parse_pos_file(pos_file, pos_len, head.data(), seg->version, &start, &why);
-  if (rc != 0) return fail(rc, why);
-  if (seg->d_pos) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(seg->d_pos); seg->d_pos = nullptr; }
-  const size_t pad = 8192;  // speculative row / VInt-block loads may run past the last position byte
-  HIP_TRY(hipMalloc(&seg->d_pos, pos_len + pad));
-  HIP_TRY(hipMemcpy(seg->d_pos, pos_file, pos_len, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(seg->d_pos + pos_len, 0, pad));
-  seg->pos_len = pos_len;
-  return RGPU_OK;
-}
-
-// Lucene50PostingsReader::open's third file (posting_reader.rs:131-156). Nothing on this path reads payload bytes or offsets
-// (phrase scorers ask for positions only and get the iterator that walks past them, :189-212), so the file is checked — header,
-// version, segment id / suffix, footer — as open() checks it, and not kept.
-extern "C" int32_t rgpu_segment_attach_payloads(rgpu_segment* seg, const uint8_t* pay_file, size_t pay_len) {
-  if (!seg || !pay_file) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (!seg->has_offsets && !seg->has_payloads)
-    return fail(RGPU_ERR_ILLEGAL_STATE, "the segment's field stores neither payloads nor offsets (index_options 4 / RGPU_FIELD_STORES_PAYLOADS)");
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  std::vector<uint8_t> head(128);
-  const size_t head_n = std::min(seg->doc_len, head.size());
-  HIP_TRY(hipMemcpy(head.data(), seg->d_doc, head_n, hipMemcpyDeviceToHost));
-  int64_t start = 0;
-  std::string why;
-  const int rc = rucene::parse_pay_file(pay_file, pay_len, head.data(), seg->version, &start, &why);
-  if (rc != 0) return fail(rc, why);
-  seg->pay_checked = true;
-  return RGPU_OK;
-}
-
-// BlockPostingIterator::{next, next_position} to exhaustion for every given term (kernels/decode_positions.hpp): ends synchronised
-// where a term's positions lie in .pos (a phrase's planner adds phrase_pos / query_ord / same_as: emit_phrase)
-static PosTerm pos_term_of(const rgpu_term_state& st, const rgpu_term_positions& pos) {
-  PosTerm p{};
-  p.pos_start_fp = (uint64_t)pos.pos_start_fp;
-  p.total_term_freq = st.total_term_freq;
-  // posting_reader.rs:1195-1203: fewer than 128 positions -> all VInts; exactly 128 -> one packed block, no trailing one
-  p.last_pos_block_fp = st.total_term_freq < 128 ? pos.pos_start_fp : (st.total_term_freq == 128 ? -1 : pos.pos_start_fp + pos.last_pos_block_offset);
-  return p;
-}
-
-static int32_t decode_positions_impl(rgpu_segment* seg, const rgpu_term_state* terms, const rgpu_term_positions* positions, int64_t n_terms,
-                                     int32_t* positions_dev, hipStream_t stream) {
-  rgpu_ctx* c = seg->ctx;
-  if (!seg->has_positions || !seg->d_pos) return fail(RGPU_ERR_ILLEGAL_STATE, "a positions decode needs a positions field with its .pos file attached");
-  std::vector<const rgpu_term_state*> ptrs;
-  int64_t expect = 0;
-  for (int64_t i = 0; i < n_terms; ++i) {
-    const rgpu_term_state& st = terms[i];
-    if (st.doc_freq < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "negative doc_freq");
-    if (st.doc_freq == 0) continue;
-    if (st.total_term_freq < st.doc_freq) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "total_term_freq below doc_freq");
-    if (positions[i].pos_start_fp < 0 || (size_t)positions[i].pos_start_fp >= seg->pos_len) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "pos_start_fp outside the .pos file");
-    expect += st.total_term_freq;
-    ptrs.push_back(&st);
-  }
-  if (expect == 0) return RGPU_OK;
-  if (expect > 0xfffffff0ll) return fail(RGPU_ERR_UNSUPPORTED, "one call decodes at most 2^32 positions: split the term list");
-  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size(), false));  // stage A: directory (with dir_pos), block store, tails
-  std::vector<DevTerm> dt;
-  std::vector<PosTerm> pt;
-  std::vector<int64_t> item_prefix;
-  int64_t items = 0;
-  for (int64_t i = 0; i < n_terms; ++i) {
-    const rgpu_term_state& st = terms[i];
-    if (st.doc_freq == 0) continue;
-    DevTerm d;
-    RGPU_TRY(make_dev_term(seg, st, 0.f, 0, &d, false));
-    dt.push_back(d);
-    pt.push_back(pos_term_of(st, positions[i]));
-    item_prefix.push_back(items);
-    items += (int64_t)d.nblocks + ((d.df == 1 || d.tail_n > 0) ? 1 : 0);
-  }
-  item_prefix.push_back(items);
-  const int nt = (int)dt.size();
-  SCRATCH_TAKE(c);
-  Stager st(c);
-  const auto r_t = st.add<DevTerm>(dt.size());
-  const auto r_pt = st.add<PosTerm>(pt.size());
-  const auto r_ip = st.add<int64_t>(item_prefix.size());
-  STAGE_SIZED(sg, st);
-  sg.put(r_t, dt);
-  sg.put(r_pt, pt);
-  sg.put(r_ip, item_prefix);
-  RGPU_TRY(sg.upload(stream));
-  const int64_t n_tiles = (items + SCAN_TILE - 1) / SCAN_TILE;
-  HIP_TRY(c->pos_counts.reserve((size_t)items + 64, 0, stream));
-  HIP_TRY(c->pos_tiles.reserve((size_t)n_tiles + 8, 0, stream));
-  HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(int), stream));
-  const DevTerm* d_t = sg.dev(r_t);
-  const PosTerm* d_pt = sg.dev(r_pt);
-  const int64_t* d_ip = sg.dev(r_ip);
-  unsigned long long* d_tiles = c->pos_tiles.p + 8;
-  unsigned long long* d_total = c->pos_tiles.p + 1;
-  const SegView sv = seg_view(seg);
-  const bool legacy = seg->version < 1;
-  const unsigned grid = wg_count((items + WG_WAVES - 1) / WG_WAVES);
-  {
-    TimedLaunch tl(c, stream, "k_pos_counts", expect);
-    if (legacy) RGPU_LAUNCH(k_pos_counts<true>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, d_t, d_ip, nt, items, c->pos_counts.p);
-    else RGPU_LAUNCH(k_pos_counts<false>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, d_t, d_ip, nt, items, c->pos_counts.p);
-  }
-  {
-    TimedLaunch tl(c, stream, "k_scan_rows", 0);
-    RGPU_LAUNCH(k_scan_reduce, dim3((unsigned)n_tiles), dim3(PREP_THREADS), 0, stream, c->pos_counts.p, items, d_tiles);
-    RGPU_LAUNCH(k_scan_tiles, dim3(1), dim3(PREP_THREADS), 0, stream, d_tiles, n_tiles, (unsigned long long)expect, d_total, c->d_err);
-    RGPU_LAUNCH(k_scan_down, dim3((unsigned)n_tiles), dim3(PREP_THREADS), 0, stream, c->pos_counts.p, items, d_tiles);
-  }
-  {
-    TimedLaunch tl(c, stream, "k_decode_positions", expect);
-    if (legacy)
-      RGPU_LAUNCH(k_decode_positions<true>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, d_t, d_pt, d_ip, nt, items, c->pos_counts.p,
-                         (int64_t)seg->pos_len, positions_dev, c->d_err);
-    else
-      RGPU_LAUNCH(k_decode_positions<false>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, d_t, d_pt, d_ip, nt, items, c->pos_counts.p,
-                         (int64_t)seg->pos_len, positions_dev, c->d_err);
-  }
-  int err4[4] = {0, 0, 0, 0};
-  unsigned long long total = 0;
-  HIP_TRY(hipMemcpyAsync(err4, c->d_err, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  HIP_TRY(launch_status());
-  if (err4[0] != 0 || total != (unsigned long long)expect)
-    return fail(RGPU_ERR_CORRUPT_INDEX, total != (unsigned long long)expect ? "the postings' freqs do not add up to total_term_freq" : "corrupt position data in .pos");
-  return RGPU_OK;
-}
-
-extern "C" int32_t rgpu_decode_positions_device(rgpu_segment* seg, const rgpu_term_state* terms, const rgpu_term_positions* positions, int64_t n_terms,
-                                                void* positions_dev, void* hip_stream) {
-  if (!seg || !terms || !positions || n_terms <= 0 || !positions_dev) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  std::lock_guard<std::mutex> g(seg->ctx->mu);
-  HIP_TRY(hipSetDevice(seg->ctx->device));
-  return decode_positions_impl(seg, terms, positions, n_terms, (int32_t*)positions_dev, hip_stream ? (hipStream_t)hip_stream : seg->ctx->stream);
-}
-
-extern "C" int32_t rgpu_decode_positions(rgpu_segment* seg, const rgpu_term_state* terms, const rgpu_term_positions* positions, int64_t n_terms,
-                                         int32_t* positions_out) {
-  if (!seg || !terms || !positions || n_terms <= 0 || !positions_out) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  int64_t total = 0;
-  for (int64_t i = 0; i < n_terms; ++i) if (terms[i].doc_freq > 0) total += std::max<int64_t>(0, terms[i].total_term_freq);
-  if (total == 0) return RGPU_OK;
-  int32_t* d_pos = nullptr;
-  HIP_TRY(hipMalloc(&d_pos, (size_t)total * 4));
-  int32_t rc = decode_positions_impl(seg, terms, positions, n_terms, d_pos, c->stream);
-  if (rc == RGPU_OK && hipMemcpy(positions_out, d_pos, (size_t)total * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(RGPU_ERR_RUNTIME, "device to host copy failed");
-  (void)hipFree(d_pos);
-  return rc;
-}
-
-// ---- the match stage of a phrase search: one key per candidate slot into c->phrase_keys ------------------------------------------
-// The kernels read an array of candidate slots (emit_prefix / emit_count / emit_docs = c->phrase_count / c->phrase_docs) and do not
-// care what filled it: and_emit_stage (the conjunction of rgpu_search_phrase_batch, _phrase_bool_batch and _phrase_or_batch) or
-// k_rescore_phrase_candidates (the window of rgpu_rescore_phrase_batch). phrase_match_setup has run in front of whatever fills
-// the slots (and_emit_stage runs it; a rescoring calls it): it reserves c->phrase_docs, c->phrase_keys and c->phrase_redo (redo_cap slots) and zeroes c->d_err. What
-// comes behind the stage: phrase_collect_stage, k_phrase_bool_score, the run-building kernels of a disjunction,
-// k_rescore_phrase_combine; the callers read the verdict, d_err[0], afterwards (phrase_match_status).
-struct PhraseMatchStage {
-  const DevQuery* d_q;
-  const DevTerm* d_t;
-  const PosTerm* d_pt;
-  const int64_t* d_ep;
-  const int32_t* d_sl;
-  SloppyGroups* d_gr;
-  int32_t n_queries;
-  int64_t slots;     // a multiple of 64, every query's share too
-  int64_t redo_cap;  // phrase_match_setup's
-  bool any_exact, any_sloppy;
-  bool sloppy_rpts;  // some sloppy phrase names a term twice
-  // k_sloppy_groups (a search only: a rescoring refuses sloppy phrases that repeat a term and leaves the groups at "none")
-  bool with_groups;
-  PhraseCut* d_cut0;
-  const int64_t* d_cp0;
-  const int32_t* d_nl0;
-  int64_t collect_items;
-  // rgpu_search_span_near_batch: every live query of the call is an ordered SpanNearQuery (d_sl: its true slops) - the span
-  // kernels run instead of the phrase kernels (any_exact and any_sloppy are false then)
-  bool any_span = false;
-  // rgpu_search_span_unordered_batch: the span queries are unordered (NearSpansUnordered) - kernels/search_span_unordered.hpp runs
-  // in place of kernels/search_span.hpp, on the same ladder. No other caller sets it.
-  bool unordered_span = false;
-};
-static int32_t phrase_match_stage(rgpu_segment* seg, hipStream_t stream, const PhraseMatchStage& a) {
-  rgpu_ctx* c = seg->ctx;
-  if (a.slots == 0 || !(a.any_exact || a.any_sloppy || a.any_span)) return RGPU_OK;  // no slot, or no live phrase to look at one: d_err stays "fine"
-  const SegView sv = seg_view(seg);
-  const bool legacy = seg->version < 1;
-  // One wavefront per candidate slot, first with the small position lists / pools (seven wavefronts per SIMD). A doc that holds
-  // a term more often than those hold positions (rare: Rucene clamps freqs to 10) leaves PHRASE_REDO in its slot: one look at
-  // the flag, then the wide instantiations over the marked candidates only.
-  // (one wavefront per slot: at most PHRASE_LAUNCH_SLOTS slots per launch — a grid of more than 2^32 work-items is cut short)
-  auto per_slot = [&](int64_t n, auto launch) {
-    for (int64_t s0 = 0; s0 < n; s0 += PHRASE_LAUNCH_SLOTS) {
-      const int64_t s1 = std::min(n, s0 + PHRASE_LAUNCH_SLOTS);
-      launch(dim3(wg_count((s1 - s0 + WG_WAVES - 1) / WG_WAVES)), s0, s1);
-    }
-  };
-  // (list: null = every slot of the launch; else the listed slots — the ones a 64-candidate kernel handed on)
-  auto exact = [&](auto kern, const int64_t* list, int64_t n) {
-    per_slot(n, [&](dim3 grid, int64_t s0, int64_t s1) {
-      RGPU_LAUNCH(kern, grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl, (int)a.n_queries, s1,
-                  (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err, c->d_err + 3, list, s0);
-    });
-  };
-  auto sloppy = [&](auto kern, const int64_t* list, int64_t n) {
-    per_slot(n, [&](dim3 grid, int64_t s0, int64_t s1) {
-      RGPU_LAUNCH(kern, grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl, a.d_gr, (int)a.n_queries, s1,
-                  (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err, c->d_err + 3, list, s0);
-    });
-  };
-  auto sloppy_groups = [&]() {  // the repetition groups of each query's first candidate doc (phrases with a repeated term)
-    TimedLaunch tl(c, stream, "k_sloppy_groups", 0);
-    if (a.collect_items > 0)  // every sloppy query's smallest live candidate, chunk by chunk
-      RGPU_LAUNCH(k_phrase_cutoff_items<2>, dim3(wg_count((a.collect_items + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, a.d_cp0, a.d_ep,
-                  c->phrase_count.p, c->phrase_keys.p, (const int32_t*)c->phrase_docs.p, a.d_sl, a.d_nl0, (int)a.n_queries, a.collect_items, a.d_cut0);
-    const unsigned ggrid = wg_count((a.n_queries + WG_WAVES - 1) / WG_WAVES);
-    auto go = [&](auto kern) {
-      RGPU_LAUNCH(kern, dim3(ggrid), dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl,
-                  (int)a.n_queries, (int64_t)seg->pos_len, a.d_gr, c->d_err, (const PhraseCut*)a.d_cut0);
-    };
-    if (legacy) go(k_sloppy_groups<true>); else go(k_sloppy_groups<false>);
-  };
-  const int64_t* const all_slots = nullptr;
-  const int64_t groups = a.slots / 64;
-  const dim3 lanes_grid(wg_count((groups + WG_WAVES - 1) / WG_WAVES));
-  // ---- first pass. Packed (.doc version 1) segments: 64 candidates per wavefront; what those kernels hand on is listed.
-  // Legacy segments (the packed streams of a block are laid out differently): one candidate per wavefront throughout.
-  if (a.any_exact) {
-    if (legacy) {
-      TimedLaunch tl(c, stream, "k_phrase_match", 0);
-      exact(k_phrase_match<true, PHRASE_SMALL_CAP, false>, all_slots, a.slots);
-    } else {
-      TimedLaunch tl(c, stream, "k_phrase_match_lanes", 0);
-      RGPU_LAUNCH(k_phrase_match_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl,
-                  (int)a.n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)a.redo_cap, c->d_err + 2);
-    }
-  }
-  if (a.any_sloppy) {
-    if (legacy) {
-      if (a.with_groups) sloppy_groups();
-      TimedLaunch tl(c, stream, "k_sloppy_match", 0);
-      sloppy(k_sloppy_match<true, SLOPPY_SMALL_POOL, false>, all_slots, a.slots);
-    } else {
-      if (a.sloppy_rpts) sloppy_groups();  // the repetition groups: k_sloppy_rpt_lanes (and what it hands on) needs them
-      {
-        TimedLaunch tl(c, stream, "k_sloppy_match_lanes", 0);
-        RGPU_LAUNCH(k_sloppy_match_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl,
-                    (int)a.n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)a.redo_cap, c->d_err + 2,
-                    a.sloppy_rpts ? 1 : 0);
-      }
-      if (a.sloppy_rpts) {  // phrases that repeat a term: the scorer's repeats machinery per lane
-        TimedLaunch tl(c, stream, "k_sloppy_rpt_lanes", 0);
-        RGPU_LAUNCH(k_sloppy_rpt_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl,
-                    a.d_gr, (int)a.n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)a.redo_cap, c->d_err + 2);
-      }
-    }
-  }
-  if (a.any_span && a.unordered_span) {  // unordered span-near queries: the sloppy phrases' ladder (one pool), NearSpansUnordered's walk
-    if (legacy) {
-      TimedLaunch tl(c, stream, "k_span_unordered", 0);
-      exact(k_span_unordered<true, SLOPPY_SMALL_POOL, false>, all_slots, a.slots);
-    } else {
-      TimedLaunch tl(c, stream, "k_span_unordered_lanes", 0);
-      RGPU_LAUNCH(k_span_unordered_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl,
-                  (int)a.n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)a.redo_cap, c->d_err + 2);
-    }
-  } else if (a.any_span) {  // ordered span-near queries: as the exact phrases' ladder, with the span walk (kernels/search_span.hpp)
-    if (legacy) {
-      TimedLaunch tl(c, stream, "k_span_near", 0);
-      exact(k_span_near<true, PHRASE_SMALL_CAP, false>, all_slots, a.slots);
-    } else {
-      TimedLaunch tl(c, stream, "k_span_near_lanes", 0);
-      RGPU_LAUNCH(k_span_near_lanes, lanes_grid, dim3(WG_THREADS), 0, stream, sv, a.d_q, a.d_t, a.d_pt, a.d_ep, c->phrase_count.p, c->phrase_docs.p, a.d_sl,
-                  (int)a.n_queries, groups, (int64_t)seg->pos_len, c->phrase_keys.p, c->d_err + 3, c->phrase_redo.p, (int)a.redo_cap, c->d_err + 2);
-    }
-  }
-  // ---- which candidates wait for another pass (bits PHRASE_REDO_*): one look per stage that can raise one
-  int listed = 0, redo = 0;  // d_err[2]: slots on the list, d_err[3]: the bits
-  auto redo_bits = [&]() -> int32_t {
-    int two[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(two, c->d_err + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    listed = two[0];
-    redo = two[1];
-    return RGPU_OK;
-  };
-  RGPU_TRY(redo_bits());
-  // the one-candidate kernels over the listed slots (or, should the list have overflowed, over every slot)
-  const bool by_list = !legacy && (int64_t)listed <= a.redo_cap;
-  const int64_t* const left = by_list ? (const int64_t*)c->phrase_redo.p : all_slots;
-  const int64_t n_left = by_list ? (int64_t)listed : a.slots;
-  constexpr int REDO_FROM_LANES = PHRASE_REDO_LANES | PHRASE_REDO_SLOPPY_LANES | PHRASE_REDO_SPAN_LANES | PHRASE_REDO_SPAN_UNORD_LANES;
-  if (HostClock::on() && (redo & REDO_FROM_LANES))
-    std::fprintf(stderr, "[phrase] %d of %lld candidate slots left for the one-candidate kernels\n", listed, (long long)a.slots);
-  if (redo & PHRASE_REDO_LANES) {
-    TimedLaunch tl(c, stream, "k_phrase_match(left by the 64-candidate kernel)", 0);
-    exact(k_phrase_match<false, PHRASE_SMALL_CAP, true>, left, n_left);
-  }
-  if (redo & PHRASE_REDO_SLOPPY_LANES) {
-    TimedLaunch tl(c, stream, "k_sloppy_match(left by the 64-candidate kernel)", 0);  // (the groups are there: computed in front of the 64-candidate kernels)
-    sloppy(k_sloppy_match<false, SLOPPY_SMALL_POOL, true>, left, n_left);
-  }
-  if (redo & PHRASE_REDO_SPAN_LANES) {
-    TimedLaunch tl(c, stream, "k_span_near(left by the 64-candidate kernel)", 0);
-    exact(k_span_near<false, PHRASE_SMALL_CAP, true>, left, n_left);
-  }
-  if (redo & PHRASE_REDO_SPAN_UNORD_LANES) {
-    // ("unord": rgpu_kernel_stat.name holds 47 characters)
-    TimedLaunch tl(c, stream, "k_span_unord(left by the 64-candidate kernel)", 0);
-    exact(k_span_unordered<false, SLOPPY_SMALL_POOL, true>, left, n_left);
-  }
-  if (redo & REDO_FROM_LANES) RGPU_TRY(redo_bits());
-  if (redo & PHRASE_REDO_WIDE) {
-    TimedLaunch tl(c, stream, "k_phrase_match(wide lists)", 0);
-    if (legacy) exact(k_phrase_match<true, PHRASE_LIST_CAP, true>, left, n_left); else exact(k_phrase_match<false, PHRASE_LIST_CAP, true>, left, n_left);
-  }
-  if (redo & PHRASE_REDO_SPAN_WIDE) {
-    TimedLaunch tl(c, stream, "k_span_near(wide lists)", 0);
-    if (legacy) exact(k_span_near<true, PHRASE_LIST_CAP, true>, left, n_left); else exact(k_span_near<false, PHRASE_LIST_CAP, true>, left, n_left);
-  }
-  if (redo & PHRASE_REDO_SPAN_UNORD_WIDE) {
-    TimedLaunch tl(c, stream, "k_span_unordered(wide pool)", 0);
-    if (legacy) exact(k_span_unordered<true, SLOPPY_POOL, true>, left, n_left); else exact(k_span_unordered<false, SLOPPY_POOL, true>, left, n_left);
-  }
-  if (redo & PHRASE_REDO_SLOPPY) {
-    TimedLaunch tl(c, stream, "k_sloppy_match(wide pool)", 0);
-    if (legacy) sloppy(k_sloppy_match<true, SLOPPY_POOL, true>, left, n_left); else sloppy(k_sloppy_match<false, SLOPPY_POOL, true>, left, n_left);
-  }
-  return RGPU_OK;
-}
-
-// ---- the plan in front of it, shared by the phrase search and the phrase rescoring -----------------------------------------------
-// Term equality: how PosTerm::same_as tells repeated terms (repeating_terms, phrase_scorer.rs:909-931)
-static bool same_term(const rgpu_term_state& a, const rgpu_term_state& b) {
-  return a.doc_start_fp == b.doc_start_fp && a.doc_freq == b.doc_freq && a.singleton_doc_id == b.singleton_doc_id && a.total_term_freq == b.total_term_freq;
-}
-// a query's own fields (`searching`: next_limit is looked at, a rescoring has no use for it) ...
-static int32_t check_phrase_query(const rgpu_ctx* c, const rgpu_phrase_query& Q, int32_t n_terms_total, bool searching) {
-  if (Q.n_terms < 2 || Q.n_terms > RGPU_MAX_PHRASE_TERMS) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "a phrase has 2..RGPU_MAX_PHRASE_TERMS terms");
-  if (Q.slop < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "Slop must be >= 0");  // PhraseQuery::new (phrase_query.rs:77)
-  if (searching && Q.next_limit < RGPU_NEXT_LIMIT_ZERO) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "rgpu_phrase_query.next_limit: 0 (the searcher's default), n > 0, -1 (none) or RGPU_NEXT_LIMIT_ZERO");
-  if (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms > (int64_t)n_terms_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "term range outside terms[]");
-  if (Q.sim_table < 0 || Q.sim_table >= c->n_sim_tables) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
-  return RGPU_OK;
-}
-// ... and its terms: those the leaf holds go to `ptrs` for the preparation, the ones of a row with an absent term too
-static int32_t check_phrase_terms(const rgpu_segment* seg, const rgpu_phrase_query& Q, const rgpu_phrase_term* terms, std::vector<const rgpu_term_state*>* ptrs) {
-  for (int i = 0; i < Q.n_terms; ++i) {
-    const rgpu_phrase_term& t = terms[Q.first_term + i];
-    if (t.state.doc_freq <= 0) continue;
-    if (t.positions.pos_start_fp < 0 || (size_t)t.positions.pos_start_fp >= seg->pos_len) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "pos_start_fp outside the .pos file");
-    if (t.state.total_term_freq < t.state.doc_freq) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "total_term_freq below doc_freq");
-    ptrs->push_back(&t.state);
-  }
-  return RGPU_OK;
-}
-static bool phrase_is_dead(const rgpu_phrase_query& Q, const rgpu_phrase_term* terms) {  // a term absent from the leaf
-  for (int i = 0; i < Q.n_terms; ++i) if (terms[Q.first_term + i].state.doc_freq <= 0) return true;
-  return false;
-}
-// One query's clauses behind `dt` / `pt`, rarest term first: it drives the conjunction (conjunction_scorer.rs:30). *dead: nothing was
-// pushed, PhraseWeight::create_scorer -> None (phrase_query.rs:275-283) — no doc of this leaf matches.
-static int32_t emit_phrase(const rgpu_segment* seg, const rgpu_phrase_query& Q, const rgpu_phrase_term* terms, std::vector<DevTerm>* dt, std::vector<PosTerm>* pt, bool* dead) {
-  *dead = phrase_is_dead(Q, terms);
-  if (*dead) return RGPU_OK;
-  const rgpu_phrase_term* mine = terms + Q.first_term;
-  int order[RGPU_MAX_PHRASE_TERMS];
-  for (int i = 0; i < Q.n_terms; ++i) order[i] = i;
-  std::stable_sort(order, order + Q.n_terms, [&](int a, int b) { return mine[a].state.doc_freq < mine[b].state.doc_freq; });
-  for (int o = 0; o < Q.n_terms; ++o) {
-    const int i = order[o];
-    dt->emplace_back();
-    RGPU_TRY(make_dev_term(seg, mine[i].state, Q.weight, Q.sim_table, &dt->back()));
-    PosTerm p = pos_term_of(mine[i].state, mine[i].positions);
-    p.phrase_pos = mine[i].position;
-    p.query_ord = i;  // PhrasePositions::ord: the sloppy scorer keeps the query's order (phrase_query.rs:324-331 does not sort)
-    p.same_as = i;    // ... and tells repeated terms by Term equality
-    for (int j = 0; j < i; ++j) if (same_term(mine[j].state, mine[i].state)) { p.same_as = j; break; }
-    pt->push_back(p);
-  }
-  return RGPU_OK;
-}
-// what the match stage left in d_err[0], in the caller's words
-static int32_t phrase_match_status(int err, const char* held_too_often, const char* not_found_again) {
-  if (err == 0) return RGPU_OK;
-  return fail(err, err == RGPU_ERR_UNSUPPORTED ? held_too_often : (err == RGPU_ERR_ILLEGAL_STATE ? not_found_again : "corrupt position data in .pos"));
-}
-// ... fetched by itself, synchronised: the calls that look at the verdict before they write anything to the caller's arrays
-static int32_t phrase_match_verdict(rgpu_ctx* c, hipStream_t stream, const char* held_too_often, const char* not_found_again) {
-  int err = 0;
-  HIP_TRY(hipMemcpyAsync(&err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  return phrase_match_status(err, held_too_often, not_found_again);
-}
-
-// ---- the collectors behind it: every query's best k keys (its candidate slots: and_emit_stage's) into the call's rows --------------
-// k <= RGPU_PASS_K: one wavefront per chunk of PHRASE_COLLECT_CHUNK candidates (lead_collect_chunks), k_merge_items folds a query's
-// lists; deeper pages (or nothing to chunk): one wavefront per query, in passes. The chunked collector's lists live in
-// c->S->d_partial_keys / d_partial_counts: and_emit_stage is asked for collect_items * k and collect_items of them.
-static bool phrase_collect_chunked(int32_t k, int64_t collect_items) { return k <= RGPU_PASS_K && collect_items > 0; }
-struct PhraseCollectStage {
-  const int64_t* d_ep;  // slots in front of each query's
-  const int64_t* d_cp;  // chunks in front of each query's
-  const int32_t* d_sl;  // slops
-  const int32_t* d_nl;  // next_limit per query, -1: none
-  int32_t n_queries, k;
-  int64_t collect_items;
-  // Some sloppy query has a next_limit (the two-phase rule: a query whose first collected doc has more than next_limit candidates
-  // in front of it yields nothing): k_phrase_cutoff_items finds, chunk by chunk, the first collected doc and the candidates in
-  // front of it into d_cut, k_phrase_cutoff_decide sets the flags. Without: d_ab is all zero (nothing is abandoned), d_cut unused.
-  bool any_cutoff;
-  int32_t* d_ab;
-  PhraseCut* d_cut;
-};
-static void phrase_collect_stage(rgpu_segment* seg, hipStream_t stream, const PhraseCollectStage& a) {
-  rgpu_ctx* c = seg->ctx;
-  const bool wide = a.k > 64;  // the wide top-k lists
-  if (phrase_collect_chunked(a.k, a.collect_items)) {
-    {
-      TimedLaunch tl(c, stream, "k_phrase_collect", 0);
-      const unsigned grid = wg_count((a.collect_items + WG_WAVES - 1) / WG_WAVES);
-      if (a.any_cutoff) {
-        RGPU_LAUNCH(k_phrase_cutoff_items<0>, dim3(grid), dim3(WG_THREADS), 0, stream, a.d_cp, a.d_ep, c->phrase_count.p, c->phrase_keys.p,
-                    (const int32_t*)c->phrase_docs.p, a.d_sl, a.d_nl, (int)a.n_queries, a.collect_items, a.d_cut);
-        RGPU_LAUNCH(k_phrase_cutoff_items<1>, dim3(grid), dim3(WG_THREADS), 0, stream, a.d_cp, a.d_ep, c->phrase_count.p, c->phrase_keys.p,
-                    (const int32_t*)c->phrase_docs.p, a.d_sl, a.d_nl, (int)a.n_queries, a.collect_items, a.d_cut);
-        RGPU_LAUNCH(k_phrase_cutoff_decide, dim3(wg_count((a.n_queries + 255) / 256)), dim3(256), 0, stream, c->phrase_count.p, a.d_sl, a.d_nl, (int)a.n_queries,
-                    a.d_cut, a.d_ab);
-      }
-      const auto collect_items = wide ? k_phrase_collect_items<true> : k_phrase_collect_items<false>;
-      RGPU_LAUNCH(collect_items, dim3(grid), dim3(WG_THREADS), 0, stream, a.d_cp, a.d_ep, c->phrase_count.p, c->phrase_keys.p, (const int32_t*)a.d_ab,
-                  (int)a.n_queries, a.collect_items, (int)a.k, c->S->d_partial_keys.p, c->S->d_partial_counts.p);
-    }
-    if (wide) launch_merge<true>(c, stream, a.n_queries, a.k, a.d_cp, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
-    else launch_merge<false>(c, stream, a.n_queries, a.k, a.d_cp, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
-  } else {
-    TimedLaunch tl(c, stream, "k_phrase_collect", 0);
-    const auto collect = wide ? k_phrase_collect<true> : k_phrase_collect<false>;
-    RGPU_LAUNCH(collect, dim3(wg_count((a.n_queries + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, a.d_ep, c->phrase_count.p, c->phrase_keys.p,
-                (const int32_t*)c->phrase_docs.p, a.d_sl, a.d_nl, (int)a.n_queries, (int)a.k, seg->doc_base, c->host_api_hits.p, c->host_api_totals.p);
-  }
-}
-
-// ---- a boolean query over phrases, as rgpu_search_phrase_bool_batch and rgpu_search_phrase_or_batch take one: its own fields, its
-// phrases and its term clauses (those the leaf holds go to `ptrs` for the preparation). `noun`: what the caller's messages call it.
-struct PhraseClauseArrays {
-  const rgpu_phrase_query* phrases;
-  int32_t n_phrases_total;
-  const rgpu_phrase_term* phrase_terms;
-  int32_t n_phrase_terms_total;
-  const rgpu_query_term* terms;
-  int32_t n_terms_total;
-};
-template <typename BoolQuery>
-static int32_t check_phrases_query(const rgpu_segment* seg, const BoolQuery& Q, const char* noun, const PhraseClauseArrays& a, std::vector<const rgpu_term_state*>* ptrs) {
-  const rgpu_ctx* c = seg->ctx;
-  if (Q.n_phrases < 1 || Q.n_phrases > RGPU_MAX_BOOL_PHRASES) return fail(RGPU_ERR_UNSUPPORTED, std::string(noun) + " holds 1..RGPU_MAX_BOOL_PHRASES phrases");
-  if (Q.first_phrase < 0 || (int64_t)Q.first_phrase + Q.n_phrases > (int64_t)a.n_phrases_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "phrase range outside phrases[]");
-  if (Q.n_terms < 0 || Q.n_must_not < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "negative clause count");
-  if (Q.n_terms + (int64_t)Q.n_must_not > 0 && (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms + Q.n_must_not > (int64_t)a.n_terms_total))
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "clause range outside terms[]");
-  for (int i = 0; i < Q.n_phrases; ++i) {
-    const rgpu_phrase_query& P = a.phrases[Q.first_phrase + i];
-    RGPU_TRY(check_phrase_query(c, P, a.n_phrase_terms_total, false));
-    RGPU_TRY(check_phrase_terms(seg, P, a.phrase_terms, ptrs));
-  }
-  for (int64_t i = 0; i < (int64_t)Q.n_terms + Q.n_must_not; ++i) {
-    const rgpu_query_term& t = a.terms[Q.first_term + i];
-    if (i < Q.n_terms && (t.sim_table < 0 || t.sim_table >= c->n_sim_tables)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
-    if (t.state.doc_freq > 0) ptrs->push_back(&t.state);
-  }
-  return RGPU_OK;
-}
-
-// rgpu_search_span_near_batch: clause i of a span-near query is rgpu_phrase_term i with position = i, reserved = 0
-static int32_t check_span_clauses(const rgpu_phrase_query& Q, const rgpu_phrase_term* terms) {
-  for (int i = 0; i < Q.n_terms; ++i) {
-    const rgpu_phrase_term& t = terms[Q.first_term + i];
-    if (t.position != i) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "span near: rgpu_phrase_term.position must be the clause's index");
-    if (t.reserved != 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "span near: rgpu_phrase_term.reserved must be 0");
-  }
-  return RGPU_OK;
-}
-
-static int32_t search_phrase_batch_impl(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_query* queries, int32_t n_queries,
-                                        const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
-                                        int64_t* total_hits_out, bool span = false, bool unordered = false) {
-  // unordered (with span): rgpu_search_span_unordered_batch - the same plan, checks and collectors; the match stage runs
-  // NearSpansUnordered's kernels (kernels/search_span_unordered.hpp).
-  // span: rgpu_search_span_near_batch - the queries are ordered SpanNearQuerys over SpanTermQuery clauses. The plan, the candidate
-  // stage and the collectors are the phrases'; the match stage runs the span kernels, and the collectors are handed a marker in
-  // place of the slops: SpanScorer is two-phase whatever the slop (span.rs:1033-1091), so next_limit applies at slop 0 too.
-  if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !hits_out || !total_hits_out)
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (set) { RGPU_TRY(docset_check(seg, set)); RGPU_TRY(refuse_sloppy_masked(queries, n_queries)); }
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "phrase search: k must be in 1..RGPU_MAX_K");
-  if (!seg->has_positions || !seg->d_pos) return fail(RGPU_ERR_ILLEGAL_STATE, "phrase search needs a positions field with its .pos file attached");
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t stream = c->stream;
-  // ---- validate, resolve, plan
-  std::vector<const rgpu_term_state*> ptrs;
-  for (int32_t q = 0; q < n_queries; ++q) {
-    RGPU_TRY(check_phrase_query(c, queries[q], n_terms_total, true));
-    RGPU_TRY(check_phrase_terms(seg, queries[q], terms, &ptrs));
-    if (span) RGPU_TRY(check_span_clauses(queries[q], terms));
-  }
-  PhraseMask masked;
-  RGPU_TRY(masked.install(seg, set));
-  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
-  // the conjunction that finds a phrase's candidates answers a dense clause from its doc bitmap, as a BooleanQuery's does
-  int64_t bitmap_df = INT64_MAX;
-  {
-    std::vector<const rgpu_term_state*> clauses;
-    std::vector<int32_t> clause_sim;
-    clauses.reserve((size_t)n_terms_total);
-    clause_sim.reserve((size_t)n_terms_total);
-    for (int32_t q = 0; q < n_queries; ++q)
-      for (int i = 0; i < queries[q].n_terms; ++i) { clauses.push_back(&terms[queries[q].first_term + i].state); clause_sim.push_back(queries[q].sim_table); }
-    RGPU_TRY(ensure_and_bitmaps_locked(seg, clauses, clause_sim, &bitmap_df));
-  }
-  std::vector<DevQuery> dq((size_t)n_queries);
-  std::vector<DevTerm> dt;
-  std::vector<PosTerm> pt;
-  std::vector<int64_t> item_prefix((size_t)n_queries + 1), emit_prefix((size_t)n_queries + 1), collect_prefix((size_t)n_queries + 1);
-  std::vector<int32_t> slops((size_t)n_queries, 0), limits((size_t)n_queries, -1);
-  std::vector<int32_t> two_phase;  // span: what the collectors read in place of the slops - 1 for every live query
-  if (span) two_phase.assign((size_t)n_queries, 0);
-  bool any_span = false;
-  int64_t collect_items = 0;
-  bool any_cutoff = false;
-  bool any_sloppy = false, any_exact = false;
-  bool sloppy_rpts = false;  // some sloppy phrase names a term twice (SloppyPhraseScorer's repetition groups: k_sloppy_groups)
-  int64_t phrase_lead_blocks = 0;  // the conjunctions' lead blocks: every phrase's rarest term
-  for (int32_t q = 0; q < n_queries; ++q) {
-    int64_t least = INT64_MAX;
-    for (int i = 0; i < queries[q].n_terms; ++i) least = std::min<int64_t>(least, std::max<int64_t>(0, terms[queries[q].first_term + i].state.doc_freq));
-    if (least != INT64_MAX) phrase_lead_blocks += least / 128;
-  }
-  const int blocks_per_item = and_item_blocks(c, phrase_lead_blocks);
-  int64_t items = 0, slots = 0;
-  for (int32_t q = 0; q < n_queries; ++q) {
-    const rgpu_phrase_query& Q = queries[q];
-    item_prefix[(size_t)q] = items;
-    emit_prefix[(size_t)q] = slots;
-    collect_prefix[(size_t)q] = collect_items;
-    dq[(size_t)q] = DevQuery{RGPU_OP_AND, 0, (int32_t)dt.size(), 0};
-    bool dead = false;
-    RGPU_TRY(emit_phrase(seg, Q, terms, &dt, &pt, &dead));
-    if (dead) continue;
-    slops[(size_t)q] = Q.slop;
-    limits[(size_t)q] = Q.next_limit == 0 ? 500000 /* searcher.rs:47 DEFAULT_DISMATCH_NEXT_LIMIT */
-                                          : (Q.next_limit == RGPU_NEXT_LIMIT_ZERO ? 0 /* DefaultIndexSearcher::new(reader, Some(0)) */ : Q.next_limit);
-    if (span) {
-      // the loaders hand out position - phrase_pos: a span clause's positions are the term's own
-      for (size_t i = pt.size() - (size_t)Q.n_terms; i < pt.size(); ++i) pt[i].phrase_pos = 0;
-      two_phase[(size_t)q] = 1;
-      any_span = true;
-    } else {
-      (Q.slop > 0 ? any_sloppy : any_exact) = true;
-    }
-    if (!span && Q.slop > 0) for (size_t i = pt.size() - (size_t)Q.n_terms; i < pt.size(); ++i) sloppy_rpts = sloppy_rpts || pt[i].same_as != pt[i].query_ord;
-    dq[(size_t)q].n_terms = Q.n_terms;
-    const DevTerm& lead = dt[(size_t)dq[(size_t)q].first_term];
-    items += lead_items(lead, blocks_per_item);
-    slots += lead_slots(lead);
-    collect_items += lead_collect_chunks(lead);
-    any_cutoff = any_cutoff || ((span || Q.slop > 0) && limits[(size_t)q] >= 0);
-  }
-  item_prefix[(size_t)n_queries] = items;
-  emit_prefix[(size_t)n_queries] = slots;
-  collect_prefix[(size_t)n_queries] = collect_items;
-  RGPU_TRY(api_rows_default(c, stream, n_queries, k));
-  if (items > 0) {
-    SCRATCH_TAKE(c);
-    Stager st(c);
-    const size_t nq = (size_t)n_queries;
-    const auto r_q = st.add<DevQuery>(nq);
-    const auto r_t = st.add<DevTerm>(dt.size());
-    const auto r_pt = st.add<PosTerm>(pt.size());
-    const auto r_ip = st.add<int64_t>(nq + 1), r_ep = st.add<int64_t>(nq + 1);
-    const auto r_sl = st.add<int32_t>(nq), r_nl = st.add<int32_t>(nq);
-    const auto r_tp = st.add_if<int32_t>(span, nq);
-    const auto r_gr = st.add<SloppyGroups>(nq);  // written by k_sloppy_groups
-    const auto r_cp = st.add<int64_t>(nq + 1);   // the chunked collector's items
-    const auto r_ab = st.add<int32_t>(nq);       // k_phrase_cutoff's flags (zeroed by the copy)
-    const auto r_cut = st.add<PhraseCut>(nq);    // ... and what its chunked form reduces into
-    const std::vector<TermBitmap> clause_bitmaps = clause_bitmap_table(seg, dq, dt, bitmap_df);
-    const auto r_bm = st.add_if<TermBitmap>(!clause_bitmaps.empty(), clause_bitmaps.size());
-    STAGE_SIZED(sg, st);
-    sg.put(r_q, dq);
-    sg.put(r_t, dt);
-    sg.put(r_pt, pt);
-    sg.put(r_sl, slops);
-    sg.put(r_tp, two_phase);
-    sg.put(r_nl, limits);
-    sg.put(r_ip, item_prefix);
-    sg.put(r_ep, emit_prefix);
-    sg.put(r_cp, collect_prefix);
-    sg.fill(r_ab, 0);
-    for (size_t q = 0; q < nq; ++q) sg.host(r_cut)[q] = PhraseCut{0x7fffffff, 0x7fffffff, 0ull};
-    // "no repetition group" for every query (grp = -1): k_sloppy_groups only runs when some phrase repeats a term, k_sloppy_match
-    // reads the region either way (the copy used to carry whatever the pinned buffer held)
-    sg.fill(r_gr, 0xff);
-    sg.put(r_bm, clause_bitmaps);
-    RGPU_TRY(sg.upload(stream));
-    const DevQuery* d_q = sg.dev(r_q);
-    const DevTerm* d_t = sg.dev(r_t);
-    const int64_t *d_ep = sg.dev(r_ep), *d_cp = sg.dev(r_cp);
-    const int32_t *d_sl = sg.dev(r_sl), *d_nl = sg.dev(r_nl);
-    PhraseCut* d_cut = sg.dev(r_cut);
-    const bool chunked = phrase_collect_chunked(k, collect_items);
-    int64_t redo_cap = 0;
-    // (k_emit: the conjunction only emits candidates, its (empty) top-k lists are the narrow kind)
-    const char* stage_name = masked.on() ? masked_stage_name(c, "k_search_and(masked phrase candidates)", "k_search_and(masked phrase, marked)")
-                                         : (span ? "k_search_and(span candidates)" : "k_search_and(phrase candidates)");
-    const int32_t* d_collect_sl = span ? sg.dev(r_tp) : d_sl;  // "two-phase" to the collectors: slop > 0, or a span query
-    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{stage_name, d_q, d_t, sg.dev(r_ip), d_ep, clause_bitmaps.empty() ? nullptr : sg.dev(r_bm),
-                                                      n_queries, nq, items, slots, blocks_per_item, std::min<int>(k, 64), false,
-                                                      chunked ? (size_t)collect_items * (size_t)k : 0, chunked ? (size_t)collect_items : 0,
-                                                      &redo_cap, false /* the collectors read a query's first emit_count slots only */,
-                                                      masked.on() && c->phrase_mask_compact}));
-    RGPU_TRY(phrase_match_stage(seg, stream, PhraseMatchStage{d_q, d_t, sg.dev(r_pt), d_ep, d_sl, sg.dev(r_gr), n_queries, slots, redo_cap, any_exact, any_sloppy,
-                                                              sloppy_rpts, true, d_cut, d_cp, d_nl, collect_items, any_span, span && unordered}));
-    phrase_collect_stage(seg, stream, PhraseCollectStage{d_ep, d_cp, d_collect_sl, d_nl, n_queries, k, collect_items, any_cutoff, sg.dev(r_ab), d_cut});
-    HIP_TRY(launch_status());
-  }
-  // the verdict in the same round as the rows (nothing launched: nothing to ask, and d_err may hold another call's)
-  int err = 0;
-  RGPU_TRY(api_rows_read_back(c, stream, n_queries, k, hits_out, total_hits_out, items > 0 ? &err : nullptr));
-  return phrase_match_status(err, span ? (unordered ? "a doc holds the terms of an unordered span query's clauses more than 2048 times in all"
-                                                   : "a doc holds the term of a span clause more than 1024 times")
-                                       : "a doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)",
-                             "internal: a conjunction match was not found again");
-}
-// (include/rucene_gpu.h rgpu_search_span_near_batch; the match kernels: kernels/search_span.hpp)
-extern "C" int32_t rgpu_search_span_near_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
-                                               const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t in_order, int32_t k,
-                                               rgpu_hit* hits_out, int64_t* total_hits_out) {
-  // NearSpansUnordered is another walk and another call: rgpu_search_span_unordered_batch
-  if (in_order == 0) return fail(RGPU_ERR_UNSUPPORTED, "span near: only in_order = true is served (unordered near: rgpu_search_span_unordered_batch)");
-  return search_phrase_batch_impl(seg, nullptr, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out, true);
-}
-// (include/rucene_gpu.h rgpu_search_span_unordered_batch; the match kernels: kernels/search_span_unordered.hpp)
-extern "C" int32_t rgpu_search_span_unordered_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
-                                                    const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
-                                                    int64_t* total_hits_out) {
-  return search_phrase_batch_impl(seg, nullptr, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out, true, true);
-}
-extern "C" int32_t rgpu_search_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
-                                            const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
-                                            int64_t* total_hits_out) {
-  return search_phrase_batch_impl(seg, nullptr, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out);
-}
-extern "C" int32_t rgpu_search_phrase_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_query* queries, int32_t n_queries,
-                                                   const rgpu_phrase_term* terms, int32_t n_terms_total, int32_t k, rgpu_hit* hits_out,
-                                                   int64_t* total_hits_out) {
-  if (!set) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  return search_phrase_batch_impl(seg, set, queries, n_queries, terms, n_terms_total, k, hits_out, total_hits_out);
-}
-
-// ---- BooleanQuery with exact PhraseQuery clauses among its required clauses: +"a b" +c -d #e ------------------------------------
-// (include/rucene_gpu.h rgpu_search_phrase_bool_batch; the plan: host/phrase_bool_plan.hpp; the two kernels of its own:
-// kernels/search_phrase_bool.hpp.) Launch sequence, all on the call's stream:
-//   1. and_emit_stage (with phrase_match_setup among its memsets in front of the launch: keys zeroed, the redo list sized from the
-//      slots of all planes, d_err zeroed): k_search_and in emit mode over every query's DISTINCT required terms -> plane 0's candidate docs (dense
-//      clauses from their doc bitmaps: ensure_and_bitmaps_locked, clause_bitmap_table). MUST_NOT terms are removed
-//      here, through the HAS_NOT instantiation: the prohibited probe clears a0 / a1 before the emit branch is reached, and
-//      DevQuery::pad is what n_req_not is computed from whether the kernel emits or collects;
-//   2. k_phrase_bool_fanout (batches with a query of more than one phrase): plane 0's docs and count to the other planes;
-//   3. phrase_match_stage over the virtual queries (query, phrase), plane-major — exact kernels only;
-//   4. k_phrase_bool_score: the reference-order f32 sum over plane 0's key;
-//   5. phrase_collect_stage over plane 0; the verdict (phrase_match_verdict), then api_rows_read_back.
-// Unsupported shapes (see the header): sloppy clauses, phrases under SHOULD / MUST_NOT, SHOULD clauses or nested BooleanQuery clauses
-// beside a phrase, more than RGPU_MAX_BOOL_PHRASES phrases.
-static_assert(PHRASE_BOOL_MAX_PLANES == RGPU_MAX_BOOL_PHRASES, "k_phrase_bool_score keeps one key per plane in registers");
-static int32_t search_phrase_bool_batch_impl(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_bool_query* queries, int32_t n_queries,
-                                             const rgpu_phrase_query* phrases, int32_t n_phrases_total,
-                                             const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
-                                             const rgpu_query_term* terms, int32_t n_terms_total,
-                                             int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
-  if (!seg || !queries || n_queries <= 0 || !phrases || n_phrases_total <= 0 || !phrase_terms || n_phrase_terms_total <= 0 || n_terms_total < 0 ||
-      (n_terms_total > 0 && !terms) || !hits_out || !total_hits_out)
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (set) RGPU_TRY(docset_check(seg, set));
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "boolean query over phrases: k must be in 1..RGPU_MAX_K");
-  if (!seg->has_positions || !seg->d_pos) return fail(RGPU_ERR_ILLEGAL_STATE, "a boolean query over phrases needs a positions field with its .pos file attached");
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t stream = c->stream;
-  // ---- validate, plan
-  const size_t nq = (size_t)n_queries;
-  std::vector<const rgpu_term_state*> ptrs;
-  std::vector<rgpu_host::PhraseBoolPlan> plans(nq);
-  int max_planes = 1;
-  bool any_not = false;
-  const PhraseClauseArrays arrays{phrases, n_phrases_total, phrase_terms, n_phrase_terms_total, terms, n_terms_total};
-  for (int32_t q = 0; q < n_queries; ++q) {
-    const rgpu_phrase_bool_query& Q = queries[q];
-    RGPU_TRY(check_phrases_query(seg, Q, "a boolean query over phrases", arrays, &ptrs));
-    plans[(size_t)q] = rgpu_host::plan_phrase_bool(Q, phrases, phrase_terms, terms);
-    const rgpu_host::PhraseBoolPlan& P = plans[(size_t)q];
-    if (P.status != RGPU_OK) return fail(P.status, P.why);
-    if (!P.dead) { max_planes = std::max(max_planes, (int)Q.n_phrases); any_not = any_not || !P.must_not.empty(); }
-  }
-  PhraseMask masked;
-  RGPU_TRY(masked.install(seg, set));
-  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
-  // the candidate conjunction answers a dense clause from its doc bitmap, as a phrase search's does
-  int64_t bitmap_df = INT64_MAX;
-  {
-    std::vector<const rgpu_term_state*> clauses;
-    std::vector<int32_t> clause_sim;
-    clauses.reserve(ptrs.size());  // (every clause of a conjunction is a live term: ptrs holds them all)
-    clause_sim.reserve(ptrs.size());
-    for (int32_t q = 0; q < n_queries; ++q) {
-      if (plans[(size_t)q].dead) continue;
-      for (const rgpu_term_state* st : plans[(size_t)q].conj) { clauses.push_back(st); clause_sim.push_back(phrases[queries[q].first_phrase].sim_table); }
-    }
-    RGPU_TRY(ensure_and_bitmaps_locked(seg, clauses, clause_sim, &bitmap_df));
-  }
-  // ---- the launch's arrays. Virtual queries (query, phrase) are plane-major: v = j * n_queries + q
-  const size_t nv = nq * (size_t)max_planes;
-  std::vector<DevQuery> cq(nq, DevQuery{RGPU_OP_AND, 0, 0, 0});  // the candidate conjunction: [distinct required terms][MUST_NOT x pad]
-  std::vector<DevTerm> cdt;
-  std::vector<DevQuery> vq(nv, DevQuery{RGPU_OP_AND, 0, 0, 0});  // the match stage: one phrase each
-  std::vector<DevTerm> pdt;
-  std::vector<PosTerm> ppt;
-  std::vector<PhraseBoolDev> pbd(nq, PhraseBoolDev{0, 0, 0, 0});  // the scoring kernel
-  std::vector<int32_t> order;
-  std::vector<DevTerm> sdt;
-  std::vector<int64_t> item_prefix(nq + 1), emit_prefix(nv + 1), collect_prefix(nq + 1);
-  int64_t lead_blocks = 0;
-  for (const rgpu_host::PhraseBoolPlan& P : plans) if (!P.dead) lead_blocks += P.lead_df / 128;
-  const int blocks_per_item = and_item_blocks(c, lead_blocks);
-  int64_t items = 0, collect_items = 0;
-  for (int32_t q = 0; q < n_queries; ++q) {
-    const rgpu_phrase_bool_query& Q = queries[q];
-    const rgpu_host::PhraseBoolPlan& P = plans[(size_t)q];
-    item_prefix[(size_t)q] = items;
-    collect_prefix[(size_t)q] = collect_items;
-    if (P.dead) continue;
-    const int32_t conj_sim = phrases[Q.first_phrase].sim_table;  // (an emitting conjunction loads its lead's table and scores nothing)
-    cq[(size_t)q] = DevQuery{RGPU_OP_AND, (int32_t)P.conj.size(), (int32_t)cdt.size(), (int32_t)P.must_not.size()};
-    for (const rgpu_term_state* st : P.conj) { cdt.emplace_back(); RGPU_TRY(make_dev_term(seg, *st, 0.0f, conj_sim, &cdt.back())); }
-    for (const rgpu_term_state* st : P.must_not) { cdt.emplace_back(); RGPU_TRY(make_dev_term(seg, *st, 0.0f, conj_sim, &cdt.back())); }
-    const DevTerm& lead = cdt[(size_t)cq[(size_t)q].first_term];
-    items += lead_items(lead, blocks_per_item);
-    collect_items += lead_collect_chunks(lead);
-    for (int j = 0; j < Q.n_phrases; ++j) {
-      const size_t v = (size_t)j * nq + (size_t)q;
-      vq[v] = DevQuery{RGPU_OP_AND, 0, (int32_t)pdt.size(), 0};
-      bool dead = false;
-      RGPU_TRY(emit_phrase(seg, phrases[Q.first_phrase + j], phrase_terms, &pdt, &ppt, &dead));  // (dead: the plan has said so already)
-      vq[v].n_terms = dead ? 0 : phrases[Q.first_phrase + j].n_terms;
-    }
-    pbd[(size_t)q] = PhraseBoolDev{Q.n_phrases, (int32_t)order.size(), (int32_t)P.order.size(), 0};
-    const int32_t first_clause = (int32_t)sdt.size();
-    for (int i = 0; i < Q.n_terms; ++i) {
-      const rgpu_query_term& t = terms[Q.first_term + i];
-      sdt.emplace_back();
-      RGPU_TRY(make_dev_term(seg, t.state, t.weight, t.sim_table, &sdt.back()));
-    }
-    for (int32_t o : P.order) order.push_back(o < 0 ? o : first_clause + o);
-  }
-  item_prefix[nq] = items;
-  collect_prefix[nq] = collect_items;
-  int64_t slots = 0;
-  for (int j = 0; j < max_planes; ++j)
-    for (size_t q = 0; q < nq; ++q) {
-      emit_prefix[(size_t)j * nq + q] = slots;
-      if (!plans[q].dead && j < queries[q].n_phrases) slots += plans[q].plane_slots;
-    }
-  emit_prefix[nv] = slots;
-  const int64_t groups0 = emit_prefix[nq] / 64;  // plane 0's 64-slot groups
-  RGPU_TRY(api_rows_default(c, stream, n_queries, k));
-  if (items > 0) {
-    SCRATCH_TAKE(c);
-    Stager st(c);
-    const auto r_cq = st.add<DevQuery>(nq), r_vq = st.add<DevQuery>(nv);
-    const auto r_cdt = st.add<DevTerm>(cdt.size()), r_pdt = st.add<DevTerm>(pdt.size()), r_sdt = st.add<DevTerm>(std::max<size_t>(1, sdt.size()));
-    const auto r_ppt = st.add<PosTerm>(ppt.size());
-    const auto r_pb = st.add<PhraseBoolDev>(nq);
-    const auto r_or = st.add<int32_t>(order.size());
-    const auto r_ip = st.add<int64_t>(nq + 1), r_ep = st.add<int64_t>(nv + 1), r_cp = st.add<int64_t>(nq + 1);
-    const auto r_sl = st.add<int32_t>(nv);  // slop 0 throughout
-    const auto r_nl = st.add<int32_t>(nq);  // no next_limit: no scorer here is two-phase
-    const auto r_ab = st.add<int32_t>(nq);  // nothing is abandoned
-    const auto r_gr = st.add<SloppyGroups>(nv);
-    const std::vector<TermBitmap> clause_bitmaps = clause_bitmap_table(seg, cq, cdt, bitmap_df);  // (the required clauses: MUST_NOT ones are walked)
-    const auto r_bm = st.add_if<TermBitmap>(!clause_bitmaps.empty(), clause_bitmaps.size());
-    STAGE_SIZED(sg, st);
-    sg.put(r_cq, cq);
-    sg.put(r_vq, vq);
-    sg.put(r_cdt, cdt);
-    sg.put(r_pdt, pdt);
-    sg.put(r_sdt, sdt);
-    sg.put(r_ppt, ppt);
-    sg.put(r_pb, pbd);
-    sg.put(r_or, order);
-    sg.put(r_ip, item_prefix);
-    sg.put(r_ep, emit_prefix);
-    sg.put(r_cp, collect_prefix);
-    sg.fill(r_sl, 0);
-    sg.fill(r_nl, 0xff);
-    sg.fill(r_ab, 0);
-    sg.fill(r_gr, 0xff);
-    sg.put(r_bm, clause_bitmaps);
-    RGPU_TRY(sg.upload(stream));
-    const int64_t *d_ep = sg.dev(r_ep), *d_cp = sg.dev(r_cp);
-    const int32_t *d_sl = sg.dev(r_sl), *d_nl = sg.dev(r_nl);
-    const PhraseBoolDev* d_pb = sg.dev(r_pb);
-    const bool chunked = phrase_collect_chunked(k, collect_items);
-    int64_t redo_cap = 0;  // (sized from the slots of ALL planes: any of them may hand candidates on)
-    // (the conjunctions: one per query, plane 0; slots and counts: every plane's - k_phrase_bool_fanout fills the others)
-    const char* stage_name = masked.on() ? masked_stage_name(c, "k_search_and(masked phrase-bool candidates)", "k_search_and(masked phrase-bool, marked)")
-                                         : "k_search_and(phrase-bool candidates)";
-    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{stage_name, sg.dev(r_cq), sg.dev(r_cdt), sg.dev(r_ip), d_ep,
-                                                      clause_bitmaps.empty() ? nullptr : sg.dev(r_bm), n_queries, nv, items, slots, blocks_per_item, std::min<int>(k, 64),
-                                                      any_not, chunked ? (size_t)collect_items * (size_t)k : 0, chunked ? (size_t)collect_items : 0, &redo_cap, true,
-                                                      masked.on() && c->phrase_mask_compact}));
-    const unsigned ggrid = wg_count((groups0 + WG_WAVES - 1) / WG_WAVES);
-    if (groups0 > 0 && max_planes > 1) {
-      TimedLaunch tl(c, stream, "k_phrase_bool_fanout", 0);
-      RGPU_LAUNCH(k_phrase_bool_fanout, dim3(ggrid), dim3(WG_THREADS), 0, stream, d_pb, d_ep, c->phrase_count.p, c->phrase_docs.p, (int)n_queries, groups0);
-    }
-    RGPU_TRY(phrase_match_stage(seg, stream, PhraseMatchStage{sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ppt), d_ep, d_sl, sg.dev(r_gr), (int32_t)nv, slots, redo_cap, true,
-                                                              false, false, false, nullptr, nullptr, nullptr, 0}));
-    if (groups0 > 0) {
-      const SegView sv = seg_view(seg);
-      TimedLaunch tl(c, stream, "k_phrase_bool_score", 0);
-      auto go = [&](auto kern) {
-        RGPU_LAUNCH(kern, dim3(ggrid), dim3(WG_THREADS), 0, stream, sv, d_pb, (const int32_t*)sg.dev(r_or), (const DevTerm*)sg.dev(r_sdt), d_ep,
-                    (const unsigned long long*)c->phrase_count.p, (int)n_queries, groups0, c->phrase_keys.p, c->d_err);
-      };
-      if (seg->version < 1) go(k_phrase_bool_score<true>); else go(k_phrase_bool_score<false>);
-    }
-    // (no sloppy clause, no next_limit: no scorer here is two-phase, nothing is abandoned)
-    phrase_collect_stage(seg, stream, PhraseCollectStage{d_ep, d_cp, d_sl, d_nl, n_queries, k, collect_items, false, sg.dev(r_ab), nullptr});
-    HIP_TRY(launch_status());
-    // a refused call writes nothing: the match stage's verdict first, the rows after it
-    RGPU_TRY(phrase_match_verdict(c, stream, "a doc holds one of an exact phrase's terms more than 1024 times", "internal: a conjunction match was not found again"));
-  }
-  return api_rows_read_back(c, stream, n_queries, k, hits_out, total_hits_out);
-}
-extern "C" int32_t rgpu_search_phrase_bool_batch(rgpu_segment* seg, const rgpu_phrase_bool_query* queries, int32_t n_queries,
-                                                 const rgpu_phrase_query* phrases, int32_t n_phrases_total,
-                                                 const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
-                                                 const rgpu_query_term* terms, int32_t n_terms_total,
-                                                 int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
-  return search_phrase_bool_batch_impl(seg, nullptr, queries, n_queries, phrases, n_phrases_total, phrase_terms, n_phrase_terms_total, terms, n_terms_total, k,
-                                       hits_out, total_hits_out);
-}
-extern "C" int32_t rgpu_search_phrase_bool_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_bool_query* queries, int32_t n_queries,
-                                                        const rgpu_phrase_query* phrases, int32_t n_phrases_total,
-                                                        const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
-                                                        const rgpu_query_term* terms, int32_t n_terms_total,
-                                                        int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
-  if (!set) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  return search_phrase_bool_batch_impl(seg, set, queries, n_queries, phrases, n_phrases_total, phrase_terms, n_phrase_terms_total, terms, n_terms_total, k,
-                                       hits_out, total_hits_out);
-}
-
-// ---- BooleanQuery of SHOULD / MUST_NOT clauses with exact PhraseQuery clauses among the SHOULD ones: "a b" "c d" e -f -------------
-// (include/rucene_gpu.h rgpu_search_phrase_or_batch; the plan: host/phrase_or_plan.hpp; the run-building kernels:
-// kernels/search_phrase_or.hpp.) Launch sequence, all on the call's stream:
-//   1. and_emit_stage (with phrase_match_setup among its memsets in front of the launch: keys zeroed, the redo list sized, d_err
-//      zeroed): k_search_and in emit mode, one "virtual query" per (query, phrase that exists in the leaf) -> that phrase's
-//      candidate docs (the conjunction of its terms, as rgpu_search_phrase_batch finds them);
-//   2. phrase_match_stage over the virtual queries — exact kernels only: one make_key(BM25(phrase freq, norm), doc) or 0 per slot.
-//      Once per call; its verdict (phrase_match_verdict: a doc that holds a phrase term more than 1024 times ...) is looked at
-//      before anything else runs;
-//   3. api_rows_default, then search_or_group over a Group of op OR: clauses in query order, a pseudo DevTerm (df = capacity) at every phrase position,
-//      MUST_NOT terms behind them (DevQuery::pad), min_should_match in op bits 8... Its hook fills the phrase clauses' runs between
-//      k_score_terms and k_or_windows: k_phrase_run_fill, _count, _scan, _scatter, _sort;
-//   4. k > RGPU_PASS_K: step 3 once per pass of 128 hits, as search_impl runs its passes (rgpu_ctx::Pass, ceiling slots). The keys of
-//      step 2 stay in c->phrase_keys; what the run-building kernels read besides lives in buffers of the context's, not in the scratch
-//      slot that staged steps 1-2 (four passes later that slot is somebody else's).
-static int32_t search_phrase_or_batch_impl(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_or_query* queries, int32_t n_queries,
-                                           const rgpu_phrase_query* phrases, int32_t n_phrases_total,
-                                           const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
-                                           const rgpu_query_term* terms, int32_t n_terms_total,
-                                           int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
-  if (!seg || !queries || n_queries <= 0 || !phrases || n_phrases_total <= 0 || !phrase_terms || n_phrase_terms_total <= 0 || n_terms_total < 0 ||
-      (n_terms_total > 0 && !terms) || !hits_out || !total_hits_out)
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (set) RGPU_TRY(docset_check(seg, set));
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "disjunction over phrases: k must be in 1..RGPU_MAX_K");
-  if (!seg->has_positions || !seg->d_pos) return fail(RGPU_ERR_ILLEGAL_STATE, "a disjunction over phrases needs a positions field with its .pos file attached");
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t stream = c->stream;
-  // ---- validate, plan
-  const size_t nq = (size_t)n_queries;
-  std::vector<const rgpu_term_state*> ptrs;
-  std::vector<rgpu_host::PhraseOrPlan> plans(nq);
-  std::vector<int32_t> first_virtual(nq + 1, 0);  // virtual query (query q, phrase j) = first_virtual[q] + j
-  const PhraseClauseArrays arrays{phrases, n_phrases_total, phrase_terms, n_phrase_terms_total, terms, n_terms_total};
-  for (int32_t q = 0; q < n_queries; ++q) {
-    const rgpu_phrase_or_query& Q = queries[q];
-    RGPU_TRY(check_phrases_query(seg, Q, "a disjunction over phrases", arrays, &ptrs));
-    plans[(size_t)q] = rgpu_host::plan_phrase_or(Q, phrases, phrase_terms, terms);
-    if (plans[(size_t)q].status != RGPU_OK) return fail(plans[(size_t)q].status, plans[(size_t)q].why);
-    first_virtual[(size_t)q + 1] = first_virtual[(size_t)q] + Q.n_phrases;
-  }
-  PhraseMask masked;  // (installed for the whole call: every pass of k > RGPU_PASS_K runs under it)
-  RGPU_TRY(masked.install(seg, set));
-  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
-  // the candidate conjunctions answer a dense clause from its doc bitmap, as a phrase search's do
-  int64_t bitmap_df = INT64_MAX;
-  {
-    std::vector<const rgpu_term_state*> clauses;
-    std::vector<int32_t> clause_sim;
-    clauses.reserve(ptrs.size());  // (every clause of a conjunction is a live term: ptrs holds them all)
-    clause_sim.reserve(ptrs.size());
-    for (int32_t q = 0; q < n_queries; ++q) {
-      const rgpu_host::PhraseOrPlan& P = plans[(size_t)q];
-      if (P.dead) continue;
-      for (int j = 0; j < queries[q].n_phrases; ++j) {
-        if (P.capacity[(size_t)j] <= 0) continue;
-        const rgpu_phrase_query& ph = phrases[queries[q].first_phrase + j];
-        for (int i = 0; i < ph.n_terms; ++i) { clauses.push_back(&phrase_terms[ph.first_term + i].state); clause_sim.push_back(ph.sim_table); }
-      }
-    }
-    RGPU_TRY(ensure_and_bitmaps_locked(seg, clauses, clause_sim, &bitmap_df));
-  }
-  // ---- the match stage's arrays (one virtual query per phrase) and the disjunction's Group
-  const size_t nv = (size_t)first_virtual[nq];
-  std::vector<DevQuery> vq(nv, DevQuery{RGPU_OP_AND, 0, 0, 0});
-  std::vector<DevTerm> pdt;
-  std::vector<PosTerm> ppt;
-  std::vector<int64_t> item_prefix(nv + 1), emit_prefix(nv + 1);
-  std::vector<PhraseRunDev> prd(nv, PhraseRunDev{0, 0});
-  int64_t lead_blocks = 0;
-  for (const rgpu_host::PhraseOrPlan& P : plans) if (!P.dead) for (int32_t cap : P.capacity) lead_blocks += cap / 128;
-  const int blocks_per_item = and_item_blocks(c, lead_blocks);
-  Group G0;
-  G0.op = RGPU_OP_OR;
-  OrPhraseRuns hook;
-  int64_t items = 0, slots = 0;
-  for (int32_t q = 0; q < n_queries; ++q) {
-    const rgpu_phrase_or_query& Q = queries[q];
-    const rgpu_host::PhraseOrPlan& P = plans[(size_t)q];
-    for (int j = 0; j < Q.n_phrases; ++j) {
-      const size_t v = (size_t)first_virtual[(size_t)q] + (size_t)j;
-      item_prefix[v] = items;
-      emit_prefix[v] = slots;
-      vq[v].first_term = (int32_t)pdt.size();
-      if (P.dead || P.capacity[(size_t)j] <= 0) continue;
-      const rgpu_phrase_query& ph = phrases[Q.first_phrase + j];
-      bool dead = false;
-      RGPU_TRY(emit_phrase(seg, ph, phrase_terms, &pdt, &ppt, &dead));  // (dead: the plan has said so already)
-      if (dead) continue;
-      vq[v].n_terms = ph.n_terms;
-      const DevTerm& lead = pdt[(size_t)vq[v].first_term];
-      if (lead.df != P.capacity[(size_t)j]) return fail(RGPU_ERR_ILLEGAL_STATE, "internal: a phrase's lead term is not its rarest");
-      items += lead_items(lead, blocks_per_item);
-      slots += lead_slots(lead);
-    }
-    // DisjunctionSumScorer's children in query order, pseudo terms at the phrase positions; the MUST_NOT terms behind them
-    DevQuery dq{RGPU_OP_OR | (P.min_should_match > 1 ? P.min_should_match << 8 : 0), 0, (int32_t)G0.terms.size(), 0};
-    if (!P.dead) {
-      for (int32_t o : P.order) {
-        DevTerm t;
-        if (o >= 0) {
-          const rgpu_query_term& qt = terms[Q.first_term + o];
-          RGPU_TRY(make_dev_term(seg, qt.state, qt.weight, qt.sim_table, &t));
-        } else {
-          std::memset(&t, 0, sizeof t);
-          t.df = P.capacity[(size_t)~o];
-          t.singleton_doc = -1;
-          t.sim_table = phrases[Q.first_phrase + ~o].sim_table;  // (never read: the clause has no k_score_terms item and is never dense)
-          prd[(size_t)first_virtual[(size_t)q] + (size_t)~o] = PhraseRunDev{(int32_t)G0.terms.size(), t.df};
-        }
-        G0.terms.push_back(t);
-        hook.pseudo.push_back(o < 0 ? 1 : 0);
-        G0.postings += t.df;
-      }
-      for (const rgpu_term_state* st : P.must_not) {
-        DevTerm t;
-        RGPU_TRY(make_dev_term(seg, *st, 0.0f, 0, &t));  // needs_scores = false: weight and table are never read
-        G0.terms.push_back(t);
-        hook.pseudo.push_back(0);
-        G0.postings += t.df;
-      }
-      dq.n_terms = (int32_t)P.order.size();
-      dq.pad = (int32_t)P.must_not.size();
-    }
-    G0.queries.push_back(dq);
-    G0.qmap.push_back(q);
-  }
-  item_prefix[nv] = items;
-  emit_prefix[nv] = slots;
-  const int n_buckets = (int)(((int64_t)seg->max_doc + PHRASE_OR_BUCKET - 1) / PHRASE_OR_BUCKET);
-  const size_t n_cells = nv * (size_t)std::max(1, n_buckets);
-  if (items > 0) {
-    // ---- 1. + 2.: candidates and keys, once per call
-    SCRATCH_TAKE(c);
-    Stager st(c);
-    const auto r_vq = st.add<DevQuery>(nv);
-    const auto r_pdt = st.add<DevTerm>(pdt.size());
-    const auto r_ppt = st.add<PosTerm>(ppt.size());
-    const auto r_ip = st.add<int64_t>(nv + 1), r_ep = st.add<int64_t>(nv + 1);
-    const auto r_sl = st.add<int32_t>(nv);  // slop 0 throughout
-    const auto r_gr = st.add<SloppyGroups>(nv);
-    const std::vector<TermBitmap> clause_bitmaps = clause_bitmap_table(seg, vq, pdt, bitmap_df);
-    const auto r_bm = st.add_if<TermBitmap>(!clause_bitmaps.empty(), clause_bitmaps.size());
-    STAGE_SIZED(sg, st);
-    sg.put(r_vq, vq);
-    sg.put(r_pdt, pdt);
-    sg.put(r_ppt, ppt);
-    sg.put(r_ip, item_prefix);
-    sg.put(r_ep, emit_prefix);
-    sg.fill(r_sl, 0);
-    sg.fill(r_gr, 0xff);
-    sg.put(r_bm, clause_bitmaps);
-    RGPU_TRY(sg.upload(stream));
-    int64_t redo_cap = 0;
-    // (one conjunction per virtual query; the MUST_NOT clauses belong to the disjunction, step 3; nothing is collected here)
-    const char* stage_name = masked.on() ? masked_stage_name(c, "k_search_and(masked phrase-or candidates)", "k_search_and(masked phrase-or, marked)")
-                                         : "k_search_and(phrase-or candidates)";
-    RGPU_TRY(and_emit_stage(seg, stream, AndEmitStage{stage_name, sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ip), sg.dev(r_ep),
-                                                      clause_bitmaps.empty() ? nullptr : sg.dev(r_bm), (int32_t)nv, nv, items, slots, blocks_per_item,
-                                                      std::min<int>(k, 64), false, 0, 0, &redo_cap, true, masked.on() && c->phrase_mask_compact}));
-    RGPU_TRY(phrase_match_stage(seg, stream, PhraseMatchStage{sg.dev(r_vq), sg.dev(r_pdt), sg.dev(r_ppt), sg.dev(r_ep), sg.dev(r_sl), sg.dev(r_gr), (int32_t)nv, slots,
-                                                              redo_cap, true, false, false, false, nullptr, nullptr, nullptr, 0}));
-    HIP_TRY(launch_status());
-    // a refused call writes nothing: the match stage's verdict before the disjunction runs (the sync also frees the slot's stage)
-    RGPU_TRY(phrase_match_verdict(c, stream, "a doc holds one of an exact phrase's terms more than 1024 times", "internal: a conjunction match was not found again"));
-    // what the run-building kernels read in every pass
-    HIP_TRY(c->phrase_or_prefix.reserve(nv + 1, 0, stream));
-    HIP_TRY(c->phrase_or_runs.reserve(nv, 0, stream));
-    HIP_TRY(c->phrase_or_buckets.reserve(2 * n_cells, 0, stream));
-    HIP_TRY(hipMemcpyAsync(c->phrase_or_prefix.p, emit_prefix.data(), (nv + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(c->phrase_or_runs.p, prd.data(), nv * sizeof(PhraseRunDev), hipMemcpyHostToDevice, stream));
-  }
-  // ---- 3.: the hook of search_or_group — the phrase clauses' runs (bounds: kernels/search_phrase_or.hpp)
-  hook.fill = [&](const int64_t* d_run_prefix, ScoredPosting* runs) -> int32_t {
-    if (items <= 0 || n_buckets <= 0) return RGPU_OK;  // (no phrase exists in this leaf: the group holds no pseudo term)
-    const PhraseRunDev* d_pr = c->phrase_or_runs.p;
-    uint32_t* counts = c->phrase_or_buckets.p;
-    uint32_t* offsets = counts + n_cells;
-    const int groups_per_clause = (n_buckets + 63) / 64;  // k_phrase_run_sort: one wavefront per (clause, 64 buckets)
-    const int64_t groups = slots / 64, sort_items = (int64_t)nv * groups_per_clause;
-    const unsigned ggrid = wg_count((groups + WG_WAVES - 1) / WG_WAVES);
-    HIP_TRY(hipMemsetAsync(counts, 0, n_cells * sizeof(uint32_t), stream));
-    {
-      TimedLaunch tl(c, stream, "k_phrase_run_fill", 0);
-      RGPU_LAUNCH(k_phrase_run_fill, dim3((unsigned)nv, PHRASE_OR_FILL_SPLIT), dim3(WG_THREADS), 0, stream, d_pr, d_run_prefix, runs);
-    }
-    {
-      TimedLaunch tl(c, stream, "k_phrase_run_count", 0);
-      RGPU_LAUNCH(k_phrase_run_place<false>, dim3(ggrid), dim3(WG_THREADS), 0, stream, d_pr, (const int64_t*)c->phrase_or_prefix.p,
-                  (const unsigned long long*)c->phrase_count.p, (const uint64_t*)c->phrase_keys.p, (int)nv, groups, seg->max_doc, n_buckets, counts,
-                  (const uint32_t*)offsets, d_run_prefix, runs);
-    }
-    {
-      TimedLaunch tl(c, stream, "k_phrase_run_scan", 0);
-      RGPU_LAUNCH(k_phrase_run_scan, dim3(wg_count((nv + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, (int)nv, n_buckets, counts, offsets);
-    }
-    {
-      TimedLaunch tl(c, stream, "k_phrase_run_scatter", 0);
-      RGPU_LAUNCH(k_phrase_run_place<true>, dim3(ggrid), dim3(WG_THREADS), 0, stream, d_pr, (const int64_t*)c->phrase_or_prefix.p,
-                  (const unsigned long long*)c->phrase_count.p, (const uint64_t*)c->phrase_keys.p, (int)nv, groups, seg->max_doc, n_buckets, counts,
-                  (const uint32_t*)offsets, d_run_prefix, runs);
-    }
-    {
-      TimedLaunch tl(c, stream, "k_phrase_run_sort", 0);
-      RGPU_LAUNCH(k_phrase_run_sort, dim3(wg_count((sort_items + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, d_pr, sort_items, n_buckets,
-                  groups_per_clause, (const uint32_t*)counts, (const uint32_t*)offsets, d_run_prefix, runs);
-    }
-    return RGPU_OK;
-  };
-  // one pass: defaults for every row (a leaf that holds no clause of any query merges nothing), then the group
-  auto one_pass = [&](int32_t k_pass) -> int32_t {
-    const RowColumns cols{k_pass, c->pass.stride > 0 ? c->pass.stride : k_pass, c->pass.col0};
-    RGPU_TRY(api_rows_default(c, stream, n_queries, k, &cols));
-    if (c->pass.ceil_out) HIP_TRY(hipMemsetAsync(c->pass.ceil_out, 0, nq * 8, stream));
-    Group G = G0;  // (search_or_group marks dense clauses in the group it is given)
-    return search_or_group(seg, G, k_pass, c->host_api_hits.p, c->host_api_totals.p, stream, &hook);
-  };
-  c->pass = rgpu_ctx::Pass{};
-  int32_t rc = RGPU_OK;
-  if (k <= RGPU_PASS_K) {
-    rc = one_pass(k);
-  } else {  // search_impl's passes: pass p collects the best hits strictly below the worst hit of pass p - 1
-    rgpu_ctx::CeilSlot& cs = c->ceil_slots[c->ceil_next];
-    c->ceil_next = (c->ceil_next + 1) % N_SCRATCH;
-    if (cs.busy) { HIP_TRY(hipEventSynchronize(cs.done)); cs.busy = false; }
-    HIP_TRY(cs.d.reserve(nq * 2, 0, stream));
-    int flip = 0;
-    for (int32_t col0 = 0; col0 < k && rc == RGPU_OK; col0 += RGPU_PASS_K, flip ^= 1) {
-      c->pass.stride = k;
-      c->pass.col0 = col0;
-      c->pass.ceil_in = col0 == 0 ? nullptr : cs.d.p + (size_t)(flip ^ 1) * nq;
-      c->pass.ceil_out = cs.d.p + (size_t)flip * nq;
-      rc = one_pass(std::min<int32_t>(RGPU_PASS_K, k - col0));
-    }
-    c->pass = rgpu_ctx::Pass{};
-  }
-  if (rc != RGPU_OK) { (void)hipStreamSynchronize(stream); return rc; }
-  HIP_TRY(launch_status());
-  return api_rows_read_back(c, stream, n_queries, k, hits_out, total_hits_out);
-}
-extern "C" int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phrase_or_query* queries, int32_t n_queries,
-                                               const rgpu_phrase_query* phrases, int32_t n_phrases_total,
-                                               const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
-                                               const rgpu_query_term* terms, int32_t n_terms_total,
-                                               int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
-  return search_phrase_or_batch_impl(seg, nullptr, queries, n_queries, phrases, n_phrases_total, phrase_terms, n_phrase_terms_total, terms, n_terms_total, k,
-                                     hits_out, total_hits_out);
-}
-extern "C" int32_t rgpu_search_phrase_or_batch_masked(rgpu_segment* seg, rgpu_docset* set, const rgpu_phrase_or_query* queries, int32_t n_queries,
-                                                      const rgpu_phrase_query* phrases, int32_t n_phrases_total,
-                                                      const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
-                                                      const rgpu_query_term* terms, int32_t n_terms_total,
-                                                      int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out) {
-  if (!set) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  return search_phrase_or_batch_impl(seg, set, queries, n_queries, phrases, n_phrases_total, phrase_terms, n_phrase_terms_total, terms, n_terms_total, k,
-                                     hits_out, total_hits_out);
-}
-
-// ---- QueryRescorer ------------------------------------------------------------------------------------------------------------
-static_assert(sizeof(RescoreParams) == sizeof(rgpu_rescore_request), "RescoreParams mirrors rgpu_rescore_request");
-// a row's request, as the kernels read it: the window is cut to the row and to what one pass sorts
-static int32_t rescore_params_of(const rgpu_rescore_request& r, int32_t k, RescoreParams* out) {
-  if (r.mode < RGPU_RESCORE_AVG || r.mode > RGPU_RESCORE_MULTIPLY || r.window_size < 0) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad rescore request");
-  *out = RescoreParams{r.query_weight, r.rescore_weight, r.mode, std::min(std::min(r.window_size, k), RGPU_PASS_K)};
-  return RGPU_OK;
-}
-// `finish`: every row's window back into score order
-static void launch_rescore_sort(rgpu_ctx* c, hipStream_t stream, RescoreParams* d_r, int32_t n_queries, int32_t k) {
-  TimedLaunch tl(c, stream, "k_rescore_sort", 0);
-  RGPU_LAUNCH(k_rescore_sort, dim3(wg_count((n_queries + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, stream, d_r, (int)n_queries, (int)k, c->host_api_hits.p);
-}
-extern "C" int32_t rgpu_rescore_batch(rgpu_segment* seg, const rgpu_query* queries, int32_t n_queries, const rgpu_query_term* terms,
-                                      int32_t n_terms_total, const rgpu_rescore_request* requests, int32_t k, rgpu_hit* hits_inout,
-                                      int32_t finish) {
-  if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !requests || !hits_inout)
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (k <= 0 || k > RGPU_PASS_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "rescoring: k must be in 1..128");
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t stream = c->stream;
-  std::vector<const rgpu_term_state*> ptrs;
-  std::vector<RescoreParams> rp((size_t)n_queries);
-  for (int32_t q = 0; q < n_queries; ++q) {
-    const rgpu_query& Q = queries[q];
-    const int qop = Q.op & 0xff;
-    if (qop < RGPU_OP_TERM || qop > RGPU_OP_OR || (Q.op >> 8) > 1 || Q.n_must_not != 0)  // (MUST_NOT or demoting clauses: any bit of the field)
-      return fail(RGPU_ERR_UNSUPPORTED, "rescore queries are TERM, all-MUST or all-SHOULD term queries");
-    if (Q.n_terms < 1 || Q.n_terms > RGPU_MAX_QUERY_TERMS || (qop == RGPU_OP_TERM && Q.n_terms != 1)) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad clause count");
-    if (Q.first_term < 0 || (int64_t)Q.first_term + Q.n_terms > (int64_t)n_terms_total) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "clause range outside terms[]");
-    RGPU_TRY(rescore_params_of(requests[q], k, &rp[(size_t)q]));
-    for (int i = 0; i < Q.n_terms; ++i) {
-      const rgpu_query_term& t = terms[Q.first_term + i];
-      if (t.sim_table < 0 || t.sim_table >= c->n_sim_tables) return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "unknown sim_table handle");
-      if (t.state.doc_freq > 0) ptrs.push_back(&t.state);
-    }
-  }
-  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
-  std::vector<DevQuery> dq((size_t)n_queries);
-  std::vector<DevTerm> dt;
-  std::vector<DevTerm> mine;
-  for (int32_t q = 0; q < n_queries; ++q) {
-    const rgpu_query& Q = queries[q];
-    const int qop = Q.op & 0xff;
-    mine.clear();
-    bool dead = false;
-    for (int i = 0; i < Q.n_terms; ++i) {
-      const rgpu_query_term& t = terms[Q.first_term + i];
-      if (t.state.doc_freq <= 0) { if (qop != RGPU_OP_OR) dead = true; continue; }  // create_scorer -> None: the query matches nothing here
-      DevTerm d;
-      RGPU_TRY(make_dev_term(seg, t.state, t.weight, t.sim_table, &d));
-      mine.push_back(d);
-    }
-    if (dead) mine.clear();
-    if (qop == RGPU_OP_AND) std::stable_sort(mine.begin(), mine.end(), [](const DevTerm& a, const DevTerm& b) { return a.df < b.df; });
-    dq[(size_t)q] = DevQuery{qop, (int32_t)mine.size(), (int32_t)dt.size(), 0};
-    for (auto& m : mine) dt.push_back(m);
-  }
-  SCRATCH_TAKE(c);
-  Stager st(c);
-  const auto r_q = st.add<DevQuery>((size_t)n_queries);
-  const auto r_t = st.add<DevTerm>(std::max<size_t>(1, dt.size()));
-  const auto r_r = st.add<RescoreParams>((size_t)n_queries);
-  STAGE_SIZED(sg, st);
-  sg.put(r_q, dq);
-  sg.put(r_t, dt);
-  sg.put(r_r, rp);
-  RGPU_TRY(sg.upload(stream));
-  const size_t n_hits = (size_t)n_queries * (size_t)k;
-  HIP_TRY(c->host_api_hits.reserve(n_hits, 0, stream));
-  HIP_TRY(hipMemcpyAsync(c->host_api_hits.p, hits_inout, n_hits * sizeof(HitOut), hipMemcpyHostToDevice, stream));
-  const DevQuery* d_q = sg.dev(r_q);
-  const DevTerm* d_t = sg.dev(r_t);
-  RescoreParams* d_r = sg.dev(r_r);
-  {
-    TimedLaunch tl(c, stream, "k_rescore", 0);
-    const unsigned grid = wg_count((n_hits + WG_WAVES - 1) / WG_WAVES);
-    if (seg->version < 1) RGPU_LAUNCH(k_rescore<true>, dim3(grid), dim3(WG_THREADS), 0, stream, seg_view(seg), d_q, d_t, d_r, (int)n_queries, (int)k, c->host_api_hits.p, finish ? 1 : 0);
-    else RGPU_LAUNCH(k_rescore<false>, dim3(grid), dim3(WG_THREADS), 0, stream, seg_view(seg), d_q, d_t, d_r, (int)n_queries, (int)k, c->host_api_hits.p, finish ? 1 : 0);
-  }
-  if (finish) launch_rescore_sort(c, stream, d_r, n_queries, k);
-  HIP_TRY(launch_status());
-  HIP_TRY(hipMemcpyAsync(hits_inout, c->host_api_hits.p, n_hits * sizeof(HitOut), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  return RGPU_OK;
-}
-
-// QueryRescorer whose second query is a PhraseQuery: the window's hits are the candidate slots of the phrase match stage.
-extern "C" int32_t rgpu_rescore_phrase_batch(rgpu_segment* seg, const rgpu_phrase_query* queries, int32_t n_queries,
-                                             const rgpu_phrase_term* terms, int32_t n_terms_total, const rgpu_rescore_request* requests,
-                                             int32_t k, rgpu_hit* hits_inout, int32_t finish) {
-  if (!seg || !queries || n_queries <= 0 || !terms || n_terms_total <= 0 || !requests || !hits_inout)
-    return fail(RGPU_ERR_ILLEGAL_ARGUMENT, "bad arguments");
-  if (k <= 0 || k > RGPU_MAX_K) return fail(k <= 0 ? RGPU_ERR_ILLEGAL_ARGUMENT : RGPU_ERR_UNSUPPORTED, "phrase rescoring: k must be in 1..RGPU_MAX_K");
-  if (!seg->has_positions || !seg->d_pos) return fail(RGPU_ERR_ILLEGAL_STATE, "phrase rescoring needs a positions field with its .pos file attached");
-  rgpu_ctx* c = seg->ctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t stream = c->stream;
-  // ---- validate (every refusal comes before hits_inout is touched)
-  std::vector<const rgpu_term_state*> ptrs;
-  std::vector<RescoreParams> rp((size_t)n_queries);
-  for (int32_t q = 0; q < n_queries; ++q) {
-    RGPU_TRY(check_phrase_query(c, queries[q], n_terms_total, false));
-    RGPU_TRY(rescore_params_of(requests[q], k, &rp[(size_t)q]));
-    RGPU_TRY(check_phrase_terms(seg, queries[q], terms, &ptrs));
-  }
-  for (int32_t q = 0; q < n_queries; ++q) {
-    const rgpu_phrase_query& Q = queries[q];
-    // SloppyPhraseScorer finds its repetition groups on the first doc it evaluates in the leaf (init_first_time,
-    // phrase_scorer.rs:807-820): in a rescoring that is a conjunction match at or behind the first window hit, not a hit.
-    // (A row with a term absent from the leaf is served whatever its terms — create_scorer -> None, nothing matches — and
-    // emit_phrase fills same_as for live rows only: absent terms all look alike.)
-    if (Q.slop > 0 && !phrase_is_dead(Q, terms))
-      for (int i = 1; i < Q.n_terms; ++i)
-        for (int j = 0; j < i; ++j)
-          if (same_term(terms[Q.first_term + j].state, terms[Q.first_term + i].state))
-            return fail(RGPU_ERR_UNSUPPORTED, "phrase rescoring: a sloppy phrase that names a term twice is not served");
-  }
-  RGPU_TRY(prepare_terms_locked(seg, ptrs.data(), ptrs.size()));
-  // ---- plan: row q owns the candidate slots [q * S, q * S + S)
-  const int S = (int)rgpu_host::pb_round_up_64(k);
-  const int64_t slots = (int64_t)n_queries * S;
-  std::vector<DevQuery> dq((size_t)n_queries);
-  std::vector<DevTerm> dt;
-  std::vector<PosTerm> pt;
-  std::vector<int64_t> emit_prefix((size_t)n_queries + 1);
-  std::vector<unsigned long long> emit_count((size_t)n_queries);
-  std::vector<int32_t> slops((size_t)n_queries, 0);
-  bool any_sloppy = false, any_exact = false;
-  for (int32_t q = 0; q < n_queries; ++q) {
-    const rgpu_phrase_query& Q = queries[q];
-    emit_prefix[(size_t)q] = (int64_t)q * S;
-    emit_count[(size_t)q] = (unsigned long long)rp[(size_t)q].window;
-    dq[(size_t)q] = DevQuery{RGPU_OP_AND, 0, (int32_t)dt.size(), 0};
-    bool dead = false;  // (no hit of the row matches in this leaf)
-    RGPU_TRY(emit_phrase(seg, Q, terms, &dt, &pt, &dead));  // (same_as != query_ord: exact phrases only here, "a b a")
-    if (dead) continue;
-    slops[(size_t)q] = Q.slop;
-    (Q.slop > 0 ? any_sloppy : any_exact) = true;
-    dq[(size_t)q].n_terms = Q.n_terms;
-  }
-  emit_prefix[(size_t)n_queries] = slots;
-  SCRATCH_TAKE(c);
-  Stager st(c);
-  const auto r_q = st.add<DevQuery>((size_t)n_queries);
-  const auto r_t = st.add<DevTerm>(std::max<size_t>(1, dt.size()));
-  const auto r_pt = st.add<PosTerm>(std::max<size_t>(1, pt.size()));
-  const auto r_ep = st.add<int64_t>((size_t)n_queries + 1);
-  const auto r_ec = st.add<unsigned long long>((size_t)n_queries);
-  const auto r_sl = st.add<int32_t>((size_t)n_queries);
-  const auto r_gr = st.add<SloppyGroups>((size_t)n_queries);
-  const auto r_r = st.add<RescoreParams>((size_t)n_queries);
-  STAGE_SIZED(sg, st);
-  sg.put(r_q, dq);
-  sg.put(r_t, dt);
-  sg.put(r_pt, pt);
-  sg.put(r_ep, emit_prefix);
-  sg.put(r_ec, emit_count);
-  sg.put(r_sl, slops);
-  sg.fill(r_gr, 0xff);  // "no repetition group": k_sloppy_match reads the region
-  sg.put(r_r, rp);
-  RGPU_TRY(sg.upload(stream));
-  const size_t n_hits = (size_t)n_queries * (size_t)k;
-  HIP_TRY(c->host_api_hits.reserve(n_hits, 0, stream));
-  HIP_TRY(hipMemcpyAsync(c->host_api_hits.p, hits_inout, n_hits * sizeof(HitOut), hipMemcpyHostToDevice, stream));
-  int64_t redo_cap = 0;
-  // (zero_keys: k_rescore_phrase_combine reads the slots behind a row's window, and a batch of absent-term rows launches no match kernel)
-  RGPU_TRY(phrase_match_setup(c, stream, slots, true, &redo_cap));
-  HIP_TRY(c->phrase_count.reserve((size_t)n_queries, 0, stream));
-  HIP_TRY(hipMemcpyAsync(c->phrase_count.p, sg.dev(r_ec), (size_t)n_queries * 8, hipMemcpyDeviceToDevice, stream));
-  const DevQuery* d_q = sg.dev(r_q);
-  const DevTerm* d_t = sg.dev(r_t);
-  RescoreParams* d_r = sg.dev(r_r);
-  const SegView sv = seg_view(seg);
-  {
-    TimedLaunch tl(c, stream, "k_rescore_phrase_candidates", 0);
-    const unsigned grid = wg_count((slots + WG_WAVES - 1) / WG_WAVES);
-    if (seg->version < 1) RGPU_LAUNCH(k_rescore_phrase_candidates<true>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_r, (int)n_queries, (int)k, S, c->host_api_hits.p, c->phrase_docs.p);
-    else RGPU_LAUNCH(k_rescore_phrase_candidates<false>, dim3(grid), dim3(WG_THREADS), 0, stream, sv, d_q, d_t, d_r, (int)n_queries, (int)k, S, c->host_api_hits.p, c->phrase_docs.p);
-  }
-  RGPU_TRY(phrase_match_stage(seg, stream, PhraseMatchStage{d_q, d_t, sg.dev(r_pt), sg.dev(r_ep), sg.dev(r_sl), sg.dev(r_gr), n_queries, slots, redo_cap, any_exact,
-                                                            any_sloppy, false, false, nullptr, nullptr, nullptr, 0}));
-  {
-    TimedLaunch tl(c, stream, "k_rescore_phrase_combine", 0);
-    RGPU_LAUNCH(k_rescore_phrase_combine, dim3(wg_count((n_hits + 255) / 256)), dim3(256), 0, stream, sv, d_r, (int)n_queries, (int)k, S, c->phrase_keys.p, c->host_api_hits.p, finish ? 1 : 0);
-  }
-  if (finish) launch_rescore_sort(c, stream, d_r, n_queries, k);
-  HIP_TRY(launch_status());
-  // (a refusal here too leaves hits_inout as it came)
-  RGPU_TRY(phrase_match_verdict(c, stream, "a hit doc holds one of an exact phrase's terms more than 1024 times (a sloppy phrase's terms: more than 2048 times in all)",
-                               "internal: a candidate doc was not found again"));
-  HIP_TRY(hipMemcpyAsync(hits_inout, c->host_api_hits.p, n_hits * sizeof(HitOut), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  return RGPU_OK;
-}
-
 // ---- the tail of this translation unit, cut by concern ------------------------------------------------------------------
-// The first step of splitting this file: what followed here stands in the parts below, moved verbatim. A part is not a header of
-// its own: it relies on everything above and on the parts in front of it (each says on what), so the order is part of the program.
+// Everything from the candidate stage on stands in the parts below, moved verbatim (scripts/same_translation_unit.sh). A part is not a
+// header of its own: it relies on everything above and on the parts in front of it (each says on what), so the order is part of the program.
 // Each part is included once, here and nowhere else (tests/test_api_parts.py); nothing else is defined from here on.
-#include "api/sharded.hpp"       // rgpu_comm_*, records, rgpu_search_batch_record_device, rgpu_merge_records_device, rgpu_search_batch_sharded*
-#include "api/host_formats.hpp"  // rgpu_bm25_*, norms, live docs, rgpu_terms_*, segment / commit / compound / field infos
-#include "api/planner.hpp"       // rgpu_planner_create* / destroy / sim_table, rgpu_plan_batch_*, rgpu_plan_uniform_*
-#include "api/fused.hpp"         // term_batch_resident, term_batch_fast, search_uniform_locked, rgpu_planner_search_uniform_ids_device / _sharded
-#include "api/fields.hpp"        // rgpu_segment_attach_field / _prepare_field_terms / _get_field_info, rgpu_search_fields_batch
-#include "api/debug.hpp"         // rgpu_bm25_encode_norm; rgpu_debug_counters / rgpu_debug_trace of the variant builds
+#include "api/rows.hpp"            // rgpu_search_batch; api_rows_default / api_rows_read_back, search_batch_host_locked, phrase_redo_cap
+#include "api/candidates.hpp"      // phrase_match_setup, lead_items / lead_slots / lead_collect_chunks, and_emit_stage
+#include "api/docsets.hpp"         // rgpu_docset, docset_*, rgpu_docset_from_words / _from_docs / _combine / _cardinality / _bytes / _words / _free
+#include "api/point_ranges.hpp"    // rgpu_points, rgpu_points_attach / _get_info / _free, rgpu_docset_from_point_ranges
+#include "api/docset_collect.hpp"  // rgpu_docset_collect_batch
+#include "api/masked.hpp"          // docset_mask_locked, MaskScope, PhraseMask, rgpu_search_batch_device_masked, rgpu_search_batch_masked
+#include "api/counts.hpp"          // rgpu_count_batch
+#include "api/required_set.hpp"    // rgpu_docset_head, rgpu_search_batch_device_required_set / _required_set, rgpu_merge_topk_device
+#include "api/positions.hpp"       // rgpu_segment_attach_positions / _payloads, rgpu_decode_positions / _device
+#include "api/phrase_stages.hpp"   // phrase_match_stage, check_phrase_*, emit_phrase, phrase_match_verdict, phrase_collect_stage
+#include "api/phrase_search.hpp"   // rgpu_search_phrase_batch / _masked, rgpu_search_span_near_batch, rgpu_search_span_unordered_batch
+#include "api/phrase_bool.hpp"     // rgpu_search_phrase_bool_batch / _masked
+#include "api/phrase_or.hpp"       // rgpu_search_phrase_or_batch / _masked
+#include "api/rescore.hpp"         // rgpu_rescore_batch, rgpu_rescore_phrase_batch
+#include "api/sharded.hpp"         // rgpu_comm_*, records, rgpu_search_batch_record_device, rgpu_merge_records_device, rgpu_search_batch_sharded*
+#include "api/host_formats.hpp"    // rgpu_bm25_*, norms, live docs, rgpu_terms_*, segment / commit / compound / field infos
+#include "api/planner.hpp"         // rgpu_planner_create* / destroy / sim_table, rgpu_plan_batch_*, rgpu_plan_uniform_*
+#include "api/fused.hpp"           // term_batch_resident, term_batch_fast, search_uniform_locked, rgpu_planner_search_uniform_ids_device / _sharded
+#include "api/fields.hpp"          // rgpu_segment_attach_field / _prepare_field_terms / _get_field_info, rgpu_search_fields_batch
+#include "api/debug.hpp"           // rgpu_bm25_encode_norm; rgpu_debug_counters / rgpu_debug_trace of the variant builds

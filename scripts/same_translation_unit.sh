@@ -2,6 +2,9 @@
 # Is the working tree's rucene_amd/csrc/rgpu_api.hip the same program as the one at <git-rev>? For changes that only move text between
 # files (the parts under csrc/api/): nothing the compiler sees may differ. No GPU. Exits non-zero at the first difference.
 #   scripts/same_translation_unit.sh <git-rev>
+# (0) the expanded source text, comments included, which (a) cannot see: rgpu_api.hip in front of the banner of its tail, then each part
+#     in include order without its head (everything through its "Not a stand-alone header" line and the blank line behind it), with
+#     `#include "../host/` read as `#include "host/`. First, because it is instant: text moved verbatim and in order compares equal;
 # (a) the preprocessed text (hipcc -E -P, blank lines deleted) of the host and of the device side, for the default build and for each
 #     variant macro the file branches on;
 # (b) the device-only object of the default build, under the build's own flags and one fixed compilation-unit id on both sides
@@ -35,6 +38,21 @@ pair() {
 }
 
 echo "rgpu_api.hip: the working tree against $(git -C "$R" rev-parse --short "$REV")"
+# (0) expanded <csrc dir>: rgpu_api.hip in front of the banner of its tail, then every part in include order, each from behind its head
+expanded() {
+  sed '/^\/\/ ---- the tail of this translation unit/,$d' "$1/rgpu_api.hip"
+  sed -n 's|^#include "\(api/[a-z_]*\.hpp\)".*|\1|p' "$1/rgpu_api.hip" | while read -r part; do
+    awk 'h == 2 { print } h == 1 { h = 2; if ($0 != "") print } h == 0 && /Not a stand-alone header/ { h = 1 }' "$1/$part"
+  done
+}
+expanded "$T/old/rucene_amd/csrc" | sed 's|#include "\.\./host/|#include "host/|' > "$T/out/expanded.old"
+expanded "$R/rucene_amd/csrc" | sed 's|#include "\.\./host/|#include "host/|' > "$T/out/expanded.new"
+if ! cmp -s "$T/out/expanded.old" "$T/out/expanded.new"; then
+  echo "DIFFERENT  expanded source text"
+  diff "$T/out/expanded.old" "$T/out/expanded.new" | head -n 20
+  exit 1
+fi
+printf 'same  expanded source text  %d lines\n' "$(wc -l < "$T/out/expanded.new")"
 for variant in "" -DRGPU_LZ_TIME -DRGPU_ORX_TIME -DRGPU_AND_TIME -DRGPU_TERM_TRACE -DRGPU_AND_TRACE -DRGPU_EXP_COUNT -DRGPU_EXP_KEEP_TAU \
                -DRGPU_HOST_TIME -DRGPU_ORX_WAVES=16; do
   for side in host device; do
