@@ -164,7 +164,13 @@ typedef enum rgpu_query_op {
  * MUST score alone (:46-50). That rule is applied (default): the conjunction kernel leaves one record per lead posting and a
  * second kernel walks a query's matches in doc order (a sequential pass: a few ms per million matches) — scores equal the
  * reference's bit for bit. rgpu_config.req_opt_rule = -1 always adds the optional sums instead (one pass; doc ids and hit
- * counts equal the reference's, scores >= its and equal wherever it did not skip). */
+ * counts equal the reference's, scores >= its and equal wherever it did not skip).
+ * Ten or more optional clauses present in the leaf are served as well (unlike a REQUIRED disjunction of ten, see
+ * RGPU_OP_SHOULD_REQUIRED): the reference's DisjunctionSumScorer sums that many in heap order (disjunction_scorer.rs:41-45) and so
+ * pins the optional sum no tighter than 1e-5 relative; here it stays the f32 sum in clause order. Hit counts and the rule's skip
+ * decisions - they look at the MUST score alone - are exact; doc ids and scores hold under the rule of the >= 10-clause disjunctions
+ * (rgpu_search_batch: within 1e-5 relative, docs exchanged only among scores that tie within it). With nine or fewer optional
+ * clauses present - whatever the number named - scores are bit-equal (tests/test_gpu_opt_spectrum.py). */
 #define RGPU_OP_WITH_SHOULD(op, n_should) ((int32_t)(op) | ((int32_t)(n_should) << 16))
 /* RGPU_OP_SHOULD_REQUIRED on top of RGPU_OP_WITH_SHOULD: the n SHOULD clauses are a MUST clause of their own — the tree
  * "+a +(b c)", a should-only BooleanQuery (min_should_match <= 1) nested under MUST, which BooleanWeight::create_scorer turns into

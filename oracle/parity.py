@@ -26,6 +26,30 @@ def check_heap_order_row(osearcher, op, term_ids, got_docs, got_scores, got_tota
                          rtol=1e-5, min_should_match=0, what=""):
     """One query's row against the oracle's (canonical mode). `got_*`: the k-row under test, unused slots doc -1;
     `want_*`: the oracle's row, `want_n` slots filled. Returns docs_differing; raises HeapOrderParityError."""
+    return _check_row(lambda gd: osearcher.score_docs(op, term_ids, gd, min_should_match=min_should_match), got_docs, got_scores, got_total,
+                      want_docs, want_scores, want_n, want_total, rtol, what)
+
+
+def check_heap_order_opt_row(full_docs, full_scores, got_docs, got_scores, got_total, k, rtol=1e-5, what=""):
+    """The same rule for a MUST + SHOULD row (ReqOptScorer) whose ten or more optional clauses the reference sums in heap order.
+    ReqOptScorer's skipping rule runs from doc to doc, so the oracle's score of one doc cannot be asked for on its own: `full_*` is
+    the oracle's COMPLETE canonical row (search_opt with k >= total_hits), every match with the score the rule gave it. A doc the
+    rule decided otherwise for misses its score by a whole optional sum and fails 3. Returns docs_differing."""
+    full_docs, full_scores = np.asarray(full_docs), np.asarray(full_scores, dtype=np.float32)
+    order = np.argsort(full_docs, kind="stable")
+    by_doc, by_doc_scores = full_docs[order], full_scores[order]
+
+    def score_of(gd):
+        at = np.minimum(np.searchsorted(by_doc, gd), max(by_doc.size - 1, 0))
+        matched = (by_doc[at] == gd) if by_doc.size else np.zeros(gd.size, bool)
+        return np.where(matched, by_doc_scores[at] if by_doc.size else 0.0, 0.0).astype(np.float32), matched
+
+    n = min(int(k), int(full_docs.size))
+    return _check_row(score_of, got_docs, got_scores, got_total, full_docs[:n], full_scores[:n], n, int(full_docs.size), rtol, what)
+
+
+def _check_row(score_of, got_docs, got_scores, got_total, want_docs, want_scores, want_n, want_total, rtol, what):
+    """Rules 1 to 5. score_of(docs) -> (the oracle's score of each, whether it matches)."""
     def fail(msg):
         raise HeapOrderParityError("%s: %s" % (what, msg))
 
@@ -49,7 +73,7 @@ def check_heap_order_row(osearcher, op, term_ids, got_docs, got_scores, got_tota
     if (np.diff(gd)[ds == 0] <= 0).any():
         fail("equal scores not in ascending doc order")
     # 3. the oracle's score of the returned docs
-    os_, matched = osearcher.score_docs(op, term_ids, gd, min_should_match=min_should_match)
+    os_, matched = score_of(gd)
     if not matched.all():
         fail("returned docs that do not match the query: %s" % gd[~matched].tolist())
     bad = np.abs(os_.astype(np.float64) - gs.astype(np.float64)) > rtol * np.abs(os_.astype(np.float64))
