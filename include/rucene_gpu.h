@@ -896,7 +896,8 @@ int32_t rgpu_search_span_unordered_batch(rgpu_segment* seg, const rgpu_phrase_qu
  * term it lacks excludes nothing.
  * NOT served (the caller keeps these on its CPU path): sloppy phrase clauses (slop > 0 -> RGPU_ERR_UNSUPPORTED: as a child of a
  * conjunction the reference's SloppyPhraseScorer matches on its approximation and scores a stale sloppy_freq, which is not
- * reproduced); phrase clauses under SHOULD or MUST_NOT; SHOULD clauses of any kind beside a required phrase (ReqOptScorer); nested
+ * reproduced); phrase clauses under SHOULD or MUST_NOT; SHOULD clauses of any kind beside a required phrase (ReqOptScorer:
+ * rgpu_search_phrase_opt_batch, below, serves that tree); nested
  * BooleanQuery clauses beside a phrase; more than RGPU_MAX_BOOL_PHRASES phrases — none of them can be written in this struct. */
 #define RGPU_MAX_BOOL_PHRASES 4
 typedef struct rgpu_phrase_bool_query {
@@ -964,7 +965,61 @@ int32_t rgpu_search_phrase_or_batch(rgpu_segment* seg, const rgpu_phrase_or_quer
                                     const rgpu_query_term* terms, int32_t n_terms_total,
                                     int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out);
 
-/* The three exact-phrase calls above restricted to a doc set (rgpu_docset_*, above): "a b" #F -X, +"a b" +c #F -X, "a b" c -X with
+/* BooleanQuery of MUST / FILTER clauses beside SHOULD clauses, with exact PhraseQuery clauses on either side: +new +york "new york"
+ * (the phrase boost), +"new york" pizza delivery, +"new york" +city "big apple" pizza -jersey #lang:en.
+ * BooleanWeight::create_scorer (boolean_query.rs:196-279) builds ReqOptScorer(must, DisjunctionSumScorer(should, needs_scores, msm)),
+ * inside a ReqNotScorer when MUST_NOT clauses exist in the leaf. `must` is the single required scorer or a ConjunctionScorer over
+ * must_weights - the MUST clauses in query order, then the FILTER clauses - stable-sorted by cost and summed in that order, the first
+ * addend as it is and the rest += (conjunction_scorer.rs:27-42, 87-95); an ExactPhraseScorer is not two-phase and costs its rarest
+ * term's doc_freq. Below ten children the disjunction is the SimpleQueue arm: 0.0f, then += each child on the doc, in clause order
+ * (disjunction_scorer.rs:211-225). ReqOptScorer::score (req_opt_scorer.rs:41-66) carries scores_sum / scores_num from collected doc
+ * to collected doc and skips the optional side once more than 100 docs took it and 2 * req < mean.
+ * Served, per leaf: at least one required clause (term or phrase) and 1..9 optional clauses in all, up to RGPU_MAX_BOOL_PHRASES
+ * exact phrases on each side, at any positions; a query with no phrase at all is accepted too (the tree RGPU_OP_WITH_SHOULD serves).
+ * A required clause absent from the leaf: the query matches nothing there. An optional clause absent from the leaf (a term of
+ * doc_freq 0, a phrase that lacks a term) drops out; with every optional clause absent there is no ReqOptScorer and the row is the
+ * required scorer's. A doc is a hit iff every required clause holds it, no MUST_NOT term present in the leaf holds it, and it is
+ * live; total_hits counts those docs. `req` is the conjunction's sum in the leaf's stable cost order (or the single required
+ * scorer's own score), `opt` is 0.0f + s_i ... over the present optional clauses that hold the doc, in clause order, and the final
+ * score follows req_opt_scorer.rs:41-66 with its state moved only by collected docs: dead docs, docs a MUST_NOT clause holds and
+ * skipped docs leave it alone, and it starts afresh in every leaf. rgpu_config.req_opt_rule = -1 adds `opt` everywhere, as for
+ * RGPU_OP_WITH_SHOULD. A FILTER-only required side scores 0.0 and never trips the rule (0 < 0). A doc no optional clause holds
+ * scores req + 0.0f where the reference returns req itself: the masked calls' documented deviation, a -0.0 becomes +0.0 (BM25
+ * scores are never -0.0). min_should_match is accepted and without effect: ReqOptScorer only advance()s the optional scorer.
+ * k up to RGPU_MAX_K; next_limit is ignored.
+ * NOT served (RGPU_ERR_UNSUPPORTED, the caller keeps these on its CPU path): any slop > 0; ten or more optional clauses; more than
+ * RGPU_MAX_BOOL_PHRASES phrases on either side; more than RGPU_MAX_QUERY_TERMS distinct terms; a doc holding a phrase term more
+ * than 1024 times; k > RGPU_MAX_K. Nested clauses and a phrase under MUST_NOT cannot be written in this struct.
+ * There is no masked, sharded, planner, count or rescore form of this call. */
+typedef struct rgpu_phrase_opt_query {
+  int32_t n_req_phrases;      /* 0..RGPU_MAX_BOOL_PHRASES required exact phrases (MUST, or FILTER: weight 0) */
+  int32_t n_opt_phrases;      /* 0..RGPU_MAX_BOOL_PHRASES optional (SHOULD) exact phrases */
+  int32_t first_phrase;       /* in `phrases`: the required ones, then the optional ones */
+  int32_t n_req_terms;        /* required term clauses: MUST in query order, then FILTER with weight 0 */
+  int32_t n_opt_terms;        /* SHOULD term clauses in query order */
+  int32_t first_term;         /* in `terms`: required, then optional, then the n_must_not MUST_NOT clauses */
+  int32_t n_must_not;
+  int32_t min_should_match;   /* 0..255, accepted and without effect: ReqOptScorer only advance()s the optional scorer */
+  int32_t req_phrase_slot[RGPU_MAX_BOOL_PHRASES]; /* position in must_weights, as rgpu_phrase_bool_query.phrase_slot */
+  int32_t opt_phrase_slot[RGPU_MAX_BOOL_PHRASES]; /* position in should_weights, as rgpu_phrase_or_query.phrase_slot */
+} rgpu_phrase_opt_query;      /* 64 bytes */
+/* One leaf of IndexSearcher::search(BooleanQuery of required and optional clauses over phrases and terms, TopDocsCollector(k)).
+ * `phrases` / `phrase_terms` as the queries / terms of rgpu_search_phrase_batch (both may be null when no query names a phrase),
+ * `terms` as those of rgpu_search_batch. Outputs and calling protocol as rgpu_search_batch; docs, scores and total_hits are
+ * bit-exact with the CPU scorers.
+ * Refused, nothing launched or written: no required clause, or no optional clause; a phrase slot out of range or named twice;
+ * index ranges outside the arrays or negative counts; min_should_match outside 0..255; an unknown sim_table; whatever else
+ * rgpu_search_phrase_batch refuses (RGPU_ERR_ILLEGAL_ARGUMENT); no positions attached while a phrase is named
+ * (RGPU_ERR_ILLEGAL_STATE); the shapes listed above as not served (RGPU_ERR_UNSUPPORTED - a doc that holds a phrase term more than
+ * 1024 times is found by the match kernels: nothing is written then either). */
+int32_t rgpu_search_phrase_opt_batch(rgpu_segment* seg, const rgpu_phrase_opt_query* queries, int32_t n_queries,
+                                     const rgpu_phrase_query* phrases, int32_t n_phrases_total,
+                                     const rgpu_phrase_term* phrase_terms, int32_t n_phrase_terms_total,
+                                     const rgpu_query_term* terms, int32_t n_terms_total,
+                                     int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out);
+
+/* rgpu_search_phrase_batch, _phrase_bool_batch and _phrase_or_batch restricted to a doc set (rgpu_docset_*, above; rgpu_search_phrase_opt_batch
+ * has no such form): "a b" #F -X, +"a b" +c #F -X, "a b" c -X with
  * the filters combined into `set`. Bit for bit the rows and totals the unmasked call returns on a segment uploaded with live_docs =
  * live AND set: no scorer of an exact phrase is two-phase, so a doc outside the mask is a deleted doc and nothing else. The rules
  * are rgpu_search_batch_masked's: the set belongs to `seg` (RGPU_ERR_ILLEGAL_ARGUMENT otherwise), live AND set is formed once and

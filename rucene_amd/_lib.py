@@ -45,6 +45,10 @@ PHRASE_OR_QUERY_DTYPE = np.dtype([("n_phrases", "<i4"), ("first_phrase", "<i4"),
                                   ("min_should_match", "<i4"), ("phrase_slot", "<i4", (MAX_BOOL_PHRASES,)), ("reserved", "<i4", (2,))], align=True)
 assert PHRASE_OR_QUERY_DTYPE.itemsize == 48
 PHRASE_OR_MAX_SHOULD = 9   # ten or more SHOULD clauses sum in heap order (disjunction_scorer.rs:41-45)
+PHRASE_OPT_QUERY_DTYPE = np.dtype([("n_req_phrases", "<i4"), ("n_opt_phrases", "<i4"), ("first_phrase", "<i4"), ("n_req_terms", "<i4"), ("n_opt_terms", "<i4"),
+                                   ("first_term", "<i4"), ("n_must_not", "<i4"), ("min_should_match", "<i4"), ("req_phrase_slot", "<i4", (MAX_BOOL_PHRASES,)),
+                                   ("opt_phrase_slot", "<i4", (MAX_BOOL_PHRASES,))], align=True)
+assert PHRASE_OPT_QUERY_DTYPE.itemsize == 64
 FIELD_INFO_DTYPE = np.dtype([("number", "<i4"), ("index_options", "<i4"), ("has_payloads", "<i4"), ("flags", "<i4")], align=True)
 # rgpu_search_fields_batch: clauses that say which field of the segment their term lives in, groups of them, queries of groups
 MAX_FIELDS = 8                    # RGPU_MAX_FIELDS: field 0 (the upload's) + attached slots 1..7
@@ -81,7 +85,7 @@ STATUS_NAMES = {0: "OK", -1: "IllegalState", -2: "IllegalArgument", -3: "Unexpec
 # every symbol include/rucene_gpu.h declares (tests/test_abi.py checks the header and this list agree)
 EXPORTS = [
     "rgpu_init", "rgpu_shutdown", "rgpu_last_error", "rgpu_abi_version", "rgpu_device_name", "rgpu_segment_upload",
-    "rgpu_segment_upload_field", "rgpu_segment_release_prepared_terms", "rgpu_segment_get_footprint", "rgpu_segment_attach_positions", "rgpu_segment_attach_payloads", "rgpu_decode_positions", "rgpu_decode_positions_device", "rgpu_search_phrase_batch", "rgpu_search_phrase_bool_batch", "rgpu_search_phrase_or_batch", "rgpu_rescore_batch", "rgpu_rescore_phrase_batch",
+    "rgpu_segment_upload_field", "rgpu_segment_release_prepared_terms", "rgpu_segment_get_footprint", "rgpu_segment_attach_positions", "rgpu_segment_attach_payloads", "rgpu_decode_positions", "rgpu_decode_positions_device", "rgpu_search_phrase_batch", "rgpu_search_phrase_bool_batch", "rgpu_search_phrase_or_batch", "rgpu_search_phrase_opt_batch", "rgpu_rescore_batch", "rgpu_rescore_phrase_batch",
     "rgpu_segment_free", "rgpu_segment_version", "rgpu_segment_prepare_terms", "rgpu_decode_terms",
     "rgpu_decode_terms_device", "rgpu_advance_batch", "rgpu_sim_table_upload", "rgpu_search_batch",
     "rgpu_search_batch_device", "rgpu_merge_topk_device", "rgpu_bm25_compute_weight", "rgpu_bm25_encode_norm", "rgpu_bm25_term_weights",
@@ -194,6 +198,7 @@ def lib():
         "rgpu_search_span_unordered_batch": (i32, [vp, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_phrase_bool_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_phrase_or_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
+        "rgpu_search_phrase_opt_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_rescore_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32]),
         "rgpu_rescore_phrase_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32]),
         "rgpu_decode_terms": (i32, [vp, vp, i64, vp, vp]),
@@ -887,6 +892,24 @@ class Segment:
         totals = np.zeros(q.size, dtype=np.int64)
         _check(lib().rgpu_search_phrase_or_batch(self._h, q.ctypes.data, q.size, p.ctypes.data, p.size, pt.ctypes.data, pt.size,
                                                  t.ctypes.data if t.size else None, t.size, k, hits.ctypes.data, totals.ctypes.data))
+        return hits, totals
+
+    def search_phrase_opt_batch(self, queries, phrases, phrase_terms, terms, k, hits=None, totals=None):
+        """BooleanQuery rows of required and optional clauses with exact phrases on either side (rgpu_search_phrase_opt_batch):
+        `queries` PHRASE_OPT_QUERY_DTYPE, `phrases` / `phrase_terms` as for search_phrase_batch (both may be empty), `terms`
+        QUERY_TERM_DTYPE (may be empty). A refusal raises and returns nothing; `hits` / `totals`: the caller's own output arrays
+        (a refused call leaves them as they were)."""
+        q = np.ascontiguousarray(queries, dtype=PHRASE_OPT_QUERY_DTYPE)
+        p = np.ascontiguousarray(phrases, dtype=PHRASE_QUERY_DTYPE)
+        pt = np.ascontiguousarray(phrase_terms, dtype=PHRASE_TERM_DTYPE)
+        t = np.ascontiguousarray(terms, dtype=QUERY_TERM_DTYPE)
+        if hits is None:
+            hits = np.zeros((q.size, max(k, 0)), dtype=HIT_DTYPE)
+        if totals is None:
+            totals = np.zeros(q.size, dtype=np.int64)
+        _check(lib().rgpu_search_phrase_opt_batch(self._h, q.ctypes.data if q.size else None, q.size, p.ctypes.data if p.size else None, p.size,
+                                                  pt.ctypes.data if pt.size else None, pt.size, t.ctypes.data if t.size else None, t.size, k,
+                                                  hits.ctypes.data, totals.ctypes.data))
         return hits, totals
 
     def search_phrase_batch_masked(self, docset, queries, terms, k):

@@ -513,6 +513,57 @@ struct PhraseDisjunctionQuery : Query {
   }
 };
 
+// BooleanQuery of required (MUST / FILTER) AND optional (SHOULD) clauses with exact PhraseQuery clauses on either side: +a +b "a b",
+// +"a b" c, +"a b" +c "b c" d -n #f (rgpu_search_phrase_opt_batch): ReqOptScorer(must, DisjunctionSumScorer(should)), its sequential
+// rule kept. `required`: BooleanWeight::must_weights — the MUST clauses in query order, then the FILTER clauses (they score 0);
+// `should_queries`: should_weights, the SHOULD clauses in query order; a clause is a phrase or a term. Served only by a searcher
+// with GpuIndexSearcher::optional_phrases = true (off by default: UnsupportedOperation, as such trees have been). Only the shapes
+// the call can express can be written here (no nested BooleanQuery, no phrase under MUST_NOT); a sloppy phrase clause, more than
+// RGPU_MAX_BOOL_PHRASES phrases on a side, ten or more SHOULD clauses or a side without a clause are UnsupportedOperation when the query
+// is searched — the caller's CPU path. min_should_match is carried and without effect (ReqOptScorer only advances the optional scorer).
+struct PhraseOptionalQuery : Query {
+  struct Clause {
+    std::shared_ptr<PhraseQuery> phrase;  // null: a term clause
+    TermQuery term{int64_t(-1)};
+    bool filter = false;
+  };
+  std::vector<Clause> required;
+  std::vector<Clause> should_queries;
+  std::vector<TermQuery> must_not_queries;
+  int32_t min_should_match = 0;
+  PhraseOptionalQuery& must(PhraseQuery p) { return add(Clause{std::make_shared<PhraseQuery>(std::move(p)), TermQuery(int64_t(-1)), false}); }
+  PhraseOptionalQuery& must(TermQuery t) { return add(Clause{nullptr, std::move(t), false}); }
+  PhraseOptionalQuery& filter(PhraseQuery p) { return add(Clause{std::make_shared<PhraseQuery>(std::move(p)), TermQuery(int64_t(-1)), true}); }
+  PhraseOptionalQuery& filter(TermQuery t) { return add(Clause{nullptr, std::move(t), true}); }
+  PhraseOptionalQuery& should(PhraseQuery p) { should_queries.push_back(Clause{std::make_shared<PhraseQuery>(std::move(p)), TermQuery(int64_t(-1)), false}); return *this; }
+  PhraseOptionalQuery& should(TermQuery t) { should_queries.push_back(Clause{nullptr, std::move(t), false}); return *this; }
+  PhraseOptionalQuery& must_not(TermQuery t) { must_not_queries.push_back(std::move(t)); return *this; }
+  PhraseOptionalQuery& min_should(int32_t n) { min_should_match = n; return *this; }
+  // refused before any leaf is touched
+  void check_served() const {
+    if (required.empty() || should_queries.empty()) throw Error(RGPU_ERR_UNSUPPORTED, "a MUST + SHOULD tree has a required and an optional clause");
+    for (const std::vector<Clause>* side : {&required, &should_queries}) {
+      int n_phrases = 0;
+      for (const Clause& c : *side) {
+        if (!c.phrase) continue;
+        ++n_phrases;
+        if (c.phrase->slop > 0) throw Error(RGPU_ERR_UNSUPPORTED, "a sloppy phrase inside a boolean query is not served by the GPU path");
+      }
+      if (n_phrases > RGPU_MAX_BOOL_PHRASES) throw Error(RGPU_ERR_UNSUPPORTED, "more than RGPU_MAX_BOOL_PHRASES phrases on one side of a boolean query");
+    }
+    if (should_queries.size() > 9) throw Error(RGPU_ERR_UNSUPPORTED, "ten or more SHOULD clauses sum in heap order");
+    if (min_should_match < 0 || min_should_match > 255) throw Error(RGPU_ERR_UNSUPPORTED, "min_should_match outside 0..255");
+  }
+
+ private:
+  PhraseOptionalQuery& add(Clause c) {  // (FILTER clauses stand behind the MUST clauses in must_weights)
+    auto at = required.end();
+    if (!c.filter) at = std::find_if(required.begin(), required.end(), [](const Clause& x) { return x.filter; });
+    required.insert(at, std::move(c));
+    return *this;
+  }
+};
+
 // RescoreRequest (search/scorer/rescorer.rs:67-116): how a second query's score is folded into the first pass's
 // A filter that is not a term, as the query cache holds it (search/cache/query_cache.rs:301-372): a handle to one doc set per leaf,
 // owned by the GpuIndexSearcher that made it (cache_filter / filter_from_docs / filter_from_bits) until drop_filter or its end.
@@ -942,6 +993,11 @@ class GpuIndexSearcher {
   // (NearSpansUnordered, the heap's array order kept) instead of being UnsupportedOperation. Refused either way: nested span clauses,
   // a span query under a FilteredQuery or in a rescore request.
   bool unordered_spans = false;
+  // A PhraseOptionalQuery - MUST / FILTER + SHOULD clauses with exact phrases on either side: +a +b "a b", +"a b" c - goes through
+  // rgpu_search_phrase_opt_batch (ReqOptScorer over the phrase scorers, its sequential rule kept) instead of being
+  // UnsupportedOperation. Refused either way: what PhraseOptionalQuery::check_served refuses, and such a row under a FilteredQuery
+  // (the call has no masked form).
+  bool optional_phrases = false;
   std::function<void(const Query&, TopDocsCollector&)> cpu_fallback;
 
   // ---- cached filters: doc sets in HBM as FILTER / MUST_NOT masks (include/rucene_gpu.h rgpu_docset_*) ---------------------------
@@ -1167,15 +1223,21 @@ class GpuIndexSearcher {
     }
     for (const Query* q : queries)
       if (dynamic_cast<const FilteredQuery*>(q) || dynamic_cast<const MatchAllDocsQuery*>(q)) return search_filtered(queries, k);
-    std::vector<size_t> phrase_rows, bool_rows, or_rows, span_rows, plain_rows;
+    std::vector<size_t> phrase_rows, bool_rows, or_rows, opt_rows, span_rows, plain_rows;
+    for (const Query* q : queries)  // refused before any leaf is touched
+      if (const PhraseOptionalQuery* po = dynamic_cast<const PhraseOptionalQuery*>(q)) {
+        if (!optional_phrases) throw Error(RGPU_ERR_UNSUPPORTED, "SHOULD clauses beside a required clause of a boolean query over phrases are not served by the GPU path (optional_phrases)");
+        po->check_served();
+      }
     for (size_t i = 0; i < queries.size(); ++i) {
-      if (dynamic_cast<const SpanNearQuery*>(queries[i])) span_rows.push_back(i);
+      if (dynamic_cast<const PhraseOptionalQuery*>(queries[i])) opt_rows.push_back(i);
+      else if (dynamic_cast<const SpanNearQuery*>(queries[i])) span_rows.push_back(i);
       else if (dynamic_cast<const PhraseQuery*>(queries[i])) phrase_rows.push_back(i);
       else if (dynamic_cast<const PhraseBooleanQuery*>(queries[i])) bool_rows.push_back(i);
       else if (dynamic_cast<const PhraseDisjunctionQuery*>(queries[i])) or_rows.push_back(i);
       else plain_rows.push_back(i);
     }
-    if (!phrase_rows.empty() || !bool_rows.empty() || !or_rows.empty() || !span_rows.empty()) {
+    if (!phrase_rows.empty() || !bool_rows.empty() || !or_rows.empty() || !opt_rows.empty() || !span_rows.empty()) {
       std::vector<TopDocs> out(queries.size());
       auto place = [&](const std::vector<size_t>& rows, std::vector<TopDocs> got) { for (size_t i = 0; i < rows.size(); ++i) out[rows[i]] = std::move(got[i]); };
       std::vector<const PhraseBooleanQuery*> bools;
@@ -1194,6 +1256,11 @@ class GpuIndexSearcher {
       }
       if (!bools.empty()) place(bool_rows, search_phrase_bools(bools, k));
       if (!ors.empty()) place(or_rows, search_phrase_ors(ors, k));
+      if (!opt_rows.empty()) {
+        std::vector<const PhraseOptionalQuery*> opts;
+        for (size_t i : opt_rows) opts.push_back(static_cast<const PhraseOptionalQuery*>(queries[i]));
+        place(opt_rows, search_phrase_opts(opts, k));
+      }
       if (!span_rows.empty()) {  // ordered rows: rgpu_search_span_near_batch; unordered ones (unordered_spans): rgpu_search_span_unordered_batch
         for (const bool in_order : {true, false}) {
           std::vector<size_t> rows;
@@ -1452,6 +1519,76 @@ class GpuIndexSearcher {
         check(rgpu_search_phrase_or_batch(leaf.segment, qs.data(), nq, ps.data(), static_cast<int32_t>(ps.size()), pts.data(), static_cast<int32_t>(pts.size()),
                                           ts.empty() ? nullptr : ts.data(), static_cast<int32_t>(ts.size()), static_cast<int32_t>(k),
                                           leaf_hits[li].data(), leaf_totals[li].data()));
+    }
+    return merge_leaves(leaf_hits, leaf_totals, nq, k);
+  }
+
+  // IndexSearcher::search(BooleanQuery of required and optional clauses over phrases and terms, TopDocsCollector(k)) for a batch:
+  // rgpu_search_phrase_opt_batch per leaf (optional_phrases). A FILTER clause rides with weight 0; req_phrase_slot[i] / opt_phrase_slot[i]
+  // = the phrase's index in `required` / `should_queries`; the phrases stand required first, then optional, the terms required,
+  // optional, MUST_NOT. A leaf without positions is served while no query of the batch names a phrase.
+  std::vector<TopDocs> search_phrase_opts(const std::vector<const PhraseOptionalQuery*>& queries, size_t k) {
+    if (!optional_phrases) throw Error(RGPU_ERR_UNSUPPORTED, "a MUST + SHOULD tree over phrases is not served by the GPU path (optional_phrases)");
+    for (const auto* q : queries) refuse_other_fields(*q);  // (these paths read the primary field's postings, idf and sim table)
+    const int32_t nq = static_cast<int32_t>(queries.size());
+    for (const PhraseOptionalQuery* q : queries) q->check_served();
+    std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
+    std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
+    for (size_t li = 0; li < leaves_.size(); ++li) {
+      const LeafReader& leaf = leaves_[li];
+      std::vector<rgpu_phrase_opt_query> qs;
+      std::vector<const PhraseQuery*> phrases;
+      std::vector<bool> filtered;
+      std::vector<rgpu_query_term> ts;
+      auto term_clause = [&](const TermQuery& c, bool scoring) {
+        rgpu_query_term qt{};
+        if (!leaf.term_state(c, &qt.state)) { qt.state = rgpu_term_state{}; qt.state.skip_offset = -1; qt.state.singleton_doc_id = -1; }
+        auto w = weight_of(c);
+        qt.weight = scoring ? w.first : 0.0f;
+        qt.sim_table = w.second;
+        ts.push_back(qt);
+      };
+      for (const PhraseOptionalQuery* q : queries) {
+        rgpu_phrase_opt_query oq{};
+        oq.first_phrase = static_cast<int32_t>(phrases.size());
+        oq.first_term = static_cast<int32_t>(ts.size());
+        oq.min_should_match = q->min_should_match;
+        for (size_t s = 0; s < q->required.size(); ++s) {
+          const PhraseOptionalQuery::Clause& c = q->required[s];
+          if (c.phrase) {
+            oq.req_phrase_slot[oq.n_req_phrases++] = static_cast<int32_t>(s);
+            phrases.push_back(c.phrase.get());
+            filtered.push_back(c.filter);
+          } else {
+            term_clause(c.term, !c.filter);
+            oq.n_req_terms++;
+          }
+        }
+        for (size_t s = 0; s < q->should_queries.size(); ++s) {
+          const PhraseOptionalQuery::Clause& c = q->should_queries[s];
+          if (c.phrase) {
+            oq.opt_phrase_slot[oq.n_opt_phrases++] = static_cast<int32_t>(s);
+            phrases.push_back(c.phrase.get());
+            filtered.push_back(false);
+          } else {
+            term_clause(c.term, true);
+            oq.n_opt_terms++;
+          }
+        }
+        for (const TermQuery& c : q->must_not_queries) term_clause(c, false);
+        oq.n_must_not = static_cast<int32_t>(q->must_not_queries.size());
+        qs.push_back(oq);
+      }
+      if (!phrases.empty() && !leaf.pos_bytes) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "phrase search needs a positions field (LeafReader::pos_bytes)");
+      std::vector<rgpu_phrase_query> ps;
+      std::vector<rgpu_phrase_term> pts;
+      if (!phrases.empty()) pack_phrases(phrases, leaf, &ps, &pts);
+      for (size_t i = 0; i < ps.size(); ++i) { if (filtered[i]) ps[i].weight = 0.0f; ps[i].next_limit = 0; }
+      leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
+      leaf_totals[li].assign(static_cast<size_t>(nq), 0);
+      check(rgpu_search_phrase_opt_batch(leaf.segment, qs.data(), nq, ps.empty() ? nullptr : ps.data(), static_cast<int32_t>(ps.size()),
+                                         pts.empty() ? nullptr : pts.data(), static_cast<int32_t>(pts.size()), ts.empty() ? nullptr : ts.data(),
+                                         static_cast<int32_t>(ts.size()), static_cast<int32_t>(k), leaf_hits[li].data(), leaf_totals[li].data()));
     }
     return merge_leaves(leaf_hits, leaf_totals, nq, k);
   }
@@ -1763,6 +1900,12 @@ class GpuIndexSearcher {
       for (const PhraseDisjunctionQuery::Should& c : pd->should_queries)
         if (c.phrase ? any_other_field(c.phrase->terms) : !primary(c.term)) return true;
       return any_other_field(pd->must_not_queries);
+    }
+    if (auto* po = dynamic_cast<const PhraseOptionalQuery*>(&q)) {
+      for (const auto* side : {&po->required, &po->should_queries})
+        for (const PhraseOptionalQuery::Clause& c : *side)
+          if (c.phrase ? any_other_field(c.phrase->terms) : !primary(c.term)) return true;
+      return any_other_field(po->must_not_queries);
     }
     if (auto* fq = dynamic_cast<const FilteredQuery*>(&q)) return fq->query && names_other_field(*fq->query);
     if (auto* nb = dynamic_cast<const NestedBooleanQuery*>(&q)) {

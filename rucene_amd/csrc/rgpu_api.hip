@@ -53,6 +53,8 @@
 #include "host/points_plan.hpp"
 #include "kernels/search_fields.hpp"
 #include "host/fields_plan.hpp"
+#include "kernels/search_phrase_opt.hpp"
+#include "host/phrase_opt_plan.hpp"
 
 using namespace rgpu;
 
@@ -3600,6 +3602,7 @@ extern "C" int32_t rgpu_search_batch_device(rgpu_segment* seg, const rgpu_query*
 #include "api/phrase_search.hpp"   // rgpu_search_phrase_batch / _masked, rgpu_search_span_near_batch, rgpu_search_span_unordered_batch
 #include "api/phrase_bool.hpp"     // rgpu_search_phrase_bool_batch / _masked
 #include "api/phrase_or.hpp"       // rgpu_search_phrase_or_batch / _masked
+#include "api/phrase_opt.hpp"      // rgpu_search_phrase_opt_batch
 #include "api/rescore.hpp"         // rgpu_rescore_batch, rgpu_rescore_phrase_batch
 #include "api/sharded.hpp"         // rgpu_comm_*, records, rgpu_search_batch_record_device, rgpu_merge_records_device, rgpu_search_batch_sharded*
 #include "api/host_formats.hpp"    // rgpu_bm25_*, norms, live docs, rgpu_terms_*, segment / commit / compound / field infos

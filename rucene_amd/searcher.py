@@ -824,8 +824,13 @@ class GpuIndexSearcher:
     range_filter_capacity = 256   # memoised range filters kept from one search_batch to the next (range_filter); set per searcher
 
     def __init__(self, leaves, ctx=None, similarity=None, next_limit=None, flatten_nested=False, cpu_fallback=None, filtered_phrases=False,
-                 required_sets=False, unordered_spans=False):
-        """unordered_spans: serve a top-level SpanNearQuery(in_order=False) over SpanTermQuery clauses through
+                 required_sets=False, unordered_spans=False, optional_phrases=False):
+        """optional_phrases: serve MUST / FILTER + SHOULD trees with exact phrases on either side - +a +b "a b" (the phrase boost),
+        +"a b" c, +"a b" +c "b c" d -n #f - through rgpu_search_phrase_opt_batch (ReqOptScorer over the phrase scorers, its
+        sequential rule kept; off by default: such rows are UnsupportedOperation, as they have been). Still refused with it on:
+        whatever phrase_opt_parts refuses (nested clauses beside a phrase, a phrase under MUST_NOT, sloppy clauses, ten or more
+        optional clauses, more than 4 phrases on a side) and such a row beside doc-set clauses (the call has no masked form).
+        unordered_spans: serve a top-level SpanNearQuery(in_order=False) over SpanTermQuery clauses through
         rgpu_search_span_unordered_batch (NearSpansUnordered, the heap's array order kept; off by default: such rows are
         UnsupportedOperation, as they have been). Still refused with it on: nested span clauses, a span query inside a boolean,
         filtered, dismax, boosting or rescoring query.
@@ -848,6 +853,7 @@ class GpuIndexSearcher:
         self.filtered_phrases = bool(filtered_phrases)
         self.required_sets = bool(required_sets)
         self.unordered_spans = bool(unordered_spans)
+        self.optional_phrases = bool(optional_phrases)
         self.cpu_fallback = cpu_fallback
         self.leaves = list(leaves)
         # DefaultIndexSearcher::new(reader, next_limit: Option<usize>) (searcher.rs:291-296, :361): how many approximations of a
@@ -1391,6 +1397,57 @@ class GpuIndexSearcher:
         ps["next_limit"] = 0
         return qs, ps, pts, self._pack_term_clauses(term_cs, leaf)
 
+    @staticmethod
+    def phrase_opt_parts(query):
+        """A BooleanQuery with required (MUST / FILTER) AND SHOULD clauses and a PhraseQuery among them -> (required clauses in
+        BooleanWeight::must_weights order: MUST clauses in query order, then FILTER clauses; how many of them are MUST clauses; SHOULD
+        clauses in query order, i.e. should_weights; MUST_NOT TermQuery clauses; min_should_match) when the GPU path serves the tree
+        (rgpu_search_phrase_opt_batch), else UnsupportedOperation: no required or no SHOULD clause (phrase_or_parts /
+        phrase_bool_parts), a sloppy phrase clause, a phrase under MUST_NOT, a nested BooleanQuery clause, more than 4 phrases on
+        either side, ten or more SHOULD clauses (the reference then sums in heap order)."""
+        required = list(query.must_queries) + list(query.filter_queries)
+        shoulds = list(query.should_queries)
+        if not required or not shoulds:
+            raise RgpuError(-5, "phrase_opt_parts: a MUST + SHOULD tree has a required and an optional clause")
+        if any(isinstance(q, PhraseQuery) for q in query.must_not_queries):
+            raise RgpuError(-5, "a phrase clause under MUST_NOT is not served by the GPU path")
+        if any(not isinstance(q, (PhraseQuery, TermQuery)) for q in required + shoulds + list(query.must_not_queries)):
+            raise RgpuError(-5, "nested boolean clauses beside a phrase are not served by the GPU path")
+        if any(q.slop > 0 for q in required + shoulds if isinstance(q, PhraseQuery)):
+            raise RgpuError(-5, "a sloppy phrase inside a boolean query is not served by the GPU path")
+        for side in (required, shoulds):
+            if sum(isinstance(q, PhraseQuery) for q in side) > _lib.MAX_BOOL_PHRASES:
+                raise RgpuError(-5, "more than %d phrases on one side of a boolean query" % _lib.MAX_BOOL_PHRASES)
+        if len(shoulds) > _lib.PHRASE_OR_MAX_SHOULD:
+            raise RgpuError(-5, "ten or more SHOULD clauses sum in heap order")
+        return required, len(query.must_queries), shoulds, list(query.must_not_queries), query.min_should_match
+
+    def pack_phrase_opt(self, queries, leaf):
+        """BooleanQuery objects of required and optional clauses with phrase clauses -> the (rgpu_phrase_opt_query[],
+        rgpu_phrase_query[], rgpu_phrase_term[], rgpu_query_term[]) of rgpu_search_phrase_opt_batch for one leaf. A FILTER clause
+        rides with weight 0 (needs_scores = false)."""
+        parts = [self.phrase_opt_parts(q) for q in queries]
+        phrase_qs, filtered, term_cs = [], [], []
+        qs = np.zeros(len(queries), dtype=_lib.PHRASE_OPT_QUERY_DTYPE)
+        for i, (required, n_must, shoulds, nots, msm) in enumerate(parts):
+            rslots = [s for s, c in enumerate(required) if isinstance(c, PhraseQuery)]
+            oslots = [s for s, c in enumerate(shoulds) if isinstance(c, PhraseQuery)]
+            rterms = [TermQuery(c.term, c.boost if s < n_must else 0.0) for s, c in enumerate(required) if not isinstance(c, PhraseQuery)]
+            oterms = [c for c in shoulds if not isinstance(c, PhraseQuery)]
+            qs[i]["n_req_phrases"], qs[i]["n_opt_phrases"], qs[i]["first_phrase"] = len(rslots), len(oslots), len(phrase_qs)
+            qs[i]["n_req_terms"], qs[i]["n_opt_terms"], qs[i]["first_term"], qs[i]["n_must_not"] = len(rterms), len(oterms), len(term_cs), len(nots)
+            qs[i]["min_should_match"] = msm
+            qs[i]["req_phrase_slot"][:len(rslots)] = rslots
+            qs[i]["opt_phrase_slot"][:len(oslots)] = oslots
+            phrase_qs += [required[s] for s in rslots] + [shoulds[s] for s in oslots]
+            filtered += [s >= n_must for s in rslots] + [False] * len(oslots)
+            term_cs += rterms + oterms + nots
+        ps, pts = self.pack_phrases(phrase_qs, leaf)
+        if len(filtered):
+            ps["weight"][np.array(filtered, dtype=bool)] = 0.0
+        ps["next_limit"] = 0
+        return qs, ps, pts, self._pack_term_clauses(term_cs, leaf)
+
     # ---- doc sets: cached filters as FILTER / MUST_NOT masks ---------------------------------------------------------------------
     def _cached(self, sets):
         if len(sets) != len(self.leaves):
@@ -1718,6 +1775,8 @@ class GpuIndexSearcher:
             if isinstance(q, SpanNearQuery):
                 return 4 if q.in_order else 5
             if isinstance(q, BooleanQuery) and q.has_phrases():   # no MUST, no FILTER: the disjunction route; else phrase_bool_parts decides
+                if (q.must_queries or q.filter_queries) and q.should_queries and getattr(self, "optional_phrases", False):
+                    return 6   # required AND optional clauses (optional_phrases): phrase_opt_parts decides
                 return 2 if (q.must_queries or q.filter_queries) else 3
             return 0
         if queries and isinstance(queries[0], _RequiredSet):   # (a group holds such rows alone: search_batch)
@@ -1735,12 +1794,16 @@ class GpuIndexSearcher:
                 raise RgpuError(-5, "a filtered span query is not served by the GPU path")
             if 5 in kinds and not getattr(self, "unordered_spans", False):   # (search_batch has refused it already)
                 raise RgpuError(-5, "an unordered SpanNearQuery is not served by the GPU path")
-            rows = [np.flatnonzero(np.array(kinds) == kd) for kd in (0, 1, 2, 3, 4, 5)]
+            if masks is not None and 6 in kinds:
+                raise RgpuError(-5, "a filtered MUST + SHOULD tree over phrases is not served by the GPU path")
+            rows = [np.flatnonzero(np.array(kinds) == kd) for kd in (0, 1, 2, 3, 4, 5, 6)]
             groups = [[queries[i] for i in r] for r in rows]
             for q in groups[2]:   # refused before any leaf is touched
                 self.phrase_bool_parts(q)
             for q in groups[3]:
                 self.phrase_or_parts(q)
+            for q in groups[6]:
+                self.phrase_opt_parts(q)
             per_leaf = []
             for i, leaf in enumerate(self.leaves):
                 hits, totals = np.zeros((len(queries), k), dtype=_lib.HIT_DTYPE), np.zeros(len(queries), dtype=np.int64)
@@ -1765,6 +1828,8 @@ class GpuIndexSearcher:
                 if groups[5]:   # unordered SpanNearQuery rows (unordered_spans): packed exactly as the ordered ones
                     qs, ts = self.pack_phrases(groups[5], leaf)
                     hits[rows[5]], totals[rows[5]] = seg.search_span_unordered_batch(qs, ts, k)
+                if groups[6]:   # MUST + SHOULD trees over phrases (optional_phrases)
+                    hits[rows[6]], totals[rows[6]] = seg.search_phrase_opt_batch(*self.pack_phrase_opt(groups[6], leaf), k)
                 per_leaf.append((hits, totals))
         return per_leaf
 

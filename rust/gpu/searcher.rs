@@ -174,6 +174,12 @@ pub struct GpuIndexSearcher<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: De
     /// nested span clauses, SpanOrQuery and SpanGapQuery clauses, a span query inside a boolean, filtered, dismax, boosting or
     /// rescoring query (no tree this shim flattens holds one), and - in this shim - the ordered SpanNearQuery.
     pub unordered_spans: bool,
+    /// try_gpu serves a BooleanQuery with required (MUST / FILTER) AND SHOULD clauses and exact PhraseQuery clauses on either side -
+    /// +a +b "a b", +"a b" c, +"a b" +c "b c" d -n #f - through rgpu_search_phrase_opt_batch (try_phrase_opt: ReqOptScorer over the
+    /// phrase scorers, its sequential rule kept, bit-exact) instead of leaving it to the CPU searcher. Off by default, as
+    /// `optional_phrases` of the Python and C++ mirrors. The CPU's either way: a sloppy clause, a nested clause, a phrase under
+    /// MUST_NOT, ten or more SHOULD clauses, more than RGPU_MAX_BOOL_PHRASES phrases on a side, and such a tree beside doc-set clauses.
+    pub optional_phrases: bool,
 }
 
 unsafe impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: SimilarityProducer<C>> Send for GpuIndexSearcher<C, R, IR, SP> {}
@@ -207,7 +213,7 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             leaves.push(GpuLeaf { seg, has_positions: pos.is_some() });
         }
         let next_limit = match next_limit { None => 0, Some(0) => RGPU_NEXT_LIMIT_ZERO, Some(n) => n.min(i32::max_value() as usize) as i32 };
-        Ok(GpuIndexSearcher { cpu, ctx, field: field.to_string(), leaves, extra_fields: Vec::new(), sim_tables: Mutex::new(HashMap::new()), next_limit, allow_flatten, filtered_phrases: false, required_sets: false, unordered_spans: false })
+        Ok(GpuIndexSearcher { cpu, ctx, field: field.to_string(), leaves, extra_fields: Vec::new(), sim_tables: Mutex::new(HashMap::new()), next_limit, allow_flatten, filtered_phrases: false, required_sets: false, unordered_spans: false, optional_phrases: false })
     }
 
     /// A further indexed field of the same segments (rgpu_segment_attach_field): `norms(leaf)` hands over the field's norms as one
@@ -558,6 +564,7 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             if must.iter().chain(should).chain(filter).chain(must_not).any(|q| q.as_any().downcast_ref::<PhraseQuery>().is_some()) {
                 // no MUST and no FILTER clause: one DisjunctionSumScorer over the SHOULD clauses; else the conjunction's rules decide
                 if must.is_empty() && filter.is_empty() { return self.try_phrase_or(b, None, top, k); }
+                if !should.is_empty() && self.optional_phrases { return self.try_phrase_opt(b, top, k); }
                 return self.try_phrase_bool(b, None, top, k);
             }
         }
@@ -882,6 +889,101 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
                     None => rgpu_search_phrase_or_batch(seg, &oq, 1, pqs.as_ptr(), pqs.len() as i32, pterms.as_ptr(), pterms.len() as i32,
                                                         terms_ptr, terms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total),
                 }
+            }, self.ctx)?;
+            Self::hand_over(top, &hits, total);
+        }
+        Ok(true)
+    }
+
+    /// BooleanQuery with at least one required (MUST / FILTER) clause AND 1..=9 SHOULD clauses, up to RGPU_MAX_BOOL_PHRASES exact
+    /// PhraseQuery clauses on each side beside TermQuery clauses, with MUST_NOT TermQuery clauses: "+a +b \"a b\"", "+\"a b\" c -d #e" ->
+    /// rgpu_search_phrase_opt_batch per leaf (`optional_phrases`). req_phrase_slot / opt_phrase_slot = the phrase's index in
+    /// BooleanWeight::must_weights (MUST clauses in query order, then FILTER clauses, which ride with weight 0) / should_weights; the
+    /// library sums the required side in the leaf's stable cost order, the optional side from 0.0 in clause order over the clauses
+    /// the leaf holds, and applies ReqOptScorer's sequential rule (req_opt_scorer.rs:41-66) per leaf. min_should_match is carried and
+    /// without effect, as in the reference. Ok(false) - the CPU searcher - under try_phrase's rules (another field, a leaf without
+    /// positions, a phrase of the wrong size) and for every shape the library does not serve: a sloppy phrase clause, ten or more SHOULD
+    /// clauses, a phrase under MUST_NOT, a nested BooleanQuery, more than RGPU_MAX_BOOL_PHRASES phrases on a side, more than
+    /// RGPU_MAX_QUERY_TERMS clause terms. There is no masked form: a filtered tree of this kind stays the CPU's.
+    fn try_phrase_opt(&self, b: &BooleanQuery<C>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
+        let (must, should, filter, must_not, min_should_match) = b.clauses();
+        if (must.is_empty() && filter.is_empty()) || should.is_empty() || should.len() > 9 || min_should_match < 0 || min_should_match > 255
+            || self.leaves.iter().any(|l| !l.has_positions) {
+            return Ok(false);
+        }
+        let term_of = |q: &Box<dyn Query<C>>| q.as_any().downcast_ref::<TermQuery>().filter(|t| t.term.field == self.field);
+        // (the phrase, its slot on its side, scores?) - required ones first, then optional ones: the call's phrase order
+        let mut req_phrases: Vec<(&PhraseQuery, usize, bool)> = Vec::new();
+        let mut opt_phrases: Vec<(&PhraseQuery, usize, bool)> = Vec::new();
+        let mut required: Vec<(&TermQuery, bool)> = Vec::new();
+        let mut optional: Vec<(&TermQuery, bool)> = Vec::new();
+        let n_must = must.len();
+        let sides: [(Vec<&Box<dyn Query<C>>>, bool); 2] = [(must.iter().chain(filter.iter()).collect(), true), (should.iter().collect(), false)];
+        for (side, is_required) in sides.iter() {
+            for (slot, q) in side.iter().enumerate() {
+                let scoring = !*is_required || slot < n_must;
+                if let Some(p) = q.as_any().downcast_ref::<PhraseQuery>() {
+                    let (field, terms, positions, slop) = p.parts();
+                    if field != self.field || slop != 0 || terms.len() < 2 || terms.len() > RGPU_MAX_PHRASE_TERMS as usize || terms.len() != positions.len() {
+                        return Ok(false);
+                    }
+                    if *is_required { req_phrases.push((p, slot, scoring)); } else { opt_phrases.push((p, slot, scoring)); }
+                } else if let Some(t) = term_of(q) {
+                    if *is_required { required.push((t, scoring)); } else { optional.push((t, scoring)); }
+                } else {
+                    return Ok(false);
+                }
+            }
+        }
+        if req_phrases.len() > RGPU_MAX_BOOL_PHRASES as usize || opt_phrases.len() > RGPU_MAX_BOOL_PHRASES as usize { return Ok(false); }
+        let mut prohibited: Vec<&TermQuery> = Vec::with_capacity(must_not.len());
+        for q in must_not {
+            match term_of(q) { Some(t) => prohibited.push(t), None => return Ok(false) }
+        }
+        let phrases: Vec<&(&PhraseQuery, usize, bool)> = req_phrases.iter().chain(opt_phrases.iter()).collect();
+        let scored: Vec<&(&TermQuery, bool)> = required.iter().chain(optional.iter()).collect();
+        let n_phrase_terms: usize = phrases.iter().map(|(p, _, _)| p.parts().1.len()).sum();
+        if n_phrase_terms + scored.len() + prohibited.len() > RGPU_MAX_QUERY_TERMS as usize { return Ok(false); }
+        let mut phrase_weights = Vec::with_capacity(phrases.len());
+        for (p, _, scoring) in &phrases {
+            let term_refs: Vec<&Term> = p.parts().1.iter().collect();
+            let w = self.weight_of(&term_refs, 1.0)?;
+            phrase_weights.push((if *scoring { w.0 } else { 0.0 }, w.1)); // a FILTER phrase scores 0 (needs_scores = false)
+        }
+        let mut term_weights = Vec::with_capacity(scored.len());
+        for (t, scoring) in &scored {
+            let w = self.weight_of(&[&t.term], t.boost)?;
+            term_weights.push((if *scoring { w.0 } else { 0.0 }, w.1));
+        }
+        let mut oq = RgpuPhraseOptQuery { n_req_phrases: req_phrases.len() as i32, n_opt_phrases: opt_phrases.len() as i32, first_phrase: 0,
+                                          n_req_terms: required.len() as i32, n_opt_terms: optional.len() as i32, first_term: 0,
+                                          n_must_not: prohibited.len() as i32, min_should_match, req_phrase_slot: [0; 4], opt_phrase_slot: [0; 4] };
+        for (i, (_, slot, _)) in req_phrases.iter().enumerate() { oq.req_phrase_slot[i] = *slot as i32; }
+        for (i, (_, slot, _)) in opt_phrases.iter().enumerate() { oq.opt_phrase_slot[i] = *slot as i32; }
+        for leaf in self.cpu.reader().leaves() {
+            let mut pqs = Vec::with_capacity(phrases.len());
+            let mut pterms: Vec<RgpuPhraseTerm> = Vec::with_capacity(n_phrase_terms);
+            for (i, (p, _, _)) in phrases.iter().enumerate() {
+                let (_, terms, positions, _) = p.parts();
+                let mine = self.phrase_terms(&leaf, terms, positions)?;
+                pqs.push(RgpuPhraseQuery { n_terms: mine.len() as i32, first_term: pterms.len() as i32, weight: phrase_weights[i].0, sim_table: phrase_weights[i].1,
+                                           slop: 0, next_limit: 0 });
+                pterms.extend(mine);
+            }
+            let mut terms = Vec::with_capacity(scored.len() + prohibited.len());
+            for (i, (t, _)) in scored.iter().enumerate() {
+                terms.push(RgpuQueryTerm { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: term_weights[i].0, sim_table: term_weights[i].1 });
+            }
+            for t in &prohibited {
+                terms.push(RgpuQueryTerm { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: 0.0, sim_table: 0 }); // never scored
+            }
+            let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
+            let mut total: i64 = 0;
+            let seg = self.leaves[leaf.ord].seg;
+            let terms_ptr = if terms.is_empty() { std::ptr::null() } else { terms.as_ptr() };
+            check(unsafe {
+                rgpu_search_phrase_opt_batch(seg, &oq, 1, pqs.as_ptr(), pqs.len() as i32, pterms.as_ptr(), pterms.len() as i32,
+                                             terms_ptr, terms.len() as i32, k as i32, hits.as_mut_ptr(), &mut total)
             }, self.ctx)?;
             Self::hand_over(top, &hits, total);
         }
