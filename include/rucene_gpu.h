@@ -1179,6 +1179,58 @@ int32_t rgpu_search_fields_batch(rgpu_segment* seg, const rgpu_fields_query* que
                                  int32_t n_groups_total, const rgpu_field_clause* clauses, int32_t n_clauses_total, int32_t k,
                                  rgpu_hit* hits_out, int64_t* total_hits_out);
 
+/* ---- cross-field query-string trees: sum groups, MUST + SHOULD ------------------------------------------------------------ */
+/* What QueryStringQueryBuilder (search/query/query_string.rs) emits over two or more fields: every word becomes a nested all-SHOULD
+ * BooleanQuery with one TermQuery per field (build_field_query, :183-196), and the groups go under MUST or SHOULD by the `+` sign
+ * (parse_query, :60-177): "test +search" over title, content is
+ * BooleanQuery(must: [Bool(should: [title:search, content:search])], should: [Bool(should: [title:test, content:test])]).
+ * A call of its own, with its own group and query structs: rgpu_search_fields_batch keeps its contract. */
+#define RGPU_GROUP_SUM 2     /* nested all-SHOULD BooleanQuery of 1..RGPU_MAX_GROUP_DISJUNCTS TermQuery clauses, in any fields */
+typedef struct rgpu_field_tree_group {
+  int32_t first_term;        /* index of the group's first clause in `clauses` */
+  int32_t n_terms;
+  uint32_t tie_bits;         /* RGPU_GROUP_DISMAX: bit pattern of the f32 tie_breaker_multiplier (finite); else ignored */
+  int32_t kind;              /* RGPU_GROUP_TERM / RGPU_GROUP_DISMAX / RGPU_GROUP_SUM */
+  int32_t min_should_match;  /* RGPU_GROUP_SUM: the nested BooleanQuery's; 0 and 1 alike, 2 or more refused. Else 0 */
+  int32_t reserved;          /* 0 */
+} rgpu_field_tree_group;
+typedef struct rgpu_fields_tree_query {
+  int32_t first_group;       /* the query's groups in `groups`: n_must MUST groups first, then n_should SHOULD groups */
+  int32_t n_must;            /* 0..RGPU_MAX_FIELD_GROUPS */
+  int32_t n_should;          /* 0..RGPU_MAX_FIELD_GROUPS; n_must + n_should >= 1 */
+  int32_t min_should_match;  /* BooleanQuery::min_should_match (no effect beside MUST groups, below) */
+  int32_t first_must_not;    /* MUST_NOT TermQuery clauses of any field: a range of `clauses` (weight / sim_table unused) */
+  int32_t n_must_not;
+} rgpu_fields_tree_query;
+/* BooleanQuery over TermQuery, DisjunctionMaxQuery and nested should-only BooleanQuery clauses whose terms live in different fields
+ * of one segment, per leaf, by BooleanWeight::create_scorer (query/boolean_query.rs:200-273). Clauses, presence, live docs, rows,
+ * totals, doc_base and the implicit per-field preparation are rgpu_search_fields_batch's. 1 <= k <= 128. Blocking; rows are bit-equal
+ * to the reference.
+ *   SUM group   ONE DisjunctionSumScorer over the clauses present in the leaf, even when only one is left (boolean_query.rs:217-234):
+ *               its score on a doc is 0.0f + s_i .. over the present clauses that hold the doc, in clause order
+ *               (disjunction_scorer.rs:211-225), its cost the sum of their doc_freq (:39); no present clause: no scorer.
+ *   n_should = 0 or n_must = 0: exactly the MUST / SHOULD rules of rgpu_search_fields_batch, a SUM group's score and cost at its place.
+ *   both        ReqNotScorer(ReqOptScorer(must, should), must_not) (boolean_query.rs:253-262): a doc is a hit iff every MUST group holds
+ *               it, no present MUST_NOT clause holds it and it is live. req = the single MUST group's score as it is, or
+ *               ConjunctionScorer::score in the leaf's stable cost order; opt = 0.0f + g_i .. over the present SHOULD groups on the
+ *               doc, in clause order. The final score follows req_opt_scorer.rs:41-66 over the collected docs in doc order, the state
+ *               afresh in every leaf; rgpu_config.req_opt_rule = -1 adds opt everywhere instead (as for RGPU_OP_WITH_SHOULD).
+ *               min_should_match is accepted and has no effect (ReqOptScorer only advance()s the optional scorer). Every SHOULD group
+ *               absent from the leaf: the row is the MUST side's own. A MUST group absent: the query matches nothing there. A doc no
+ *               optional group holds scores req + 0.0f (the deviation documented for rgpu_search_phrase_opt_batch).
+ * Refused with RGPU_ERR_UNSUPPORTED, nothing launched and nothing written: more than RGPU_MAX_FIELD_GROUPS groups on a side or
+ * more than RGPU_MAX_GROUP_DISJUNCTS disjuncts; a SUM group with min_should_match >= 2 (the reference's advance() ignores it while
+ * next() honours it, disjunction_scorer.rs:295-376: which docs match would depend on whether the group leads the conjunction);
+ * MUST_NOT clauses beside min_should_match >= 2 in a query without MUST groups; more than RGPU_MAX_FIELDS_QUERY_CLAUSES clauses in a
+ * query; k > 128. FILTER clauses cannot be written.
+ * RGPU_ERR_ILLEGAL_ARGUMENT, likewise: what rgpu_search_fields_batch names (field slots, ties, ranges, counts, sim tables, one
+ * doc_start_fp under two fields - checked before anything is prepared), a group kind outside the three, a negative side count, a
+ * query with no group, a SUM group without a clause, a non-zero `reserved`, a non-zero
+ * min_should_match on a TERM or DISMAX group. There are no masked, sharded, planner, count or rescore forms. */
+int32_t rgpu_search_fields_tree_batch(rgpu_segment* seg, const rgpu_fields_tree_query* queries, int32_t n_queries,
+                                      const rgpu_field_tree_group* groups, int32_t n_groups_total, const rgpu_field_clause* clauses,
+                                      int32_t n_clauses_total, int32_t k, rgpu_hit* hits_out, int64_t* total_hits_out);
+
 /* ---- measurement ------------------------------------------------------------------------------------------ */
 typedef struct rgpu_kernel_stat {
   char name[48];

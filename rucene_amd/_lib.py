@@ -64,6 +64,13 @@ FIELDS_QUERY_DTYPE = np.dtype([("occur", "<i4"), ("first_group", "<i4"), ("n_gro
 SEGMENT_FIELD_INFO_DTYPE = np.dtype([("norms_bytes", "<i8"), ("norm_mode", "<i4"), ("n_norm_ranks", "<i4"), ("index_options", "<i4"), ("skip_values", "<i4")],
                                     align=True)
 assert FIELD_CLAUSE_DTYPE.itemsize == 48 and FIELD_GROUP_DTYPE.itemsize == 16 and FIELDS_QUERY_DTYPE.itemsize == 24 and SEGMENT_FIELD_INFO_DTYPE.itemsize == 24
+# rgpu_search_fields_tree_batch: sum groups (nested should-only BooleanQuery), MUST groups first, then SHOULD groups
+GROUP_SUM = 2                     # RGPU_GROUP_SUM
+FIELD_TREE_GROUP_DTYPE = np.dtype([("first_term", "<i4"), ("n_terms", "<i4"), ("tie_bits", "<u4"), ("kind", "<i4"), ("min_should_match", "<i4"),
+                                   ("reserved", "<i4")], align=True)
+FIELDS_TREE_QUERY_DTYPE = np.dtype([("first_group", "<i4"), ("n_must", "<i4"), ("n_should", "<i4"), ("min_should_match", "<i4"),
+                                    ("first_must_not", "<i4"), ("n_must_not", "<i4")], align=True)
+assert FIELD_TREE_GROUP_DTYPE.itemsize == 24 and FIELDS_TREE_QUERY_DTYPE.itemsize == 24
 NORM_MODE_NONE, NORM_MODE_RANK, NORM_MODE_RAW = 0, 1, 2   # rgpu_segment_field_info.norm_mode
 FIELD_STATS_DTYPE = np.dtype([("num_terms", "<i8"), ("sum_total_term_freq", "<i8"), ("sum_doc_freq", "<i8"), ("doc_count", "<i4"),
                               ("longs_size", "<i4")], align=True)
@@ -102,6 +109,7 @@ EXPORTS = [
     "rgpu_search_span_near_batch",
     "rgpu_search_span_unordered_batch",
     "rgpu_segment_attach_field", "rgpu_segment_prepare_field_terms", "rgpu_segment_get_field_info", "rgpu_search_fields_batch",
+    "rgpu_search_fields_tree_batch",
     "rgpu_points_attach", "rgpu_points_get_info", "rgpu_points_free", "rgpu_docset_from_point_ranges",
     "rgpu_plan_uniform_bytes", "rgpu_plan_batch_ids", "rgpu_plan_batch_bytes", "rgpu_planner_search_uniform_ids_device", "rgpu_planner_search_uniform_ids_sharded",
 ]
@@ -210,6 +218,7 @@ def lib():
         "rgpu_segment_prepare_field_terms": (i32, [vp, i32, vp, i64]),
         "rgpu_segment_get_field_info": (i32, [vp, i32, vp]),
         "rgpu_search_fields_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
+        "rgpu_search_fields_tree_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp]),
         "rgpu_search_batch_device": (i32, [vp, vp, i32, vp, i32, i32, vp, vp, vp]),
         "rgpu_merge_topk_device": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "rgpu_docset_from_words": (i32, [vp, vp, C.POINTER(vp)]),
@@ -995,6 +1004,18 @@ class Segment:
         totals = np.zeros(q.size, dtype=np.int64) if totals is None else totals
         _check(lib().rgpu_search_fields_batch(self._h, q.ctypes.data if q.size else None, q.size, g.ctypes.data if g.size else None, g.size,
                                               t.ctypes.data if t.size else None, t.size, k, hits.ctypes.data, totals.ctypes.data))
+        return hits, totals
+
+    def search_fields_tree_batch(self, queries, groups, clauses, k, hits=None, totals=None):
+        """rgpu_search_fields_tree_batch: BooleanQuery rows over TermQuery / DisjunctionMaxQuery / nested should-only BooleanQuery groups
+        under MUST and SHOULD. `hits` / `totals`: arrays to write into (tests: a refusal leaves them untouched)."""
+        q = np.ascontiguousarray(queries, dtype=FIELDS_TREE_QUERY_DTYPE)
+        g = np.ascontiguousarray(groups, dtype=FIELD_TREE_GROUP_DTYPE)
+        t = np.ascontiguousarray(clauses, dtype=FIELD_CLAUSE_DTYPE)
+        hits = np.zeros((q.size, max(k, 1)), dtype=HIT_DTYPE) if hits is None else hits
+        totals = np.zeros(q.size, dtype=np.int64) if totals is None else totals
+        _check(lib().rgpu_search_fields_tree_batch(self._h, q.ctypes.data if q.size else None, q.size, g.ctypes.data if g.size else None, g.size,
+                                                   t.ctypes.data if t.size else None, t.size, k, hits.ctypes.data, totals.ctypes.data))
         return hits, totals
 
     def release_prepared_terms(self):

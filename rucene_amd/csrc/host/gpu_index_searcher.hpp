@@ -161,16 +161,36 @@ struct DisjunctionMaxQuery : Query {
 // SHOULD (min_should_match counts groups) or all MUST, with MUST_NOT TermQuery clauses of any field. A BooleanQuery / DisjunctionMaxQuery
 // / TermQuery that names a further field is served the same way (GpuIndexSearcher::cross_spec). Ten or more groups or disjuncts are
 // UnsupportedOperation when searched: the reference sums those in heap order.
+// With GpuIndexSearcher::field_trees = true the trees QueryStringQueryBuilder builds over several fields are served too
+// (rgpu_search_fields_tree_batch): a group may be a SUM - a nested should-only BooleanQuery of TermQuery clauses, "(title:w body:w)" -
+// and MUST groups may stand beside SHOULD groups (must_should: ReqOptScorer, its sequential rule kept). Off by default: such a query
+// is UnsupportedOperation, as these trees have been.
 struct MultiFieldQuery : Query {
   struct Group {
     bool dismax = false;
     float tie_breaker_multiplier = 0.0f;
-    std::vector<TermQuery> terms;  // one TermQuery, or the disjuncts
+    std::vector<TermQuery> terms;  // one TermQuery, or the disjuncts, or the nested clauses
+    bool sum = false;              // a nested should-only BooleanQuery of `terms`
+    int32_t min_should_match = 0;  // ... and its min_should_match (0 and 1 are served)
   };
   std::vector<Group> groups;
   bool must = false;  // the groups are MUST clauses (else SHOULD)
   int32_t min_should_match = 0;
   std::vector<TermQuery> must_not_queries;
+  std::vector<Group> should_groups;  // must = true: SHOULD groups beside the MUST ones (the optional side of ReqOptScorer)
+  static Group sum_of(std::vector<TermQuery> clauses, int32_t min_should_match = 0) {
+    if (clauses.empty()) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "boolean query should at least contain one inner query!");
+    Group g;
+    g.sum = true;
+    g.min_should_match = min_should_match;
+    g.terms = std::move(clauses);
+    return g;
+  }
+  bool is_tree() const {
+    if (!should_groups.empty()) return true;
+    for (const Group& g : groups) if (g.sum) return true;
+    return false;
+  }
   static Group term(TermQuery t) { Group g; g.terms.push_back(std::move(t)); return g; }
   static Group dismax(std::vector<TermQuery> disjuncts, float tie) {
     if (disjuncts.empty()) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "DisjunctionMaxQuery: sub query should not be empty!");
@@ -190,6 +210,13 @@ struct MultiFieldQuery : Query {
   static std::unique_ptr<MultiFieldQuery> all_must(std::vector<Group> groups, std::vector<TermQuery> must_nots = {}) {
     std::unique_ptr<MultiFieldQuery> q = should(std::move(groups), 0, std::move(must_nots));
     q->must = true;
+    return q;
+  }
+  static std::unique_ptr<MultiFieldQuery> must_should(std::vector<Group> musts, std::vector<Group> shoulds, int32_t min_should_match = 0,
+                                                      std::vector<TermQuery> must_nots = {}) {
+    std::unique_ptr<MultiFieldQuery> q = all_must(std::move(musts), std::move(must_nots));
+    q->should_groups = std::move(shoulds);
+    q->min_should_match = min_should_match;  // (accepted, without effect: ReqOptScorer only advance()s the optional scorer)
     return q;
   }
 };
@@ -998,6 +1025,13 @@ class GpuIndexSearcher {
   // UnsupportedOperation. Refused either way: what PhraseOptionalQuery::check_served refuses, and such a row under a FilteredQuery
   // (the call has no masked form).
   bool optional_phrases = false;
+  // serve MultiFieldQuery trees with SUM groups and with SHOULD groups beside MUST groups through rgpu_search_fields_tree_batch (off by
+  // default: such rows are UnsupportedOperation, as they have been); rows rgpu_search_fields_batch can express keep going there.
+  // What it costs: every must_should query then takes ReqOptScorer's rule, where ONE wavefront walks the query's hits in doc order -
+  // about 7 ns per posting of the cheapest MUST group, tens of milliseconds for a `+word` that millions of docs hold (1024 such
+  // trees over 10 M docs: 1.3 s against 24 ms without the rule). rgpu_config.req_opt_rule = -1 adds the
+  // optional sums everywhere instead, in one pass (same docs and counts, scores >= the reference's).
+  bool field_trees = false;
   std::function<void(const Query&, TopDocsCollector&)> cpu_fallback;
 
   // ---- cached filters: doc sets in HBM as FILTER / MUST_NOT masks (include/rucene_gpu.h rgpu_docset_*) ---------------------------
@@ -1210,8 +1244,20 @@ class GpuIndexSearcher {
           std::vector<TopDocs> got = search_many(rest, k);
           for (size_t i = 0; i < rest_rows.size(); ++i) out[rest_rows[i]] = std::move(got[i]);
         }
-        std::vector<TopDocs> got = search_fields(specs, k);
-        for (size_t i = 0; i < cross_rows.size(); ++i) out[cross_rows[i]] = std::move(got[i]);
+        std::vector<MultiFieldQuery> flat, trees;
+        std::vector<size_t> flat_rows, tree_rows;
+        for (size_t i = 0; i < specs.size(); ++i) {
+          (specs[i].is_tree() ? trees : flat).push_back(specs[i]);
+          (specs[i].is_tree() ? tree_rows : flat_rows).push_back(cross_rows[i]);
+        }
+        if (!flat.empty()) {
+          std::vector<TopDocs> got = search_fields(flat, k);
+          for (size_t i = 0; i < flat_rows.size(); ++i) out[flat_rows[i]] = std::move(got[i]);
+        }
+        if (!trees.empty()) {
+          std::vector<TopDocs> got = search_fields_tree(trees, k);
+          for (size_t i = 0; i < tree_rows.size(); ++i) out[tree_rows[i]] = std::move(got[i]);
+        }
         return out;
       }
     }
@@ -1936,7 +1982,11 @@ class GpuIndexSearcher {
     } else {
       throw Error(RGPU_ERR_UNSUPPORTED, "query type not served across fields by the GPU path");
     }
+    if (m.is_tree() && !field_trees)
+      throw Error(RGPU_ERR_UNSUPPORTED, "nested should-only groups and MUST beside SHOULD groups are not served across fields by the GPU path (field_trees)");
+    if (!m.should_groups.empty() && !m.must) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "should_groups stand beside MUST groups");
     if (m.groups.empty()) throw Error(RGPU_ERR_UNSUPPORTED, "a query of MUST_NOT clauses alone is not served across fields by the GPU path");
+    if (m.should_groups.size() > static_cast<size_t>(RGPU_MAX_FIELD_GROUPS)) throw Error(RGPU_ERR_UNSUPPORTED, "ten or more clauses are summed in heap order by the reference");
     if (m.groups.size() > static_cast<size_t>(RGPU_MAX_FIELD_GROUPS)) throw Error(RGPU_ERR_UNSUPPORTED, "ten or more clauses are summed in heap order by the reference");
     if (!m.must && m.min_should_match >= 2 && !m.must_not_queries.empty())
       throw Error(RGPU_ERR_UNSUPPORTED, "MUST_NOT clauses beside min_should_match >= 2 are not served across fields by the GPU path");
@@ -1944,11 +1994,13 @@ class GpuIndexSearcher {
       if (primary(t)) return;
       for (const LeafReader& l : leaves_) if (!l.extra(t.field)) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "no field '" + t.field + "' among the leaves' extra_fields");
     };
-    for (const MultiFieldQuery::Group& g : m.groups) {
-      if (g.terms.size() > static_cast<size_t>(RGPU_MAX_GROUP_DISJUNCTS)) throw Error(RGPU_ERR_UNSUPPORTED, "ten or more disjuncts are summed in heap order by the reference");
-      if (g.dismax && !std::isfinite(g.tie_breaker_multiplier)) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "tie_breaker_multiplier is not finite");
-      for (const TermQuery& t : g.terms) known(t);
-    }
+    for (const auto* side : {&m.groups, &m.should_groups})
+      for (const MultiFieldQuery::Group& g : *side) {
+        if (g.terms.size() > static_cast<size_t>(RGPU_MAX_GROUP_DISJUNCTS)) throw Error(RGPU_ERR_UNSUPPORTED, "ten or more disjuncts are summed in heap order by the reference");
+        if (g.dismax && !std::isfinite(g.tie_breaker_multiplier)) throw Error(RGPU_ERR_ILLEGAL_ARGUMENT, "tie_breaker_multiplier is not finite");
+        if (g.sum && g.min_should_match >= 2) throw Error(RGPU_ERR_UNSUPPORTED, "a nested min_should_match >= 2 is not served across fields by the GPU path");
+        for (const TermQuery& t : g.terms) known(t);
+      }
     for (const TermQuery& t : m.must_not_queries) known(t);
     return m;
   }
@@ -2017,6 +2069,55 @@ class GpuIndexSearcher {
       leaf_totals[li].assign(static_cast<size_t>(nq), 0);
       check(rgpu_search_fields_batch(leaf.segment, qs.data(), nq, gs.data(), static_cast<int32_t>(gs.size()), cs.data(), static_cast<int32_t>(cs.size()),
                                      static_cast<int32_t>(k), leaf_hits[li].data(), leaf_totals[li].data()));
+    }
+    return merge_leaves(leaf_hits, leaf_totals, nq, k);
+  }
+  // field_trees: the rows with SUM groups or SHOULD groups beside MUST groups, through rgpu_search_fields_tree_batch per leaf
+  std::vector<TopDocs> search_fields_tree(const std::vector<MultiFieldQuery>& specs, size_t k) {
+    if (k > 128) throw Error(RGPU_ERR_UNSUPPORTED, "a cross-field query is served for k <= 128");
+    const int32_t nq = static_cast<int32_t>(specs.size());
+    std::vector<std::vector<rgpu_hit>> leaf_hits(leaves_.size());
+    std::vector<std::vector<int64_t>> leaf_totals(leaves_.size());
+    for (size_t li = 0; li < leaves_.size(); ++li) {
+      const LeafReader& leaf = leaves_[li];
+      std::vector<rgpu_fields_tree_query> qs;
+      std::vector<rgpu_field_tree_group> gs;
+      std::vector<rgpu_field_clause> cs;
+      auto clause = [&](const TermQuery& t, bool scored) {
+        rgpu_field_clause c{};
+        const ExtraField* x = primary(t) ? nullptr : leaf.extra(t.field);
+        const bool have = x ? x->term_state(t, &c.state) : leaf.term_state(t, &c.state);
+        if (!have) { c.state = rgpu_term_state{}; c.state.skip_offset = -1; c.state.singleton_doc_id = -1; }
+        if (scored) { auto w = field_weight_of(t); c.weight = w.first; c.sim_table = w.second; }
+        c.field = x ? x->slot : 0;
+        cs.push_back(c);
+      };
+      for (const MultiFieldQuery& m : specs) {
+        rgpu_fields_tree_query fq{};
+        fq.first_group = static_cast<int32_t>(gs.size());
+        fq.n_must = m.must ? static_cast<int32_t>(m.groups.size()) : 0;
+        fq.n_should = static_cast<int32_t>(m.must ? m.should_groups.size() : m.groups.size());
+        fq.min_should_match = m.min_should_match;
+        for (const auto* side : {&m.groups, &m.should_groups})
+          for (const MultiFieldQuery::Group& g : *side) {
+            rgpu_field_tree_group fg{};
+            fg.first_term = static_cast<int32_t>(cs.size());
+            fg.n_terms = static_cast<int32_t>(g.terms.size());
+            fg.kind = g.sum ? RGPU_GROUP_SUM : g.dismax ? RGPU_GROUP_DISMAX : RGPU_GROUP_TERM;
+            fg.min_should_match = g.sum ? g.min_should_match : 0;
+            std::memcpy(&fg.tie_bits, &g.tie_breaker_multiplier, sizeof fg.tie_bits);
+            for (const TermQuery& t : g.terms) clause(t, true);
+            gs.push_back(fg);
+          }
+        fq.first_must_not = static_cast<int32_t>(cs.size());
+        fq.n_must_not = static_cast<int32_t>(m.must_not_queries.size());
+        for (const TermQuery& t : m.must_not_queries) clause(t, false);
+        qs.push_back(fq);
+      }
+      leaf_hits[li].assign(static_cast<size_t>(nq) * k, rgpu_hit{-1, 0.f});
+      leaf_totals[li].assign(static_cast<size_t>(nq), 0);
+      check(rgpu_search_fields_tree_batch(leaf.segment, qs.data(), nq, gs.data(), static_cast<int32_t>(gs.size()), cs.data(), static_cast<int32_t>(cs.size()),
+                                          static_cast<int32_t>(k), leaf_hits[li].data(), leaf_totals[li].data()));
     }
     return merge_leaves(leaf_hits, leaf_totals, nq, k);
   }

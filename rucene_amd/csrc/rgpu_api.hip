@@ -3609,4 +3609,5 @@ extern "C" int32_t rgpu_search_batch_device(rgpu_segment* seg, const rgpu_query*
 #include "api/planner.hpp"         // rgpu_planner_create* / destroy / sim_table, rgpu_plan_batch_*, rgpu_plan_uniform_*
 #include "api/fused.hpp"           // term_batch_resident, term_batch_fast, search_uniform_locked, rgpu_planner_search_uniform_ids_device / _sharded
 #include "api/fields.hpp"          // rgpu_segment_attach_field / _prepare_field_terms / _get_field_info, rgpu_search_fields_batch
+#include "api/fields_tree.hpp"     // rgpu_search_fields_tree_batch
 #include "api/debug.hpp"           // rgpu_bm25_encode_norm; rgpu_debug_counters / rgpu_debug_trace of the variant builds

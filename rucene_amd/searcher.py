@@ -724,6 +724,116 @@ class BooleanQuery:
         return out
 
 
+class QueryStringQueryBuilder:
+    """search/query/query_string.rs:28-250 restated: `+` makes the next clause a MUST clause, `|` and a blank a SHOULD clause,
+    parentheses nest, "quoted terms", term^boost, and "a b"~n as one boosted PhraseQuery per field. Over one field a word is that
+    field's TermQuery; over several it is a nested should-only BooleanQuery with one TermQuery per field (build_field_query,
+    :183-196), boost = the field's boost times the word's. A level with one clause in all is that clause (:167-172). The reference's
+    quirks are kept: `boost` is unused, min_should_match is handed to EVERY nested build (:174, :193), the character behind a closing
+    quote is swallowed unless it is `^` or `~` (:90-100), a nested parse that fails is dropped silently (:73).
+    fields: [(name, boost)]; term(field name, text) -> what TermQuery takes as its term (default: the text's UTF-8 bytes; leaves
+    without a term dictionary are queried by term id)."""
+
+    def __init__(self, query_string, fields, min_should_match=0, boost=1.0, term=None):
+        self.query_string, self.fields = str(query_string), [(str(f), float(b)) for f, b in fields]
+        self.min_should_match, self.boost = int(min_should_match), float(boost)
+        self.term = term or (lambda field, text: text.encode("utf-8"))
+
+    def build(self):
+        return self._parse(iter(self.query_string), None)
+
+    def _parse(self, chars, end_char):
+        musts, shoulds = [], []
+        is_option = True
+
+        def push(q):
+            (shoulds if is_option else musts).append(q)
+        for ch in chars:
+            if ch == "+":
+                is_option = False
+            elif ch == "|":
+                is_option = True
+            elif ch == "(":
+                try:
+                    push(self._parse(chars, ")"))
+                except RgpuError:
+                    pass
+            elif ch == '"':
+                text = []
+                for c in chars:
+                    if c == '"':
+                        break
+                    text.append(c)
+                c = next(chars, None)
+                if c is not None and c in "^~":
+                    text.append(c)
+                    for c in chars:
+                        if c == " ":
+                            break
+                        text.append(c)
+                if text:
+                    push(self._field_query("".join(text)))
+                is_option = True
+            elif ch == " ":
+                is_option = True
+            elif ch == ")":
+                if end_char != ")":
+                    raise RgpuError(-2, "parenthesis not match!")
+                break
+            else:
+                text, done = [ch], False
+                for c in chars:
+                    if c == " ":
+                        break
+                    if c == ")":
+                        if end_char != ")":
+                            raise RgpuError(-2, "parenthesis not match!")
+                        done = True
+                        break
+                    text.append(c)
+                push(self._field_query("".join(text)))
+                is_option = True
+                if done:
+                    break
+        if len(musts) + len(shoulds) == 1:
+            return (musts or shoulds)[0]
+        if not musts and not shoulds:
+            raise RgpuError(-2, "empty query string!")
+        return BooleanQuery.build(musts, shoulds, [], [], self.min_should_match)
+
+    def _field_query(self, text):
+        queries = self._phrases(text) if "~" in text else self._terms(text)
+        return queries[0] if len(queries) == 1 else BooleanQuery.build([], queries, [], [], self.min_should_match)
+
+    def _terms(self, text):
+        boost = np.float32(1.0)
+        if "^" in text:
+            text, b = text.split("^", 1)
+            try:
+                boost = np.float32(b)
+            except ValueError:
+                raise RgpuError(-2, "invalid float literal")
+        if text.startswith('"'):
+            text = text[1:len(text) - 1]
+        return [TermQuery(self.term(f, text), float(np.float32(fb) * boost), field=f) for f, fb in self.fields]
+
+    def _phrases(self, text):
+        words, slop = text.split("~", 1)
+        try:
+            slop = int(slop)
+        except ValueError:
+            raise RgpuError(-2, "invalid digit found in string")
+        words = words.split()
+        if len(words) < 2:
+            raise RgpuError(-2, "phrase query terms size must not small than 2")
+        out = []
+        for f, fb in self.fields:
+            q = PhraseQuery([self.term(f, w) for w in words], None, fb, slop)
+            q.field = f
+            out.append(q)
+        return out
+
+
 class DisjunctionMaxQuery:
     """query/disjunction_max_query.rs:43-114: the union of the disjuncts' docs, each scored max + (sum - max) * tie_breaker_multiplier
     over the disjuncts that hold it (DisjunctionMaxScorer, scorer/disjunction_scorer.rs:106-185, 246-286). The GPU path serves
@@ -824,8 +934,19 @@ class GpuIndexSearcher:
     range_filter_capacity = 256   # memoised range filters kept from one search_batch to the next (range_filter); set per searcher
 
     def __init__(self, leaves, ctx=None, similarity=None, next_limit=None, flatten_nested=False, cpu_fallback=None, filtered_phrases=False,
-                 required_sets=False, unordered_spans=False, optional_phrases=False):
-        """optional_phrases: serve MUST / FILTER + SHOULD trees with exact phrases on either side - +a +b "a b" (the phrase boost),
+                 required_sets=False, unordered_spans=False, optional_phrases=False, field_trees=False):
+        """field_trees: serve the trees QueryStringQueryBuilder builds over several fields - every word a nested should-only
+        BooleanQuery with one TermQuery per field, those groups under MUST and SHOULD by the `+` sign ("gpu +search") - through
+        rgpu_search_fields_tree_batch (ReqOptScorer's sequential rule kept; off by default: such rows are UnsupportedOperation, as
+        they have been). Rows rgpu_search_fields_batch can express keep going there. Still refused with it on: a nested clause that
+        is not a should-only BooleanQuery of TermQuery clauses, a nested min_should_match >= 2, phrases, FILTER clauses, ten or more
+        groups on a side, k > 128.
+        What it costs: with the flag on EVERY `+a b` query string takes the rule's path, where ONE wavefront walks the query's hits in
+        doc order - about 7 ns per posting of the cheapest MUST group, so a `+word` that millions of docs hold costs tens of
+        milliseconds by itself and a batch of 1024 such trees over 10 M docs took 1.3 s against 24 ms without the rule (DESIGN.md
+        section 4.6). A context opened with req_opt_rule=-1 adds the optional sums everywhere instead, in one pass: same docs and
+        counts, scores >= the reference's. `a b` trees (no `+`) never take that path.
+        optional_phrases: serve MUST / FILTER + SHOULD trees with exact phrases on either side - +a +b "a b" (the phrase boost),
         +"a b" c, +"a b" +c "b c" d -n #f - through rgpu_search_phrase_opt_batch (ReqOptScorer over the phrase scorers, its
         sequential rule kept; off by default: such rows are UnsupportedOperation, as they have been). Still refused with it on:
         whatever phrase_opt_parts refuses (nested clauses beside a phrase, a phrase under MUST_NOT, sloppy clauses, ten or more
@@ -854,6 +975,7 @@ class GpuIndexSearcher:
         self.required_sets = bool(required_sets)
         self.unordered_spans = bool(unordered_spans)
         self.optional_phrases = bool(optional_phrases)
+        self.field_trees = bool(field_trees)
         self.cpu_fallback = cpu_fallback
         self.leaves = list(leaves)
         # DefaultIndexSearcher::new(reader, next_limit: Option<usize>) (searcher.rs:291-296, :361): how many approximations of a
@@ -922,6 +1044,8 @@ class GpuIndexSearcher:
         """Does some TermQuery of the tree name a field other than the leaves' primary one?"""
         if isinstance(query, TermQuery):
             return not self._primary(query)
+        if isinstance(query, PhraseQuery):   # (QueryStringQueryBuilder's phrases carry their field; no cross-field call takes one)
+            return getattr(query, "field", None) is not None and query.field != self.leaves[0].field
         if isinstance(query, DisjunctionMaxQuery):
             return any(self._names_other_field(q) for q in query.disjuncts)
         if isinstance(query, BooleanQuery):
@@ -983,6 +1107,9 @@ class GpuIndexSearcher:
             raise RgpuError(-5, "query type not served across fields by the GPU path: %r" % (query,))
         if query.filter_queries:
             raise RgpuError(-5, "FILTER clauses are not served across fields by the GPU path")
+        if getattr(self, "field_trees", False) and ((query.must_queries and query.should_queries) or
+                                                    any(isinstance(q, BooleanQuery) for q in list(query.must_queries) + list(query.should_queries))):
+            return self._tree_spec(query, group)
         if query.must_queries and query.should_queries:
             raise RgpuError(-5, "MUST and SHOULD clauses in one cross-field query (ReqOptScorer) are not served by the GPU path")
         if not all(isinstance(q, TermQuery) for q in query.must_not_queries):
@@ -1000,6 +1127,63 @@ class GpuIndexSearcher:
         if sum(len(g[2]) for g in groups) + len(query.must_not_queries) > _lib.MAX_FIELDS_QUERY_CLAUSES:
             raise RgpuError(-5, "too many clauses in one cross-field query")
         return known((occur, groups, msm, list(query.must_not_queries)))
+
+    def _tree_spec(self, query, flat_group):
+        """field_trees: a BooleanQuery with nested should-only BooleanQuery-of-TermQuery clauses and / or MUST beside SHOULD clauses ->
+        ("tree", [MUST groups], [SHOULD groups], msm, [MUST_NOT TermQuery]), a group (kind, tie bits, [TermQuery], nested msm); what
+        rgpu_search_fields_tree_batch cannot express is UnsupportedOperation"""
+        def group(q):
+            if not isinstance(q, BooleanQuery):
+                return flat_group(q) + (0,)
+            if (q.must_queries or q.must_not_queries or q.filter_queries or not q.should_queries
+                    or not all(isinstance(t, TermQuery) for t in q.should_queries)):
+                raise RgpuError(-5, "a nested clause of a cross-field tree is a should-only BooleanQuery of TermQuery clauses")
+            if q.min_should_match >= 2:
+                raise RgpuError(-5, "a nested min_should_match >= 2 is not served across fields by the GPU path")
+            if len(q.should_queries) > _lib.MAX_GROUP_DISJUNCTS:
+                raise RgpuError(-5, "ten or more disjuncts are summed in heap order by the reference")
+            return (_lib.GROUP_SUM, 0, list(q.should_queries), int(q.min_should_match))
+        if not all(isinstance(q, TermQuery) for q in query.must_not_queries):
+            raise RgpuError(-5, "a cross-field query's MUST_NOT clauses are TermQuerys")
+        if len(query.must_queries) > _lib.MAX_FIELD_GROUPS or len(query.should_queries) > _lib.MAX_FIELD_GROUPS:
+            raise RgpuError(-5, "ten or more clauses on a side are summed in heap order by the reference")
+        msm = int(query.min_should_match)
+        if not query.must_queries and msm >= 2 and query.must_not_queries:
+            raise RgpuError(-5, "MUST_NOT clauses beside min_should_match >= 2 are not served across fields by the GPU path")
+        musts, shoulds = [group(q) for q in query.must_queries], [group(q) for q in query.should_queries]
+        if sum(len(g[2]) for g in musts + shoulds) + len(query.must_not_queries) > _lib.MAX_FIELDS_QUERY_CLAUSES:
+            raise RgpuError(-5, "too many clauses in one cross-field query")
+        for tq in [t for g in musts + shoulds for t in g[2]] + list(query.must_not_queries):
+            if not self._primary(tq) and any(tq.field not in leaf.extra_fields for leaf in self.leaves):
+                raise RgpuError(-2, "no field %r among the leaves' extra_fields" % tq.field)
+        return ("tree", musts, shoulds, msm, list(query.must_not_queries))
+
+    def pack_fields_tree(self, specs, leaf):
+        """_tree_spec rows -> (rgpu_fields_tree_query[], rgpu_field_tree_group[], rgpu_field_clause[]) for one leaf"""
+        Q, G, C = [], [], []
+
+        def clause(tq, scored=True):
+            row = np.zeros(1, _lib.FIELD_CLAUSE_DTYPE)[0]
+            xf = None if self._primary(tq) else leaf.extra_fields[tq.field]
+            st = leaf.term_state(tq.term) if xf is None else xf.term_state(tq.term)
+            if st is not None:
+                row["state"] = st
+            if scored:
+                row["weight"], row["sim_table"] = self._field_weight(tq)
+            row["field"] = 0 if xf is None else xf.slot
+            C.append(row)
+        for _, musts, shoulds, msm, nots in specs:
+            g0 = len(G)
+            for kind, tie_bits, tqs, gmsm in musts + shoulds:
+                c0 = len(C)
+                for tq in tqs:
+                    clause(tq)
+                G.append((c0, len(tqs), tie_bits, kind, gmsm, 0))
+            n0 = len(C)
+            for tq in nots:
+                clause(tq, scored=False)
+            Q.append((g0, len(musts), len(shoulds), msm, n0, len(nots)))
+        return np.array(Q, _lib.FIELDS_TREE_QUERY_DTYPE), np.array(G, _lib.FIELD_TREE_GROUP_DTYPE), np.array(C, _lib.FIELD_CLAUSE_DTYPE)
 
     def pack_fields(self, specs, leaf):
         """_cross_spec rows -> (rgpu_fields_query[], rgpu_field_group[], rgpu_field_clause[]) for one leaf"""
@@ -1032,6 +1216,16 @@ class GpuIndexSearcher:
         """(hits, totals) of _cross_spec rows (rows that name a further field), merged over the leaves"""
         if k > 128:
             raise RgpuError(-5, "a cross-field query is served for k <= 128")
+        trees = [i for i, s in enumerate(specs) if s[0] == "tree"]   # field_trees: the rows rgpu_search_fields_batch cannot express
+        if trees:
+            flat = [i for i in range(len(specs)) if specs[i][0] != "tree"]
+            hits, totals = np.zeros((len(specs), k), dtype=_lib.HIT_DTYPE), np.zeros(len(specs), dtype=np.int64)
+            if flat:
+                hits[flat], totals[flat] = self._cross_rows([specs[i] for i in flat], k)
+            tree_specs = [specs[i] for i in trees]
+            per_leaf = [leaf.segment.search_fields_tree_batch(*self.pack_fields_tree(tree_specs, leaf), k) for leaf in self.leaves]
+            hits[trees], totals[trees] = per_leaf[0] if len(per_leaf) == 1 else self._merge_leaves(per_leaf, len(tree_specs), k)
+            return hits, totals
         per_leaf = [leaf.segment.search_fields_batch(*self.pack_fields(specs, leaf), k) for leaf in self.leaves]
         return per_leaf[0] if len(per_leaf) == 1 else self._merge_leaves(per_leaf, len(specs), k)
 

@@ -131,18 +131,29 @@ impl<'q> FlatQuery<'q> {
     }
 }
 
-/// One group of a cross-field query (rgpu_field_group): a TermQuery, or a DisjunctionMaxQuery of TermQuery disjuncts in any fields
+/// One group of a cross-field query (rgpu_field_group / rgpu_field_tree_group): a TermQuery, a DisjunctionMaxQuery of TermQuery
+/// disjuncts in any fields or - `field_trees` - a nested should-only BooleanQuery of TermQuery clauses (`sum`, with its own
+/// min_should_match `sum_msm`): what QueryStringQueryBuilder builds per word over several fields
 struct CrossGroup<'q> {
     dismax: bool,
     tie: f32,
     terms: Vec<&'q TermQuery>,
+    sum: bool,
+    sum_msm: i32,
 }
-/// A BooleanQuery of all-SHOULD or all-MUST groups whose terms live in the uploaded field or in attached ones (rgpu_fields_query)
+/// A BooleanQuery of all-SHOULD or all-MUST groups whose terms live in the uploaded field or in attached ones (rgpu_fields_query);
+/// `field_trees`: `should_groups` beside MUST groups (ReqOptScorer) and sum groups (rgpu_fields_tree_query)
 struct CrossQuery<'q> {
     must: bool,
     msm: i32,
     groups: Vec<CrossGroup<'q>>,
+    should_groups: Vec<CrossGroup<'q>>,
     must_not: Vec<&'q TermQuery>,
+}
+
+impl<'q> CrossQuery<'q> {
+    /// a tree rgpu_search_fields_batch cannot express: rgpu_search_fields_tree_batch's
+    fn is_tree(&self) -> bool { !self.should_groups.is_empty() || self.groups.iter().any(|g| g.sum) }
 }
 
 pub struct GpuIndexSearcher<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: SimilarityProducer<C>> {
@@ -180,6 +191,15 @@ pub struct GpuIndexSearcher<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: De
     /// `optional_phrases` of the Python and C++ mirrors. The CPU's either way: a sloppy clause, a nested clause, a phrase under
     /// MUST_NOT, ten or more SHOULD clauses, more than RGPU_MAX_BOOL_PHRASES phrases on a side, and such a tree beside doc-set clauses.
     pub optional_phrases: bool,
+    /// try_gpu serves the trees QueryStringQueryBuilder builds over several fields - every word a nested should-only BooleanQuery
+    /// with one TermQuery per field, those groups under MUST and SHOULD by the `+` sign: "gpu +search" - through
+    /// rgpu_search_fields_tree_batch (try_fields_tree: ReqOptScorer's sequential rule kept, bit-exact) instead of leaving them to the
+    /// CPU searcher. Off by default, as `field_trees` of the Python and C++ mirrors; trees rgpu_search_fields_batch can express keep
+    /// going to try_fields. Under the rule a query's hits are walked by ONE wavefront, about 7 ns per posting of its cheapest MUST
+    /// group: a `+word` that millions of docs hold costs tens of milliseconds (rgpu_config.req_opt_rule = -1 adds the optional sums
+    /// everywhere instead, in one pass). The CPU's either way: a nested clause that is not a should-only BooleanQuery of TermQuery
+    /// clauses, a nested min_should_match >= 2, phrases, FILTER clauses, ten or more groups on a side, k > 128.
+    pub field_trees: bool,
 }
 
 unsafe impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: SimilarityProducer<C>> Send for GpuIndexSearcher<C, R, IR, SP> {}
@@ -213,7 +233,7 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             leaves.push(GpuLeaf { seg, has_positions: pos.is_some() });
         }
         let next_limit = match next_limit { None => 0, Some(0) => RGPU_NEXT_LIMIT_ZERO, Some(n) => n.min(i32::max_value() as usize) as i32 };
-        Ok(GpuIndexSearcher { cpu, ctx, field: field.to_string(), leaves, extra_fields: Vec::new(), sim_tables: Mutex::new(HashMap::new()), next_limit, allow_flatten, filtered_phrases: false, required_sets: false, unordered_spans: false, optional_phrases: false })
+        Ok(GpuIndexSearcher { cpu, ctx, field: field.to_string(), leaves, extra_fields: Vec::new(), sim_tables: Mutex::new(HashMap::new()), next_limit, allow_flatten, filtered_phrases: false, required_sets: false, unordered_spans: false, optional_phrases: false, field_trees: false })
     }
 
     /// A further indexed field of the same segments (rgpu_segment_attach_field): `norms(leaf)` hands over the field's norms as one
@@ -245,12 +265,26 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
     /// disjuncts, a BooleanQuery of 1..=9 such clauses that are all MUST or all SHOULD, with MUST_NOT TermQuery clauses. None = not
     /// this call's: a tree over the uploaded field alone goes the way it went (flatten), FILTER clauses, MUST beside SHOULD
     /// (ReqOptScorer), ten or more groups or disjuncts (the heap-order arm), MUST_NOT beside min_should_match >= 2 and a field that
-    /// is not attached stay the CPU searcher's.
+    /// is not attached stay the CPU searcher's. With `field_trees` a clause may also be a nested should-only BooleanQuery of 1..=9
+    /// TermQuery clauses (min_should_match <= 1) and MUST clauses may stand beside SHOULD clauses, up to nine on a side.
     fn cross_spec<'q>(&self, query: &'q dyn Query<C>) -> Option<CrossQuery<'q>> {
         let known = |t: &TermQuery| self.slot_of(&t.term.field, 0).is_some();
         let group = |q: &'q dyn Query<C>| -> Option<CrossGroup<'q>> {
             if let Some(t) = q.as_any().downcast_ref::<TermQuery>() {
-                return if known(t) { Some(CrossGroup { dismax: false, tie: 0.0, terms: vec![t] }) } else { None };
+                return if known(t) { Some(CrossGroup { dismax: false, tie: 0.0, terms: vec![t], sum: false, sum_msm: 0 }) } else { None };
+            }
+            if let Some(n) = q.as_any().downcast_ref::<BooleanQuery<C>>() {   // (title:w body:w)
+                if !self.field_trees { return None; }
+                let (must, should, filter, must_not, msm) = n.clauses();
+                if !must.is_empty() || !filter.is_empty() || !must_not.is_empty() || should.is_empty() { return None; }
+                if should.len() > RGPU_MAX_GROUP_DISJUNCTS as usize || msm >= 2 { return None; }
+                let mut terms = Vec::with_capacity(should.len());
+                for c in should {
+                    let t = c.as_any().downcast_ref::<TermQuery>()?;
+                    if !known(t) { return None; }
+                    terms.push(t);
+                }
+                return Some(CrossGroup { dismax: false, tie: 0.0, terms, sum: true, sum_msm: msm.max(0) });
             }
             let d = q.as_any().downcast_ref::<DisjunctionMaxQuery<C>>()?;
             if d.disjuncts.is_empty() || d.disjuncts.len() > RGPU_MAX_GROUP_DISJUNCTS as usize || !d.tie_breaker_multiplier.is_finite() { return None; }
@@ -260,15 +294,18 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
                 if !known(t) { return None; }
                 terms.push(t);
             }
-            Some(CrossGroup { dismax: true, tie: d.tie_breaker_multiplier, terms })
+            Some(CrossGroup { dismax: true, tie: d.tie_breaker_multiplier, terms, sum: false, sum_msm: 0 })
         };
         let spec = if let Some(b) = query.as_any().downcast_ref::<BooleanQuery<C>>() {
             let (must, should, filter, must_not, msm) = b.clauses();
-            if !filter.is_empty() || (!must.is_empty() && !should.is_empty()) || (must.is_empty() && should.is_empty()) { return None; }
+            let both = !must.is_empty() && !should.is_empty();
+            if !filter.is_empty() || (both && !self.field_trees) || (must.is_empty() && should.is_empty()) { return None; }
             let positive = if must.is_empty() { should } else { must };
-            if positive.len() > RGPU_MAX_FIELD_GROUPS as usize { return None; }
+            if positive.len() > RGPU_MAX_FIELD_GROUPS as usize || (both && should.len() > RGPU_MAX_FIELD_GROUPS as usize) { return None; }
             let mut groups = Vec::with_capacity(positive.len());
             for q in positive { groups.push(group(q.as_ref())?); }
+            let mut should_groups = Vec::new();
+            if both { for q in should { should_groups.push(group(q.as_ref())?); } }
             let mut prohibited = Vec::with_capacity(must_not.len());
             for q in must_not {
                 let t = q.as_any().downcast_ref::<TermQuery>()?;
@@ -276,14 +313,15 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
                 prohibited.push(t);
             }
             if must.is_empty() && msm >= 2 && !prohibited.is_empty() { return None; }
-            CrossQuery { must: !must.is_empty(), msm: if must.is_empty() { msm } else { 0 }, groups, must_not: prohibited }
+            CrossQuery { must: !must.is_empty(), msm: if must.is_empty() { msm } else { 0 }, groups, should_groups, must_not: prohibited }
         } else {
-            CrossQuery { must: false, msm: 0, groups: vec![group(query)?], must_not: vec![] }
+            CrossQuery { must: false, msm: 0, groups: vec![group(query)?], should_groups: vec![], must_not: vec![] }
         };
-        let n: usize = spec.groups.iter().map(|g| g.terms.len()).sum::<usize>() + spec.must_not.len();
+        let n: usize = spec.groups.iter().chain(spec.should_groups.iter()).map(|g| g.terms.len()).sum::<usize>() + spec.must_not.len();
         if n > RGPU_MAX_FIELDS_QUERY_CLAUSES as usize { return None; }
         // a tree over the uploaded field alone is flatten's, as it has been
-        let other = spec.groups.iter().flat_map(|g| g.terms.iter()).chain(spec.must_not.iter()).any(|t| t.term.field != self.field);
+        let other = spec.groups.iter().chain(spec.should_groups.iter()).flat_map(|g| g.terms.iter()).chain(spec.must_not.iter())
+            .any(|t| t.term.field != self.field);
         if other { Some(spec) } else { None }
     }
 
@@ -331,6 +369,46 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             let mut total: i64 = 0;
             check(unsafe { rgpu_search_fields_batch(self.leaves[leaf.ord].seg, &q, 1, groups.as_ptr(), groups.len() as i32, clauses.as_ptr(), clauses.len() as i32,
                                                     k as i32, hits.as_mut_ptr(), &mut total) }, self.ctx)?;
+            Self::hand_over(top, &hits, total);
+        }
+        Ok(true)
+    }
+
+    /// A cross-field tree with sum groups and / or SHOULD groups beside MUST groups (`field_trees`) through
+    /// rgpu_search_fields_tree_batch, one call per leaf, as try_fields: the MUST groups first, then the SHOULD groups; the library
+    /// sums the MUST side in the leaf's stable cost order, the SHOULD side in clause order, and applies ReqOptScorer's rule per leaf -
+    /// bit-equal rows. k above 128 stays the CPU searcher's.
+    fn try_fields_tree(&self, spec: &CrossQuery<'_>, top: &mut TopDocsCollector, k: usize) -> Result<bool> {
+        if k > 128 { return Ok(false); }
+        let mut weights = Vec::new();
+        for g in spec.groups.iter().chain(spec.should_groups.iter()) { for t in &g.terms { weights.push(self.field_weight_of(&t.term, t.boost)?); } }
+        for leaf in self.cpu.reader().leaves() {
+            let mut clauses: Vec<RgpuFieldClause> = Vec::with_capacity(weights.len() + spec.must_not.len());
+            let mut groups: Vec<RgpuFieldTreeGroup> = Vec::with_capacity(spec.groups.len() + spec.should_groups.len());
+            let mut at = 0usize;
+            for g in spec.groups.iter().chain(spec.should_groups.iter()) {
+                groups.push(RgpuFieldTreeGroup { first_term: clauses.len() as i32, n_terms: g.terms.len() as i32, tie_bits: g.tie.to_bits(),
+                                                 kind: if g.sum { RGPU_GROUP_SUM } else if g.dismax { RGPU_GROUP_DISMAX } else { RGPU_GROUP_TERM },
+                                                 min_should_match: if g.sum { g.sum_msm } else { 0 }, reserved: 0 });
+                for t in &g.terms {
+                    let slot = self.slot_of(&t.term.field, leaf.ord).unwrap_or(0);
+                    clauses.push(RgpuFieldClause { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: weights[at].0, sim_table: weights[at].1,
+                                                   field: slot, reserved: 0 });
+                    at += 1;
+                }
+            }
+            let first_must_not = clauses.len() as i32;
+            for t in &spec.must_not {
+                let slot = self.slot_of(&t.term.field, leaf.ord).unwrap_or(0);
+                clauses.push(RgpuFieldClause { state: Self::term_state(&self.block_state(&leaf, &t.term)?), weight: 0.0, sim_table: 0, field: slot, reserved: 0 });
+            }
+            let (n_must, n_should) = if spec.must { (spec.groups.len(), spec.should_groups.len()) } else { (0, spec.groups.len()) };
+            let q = RgpuFieldsTreeQuery { first_group: 0, n_must: n_must as i32, n_should: n_should as i32, min_should_match: spec.msm, first_must_not,
+                                          n_must_not: spec.must_not.len() as i32 };
+            let mut hits = vec![RgpuHit { doc: -1, score: 0.0 }; k];
+            let mut total: i64 = 0;
+            check(unsafe { rgpu_search_fields_tree_batch(self.leaves[leaf.ord].seg, &q, 1, groups.as_ptr(), groups.len() as i32, clauses.as_ptr(),
+                                                         clauses.len() as i32, k as i32, hits.as_mut_ptr(), &mut total) }, self.ctx)?;
             Self::hand_over(top, &hits, total);
         }
         Ok(true)
@@ -569,7 +647,9 @@ impl<C: Codec, R: IndexReader<Codec = C> + ?Sized, IR: Deref<Target = R>, SP: Si
             }
         }
         if !self.extra_fields.is_empty() {   // a tree that names an attached field: rgpu_search_fields_batch
-            if let Some(spec) = self.cross_spec(query) { return self.try_fields(&spec, top, k); }
+            if let Some(spec) = self.cross_spec(query) {
+                return if spec.is_tree() { self.try_fields_tree(&spec, top, k) } else { self.try_fields(&spec, top, k) };   // (a tree only with field_trees)
+            }
         }
         let flat = match self.flatten(query) { Some(f) => f, None => return Ok(false) };
         let n = flat.n_clauses();
